@@ -12,10 +12,13 @@ barrier + synchronize on both sides, MAX over ranks.  `python bench.py --gpus N`
 (re-executes under torch.distributed.run on 127.0.0.1); started under torch.distributed.run it uses the ranks it is
 given.
 
-The timed region (EXACTLY --steps steps between barrier + synchronize) is repeated --repeats times; `value` is the
-MEDIAN repeat, all repeats are listed under "repeats".  Steps are issued round-robin on --streams HIP streams (default 2:
-two batch-1 volumes in flight per GPU; every step is still one complete pass over one volume; `ms_per_step` is
+The timed region (EXACTLY --steps steps between barrier + synchronize) is repeated --repeats times (default 1, so that
+--steps is the number of timed steps); `value` is the MEDIAN repeat, all repeats are listed under "repeats".  Steps are
+issued round-robin on --streams HIP streams (default 2: two batch-1 volumes in flight per GPU; every step is still one complete pass over one volume; `ms_per_step` is
 elapsed / steps, i.e. the reciprocal of the throughput, and `ms_per_step_one_stream` the latency of one volume alone).
+
+--dump-outputs DIR writes what the last timed step computed (inputs_embeds, float32) to DIR/*.npy: weights and inputs
+come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline            -- the dominant kernel class (bf16 MFMA GEMM): algorithmic FLOPs of its launches in one step /
@@ -471,12 +474,36 @@ def timed_repeats(step, steps, warmup, repeats, sync, reduce_max):
     return times, out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, out, rank, world):
+    """--dump-outputs: the last timed step's inputs_embeds (B, S, E) as float32.  Rank r > 0 writes inputs_embeds_rank<r>;
+    every rank stays within DUMP_BYTES / world.  A larger output is sampled by whole rows (of the flattened (B * S, E)),
+    chosen by a fixed seed, and the row indices go beside it as <name>_rows.npy."""
+    import numpy as np
+
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "inputs_embeds" if rank == 0 else f"inputs_embeds_rank{rank}"
+    a = out.detach().float().cpu()  # out was produced on a side stream: the caller has synchronised the device
+    budget = DUMP_BYTES // max(1, world)
+    if a.numel() * 4 > budget:
+        rows = a.reshape(-1, a.shape[-1])
+        n = max(1, budget // (4 * rows.shape[1]) - 1)  # (one row's worth left for the index file)
+        idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+        a = rows[idx]
+        np.save(d / f"{name}_rows.npy", idx.numpy().astype(np.float64))
+    np.save(d / f"{name}.npy", a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = median")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of --steps steps each; value = median (1: --steps is the number of timed steps)")
     ap.add_argument("--hidden", type=int, default=4096, help="LLM hidden size E (4096 = Qwen3-8B, 2048 = Qwen3-1.7B)")
     ap.add_argument("--batch", type=int, default=1, help="volumes per step per GPU")
     ap.add_argument("--streams", type=int, default=2,
@@ -493,6 +520,10 @@ def main():
                     help="TEST PLUMBING ONLY (tests/test_bench_launcher.py): replace the step by a host no-op and use the "
                          "gloo backend, so that the launcher / barrier / MAX-over-ranks / JSON path can run on a box "
                          "without GPUs.  The line it prints is marked invalid.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the spliced inputs_embeds a caller "
+                         "of the path receives) as DIR/<name>.npy in float32 (at most 64 MB in all; a seeded row sample "
+                         "beyond that), so that two builds can be compared output for output on identical inputs")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -565,6 +596,8 @@ def main():
     if not args.stub_cpu:
         assert out.shape == (B, S, E) and bool(torch.isfinite(out.float()).all())
     elapsed = statistics.median(times)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     # the same K steps issued on ONE stream (one volume in flight): the latency of a volume
     single = None

@@ -45,3 +45,31 @@ def test_single_rank_stub():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and "roofline" not in j and "cpu_baseline" not in j
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "0", "--stub-cpu",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    j = _line(r.stdout)
+    assert j["steps"] == 2 and j["repeats"]["n"] == 1 and len(j["repeats"]["ms_per_step_each"]) == 1
+    import numpy as np
+    a = np.load(tmp_path / "out" / "inputs_embeds.npy")
+    assert a.dtype == np.float32 and a.shape == (8,)
+
+
+def test_dump_outputs_samples_rows_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    out = torch.arange(4 * 1024 * 4096, dtype=torch.float32).reshape(4, 1024, 4096).to(torch.bfloat16)
+    bench.dump_outputs(tmp_path, out, rank=1, world=2)
+    a = np.load(tmp_path / "inputs_embeds_rank1.npy")
+    rows = np.load(tmp_path / "inputs_embeds_rank1_rows.npy")
+    assert a.dtype == np.float32 and rows.dtype == np.float64
+    assert a.nbytes + rows.nbytes <= bench.DUMP_BYTES // 2 and a.shape[1] == 4096 and len(rows) == a.shape[0] > 1000
+    assert np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(a, out.reshape(-1, 4096)[torch.from_numpy(rows).long()].float().numpy())
+    bench.dump_outputs(tmp_path / "again", out, rank=1, world=2)  # the sample is fixed: the same rows every time
+    assert np.array_equal(np.load(tmp_path / "again" / "inputs_embeds_rank1_rows.npy"), rows)
