@@ -58,11 +58,10 @@ u2tok_ctx_t u2tok_ctx_get_current(void);     /* NULL when the thread uses the de
 /* Tuning / diagnostics switches of the calling thread's current context; U2TOK_ERR_ARG if unknown / out of range:
     "gemm_tile" {0 heuristic, 64, 128: tile of the small-tile kernel}, "gemm_splitk" {-1 never, 0 heuristic, 2..16 force
     that many K slices where scratch allows}, "gemm_big" {-1 never, 0 heuristic; force a form of the big-tile kernel: 20 / 21 =
-    256x256 / 256x192 tiles with two LDS stages, 22 = 256x128 ring (three stages), 23 / 24 = 256x192 with three stages for A /
-    for B, 25 / 26 = the same at 256x256}, "gemm_big_grid" {persistent workgroups}, "gemm_big_gelu" {1: GELU products may take
-    the big-tile kernel, 0: never}, "gemm_big_ring" / "gemm_big_deep" {1: the heuristic may pick the ring / launches the deep
-    forms, 0: two-stage forms only}, "gemm_big_splitk" {K slices of a FORCED big-tile launch}, "gemm_big_skinny" {1: partial-round
-    products may take the big-tile kernel with K slices}, "kmajor_b" {1: P V and the DiffTS aggregation read V / X in place as
+    256x256 / 256x192 tiles with two LDS stages, 22 = 256x128 ring (three stages), 24 / 26 = 256x192 / 256x256 with three stages
+    for B, 27 = the drain form of 24}, "gemm_big_grid" {persistent workgroups}, "gemm_big_splitk" {K slices of a FORCED big-tile
+    launch}, "gemm_big_drain" {1: the heuristic may pick the drain form, 0: never}, "gemm_skinny" {2: 64 < M <= 256 rows against
+    2048 .. 4096 columns take the unsplit skinny kernel, 1: its FLAT-encoded form, 0: never}, "kmajor_b" {1: P V and the DiffTS aggregation read V / X in place as
     K-major operands, 0: through transposed copies}, "gemm_tail_fused" {1: <= 16 rows behind a multiple of 256 rows (the ViT's cls
     rows) are computed inside the big-tile launch by the few-rows kernel's arithmetic, 0: a few-rows launch of their own},
     "flash_mode" {0 pick, 1 plain 128-row units, 7 double pipeline (generated asm KV loop)}, "flash_q_prescaled" {1: the q handed to

@@ -17,8 +17,6 @@ if "--big" in sys.argv:                      # force a big-tile variant (gemm_bi
     ops.set_option("gemm_big", int(sys.argv[sys.argv.index("--big") + 1]))
     tag += " big=" + sys.argv[sys.argv.index("--big") + 1]
 GELU = "--gelu" in sys.argv                   # only the ViT's fc1 + bias + erf-GELU product
-if GELU:
-    ops.set_option("gemm_big_gelu", 1)
 for (M, N, K, res) in ([(16384, 3072, 768, False)] if GELU else
                        [(16384, 2304, 768, False), (16384, 768, 768, True), (16384, 768, 3072, True), (16384, 3072, 768, False),
                         (2048, 12288, 4096, False)]):

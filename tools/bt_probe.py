@@ -28,7 +28,6 @@ for (M, N, K, gelu) in shapes:
     for stag in SWEEP:
         if OPT:
             ops.set_option(OPT, stag)
-        ops.set_option("gemm_big_gelu", 1)
         for _ in range(3):
             ops.gemm(a, w, bias=bias, gelu=gelu, out=out)
         torch.cuda.synchronize()
@@ -43,4 +42,3 @@ for (M, N, K, gelu) in shapes:
     print(row)
 if OPT:
     ops.set_option(OPT, 0)
-ops.set_option("gemm_big_gelu", 1)

@@ -460,170 +460,68 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(GemmDesc d) {
   rows16_store(d, v, m, n0 + 4 * g, reinterpret_cast<char*>(d.C), d.R);
 }
 
-// M <= 16, one batch entry, K-contiguous operands, K % 32 == 0: returns 1 when launched, 0 when not applicable
-static int gemm_rows16_try(const GemmDesc& d, hipStream_t stream) {
-  if (d.M > 16 || d.nz != 1 || (d.K & 31) || d.ldbk || (d.flags & (GEMM_A_KMAJOR | GEMM_B_KMAJOR))) return 0;
-  const int nsteps = d.K >> 5;
-  dim3 grid((unsigned)cdiv(d.N, 16));
-  if (d.flags & GEMM_SWIGLU) {  // (validated by gemm_bf16: alone, N = 2 I)
-    if (nsteps >= 64) hipLaunchKernelGGL((gemm_rows16_kernel<16, true>), grid, dim3(1024), 0, stream, d);
-    else if (nsteps >= 16) hipLaunchKernelGGL((gemm_rows16_kernel<8, true>), grid, dim3(512), 0, stream, d);
-    else hipLaunchKernelGGL((gemm_rows16_kernel<4, true>), grid, dim3(256), 0, stream, d);
-    return launch_status() == U2_OK ? 1 : U2_ERR_LAUNCH;
+// One step of a plan (gemm_plan.hip) on the rows it covers; `partial`: the stream's scratch.
+static int gemm_step(const GemmDesc& d, const GemmStep& s, void* partial, hipStream_t stream) {
+  GemmDesc g = d;
+  g.A = d.A + (int64_t)s.row0 * d.lda;
+  g.C = reinterpret_cast<char*>(d.C) + (int64_t)s.row0 * d.ldc * ((d.flags & GEMM_OUT_F32) ? 4 : 2);
+  if (d.flags & GEMM_RESIDUAL) g.R = d.R + (int64_t)s.row0 * d.ldr;
+  g.M = s.rows;
+  g.ksplit = s.ksplit, g.kt_per = s.kt_per, g.partial = s.ksplit > 1 ? reinterpret_cast<float*>(partial) : nullptr;
+  g.tail_rows = s.tail_rows, g.tiles_m = s.tiles_m, g.tiles_n = s.tiles_n, g.mubuf = s.mubuf;
+  const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
+  int e;
+  if (s.kind == GK_ROWS16) {
+    void (*const k[2][3])(GemmDesc) = {{gemm_rows16_kernel<16, true>, gemm_rows16_kernel<8, true>, gemm_rows16_kernel<4, true>},
+                                       {gemm_rows16_kernel<16>, gemm_rows16_kernel<8>, gemm_rows16_kernel<4>}};
+    hipLaunchKernelGGL(k[!s.pair][2 - s.form / 8], grid, dim3(s.form * 64), 0, stream, g);
+    e = launch_status();
+  } else if (s.kind == GK_TILE) {
+    void (*const k[2][3])(GemmDesc) = {
+        {gemm_bf16_nt_kernel<128, 128, true, true>, gemm_bf16_nt_kernel<128, 128, false, true>, gemm_bf16_nt_kernel<128, 128>},
+        {gemm_bf16_nt_kernel<64, 64, true, true>, gemm_bf16_nt_kernel<64, 64, false, true>, gemm_bf16_nt_kernel<64, 64>}};
+    hipLaunchKernelGGL(k[s.form != 128][s.ta ? 0 : s.tb ? 1 : 2], grid, dim3(256), 2 * (2 * s.form) * 64 * 2, stream, g);
+    e = launch_status();
+  } else {
+    e = s.kind == GK_SKINNY ? gemm_skinny_launch(g, s, stream) : gemm_bt_launch(g, s, stream);
   }
-  if (nsteps >= 64) hipLaunchKernelGGL((gemm_rows16_kernel<16>), grid, dim3(1024), 0, stream, d);
-  else if (nsteps >= 16) hipLaunchKernelGGL((gemm_rows16_kernel<8>), grid, dim3(512), 0, stream, d);
-  else hipLaunchKernelGGL((gemm_rows16_kernel<4>), grid, dim3(256), 0, stream, d);
-  return launch_status() == U2_OK ? 1 : U2_ERR_LAUNCH;
-}
-
-template <int BM, int BN>
-static int launch_tile(GemmDesc d, hipStream_t stream) {
-  d.tiles_m = (int)cdiv(d.M, BM);
-  d.tiles_n = (int)cdiv(d.N, BN);
-  dim3 grid(d.tiles_m * d.tiles_n, d.nz, d.ksplit > 1 ? d.ksplit : 1);
-  constexpr int smem = 2 * (BM + BN) * 64 * 2;
-  const bool ta = d.flags & GEMM_A_KMAJOR, tb = d.flags & GEMM_B_KMAJOR;
-  {  // MUBUF pieces when every byte offset of a batch entry's operands (K tile advance included) stays below 2^31
-    const int64_t ktiles = cdiv(d.K, 64) + 1;
-    const int64_t ea = (ta ? ktiles * 64 * d.lda + d.M : (int64_t)d.M * d.lda + ktiles * 64) * 2;
-    const int64_t eb = (tb ? ktiles * 64 * d.ldb + d.N : d.ldbk ? ktiles * d.ldbk + (int64_t)d.N * d.ldb : (int64_t)d.N * d.ldb + ktiles * 64) * 2;
-    d.mubuf = (opts().gemm_mubuf && ea < (1ll << 31) - 65536 && eb < (1ll << 31) - 65536) ? 1 : 0;
-  }
-  if (ta) hipLaunchKernelGGL((gemm_bf16_nt_kernel<BM, BN, true, true>), grid, dim3(256), smem, stream, d);
-  else if (tb) hipLaunchKernelGGL((gemm_bf16_nt_kernel<BM, BN, false, true>), grid, dim3(256), smem, stream, d);
-  else hipLaunchKernelGGL((gemm_bf16_nt_kernel<BM, BN>), grid, dim3(256), smem, stream, d);
+  if (e != U2_OK || s.ksplit == 1) return e;
+  // split-K: the epilogue over g.partial[ksplit][nz][M][N]
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)cdiv((int64_t)g.nz * g.M * ((g.N + 3) >> 2), 256)), dim3(256), 0, stream, g);
   return launch_status();
 }
 
 int gemm_bf16(GemmDesc d, hipStream_t stream) {
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.nz <= 0 || d.nz > 65535) return U2_ERR_ARG;
-  if (!d.A || !d.B || !d.C) return U2_ERR_ARG;
-  if (d.nsplit < 0 || (d.nsplit & 15) || (d.nsplit && (d.flags & GEMM_SWIGLU))) return U2_ERR_ARG;
-  if (d.nbh <= 0) d.nbh = 1;
-  static const bool trace = getenv("U2TOK_GEMM_TRACE") != nullptr;  // diagnostics: one line per product on stderr
-  if (trace) fprintf(stderr, "gemm M=%d N=%d K=%d nz=%d flags=0x%x lda=%d ldb=%d ldc=%d\n", d.M, d.N, d.K, d.nz, d.flags, (int)d.lda, (int)d.ldb, (int)d.ldc);
-  // 16-byte chunked loads along the contiguous dimension of each operand (K, or M / N of a K-major one): that dimension,
-  // leading dims and batch strides must keep every chunk aligned
-  if (d.flags & GEMM_SWIGLU) {  // gate | up pair product with SiLU(gate) * up in the epilogue: the 256 x 192-tile kernel only
-    const int64_t I = d.N >> 1;
-    if ((d.flags & ~GEMM_SWIGLU) || d.nz != 1 || d.ldbk || (d.N & 1) || (I & 15) || (d.K & 63) || d.ldc < I || (d.ldc & 7) ||
-        (d.lda & 7) || (d.ldb & 7) || (((uintptr_t)d.A | (uintptr_t)d.B | (uintptr_t)d.C) & 15))
-      return U2_ERR_ARG;
-    ProfScope ps(PROF_GEMM, 2.0 * d.M * d.N * d.K, stream, 2.0 * d.M * d.K + 2.0 * d.N * d.K + 2.0 * d.M * I);
-    if (d.M <= 16 && opts().gemm_tile == 0) {  // a few rows (decode steps): the few-rows kernel has the pair form too
-      const int r = gemm_rows16_try(d, stream);
-      if (r != 0) return r > 0 ? U2_OK : r;
-    }
-    const int big = gemm_big_try(d, stream);
-    return big > 0 ? U2_OK : (big < 0 ? big : U2_ERR_ARG);
+  const int flags = d.flags;
+  const Scratch sc = ctx().scratch_of(stream);
+  GemmPlan p;
+  int e = gemm_validate(d);
+  if (e == U2_OK) e = gemm_plan(d, opts(), sc.p ? sc.bytes : 0, p);
+  static const bool trace = getenv("U2TOK_GEMM_TRACE") != nullptr;  // diagnostics: one line per product and its plan on stderr
+  if (trace) {
+    char route[512] = " | error";
+    if (e == U2_OK) gemm_plan_format(p, route, sizeof(route));
+    fprintf(stderr, "gemm M=%d N=%d K=%d nz=%d flags=0x%x lda=%d ldb=%d ldc=%d%s\n", d.M, d.N, d.K, d.nz, flags, (int)d.lda,
+            (int)d.ldb, (int)d.ldc, route);
   }
-  const bool ta = d.flags & GEMM_A_KMAJOR, tb = d.flags & GEMM_B_KMAJOR;
-  if ((ta && !tb) || (tb && d.ldbk)) return U2_ERR_ARG;
-  if ((ta ? d.M : d.K) & 7) return U2_ERR_ARG;
-  if ((tb ? d.N : d.K) & 7) return U2_ERR_ARG;
-  if ((ta && d.lda < d.M) || (tb && d.ldb < d.N)) return U2_ERR_ARG;
-  if ((d.lda & 7) || (d.ldb & 7) || (d.sAb & 7) || (d.sAh & 7) || (d.sBb & 7) || (d.sBh & 7)) return U2_ERR_ARG;
-  if (((uintptr_t)d.A & 15) || ((uintptr_t)d.B & 15)) return U2_ERR_ARG;
-  if ((d.flags & (GEMM_BIAS_N | GEMM_BIAS_M)) && !d.bias) return U2_ERR_ARG;
-  if ((d.flags & GEMM_RESIDUAL) && !d.R) return U2_ERR_ARG;
+  if (e != U2_OK) return e;
   const bool out_f32 = d.flags & GEMM_OUT_F32;
-  bool vec = (d.ldc % 4 == 0) && (d.sCb % 4 == 0) && (d.sCh % 4 == 0) &&
-             (((uintptr_t)d.C & (out_f32 ? 15 : 7)) == 0);
-  if (d.flags & GEMM_BIAS_N) vec = vec && (((uintptr_t)d.bias & 7) == 0);
-  if (d.flags & GEMM_RESIDUAL)
-    vec = vec && (d.ldr % 4 == 0) && (d.sRb % 4 == 0) && (d.sRh % 4 == 0) && (((uintptr_t)d.R & 7) == 0);
-  d.flags = vec ? (d.flags | GEMM_VEC_OK) : (d.flags & ~GEMM_VEC_OK);
-
   const double zA = (d.sAb || d.sAh) ? d.nz : 1, zB = (d.sBb || d.sBh) ? d.nz : 1;  // a batch-shared operand is read once
   ProfScope ps(PROF_GEMM, 2.0 * d.M * d.N * d.K * d.nz, stream,
-               2.0 * d.M * d.K * zA + 2.0 * d.N * d.K * zB +
-                   d.nz * ((out_f32 ? 4.0 : 2.0) * d.M * d.N + ((d.flags & GEMM_RESIDUAL) ? 2.0 * d.M * d.N : 0.0)));
-  if (d.ldbk == 0) {  // (the 256-wide-tile kernels read row-major B only)
-    const int sk = gemm_skinny_try(d, stream);  // <= 256 rows against a cold E x E weight: all rows x 64 columns per workgroup, slices combined in the launch
-    if (sk != 0) return sk > 0 ? U2_OK : sk;
-    const int big = gemm_big_try(d, stream);  // large products: the big-tile kernel (gemm_bt.hip)
-    if (big != 0) return big > 0 ? U2_OK : big;
-  }
-  if (d.vt) return U2_ERR_ARG;  // (a transposed side output only exists in the big-tile kernel: ask gemm_vt_supported first)
-  return gemm_classic(d, stream);
+               (d.flags & GEMM_SWIGLU) ? 2.0 * d.M * d.K + 2.0 * d.N * d.K + 2.0 * d.M * (d.N >> 1)
+                                       : 2.0 * d.M * d.K * zA + 2.0 * d.N * d.K * zB +
+                                             d.nz * ((out_f32 ? 4.0 : 2.0) * d.M * d.N + ((d.flags & GEMM_RESIDUAL) ? 2.0 * d.M * d.N : 0.0)));
+  for (int i = 0; i < p.nsteps && e == U2_OK; ++i) e = gemm_step(d, p.step[i], sc.p, stream);
+  return e;
 }
 
-// 128^2 / 64^2 tile kernel above; `d` already validated (GEMM_VEC_OK resolved).
-int gemm_classic(GemmDesc d, hipStream_t stream) {
-  const Options& o = opts();
-  if (o.gemm_tile == 0) {  // (a forced tile keeps the tile kernels: tests of their row tails)
-    const int r = gemm_rows16_try(d, stream);
-    if (r != 0) return r > 0 ? U2_OK : r;
-    // <= 16 rows past a multiple of 128 in a many-row product (the ViT's GELU product: M = 16384 + 8 cls rows, 24 column
-    // tiles): one more row of 128 x 128 tiles is 24 workgroups that start a SEVENTH round after six full ones (+ 16 %);
-    // the few-rows kernel takes them instead
-    const int rem = d.M & 127;
-    if (d.nz == 1 && d.M >= 2048 && rem != 0 && rem <= 16 && !(d.K & 31) && !d.ldbk &&
-        !(d.flags & (GEMM_A_KMAJOR | GEMM_B_KMAJOR | GEMM_BIAS_M))) {
-      const bool f32 = d.flags & GEMM_OUT_F32;
-      GemmDesc main = d, tail = d;
-      main.M = d.M - rem;
-      tail.M = rem;
-      tail.A = d.A + (int64_t)main.M * d.lda;
-      tail.C = reinterpret_cast<char*>(d.C) + (int64_t)main.M * d.ldc * (f32 ? 4 : 2);
-      if (d.flags & GEMM_RESIDUAL) tail.R = d.R + (int64_t)main.M * d.ldr;
-      const int e = gemm_classic(main, stream);
-      if (e != U2_OK) return e;
-      const int r2 = gemm_rows16_try(tail, stream);
-      return r2 > 0 ? U2_OK : (r2 < 0 ? r2 : U2_ERR_ARG);
-    }
-  }
-  int tile = o.gemm_tile;
-  // "long K": weight-gradient products of the training path (dW = dY^T X: a small output, K = the 16392 token rows of the
-  // ViT).  64 x 64 tiles fill the CUs there but run at ~0.35-0.4 PF/s (197 us for 3072 x 768 x 16392); 128 x 128 tiles with
-  // K sliced over 5-8 workgroups keep the better tile and fill the machine.  No inference product has K >= 8192.
-  bool longk = false;
-  if (tile != 64 && tile != 128) {
-    const int64_t big = cdiv(d.M, 128) * cdiv(d.N, 128) * d.nz;
-    tile = (big >= 192) ? 128 : 64;  // fill 256 CUs; small-M weight-streaming shapes get 64^2 tiles
-    if (tile == 64 && o.gemm_splitk == 0 && d.nz == 1 && d.M >= 512 && d.N >= 512 && d.K >= 8192) {
-      tile = 128;
-      longk = true;
-    }
-  }
-  // split-K: a product with fewer workgroups than ~2 per CU runs one single-stage-prefetch K loop per CU and is
-  // latency-bound (M = 256, N = K = 4096: 36 us, 0.24 PF/s).  Slicing K puts several workgroups on every CU.
-  d.ksplit = 1;
-  if (o.gemm_splitk >= 0) {
-    const int64_t wgs = cdiv(d.M, tile) * cdiv(d.N, tile) * d.nz;
-    const int nkt = (int)cdiv(d.K, 64);
-    int s = o.gemm_splitk > 1 ? o.gemm_splitk : 0;
-    // (128 x 128 tiles: two workgroups per CU are resident -> aim at 512; the decoder prefill's M = 1024 out / down
-    //  projections are 256 tiles with K = 4096 / 12288: one K loop per CU with nothing to overlap it otherwise)
-    if (s == 0 && d.nz == 1 && (wgs <= 320 || longk) && nkt >= 16)
-      s = (int)std::min<int64_t>(8, std::min<int64_t>(nkt / 4, cdiv(longk ? 640 : (tile == 128 ? 512 : 1024), wgs)));
-    if (s > 1) {
-      const Scratch sc = ctx().scratch_of(stream);
-      const size_t slice = (size_t)d.nz * d.M * d.N * sizeof(float);
-      // partial sums cost HBM traffic: capped at 24 MB unless the K loop is long enough to dwarf it
-      if (o.gemm_splitk <= 1)
-        s = (int)std::min<size_t>(s, (longk ? sc.bytes : std::min<size_t>(sc.bytes, (tile == 128 ? 40u : 24u) << 20)) / slice);
-      const size_t need = (size_t)s * slice;
-      if (s > 1 && sc.p && need <= sc.bytes && d.nz <= 65535) {
-        d.ksplit = s;
-        d.kt_per = (int)cdiv(nkt, s);
-        d.ksplit = (int)cdiv(nkt, d.kt_per);  // no empty slices
-        d.partial = reinterpret_cast<float*>(sc.p);
-      }
-    }
-    if (d.ksplit <= 1) d.ksplit = 1;
-  }
-  if (longk && d.ksplit == 1) tile = 64;  // no scratch for the slices: the tile that fills the CUs
-  const int e = tile == 128 ? launch_tile<128, 128>(d, stream) : launch_tile<64, 64>(d, stream);
-  if (e != U2_OK || d.ksplit == 1) return e;
-  return gemm_splitk_reduce(d, stream);
-}
-
-int gemm_splitk_reduce(const GemmDesc& d, hipStream_t stream) {
-  const int64_t total = (int64_t)d.nz * d.M * ((d.N + 3) >> 2);
-  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, d);
-  return launch_status();
+bool gemm_vt_supported(const GemmDesc& d, int vt_n0, int vt_rows) {
+  GemmDesc v = d;
+  v.vt = static_cast<bf16_t*>(v.C);  // (the plan only asks whether a transposed output is requested)
+  v.vt_n0 = vt_n0;
+  v.vt_rows = vt_rows;
+  GemmPlan p;
+  return gemm_validate(v) == U2_OK && gemm_plan(v, opts(), 0, p) == U2_OK && p.step[0].kind == GK_BIG && p.step[0].vt;
 }
 
 }  // namespace u2

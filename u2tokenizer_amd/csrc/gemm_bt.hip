@@ -14,7 +14,7 @@
 //    output tile into the next (the last iterations stage the next tile's first K tiles).
 //  * round 4: THREE-stage forms of the same loop -- the ring form (NJ = 2: 256 x 128 tiles) and the deep forms (DEEP = 1 / 2: three
 //    stages for A / for B, two for the other operand) -- because what bounds the two-stage K loop is the latency of its own
-//    LDS-DMA stream ("Round 4: the big-tile GEMM"); gemm_big_try below says which form a product takes.
+//    LDS-DMA stream ("Round 4: the big-tile GEMM"); gemm_plan.hip says which form a product takes.
 // Requirements checked by the launcher: K % 64 == 0, operands addressable with 32-bit byte offsets.
 #include <algorithm>
 #include <type_traits>
@@ -740,299 +740,30 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_drain_kernel(GemmDesc d) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// May the deep 256 x 192 launch of `d` (many-row part: M a multiple of 256) run as the drain form?
-static bool bt_drain_ok(const GemmDesc& d) {
-  if (!opts().gemm_big_drain || !opts().gemm_big_deep || d.nz != 1 || d.ksplit > 1) return false;
-  if ((d.flags & GEMM_GELU) && opts().gemm_big_drain == 2) return false;  // (2: the forms whose arithmetic is that of the plain deep form only)
-  if (d.flags & ~(GEMM_VEC_OK | GEMM_BIAS_N | GEMM_GELU)) return false;
-  if (d.K % 384 || d.K < 768 || d.M % 256 || d.N % 192 || d.nsplit % 192) return false;
-  if ((d.flags & GEMM_BIAS_N) && d.N > 6144) return false;
-  if ((d.flags & GEMM_GELU) && d.vt) return false;
-  if (((int64_t)d.M - 1) * d.ldc + d.N >= (1ll << 30)) return false;
-  if (d.vt && (int64_t)(d.M / d.vt_rows) * d.vt_bs >= (1ll << 30)) return false;
-  const int64_t tiles = (int64_t)(d.M / 256) * (d.N / 192);
-  return tiles >= 2 * (int64_t)opts().gemm_big_grid;   // every workgroup has a tile to hide the previous one under
-}
-
-// Row tiles per group of the tile walk (pp_tile).  An XCD runs 32 consecutive ids = group_m row tiles x 32 / group_m column tiles at a time.
-static int bt_group_m(const GemmDesc& d) {
-  const int o = opts().gemm_big_group_m;
-  return o > 0 ? o : 8;
-}
-
-static int bt_launch_drain(GemmDesc d, hipStream_t stream) {
-  d.tiles_m = d.M / 256;
-  d.tiles_n = d.N / 192;
-  d.group_m = bt_group_m(d);
-  const int64_t total = (int64_t)d.tiles_m * d.tiles_n;
-  const int grid = (int)std::min<int64_t>(total, opts().gemm_big_grid);
-  const bool tail = d.tail_rows > 0;
-#define U2_DRAIN(G_, V_, T_) hipLaunchKernelGGL((gemm_bt_drain_kernel<G_, V_, T_>), dim3(grid), dim3(256), 0, stream, d)
-  if (d.flags & GEMM_GELU) { if (tail) U2_DRAIN(true, false, true); else U2_DRAIN(true, false, false); }
-  else if (d.vt) { if (tail) U2_DRAIN(false, true, true); else U2_DRAIN(false, true, false); }
-  else { if (tail) U2_DRAIN(false, false, true); else U2_DRAIN(false, false, false); }
-#undef U2_DRAIN
+// the kernel's steps of a plan (gemm_plan.hip: plan_big): variant 20 / 21 / 22 = 256 x 256 / 192 / 128 tiles (K slices, pair form,
+// in-launch tail as planned), 24 / 26 = the deep 256 x 192 / 256 x 256 forms, 27 = the drain form
+int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream) {
+  using K = void (*)(GemmDesc);
+  const bool tail = s.tail_rows > 0;
+  K k;
+  switch (s.form) {  // (cases in the order the kernels were first instantiated: the code object keeps its layout)
+    case 27: k = s.gelu ? (tail ? gemm_bt_drain_kernel<true, false, true> : gemm_bt_drain_kernel<true, false, false>)
+               : s.vt ? (tail ? gemm_bt_drain_kernel<false, true, true> : gemm_bt_drain_kernel<false, true, false>)
+                      : (tail ? gemm_bt_drain_kernel<false, false, true> : gemm_bt_drain_kernel<false, false, false>); break;
+    case 20: {
+      const K v[3] = {gemm_bt_kernel<4, false, true>, gemm_bt_kernel<4, false, false, 0, false, true>, gemm_bt_kernel<4>};
+      k = v[s.ksplit > 1 ? 0 : tail ? 1 : 2];
+      break;
+    }
+    case 22: k = s.ksplit > 1 ? gemm_bt_kernel<2, false, true> : gemm_bt_kernel<2>; break;
+    case 24: k = s.vt ? (tail ? gemm_bt_kernel<3, false, false, 2, true, true> : gemm_bt_kernel<3, false, false, 2, true>)
+                      : (tail ? gemm_bt_kernel<3, false, false, 2, false, true> : gemm_bt_kernel<3, false, false, 2>); break;
+    case 26: k = gemm_bt_kernel<4, false, false, 2>; break;
+    case 21: k = !s.pair ? (s.ksplit > 1 ? gemm_bt_kernel<3, false, true> : gemm_bt_kernel<3>) : gemm_bt_kernel<3, true>; break;
+    default: return U2_ERR_ARG;
+  }
+  hipLaunchKernelGGL(k, dim3(s.grid[0]), dim3(256), 0, stream, d);
   return launch_status();
-}
-
-template <int NJ, int DEEP>
-static int bt_launch_deep(GemmDesc d, hipStream_t stream) {
-  if (d.ksplit > 1) return U2_ERR_ARG;
-  d.tiles_m = (int)cdiv(d.M, 256);
-  d.tiles_n = (int)cdiv(d.N, 64 * NJ);
-  d.group_m = bt_group_m(d);
-  const int64_t total = (int64_t)d.tiles_m * d.tiles_n * d.nz;
-  if (total > 0x3fffffff) return U2_ERR_ARG;
-  const int grid = (int)std::min<int64_t>(total, opts().gemm_big_grid);
-  if constexpr (NJ == 3 && DEEP == 2) {
-    if (d.vt) {
-      if (d.tail_rows) hipLaunchKernelGGL((gemm_bt_kernel<3, false, false, 2, true, true>), dim3(grid), dim3(256), 0, stream, d);
-      else hipLaunchKernelGGL((gemm_bt_kernel<3, false, false, 2, true>), dim3(grid), dim3(256), 0, stream, d);
-      return launch_status();
-    }
-    if (d.tail_rows) {
-      hipLaunchKernelGGL((gemm_bt_kernel<3, false, false, 2, false, true>), dim3(grid), dim3(256), 0, stream, d);
-      return launch_status();
-    }
-  }
-  if (d.vt || d.tail_rows) return U2_ERR_ARG;
-  hipLaunchKernelGGL((gemm_bt_kernel<NJ, false, false, DEEP>), dim3(grid), dim3(256), 0, stream, d);
-  return launch_status();
-}
-
-template <int NJ, bool PAIR = false>
-static int bt_launch(GemmDesc d, hipStream_t stream) {
-  if (d.vt) return U2_ERR_ARG;  // only the deep 256 x 192 form leaves transposed tiles (bt_launch_deep): never drop the request silently
-  d.tiles_m = (int)cdiv(d.M, 256);
-  d.tiles_n = (int)cdiv(d.N, 64 * NJ);
-  d.group_m = bt_group_m(d);
-  if (d.ksplit > 1 && (d.nz != 1 || PAIR || !d.partial)) return U2_ERR_ARG;
-  const int64_t total = (int64_t)d.tiles_m * d.tiles_n * (d.ksplit > 1 ? d.ksplit : d.nz);
-  if (total > 0x3fffffff) return U2_ERR_ARG;
-  const int grid = (int)std::min<int64_t>(total, opts().gemm_big_grid);
-  if constexpr (!PAIR) {
-    if (d.ksplit > 1) {
-      hipLaunchKernelGGL((gemm_bt_kernel<NJ, false, true>), dim3(grid), dim3(256), 0, stream, d);
-      return gemm_splitk_reduce(d, stream);
-    }
-  }
-  if constexpr (NJ == 4 && !PAIR) {
-    if (d.tail_rows) {
-      hipLaunchKernelGGL((gemm_bt_kernel<4, false, false, 0, false, true>), dim3(grid), dim3(256), 0, stream, d);
-      return launch_status();
-    }
-  }
-  if (d.tail_rows) return U2_ERR_ARG;
-  hipLaunchKernelGGL((gemm_bt_kernel<NJ, PAIR>), dim3(grid), dim3(256), 0, stream, d);
-  return launch_status();
-}
-
-// 64-wide K tiles only (at least two); 32-bit byte offsets into A and B (per z)
-static bool bt_legal(const GemmDesc& d) {
-  return !(d.K & 63) && d.K >= 128 && (int64_t)d.M * d.lda < (1ll << 30) && (int64_t)d.N * d.ldb < (1ll << 30);
-}
-
-// K slices for a product of `tiles` output tiles: fill the 256 CUs, keep >= 4 K tiles per slice (and >= 2 in the last one:
-// the K loop's pipeline), within the stream's scratch.  0 / 1 = unsplit.
-static int bt_slices(GemmDesc& d, int64_t tiles, int want, hipStream_t stream) {
-  d.ksplit = 1;
-  const int nkt = d.K >> 6;
-  if (want <= 1 || d.nz != 1 || nkt < 8) return 1;
-  const Scratch sc = ctx().scratch_of(stream);
-  const size_t slice = (size_t)d.M * d.N * sizeof(float);
-  if (!sc.p || sc.bytes < 2 * slice) return 1;
-  int s = (int)std::min<int64_t>(std::min<int64_t>(want, nkt / 4), (int64_t)(sc.bytes / slice));
-  while (s > 1) {
-    const int per = (int)cdiv(nkt, s), used = (int)cdiv(nkt, per);
-    if (nkt - (used - 1) * per >= 2) {  // last slice long enough
-      d.ksplit = used;
-      d.kt_per = per;
-      d.partial = reinterpret_cast<float*>(sc.p);
-      return used > 1 ? used : (d.ksplit = 1);
-    }
-    --s;
-  }
-  (void)tiles;
-  return 1;
-}
-
-// variants: 20 = 256 x 256, 21 = 256 x 192, 22 = 256 x 128 tiles (ring form); 24 = 256 x 192 with B deep, 26 = 256 x 256 with B deep,
-// 27 = 24 as the drain form (tile i's epilogue under tile i + 1's K loop)
-static int bt_launch_variant(int v, const GemmDesc& d, hipStream_t stream) {
-  switch (v) {
-    case 20: return bt_launch<4>(d, stream);
-    case 22: return bt_launch<2>(d, stream);
-    case 23: case 25: return U2_ERR_ARG;  // (the A-deep twins of round 4: removed)
-    case 24: return bt_launch_deep<3, 2>(d, stream);
-    case 26: return bt_launch_deep<4, 2>(d, stream);
-    case 27: return bt_drain_ok(d) ? bt_launch_drain(d, stream) : U2_ERR_ARG;
-    default: return bt_launch<3>(d, stream);
-  }
-}
-
-// The heuristic's choice (20 / 21) as launched: the deep form of the same tile width with B as the three-stage operand (26 / 24) --
-// tools/bt_sweep.py / bt_epilogue_probe.py, cold operands, us two-stage -> deep B (deep A beside it), profiles/r04_bt_deep_*.log:
-//   ViT q|k|v 67.6 -> 64.2 (65.6), out-projection 32.1 -> 30.6 (31.0), fc2 72.2 -> 67.4 (67.3); 2048 x 12288 x 4096 191.4 -> 163.0 (166.3);
-//   1792 x 8192 x 4096 114.9 -> 102.6 (102.9); 4096^3 117.8 -> 110.6 (110.4); 8192^3 890 -> 816 (831) = 1.35 PF/s.
-//   (GELU products keep two stages: fc1 + bias + GELU 112.7 us against 123.6 deep, profiles/r04_bt_gelu_forms.log)
-static int bt_deep_of(int v, int flags) {
-  return (!opts().gemm_big_deep || (flags & GEMM_GELU)) ? v : v == 20 ? 26 : v == 21 ? 24 : v;
-}
-
-// Which tile (tools/gpu_check.py ppperf on MI355X, random operands; DESIGN.md section 3 has the tables): the kernel
-// runs its K loop at ~50 % of the MFMA peak (8192^3: 1.23-1.29 PF/s; gemm.hip's 128 x 128 tiles: 0.9) but nothing
-// overlaps its prologue and epilogue, and a product is as slow as its last round of tiles: it is taken when the tiles
-// fill their rounds of 256 workgroups to >= 70 %, with the tile width that needs the fewest (work-weighted) rounds --
-// the ViT's N = 2304 / 768 projections are exactly 3 / 1 rounds of 192-wide tiles, N = 3072 exactly 3 rounds of
-// 256-wide ones.
-static int bt_pick(const GemmDesc& d) {
-  if (!bt_legal(d) || d.K < 256) return 0;
-  // the GELU epilogue is 256 values per lane of VALU work that the 128 x 128 kernel hides under its second workgroup
-  // per CU (fc1 of the ViT: 112 us there, 120 us here in round 1).  Round 4 (packed-math GELU, gelu_fast2): 128 -> 113 us with cold
-  // operands (profiles/r04_bt_gelu_forms.log), pipeline 8.98 -> 8.93 ms per volume (r04_ab_gelu_pipeline.log): default on;
-  // option "gemm_big_gelu" = 0 keeps GELU products on the 128 x 128 kernel
-  if ((d.flags & GEMM_GELU) && !opts().gemm_big_gelu) return 0;
-  const int gmax = opts().gemm_big_grid;
-  const int64_t tm = cdiv(d.M, 256) * d.nz;
-  const int64_t t4 = tm * cdiv(d.N, 256), t3 = tm * cdiv(d.N, 192);
-  const int64_t r4 = cdiv(t4, gmax), r3 = cdiv(t3, gmax);
-  const double fill4 = (double)d.M * d.N * d.nz / ((double)r4 * gmax * 65536.0);
-  const double fill3 = (double)d.M * d.N * d.nz / ((double)r3 * gmax * 49152.0);
-  const double c4 = (double)r4, c3 = 0.9 * (double)r3;  // a 192-wide tile takes ~0.9 of the time of a 256-wide one
-  if (c3 < c4) return fill3 >= 0.7 ? 21 : (fill4 >= 0.7 ? 20 : 0);
-  return fill4 >= 0.7 ? 20 : (fill3 >= 0.7 ? 21 : 0);
-}
-
-// The ring form (256 x 128 tiles, variant 22) for products whose 256- and 192-wide tiles leave the CUs a partial round
-// (bt_pick: fill < 70 %) while the 128-wide ones make ONE round that is at least three-quarters full: M = 2048 rows against an
-// E x E weight (the SVR's output projections), 1024 against 2E x E (the TTA's text k | v), 2048 x 4096 x 6144 (projector) --
-// 256 tiles each.  tools/bt_sweep.py, cold weights, us (128^2 kernel -> here; vendor library beside it): 89.7 -> 69.4 (65.9),
-// 82.0 -> 64.4 (62.9), 115.1 -> 95.5 (profiles/r04_bt_ring_sweep.log); 192 tiles (prefill q|k|v, 1024 x 6144 x 4096): 71.2 with two K
-// slices of 256 x 192 tiles -> 57.5 (r04_bt_counted_waits_ab.log).  With 128 tiles (1024 x 4096 x 4096) it ties the 128^2 kernel.
-static int bt_pick_ring(const GemmDesc& d) {
-  if (!bt_legal(d) || d.K < 512) return 0;
-  if ((d.flags & GEMM_GELU) && !opts().gemm_big_gelu) return 0;
-  const int gmax = opts().gemm_big_grid;
-  const int64_t t2 = cdiv(d.M, 256) * cdiv(d.N, 128) * d.nz;
-  return (t2 * 4 >= (int64_t)gmax * 3 && t2 <= gmax) ? 22 : 0;
-}
-
-// Products that leave the 256 CUs a partial round of big tiles, sliced along K so that (tiles x slices) fills them -- the
-// cases tools/bt_sweep.py measured ahead of the 128 x 128 kernel with its own split-K (profiles/r03_bt_sweep.log, cold weights,
-// us: 128^2 kernel -> here):
-//   (a) 129..256 rows against a wide weight (the TTA self-attention's packed q|k|v, 256 x 12288 x 4096): 71.5 -> 51.0
-//       (256 x 192 tiles, 4 slices); the 256 x 4096 x 4096 products of the same chain tie at 30 us and stay where they are
-//   (b) 512..1024 rows, K >= 8192 (decoder down-projection at prefill, 1024 x 4096 x 12288): 131.7 -> 111.0 (256 x 256, 4)
-//   (c) 512..1024 rows whose 192-wide tiles make exactly half a round (prefill q|k|v, 1024 x 6144 x 4096): 77.1 -> 71.6
-//       (256 x 192, 2)
-// Returns variant | slices << 8, or 0.  The caller falls back to the small-tile kernel when the scratch cannot hold the slices.
-static int bt_pick_sliced(const GemmDesc& d) {
-  if (!bt_legal(d) || d.nz != 1 || (d.flags & GEMM_GELU)) return 0;
-  const int64_t tm = cdiv(d.M, 256);
-  if (d.M > 128 && d.M <= 256 && d.N >= 8192 && d.K >= 2048) return 21 | (4 << 8);
-  if (d.M >= 512 && d.M <= 1024 && (d.M & 255) == 0) {
-    if (d.K >= 8192 && d.N >= 2048 && tm * cdiv(d.N, 256) <= 64) return 20 | (4 << 8);
-    const int64_t t3 = tm * (d.N / 192);
-    if (d.N % 192 == 0 && d.K >= 4096 && t3 >= 112 && t3 <= 128) return 21 | (2 << 8);
-  }
-  return 0;
-}
-
-// Can the product leave its columns [vt_n0, N) TRANSPOSED in d.vt (GemmDesc::vt) instead of C?  Only the 256 x 192 deep form does that,
-// so: the heuristic must pick it for the many-row part of the product (a cls-row tail goes to the few-rows kernel and is written to
-// C as usual), nothing forced / sliced, plain bf16 output without bias or residual, whole tiles on both sides of vt_n0, and 256-row
-// tiles that do not straddle a chunk of vt_rows keys.  The pipeline asks before it sets d.vt (and runs transpose_bf16 otherwise).
-bool gemm_vt_supported(const GemmDesc& d, int vt_n0, int vt_rows) {
-  if (opts().gemm_big != 0 || !opts().gemm_big_deep || d.nz != 1 || d.flags & ~GEMM_VEC_OK) return false;
-  const int rem = d.M & 255, Mm = d.M - rem;
-  if (rem > 64 || Mm < 512 || d.N < 256 || d.K < 128) return false;
-  if (vt_n0 % 192 || (d.N - vt_n0) % 192 || vt_n0 <= 0 || vt_n0 >= d.N || vt_rows % 256 || Mm % vt_rows || (d.nsplit > vt_n0)) return false;
-  GemmDesc m = d;
-  m.M = Mm;
-  if (opts().gemm_big_ring && bt_pick(m) == 0 && bt_pick_ring(m) == 22) return false;
-  if (opts().gemm_big_skinny && rem == 0 && bt_pick_sliced(d) != 0) return false;  // gemm_big_try takes the sliced forms first
-  return bt_pick(m) == 21;
-}
-
-// Returns 1 when the product was launched here, 0 when the caller should use gemm.hip's kernel, < 0 on error.
-// `d` has been validated by gemm_bf16 (alignment of A / B, GEMM_VEC_OK resolved).
-int gemm_big_try(const GemmDesc& d, hipStream_t stream) {
-  if (d.vt && !gemm_vt_supported(d, d.vt_n0, d.vt_rows)) return U2_ERR_ARG;  // (the caller did not ask first)
-  if (d.flags & GEMM_SWIGLU) {  // only this kernel has the pair form (256 x 192 tiles = 96 output columns); gemm_bf16 validated
-    if (!bt_legal(d)) return U2_ERR_ARG;
-    const int e = bt_launch<3, true>(d, stream);
-    return e == U2_OK ? 1 : e;
-  }
-  const int mode = opts().gemm_big;
-  if (mode < 0) return 0;
-  if (!(d.flags & GEMM_VEC_OK) || (d.flags & (GEMM_BIAS_M | GEMM_A_KMAJOR | GEMM_B_KMAJOR)) || (d.N & 7)) return 0;
-  switch (d.flags & (GEMM_BIAS_N | GEMM_GELU | GEMM_RESIDUAL | GEMM_OUT_F32)) {
-    case 0: case GEMM_OUT_F32: case GEMM_BIAS_N: case GEMM_BIAS_N | GEMM_OUT_F32: case GEMM_BIAS_N | GEMM_GELU:
-    case GEMM_BIAS_N | GEMM_RESIDUAL: case GEMM_RESIDUAL: break;
-    default: return 0;
-  }
-  // 16-byte epilogue accesses (8 consecutive n per lane)
-  const bool f32 = d.flags & GEMM_OUT_F32;
-  if (((uintptr_t)d.C & 15) || (d.ldc & (f32 ? 3 : 7)) || (d.sCb & (f32 ? 3 : 7)) || (d.sCh & (f32 ? 3 : 7))) return 0;
-  if ((d.flags & GEMM_BIAS_N) && ((uintptr_t)d.bias & 15)) return 0;
-  if ((d.flags & GEMM_RESIDUAL) && (((uintptr_t)d.R & 15) || (d.ldr & 7) || (d.sRb & 7) || (d.sRh & 7))) return 0;
-  if (mode > 0) {  // forced (tests, measurements)
-    if (!bt_legal(d)) return 0;
-    GemmDesc ds = d;
-    if (mode <= 22) bt_slices(ds, 0, opts().gemm_big_splitk, stream);
-    if (mode == 27 && !bt_drain_ok(ds)) return 0;
-    const int e = bt_launch_variant(mode, ds, stream);
-    return e == U2_OK ? 1 : e;
-  }
-  // A few rows past a multiple of 256 (the ViT's cls rows: M = 2049 per chunk, 8 * 2049 per volume) would cost a whole extra
-  // row of tiles: they go through the few-rows / small-tile kernel -- for EVERY form, so that a chunk's rows are computed
-  // by the same arithmetic whatever the number of chunks in the call (tests/test_gpu_path.py::test_vit_full_size_properties).
-  const int rem = d.M & 255;
-  const bool split_tail = d.nz == 1 && rem != 0 && rem <= 64 && d.M > 256;
-  GemmDesc main = d, tail = d;
-  if (split_tail) {
-    main.M = d.M - rem;
-    tail.M = rem;
-    tail.A = d.A + (int64_t)main.M * d.lda;
-    tail.C = reinterpret_cast<char*>(d.C) + (int64_t)main.M * d.ldc * (f32 ? 4 : 2);
-    if (d.flags & GEMM_RESIDUAL) tail.R = d.R + (int64_t)main.M * d.ldr;
-  }
-  auto launch = [&](int v) {
-    // <= 16 tail rows ride in the launch of the plain 256 x 256 (20) and deep 256 x 192 (24) forms -- what the ViT's products run
-    const bool in_launch = split_tail && rem <= 16 && !(d.K & 31) && !(d.flags & GEMM_BIAS_M) && (v == 20 || v == 24 || v == 27) &&
-                           opts().gemm_tail_fused && main.ksplit <= 1;
-    if (in_launch) main.tail_rows = rem;
-    int e = bt_launch_variant(v, main, stream);
-    main.tail_rows = 0;
-    if (e == U2_OK && split_tail && !in_launch) e = gemm_classic(tail, stream);
-    return e == U2_OK ? 1 : e;
-  };
-  // (ahead of the sliced forms: 192 ring tiles beat 2 x 128 sliced ones)
-  if (opts().gemm_big_ring && main.M >= 512 && bt_pick(main) == 0 && bt_pick_ring(main) == 22) return launch(22);
-  if (opts().gemm_big_skinny && !split_tail) {
-    const int v = bt_pick_sliced(d);
-    if (v > 0) {
-      GemmDesc ds = d;
-      if (bt_slices(ds, 0, v >> 8, stream) == (v >> 8)) {  // (fewer slices than wanted: the small-tile kernel is the better one)
-        const int e = bt_launch_variant(v & 0xff, ds, stream);
-        return e == U2_OK ? 1 : e;
-      }
-    }
-  }
-  if (d.M < 512 || d.N < 256 || d.K < 128) return 0;
-  const int v = bt_pick(main);
-  if (v == 0) return 0;
-  int vv = bt_deep_of(v, d.flags);
-  // round 6, the drain form: products whose workgroups walk two or more 256 x 192 tiles hide tile i's epilogue under tile i + 1's K
-  // loop.  A GELU product prefers it over the 256-wide two-stage form whenever its 192-wide tiles fill their rounds (fc1 of the ViT:
-  // four whole rounds instead of three with 256 GELUs per lane exposed in each).
-  if (bt_drain_ok(main)) {
-    const int gmax = opts().gemm_big_grid;
-    const int64_t t3 = (int64_t)(main.M / 256) * (main.N / 192);
-    const double fill3 = (double)t3 / ((double)cdiv(t3, gmax) * gmax);
-    if (vv == 24 || ((d.flags & GEMM_GELU) && fill3 >= 0.7)) vv = 27;
-  }
-  return launch(vv);
 }
 
 }  // namespace u2

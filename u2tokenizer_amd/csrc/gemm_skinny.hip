@@ -158,26 +158,11 @@ __global__ __launch_bounds__(256, 1) void gemm_skinny64_kernel(GemmDesc d, int n
 
 }  // namespace
 
-// Returns 1 when the product was launched here, 0 when it is not this kernel's (the caller goes on), < 0 on error.  `d` validated by
-// gemm_bf16 (GEMM_VEC_OK resolved).  Taken: one batch entry, 64 < M <= 256 rows, row-major operands, K a multiple of 128 with >= 16 K
-// tiles of 64, N = 2048 .. 4096 in whole 64-column strips (about one workgroup per CU; wider products fill the chip with the big-tile
-// kernel's slices), 16-byte epilogue accesses.  Needs no scratch.
-int gemm_skinny_try(const GemmDesc& d, hipStream_t stream) {
-  const Options& o = opts();
-  if (!o.gemm_skinny || o.gemm_tile != 0 || o.gemm_big != 0 || o.gemm_splitk != 0) return 0;   // (forced choices keep their kernels)
-  if (d.nz != 1 || d.M <= 64 || d.M > 256 || (d.N & 63) || (d.K & 127) || d.ldbk) return 0;
-  if (d.flags & (GEMM_BIAS_M | GEMM_A_KMAJOR | GEMM_B_KMAJOR | GEMM_SWIGLU) || !(d.flags & GEMM_VEC_OK) || d.vt) return 0;
-  const bool f32 = d.flags & GEMM_OUT_F32;
-  if (((uintptr_t)d.C & 15) || (d.ldc & (f32 ? 3 : 7))) return 0;
-  if ((d.flags & GEMM_BIAS_N) && ((uintptr_t)d.bias & 15)) return 0;
-  if ((d.flags & GEMM_RESIDUAL) && (((uintptr_t)d.R & 15) || (d.ldr & 7))) return 0;
-  const int nstrips = d.N >> 6;
-  if ((d.K >> 6) < 16 || nstrips < 32 || nstrips > 64) return 0;
-  const int mtiles = (d.M + 63) >> 6;
-  const bool mubuf = o.gemm_skinny == 2 && (int64_t)d.M * d.lda < (1ll << 29) && (int64_t)d.N * d.ldb < (1ll << 29);
-  if (mubuf) hipLaunchKernelGGL(gemm_skinny64_kernel<true>, dim3(nstrips * mtiles), dim3(256), S64_NS * S64_STAGE, stream, d, nstrips, mtiles);
-  else hipLaunchKernelGGL(gemm_skinny64_kernel<false>, dim3(nstrips * mtiles), dim3(256), S64_NS * S64_STAGE, stream, d, nstrips, mtiles);
-  return launch_status() == U2_OK ? 1 : U2_ERR_LAUNCH;
+// the kernel's step of a plan (gemm_plan.hip: skinny_ok): tiles_n 64-column strips x tiles_m 64-row tiles
+int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream) {
+  hipLaunchKernelGGL(s.mubuf ? gemm_skinny64_kernel<true> : gemm_skinny64_kernel<false>, dim3(s.grid[0]), dim3(256), S64_NS * S64_STAGE, stream,
+                     d, s.tiles_n, s.tiles_m);
+  return launch_status();
 }
 
 }  // namespace u2

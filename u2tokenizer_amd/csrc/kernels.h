@@ -71,19 +71,34 @@ struct GemmDesc {
   // classic tile kernel (filled by its launcher): 1 = the LDS-DMA pieces leave as buffer_load ... lds (both operands of a batch entry
   // span < 2 GB), 0 = FLAT-encoded global_load_lds (option gemm_mubuf 0, or larger operands)
   int mubuf = 0;
-  // big-tile kernels (filled by their launchers): row tiles per group of the tile walk (pp_tile: ids walk `group_m` row tiles column by column)
+  // big-tile kernels: row tiles per group of the tile walk (pp_tile: ids walk `group_m` row tiles column by column)
   int group_m = 8;
 };
 
 // Options (tile, split-K, big-tile selection) and the split-K scratch registration of the launch stream come from the
 // calling thread's current Context (ctx.h).  Without a registered scratch, products run unsplit.
 int gemm_bf16(GemmDesc d, hipStream_t stream);
-// internal: the kernels behind gemm_bf16 (descriptor already validated there)
-int gemm_classic(GemmDesc d, hipStream_t stream);        // gemm.hip: 128^2 / 64^2 tiles, 2+ workgroups per CU
-int gemm_big_try(const GemmDesc& d, hipStream_t stream);  // gemm_bt.hip: 1 launched, 0 not applicable, < 0 error
-int gemm_skinny_try(const GemmDesc& d, hipStream_t stream);  // gemm_skinny.hip (M <= 256 against a cold weight): same convention
-bool gemm_vt_supported(const GemmDesc& d, int vt_n0, int vt_rows);  // gemm_bt.hip: may d.vt be set for this product?
-int gemm_splitk_reduce(const GemmDesc& d, hipStream_t stream);  // gemm.hip: epilogue over d.partial[ksplit][nz][M][N]
+bool gemm_vt_supported(const GemmDesc& d, int vt_n0, int vt_rows);  // gemm.hip: may d.vt be set for this product?
+
+// Routing (gemm_plan.hip, host code only): gemm_bf16 = gemm_validate -> gemm_plan -> one launch per step.
+enum : int { GK_ROWS16 = 0, GK_TILE = 1, GK_SKINNY = 2, GK_BIG = 3 };
+struct GemmStep {  // one kernel instantiation over rows [row0, row0 + rows) of the product
+  int kind = GK_TILE;
+  int form = 0;  // GK_ROWS16: waves (4 / 8 / 16); GK_TILE: tile (64 / 128); GK_BIG: variant (20 21 22 24 26 27, gemm_plan.hip)
+  int row0 = 0, rows = 0;
+  bool pair = false, ta = false, tb = false, mubuf = false, gelu = false, vt = false;  // template arguments
+  int ksplit = 1, kt_per = 0;  // K slices (> 1: fp32 partial sums in the stream's scratch, then gemm_splitk_reduce_kernel)
+  int tail_rows = 0;           // GK_BIG: rows [row0 + rows, + tail_rows) computed in the same launch (rows16.h)
+  int tiles_m = 0, tiles_n = 0;
+  int grid[3] = {1, 1, 1};
+};
+struct GemmPlan { int nsteps = 0; GemmStep step[2]; };  // main, tail
+int gemm_validate(GemmDesc& d);  // U2_ERR_ARG or U2_OK with GEMM_VEC_OK resolved
+int gemm_plan(const GemmDesc& d, const Options& o, size_t scratch_bytes, GemmPlan& p);  // d validated; U2_ERR_ARG if no kernel takes it
+void gemm_plan_format(const GemmPlan& p, char* buf, size_t n);  // " | <kernel> rows= grid= slices= tail=" per step (the trace)
+// the launchers of the steps (descriptor of the step's rows, launcher fields filled)
+int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);  // gemm_skinny.hip
+int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);      // gemm_bt.hip
 
 // ------------------------------------------------------------------ row ops (rowops.hip)
 // y[b][r][:] = LayerNorm(x[b][r][:] (+ res[b][r][:])) * w + bias   (bf16 in/out, fp32 math)
