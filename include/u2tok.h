@@ -295,7 +295,7 @@ int u2tok_flash_attention_d64_lse(const void* q, const void* k, const void* vt, 
 /* Fused attention core of the tokenizer's attention modules -- RelativeMultiheadAttention (rma.py:60-75: + relative_bias
  * [j - i + max_len - 1][h], bf16 (2 max_len - 1, H)), RotaryMultiheadAttention (rope.py:82-86), MultiHeadCrossAttention /
  * LinearAggregation (tta.py:55-61; rel_bias NULL):  out = softmax(q k^T scale + bias) v  per (batch, head), scores and
- * probabilities never in HBM.  Row r of batch b at ptr + b*?_bs + r*ld?, head h at column h*d, d in {64, 128, 256, 512};
+ * probabilities never in HBM.  Row r of batch b at ptr + b*?_bs + r*ld?, head h at column h*d, d in {64, 96, 128, 256, 512};
  * q / k / v 16-byte aligned with strides % 8 == 0, out 8-byte aligned with strides % 4 == 0; with rel_bias: Sq, Skv <=
  * max_len.  splits: 0 = heuristic, n > 0 = cut the keys into n ranges (fp32 partial sums in `workspace`:
  * u2tok_tok_attention_workspace_bytes, 16-byte aligned; NULL = unsplit).  U2TOK_ERR_ARG for shapes it does not take. */
@@ -311,7 +311,7 @@ int u2tok_tok_attention(const void* q, const void* k, const void* v, void* out, 
  * layer of the PREFILL as RMSNorm -> packed q|k|v GEMM -> head norm + rotary -> causal grouped-query attention -> out
  * projection (+ residual) -> RMSNorm -> packed gate|up GEMM -> SiLU(gate) * up -> down projection (+ residual). */
 /* softmax(q k^T scale [causal: key j <= query i + Skv - Sq]) v with grouped-query heads: query head h (column h*d of q / out)
- * reads key / value head h / (Hq / Hkv) (column of k / v); d in {64, 128, 256, 512}; layout conventions of
+ * reads key / value head h / (Hq / Hkv) (column of k / v); d in {64, 96, 128, 256, 512}; layout conventions of
  * u2tok_tok_attention. */
 int u2tok_attention_gqa(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t Hq,
                         int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs,
@@ -327,7 +327,7 @@ int u2tok_attention_gqa_split(const void* q, const void* k, const void* v, void*
 /* y[r] = bf16(x[r] * rsqrt(mean(x[r]^2) + eps)) * w   (LlamaRMSNorm / Qwen3RMSNorm); C % 8 == 0, C <= 8192 */
 int u2tok_rmsnorm_bf16(const void* x, const void* w, void* y, int64_t rows, int32_t C, int64_t ldx, int64_t ldy, float eps,
                        u2tok_stream_t stream);
-/* In place on the q and k heads of a packed projection output qkv[rows][(Hq + 2 Hkv) D] (D = 64 / 128): per-head RMSNorm
+/* In place on the q and k heads of a packed projection output qkv[rows][(Hq + 2 Hkv) D] (D = 64 / 96 / 128): per-head RMSNorm
  * with weights wq / wk (Qwen3Attention.q_norm / k_norm; both NULL: none, Llama) and x cos + rotate_half(x) sin
  * (apply_rotary_pos_emb) with cos / sin [rows][cs_ld >= D], fp32 (cos_sin_f32 != 0) or bf16. */
 int u2tok_qk_norm_rope(void* qkv, const void* wq, const void* wk, const void* cos, const void* sin, int32_t cos_sin_f32,
@@ -352,7 +352,8 @@ int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, i
  *         (B, Hkv, capacity, D; kv_stride = capacity * D, 0: a dense (B, Hkv, 1, D) pair with s_off = 0)
  *   post: attention of the B query rows over the first T positions of K / V (same layout; keys split over workgroups, merged
  *         in a fixed order) -> out projection + residual x -> RMSNorm -> packed gate|up -> SiLU(gate) * up -> down + residual
- * B <= 16, D in {64, 128}, E % 32 == 0, I % 32 == 0; biases may be NULL; same rounding points as the HF modules in bf16.
+ * B <= 16, D in {64, 96, 128}, E % 32 == 0, I % 32 == 0; biases may be NULL; same rounding points as the HF modules in bf16.
+ * A sliding-window layer (Phi-3: the last W positions) passes K / V advanced to its first visible position and T = W.
  * One workspace for both calls: u2tok_decoder_decode_workspace_bytes(cfg, T) bytes. */
 typedef struct u2tok_decode_config {
   int32_t B, E, Hq, Hkv, D, I; /* new tokens (= batch), hidden size, query / key-value heads, head dim, MLP width */

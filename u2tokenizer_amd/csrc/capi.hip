@@ -304,7 +304,7 @@ static DecodeCfg dec_cfg(const u2tok_decode_config* c) {
 }
 static bool dec_ok(const u2tok_decode_config* c) {
   return c && c->B > 0 && c->B <= 16 && c->E > 0 && !(c->E & 31) && c->Hq > 0 && c->Hkv > 0 && c->Hq % c->Hkv == 0 &&
-         (c->D == 64 || c->D == 128) && c->I > 0 && !(c->I & 31);
+         (c->D == 64 || c->D == 96 || c->D == 128) && c->I > 0 && !(c->I & 31);
 }
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* c, int32_t T) {
   return dec_ok(c) && T > 0 ? decoder_decode_workspace_bytes(dec_cfg(c), T) : 0;

@@ -140,7 +140,7 @@ struct Bf16Val {  // bf16 cos / sin tables
 int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32,
                  int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int S,
                  int64_t kv_stride, int s_off, hipStream_t stream) {
-  if (!qkv || !cosp || !sinp || rows <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 128) || (!wq) != (!wk)) return U2_ERR_ARG;
+  if (!qkv || !cosp || !sinp || rows <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 96 && D != 128) || (!wq) != (!wk)) return U2_ERR_ARG;
   if ((!kc) != (!vc) || (kc && (S <= 0 || rows % S))) return U2_ERR_ARG;
   if (kv_stride == 0) kv_stride = (int64_t)S * D;
   if (kc && (s_off < 0 || kv_stride < (int64_t)(s_off + S) * D)) return U2_ERR_ARG;
@@ -153,6 +153,8 @@ int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* co
                      reinterpret_cast<const T_*>(sinp), rows, Hq, Hkv, ld, cs_ld, eps, kc, vc, S, kv_stride, s_off)
   if (D == 128 && cs_is_f32) U2_QK(128, float);
   else if (D == 128) U2_QK(128, Bf16Val);
+  else if (D == 96 && cs_is_f32) U2_QK(96, float);   // (lanes 48..63 of each wave idle)
+  else if (D == 96) U2_QK(96, Bf16Val);
   else if (cs_is_f32) U2_QK(64, float);
   else U2_QK(64, Bf16Val);
 #undef U2_QK

@@ -29,6 +29,12 @@
 //   V tile (transpose reads; a 16-lane group reads a [4 keys][16 d] block, lane a supplies row a >> 2 / 8-byte piece a & 3):
 //       chunks rotated inside each 256-byte segment by 2 (key & 3) + 8 ((key >> 2) & 1) so that the 8 rows x 32 bytes a
 //       half wave touches fall into 16 different 16-byte slots (the layout family of gemm.hip's K-major operands).
+//   d = 96 (Phi-3-mini): 192-byte rows of 12 chunks, so neither form applies (chunks 8..11 would leave the row, and with no
+//   permutation the 192-byte row pitch puts one logical chunk of 16 consecutive rows on only 4 slots).  Both tiles use
+//   chunk L ^ ((row >> 1) & 2): the halves of each 4-chunk quad swap on rows with bit 2 set.  A row moves the slot by
+//   -4 row (mod 16), which sorts a lane group's rows into 4 classes by row & 3; the swap gives the two rows of a class
+//   (r, r + 4 or r + 12) different low slot bits, and the g / g + 1 halves of a ds_read_b128 group, or the two 8-byte halves
+//   of a V read, fill the rest: 16 distinct slots per lane group (tests/test_phi3_decoder_host.py restates it).
 #include "kernels.h"
 #if U2_ELEM_IS_F16
 #include "build_f16/tokattn_pv_asm.inc"  // derived at build time: tools/asm_elem_f16.py
@@ -62,6 +68,9 @@ __device__ __forceinline__ int tv_rot(int k) {
   if constexpr (SEG == 16) return 2 * (k & 3) + 8 * ((k >> 2) & 1);
   else return 2 * ((k >> 1) & 1) + 4 * ((k >> 2) & 1);
 }
+
+// d = 96: LDS position of logical chunk L of tile row `row` (an involution: also the DMA's source chunk of position L)
+__device__ __forceinline__ int t96_pos(int row, int L) { return L ^ ((row >> 1) & 2); }
 
 typedef short ta_v4s_t __attribute__((ext_vector_type(4)));
 
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
     for (int i = 0; i < NP; ++i) {
       // (a wave instruction covers 64 consecutive chunks: one row when CPR == 64 -- its row index is then scalar)
       const int c = i * 256 + w * 64 + lane, row = CPR >= 64 ? (i * 256 + w * 64) / CPR : c / CPR, cp = c % CPR;
-      const int src_chunk = cp ^ (row & (SEG - 1));
+      const int src_chunk = DH == 96 ? t96_pos(row, cp) : cp ^ (row & (SEG - 1));
       const bf16_t* src = kb_ + (int64_t)min(kt * BK + row, Skv - 1) * a.ldk + src_chunk * 8;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(sK + (i * 256 + w * 64) * 16), 16, 0, 0);
@@ -159,7 +168,7 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int c = i * 256 + w * 64 + lane, row = CPR >= 64 ? (i * 256 + w * 64) / CPR : c / CPR, cp = c % CPR;
-      const int src_chunk = (cp & ~(SEG - 1)) | (((cp & (SEG - 1)) - tv_rot<SEG>(row)) & (SEG - 1));
+      const int src_chunk = DH == 96 ? t96_pos(row, cp) : (cp & ~(SEG - 1)) | (((cp & (SEG - 1)) - tv_rot<SEG>(row)) & (SEG - 1));
       const bf16_t* src = vb_ + (int64_t)min(kt * BK + row, Skv - 1) * a.ldv + src_chunk * 8;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(sV + (i * 256 + w * 64) * 16), 16, 0, 0);
@@ -167,9 +176,10 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
   };
 
   // ---- per-lane fragment offsets
-  // K: row 16 kb + l15, chunk (4 ks + g) ^ (row & (SEG - 1)); the XOR value does not depend on kb (16 kb keeps the low bits)
+  // K: row 16 kb + l15, chunk (4 ks + g) ^ (row & (SEG - 1)) [d = 96: ^ ((row >> 1) & 2)]; the XOR value does not depend on kb
+  // (16 kb keeps the low bits)
   const int k_row_off = l15 * ROWB;
-  const int k_swz = l15 & (SEG - 1);
+  const int k_swz = DH == 96 ? (l15 >> 1) & 2 : l15 & (SEG - 1);
   // V: rows 4 g + (l15 >> 2) (+ 16 for the second read), chunk 2 db + ((l15 & 3) >> 1) rotated, 8-byte half l15 & 1
   const int v_row = 4 * g + (l15 >> 2);
   const int v_rot = tv_rot<SEG>(v_row);
@@ -309,7 +319,7 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
 #pragma unroll
       for (int i = 0; i < NPV; ++i) {
         const int cc = 2 * (i % DB) + v_cc;
-        const int cp = (cc & ~(SEG - 1)) | (((cc & (SEG - 1)) + v_rot) & (SEG - 1));
+        const int cp = DH == 96 ? t96_pos(v_row, cc) : (cc & ~(SEG - 1)) | (((cc & (SEG - 1)) + v_rot) & (SEG - 1));
         const char* p = tV + (i / DB) * 32 * ROWB + v_base_off + cp * 16;
         const ta_v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)p);
         const ta_v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(p + 16 * ROWB));
@@ -835,7 +845,7 @@ size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d) {
 bool tok_attention_supported(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* out, int Sq, int Skv, int d,
                              int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                              int64_t o_bs, const bf16_t* rel_bias, int max_len) {
-  if (d != 64 && d != 128 && d != 256 && d != 512) return false;
+  if (d != 64 && d != 96 && d != 128 && d != 256 && d != 512) return false;
   if ((ldq | ldk | ldv | q_bs | k_bs | v_bs) & 7) return false;
   if ((ldo | o_bs) & 3) return false;
   if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 7)) return false;
@@ -905,6 +915,7 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
   if (d == 512) { if (wide) U2_TA2(512); else U2_TA(512); }
   else if (d == 256) { if (wide) U2_TA2(256); else U2_TA(256); }
   else if (d == 128) U2_TA(128);
+  else if (d == 96) U2_TA(96);
   else U2_TA(64);
 #undef U2_TA
 #undef U2_TA2

@@ -66,7 +66,7 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
         if p is not None and p.is_cuda and p.dtype in (torch.bfloat16, torch.float16):   # (either build of the library)
             from .prefill import enable_fused_prefill
-            enable_fused_prefill(self, strict=False)   # (layers of another layout -- Phi3 -- stay stock)
+            enable_fused_prefill(self, strict=False)   # (layers the kernels do not compute stay stock)
             self._u2_prefill_checked = True
 
     def forward(self, images: Optional[torch.FloatTensor] = None, input_ids: torch.LongTensor = None,
@@ -141,8 +141,10 @@ class u2Qwen3ForCausalLM(_u2CausalLMMixin, Qwen3ForCausalLM):
 
 class u2Phi3ForCausalLM(_u2CausalLMMixin, Phi3ForCausalLM):
     """language_model/u2phi3.py:25-140 (train_stage1.py:290-296, model_type "phi3").  The path in front of the decoder is the
-    same HIP path; the Phi3 decoder (fused qkv_proj / gate_up_proj modules) stays the stock HuggingFace one: the fused
-    prefill of prefill.py knows the Llama / Qwen3 layer layout only and leaves these layers alone."""
+    same HIP path; the Phi-3 decoder layers (packed qkv_proj / gate_up_proj modules, used as they are) take the fused prefill
+    and decode steps of prefill.py like the other two builds, behind the same `config.u2_fused_prefill` switch: head dim
+    96 (Phi-3-mini) or 64 / 128, SiLU, rotary over the whole head.  With `sliding_window` = W a prefill of more than W
+    positions takes the stock layers; decode steps attend over the last W positions."""
     config_class = u2Phi3Config
 
     def __init__(self, config):

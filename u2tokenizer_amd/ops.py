@@ -584,7 +584,7 @@ def tok_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
 def attention_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
                   causal: bool = True, split_keys: bool = False) -> torch.Tensor:
     """softmax(q k^T scale [+ causal mask]) v with grouped-query heads (u2tok_attention_gqa): q (nb, Sq, heads * d),
-    k / v (nb, Skv, kv_heads * d) -- views with a contiguous last dim -> (nb, Sq, heads * d).
+    k / v (nb, Skv, kv_heads * d) -- views with a contiguous last dim -> (nb, Sq, heads * d); d in {64, 96, 128, 256, 512}.
     split_keys (not causal): key ranges on separate workgroups, merged in a fixed order (u2tok_attention_gqa_split) -- few
     query rows over a long KV cache (decode steps)."""
     h = _lib.load_library()
@@ -629,7 +629,7 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-6) -> torch.Tensor
 def qk_norm_rope(qkv: torch.Tensor, q_norm_w, k_norm_w, cos: torch.Tensor, sin: torch.Tensor, heads: int, kv_heads: int,
                  head_dim: int, eps: float = 1e-6, kv_cache_seq: int = 0, kv_out=None, kv_pos: int = 0):
     """In place on the q and k heads of qkv (rows, (heads + 2 kv_heads) * head_dim): per-head RMSNorm (weights may both be
-    None: Llama) then rotary embedding with cos / sin (rows, head_dim), fp32 or bf16 (u2tok_qk_norm_rope).
+    None: Llama) then rotary embedding with cos / sin (rows, head_dim), fp32 or bf16 (u2tok_qk_norm_rope); head_dim 64 / 96 / 128.
     kv_cache_seq = S > 0 (rows = batch * S): also returns the finished keys and the values as fresh dense
     (batch, kv_heads, S, head_dim) tensors -- the KV cache's layout (u2tok_qk_norm_rope_kv): (qkv, k_cache, v_cache).
     kv_out = (k_buf, v_buf): write them instead at positions kv_pos .. kv_pos + S - 1 of (batch, kv_heads, capacity, head_dim)

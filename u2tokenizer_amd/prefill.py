@@ -18,6 +18,12 @@ DECODE step (one new position per sequence, batch <= 16, a plain HF DynamicCache
 training, CPU tensors, sliding-window layers, padded batches, other cache types -- takes the layer's original forward.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
+
+Phi-3 layers (`Phi3Attention.qkv_proj`, `Phi3MLP.gate_up_proj`: gate rows first, then up) already hold that packed layout and
+are used as they are (`_PackedLayout`).  Their configs carry `sliding_window` = W (every Phi-3-4k build: 2047; query i sees
+keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a longer prefill takes the stock layers, and a
+decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
+DynamicSlidingWindowLayer that `generate` builds for such a config.
 """
 from __future__ import annotations
 
@@ -69,18 +75,106 @@ def _ensure_gemm_scratch(device) -> None:
 _HOOK_TABLES = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
 
 
-def _is_stock(layer) -> bool:
+class _SplitLayout:
+    """Llama / Qwen3: separate q / k / v and gate / up projections, packed into one buffer each on first use."""
+    KEY = (0, 3, 4, 6)   # projections whose weights locate the packed buffers: q (q|k|v), o, gate (gate|up), down
+
+    @staticmethod
+    def projections(layer):
+        att, mlp = layer.self_attn, layer.mlp
+        return (att.q_proj, att.k_proj, att.v_proj, att.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj)
+
+    @staticmethod
+    def qkv(layer):
+        att = layer.self_attn
+        return _pack((att.q_proj, att.k_proj, att.v_proj))
+
+    @staticmethod
+    def gate_up(layer):
+        return _pack((layer.mlp.gate_proj, layer.mlp.up_proj))
+
+    @staticmethod
+    def window(layer):
+        return None
+
+    @staticmethod
+    def ready(layer, att) -> bool:
+        return getattr(att, "sliding_window", None) is None
+
+
+class _PackedLayout:
+    """Phi-3: one qkv_proj (q, k, v rows) and one gate_up_proj (gate rows, then up rows) -- the packed layout itself."""
+    KEY = (0, 1, 2, 3)
+
+    @staticmethod
+    def projections(layer):
+        return (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj, layer.mlp.down_proj)
+
+    @staticmethod
+    def qkv(layer):
+        lin = layer.self_attn.qkv_proj
+        return lin.weight, lin.bias
+
+    @staticmethod
+    def gate_up(layer):
+        lin = layer.mlp.gate_up_proj
+        return lin.weight, lin.bias
+
+    @staticmethod
+    def window(layer):
+        return getattr(layer.self_attn.config, "sliding_window", None)   # (Phi3Attention has no attribute of its own)
+
+    @staticmethod
+    def ready(layer, att) -> bool:
+        """No dropout that the fused forward would skip (training mode with resid_pdrop / attention_dropout > 0), weights as
+        one dense matrix each."""
+        for m in (layer.resid_attn_dropout, layer.resid_mlp_dropout):
+            if m.training and m.p > 0:
+                return False
+        if att.training and att.attention_dropout > 0:
+            return False
+        return att.qkv_proj.weight.is_contiguous() and layer.mlp.gate_up_proj.weight.is_contiguous()
+
+    @staticmethod
+    def supported(layer) -> bool:
+        """What the kernels compute: SiLU gate, rotary over the whole head (no partial_rotary_factor < 1, as in Phi-4-mini),
+        head dim 64 / 96 / 128 (Phi-3-mini / -3.5-mini: 96, Phi-3-medium: 128)."""
+        att = layer.self_attn
+        cfg = att.config
+        rp = getattr(cfg, "rope_parameters", None) or {}
+        prf = rp.get("partial_rotary_factor", getattr(cfg, "partial_rotary_factor", 1.0))
+        return (getattr(cfg, "hidden_act", None) == "silu" and float(prf if prf is not None else 1.0) == 1.0
+                and att.head_dim in (64, 96, 128))
+
+
+def _layout_of(layer):
+    """_SplitLayout / _PackedLayout for a decoder layer of a layout the fused forward runs, else None."""
+    if not all(hasattr(layer, a) for a in ("self_attn", "mlp", "input_layernorm", "post_attention_layernorm")):
+        return None
+    att, mlp = layer.self_attn, layer.mlp
+    if not all(hasattr(att, a) for a in ("o_proj", "head_dim", "scaling")) or not hasattr(mlp, "down_proj"):
+        return None
+    if all(hasattr(att, a) for a in ("q_proj", "k_proj", "v_proj")) and all(hasattr(mlp, a) for a in ("gate_proj", "up_proj")):
+        return _SplitLayout
+    if hasattr(att, "qkv_proj") and hasattr(mlp, "gate_up_proj") and hasattr(att, "config") \
+            and hasattr(layer, "resid_attn_dropout") and hasattr(layer, "resid_mlp_dropout") and _PackedLayout.supported(layer):
+        return _PackedLayout
+    return None
+
+
+def _is_stock(layer, projections=None) -> bool:
     """The fused forwards read the projections' `.weight` / `.bias` and never CALL the submodules.  That is only the same
     computation while every projection is exactly torch.nn.Linear and nothing hangs on the modules that are skipped: a
     peft lora.Linear exposes `.weight` as its BASE weight (the reference trains the decoder with LoRA, train_stage1.py:342-353:
     an unmerged adapter would be silently ignored), forward hooks (output_attentions recorders, activation probes) would not
-    fire.  Checked on every call: adapters and hooks come and go after enable_fused_prefill."""
-    att, mlp = layer.self_attn, layer.mlp
-    for m in (att.q_proj, att.k_proj, att.v_proj, att.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
+    fire.  Checked on every call: adapters and hooks come and go after enable_fused_prefill.  (`projections`: the layout's
+    projection modules when the caller has them already -- module attribute reads are what this costs per layer and step.)"""
+    if projections is None:
+        projections = layer._u2_prefill["layout"].projections(layer)
+    for m in projections:
         if type(m) is not torch.nn.Linear:
             return False
-    for m in (att.q_proj, att.k_proj, att.v_proj, att.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj, att, mlp,
-              layer.input_layernorm, layer.post_attention_layernorm):
+    for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
         for t in _HOOK_TABLES:
             if getattr(m, t, None):
                 return False
@@ -89,23 +183,28 @@ def _is_stock(layer) -> bool:
 
 def _layer_forward(self, hidden_states, *args, **kwargs):
     st = self._u2_prefill
+    lo = st["layout"]
     x = hidden_states
     pe = kwargs.get("position_embeddings")
     cache = kwargs.get("past_key_values")
     att = self.self_attn
+    pr = lo.projections(self)
     # `past_key_value` (singular) is the layer protocol of transformers 4.46 .. 4.5x, whose layers also return tuples: never
     # patched (enable_fused_prefill checks the signature), and a caller that passes it anyway gets the stock layer
     common = (not args and "past_key_value" not in kwargs and not kwargs.get("output_attentions")
               and not torch.is_grad_enabled() and x.is_cuda and x.dtype in ops.ELEM_OF and x.dim() == 3
-              and att.q_proj.weight.dtype == x.dtype      # (bf16 weights under an fp16 autocast hand fp16 activations on: stock layers)
-              and pe is not None and st["owner"]._u2_prefill_mask_ok and _is_stock(self)
-              and getattr(att, "sliding_window", None) is None and att.head_dim in (64, 128))
+              and pr[0].weight.dtype == x.dtype      # (bf16 weights under an fp16 autocast hand fp16 activations on: stock layers)
+              and pe is not None and pe[0].shape[-1] == att.head_dim and st["owner"]._u2_prefill_mask_ok and _is_stock(self, pr)
+              and lo.ready(self, att) and att.head_dim in (64, 96, 128))
+    W = lo.window(self) if common else None
     if common and x.shape[1] == 1 and x.shape[0] <= 16 and st["owner"]._u2_fused_decode \
-            and _plain_dynamic_layer(cache, att.layer_idx) is not None:
-        out = _decode_step(self, x, pe, cache)
+            and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None:
+        out = _decode_step(self, x, pe, cache, W, pr)
         if out is not None:
             return out
-    fused = common and x.shape[1] > 1 and (cache is None or cache.get_seq_length(att.layer_idx) == 0)
+    # (a prefill longer than the window would need the band inside the attention kernel: stock layers)
+    fused = common and x.shape[1] > 1 and (W is None or x.shape[1] <= W) \
+        and (cache is None or cache.get_seq_length(att.layer_idx) == 0)
     if not fused:
         return st["orig"](hidden_states, *args, **kwargs)
     B, S, E = x.shape
@@ -114,8 +213,8 @@ def _layer_forward(self, hidden_states, *args, **kwargs):
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     _ensure_gemm_scratch(x.device)
     with ops.on_device(x):
-        Wqkv, bqkv = _pack((att.q_proj, att.k_proj, att.v_proj))
-        Wgu, bgu = _pack((self.mlp.gate_proj, self.mlp.up_proj))
+        Wqkv, bqkv = lo.qkv(self)
+        Wgu, bgu = lo.gate_up(self)
         x2 = x.reshape(rows, E)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
@@ -199,36 +298,44 @@ def _append_layer_class():
     return _APPEND_LAYER
 
 
-def _plain_dynamic_layer(cache, layer_idx: int):
+def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False):
     """The cache layer if `cache` is a plain HF DynamicCache (no offloading) whose layer `layer_idx` is a non-empty DynamicLayer
-    -- the case the fused decode step handles (its `update` is a torch.cat: dense (B, H_kv, T, d) tensors come back)."""
+    -- the case the fused decode step handles (its `update` is a torch.cat: dense (B, H_kv, T, d) tensors come back).
+    sliding=True (a layer with an attention window): a DynamicSlidingWindowLayer is taken as well."""
     try:
         from transformers.cache_utils import DynamicCache, DynamicLayer
     except ImportError:
         return None
+    kinds = (DynamicLayer, _APPEND_LAYER)
+    if sliding:
+        try:
+            from transformers.cache_utils import DynamicSlidingWindowLayer
+            kinds = kinds + (DynamicSlidingWindowLayer,)
+        except ImportError:
+            pass
     layers = getattr(cache, "layers", None)
     if type(cache) is not DynamicCache or not isinstance(layers, list) or getattr(cache, "offloading", False) \
             or layer_idx >= len(layers):
         return None
     lay = layers[layer_idx]
-    return lay if type(lay) in (DynamicLayer, _APPEND_LAYER) and lay.get_seq_length() > 0 else None
+    return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
 
 
-def _decode_state(self, B: int, device):
+def _decode_state(self, B: int, device, pr):
     """Per-layer constants of the decode step (weight pointers of the packed projections, the config struct), rebuilt when a
     weight moved; per-model scratch (workspace, q|k|v row, new cache entries) shared by all layers."""
     import ctypes as C
     from . import _lib
     st = self._u2_prefill
+    lo = st["layout"]
     att, mlp = self.self_attn, self.mlp
-    key = (att.q_proj.weight.data_ptr(), mlp.gate_proj.weight.data_ptr(), att.o_proj.weight.data_ptr(),
-           mlp.down_proj.weight.data_ptr(), B)
+    key = tuple(pr[i].weight.data_ptr() for i in lo.KEY) + (B,)
     d = st.get("dec")
     if d is None or d["key"] != key:
         cfg = att.config
         Hq, Hkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
-        Wqkv, bqkv = _pack((att.q_proj, att.k_proj, att.v_proj))
-        Wgu, bgu = _pack((mlp.gate_proj, mlp.up_proj))
+        Wqkv, bqkv = lo.qkv(self)
+        Wgu, bgu = lo.gate_up(self)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
         E, inter = Wqkv.shape[1], Wgu.shape[0] // 2
         c = _lib.DecodeConfig(B=B, E=E, Hq=Hq, Hkv=Hkv, D=hd, I=inter, eps=float(self.input_layernorm.variance_epsilon),
@@ -262,17 +369,19 @@ def _decode_state(self, B: int, device):
     return d, sc
 
 
-def _decode_step(self, x, pe, cache):
+def _decode_step(self, x, pe, cache, window=None, pr=None):
     """One decode step of a layer (B <= 16 new tokens, one each, against the KV cache): the step `generate` repeats up to 768
     times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
     few-rows GEMM (gemm.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
     fused kernel with the KEYS split over workgroups (batch x kv-head entries of (T, d) keys, the query heads of a group as its
     heads).  TWO library calls per layer (u2tok_decoder_decode_pre / _post, 10 launches) around the cache's own `update`: with a
-    Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels)."""
+    Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels).
+    window = W (a sliding-window layer): the query attends over the last min(T, W) positions -- an offset into the cache
+    buffers, the same kernels."""
     from . import _lib
     att = self.self_attn
     B, _, E = x.shape
-    d, sc = _decode_state(self, B, x.device)
+    d, sc = _decode_state(self, B, x.device, self._u2_prefill["layout"].projections(self) if pr is None else pr)
     if not d["ok"]:
         return None                                   # (the caller takes the stock layer)
     hd = d["hd"]
@@ -304,8 +413,11 @@ def _decode_step(self, x, pe, cache):
                                                   kb.data_ptr(), vb.data_ptr(), kb.stride(1), T0, ws, nws, stream),
                        "u2tok_decoder_decode_pre")
             lay._commit(T0 + 1)
-            _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), kb.data_ptr(), vb.data_ptr(),
-                                                   T0 + 1, kb.stride(1), *d["post"], out.data_ptr(), ws, nws, stream),
+            Kw, Vw = kb[:, :, :T0 + 1], vb[:, :, :T0 + 1]
+            if window is not None:
+                Kw, Vw = Kw[:, :, -window:], Vw[:, :, -window:]
+            _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), Kw.data_ptr(), Vw.data_ptr(),
+                                                   Kw.shape[2], kb.stride(1), *d["post"], out.data_ptr(), ws, nws, stream),
                        "u2tok_decoder_decode_post")
             return out
         _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], x2.data_ptr(), *d["pre"], cos.data_ptr(), sin.data_ptr(),
@@ -317,8 +429,11 @@ def _decode_step(self, x, pe, cache):
             K = K.contiguous()
         if not V.is_contiguous():
             V = V.contiguous()
+        kvs = 0
+        if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
+            K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
         _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
-                                               K.shape[2], 0, *d["post"], out.data_ptr(), ws, nws, stream),
+                                               K.shape[2], kvs, *d["post"], out.data_ptr(), ws, nws, stream),
                    "u2tok_decoder_decode_post")
     return out
 
@@ -362,7 +477,7 @@ def _mask_hook(module, args, kwargs):
 _warned_protocol = [False]
 
 
-def _layer_protocol_ok(layer) -> bool:
+def _layer_protocol_ok(layer, base=None) -> bool:
     """_layer_forward is written against the decoder-layer protocol of transformers >= 4.56 / 5.x: the cache arrives as the
     keyword `past_key_values`, rotary tables as `position_embeddings`, and the layer returns the hidden-state TENSOR.  From
     4.46 (the reference's pin) up to that change the keyword is `past_key_value` and layers return tuples: there the cache
@@ -374,7 +489,12 @@ def _layer_protocol_ok(layer) -> bool:
         ok = "past_key_values" in sig.parameters and "position_embeddings" in sig.parameters
         ret = sig.return_annotation
         if ok and ret is not inspect.Signature.empty and "tuple" in str(ret).lower():
-            ok = False
+            # (Phi3DecoderLayer of transformers 5.x still announces a tuple and returns the tensor: the decoder stack that
+            #  assigns the layer's result to its hidden states is the evidence)
+            try:
+                ok = base is not None and "hidden_states = decoder_layer(" in inspect.getsource(type(base).forward)
+            except (TypeError, OSError):
+                ok = False
     except (TypeError, ValueError):
         ok = False
     if not ok and not _warned_protocol[0]:
@@ -386,28 +506,27 @@ def _layer_protocol_ok(layer) -> bool:
 
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True) -> int:
-    """Patch the decoder layers of an HF Llama / Qwen3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM included) for the
-    fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number of layers patched.  strict=False: a
-    decoder layer of another layout is skipped instead of refused.
+    """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
+    u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
+    of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
+    activation, partial rotary, a head dim outside 64 / 96 / 128) -- is skipped instead of refused.
     `disable_fused_prefill` restores the stock forwards."""
     base = model.get_model() if hasattr(model, "get_model") else getattr(model, "model", model)
     layers = getattr(base, "layers", None)
     if layers is None:
-        raise RuntimeError("enable_fused_prefill: no decoder layers found (expected an HF Llama / Qwen3 model)")
+        raise RuntimeError("enable_fused_prefill: no decoder layers found (expected an HF Llama / Qwen3 / Phi-3 model)")
     n = 0
     for layer in layers:
         if hasattr(layer, "_u2_prefill"):
             continue
-        needed = all(hasattr(layer, a) for a in ("self_attn", "mlp", "input_layernorm", "post_attention_layernorm")) and \
-            all(hasattr(layer.self_attn, a) for a in ("q_proj", "k_proj", "v_proj", "o_proj", "head_dim", "scaling")) and \
-            all(hasattr(layer.mlp, a) for a in ("gate_proj", "up_proj", "down_proj"))
-        if not needed:
+        layout = _layout_of(layer)
+        if layout is None:
             if strict:
                 raise RuntimeError(f"enable_fused_prefill: unsupported decoder layer {type(layer).__name__}")
-            continue   # (another layer layout, e.g. Phi3's fused qkv_proj / gate_up_proj: stays stock)
-        if not _layer_protocol_ok(layer):
+            continue   # (another layer layout: stays stock)
+        if not _layer_protocol_ok(layer, base):
             continue
-        layer._u2_prefill = {"orig": layer.forward, "owner": base}
+        layer._u2_prefill = {"orig": layer.forward, "owner": base, "layout": layout}
         layer.forward = types.MethodType(_layer_forward, layer)
         n += 1
     base._u2_fused_decode = bool(decode)
