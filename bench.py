@@ -20,11 +20,17 @@ elapsed / steps, i.e. the reciprocal of the throughput, and `ms_per_step_one_str
 --dump-outputs DIR writes what the last timed step computed (inputs_embeds, float32) to DIR/*.npy: weights and inputs
 come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  Everything that takes runs of its own comes after the timed steps and only with --full (each leg
+can still be switched off there by its --no-* option):
+  value_one_stream    -- the same steps issued on ONE stream (ms_per_step_one_stream: the latency of one volume).
   roofline            -- the dominant kernel class (bf16 MFMA GEMM): algorithmic FLOPs of its launches in one step /
                          their summed HIP-event durations on the launch stream (instrumented one-stream pass after the
                          timed region; the timed region itself carries no events), vs 2.5 PFLOP/s.
   roofline_attention  -- the same for the ViT flash-attention kernel (north_star's ">= 40 % MFMA" target).
+  kernel_table        -- per-kernel durations from a rocprofv3 child of this command; `traffic` from two PMC children.
+  train_step, batched_calls, train_step_full, decoder_after_path -- the training form of the path, batch 4, a whole
+                         stage-1 step and the decoder behind the path (the last three in child processes), N = 1 only.
   cpu_baseline        -- the CPU oracle (oracle/u2_oracle.py) on the host cores: fp32 and bf16, 1 warm-up + 3 timed
                          iterations per stage on a bounded sample (1 of 8 chunks through ViT + SPP, 1 of 4 layers of
                          SVR and TTA, selection / pooling / aggregation in full), rank 0, N = 1 only.
@@ -243,7 +249,7 @@ def measure_kernels(E, options, timeout=300):
     try:
         cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "k", "--",
                sys.executable, str(Path(__file__).resolve()), "--steps", "6", "--warmup", "1", "--repeats", "1",
-               "--streams", "1", "--hidden", str(E), "--no-cpu-baseline", "--no-roofline", "--no-train-step"]
+               "--streams", "1", "--hidden", str(E)]
         for o in options:
             cmd += ["--option", o]
         r = subprocess.run(cmd, cwd="/tmp", env=_child_env(), capture_output=True, text=True, timeout=timeout)
@@ -322,7 +328,7 @@ def measure_traffic(E, timeout=240):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", os.path.join(tmp, ctr), "-o", "p", "--",
                    sys.executable, str(Path(__file__).resolve()), "--steps", "2", "--warmup", "1", "--repeats", "1",
-                   "--streams", "1", "--hidden", str(E), "--no-cpu-baseline", "--no-roofline", "--no-train-step"]
+                   "--streams", "1", "--hidden", str(E)]
             r = subprocess.run(cmd, cwd="/tmp", env=_child_env(), capture_output=True, text=True, timeout=timeout)
             if r.returncode != 0:
                 return None
@@ -384,7 +390,7 @@ def batched_throughput(E, options, batch=4, timeout=240):
     try:
         torch.cuda.empty_cache()
         cmd = [sys.executable, str(Path(__file__).resolve()), "--batch", str(batch), "--streams", "2", "--steps", "10", "--warmup", "2",
-               "--repeats", "3", "--hidden", str(E), "--no-cpu-baseline", "--no-roofline", "--no-train-step"]
+               "--repeats", "3", "--hidden", str(E)]
         for o in options:
             cmd += ["--option", o]
         r = subprocess.run(cmd, env=_child_env(), capture_output=True, text=True, timeout=timeout)
@@ -509,10 +515,16 @@ def main():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the steps are issued on round-robin (2 = two volumes in flight per GPU: the small "
                          "launches of one volume's tokenizer fill the machine under the other volume's large GEMMs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the forward + backward timing of the training path")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two live rocprofv3 PMC passes behind roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the one-stream run, the roofline objects with their kernel "
+                         "table and traffic, the training / batched / decoder legs and the CPU baseline (a plain run prints "
+                         "the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline objects and the kernel table")
+    ap.add_argument("--no-train-step", action="store_true",
+                    help="with --full: skip the training, batched-call and decoder legs")
+    ap.add_argument("--no-traffic", action="store_true",
+                    help="with --full: skip the rocprofv3 children behind roofline.traffic and the kernel table")
     ap.add_argument("--cpu-baseline-iters", type=int, default=3)
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="library tuning switch for A/B measurements (u2tok_set_option), e.g. --option flash_mode=7")
@@ -599,9 +611,9 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, out, rank, world)
 
-    # the same K steps issued on ONE stream (one volume in flight): the latency of a volume
+    # --full: the same K steps issued on ONE stream (one volume in flight): the latency of a volume
     single = None
-    if streams is not None:
+    if streams is not None and args.full:
         t1, _ = timed_repeats(lambda i: step(i, multi=False), args.steps, args.warmup, max(1, args.repeats // 2), sync, rmax)
         single = statistics.median(t1)
 
@@ -616,7 +628,7 @@ def main():
                     "ms_per_step_max": max(per_step), "value_is": "median repeat"},
         "tokens_per_s": round(value * Q, 1),
         "in_flight": (f"{args.streams} volumes per GPU on {args.streams} HIP streams: ms_per_step = elapsed / steps is the "
-                      "reciprocal of the throughput, NOT the latency of a volume (that is ms_per_step_one_stream)"
+                      "reciprocal of the throughput, NOT the latency of a volume (that is ms_per_step_one_stream, --full)"
                       if streams is not None else "1 volume per GPU"),
         "value_one_stream": round(world * B * args.steps / single, 3) if single else None,
         "ms_per_step_one_stream": round(1e3 * single / args.steps, 4) if single else None,
@@ -630,7 +642,7 @@ def main():
     if args.stub_cpu:
         line.update({"data": "stub (launcher self-test, no GPU work)", "valid": False})
 
-    if rank == 0 and not args.no_roofline and not args.stub_cpu:
+    if args.full and rank == 0 and not args.no_roofline and not args.stub_cpu:
         import ctypes as C
         ops.set_option("profile", 1)
         nprof = 3
@@ -770,17 +782,17 @@ def main():
                               "note": "algorithmic bytes (q, k, v read once, o written once) / average launch duration; the key-split "
                                       "launches add fp32 partial sums on top (`traffic`)"}
             line["roofline_tokenizer_attention"] = ta
-    if rank == 0 and world == 1 and not args.no_train_step and not args.stub_cpu and B == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_train_step and not args.stub_cpu and B == 1:
         # SURVEY 8f rank 1 (built in round 2): a measured line for the training form of the path, after the timed region
         try:
             line["train_step"] = train_step(path, ids, qids, vols[0], E)
         except Exception as e:  # never lose the inference line to the extra
             line["train_step"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and world == 1 and not args.no_train_step and not args.stub_cpu and B == 1 and E == 4096:
+    if args.full and rank == 0 and world == 1 and not args.no_train_step and not args.stub_cpu and B == 1 and E == 4096:
         line["batched_calls"] = batched_throughput(E, args.option)
         line["train_step_full"] = train_step_full()
         line["decoder_after_path"] = decoder_after_path()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_cpu:
         line["cpu_baseline"] = cpu_baseline(E, Lt, iters=args.cpu_baseline_iters)
     if rank == 0:
         print(json.dumps(line), flush=True)

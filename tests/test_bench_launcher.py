@@ -47,6 +47,14 @@ def test_single_rank_stub():
     assert j["n_gpus"] == 1 and "roofline" not in j and "cpu_baseline" not in j
 
 
+def test_full_option_keeps_the_headline():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--stub-cpu"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    j = _line(r.stdout)
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "volumes/s" and j["higher_is_better"] is True
+
+
 def test_dump_outputs_writes_the_last_step(tmp_path):
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "0", "--stub-cpu",
                         "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Prints the kernel table of a bench.py JSON line (stdin or file): per kernel launches / volume, average us, ms per volume."""
+"""Prints the kernel table of a `bench.py --full` JSON line (stdin or file): per kernel launches / volume, average us, ms per volume."""
 import json
 import sys
 for ln in (open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin):
