@@ -77,14 +77,6 @@ int u2tok_set_option(const char* name, int value);
  * current context: skinny products (few output tiles, long K) are cut along K when a scratch is registered; NULL / 0
  * removes it.  The module forwards below carve their own from their workspace and do not need this. */
 int u2tok_set_gemm_scratch(void* device_ptr, size_t bytes, void* stream);
-/* Diagnostics only, process-wide (not for concurrent use): device buffer (>= grid*4*8 uint64, zeroed by the caller)
- * for the flash attention kernel; while attached the kernel runs its s_memtime-instrumented build and ADDS per-phase
- * cycle sums per (workgroup, wave). */
-int u2tok_flash_debug_buffer(void* device_ptr);
-/* Same for u2tok_tok_attention: >= grid*4*8 uint64 (grid*8*16 for the 8-wave form of head dims 256 / 512, which also leaves s_memrealtime stamps in slots 8..15); slots = cycles in
- * {DMA wait, barrier, K DMA issue (8-wave form: all DMA issue), Q K^T, softmax, V DMA issue (8-wave form: unused), P V},
- * [7] = tiles. */
-int u2tok_tok_attention_debug_buffer(void* device_ptr);
 
 /* With option "profile" = 1 every launch is bracketed by hipEvents on its stream.  Collect (HOST arrays of ncat <= 6
  * entries; synchronises on the recorded events, then resets): summed milliseconds, algorithmic FLOPs and launch

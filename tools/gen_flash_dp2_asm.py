@@ -36,7 +36,6 @@ import sys
 EXACT = "--exact" in sys.argv   # Q fragments as given; every score is multiplied by scale * log2 e in fp32 (2 more VALU per slot)
 SHARE = "--no-share" not in sys.argv     # the two query blocks of a wave read each K / V^T fragment from LDS once (8 live tuples)
 DMAPH = "--no-dmaphase" not in sys.argv  # next tile's LDS-DMA pieces issued from MFMA slots of the phase behind the barrier
-TIMED = "--timed" in sys.argv   # diagnostics build: s_memtime deltas of the loop sections -> 5 x uint64 at %[dbg]
 PF = 3          # fragment reads in flight
 NSLOT = 4       # LDS ring slots (16 KB each: K tile 8 KB | V^T tile 8 KB)
 AHEAD = 3       # tiles in flight
@@ -66,8 +65,7 @@ VHI = 255
 # ---- fixed SGPRs -------------------------------------------------------------------------------------------------
 S_T, S_ISSUE, S_NV, S_A, S_B, S_KOFF, S_VOFF, S_AV = range(36, 44)
 S_RA = 44                            # 64-bit return address of the out-of-line pieces
-S_NOW, S_PREV, S_ACC = 46, 48, 50    # TIMED: now, prev, 5 accumulators (50..59)
-SLO, SHI = 36, 59 if TIMED else 45
+SLO, SHI = 36, 45
 
 out = []
 uid = [0]
@@ -117,22 +115,6 @@ def m_run(b):
 
 def l_run(b):
     return f"%[lr{b}]"
-
-
-def stamp(i):
-    """adds the time since the previous stamp to accumulator i (only at points where no LDS read is in flight)"""
-    if not TIMED:
-        return
-    e(f"s_memtime s[{S_NOW}:{S_NOW + 1}]")
-    e("s_waitcnt lgkmcnt(0)")
-    lds_drained()
-    if i is not None:
-        a = S_ACC + 2 * i
-        e(f"s_sub_u32 {s(S_A)}, {s(S_NOW)}, {s(S_PREV)}")
-        e(f"s_subb_u32 {s(S_B)}, {s(S_NOW + 1)}, {s(S_PREV + 1)}")
-        e(f"s_add_u32 {s(a)}, {s(a)}, {s(S_A)}")
-        e(f"s_addc_u32 {s(a + 1)}, {s(a + 1)}, {s(S_B)}")
-    e(f"s_mov_b64 s[{S_PREV}:{S_PREV + 1}], s[{S_NOW}:{S_NOW + 1}]")
 
 
 def call(label):
@@ -479,10 +461,6 @@ def gen():
     mask_call(1)
     init_max(1)
     # ---- tile loop, unrolled over the ring slots
-    if TIMED:
-        for i in range(5):
-            e(f"s_mov_b64 s[{S_ACC + 2 * i}:{S_ACC + 2 * i + 1}], 0")
-    stamp(None)
     e(".p2align 6")
     e(".Lfd2_loop_%=:")
     for j in range(NSLOT):
@@ -496,7 +474,6 @@ def gen():
         mask_call(0)
         phase(1, True, True, True, base + 4096, base + 8192, 0, reuse=SHARE)
         mask_call(1)
-        stamp(0)
         e(f"s_add_u32 {s(S_A)}, {s(S_T)}, 1")
         e(f"s_cmp_eq_u32 {s(S_A)}, %[ntile]")
         e(f"s_mov_b32 {s(S_AV)}, {base + 8192}")
@@ -513,12 +490,9 @@ def gen():
             e(f".Lfd2_lw4_{j}_%=:")
             e("s_waitcnt vmcnt(4)")
             e(f".Lfd2_lw_{j}_%=:")
-        stamp(1)
         e("s_barrier")
-        stamp(2)
         if not DMAPH:
             issue((j + AHEAD) % NSLOT, f"loop{j}")
-        stamp(3)
         e(f"s_sub_i32 {s(S_NV)}, {s(S_NV)}, 32")              # half 2t+2
         # K rows 0..31 of tile t+1 (next slot); V^T tile t, keys 32..63 (vh = 1)
         phase(0, True, True, True, nxt, base + 8192, 1, dma=(j + AHEAD) % NSLOT if DMAPH else None)
@@ -527,7 +501,6 @@ def gen():
         # pieces stay in the reading phase above: moved here they measured 2677 -> 2714 cycles per tile)
         phase(1, True, True, True, nxt, base + 8192, 1, reuse=SHARE, prefetch=(nxt + 4096, nxt + 8192, 0) if PRE else None)
         mask_call(1)
-        stamp(4)
         e(f"s_add_u32 {s(S_T)}, {s(S_T)}, 1")
     e("s_branch .Lfd2_loop_%=")
     # ---- epilogue: the last half (tile ntile-1, keys 32..63): its V^T tile is at LDS offset S_AV
@@ -545,13 +518,6 @@ def gen():
             e(f"ds_write_b128 %[dump], {vr(O[key] + 4 * j, 4)} offset:{q * 1024}")
             q += 1
     e("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    if TIMED:
-        for i in range(5):
-            a = S_ACC + 2 * i
-            e(f"v_mov_b32 {v(TT[0][0])}, {s(a)}")
-            e(f"v_mov_b32 {v(TT[0][1])}, {s(a + 1)}")
-            e(f"global_store_dwordx2 %[dbg], {vr(TT[0][0], 2)}, off offset:{8 * i}")
-        e("s_waitcnt vmcnt(0)")
     # the lane id again, as an OUTPUT: what the C++ epilogue derives from it cannot be hoisted above the block and
     # kept alive across it (the compiler only has the registers below VLO there)
     e("v_mbcnt_lo_u32_b32 %[lid], -1, 0")
@@ -566,7 +532,7 @@ def gen():
 
 
 gen()
-sfx = ("_X" if EXACT else "") + ("" if SHARE else "_NS") + ("" if DMAPH else "_ND") + ("_TIMED" if TIMED else "")
+sfx = ("_X" if EXACT else "") + ("" if SHARE else "_NS") + ("" if DMAPH else "_ND")
 print("// clang-format off")
 print(f"#define FLASH_DP2_ASM_TEXT{sfx} \\")
 body = [l for l in out if not l.startswith("//")]

@@ -443,83 +443,6 @@ def _flash_ref(qkv, H):
     return (p @ x[2]).permute(0, 2, 1, 3).reshape(nb, S, H * 64)
 
 
-def flash_timeline(buf, split):
-    """modes 7 / 8, TIMED build: wall-clock (100 MHz) stamps per wave: [0] entry, [1] before the KV loop, [2] after it,
-    [3] exit; the first region of the buffer has the number of key tiles the wave walked in [7]"""
-    n = 2048 * 4
-    t = buf[65536:65536 + n * 8].view(-1, 8).cpu().double()
-    tiles = buf[:n * 8].view(-1, 8).cpu().double()[:, 7]
-    ok = t[:, 0] > 0
-    t, tiles = t[ok], tiles[ok]
-    t0 = t[:, 0].min()
-    us = lambda x: (x - t0) / 100.0
-    ent, pre, post, ex = us(t[:, 0]), us(t[:, 1]), us(t[:, 2]), us(t[:, 3])
-    main = t[:, 1] > 0
-    print(f"  timeline (us from the first workgroup's entry; {int(main.sum())} main waves, {int((~main).sum())} extra-row waves)")
-    tmax = tiles[main].max()
-    groups = [("whole units, entry < 5 us", main & (tiles == tmax) & (ent < 5.0)), ("whole units, later", main & (tiles == tmax) & (ent >= 5.0)),
-              ("half units", main & (tiles < tmax))]
-    for name, sel in groups:
-        if sel.sum() == 0:
-            continue
-        e_, p_, q_, x_ = ent[sel], pre[sel], post[sel], ex[sel]
-        print(f"    {name}: {int(sel.sum())} waves | entry {e_.min():6.1f}..{e_.max():6.1f} | prologue {(p_ - e_).mean():5.2f} (max {(p_ - e_).max():5.2f}) | "
-              f"KV loop {(q_ - p_).mean():6.2f} (min {(q_ - p_).min():6.2f} max {(q_ - p_).max():6.2f}) | epilogue {(x_ - q_).mean():5.2f} (max {(x_ - q_).max():5.2f}) | "
-              f"exit {x_.min():6.1f}..{x_.max():6.1f}")
-    # first-round whole units by XCD (workgroup w runs on XCD w % 8): is the spread of the loop times systematic?
-    widx = torch.arange(n)[ok] // 4
-    sel = groups[0][1]
-    if sel.sum():
-        loop = (post - pre)
-        per_xcd = [loop[sel & ((widx & 7) == x)].mean().item() for x in range(8)]
-        print("    first round, KV loop by XCD: " + "  ".join(f"{v:5.1f}" for v in per_xcd) +
-              f" | spread inside a workgroup (max - min of its 4 waves), mean: "
-              f"{(loop[sel].view(-1, 4).max(1).values - loop[sel].view(-1, 4).min(1).values).mean().item():4.2f}")
-    if (~main).sum():
-        e_, x_ = ent[~main], ex[~main]
-        print(f"    extra-row workgroups: entry {e_.min():6.1f}..{e_.max():6.1f}, duration {(x_ - e_).mean():5.2f} (max {(x_ - e_).max():5.2f}), last exit {x_.max():6.1f}")
-        tx = t[~main]
-        if (tx[:, 4] > 0).all():
-            sc, sm, pv = (tx[:, 4] - tx[:, 0]) / 100, (tx[:, 5] - tx[:, 4]) / 100, (tx[:, 3] - tx[:, 5]) / 100
-            print(f"      of which scores {sc.mean():5.2f}  softmax {sm.mean():5.2f}  P V + store {pv.mean():5.2f} us")
-    print(f"    kernel span by these stamps: {ex.max():6.1f} us")
-
-
-def sec_flashtime():
-    """s_memtime phase breakdown of the flash attention kernel (cycles per KV tile per wave)"""
-    from u2tokenizer_amd import _lib
-    h = _lib.load_library()
-    nb, S, H = 8, 2049, 12
-    qkv = rnd(nb, S, 3 * H * 64, seed=3).to(dev)
-    names = ["gload", "QK^T", "softmax", "PV", "wait+lstore", "-", "barrier"]
-    for mode, split in ((7, 0), (7, 1)):
-        ops.set_option("flash_mode", mode)
-        ops.set_option("flash_q_prescaled", split)
-        ms0 = timeit(lambda: ops.flash_attention_d64(qkv, H, 0.125, extra_last=True), iters=5)
-        buf = torch.zeros(65536 + 2048 * 4 * 8, dtype=torch.int64, device=dev)
-        _lib.check(h.u2tok_flash_debug_buffer(buf.data_ptr()), "flash_debug_buffer")
-        ops.flash_attention_d64(qkv, H, 0.125, extra_last=True)
-        torch.cuda.synchronize()
-        h.u2tok_flash_debug_buffer(None)
-        r = buf.view(-1, 8).double()
-        r = r[r[:, 7] > 0]
-        per = r[:, :7].sum(0) / r[:, 7].sum()
-        if mode == 7:
-            flash_timeline(buf, split)
-        if mode % 10 in (5, 7):
-            print(f"  mode {mode} q_prescaled {split}: {ms0 * 1e3:7.1f} us untimed | per 64-key tile per wave (2 blocks): phases u=2t {per[0]:6.0f}  dma wait {per[1]:6.0f}  "
-                  f"barrier {per[2]:6.0f}  dma issue {per[3]:6.0f}  phases u=2t+1 {per[4]:6.0f}  total {per[:5].sum():6.0f}", flush=True)
-            continue
-        if mode % 10 == 4:
-            print(f"  mode {mode} q_prescaled {split}: {ms0 * 1e3:7.1f} us untimed | per KV tile per wave: V {per[0]:6.0f}  wait {per[1]:6.0f}  M {per[2]:6.0f}  "
-                  f"wait {per[3]:6.0f}  total {per[:4].sum():6.0f}", flush=True)
-            continue
-        print(f"  mode {mode} q_prescaled {split}: {ms0 * 1e3:7.1f} us untimed | per KV tile per wave: " +
-              "  ".join(f"{n} {v:6.0f}" for n, v in zip(names, per.tolist()) if n != "-") + f"  total {per.sum():6.0f}", flush=True)
-    ops.set_option("flash_mode", 0)
-    ops.set_option("flash_q_prescaled", 0)
-
-
 def sec_preperf():
     """u2tok_preprocess_volume (u2Transform.adaptive_resize on the GPU) vs the CPU oracle, 512 x 512 x 200 CT-like volume"""
     import numpy as np

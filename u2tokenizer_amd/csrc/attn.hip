@@ -191,18 +191,9 @@ struct FlashArgs {
 
 constexpr float FLASH_RESCALE_THR = 8.0f;
 
-__device__ unsigned long long* g_flash_dbg;  // diagnostics: TIMED builds add s_memtime deltas per phase here
-
-template <int QB, bool TIMED = false>
+template <int QB>
 __device__ __forceinline__ void flash_pass(const FlashArgs& a, char (*lds)[16384], const int b, const int h, const int row0,
                                            const int tid) {
-  unsigned long long ts[7] = {0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define U2_STAMP(i_)                                                   \
-  if constexpr (TIMED) {                                               \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();        \
-    ts[i_] += t_ - tprev;                                              \
-    tprev = t_;                                                        \
-  }
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5, l31 = lane & 31;
@@ -271,12 +262,9 @@ __device__ __forceinline__ void flash_pass(const FlashArgs& a, char (*lds)[16384
   for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[qb][ks]));
-  if constexpr (TIMED) tprev = __builtin_amdgcn_s_memtime();
   for (int t = 0; t < ntile; ++t) {
     const int st = t & 1;
-    U2_STAMP(6)  // loop overhead + wait at the barrier
     if (t + 1 < ntile) U2_FLASH_GLOAD(t + 1);
-    U2_STAMP(0)  // global load issue
     if (wave_active) {
       const char* sK = lds[st];
       const char* sV = lds[st] + 8192;
@@ -296,11 +284,6 @@ __device__ __forceinline__ void flash_pass(const FlashArgs& a, char (*lds)[16384
             sc[qb][kbk] = mfma32(kf, qf[qb][ks], sc[qb][kbk]);
         }
       }
-      if constexpr (TIMED) {
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) asm volatile("" : "+v"(sc[qb][0]), "+v"(sc[qb][1]));  // S^T complete
-      }
-      U2_STAMP(1)  // K fragment reads + QK^T MFMAs
       // lane owns keys kv = t*64 + kbk*32 + (r&3) + 8*(r>>2) + 4*hi ; only the last tile can be partial
       if (t == ntile - 1 && (S & 63)) {
         const int kvb = t * 64 + 4 * hi;
@@ -343,11 +326,6 @@ __device__ __forceinline__ void flash_pass(const FlashArgs& a, char (*lds)[16384
           }
         l_run[qb] += (ps[0] + ps[1]) + (ps[2] + ps[3]);
       }
-      if constexpr (TIMED) {
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) asm volatile("" : "+v"(sc[qb][0]), "+v"(sc[qb][1]));
-      }
-      U2_STAMP(2)  // softmax
       // ---- O^T += V^T P^T ; k-slots jj of step (kbk, ks2) carry keys kbk*32 + 16*ks2 + 8*(jj>>2) + 4*hi + (jj&3),
       //      which is exactly 16-byte chunk (kbk*2 + ks2)*2 + hi of the permuted V^T row
 #pragma unroll
@@ -369,24 +347,9 @@ __device__ __forceinline__ void flash_pass(const FlashArgs& a, char (*lds)[16384
           }
         }
     }
-    if constexpr (TIMED) {
-#pragma unroll
-      for (int qb = 0; qb < QB; ++qb) asm volatile("" : "+v"(oacc[qb][0]), "+v"(oacc[qb][1]));
-    }
-    U2_STAMP(3)  // V^T fragment reads + PV MFMAs
     if (t + 1 < ntile) U2_FLASH_LSTORE((t + 1) & 1);
-    U2_STAMP(4)  // wait for the prefetched tile + LDS stores
     __syncthreads();
   }
-  if constexpr (TIMED) {
-    if ((tid & 63) == 0 && g_flash_dbg) {
-      unsigned long long* o = g_flash_dbg + ((size_t)blockIdx.x * 4 + (tid >> 6)) * 8 + (QB == 2 ? 0 : 0);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) o[i] += ts[i];
-      o[7] += (unsigned long long)ntile;
-    }
-  }
-#undef U2_STAMP
 #undef U2_FLASH_GLOAD
 #undef U2_FLASH_LSTORE
   if (!wave_active) return;
@@ -564,7 +527,7 @@ __global__ __launch_bounds__(256, 3) void flash_d64_kernel(const FlashArgs a) {
   }
   const int nqt = (a.S + 127) >> 7;
   const int hh = bid / nqt;
-  flash_pass<1, false>(a, lds, hh / a.H, hh % a.H, (bid % nqt) * 128, tid);
+  flash_pass<1>(a, lds, hh / a.H, hh % a.H, (bid % nqt) * 128, tid);
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -697,8 +660,7 @@ __device__ __forceinline__ float dot2_bf16(const uint32_t a, const uint32_t b, c
   return dot2_elem(a, b, c);
 }
 template <int NT>
-__device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf, const int b, const int h, const int tid,
-                                                 unsigned long long* tl = nullptr) {
+__device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf, const int b, const int h, const int tid) {
   constexpr int NW = NT / 64;
   float* red = sbuf + a.S_pad;                                    // [2 NW] block reductions
   bf16_t* pb = reinterpret_cast<bf16_t*>(sbuf + a.S_pad + 64);    // [S_pad] probabilities, bf16, in V^T's key order
@@ -719,7 +681,7 @@ __device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf
   const float sx = dot8(*reinterpret_cast<const uint4*>(a.kx + (int64_t)b * a.x_bs + h * 64 + ch * 8));  // the extra key
   float m = sx;
   // keys per thread in flight (8, 16 and 32 measure the same ~30 us beside the main waves: scores 18.6 + softmax 2 + P V 11.4 us
-  // by s_memrealtime; moved into the V^T launch in front of the flash launch the rows took 24 us there against 12 us for the
+  // by in-kernel clock stamps; moved into the V^T launch in front of the flash launch the rows took 24 us there against 12 us for the
   // transpose alone and bought the flash launch 2 us: removed again, profiles/r04_flash_tail_split_trial.log)
   constexpr int KU = 8;
   for (int j0 = wv * 8 + kk; j0 < S_pad; j0 += KU * 8 * NW) {
@@ -738,7 +700,6 @@ __device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf
     }
   }
   m = wave_max(m);
-  if (tl && lane == 0) tl[4] = __builtin_amdgcn_s_memrealtime();
   if (lane == 0) red[wv] = m;
   __syncthreads();
   m = red[0];
@@ -755,7 +716,6 @@ __device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf
   sum = wave_sum(sum);
   if (lane == 0) red[NW + wv] = sum;
   __syncthreads();
-  if (tl && lane == 0) tl[5] = __builtin_amdgcn_s_memrealtime();
   const float px = __builtin_amdgcn_exp2f(sx - m);
   float l_tot = px;
 #pragma unroll
@@ -800,16 +760,10 @@ __device__ __forceinline__ void flash_extra_row2(const FlashArgs& a, float* sbuf
 // measured in round 4 and removed again: the extra-row workgroups need ~30 us of a slot whatever they execute and only
 // the half-empty second round has slots to spare, and the first round's exits are spread over 16 us, which the plain
 // form absorbs for free (profiles/r04_flash_tail_split_trial.log; the commit before this form).
-template <bool TIMED, int QMODE>
+template <int QMODE>
 __global__ __launch_bounds__(256, 2) void flash_dp2_kernel(const FlashArgs a) {
   __shared__ __attribute__((aligned(1024))) char lds[FDP_SLOTS][16384];  // [slot][K tile 8 KB | V^T tile 8 KB]
   const int tid = threadIdx.x;
-  // TIMED: wall-clock stamps (s_memrealtime, 100 MHz) of the workgroup's sections in a second region of the debug buffer
-  unsigned long long* tl = nullptr;
-  if constexpr (TIMED) {
-    tl = g_flash_dbg + 65536 + ((size_t)blockIdx.x * 4 + (tid >> 6)) * 8;
-    if ((tid & 63) == 0) tl[0] = __builtin_amdgcn_s_memrealtime();
-  }
   // XCD-aware order inside each region of the grid: workgroup w runs on XCD w % 8 (observed dispatch rule); every XCD
   // gets a contiguous range of logical ids so that the units of one (batch, head) share that XCD's L2 copy of K and V^T
   auto xcd_order = [](const int w, const int nwg) {
@@ -826,8 +780,7 @@ __global__ __launch_bounds__(256, 2) void flash_dp2_kernel(const FlashArgs a) {
       // get the leftover issue slots (30 us for ~10 us of work): static priority, their demand is small
       __builtin_amdgcn_s_setprio(3);
       const int e = w - a.n_main;
-      flash_extra_row2<256>(a, reinterpret_cast<float*>(&lds[0][0]), e / a.H, e % a.H, tid, TIMED ? tl : nullptr);
-      if constexpr (TIMED) if ((tid & 63) == 0) tl[3] = __builtin_amdgcn_s_memrealtime();
+      flash_extra_row2<256>(a, reinterpret_cast<float*>(&lds[0][0]), e / a.H, e % a.H, tid);
       return;
     }
   }
@@ -876,22 +829,15 @@ __global__ __launch_bounds__(256, 2) void flash_dp2_kernel(const FlashArgs a) {
   const int xflag = a.n_extra;
   float mr0, lr0, mr1, lr1;
   int lane2;  // the lane id as the block returns it: keeps the epilogue's per-lane values from living across the block
-  unsigned long long* dbg = g_flash_dbg + ((size_t)blockIdx.x * 4 + wv) * 8;  // TIMED: 5 section times, [7] = tiles
 #define FDP2_OPERANDS                                                                                                  \
                : [mr0] "=&v"(mr0), [lr0] "=&v"(lr0), [mr1] "=&v"(mr1), [lr1] "=&v"(lr1), [lid] "=&v"(lane2)             \
                : [qa0] "v"(qa0), [qa1] "v"(qa1),                                                                        \
                  [ab0] "v"(ab0), [ko0] "v"(ko0), [ko1] "v"(ko1), [vo0] "v"(vo0), [vo1] "v"(vo1), [hi4] "v"(hi4),        \
                  [dump] "v"(dump), [rsk] "s"(rsk), [rsv] "s"(rsv), [lds] "s"(lds_u32), [dma_base] "s"(dma_base),        \
-                 [ktile] "s"(k_tile_bytes), [seq] "s"(S), [ntile] "s"(ntile), [dbg] "v"(dbg),                           \
+                 [ktile] "s"(k_tile_bytes), [seq] "s"(S), [ntile] "s"(ntile),                                         \
                  [scale] "s"(scale_log2e), [rscale] "s"(rscale), [kxa] "v"(kxa), [vxa] "v"(vxa), [xflag] "s"(xflag)
 #define FDP2_RUN(SFX_) asm volatile(FLASH_DP2_ASM_TEXT##SFX_ FDP2_OPERANDS : FLASH_DP2_ASM_CLOBBERS##SFX_)
-  if constexpr (TIMED) {
-    if (lane == 0) tl[1] = __builtin_amdgcn_s_memrealtime();
-    if constexpr (QMODE == 0) FDP2_RUN(_X_TIMED); else FDP2_RUN(_TIMED);
-    if (lane2 == 0) { dbg[7] = (unsigned long long)ntile; tl[2] = __builtin_amdgcn_s_memrealtime(); }
-  } else {
-    if constexpr (QMODE == 0) FDP2_RUN(_X); else FDP2_RUN();
-  }
+  if constexpr (QMODE == 0) FDP2_RUN(_X); else FDP2_RUN();
 #undef FDP2_RUN
 #undef FDP2_OPERANDS
   // the block left O^T in LDS: tuple T = 2 * block + nb, 16-byte quarter j at [wave][T * 4 + j][lane]
@@ -912,17 +858,6 @@ __global__ __launch_bounds__(256, 2) void flash_dp2_kernel(const FlashArgs a) {
     const bf16x8 no_q[4] = {};   // (the extra key was folded in by the block)
     fdp_finish(a, x, no_q, b, h, wrow0 + 32 * blk + l31b, hi2, QMODE != 0, true);
   }
-  if constexpr (TIMED) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane2 == 0) tl[3] = __builtin_amdgcn_s_memrealtime();
-  }
-}
-
-static bool g_flash_timed = false;
-int flash_set_debug_buffer(void* p) {  // >= grid * 4 * 8 uint64, zeroed by the caller; null detaches
-  unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
-  g_flash_timed = q != nullptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_flash_dbg), &q, sizeof(q)) == hipSuccess ? U2_OK : U2_ERR_LAUNCH;
 }
 
 int flash_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16_t* out, int nb, int S, int H,
@@ -960,13 +895,8 @@ int flash_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16
                4.0 * nbh * (double)(S + n_extra) * 64 * 2.0);  // q, k, v^T read + o written, once
   if (mode == 7) {
     const dim3 g((unsigned)grid), t(256);
-#define U2_FDP2_Q(T_)                                                                                            \
-  do {                                                                                                           \
-    if (q_prescaled) hipLaunchKernelGGL((flash_dp2_kernel<T_, 1>), g, t, 0, stream, a);                         \
-    else hipLaunchKernelGGL((flash_dp2_kernel<T_, 0>), g, t, 0, stream, a);                                     \
-  } while (0)
-    if (g_flash_timed) U2_FDP2_Q(true); else U2_FDP2_Q(false);
-#undef U2_FDP2_Q
+    if (q_prescaled) hipLaunchKernelGGL(flash_dp2_kernel<1>, g, t, 0, stream, a);
+    else hipLaunchKernelGGL(flash_dp2_kernel<0>, g, t, 0, stream, a);
   } else {
     hipLaunchKernelGGL(flash_d64_kernel, dim3((unsigned)grid), dim3(256), 0, stream, a);
   }

@@ -238,7 +238,6 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
                  float scale, const bf16_t* rel_bias, int max_len, int causal, int force_splits, void* ws, size_t ws_bytes,
                  hipStream_t stream);
-int tok_attention_set_debug_buffer(void* p);
 // ------------------------------------------------------------------ decoder prefill row kernels (decoder.hip)
 int rmsnorm_bf16(const bf16_t* x, const bf16_t* w, bf16_t* y, int64_t rows, int C, int64_t ldx, int64_t ldy, float eps,
                  hipStream_t stream);
@@ -257,9 +256,6 @@ int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_n
                        hipStream_t st);
 int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
                         int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
-                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);  // diagnostics: >= grid * 4 * 8 uint64, zeroed; null detaches (instrumented build)
-// Diagnostics only (process-wide, not for concurrent use): s_memtime phase sums per (workgroup, wave) of the double
-// pipeline kernel; while a buffer is attached the kernel runs its instrumented build.  See attn.hip.
-int flash_set_debug_buffer(void* p);
+                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace u2

@@ -57,7 +57,6 @@ struct TokAttnArgs {
   float* ml;     // ns > 1: [ns][nb * H][Sq][2] = (running max in log2 units, row sum)
   int kv_group;  // grouped-query attention: query head h reads key / value head h / kv_group (1: plain multi-head)
   int causal;    // 1: key j is visible to query i iff j <= i + (Skv - Sq)   (decoder prefill)
-  unsigned long long* dbg;  // diagnostics (tok_attention_set_debug_buffer): s_memtime sums per (workgroup, wave), 8 slots
 };
 
 constexpr float TOKATTN_RESCALE_THR = 8.0f;
@@ -74,15 +73,8 @@ __device__ __forceinline__ int t96_pos(int row, int L) { return L ^ ((row >> 1) 
 
 typedef short ta_v4s_t __attribute__((ext_vector_type(4)));
 
-template <int DH, bool TIMED = false>
+template <int DH>
 __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const TokAttnArgs a) {
-  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define U2_STAMP(i_)                                            \
-  if constexpr (TIMED) {                                        \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    ts[i_] += t_ - tprev;                                       \
-    tprev = t_;                                                 \
-  }
   constexpr int BK = DH <= 128 ? 64 : 32;  // keys per tile (narrow heads: twice the keys per barrier / DMA wait / softmax step)
   constexpr int NKB = BK / 16;        // 16-key blocks of S^T per tile
   constexpr int NPF = BK / 32;        // P fragments (32 keys = one MFMA k step of P V) per tile
@@ -199,17 +191,13 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
     dma_k(kt0, 0);
     dma_v(kt0, 0);
   }
-  if constexpr (TIMED) tprev = __builtin_amdgcn_s_memtime();
   for (int kt = kt0; kt < kt1; ++kt) {
     const int stage = (kt - kt0) & 1;
     const char* const tK = lds + stage * 2 * TILE;
     const char* const tV = tK + TILE;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    U2_STAMP(0)  // wait for the tile's DMA
     __syncthreads();  // tile kt has landed for every wave; every wave is done with tile kt - 1 (the other stage)
-    U2_STAMP(1)  // barrier
     if (kt + 1 < kt1) dma_k(kt + 1, stage ^ 1);
-    U2_STAMP(2)  // K DMA issue
     // ---- S^T = K Q^T, NKB 16-key blocks.  Independent accumulator chains (key blocks x even / odd k steps): a dependent
     // v_mfma_f32_16x16x32 chain issues at its ~8-pass latency, not at the pipe rate
     f32x4 sc[NKB];
@@ -239,11 +227,6 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb) sc[kb] = KS > 1 ? acc[kb][0] + acc[kb][1] : acc[kb][0];
     }
-    if constexpr (TIMED) {
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) asm volatile("" : "+v"(sc[kb]));
-    }
-    U2_STAMP(3)  // Q K^T
     // ---- online softmax: lane owns keys kt * 32 + 16 kb + 4 g + r of query row qrow
     // (one wave per SIMD issues a VALU instruction every 5-9 cycles: the instruction count of this block is its cost.
     //  Without bias the scale is folded into the exponent's FMA and the row max is taken on the raw scores -- scale > 0
@@ -304,13 +287,7 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       pf[j].u[3] = pack2_bf16(x[8 * j + 6], x[8 * j + 7]);
     }
 
-    if constexpr (TIMED) {
-#pragma unroll
-      for (int j = 0; j < NPF; ++j) asm volatile("" : "+v"(pf[j].v));
-    }
-    U2_STAMP(4)  // softmax
     if (kt + 1 < kt1) dma_v(kt + 1, stage ^ 1);
-    U2_STAMP(5)  // V DMA issue
     // ---- O^T += V^T P^T (same software pipeline over the d blocks)
     {
       constexpr int NPV = NPF * DB, PD = NPV < 6 ? NPV : 6;  // step i = (P fragment j = i / DB, d block db = i % DB)
@@ -336,21 +313,7 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (TIMED) {
-#pragma unroll
-      for (int db = 0; db < DB; ++db) asm volatile("" : "+v"(o[db]));
-    }
-    U2_STAMP(6)  // P V
   }
-  if constexpr (TIMED) {
-    if (lane == 0 && a.dbg) {
-      unsigned long long* dp = a.dbg + ((size_t)blockIdx.x * 4 + w) * 8;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) dp[i] += ts[i];
-      dp[7] += (unsigned long long)(kt1 - kt0);
-    }
-  }
-#undef U2_STAMP
 
   // ---- epilogue: lane holds O^T[d = 16 db + 4 g + r][q = qrow]
   float l_tot = l_run + __shfl_xor(l_run, 16, 64);
@@ -424,17 +387,8 @@ __device__ __forceinline__ float row_sum4(float v) {
 // MUBUF (option tok_wide = 2, round 6): the tiles' pieces leave as `buffer_load_dwordx4 ... lds` (descriptor over the batch entry's K / V,
 // 32-bit lane offset, tile and piece origin in the scalar offset) instead of the FLAT-encoded global_load_lds: beside waves that issue
 // MFMAs the FLAT form stages a third of what the MUBUF form does (tools/ubench/stage_bw.hip, profiles/r06_stage_bw.log).
-template <int DH, bool TIMED = false, bool MUBUF = false>
+template <int DH, bool MUBUF = false>
 __global__ __launch_bounds__(512) void tok_attn2_kernel(const TokAttnArgs a) {
-  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define U2_STAMP(i_)                                            \
-  if constexpr (TIMED) {                                        \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    ts[i_] += t_ - tprev;                                       \
-    tprev = t_;                                                 \
-  }
-  unsigned long long rt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // TIMED: s_memrealtime (100 MHz) at entry / loop start / loop end / exit; [4..7] prologue: requests issued / K(kt0) + Q here / barrier / (spare)
-  if constexpr (TIMED) rt[0] = __builtin_amdgcn_s_memrealtime();
   constexpr int BK = 32;
   constexpr int CPR = DH / 8;          // 16-byte chunks per tile row
   constexpr int ROWB = DH * 2;         // bytes per tile row
@@ -606,29 +560,19 @@ __global__ __launch_bounds__(512) void tok_attn2_kernel(const TokAttnArgs a) {
     *reinterpret_cast<f32x4*>(xb + par * 8192 + x_wr) = sc;
   };
 
-  if constexpr (TIMED) rt[4] = __builtin_amdgcn_s_memrealtime();
   // K(kt0) and Q are the oldest requests after the bias rows: everything younger (V(kt0), K(kt0 + 1)) may still be in flight
   if (two) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
   else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
-  if constexpr (TIMED) rt[5] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();  // K(kt0) has landed for every wave, the bias window is written
-  if constexpr (TIMED) rt[6] = __builtin_amdgcn_s_memrealtime();
   scores_begin(0);
   scores_end(0, 0);
-  if constexpr (TIMED) {
-    rt[1] = __builtin_amdgcn_s_memrealtime();
-    tprev = __builtin_amdgcn_s_memtime();
-  }
   for (int kt = kt0; kt < kt1; ++kt) {
     const int par = (kt - kt0) & 1;
     const bool more = kt + 1 < kt1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    U2_STAMP(0)  // wait for K(kt + 1), V(kt)
     __syncthreads();  // ... landed for every wave; scores(kt) of both halves are in the exchange; V stage par ^ 1 / K stage par are free
-    U2_STAMP(1)  // barrier
     if (more) dma_v(kt + 1, par ^ 1);
     if (kt + 2 < kt1) dma_k(kt + 2, par);
-    U2_STAMP(2)  // DMA issue
     // ---- first fragment reads of S(kt + 1): their latency passes under the softmax below
     if (more) scores_begin(par ^ 1);
     // ---- online softmax: lane owns keys kt * 32 + 16 kb + 4 g + r of query row qrow (both waves of the pair alike)
@@ -681,11 +625,8 @@ __global__ __launch_bounds__(512) void tok_attn2_kernel(const TokAttnArgs a) {
     pf.u[1] = pack2_bf16(x[2], x[3]);
     pf.u[2] = pack2_bf16(x[4], x[5]);
     pf.u[3] = pack2_bf16(x[6], x[7]);
-    if constexpr (TIMED) asm volatile("" : "+v"(pf.v));
-    U2_STAMP(4)  // softmax
     // ---- S^T of the next tile (its K tile landed with this iteration's wait)
     if (more) scores_end(par ^ 1, par ^ 1);
-    U2_STAMP(3)  // Q K^T
     // ---- O^T += V^T P^T over this wave's half of the head dim: one asm block (tools/gen_tokattn_asm.py) -- hipcc would put
     // s_waitcnt vmcnt(0) between this iteration's DMA issue and the first transpose read
     {
@@ -708,31 +649,11 @@ __global__ __launch_bounds__(512) void tok_attn2_kernel(const TokAttnArgs a) {
       }
 #undef U2_PV_ADDR
     }
-    U2_STAMP(6)  // P V
   }
-  if constexpr (TIMED) rt[2] = __builtin_amdgcn_s_memrealtime();
-#undef U2_STAMP
-  auto timed_out = [&]() {
-    if constexpr (TIMED) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores of the epilogue
-      rt[3] = __builtin_amdgcn_s_memrealtime();
-      if (lane == 0 && a.dbg) {
-        unsigned long long* dp = a.dbg + ((size_t)blockIdx.x * 8 + w) * 16;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) dp[i] += ts[i];
-        dp[7] += (unsigned long long)(kt1 - kt0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dp[8 + i] = rt[i];
-      }
-    }
-  };
 
   // ---- epilogue: lane holds O^T[d = 16 (half * DBH + i) + 4 g + r][q = qrow]
   const float l_tot = row_sum4(l_run);
-  if (qrow >= Sq) {
-    timed_out();
-    return;
-  }
+  if (qrow >= Sq) return;
   const int d0 = half * (DH / 2) + 4 * g;
   if (a.ns == 1) {
     const float inv = 1.f / l_tot;
@@ -752,7 +673,6 @@ __global__ __launch_bounds__(512) void tok_attn2_kernel(const TokAttnArgs a) {
       mp[1] = l_tot;
     }
   }
-  timed_out();
 }
 
 // out[b][q][e] = sum_s 2^(m_s - m) O_s[b][q][e] / sum_s 2^(m_s - m) l_s over the key splits, s in ascending order
@@ -828,12 +748,6 @@ static int tok_attn_pick_splits(int nb, int H, int Sq, int Skv, int d, size_t ws
   return std::max(ns, 1);
 }
 
-static unsigned long long* g_tokattn_dbg = nullptr;  // diagnostics only, process-wide (like flash_set_debug_buffer)
-int tok_attention_set_debug_buffer(void* p) {
-  g_tokattn_dbg = reinterpret_cast<unsigned long long*>(p);
-  return U2_OK;
-}
-
 size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d) {
   const int64_t base = (int64_t)nb * H * cdiv(Sq, 64);
   const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
@@ -896,19 +810,16 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
   if (grid > 0x7fffffff) return U2_ERR_ARG;
   ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
                2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));  // q, k, v read + o written, once
-  a.dbg = g_tokattn_dbg;
 #define U2_TA(D_)                                                                                                      \
   do {                                                                                                                 \
-    constexpr size_t smem_ = 4 * ((D_) <= 128 ? 64 : 32) * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                                               \
-    if (a.dbg) hipLaunchKernelGGL((tok_attn_kernel<D_, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);    \
-    else hipLaunchKernelGGL((tok_attn_kernel<D_, false>), dim3((unsigned)grid), dim3(256), smem_, stream, a);         \
+    constexpr size_t smem_ = 4 * ((D_) <= 128 ? 64 : 32) * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                          \
+    hipLaunchKernelGGL((tok_attn_kernel<D_>), dim3((unsigned)grid), dim3(256), smem_, stream, a);                      \
   } while (0)
 #define U2_TA2(D_)                                                                                                     \
   do {                                                                                                                 \
     constexpr size_t smem_ = 4 * 32 * (D_) * 2 + 16384 + TOKATTN_BIAS_SLOTS * 4;                                       \
-    if (a.dbg) hipLaunchKernelGGL((tok_attn2_kernel<D_, true>), dim3((unsigned)grid), dim3(512), smem_, stream, a);   \
-    else if (mubuf) hipLaunchKernelGGL((tok_attn2_kernel<D_, false, true>), dim3((unsigned)grid), dim3(512), smem_, stream, a); \
-    else hipLaunchKernelGGL((tok_attn2_kernel<D_, false>), dim3((unsigned)grid), dim3(512), smem_, stream, a);        \
+    if (mubuf) hipLaunchKernelGGL((tok_attn2_kernel<D_, true>), dim3((unsigned)grid), dim3(512), smem_, stream, a);    \
+    else hipLaunchKernelGGL((tok_attn2_kernel<D_, false>), dim3((unsigned)grid), dim3(512), smem_, stream, a);         \
   } while (0)
   const bool wide = d >= 256 && !causal && opts().tok_wide;  // two waves per SIMD (tok_attn2_kernel)
   const bool mubuf = opts().tok_wide == 2 && (int64_t)Skv * ldk < (1ll << 29) && (int64_t)Skv * ldv < (1ll << 29);
