@@ -234,14 +234,16 @@ int u2tok_preprocess_volume_aug(const float* vol, void* out, int32_t* info, int3
 /* ---- building blocks (exported for the parity tests; same kernels the pipelines launch) -------- */
 
 /* C[z] = epi(alpha * A[z] B[z]^T): A (M,K) lda, B (N,K) ldb, C (M,N) ldc; z = zb*nbh + zh with element strides.
- * flags: 1 bias[n], 2 bias[m], 4 GELU(erf), 8 + R[m][n], 16 C is fp32 (else bf16), 64 B is K-tile-major [K/64][N][64],
+ * flags: 1 bias[n], 2 bias[m], 4 GELU, 8 + R[m][n], 16 C is fp32 (else bf16), 64 B is K-tile-major [K/64][N][64],
  * 256 B is stored K-major, (K,N) with ldb >= N (C = A B: the input-gradient product dX = dY W without a transposed W),
  * 128 | 256 A is stored K-major too, (K,M) with lda >= M (C = A^T B: the weight-gradient product dW = dY^T X without
  * transposed activations); the K-major dimension (M resp. N) must be a multiple of 8.
  * 512: gate | up pair product of a gated MLP (LlamaMLP / Qwen3MLP: act_fn(gate_proj(x)) * up_proj(x)): B = the gate weight's
  * I rows followed by the up weight's I rows (N = 2 I), C (M, I) bf16 = bf16(silu(bf16(x gate^T))) * bf16(x up^T) -- the values
  * u2tok_gemm_bf16 + u2tok_swiglu_bf16 produce, bit for bit, without the (M, 2 I) intermediate; alone (no other flag, nz = 1),
- * K % 64 == 0, I % 16 == 0, 16-byte aligned operands; U2TOK_ERR_ARG otherwise. */
+ * K % 64 == 0, I % 16 == 0, 16-byte aligned operands; U2TOK_ERR_ARG otherwise.
+ * GELU (flag 4, and u2tok_gelu_fwd) is not exact erf-GELU: x Phi(x) with Phi a logistic-polynomial approximation, |error| <= 3.3e-6
+ * before rounding, evaluated on the pre-activation rounded to the element type (after bias, before the residual). */
 int u2tok_gemm_bf16(const void* A, const void* B, void* C, const void* bias, const void* R, int32_t M, int32_t N,
                     int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int32_t nz, int32_t nbh,
                     int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, int64_t sRb,
@@ -370,8 +372,10 @@ int u2tok_rope_apply(void* x, int64_t n_outer, int32_t S, int32_t n_inner, int32
  * The GEMM-shaped parts of the backward (dX = dY W, dW = dY^T X, dQ / dK / dV / dP of the attention cores) are
  * u2tok_gemm_bf16 calls on (transposed) operands; these are the rest.  The host side (u2tokenizer_amd/autograd.py)
  * sequences them behind torch.autograd.Function so that the drop-in modules train (train_stage1.py:244-251). */
-int u2tok_gelu_fwd(const void* z, void* y, int64_t n, u2tok_stream_t stream);                  /* y = gelu(z) (erf) */
-int u2tok_gelu_bwd(const void* z, const void* dy, void* dz, int64_t n, u2tok_stream_t stream); /* dz = dy gelu'(z) */
+/* y = gelu(z): the approximation of u2tok_gemm_bf16's flag 4 (|y - z Phi(z)| <= 3.3e-6 before rounding to the element type);
+ * dz = dy gelu'(z) with gelu' the derivative of EXACT erf-GELU, Phi(z) + z phi(z).  n % 8 == 0, 16-byte aligned buffers. */
+int u2tok_gelu_fwd(const void* z, void* y, int64_t n, u2tok_stream_t stream);
+int u2tok_gelu_bwd(const void* z, const void* dy, void* dz, int64_t n, u2tok_stream_t stream);
 /* out[c] (+)= sum_r x[r][c] (* y[r][c] when y != NULL) in fp32, fixed summation order (bit-repeatable); out (fp32)
  * and / or out_bf16 receive the result; workspace: u2tok_colsum_workspace_bytes. */
 size_t u2tok_colsum_workspace_bytes(int32_t rows, int32_t C);

@@ -796,3 +796,147 @@ def test_gemm_heuristic_split_rows(ops):
     a, b, bias, res = rnd(M, K, seed=21), rnd(N, K, seed=22), rnd(N, seed=23), rnd(M, N, seed=24)
     got = ops.gemm(a.to(D), b.to(D), bias=bias.to(D), residual=res.to(D))
     close_bf16(got, a.float() @ b.float().t() + bias.float() + res.float())
+
+
+# ---------------------------------------------------------------------------------- what each GEMM form writes, and where
+# One product per kernel form, as "key=value" descriptors of u2tok_gemm_bf16 in the terms of tests/gemm_plan_driver.cpp, except that
+# c_off counts ELEMENTS of C here (bytes there) and that nbh / sAh / sBh / sCh (not read by the plan) and kpad (columns k >= kpad of
+# both operands are zero) may appear.  Every C lies in a sentinel-filled storage with ldc > N (unless noted), a nonzero c_off and, for
+# nz = 2, a batch gap (sCb > M ldc).  tests/test_gemm_plan.py pins the route of every descriptor (gemm_write_plan_descriptor).
+GEMM_WRITE_CASES = {
+    "tile64_vec": "M=300 N=264 K=200 nz=2 ldc=272 sAb=60000 sBb=52800 sCb=81616 c_off=8 gemm_tile=64",
+    "tile64_vec_f32": "M=300 N=264 K=200 nz=2 ldc=268 sAb=60000 sBb=52800 sCb=80404 c_off=4 flags=0x10 gemm_tile=64",
+    "tile64_scalar": "M=77 N=203 K=72 nz=2 ldc=211 sAb=5544 sBb=14616 sCb=16250 c_off=5 gemm_tile=64",
+    "tile64_bias_gelu_res": "M=300 N=264 K=200 ldc=272 c_off=8 flags=0xd gemm_tile=64",
+    "tile128_vec": "M=260 N=136 K=264 nz=2 ldc=144 sAb=68640 sBb=35904 sCb=37448 c_off=8 gemm_tile=128",
+    "tile128_scalar": "M=130 N=203 K=136 nz=2 ldc=205 sAb=17680 sBb=27608 sCb=26651 c_off=3 gemm_tile=128",
+    "kmajor_a_b": "M=200 N=72 K=136 nz=2 ldc=80 sAb=27200 sBb=9792 sCb=16008 c_off=8 flags=0x180",
+    "kmajor_b": "M=77 N=520 K=1160 ldc=528 c_off=8 flags=0x100",
+    "tile_splitk": "M=77 N=520 K=1160 ldc=528 c_off=8 gemm_splitk=3 scratch=50331648",
+    "tile_splitk_f32": "M=77 N=203 K=1160 ldc=207 c_off=3 flags=0x10 gemm_splitk=3 scratch=50331648",
+    "rows16": "M=16 N=760 K=768 ldc=776 c_off=8",
+    "rows16_bias_res": "M=13 N=200 K=96 ldc=203 c_off=3 flags=0x9",
+    "skinny64": "M=200 N=2048 K=2048 ldc=2056 c_off=8",
+    "skinny64_bias_res": "M=200 N=2048 K=2048 ldc=2056 c_off=8 flags=0x9",
+    "big20": "M=515 N=264 K=192 nz=2 ldc=272 sAb=98880 sBb=50688 sCb=140088 c_off=8 gemm_big=20",
+    "big20_f32": "M=515 N=264 K=192 nz=2 ldc=268 sAb=98880 sBb=50688 sCb=138024 c_off=4 flags=0x10 gemm_big=20",
+    "big21": "M=515 N=264 K=192 nz=2 ldc=272 sAb=98880 sBb=50688 sCb=140088 c_off=8 gemm_big=21",
+    "big22": "M=515 N=264 K=192 nz=2 ldc=272 sAb=98880 sBb=50688 sCb=140088 c_off=8 gemm_big=22",
+    "big24": "M=515 N=264 K=192 nz=2 ldc=272 sAb=98880 sBb=50688 sCb=140088 c_off=8 gemm_big=24",
+    "big24_bias_res": "M=515 N=264 K=192 ldc=272 c_off=8 flags=0x9 gemm_big=24",
+    "big26": "M=515 N=264 K=192 nz=2 ldc=272 sAb=98880 sBb=50688 sCb=140088 c_off=8 gemm_big=26",
+    "big21_sliced": "M=200 N=520 K=1024 ldc=528 c_off=8 gemm_big=21 gemm_big_splitk=2 scratch=100663296",
+    "drain27": "M=1024 N=768 K=768 ldc=776 c_off=8 gemm_big=27 gemm_big_grid=4",
+    "drain27_gelu": "M=1024 N=768 K=768 ldc=776 c_off=8 flags=0x5 gemm_big=27 gemm_big_grid=4",
+    "heuristic_drain_tail_fused": "M=1032 N=384 K=768 ldc=392 c_off=8 gemm_big_grid=4",
+    "heuristic_drain_gelu_tail_fused": "M=2056 N=1536 K=768 ldc=1544 c_off=8 flags=0x5 gemm_big_grid=16",
+    "heuristic_big_bias_res_tail_fused": "M=2056 N=768 K=768 ldc=776 c_off=8 flags=0x9 gemm_big_grid=16",
+    "heuristic_big_rows16_tail": "M=2056 N=1536 K=768 ldc=1544 c_off=8 gemm_big_grid=16",
+    # the attention backward's batched per-head products (u2tokenizer_amd/autograd.py, _attn_pv / _attn_backward through transposed
+    # copies): nz = nb H, head h writes columns [h d, h d + d) of E-wide rows, K = ldp with zero pad columns -- once as autograd.py
+    # lays the output out (ldc = H d, c_off = 0), once with ldc > H d and c_off > 0
+    "attn_heads_dense": "M=37 N=64 K=56 nz=6 nbh=3 lda=56 ldb=56 ldc=192 sAb=6216 sAh=2072 sBb=10752 sBh=3584 sCb=7104 sCh=64 kpad=53",
+    "attn_heads_strided": "M=37 N=64 K=56 nz=6 nbh=3 lda=56 ldb=56 ldc=200 sAb=6216 sAh=2072 sBb=10752 sBh=3584 sCb=7416 sCh=64 c_off=8 "
+                          "kpad=53",
+}
+GEMM_OPTION_DEFAULTS = dict(gemm_tile=0, gemm_mubuf=1, gemm_splitk=0, gemm_big=0, gemm_big_grid=256, gemm_big_splitk=0,
+                            gemm_big_drain=1, gemm_skinny=2, gemm_tail_fused=1)
+
+
+def _gemm_case(desc):
+    return {k: int(v, 0) for k, v in (kv.split("=") for kv in desc.split())}
+
+
+def gemm_write_plan_descriptor(desc):
+    """The same product as tests/gemm_plan_driver.cpp reads it: c_off in bytes, the keys the plan does not read dropped."""
+    p = _gemm_case(desc)
+    out = []
+    for kv in desc.split():
+        k, v = kv.split("=")
+        if k in ("nbh", "sAh", "sBh", "sCh", "kpad"):
+            continue
+        out.append(f"c_off={int(v) * (4 if p.get('flags', 0) & 0x10 else 2)}" if k == "c_off" else kv)
+    return " ".join(out)
+
+
+@pytest.mark.parametrize("case", list(GEMM_WRITE_CASES))
+def test_gemm_writes_exactly_its_output_region(ops, case):
+    """(a) Every sentinel bit of the output storage outside the M x N region(s) of the product survives: the columns between N and ldc,
+    the gap between batch entries, the elements before c_off and the tail past the last row.  (b) Inside, on small-integer operands
+    (every fp32 partial sum exact): the plain epilogue equals the float64 product rounded once to the element type BIT FOR BIT, an
+    fp32 output equals it exactly; bias / residual / GELU epilogues (random bias and residual) are held to close_bf16."""
+    from u2tokenizer_amd import _lib
+    p = _gemm_case(GEMM_WRITE_CASES[case])
+    M, N, K, flags = p["M"], p["N"], p["K"], p.get("flags", 0)
+    nz, nbh = p.get("nz", 1), p.get("nbh", 1)
+    ta, tb, f32 = bool(flags & 0x80), bool(flags & 0x100), bool(flags & 0x10)
+    lda, ldb, ldc = p.get("lda", M if ta else K), p.get("ldb", N if tb else K), p["ldc"]
+    sAb, sAh, sBb, sBh, sCb, sCh = (p.get(k, 0) for k in ("sAb", "sAh", "sBb", "sBh", "sCb", "sCh"))
+    c_off = p["c_off"] if "c_off" in p else 0
+    g = torch.Generator().manual_seed(len(case) * 131 + M)
+    zs = [(z // nbh, z % nbh) for z in range(nz)]
+
+    def operand(rows_, cols_, ld, sb, sh):      # storage holding every batch entry's (rows_, cols_) matrix at stride ld
+        n = max(zb * sb + zh * sh for zb, zh in zs) + (rows_ - 1) * ld + cols_
+        st = torch.randint(-3, 4, (n,), generator=g).to(bf)
+        return st, [torch.as_strided(st, (rows_, cols_), (ld, 1), zb * sb + zh * sh) for zb, zh in zs]
+
+    a_st, a_z = operand(K, M, lda, sAb, sAh) if ta else operand(M, K, lda, sAb, sAh)
+    b_st, b_z = operand(K, N, ldb, sBb, sBh) if tb else operand(N, K, ldb, sBb, sBh)
+    if "kpad" in p:                               # zero pad columns of both operands (softmax_bwd / transpose_ex leave them so)
+        for t in a_z + b_z:
+            t[:, p["kpad"]:] = 0
+    base = [(az.double().t() if ta else az.double()) @ (bz.double() if tb else bz.double().t()) for az, bz in zip(a_z, b_z)]
+    bias = rnd(N, seed=5) if flags & 1 else None
+    res = rnd(M, N, seed=6) if flags & 8 else None
+    sentinel = 0x7FC00001 if f32 else (0x7E01 if bf == torch.float16 else 0x7FC1)
+    last = max(zb * sCb + zh * sCh for zb, zh in zs) + (M - 1) * ldc + N
+    c_bits = torch.full((c_off + last + 64,), sentinel, dtype=torch.int32 if f32 else torch.int16)
+    region = torch.zeros(c_bits.numel(), dtype=torch.bool)
+    for zb, zh in zs:
+        o = c_off + zb * sCb + zh * sCh
+        idx = o + torch.arange(M)[:, None] * ldc + torch.arange(N)[None, :]
+        assert not region[idx].any()              # (the regions of the batch entries do not overlap)
+        region[idx] = True
+    c_st = c_bits.view(torch.float32 if f32 else bf).to(D)
+    scratch = torch.empty(p["scratch"], dtype=torch.uint8, device=D) if "scratch" in p else None
+    try:
+        for k, v in p.items():
+            if k.startswith("gemm_"):
+                ops.set_option(k, v)
+        ops.set_gemm_scratch(scratch)
+        ad, bd = a_st.to(D), b_st.to(D)
+        if flags & (0x4 | 0x8):                   # GELU / residual: the C entry point (ops.gemm_strided has neither)
+            biasd, resd = (None if t is None else t.to(D) for t in (bias, res))
+            with ops.on_device(ad, bf) as (h, st):
+                _lib.check(h.u2tok_gemm_bf16(ad.data_ptr(), bd.data_ptr(), c_st.data_ptr() + c_st.element_size() * c_off,
+                                             None if biasd is None else biasd.data_ptr(), None if resd is None else resd.data_ptr(),
+                                             M, N, K, lda, ldb, ldc, N, nz, nbh, sAb, sAh, sBb, sBh, sCb, sCh, M * N, 0, 1.0, flags, st),
+                           "u2tok_gemm_bf16")
+        else:
+            ops.gemm_strided(ad, bd, c_st, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, nz=nz, nbh=nbh, sAb=sAb, sAh=sAh, sBb=sBb,
+                             sBh=sBh, sCb=sCb, sCh=sCh, out_f32=f32, bias=None if bias is None else bias.to(D), c_off=c_off,
+                             a_kmajor=ta, b_kmajor=tb)
+        got = c_st.cpu()
+    finally:
+        for k in p:
+            if k.startswith("gemm_"):
+                ops.set_option(k, GEMM_OPTION_DEFAULTS[k])
+        ops.set_gemm_scratch(None)
+        torch.cuda.synchronize()
+    got_bits = got.view(c_bits.dtype)
+    outside = ~region
+    assert torch.equal(got_bits[outside], c_bits[outside]), \
+        f"{(got_bits[outside] != c_bits[outside]).sum().item()} sentinel elements overwritten outside the product"
+    for (zb, zh), ref in zip(zs, base):
+        o = c_off + zb * sCb + zh * sCh
+        out = torch.as_strided(got, (M, N), (ldc, 1), o)
+        if flags & (0x1 | 0x4 | 0x8):
+            ref = ref.float() + (bias.float() if bias is not None else 0)
+            if flags & 4:
+                ref = F.gelu(ref)
+            close_bf16(out, ref + (res.float() if res is not None else 0), rounds=4 if flags & 4 else 2)
+        elif f32:
+            assert torch.equal(out, ref.float()), (zb, zh)
+        else:
+            assert torch.equal(out, ref.to(bf)), (zb, zh, (out.double() != ref.to(bf).double()).sum().item())

@@ -23,10 +23,13 @@ __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
   return uint4{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
 }
 
-// d/dz [ 0.5 z (1 + erf(z / sqrt 2)) ] = Phi(z) + z phi(z)
+// d/dz [ 0.5 z (1 + erf(z / sqrt 2)) ] = Phi(z) + z phi(z): the derivative of exact erf-GELU (not of the approximation gelu_fast
+// that the forward evaluates).  Phi(z) = erfc(-z / sqrt 2) / 2: 1 + erf(z / sqrt 2) cancels to 0 in fp32 from z < -5.3 on, where
+// Phi(z) is still 1-3 % of |z phi(z)| -- up to 8 bf16 ulps off over z in [-13.2, -5.3].  expf, not __expf: v_exp_f32 returns 0 where
+// phi(z) is subnormal (|z| > 13.2) while z phi(z) is not yet.
 __device__ __forceinline__ float gelu_grad(float z) {
-  const float cdf = 0.5f * (1.0f + erff(z * 0.70710678118654752440f));
-  const float pdf = 0.39894228040143267794f * __expf(-0.5f * z * z);
+  const float cdf = 0.5f * erfcf(z * -0.70710678118654752440f);
+  const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
   return cdf + z * pdf;
 }
 

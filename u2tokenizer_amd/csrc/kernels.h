@@ -25,7 +25,8 @@ struct ProfScope {  // brackets one launch with hipEvents on `st` when the curre
 enum : int {
   GEMM_BIAS_N = 1,     // + bias[n]   (nn.Linear bias)
   GEMM_BIAS_M = 2,     // + bias[m]   (operand-swapped products, e.g. DiffTS scores^T)
-  GEMM_GELU = 4,       // exact erf GELU after bias
+  GEMM_GELU = 4,       // GELU after bias: gelu_epi (common.h), the logistic-polynomial approximation of erf-GELU (|error| <= 3.3e-6)
+                       // on the pre-activation rounded to the element type -- not exact erf
   GEMM_RESIDUAL = 8,   // + R[m][n]   (residual stream / position embedding), after GELU
   GEMM_OUT_F32 = 16,   // C is float32 instead of bf16
   GEMM_VEC_OK = 32,    // internal: vector epilogue legal (set by the launcher)
@@ -169,8 +170,8 @@ int multiscale_pool(const bf16_t* x, bf16_t* out, int B, int k, int E, const bf1
                     const bf16_t* gate_b, float* ws, hipStream_t stream);
 
 // ------------------------------------------------------------------ backward-pass kernels (backward.hip)
-int gelu_fwd(const bf16_t* z, bf16_t* y, int64_t n, hipStream_t stream);                      // y = gelu(z), n % 8 == 0
-int gelu_bwd(const bf16_t* z, const bf16_t* dy, bf16_t* dz, int64_t n, hipStream_t stream);  // dz = dy gelu'(z)
+int gelu_fwd(const bf16_t* z, bf16_t* y, int64_t n, hipStream_t stream);                      // y = gelu_fast(z), n % 8 == 0
+int gelu_bwd(const bf16_t* z, const bf16_t* dy, bf16_t* dz, int64_t n, hipStream_t stream);  // dz = dy gelu'(z): the derivative of exact erf-GELU
 // out[c] (+)= sum_r x[r][c] (* y[r][c] when y != null), fp32, fixed summation order; ws: colsum_workspace_bytes
 size_t colsum_workspace_bytes(int rows, int C);
 int colsum_bf16(const bf16_t* x, const bf16_t* y, float* out, bf16_t* out_bf16, int rows, int C, int64_t ldx, int64_t ldy,
