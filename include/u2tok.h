@@ -421,6 +421,45 @@ int32_t u2tok_flash_attention_d64_bwd(const void* q, const void* k, const void* 
                                       const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes,
                                       u2tok_stream_t stream);
 
+/* ---- the decoder's training route (u2tokenizer_amd/decoder_train.py; opt-in): the backward of the decoder layer ------------
+ * Causal grouped-query attention with a per-sequence key length: u2tok_attention_gqa's call, plus kv_len (device int32[nb]
+ * or NULL: query i of sequence b sees key j iff j <= i + Skv - Sq and j < kv_len[b] -- HF's causal mask of a right-padded
+ * 2-D attention mask; kv_len[b] >= 1) and lse (NULL, or (nb * Hq, lse_ld) floats: log2 sum_j exp2(q.k_j scale log2 e) of
+ * each query row over its visible keys, for u2tok_attention_gqa_bwd).  Both NULL: exactly u2tok_attention_gqa. */
+int u2tok_attention_gqa_ex(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                           int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                           int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_len,
+                           float* lse, int64_t lse_ld, u2tok_stream_t stream);
+/* Its backward (causal, Sq = Skv = S, d = 64 or 128): dq, dk, dv from q, k, v, out, d_out and (optional) lse of
+ * u2tok_attention_gqa_ex, honouring kv_len.  Layout of u2tok_flash_attention_d64_bwd with Hq query heads (q / dq: head h at
+ * column h*d) and Hkv kv heads (k, v / dk, dv: head h at column h*d of their pointers): with q | k | v column views of one
+ * packed (rows, (Hq + 2 Hkv) d) buffer, dq | dk | dv land in one packed gradient.  dk / dv of a kv head sum its Hq / Hkv query
+ * heads in a fixed order; no atomics: bit-repeatable.  workspace: u2tok_attention_gqa_bwd_workspace_bytes(), 256-byte aligned. */
+size_t u2tok_attention_gqa_bwd_workspace_bytes(int32_t nb, int32_t S, int32_t Hq);
+int u2tok_attention_gqa_bwd(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t bs_qkv, const void* out,
+                            const void* d_out, int64_t ld_o, int64_t bs_o, void* dq, void* dk, void* dv, int64_t ld_d, int64_t bs_d,
+                            int32_t nb, int32_t S, int32_t Hq, int32_t Hkv, int32_t d, float scale, const int32_t* kv_len,
+                            const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* RMSNorm backward (forward: u2tok_rmsnorm_bf16; x, dy, dres, dx dense (rows, C), C % 8 == 0, C <= 4096):
+ *   dx = d/dx + dres (dres: the residual stream's gradient, or NULL);  dw (fp32, C) = sum_rows dy bf16(x rstd), added to dw when
+ *   accumulate, in a fixed order.  workspace: u2tok_rmsnorm_bwd_workspace_bytes(). */
+size_t u2tok_rmsnorm_bwd_workspace_bytes(int32_t rows, int32_t C);
+int u2tok_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, void* dx, float* dw, int32_t rows, int32_t C,
+                      float eps, void* workspace, size_t workspace_bytes, int32_t accumulate, u2tok_stream_t stream);
+/* Head norm + rotary backward, in place on the q / k columns of a packed gradient dqkv[rows][(Hq + 2 Hkv) D] (forward:
+ * u2tok_qk_norm_rope): the inverse rotation, then (wq / wk given) the per-head RMSNorm backward from the pre-norm q | k heads
+ * pre[rows][ld_pre >= (Hq + Hkv) D], dwq / dwk (fp32, D) summed over rows and heads; v columns untouched.
+ * workspace: u2tok_qk_norm_rope_bwd_workspace_bytes() (norm only; may be NULL without). */
+size_t u2tok_qk_norm_rope_bwd_workspace_bytes(int64_t rows, int32_t D);
+int u2tok_qk_norm_rope_bwd(void* dqkv, const void* pre, const void* wq, const void* wk, const void* cos, const void* sin,
+                           int32_t cos_sin_f32, int64_t rows, int32_t Hq, int32_t Hkv, int32_t D, int64_t ld, int64_t ld_pre,
+                           int64_t cs_ld, float eps, float* dwq, float* dwk, void* workspace, size_t workspace_bytes,
+                           int32_t accumulate, u2tok_stream_t stream);
+/* SwiGLU backward (forward: u2tok_swiglu_bf16): from the gate | up pre-activations gu[rows][ld_gu >= 2I] and d(act)
+ * dact[rows][ld_da >= I]: dgu[rows][ld_dgu >= 2I] = [d_gate | d_up], the packed gradient of the gate|up product. */
+int u2tok_swiglu_bwd(const void* gu, const void* dact, void* dgu, int64_t rows, int32_t I, int64_t ld_gu, int64_t ld_da,
+                     int64_t ld_dgu, u2tok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

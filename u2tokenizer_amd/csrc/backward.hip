@@ -523,4 +523,267 @@ int adamw_step(float* master, float* m, float* v, const bf16_t* grad, const uint
   return launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------ decoder training route
+// Backward of the decoder layer's row operations (u2tokenizer_amd/decoder_train.py).  The forwards are decoder.hip's; the
+// rounding points of HF's modules are followed where the reference autograd has them (bf16 tensors between the ops).
+
+// RMSNorm:  xhat = x rstd (fp32),  n = bf16(xhat),  y = bf16(n w).   g = bf16(dy w):
+//   dx = rstd (g - xhat mean_c(g xhat)) (+ dres: the residual stream's gradient added in the same pass);  dw (+)= sum_rows dy n
+// One wave per row, rows_per_wave rows per wave (lnb_rows_per_wave), the lane's dw partials in registers; the four waves
+// combine through LDS in a fixed order into one partial row per workgroup, colsum_finish adds those in a fixed order.
+template <int NC>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                          const bf16_t* __restrict__ dy, const bf16_t* __restrict__ dres,
+                                                          bf16_t* __restrict__ dx, float* __restrict__ part_w, int rows, int C,
+                                                          float eps, int rpw) {
+  __shared__ float red[3][512];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int nchunk = C >> 3;
+  float aw[NC][8], wr[NC][8];
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = i * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { aw[i][j] = 0.f; wr[i][j] = 0.f; }
+    if (c < nchunk) unpack8(*reinterpret_cast<const uint4*>(w + c * 8), wr[i]);
+  }
+  const int r_begin = (blockIdx.x * 4 + wv) * rpw;
+  for (int rr = 0; rr < rpw; ++rr) {
+    const int r = r_begin + rr;
+    if (r >= rows) break;  // wave-uniform
+    float v[NC][8], g[NC][8];
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = i * 64 + lane;
+      if (c < nchunk) {
+        unpack8(*reinterpret_cast<const uint4*>(x + (int64_t)r * C + c * 8), v[i]);
+        unpack8(*reinterpret_cast<const uint4*>(dy + (int64_t)r * C + c * 8), g[i]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sq += v[i][j] * v[i][j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { v[i][j] = 0.f; g[i][j] = 0.f; }
+      }
+    }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i)
+      if (i * 64 + lane < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float xh = v[i][j] * rstd;
+          v[i][j] = xh;
+          aw[i][j] += g[i][j] * bf16_to_f32(f32_to_bf16(xh));
+          g[i][j] = bf16_to_f32(f32_to_bf16(g[i][j] * wr[i][j]));
+          s2 += g[i][j] * xh;
+        }
+      }
+    s2 = wave_sum(s2) / (float)C;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = i * 64 + lane;
+      if (c < nchunk) {
+        float o[8], q[8];
+        if (dres) unpack8(*reinterpret_cast<const uint4*>(dres + (int64_t)r * C + c * 8), q);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = rstd * (g[i][j] - v[i][j] * s2) + (dres ? q[j] : 0.f);
+        *reinterpret_cast<uint4*>(dx + (int64_t)r * C + c * 8) = pack8(o);
+      }
+    }
+  }
+  // partial dw of this workgroup, 512 columns at a time: waves 1..3 hand theirs to wave 0 through LDS, fixed order
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    if (wv > 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wv - 1][lane * 8 + j] = aw[i][j];
+    }
+    __syncthreads();
+    const int c = i * 64 + lane;
+    if (wv == 0 && c < nchunk) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) part_w[(int64_t)blockIdx.x * C + c * 8 + j] = ((aw[i][j] + red[0][lane * 8 + j]) + red[1][lane * 8 + j]) + red[2][lane * 8 + j];
+    }
+    __syncthreads();
+  }
+}
+
+size_t rmsnorm_bwd_workspace_bytes(int rows, int C) {
+  if (rows <= 0 || C <= 0) return 0;
+  return (size_t)cdiv(rows, 4 * lnb_rows_per_wave(rows)) * C * sizeof(float);
+}
+
+int rmsnorm_bwd(const bf16_t* x, const bf16_t* w, const bf16_t* dy, const bf16_t* dres, bf16_t* dx, float* dw, int rows, int C,
+                float eps, float* ws, size_t ws_bytes, int accumulate, hipStream_t st) {
+  if (!x || !w || !dy || !dx || !dw || !ws || rows <= 0 || C <= 0 || (C & 7) || C > 4096) return U2_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx) & 15) return U2_ERR_ARG;
+  if (ws_bytes < rmsnorm_bwd_workspace_bytes(rows, C)) return U2_ERR_WORKSPACE;
+  const int rpw = lnb_rows_per_wave(rows);
+  const int nwg = (int)cdiv(rows, 4 * rpw);
+  ProfScope ps(PROF_ROWOP, 0, st, (double)rows * C * 2.0 * (dres ? 4.0 : 3.0));
+#define U2_RNB(NC) \
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<NC>), dim3(nwg), dim3(256), 0, st, x, w, dy, dres, dx, ws, rows, C, eps, rpw)
+  if (C <= 1024) U2_RNB(2);
+  else if (C <= 2048) U2_RNB(4);
+  else U2_RNB(8);
+#undef U2_RNB
+  colsum_finish(ws, dw, nullptr, nwg, C, accumulate, st);
+  return launch_status();
+}
+
+// Head norm + rotary, backward, in place on the q and k column blocks of the packed gradient dqkv[rows][(Hq + 2 Hkv) D]
+// (decoder.hip: qk_norm_rope_kernel is the forward; v columns untouched):
+//   inverse rotation   da = dy_a cos_a + dy_b sin_b,   db = dy_b cos_b - dy_a sin_a   (pair a = l, b = l + D/2)
+//   per-head RMSNorm   (wq / wk given: Qwen3's q_norm / k_norm) from the pre-norm q / k heads `pre` -- as rmsnorm_bwd, with
+//                      dwq / dwk summed over rows and heads.
+// A wave walks rows_per_wave rows and, per row, all Hq + Hkv heads in order; its lanes keep dwq / dwk partials of their two
+// columns; the waves combine through LDS into one partial row per workgroup, colsum_finish2 adds those in a fixed order.
+template <int D, typename CS>
+__global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(bf16_t* __restrict__ dqkv, const bf16_t* __restrict__ pre,
+                                                               const bf16_t* __restrict__ wq, const bf16_t* __restrict__ wk,
+                                                               const CS* __restrict__ cosp, const CS* __restrict__ sinp,
+                                                               int64_t rows, int Hq, int Hkv, int64_t ld, int64_t ld_pre,
+                                                               int64_t cs_ld, float eps, float* __restrict__ part, int rpw) {
+  constexpr int HALF = D / 2;
+  __shared__ float red[3][2][2 * 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const bool on = lane < HALF;
+  const bool norm = wq != nullptr;
+  float pq[2] = {0.f, 0.f}, pk[2] = {0.f, 0.f};
+  float wqa = 0.f, wqb = 0.f, wka = 0.f, wkb = 0.f;
+  if (norm && on) {
+    wqa = bf16_to_f32(wq[lane]); wqb = bf16_to_f32(wq[lane + HALF]);
+    wka = bf16_to_f32(wk[lane]); wkb = bf16_to_f32(wk[lane + HALF]);
+  }
+  const int64_t r_begin = ((int64_t)blockIdx.x * 4 + wv) * rpw;
+  for (int rr = 0; rr < rpw; ++rr) {
+    const int64_t row = r_begin + rr;
+    if (row >= rows) break;  // wave-uniform
+    float c0 = 0.f, c1 = 0.f, s0 = 0.f, s1 = 0.f;
+    if (on) {
+      const CS* cr = cosp + row * cs_ld;
+      const CS* sr = sinp + row * cs_ld;
+      c0 = (float)cr[lane]; c1 = (float)cr[lane + HALF]; s0 = (float)sr[lane]; s1 = (float)sr[lane + HALF];
+    }
+    for (int hh = 0; hh < Hq + Hkv; ++hh) {
+      bf16_t* p = dqkv + row * ld + (int64_t)hh * D;
+      float ya = 0.f, yb = 0.f;
+      if (on) { ya = bf16_to_f32(p[lane]); yb = bf16_to_f32(p[lane + HALF]); }
+      // forward: ra = a c0 - b s0,  rb = b c1 + a s1
+      float da = ya * c0 + yb * s1, db = yb * c1 - ya * s0;
+      if (norm) {
+        const bool isq = hh < Hq;
+        const float wa = isq ? wqa : wka, wb = isq ? wqb : wkb;
+        float xa = 0.f, xb = 0.f;
+        if (on) {
+          const bf16_t* x = pre + row * ld_pre + (int64_t)hh * D;
+          xa = bf16_to_f32(x[lane]); xb = bf16_to_f32(x[lane + HALF]);
+        }
+        const float rstd = rsqrtf(wave_sum(xa * xa + xb * xb) / (float)D + eps);
+        const float ha = xa * rstd, hb = xb * rstd;
+        const float na = bf16_to_f32(f32_to_bf16(ha)), nb = bf16_to_f32(f32_to_bf16(hb));
+        const float dwa = da * na, dwb = db * nb;
+        if (isq) { pq[0] += dwa; pq[1] += dwb; } else { pk[0] += dwa; pk[1] += dwb; }
+        const float ga = bf16_to_f32(f32_to_bf16(da * wa)), gb = bf16_to_f32(f32_to_bf16(db * wb));
+        const float s2 = wave_sum(ga * ha + gb * hb) / (float)D;
+        da = rstd * (ga - ha * s2);
+        db = rstd * (gb - hb * s2);
+      }
+      if (on) { p[lane] = f32_to_bf16(da); p[lane + HALF] = f32_to_bf16(db); }
+    }
+  }
+  if (!norm) return;  // (block-uniform)
+  if (wv > 0) {
+    red[wv - 1][0][lane] = pq[0]; red[wv - 1][0][64 + lane] = pq[1];
+    red[wv - 1][1][lane] = pk[0]; red[wv - 1][1][64 + lane] = pk[1];
+  }
+  __syncthreads();
+  if (wv == 0 && on) {
+    float* dst_q = part + (int64_t)blockIdx.x * D;
+    float* dst_k = part + ((int64_t)gridDim.x + blockIdx.x) * D;
+    dst_q[lane] = ((pq[0] + red[0][0][lane]) + red[1][0][lane]) + red[2][0][lane];
+    dst_q[lane + HALF] = ((pq[1] + red[0][0][64 + lane]) + red[1][0][64 + lane]) + red[2][0][64 + lane];
+    dst_k[lane] = ((pk[0] + red[0][1][lane]) + red[1][1][lane]) + red[2][1][lane];
+    dst_k[lane + HALF] = ((pk[1] + red[0][1][64 + lane]) + red[1][1][64 + lane]) + red[2][1][64 + lane];
+  }
+}
+
+static int qkb_rows_per_wave(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>(8, rows / 1024)); }
+
+size_t qk_norm_rope_bwd_workspace_bytes(int64_t rows, int D) {
+  if (rows <= 0 || D <= 0) return 0;
+  return (size_t)2 * cdiv(rows, 4 * qkb_rows_per_wave(rows)) * D * sizeof(float);
+}
+
+struct Bf16Cs {  // bf16 cos / sin tables
+  bf16_t v;
+  __device__ explicit operator float() const { return bf16_to_f32(v); }
+};
+
+int qk_norm_rope_bwd(bf16_t* dqkv, const bf16_t* pre, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp,
+                     int cs_is_f32, int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t ld_pre, int64_t cs_ld, float eps,
+                     float* dwq, float* dwk, float* ws, size_t ws_bytes, int accumulate, hipStream_t st) {
+  if (!dqkv || !cosp || !sinp || rows <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 96 && D != 128)) return U2_ERR_ARG;
+  if ((!wq) != (!wk) || (wq && (!pre || !dwq || !dwk || !ws))) return U2_ERR_ARG;
+  if (ld < (int64_t)(Hq + 2 * Hkv) * D || (wq && ld_pre < (int64_t)(Hq + Hkv) * D) || cs_ld < D) return U2_ERR_ARG;
+  const int rpw = qkb_rows_per_wave(rows);
+  const int64_t nwg = cdiv(rows, 4 * rpw);
+  if (nwg > 0x7fffffff) return U2_ERR_ARG;
+  if (wq && ws_bytes < qk_norm_rope_bwd_workspace_bytes(rows, D)) return U2_ERR_WORKSPACE;
+  ProfScope ps(PROF_ROWOP, 0, st, (double)rows * (Hq + Hkv) * D * (wq ? 6.0 : 4.0));
+#define U2_QKB(D_, T_)                                                                                                        \
+  hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<D_, T_>), dim3((unsigned)nwg), dim3(256), 0, st, dqkv, pre, wq, wk,             \
+                     reinterpret_cast<const T_*>(cosp), reinterpret_cast<const T_*>(sinp), rows, Hq, Hkv, ld, ld_pre, cs_ld, eps, \
+                     ws, rpw)
+  if (D == 128 && cs_is_f32) U2_QKB(128, float);
+  else if (D == 128) U2_QKB(128, Bf16Cs);
+  else if (D == 96 && cs_is_f32) U2_QKB(96, float);
+  else if (D == 96) U2_QKB(96, Bf16Cs);
+  else if (cs_is_f32) U2_QKB(64, float);
+  else U2_QKB(64, Bf16Cs);
+#undef U2_QKB
+  if (wq) colsum_finish2(ws, dwq, ws + nwg * D, dwk, (int)nwg, D, accumulate, st);
+  return launch_status();
+}
+
+// SwiGLU:  act = bf16(silu(g)) * u  (rounded).   d_up = dact bf16(silu(g)),  d_gate = bf16(dact u) silu'(g),
+//   silu'(g) = sigma(g) (1 + g (1 - sigma(g)))   -- into one packed (rows, 2I) gradient [d_gate | d_up] for the gate|up product.
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restrict__ gu, const bf16_t* __restrict__ dact,
+                                                         bf16_t* __restrict__ dgu, int64_t rows, int I, int64_t ld_gu,
+                                                         int64_t ld_da, int64_t ld_dgu) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per = I >> 3;
+  if (idx >= rows * per) return;
+  const int64_t r = idx / per;
+  const int c = (int)(idx - r * per) * 8;
+  float g[8], u[8], d[8], og[8], ou[8];
+  unpack8(*reinterpret_cast<const uint4*>(gu + r * ld_gu + c), g);
+  unpack8(*reinterpret_cast<const uint4*>(gu + r * ld_gu + I + c), u);
+  unpack8(*reinterpret_cast<const uint4*>(dact + r * ld_da + c), d);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float sg = 1.0f / (1.0f + __expf(-g[j]));
+    const float s = bf16_to_f32(f32_to_bf16(g[j] * sg));
+    ou[j] = d[j] * s;
+    og[j] = bf16_to_f32(f32_to_bf16(d[j] * u[j])) * (sg * (1.0f + g[j] * (1.0f - sg)));
+  }
+  *reinterpret_cast<uint4*>(dgu + r * ld_dgu + c) = pack8(og);
+  *reinterpret_cast<uint4*>(dgu + r * ld_dgu + I + c) = pack8(ou);
+}
+
+int swiglu_bwd(const bf16_t* gu, const bf16_t* dact, bf16_t* dgu, int64_t rows, int I, int64_t ld_gu, int64_t ld_da,
+               int64_t ld_dgu, hipStream_t st) {
+  if (!gu || !dact || !dgu || rows <= 0 || I <= 0 || (I & 7) || (ld_gu & 7) || (ld_da & 7) || (ld_dgu & 7)) return U2_ERR_ARG;
+  if (ld_gu < 2 * (int64_t)I || ld_da < I || ld_dgu < 2 * (int64_t)I) return U2_ERR_ARG;
+  if (((uintptr_t)gu | (uintptr_t)dact | (uintptr_t)dgu) & 15) return U2_ERR_ARG;
+  const int64_t total = rows * (I >> 3);
+  if (cdiv(total, 256) > 0x7fffffff) return U2_ERR_ARG;
+  ProfScope ps(PROF_ROWOP, 0, st, (double)rows * I * 10.0);
+  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, gu, dact, dgu, rows, I, ld_gu, ld_da,
+                     ld_dgu);
+  return launch_status();
+}
+
 }  // namespace u2

@@ -386,4 +386,41 @@ int32_t u2tok_flash_attention_d64_bwd(const void* q, const void* k, const void* 
                                  ld_d, bs_d, nb, S, H, scale, lse, lse_ld, workspace, workspace_bytes, ST(stream));
 }
 
+// ---- the decoder's training route
+int u2tok_attention_gqa_ex(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                           int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                           int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_len,
+                           float* lse, int64_t lse_ld, u2tok_stream_t stream) {
+  return attention_gqa_ex(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
+                          scale, causal, kv_len, lse, lse_ld, ST(stream));
+}
+size_t u2tok_attention_gqa_bwd_workspace_bytes(int32_t nb, int32_t S, int32_t Hq) {
+  return attention_gqa_bwd_workspace_bytes(nb, S, Hq);
+}
+int u2tok_attention_gqa_bwd(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t bs_qkv, const void* out,
+                            const void* d_out, int64_t ld_o, int64_t bs_o, void* dq, void* dk, void* dv, int64_t ld_d, int64_t bs_d,
+                            int32_t nb, int32_t S, int32_t Hq, int32_t Hkv, int32_t d, float scale, const int32_t* kv_len,
+                            const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return attention_gqa_bwd(BF(q), BF(k), BF(v), ld_qkv, bs_qkv, BF(out), BF(d_out), ld_o, bs_o, BFW(dq), BFW(dk), BFW(dv), ld_d,
+                           bs_d, nb, S, Hq, Hkv, d, scale, kv_len, lse, lse_ld, workspace, workspace_bytes, ST(stream));
+}
+size_t u2tok_rmsnorm_bwd_workspace_bytes(int32_t rows, int32_t C) { return rmsnorm_bwd_workspace_bytes(rows, C); }
+int u2tok_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, void* dx, float* dw, int32_t rows, int32_t C,
+                      float eps, void* workspace, size_t workspace_bytes, int32_t accumulate, u2tok_stream_t stream) {
+  return rmsnorm_bwd(BF(x), BF(w), BF(dy), BF(dres), BFW(dx), dw, rows, C, eps, reinterpret_cast<float*>(workspace),
+                     workspace_bytes, accumulate, ST(stream));
+}
+size_t u2tok_qk_norm_rope_bwd_workspace_bytes(int64_t rows, int32_t D) { return qk_norm_rope_bwd_workspace_bytes(rows, D); }
+int u2tok_qk_norm_rope_bwd(void* dqkv, const void* pre, const void* wq, const void* wk, const void* cos, const void* sin,
+                           int32_t cos_sin_f32, int64_t rows, int32_t Hq, int32_t Hkv, int32_t D, int64_t ld, int64_t ld_pre,
+                           int64_t cs_ld, float eps, float* dwq, float* dwk, void* workspace, size_t workspace_bytes,
+                           int32_t accumulate, u2tok_stream_t stream) {
+  return qk_norm_rope_bwd(BFW(dqkv), BF(pre), BF(wq), BF(wk), cos, sin, cos_sin_f32, rows, Hq, Hkv, D, ld, ld_pre, cs_ld, eps, dwq,
+                          dwk, reinterpret_cast<float*>(workspace), workspace_bytes, accumulate, ST(stream));
+}
+int u2tok_swiglu_bwd(const void* gu, const void* dact, void* dgu, int64_t rows, int32_t I, int64_t ld_gu, int64_t ld_da,
+                     int64_t ld_dgu, u2tok_stream_t stream) {
+  return swiglu_bwd(BF(gu), BF(dact), BFW(dgu), rows, I, ld_gu, ld_da, ld_dgu, ST(stream));
+}
+
 }  // extern "C"

@@ -239,6 +239,28 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
                  float scale, const bf16_t* rel_bias, int max_len, int causal, int force_splits, void* ws, size_t ws_bytes,
                  hipStream_t stream);
+// The decoder training route (u2tokenizer_amd/decoder_train.py).  attention_gqa_ex (tokattn.hip): attention_ex's causal GQA
+// call with per-sequence key lengths kv_len (key j of sequence b visible iff j < kv_len[b]) and optional row statistics lse
+// ((nb * H, lse_ld), log2 units); both null: attention_ex itself.  attention_gqa_bwd (attn_gqa_bwd.hip): its flash backward,
+// d = 64 / 128, Sq = Skv = S, layout of flash_attention_d64_bwd with Hq query and Hkv kv heads.  rmsnorm_bwd,
+// qk_norm_rope_bwd, swiglu_bwd (backward.hip): the row operations' backward.
+int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
+                     int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
+                     int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld, hipStream_t stream);
+size_t attention_gqa_bwd_workspace_bytes(int nb, int S, int Hq);
+int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
+                      const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
+                      int64_t bs_d, int nb, int S, int Hq, int Hkv, int d, float scale, const int* kv_len, const float* lse_in,
+                      int64_t lse_ld, void* workspace, size_t workspace_bytes, hipStream_t stream);
+size_t rmsnorm_bwd_workspace_bytes(int rows, int C);
+int rmsnorm_bwd(const bf16_t* x, const bf16_t* w, const bf16_t* dy, const bf16_t* dres, bf16_t* dx, float* dw, int rows, int C,
+                float eps, float* ws, size_t ws_bytes, int accumulate, hipStream_t st);
+size_t qk_norm_rope_bwd_workspace_bytes(int64_t rows, int D);
+int qk_norm_rope_bwd(bf16_t* dqkv, const bf16_t* pre, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp,
+                     int cs_is_f32, int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t ld_pre, int64_t cs_ld, float eps,
+                     float* dwq, float* dwk, float* ws, size_t ws_bytes, int accumulate, hipStream_t st);
+int swiglu_bwd(const bf16_t* gu, const bf16_t* dact, bf16_t* dgu, int64_t rows, int I, int64_t ld_gu, int64_t ld_da,
+               int64_t ld_dgu, hipStream_t st);
 // ------------------------------------------------------------------ decoder prefill row kernels (decoder.hip)
 int rmsnorm_bf16(const bf16_t* x, const bf16_t* w, bf16_t* y, int64_t rows, int C, int64_t ldx, int64_t ldy, float eps,
                  hipStream_t stream);

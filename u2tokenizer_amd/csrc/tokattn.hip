@@ -57,6 +57,10 @@ struct TokAttnArgs {
   float* ml;     // ns > 1: [ns][nb * H][Sq][2] = (running max in log2 units, row sum)
   int kv_group;  // grouped-query attention: query head h reads key / value head h / kv_group (1: plain multi-head)
   int causal;    // 1: key j is visible to query i iff j <= i + (Skv - Sq)   (decoder prefill)
+  // tok_attn_kernel<DH, true> only (u2tok_attention_gqa_ex, the decoder's training route):
+  const int* kv_len;  // optional (nb): key j of sequence b is visible only if j < kv_len[b] (right padding)
+  float* lse;         // optional (nb * H, lse_ld): log2 sum_j exp2(s_ij scale log2 e) of each query row, for the backward
+  int64_t lse_ld;
 };
 
 constexpr float TOKATTN_RESCALE_THR = 8.0f;
@@ -73,7 +77,7 @@ __device__ __forceinline__ int t96_pos(int row, int L) { return L ^ ((row >> 1) 
 
 typedef short ta_v4s_t __attribute__((ext_vector_type(4)));
 
-template <int DH>
+template <int DH, bool EX = false>  // EX: per-sequence key lengths and row statistics (TokAttnArgs::kv_len / lse)
 __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const TokAttnArgs a) {
   constexpr int BK = DH <= 128 ? 64 : 32;  // keys per tile (narrow heads: twice the keys per barrier / DMA wait / softmax step)
   constexpr int NKB = BK / 16;        // 16-key blocks of S^T per tile
@@ -114,6 +118,13 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
   const int c_off = Skv - Sq;  // causal: query i sees keys j <= i + c_off
   int kt1_ = min(ntile_all, sp * a.tps + a.tps);
   if (a.causal) kt1_ = min(kt1_, (q0 + 63 + c_off) / BK + 1);  // tiles past the block's last visible key are skipped
+  int kvl = Skv;  // (EX) keys at or beyond kv_len[b] are invisible: their tiles are skipped, a partial tile masked
+  if constexpr (EX) {
+    if (a.kv_len) {
+      kvl = max(1, min(a.kv_len[b], Skv));
+      kt1_ = min(kt1_, (kvl + BK - 1) / BK);
+    }
+  }
   const int kt0 = sp * a.tps, kt1 = kt1_;
   const int kbeg = kt0 * BK;
 
@@ -253,6 +264,13 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       for (int i = 0; i < NX; ++i)
         if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) > qrow + c_off) x[i] = -INFINITY;
     }
+    if constexpr (EX) {
+      if (kt * BK + BK > kvl) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+          if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) >= kvl) x[i] = -INFINITY;
+      }
+    }
     float mt = x[0];
 #pragma unroll
     for (int i = 1; i < NX; ++i) mt = fmaxf(mt, x[i]);
@@ -319,6 +337,9 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
   float l_tot = l_run + __shfl_xor(l_run, 16, 64);
   l_tot += __shfl_xor(l_tot, 32, 64);
   if (qrow >= Sq) return;
+  if constexpr (EX) {
+    if (a.lse && g == 0) a.lse[((int64_t)b * a.H + h) * a.lse_ld + qrow] = m_run + __builtin_log2f(l_tot);
+  }
   if (a.ns == 1) {
     const float inv = 1.f / l_tot;
     bf16_t* op = a.out + (int64_t)b * a.o_bs + (int64_t)qrow * a.ldo + h * DH + 4 * g;
@@ -792,6 +813,7 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
   const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
   a.kv_group = H / Hkv;
   a.causal = causal ? 1 : 0;
+  a.kv_len = nullptr; a.lse = nullptr; a.lse_ld = 0;
   int ns = force_splits > 0 ? std::min(force_splits, ntile) : tok_attn_pick_splits(nb, H, Sq, Skv, d, ws ? ws_bytes : 0);
   if (causal) ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
   const size_t per = (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
@@ -841,6 +863,49 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
 #undef U2_CMB
 
   }
+  return launch_status();
+}
+
+// The decoder training route's forward: attention_ex's causal / plain GQA call without key splits, plus per-sequence key lengths
+// (kv_len) and the row statistics the backward reuses (lse).  Both NULL: exactly u2tok_attention_gqa (the same kernel).
+int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
+                     int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
+                     int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld,
+                     hipStream_t stream) {
+  if (!kv_len && !lse)
+    return attention_ex(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, nullptr, 0,
+                        causal, 1, nullptr, 0, stream);
+  if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
+  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq)) return U2_ERR_ARG;
+  if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
+    return U2_ERR_ARG;
+  TokAttnArgs a;
+  a.q = q; a.k = k; a.v = v; a.out = out;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
+  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
+  a.scale_log2e = scale * 1.44269504088896340736f;
+  a.rel_bias = nullptr; a.max_len = 0;
+  a.kv_group = H / Hkv;
+  a.causal = causal ? 1 : 0;
+  a.kv_len = kv_len; a.lse = lse; a.lse_ld = lse_ld;
+  a.ns = 1;
+  a.tps = (int)cdiv(Skv, tok_attn_bk(d));
+  a.opart = nullptr; a.ml = nullptr;
+  const int64_t grid = (int64_t)nb * H * a.nqb;
+  if (grid > 0x7fffffff) return U2_ERR_ARG;
+  ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
+               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));
+#define U2_TAX(D_)                                                                                                     \
+  do {                                                                                                                 \
+    constexpr size_t smem_ = 4 * ((D_) <= 128 ? 64 : 32) * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                          \
+    hipLaunchKernelGGL((tok_attn_kernel<D_, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);                \
+  } while (0)
+  if (d == 512) U2_TAX(512);
+  else if (d == 256) U2_TAX(256);
+  else if (d == 128) U2_TAX(128);
+  else if (d == 96) U2_TAX(96);
+  else U2_TAX(64);
+#undef U2_TAX
   return launch_status();
 }
 

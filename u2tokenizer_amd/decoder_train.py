@@ -1,0 +1,301 @@
+"""Training route of the decoder layers (opt-in): the layer's forward AND backward on the library's kernels.
+
+`enable_fused_prefill(model, train=True)` (prefill.py) -- or `config.u2_fused_decoder_training = True` on a u2 causal LM --
+makes a patched Llama / Qwen3 decoder layer that is called with grad enabled run as
+
+    RMSNormFn -> PackedLinearFn (q|k|v) -> HeadNormRopeFn -> GqaAttentionFn -> PackedLinearFn (o, + residual)
+    -> RMSNormFn -> PackedLinearFn (gate|up) -> SwiGLUFn -> PackedLinearFn (down, + residual)
+
+torch.autograd.Functions over the C-ABI blocks, each saving what its backward needs:
+  * the products run on u2tok_gemm_bf16 both ways (dX = dY W and dW = dY^T X on the K-major operand forms, as autograd.LinearFn).
+    q|k|v and gate|up use the packed buffers prefill._pack lays out (the nn.Parameters are views of them): ONE product forward,
+    ONE packed dW backward, handed to autograd as one view per Parameter -- `.grad` of q_proj / k_proj / v_proj (or gate / up)
+    receives its rows, accumulated in place into an existing `.grad` (a view into a flat optimizer bucket stays one);
+  * the attention is the causal GQA kernel with per-sequence key lengths (u2tok_attention_gqa_ex, which also leaves the row
+    statistics) and its flash backward (u2tok_attention_gqa_bwd), which writes dq | dk | dv straight into one packed gradient;
+  * RMSNorm, head norm + rotary and SwiGLU have their backward kernels in csrc/backward.hip (fixed-order fp32 weight gradients);
+  * torch moves data and adds the residual stream's two gradient contributions.
+
+When a layer takes the route (route_conditions below, checked on every call; everything else keeps the stock forward):
+bf16 on the GPU, every projection exactly nn.Linear with no hooks, no active attention dropout, head dim 64 or 128, no KV
+cache, no sliding window, and an attention mask that is causal with at most right padding.  The mask is read from the
+LAYER's own `attention_mask` argument (the 4-D mask HF builds, or None) and the verdict is stored on that tensor: the
+recompute of non-reentrant gradient checkpointing calls the layer with the same argument objects, so it sees the key
+lengths of ITS forward, not those of whatever forward of the model ran last.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch.autograd import Function
+
+from . import ops
+from .autograd import _bind_context
+
+BF = torch.bfloat16
+
+# layers whose forward took the training route (tests read it: a route that silently fell back to the stock layers would
+# otherwise pass every gradient check)
+stats = {"layers": 0}
+
+
+def train_mask_rule(mask: Optional[torch.Tensor]):
+    """The 2-D attention masks the training route computes: ("causal", None) for no mask or all ones, ("lengths", lens) for
+    right padding (every row ones then zeros, at least one one; lens int64 (B,)), None for anything else (left padding, holes,
+    an empty row: stock layers).  Pure tensor logic: runs on the CPU as well."""
+    if mask is None:
+        return "causal", None
+    if not torch.is_tensor(mask) or mask.dim() != 2 or mask.shape[1] == 0:
+        return None
+    m = mask.to(torch.bool)
+    if bool(m.all()):
+        return "causal", None
+    lens = m.sum(dim=1)
+    pos = torch.arange(m.shape[1], device=m.device)
+    if bool((lens < 1).any()) or not bool(torch.equal(m, pos[None, :] < lens[:, None])):
+        return None
+    return "lengths", lens
+
+
+def layer_mask_kv_len(am, B: int, S: int):
+    """Verdict on a decoder LAYER's attention_mask argument: (True, None) plain causal, (True, kv_len int32 (B,) on the mask's
+    device) right padding, (False, None) anything else.  HF hands layers None (sdpa, no padding) or the 4-D (B, 1, S, S) mask
+    it built (bool: True = visible; float: 0 = visible); its last query row is the 2-D key mask, and the whole mask must equal
+    causal AND key < length.  Stored on the mask tensor (one check per model forward, and the recompute reads the same)."""
+    if am is None:
+        return True, None
+    if not torch.is_tensor(am):
+        return False, None
+    hit = getattr(am, "_u2_train_kv", None)
+    if hit is not None:
+        return hit
+    verdict = (False, None)
+    if am.dim() == 4 and am.shape[0] == B and am.shape[1] == 1 and am.shape[2] == S and am.shape[3] == S:
+        vis = am if am.dtype == torch.bool else am == 0
+        rule = train_mask_rule(vis[:, 0, -1, :])
+        if rule is not None:
+            pos = torch.arange(S, device=am.device)
+            causal = pos[None, :] <= pos[:, None]
+            if rule[0] == "causal":
+                want = causal[None].expand(B, S, S)
+            else:
+                want = causal[None] & (pos[None, None, :] < rule[1][:, None, None])
+            if bool(torch.equal(vis[:, 0], want)):
+                verdict = (True, None if rule[0] == "causal" else rule[1].to(torch.int32).contiguous())
+    try:
+        am._u2_train_kv = verdict
+    except (AttributeError, RuntimeError):
+        pass
+    return verdict
+
+
+# ------------------------------------------------------------------------------------------------ Functions
+@_bind_context
+class PackedLinearFn(Function):
+    """y = x W^T (+ b) (+ res) with W the packed rows of `nw` projections (their weights are `params[:nw]`, their biases
+    `params[nw:]`, packed in `b`).  W / b are the forward's operands (views of the Parameters' storage, no autograd); the
+    Parameters are inputs so that autograd hands each its gradient: one packed dW (and db), split into views."""
+
+    @staticmethod
+    def forward(ctx, x, res, W, b, nw: int, *params):
+        y = ops.gemm(x, W, bias=b, residual=res)
+        ctx.save_for_backward(x, W)
+        ctx.nw, ctx.has_b, ctx.has_res = nw, b is not None, res is not None
+        ctx.rows = [p.shape[0] for p in params[:nw]]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        N, K = W.shape
+        dy = dy.contiguous()
+        nw = ctx.nw
+        need = ctx.needs_input_grad
+        dx = dres = None
+        if need[0]:
+            if dy.shape[0] >= 4096 and W.numel() <= (1 << 23):   # (autograd.LinearFn: many rows against a small weight)
+                dx = ops.gemm(dy, ops.transpose_ex(W, 1, N, K, K, 0)[0])
+            else:
+                dx = ops.gemm_kmajor(dy, W, a_kmajor=False)
+        if ctx.has_res and need[1]:
+            dres = dy
+        gw = [None] * nw
+        if any(need[5:5 + nw]):
+            dW = ops.gemm_kmajor(dy, x, a_kmajor=True)   # (N, K): the packed gradient
+            o = 0
+            for i, r in enumerate(ctx.rows):
+                gw[i] = dW[o:o + r] if need[5 + i] else None
+                o += r
+        gb = [None] * (nw if ctx.has_b else 0)
+        if ctx.has_b and any(need[5 + nw:]):
+            db = ops.colsum(dy)
+            o = 0
+            for i, r in enumerate(ctx.rows):
+                gb[i] = db[o:o + r] if need[5 + nw + i] else None
+                o += r
+        return (dx, dres, None, None, None, *gw, *gb)
+
+
+def packed_linear(x, linears, W, b, res=None):
+    params = [lin.weight for lin in linears] + ([lin.bias for lin in linears] if b is not None else [])
+    return PackedLinearFn.apply(x, res, W, b, len(linears), *params)
+
+
+@_bind_context
+class RMSNormFn(Function):
+    """y = bf16(x rstd) * w  (LlamaRMSNorm / Qwen3RMSNorm); backward u2tok_rmsnorm_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, w, eps: float):
+        ctx.save_for_backward(x, w)
+        ctx.eps = eps
+        return ops.rmsnorm(x, w, eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dx, dw = ops.rmsnorm_bwd(x, w, dy, ctx.eps)
+        return dx, (dw.to(w.dtype) if ctx.needs_input_grad[1] else None), None
+
+
+@_bind_context
+class HeadNormRopeFn(Function):
+    """Per-head RMSNorm (Qwen3 q_norm / k_norm; none for Llama) + rotary embedding on the q / k columns of the packed q|k|v
+    product (u2tok_qk_norm_rope on a copy); backward u2tok_qk_norm_rope_bwd (inverse rotation, then the norm's backward)."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, wk, cos, sin, Hq: int, Hkv: int, d: int, eps: float):
+        out = qkv.clone()
+        ops.qk_norm_rope(out, wq, wk, cos, sin, Hq, Hkv, d, eps)
+        ctx.save_for_backward(qkv if wq is not None else None, wq, wk, cos, sin)
+        ctx.cfg = (Hq, Hkv, d, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        pre, wq, wk, cos, sin = ctx.saved_tensors
+        Hq, Hkv, d, eps = ctx.cfg
+        g = dy.clone(memory_format=torch.contiguous_format)
+        _, dwq, dwk = ops.qk_norm_rope_bwd(g, pre, wq, wk, cos, sin, Hq, Hkv, d, eps)
+        gq = dwq.to(wq.dtype) if wq is not None and ctx.needs_input_grad[1] else None
+        gk = dwk.to(wk.dtype) if wk is not None and ctx.needs_input_grad[2] else None
+        return g, gq, gk, None, None, None, None, None, None
+
+
+@_bind_context
+class GqaAttentionFn(Function):
+    """Causal grouped-query attention over the packed q|k|v rows (B * S, (Hq + 2 Hkv) d) with per-sequence key lengths;
+    -> (B * S, Hq d).  Backward: the flash kernel pair, dq | dk | dv into one packed gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, kv_len, B: int, S: int, Hq: int, Hkv: int, d: int, scale: float):
+        q3 = qkv.view(B, S, -1)
+        out, lse = ops.attention_gqa_ex(q3[..., :Hq * d], q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:], Hq, Hkv,
+                                        scale, kv_len=kv_len, with_lse=True)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.kv_len = kv_len
+        ctx.cfg = (B, S, Hq, Hkv, d, scale)
+        return out.view(B * S, Hq * d)
+
+    @staticmethod
+    def backward(ctx, dy):
+        qkv, out, lse = ctx.saved_tensors
+        B, S, Hq, Hkv, d, scale = ctx.cfg
+        dqkv = ops.attention_gqa_bwd(qkv.view(B, S, -1), out, dy.reshape(B, S, Hq * d), Hq, Hkv, scale, kv_len=ctx.kv_len,
+                                     lse=lse)
+        return dqkv.view(B * S, -1), None, None, None, None, None, None, None
+
+
+@_bind_context
+class SwiGLUFn(Function):
+    """act = bf16(silu(gate)) * up from the packed gate|up product (the two-step form: the pre-activations are saved);
+    backward: the packed [d_gate | d_up] (u2tok_swiglu_bwd)."""
+
+    @staticmethod
+    def forward(ctx, gu):
+        ctx.save_for_backward(gu)
+        return ops.swiglu(gu)
+
+    @staticmethod
+    def backward(ctx, dact):
+        (gu,) = ctx.saved_tensors
+        return ops.swiglu_bwd(gu, dact)
+
+
+# ------------------------------------------------------------------------------------------------ the layer
+def route_conditions(layer, x, kwargs, projections) -> bool:
+    """Everything but the mask: bf16 activations and weights on the GPU, stock projections without hooks, no active dropout,
+    head dim 64 / 128, no KV cache, no sliding window, widths the row kernels take."""
+    from .prefill import _SplitLayout, _is_stock
+    st = layer._u2_prefill
+    att = layer.self_attn
+    pe = kwargs.get("position_embeddings")
+    if st["layout"] is not _SplitLayout or not x.is_cuda or x.dtype != BF or x.dim() != 3 or x.shape[1] < 1:
+        return False
+    if projections[0].weight.dtype != BF or kwargs.get("past_key_values") is not None or kwargs.get("output_attentions"):
+        return False
+    if "past_key_value" in kwargs or pe is None or pe[0].shape[-1] != att.head_dim or att.head_dim not in (64, 128):
+        return False
+    if att.training and float(getattr(att, "attention_dropout", 0.0) or 0.0) > 0:
+        return False
+    if not _SplitLayout.ready(layer, att) or not _is_stock(layer, projections):
+        return False
+    E = x.shape[-1]
+    inter = layer.mlp.gate_proj.weight.shape[0]
+    return E % 8 == 0 and E <= 4096 and inter % 8 == 0 and layer.input_layernorm.weight.dtype == BF
+
+
+def layer_forward_train(layer, x, kwargs, kv_len):
+    """The layer's forward through the Functions above; x (B, S, E) -> (B, S, E)."""
+    from .prefill import _ensure_gemm_scratch
+    st = layer._u2_prefill
+    lo = st["layout"]
+    att, mlp = layer.self_attn, layer.mlp
+    cfg = att.config
+    B, S, E = x.shape
+    rows = B * S
+    Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
+    stats["layers"] += 1   # (counted on entry: a checkpoint recompute stops early, once the tensors it needs are back)
+    _ensure_gemm_scratch(x.device)
+    with ops.on_device(x):
+        Wqkv, bqkv = lo.qkv(layer)
+        Wgu, bgu = lo.gate_up(layer)
+        x2 = x.reshape(rows, E)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        cos, sin = kwargs["position_embeddings"]
+        cos = cos.expand(B, S, d).reshape(rows, d)
+        sin = sin.expand(B, S, d).reshape(rows, d)
+        if cos.dtype != sin.dtype or cos.dtype not in (torch.float32, BF) or cos.stride(1) != 1 or sin.stride(1) != 1 \
+                or cos.stride(0) != sin.stride(0):
+            cos, sin = cos.float().contiguous(), sin.float().contiguous()
+        cos, sin = cos.detach(), sin.detach()
+        xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
+        qkv = packed_linear(xn, (att.q_proj, att.k_proj, att.v_proj), Wqkv, bqkv)
+        qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
+        qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq,
+                                   Hkv, d, float(qn.variance_epsilon) if qn is not None else 1e-6)
+        ctx = GqaAttentionFn.apply(qkv, kv_len, B, S, Hq, Hkv, d, float(att.scaling))
+        h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
+                          att.o_proj.bias.detach(), res=x2)
+        hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
+        gu = packed_linear(hn, (mlp.gate_proj, mlp.up_proj), Wgu, bgu)
+        act = SwiGLUFn.apply(gu)
+        out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
+                            None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)
+    return out.view(B, S, E)
+
+
+def try_train_forward(layer, hidden_states, args, kwargs):
+    """The layer's output through the training route, or None (the caller runs the stock forward)."""
+    if args:
+        return None
+    pr = layer._u2_prefill["layout"].projections(layer)
+    if not route_conditions(layer, hidden_states, kwargs, pr):
+        return None
+    B, S, _ = hidden_states.shape
+    ok, kv_len = layer_mask_kv_len(kwargs.get("attention_mask"), B, S)
+    if not ok:
+        return None
+    return layer_forward_train(layer, hidden_states, kwargs, kv_len)

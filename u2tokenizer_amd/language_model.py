@@ -66,8 +66,22 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
         if p is not None and p.is_cuda and p.dtype in (torch.bfloat16, torch.float16):   # (either build of the library)
             from .prefill import enable_fused_prefill
-            enable_fused_prefill(self, strict=False)   # (layers the kernels do not compute stay stock)
+            # (layers the kernels do not compute stay stock; the training switch is kept as the config has it)
+            enable_fused_prefill(self, strict=False, train=bool(getattr(self.config, "u2_fused_decoder_training", False)))
             self._u2_prefill_checked = True
+
+    def _maybe_fuse_training(self) -> None:
+        """`config.u2_fused_decoder_training = True` (default False): a forward with grad enabled runs the decoder layers on the
+        training route of decoder_train.py (forward and backward on the HIP kernels) where its conditions hold -- bf16 on the
+        GPU, stock projections without hooks, no dropout, head dim 64 / 128, no KV cache, no padding or right padding only.
+        Patched once, when the decoder sits on the GPU in bf16; `config.u2_fused_prefill` still decides the inference route."""
+        if getattr(self, "_u2_train_checked", False):
+            return
+        p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
+        if p is not None and p.is_cuda and p.dtype == torch.bfloat16:
+            from .prefill import enable_fused_prefill
+            enable_fused_prefill(self, strict=False, train=True, prefill=bool(getattr(self.config, "u2_fused_prefill", True)))
+            self._u2_train_checked = True
 
     def forward(self, images: Optional[torch.FloatTensor] = None, input_ids: torch.LongTensor = None,
                 labels: Optional[torch.LongTensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -81,6 +95,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         question_ids = kwargs.pop("raw_question_ids", question_ids)
         if not torch.is_grad_enabled():
             self._maybe_fuse_prefill()
+        elif getattr(self.config, "u2_fused_decoder_training", False):
+            self._maybe_fuse_training()
         if inputs_embeds is None:
             (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds, labels) = \
                 self.prepare_inputs_for_multimodal(input_ids, position_ids, attention_mask, past_key_values, labels,

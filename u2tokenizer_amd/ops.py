@@ -854,3 +854,141 @@ def weight_table(tensors) -> "C.Array":
                                f"(got {t.dtype} on {t.device}); call model.to(torch.bfloat16).cuda() or model.half().cuda()")
         arr[i] = t.data_ptr()
     return arr
+
+
+# ---------------------------------------------------------------------------------- decoder training route (decoder_train.py)
+def _kv_len_arg(kv_len, nb: int, device):
+    if kv_len is None:
+        return None
+    if kv_len.dtype != torch.int32 or kv_len.device != device or kv_len.shape != (nb,) or not kv_len.is_contiguous():
+        raise RuntimeError(f"kv_len must be a contiguous int32 ({nb},) tensor on {device}")
+    return kv_len
+
+
+@_guarded
+def attention_gqa_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
+                     kv_len: Optional[torch.Tensor] = None, with_lse: bool = False, causal: bool = True):
+    """attention_gqa with per-sequence key lengths (u2tok_attention_gqa_ex): key j of sequence b is visible only if
+    j < kv_len[b] (int32 (nb,) on the GPU, >= 1; None: all).  with_lse: also returns the row statistics the backward reuses,
+    (nb * heads, Sq) fp32 in log2 units -> (out, lse | None)."""
+    h = _lib.load_library()
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _need(t, ELEM, n)
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise RuntimeError(f"attention_gqa_ex: {n} must be (nb, S, H * d) with a contiguous last dim")
+    nb, Sq, Eq = q.shape
+    Skv = k.shape[1]
+    d = Eq // heads
+    if Eq % heads or k.shape != (nb, Skv, kv_heads * d) or v.shape != k.shape or heads % kv_heads:
+        raise RuntimeError(f"attention_gqa_ex: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}")
+    kv_len = _kv_len_arg(kv_len, nb, q.device)
+    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    lse = torch.empty((nb * heads, Sq), dtype=torch.float32, device=q.device) if with_lse else None
+    _lib.check(h.u2tok_attention_gqa_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
+                                        k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
+                                        float(scale), int(bool(causal)), _ptr(kv_len), _ptr(lse), Sq if with_lse else 0,
+                                        _stream()), "u2tok_attention_gqa_ex")
+    return out, lse
+
+
+@_guarded
+def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, heads: int, kv_heads: int, scale: float,
+                      kv_len: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                      d_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal GQA flash backward (u2tok_attention_gqa_bwd): qkv (nb, S, (heads + 2 kv_heads) d) packed q | k | v (after the
+    rotary embedding), out / d_out (nb, S, heads * d) -> the packed gradient d_qkv (nb, S, (heads + 2 kv_heads) d): dq | dk | dv
+    (written into `d_qkv` if given).  d = 64 or 128; kv_len / lse as attention_gqa_ex."""
+    h = _lib.load_library()
+    _need(qkv, ELEM, "qkv")
+    nb, S, W = qkv.shape
+    d = W // (heads + 2 * kv_heads)
+    if W != (heads + 2 * kv_heads) * d or heads % kv_heads or qkv.stride(2) != 1 or qkv.stride(0) != S * qkv.stride(1):
+        raise RuntimeError(f"attention_gqa_bwd: qkv {tuple(qkv.shape)} is not a packed (nb, S, (heads + 2 kv_heads) d) buffer")
+    out = _need(out, ELEM, "out").contiguous()
+    d_out = _need(d_out, ELEM, "d_out").contiguous()
+    if out.shape != (nb, S, heads * d) or d_out.shape != out.shape:
+        raise RuntimeError(f"attention_gqa_bwd: out / d_out must be (nb, S, heads * d), got {tuple(out.shape)}, {tuple(d_out.shape)}")
+    kv_len = _kv_len_arg(kv_len, nb, qkv.device)
+    if lse is not None and (lse.dtype != torch.float32 or lse.shape != (nb * heads, S) or not lse.is_contiguous()):
+        raise RuntimeError("attention_gqa_bwd: lse must be the (nb * heads, S) fp32 statistics of attention_gqa_ex")
+    if d_qkv is None:
+        d_qkv = torch.empty((nb, S, W), dtype=elem_dtype(), device=qkv.device)
+    elif d_qkv.shape != (nb, S, W) or not d_qkv.is_contiguous() or d_qkv.dtype != elem_dtype():
+        raise RuntimeError("attention_gqa_bwd: d_qkv must be a contiguous tensor shaped like qkv")
+    nbytes = h.u2tok_attention_gqa_bwd_workspace_bytes(nb, S, heads)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ld, ldo = qkv.stride(1), heads * d
+    qp, dp = qkv.data_ptr(), d_qkv.data_ptr()
+    es = qkv.element_size()
+    _lib.check(h.u2tok_attention_gqa_bwd(qp, qp + heads * d * es, qp + (heads + kv_heads) * d * es, ld, S * ld, _ptr(out),
+                                         _ptr(d_out), ldo, S * ldo, dp, dp + heads * d * es, dp + (heads + kv_heads) * d * es, W,
+                                         S * W, nb, S, heads, kv_heads, d, float(scale), _ptr(kv_len), _ptr(lse), S if lse is not None else 0,
+                                         _ptr(ws), nbytes, _stream()), "u2tok_attention_gqa_bwd")
+    return d_qkv
+
+
+@_guarded
+def rmsnorm_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, eps: float = 1e-6, d_res: Optional[torch.Tensor] = None):
+    """Backward of rmsnorm (u2tok_rmsnorm_bwd): x, dy (rows, C) -> (dx (+ d_res), dw fp32 (C,))."""
+    h = _lib.load_library()
+    x, dy = _need(x, ELEM, "x").contiguous(), _need(dy, ELEM, "dy").contiguous()
+    rows, Cc = x.shape
+    if dy.shape != x.shape or (d_res is not None and d_res.shape != x.shape):
+        raise RuntimeError("rmsnorm_bwd: x, dy (and d_res) must have the same (rows, C) shape")
+    if d_res is not None:
+        d_res = _need(d_res, ELEM, "d_res").contiguous()
+    dx = torch.empty_like(x)
+    dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    nbytes = h.u2tok_rmsnorm_bwd_workspace_bytes(rows, Cc)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    _lib.check(h.u2tok_rmsnorm_bwd(_ptr(x), _ptr(_need(w, ELEM, "w")), _ptr(dy), _ptr(d_res), _ptr(dx), _ptr(dw), rows, Cc,
+                                   float(eps), _ptr(ws), nbytes, 0, _stream()), "u2tok_rmsnorm_bwd")
+    return dx, dw
+
+
+@_guarded
+def qk_norm_rope_bwd(d_qkv: torch.Tensor, pre: Optional[torch.Tensor], q_norm_w, k_norm_w, cos: torch.Tensor, sin: torch.Tensor,
+                     heads: int, kv_heads: int, head_dim: int, eps: float = 1e-6):
+    """Backward of qk_norm_rope, in place on the q / k columns of d_qkv (rows, (heads + 2 kv_heads) head_dim)
+    (u2tok_qk_norm_rope_bwd).  pre: the q | k columns before the head norm (rows, >= (heads + kv_heads) head_dim view with a
+    contiguous last dim), needed with norm weights.  -> (d_qkv, dwq fp32 | None, dwk fp32 | None)."""
+    h = _lib.load_library()
+    _need(d_qkv, ELEM, "d_qkv")
+    rows = d_qkv.shape[0]
+    if d_qkv.dim() != 2 or d_qkv.stride(1) != 1 or d_qkv.shape[1] != (heads + 2 * kv_heads) * head_dim:
+        raise RuntimeError("qk_norm_rope_bwd: d_qkv must be (rows, (heads + 2 kv_heads) * head_dim)")
+    if cos.dtype != sin.dtype or cos.dtype not in (torch.float32, elem_dtype()) or cos.shape != (rows, head_dim) \
+            or sin.shape != cos.shape or cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0):
+        raise RuntimeError("qk_norm_rope_bwd: cos / sin must be (rows, head_dim) fp32 or bf16 with equal strides")
+    norm = q_norm_w is not None
+    dwq = dwk = ws = None
+    nbytes = 0
+    if norm:
+        _need(pre, ELEM, "pre")
+        if pre.dim() != 2 or pre.shape[0] != rows or pre.shape[1] < (heads + kv_heads) * head_dim or pre.stride(1) != 1:
+            raise RuntimeError("qk_norm_rope_bwd: pre must be (rows, >= (heads + kv_heads) head_dim)")
+        dwq = torch.empty(head_dim, dtype=torch.float32, device=d_qkv.device)
+        dwk = torch.empty(head_dim, dtype=torch.float32, device=d_qkv.device)
+        nbytes = h.u2tok_qk_norm_rope_bwd_workspace_bytes(rows, head_dim)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=d_qkv.device)
+    _lib.check(h.u2tok_qk_norm_rope_bwd(_ptr(d_qkv), _ptr(pre) if norm else None, _ptr(q_norm_w), _ptr(k_norm_w), _ptr(cos),
+                                        _ptr(sin), int(cos.dtype == torch.float32), rows, heads, kv_heads, head_dim,
+                                        d_qkv.stride(0), pre.stride(0) if norm else 0, cos.stride(0), float(eps), _ptr(dwq),
+                                        _ptr(dwk), _ptr(ws), nbytes, 0, _stream()), "u2tok_qk_norm_rope_bwd")
+    return d_qkv, dwq, dwk
+
+
+@_guarded
+def swiglu_bwd(gate_up: torch.Tensor, d_act: torch.Tensor) -> torch.Tensor:
+    """Backward of swiglu (u2tok_swiglu_bwd): gate_up (rows, 2 I) pre-activations, d_act (rows, I) -> packed (rows, 2 I)
+    [d_gate | d_up]."""
+    h = _lib.load_library()
+    _need(gate_up, ELEM, "gate_up")
+    d_act = _need(d_act, ELEM, "d_act").contiguous()
+    rows, two_i = gate_up.shape
+    if gate_up.stride(1) != 1 or d_act.shape != (rows, two_i // 2):
+        raise RuntimeError("swiglu_bwd: gate_up (rows, 2 I) with a contiguous last dim and d_act (rows, I)")
+    dgu = torch.empty((rows, two_i), dtype=elem_dtype(), device=gate_up.device)
+    _lib.check(h.u2tok_swiglu_bwd(_ptr(gate_up), _ptr(d_act), _ptr(dgu), rows, two_i // 2, gate_up.stride(0), two_i // 2, two_i,
+                                  _stream()), "u2tok_swiglu_bwd")
+    return dgu

@@ -189,9 +189,15 @@ def _layer_forward(self, hidden_states, *args, **kwargs):
     cache = kwargs.get("past_key_values")
     att = self.self_attn
     pr = lo.projections(self)
+    if torch.is_grad_enabled() and getattr(st["owner"], "_u2_train", False):
+        # the opt-in training route (decoder_train.py): forward + backward on the library's kernels, or None -> stock below
+        from .decoder_train import try_train_forward
+        out = try_train_forward(self, hidden_states, args, kwargs)
+        if out is not None:
+            return out
     # `past_key_value` (singular) is the layer protocol of transformers 4.46 .. 4.5x, whose layers also return tuples: never
     # patched (enable_fused_prefill checks the signature), and a caller that passes it anyway gets the stock layer
-    common = (not args and "past_key_value" not in kwargs and not kwargs.get("output_attentions")
+    common = (st["owner"].__dict__.get("_u2_prefill_on", True) and not args and "past_key_value" not in kwargs and not kwargs.get("output_attentions")
               and not torch.is_grad_enabled() and x.is_cuda and x.dtype in ops.ELEM_OF and x.dim() == 3
               and pr[0].weight.dtype == x.dtype      # (bf16 weights under an fp16 autocast hand fp16 activations on: stock layers)
               and pe is not None and pe[0].shape[-1] == att.head_dim and st["owner"]._u2_prefill_mask_ok and _is_stock(self, pr)
@@ -505,11 +511,14 @@ def _layer_protocol_ok(layer, base=None) -> bool:
     return ok
 
 
-def enable_fused_prefill(model, decode: bool = True, strict: bool = True) -> int:
+def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
     activation, partial rotary, a head dim outside 64 / 96 / 128) -- is skipped instead of refused.
+    train=True (opt-in): a patched Llama / Qwen3 layer called with grad enabled takes the training route of decoder_train.py
+    (forward and backward on the library's kernels) when its conditions hold.  prefill=False: no fused prefill / decode (the
+    layers are patched for the training route only).  Both flags are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = model.get_model() if hasattr(model, "get_model") else getattr(model, "model", model)
     layers = getattr(base, "layers", None)
@@ -530,6 +539,8 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True) -> int
         layer.forward = types.MethodType(_layer_forward, layer)
         n += 1
     base._u2_fused_decode = bool(decode)
+    base._u2_train = bool(train)
+    base._u2_prefill_on = bool(prefill)
     if not hasattr(base, "_u2_prefill_hook"):
         base._u2_prefill_mask_ok = True
         base._u2_prefill_hook = base.register_forward_pre_hook(_mask_hook, with_kwargs=True)
@@ -546,3 +557,5 @@ def disable_fused_prefill(model) -> None:
     if hook is not None:
         hook.remove()
     base.__dict__.pop("_u2_decode_scratch", None)
+    base.__dict__.pop("_u2_train", None)
+    base.__dict__.pop("_u2_prefill_on", None)
