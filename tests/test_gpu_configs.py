@@ -256,6 +256,7 @@ def test_config3_end_to_end_first_step_logits_and_greedy_ids():
     ids are compared for TWO volumes -- the benchmark's noise volume and a smooth one whose tokens differ by ~80 % -- whose
     reference ids must differ: a path that ignored the image could not pass."""
     import e2e_config3 as R
+    from u2tokenizer_amd.prefill import is_patched
     # The HOST reference is four full-size oracle passes + four decoder runs on the CPU (fp32 and bf16, both volumes).  Its fp32
     # side and the two flip thresholds depend on seeds only: tests/golden/config3_e2e_ref.npz holds them (made by
     # tests/golden/make_config3_e2e.py from R.reference_live -- the definition used here when the fixture is absent or
@@ -274,7 +275,7 @@ def test_config3_end_to_end_first_step_logits_and_greedy_ids():
     mg = m16.to(D)
     vol = vols["noise"]
     out = mg(images=vol.to(D), input_ids=ids.to(D), question_ids=qids.to(D))
-    assert hasattr(mg.model.layers[0], "_u2_prefill")                      # the decoder ran through the fused HIP layers
+    assert is_patched(mg.model.layers[0])                      # the decoder ran through the fused HIP layers
     emb = mg.prepare_inputs_for_multimodal(ids.to(D), None, None, None, None, vol.to(D), qids.to(D))[4]
     gen = {v: mg.generate(x.to(D), ids.to(D), question_ids=qids.to(D), max_new_tokens=new, do_sample=False).cpu()[0].tolist()
            for v, x in vols.items()}

@@ -260,13 +260,14 @@ def test_generate_through_u2phi3(ops, dt):
     """u2Phi3ForCausalLM.generate: the layers are patched on the first no-grad forward (config.u2_fused_prefill), the prefill
     and every decode step go through the HIP layers; greedy ids equal the fp32 model's up to the first step whose fp32 top-2
     margin is below 0.05."""
+    from u2tokenizer_amd.prefill import is_patched
     m32 = _phi3(layers=2, u2=True)
     ids = torch.randint(3, 1024, (1, 48), generator=torch.Generator().manual_seed(5))
     new = 6
     g32 = m32.generate(inputs=ids, max_new_tokens=new, do_sample=False, output_scores=True, return_dict_in_generate=True)
     mg = _phi3(layers=2, u2=True).to(dt).to(D)
     g = mg.generate(inputs=ids.to(D), max_new_tokens=new, do_sample=False).cpu()
-    assert all(hasattr(lay, "_u2_prefill") for lay in mg.model.layers)
+    assert all(is_patched(lay) for lay in mg.model.layers)
     assert g.shape == g32.sequences.shape
     for t in range(new):
         top2 = g32.scores[t][0].topk(2).values

@@ -275,7 +275,7 @@ def test_fused_prefill_patch_is_inert_off_the_gpu_and_packs_losslessly():
             assert torch.equal(v, sd[k]), k
         assert torch.equal(m(inputs_embeds=x).logits, ref)
         P.disable_fused_prefill(m)
-        assert not hasattr(m.model.layers[0], "_u2_prefill") and torch.equal(m(inputs_embeds=x).logits, ref)
+        assert not P.is_patched(m.model.layers[0]) and torch.equal(m(inputs_embeds=x).logits, ref)
 
 
 def test_frozen_tower_feature_sharing_logic():

@@ -152,10 +152,10 @@ def test_enable_fused_prefill_patches_every_phi3_layer():
 @pytest.mark.parametrize("kw", [dict(partial_rotary_factor=0.5), dict(hidden_act="gelu_new"),
                                 dict(hidden_size=192, num_attention_heads=4, num_key_value_heads=4)])
 def test_phi3_layers_the_kernels_do_not_compute_stay_stock(kw):
-    from u2tokenizer_amd.prefill import enable_fused_prefill
+    from u2tokenizer_amd.prefill import enable_fused_prefill, is_patched
     m = _phi3(**kw)
     assert enable_fused_prefill(m, strict=False) == 0
-    assert not any(hasattr(lay, "_u2_prefill") for lay in m.model.layers)
+    assert not any(is_patched(lay) for lay in m.model.layers)
     with pytest.raises(RuntimeError, match="unsupported decoder layer"):
         enable_fused_prefill(m)
 

@@ -15,6 +15,7 @@ from helpers import err_stats  # noqa: E402
 from oracle import u2_oracle as O  # noqa: E402
 from u2tokenizer_amd import ops, synth  # noqa: E402
 from u2tokenizer_amd.language_model import u2Qwen3Config, u2Qwen3ForCausalLM  # noqa: E402
+from u2tokenizer_amd.prefill import is_patched  # noqa: E402
 from test_gpu_configs import mm_config, oracle_cfg  # noqa: E402
 
 bf, D = torch.bfloat16, "cuda"
@@ -81,7 +82,7 @@ show("ambient split-K scratch", prep())
 ops.set_gemm_scratch(None)
 out = mg(images=volD, input_ids=idsD, question_ids=qD)
 torch.cuda.synchronize()
-print("fused prefill on:", hasattr(mg.model.layers[0], "_u2_prefill"), flush=True)
+print("fused prefill on:", is_patched(mg.model.layers[0]), flush=True)
 show("after a full forward (prefill registered)", prep())
 tower.invalidate_feature_cache()
 show("  + cache invalidated", prep())

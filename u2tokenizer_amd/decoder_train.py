@@ -16,12 +16,12 @@ torch.autograd.Functions over the C-ABI blocks, each saving what its backward ne
   * RMSNorm, head norm + rotary and SwiGLU have their backward kernels in csrc/backward.hip (fixed-order fp32 weight gradients);
   * torch moves data and adds the residual stream's two gradient contributions.
 
-When a layer takes the route (route_conditions below, checked on every call; everything else keeps the stock forward):
-bf16 on the GPU, every projection exactly nn.Linear with no hooks, no active attention dropout, head dim 64 or 128, no KV
-cache, no sliding window, and an attention mask that is causal with at most right padding.  The mask is read from the
-LAYER's own `attention_mask` argument (the 4-D mask HF builds, or None) and the verdict is stored on that tensor: the
-recompute of non-reentrant gradient checkpointing calls the layer with the same argument objects, so it sees the key
-lengths of ITS forward, not those of whatever forward of the model ran last.
+When a layer takes the route (prefill.route, decided on every call; everything else keeps the stock forward): bf16 on the
+GPU, every projection exactly nn.Linear with no hooks, no active attention dropout, head dim 64 or 128, no KV cache, no
+sliding window, and an attention mask that is causal with at most right padding.  The mask is read from the LAYER's own
+`attention_mask` argument (the 4-D mask HF builds, or None; layer_mask_kv_len below) and the verdict is stored on that
+tensor: the recompute of non-reentrant gradient checkpointing calls the layer with the same argument objects, so it sees the
+key lengths of ITS forward, not those of whatever forward of the model ran last.
 """
 from __future__ import annotations
 
@@ -32,8 +32,6 @@ from torch.autograd import Function
 
 from . import ops
 from .autograd import _bind_context
-
-BF = torch.bfloat16
 
 # layers whose forward took the training route (tests read it: a route that silently fell back to the stock layers would
 # otherwise pass every gradient check)
@@ -224,78 +222,26 @@ class SwiGLUFn(Function):
 
 
 # ------------------------------------------------------------------------------------------------ the layer
-def route_conditions(layer, x, kwargs, projections) -> bool:
-    """Everything but the mask: bf16 activations and weights on the GPU, stock projections without hooks, no active dropout,
-    head dim 64 / 128, no KV cache, no sliding window, widths the row kernels take."""
-    from .prefill import _SplitLayout, _is_stock
-    st = layer._u2_prefill
-    att = layer.self_attn
-    pe = kwargs.get("position_embeddings")
-    if st["layout"] is not _SplitLayout or not x.is_cuda or x.dtype != BF or x.dim() != 3 or x.shape[1] < 1:
-        return False
-    if projections[0].weight.dtype != BF or kwargs.get("past_key_values") is not None or kwargs.get("output_attentions"):
-        return False
-    if "past_key_value" in kwargs or pe is None or pe[0].shape[-1] != att.head_dim or att.head_dim not in (64, 128):
-        return False
-    if att.training and float(getattr(att, "attention_dropout", 0.0) or 0.0) > 0:
-        return False
-    if not _SplitLayout.ready(layer, att) or not _is_stock(layer, projections):
-        return False
-    E = x.shape[-1]
-    inter = layer.mlp.gate_proj.weight.shape[0]
-    return E % 8 == 0 and E <= 4096 and inter % 8 == 0 and layer.input_layernorm.weight.dtype == BF
-
-
-def layer_forward_train(layer, x, kwargs, kv_len):
-    """The layer's forward through the Functions above; x (B, S, E) -> (B, S, E)."""
-    from .prefill import _ensure_gemm_scratch
-    st = layer._u2_prefill
-    lo = st["layout"]
+def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
+    """The layer's forward through the Functions above on its rows x2 (B S, E) -> (B, S, E); `lo` is the layer's layout
+    (prefill.py: its packed q|k|v and gate|up), cos / sin the rotary rows (B S, d), kv_len the key lengths or None."""
     att, mlp = layer.self_attn, layer.mlp
     cfg = att.config
-    B, S, E = x.shape
-    rows = B * S
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     stats["layers"] += 1   # (counted on entry: a checkpoint recompute stops early, once the tensors it needs are back)
-    _ensure_gemm_scratch(x.device)
-    with ops.on_device(x):
-        Wqkv, bqkv = lo.qkv(layer)
-        Wgu, bgu = lo.gate_up(layer)
-        x2 = x.reshape(rows, E)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        cos, sin = kwargs["position_embeddings"]
-        cos = cos.expand(B, S, d).reshape(rows, d)
-        sin = sin.expand(B, S, d).reshape(rows, d)
-        if cos.dtype != sin.dtype or cos.dtype not in (torch.float32, BF) or cos.stride(1) != 1 or sin.stride(1) != 1 \
-                or cos.stride(0) != sin.stride(0):
-            cos, sin = cos.float().contiguous(), sin.float().contiguous()
-        cos, sin = cos.detach(), sin.detach()
-        xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
-        qkv = packed_linear(xn, (att.q_proj, att.k_proj, att.v_proj), Wqkv, bqkv)
-        qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
-        qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq,
-                                   Hkv, d, float(qn.variance_epsilon) if qn is not None else 1e-6)
-        ctx = GqaAttentionFn.apply(qkv, kv_len, B, S, Hq, Hkv, d, float(att.scaling))
-        h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
-                          att.o_proj.bias.detach(), res=x2)
-        hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
-        gu = packed_linear(hn, (mlp.gate_proj, mlp.up_proj), Wgu, bgu)
-        act = SwiGLUFn.apply(gu)
-        out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
-                            None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)
-    return out.view(B, S, E)
-
-
-def try_train_forward(layer, hidden_states, args, kwargs):
-    """The layer's output through the training route, or None (the caller runs the stock forward)."""
-    if args:
-        return None
-    pr = layer._u2_prefill["layout"].projections(layer)
-    if not route_conditions(layer, hidden_states, kwargs, pr):
-        return None
-    B, S, _ = hidden_states.shape
-    ok, kv_len = layer_mask_kv_len(kwargs.get("attention_mask"), B, S)
-    if not ok:
-        return None
-    return layer_forward_train(layer, hidden_states, kwargs, kv_len)
+    Wqkv, bqkv = lo.qkv(layer)
+    Wgu, bgu = lo.gate_up(layer)
+    xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
+    qkv = packed_linear(xn, (att.q_proj, att.k_proj, att.v_proj), Wqkv, bqkv)
+    qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
+    qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv,
+                               d, float(qn.variance_epsilon) if qn is not None else 1e-6)
+    ctx = GqaAttentionFn.apply(qkv, kv_len, B, S, Hq, Hkv, d, float(att.scaling))
+    h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
+                      att.o_proj.bias.detach(), res=x2)
+    hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
+    gu = packed_linear(hn, (mlp.gate_proj, mlp.up_proj), Wgu, bgu)
+    act = SwiGLUFn.apply(gu)
+    out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
+                        None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)
+    return out.view(B, S, -1)

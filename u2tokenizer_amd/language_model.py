@@ -57,31 +57,24 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
     def get_model(self):
         return self.model
 
-    def _maybe_fuse_prefill(self) -> None:
-        """The prefill of the spliced embeddings through the HIP decoder layers (u2tokenizer_amd/prefill.py)
-        unless `config.u2_fused_prefill` is False: patched once, when the decoder sits on the GPU in bf16 (or fp16: the f16 build).  Training,
-        decode steps, padded batches and CPU runs keep the stock HuggingFace layers."""
-        if getattr(self, "_u2_prefill_checked", False) or not getattr(self.config, "u2_fused_prefill", True):
+    def _maybe_fuse(self) -> None:
+        """Patch the decoder layers for the HIP routes of prefill.py, once per grad mode, when the decoder sits on the GPU in a
+        type that mode's route computes: without grad `config.u2_fused_prefill` (default True) asks for the prefill and decode
+        steps (bf16, or fp16 on the f16 build), with grad `config.u2_fused_decoder_training` (default False)
+        for the training route of decoder_train.py (bf16).  Both switches are passed on as the config has them."""
+        grad = torch.is_grad_enabled()
+        train = bool(getattr(self.config, "u2_fused_decoder_training", False))
+        prefill = bool(getattr(self.config, "u2_fused_prefill", True))
+        checked = self.__dict__.setdefault("_u2_fuse_checked", set())
+        if grad in checked or not (train if grad else prefill):
             return
         p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
-        if p is not None and p.is_cuda and p.dtype in (torch.bfloat16, torch.float16):   # (either build of the library)
-            from .prefill import enable_fused_prefill
-            # (layers the kernels do not compute stay stock; the training switch is kept as the config has it)
-            enable_fused_prefill(self, strict=False, train=bool(getattr(self.config, "u2_fused_decoder_training", False)))
-            self._u2_prefill_checked = True
-
-    def _maybe_fuse_training(self) -> None:
-        """`config.u2_fused_decoder_training = True` (default False): a forward with grad enabled runs the decoder layers on the
-        training route of decoder_train.py (forward and backward on the HIP kernels) where its conditions hold -- bf16 on the
-        GPU, stock projections without hooks, no dropout, head dim 64 / 128, no KV cache, no padding or right padding only.
-        Patched once, when the decoder sits on the GPU in bf16; `config.u2_fused_prefill` still decides the inference route."""
-        if getattr(self, "_u2_train_checked", False):
+        if p is None or not p.is_cuda:
             return
-        p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
-        if p is not None and p.is_cuda and p.dtype == torch.bfloat16:
-            from .prefill import enable_fused_prefill
-            enable_fused_prefill(self, strict=False, train=True, prefill=bool(getattr(self.config, "u2_fused_prefill", True)))
-            self._u2_train_checked = True
+        from .prefill import INFER_DTYPES, TRAIN_DTYPES, enable_fused_prefill
+        if p.dtype in (TRAIN_DTYPES if grad else INFER_DTYPES):
+            enable_fused_prefill(self, strict=False, train=train, prefill=prefill)
+            checked.add(grad)
 
     def forward(self, images: Optional[torch.FloatTensor] = None, input_ids: torch.LongTensor = None,
                 labels: Optional[torch.LongTensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -93,10 +86,7 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         # aliases used by the in-tree Qwen3 variant (u2qwen3.py:42-47)
         images = kwargs.pop("vision_input", images)
         question_ids = kwargs.pop("raw_question_ids", question_ids)
-        if not torch.is_grad_enabled():
-            self._maybe_fuse_prefill()
-        elif getattr(self.config, "u2_fused_decoder_training", False):
-            self._maybe_fuse_training()
+        self._maybe_fuse()
         if inputs_embeds is None:
             (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds, labels) = \
                 self.prepare_inputs_for_multimodal(input_ids, position_ids, attention_mask, past_key_values, labels,

@@ -24,14 +24,28 @@ are used as they are (`_PackedLayout`).  Their configs carry `sliding_window` = 
 keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a longer prefill takes the stock layers, and a
 decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
 DynamicSlidingWindowLayer that `generate` builds for such a config.
+
+`route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
+step, the prefill or the stock forward.  The patch state is one `_LayerState` per layer and one `_StackState` per decoder stack.
 """
 from __future__ import annotations
 
 import types
+from dataclasses import dataclass, field
 
 import torch
+from transformers import cache_utils
 
-from . import ops
+from . import decoder_train, ops
+
+# the HF cache classes the fused steps work with (None where this transformers lacks one: before 4.56 no per-layer caches)
+_DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
+                                          ("DynamicCache", "DynamicLayer", "DynamicSlidingWindowLayer"))
+
+# What the kernels compute, per route: element types and head dims of the prefill / decode kernels, and of the backward
+# kernels the training route needs (bf16 only, no head dim 96)
+INFER_DTYPES, INFER_HEAD_DIMS = (torch.bfloat16, torch.float16), (64, 96, 128)
+TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
 
 
 def _pack(linears):
@@ -78,6 +92,7 @@ _HOOK_TABLES = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_bac
 class _SplitLayout:
     """Llama / Qwen3: separate q / k / v and gate / up projections, packed into one buffer each on first use."""
     KEY = (0, 3, 4, 6)   # projections whose weights locate the packed buffers: q (q|k|v), o, gate (gate|up), down
+    TRAINS = True        # the training route computes this layout
 
     @staticmethod
     def projections(layer):
@@ -105,6 +120,7 @@ class _SplitLayout:
 class _PackedLayout:
     """Phi-3: one qkv_proj (q, k, v rows) and one gate_up_proj (gate rows, then up rows) -- the packed layout itself."""
     KEY = (0, 1, 2, 3)
+    TRAINS = False
 
     @staticmethod
     def projections(layer):
@@ -144,7 +160,7 @@ class _PackedLayout:
         rp = getattr(cfg, "rope_parameters", None) or {}
         prf = rp.get("partial_rotary_factor", getattr(cfg, "partial_rotary_factor", 1.0))
         return (getattr(cfg, "hidden_act", None) == "silu" and float(prf if prf is not None else 1.0) == 1.0
-                and att.head_dim in (64, 96, 128))
+                and att.head_dim in INFER_HEAD_DIMS)
 
 
 def _layout_of(layer):
@@ -162,15 +178,13 @@ def _layout_of(layer):
     return None
 
 
-def _is_stock(layer, projections=None) -> bool:
+def _is_stock(layer, projections) -> bool:
     """The fused forwards read the projections' `.weight` / `.bias` and never CALL the submodules.  That is only the same
     computation while every projection is exactly torch.nn.Linear and nothing hangs on the modules that are skipped: a
     peft lora.Linear exposes `.weight` as its BASE weight (the reference trains the decoder with LoRA, train_stage1.py:342-353:
     an unmerged adapter would be silently ignored), forward hooks (output_attentions recorders, activation probes) would not
     fire.  Checked on every call: adapters and hooks come and go after enable_fused_prefill.  (`projections`: the layout's
-    projection modules when the caller has them already -- module attribute reads are what this costs per layer and step.)"""
-    if projections is None:
-        projections = layer._u2_prefill["layout"].projections(layer)
+    projection modules, read once per call -- module attribute reads are what this costs per layer and step.)"""
     for m in projections:
         if type(m) is not torch.nn.Linear:
             return False
@@ -181,52 +195,126 @@ def _is_stock(layer, projections=None) -> bool:
     return True
 
 
+@dataclass(slots=True, eq=False)
+class _StackState:
+    """enable_fused_prefill's state on a decoder stack: the route switches, the pre-hook's verdict on the call's 2-D mask,
+    the hook, and the decode steps' scratch ((B, device, stream) -> buffers)."""
+    hook: object
+    decode: bool = True
+    train: bool = False
+    prefill: bool = True
+    mask_ok: bool = True
+    scratch: dict = field(default_factory=dict)
+
+
+@dataclass(slots=True, eq=False)
+class _LayerState:
+    """A patched layer: its original forward, its stack's state, its layout, the decode step's cached constants."""
+    orig: object
+    stack: _StackState
+    layout: type
+    dec: dict = None
+
+    def __getitem__(self, key):   # (read as a mapping too -- layer._u2_prefill["layout"] -- as when this state was a dict)
+        return getattr(self, key)
+
+
+def is_patched(layer) -> bool:
+    """True while enable_fused_prefill's forward is installed on `layer`."""
+    return "_u2_prefill" in layer.__dict__
+
+
+def _rows(x):
+    return x.reshape(-1, x.shape[-1]).contiguous()   # (B, S, E) -> dense (B S, E) rows (no copy when they are already)
+
+
+def _rotary_rows(pe, B: int, S: int, d: int, elem=None):
+    """`position_embeddings` as (B S, d) rows of cos and sin.  With `elem` (decode, training): tables the kernels do not read as
+    they are (two types, neither fp32 nor `elem`, rows not unit stride or not of one stride) become fp32 copies."""
+    cos, sin = pe
+    cos, sin = cos.expand(B, S, d).reshape(B * S, d), sin.expand(B, S, d).reshape(B * S, d)
+    if elem is not None and (cos.dtype != sin.dtype or cos.dtype not in (torch.float32, elem) or cos.stride(1) != 1
+                             or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0)):
+        cos, sin = cos.float().contiguous(), sin.float().contiguous()
+    return cos, sin
+
+
+def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
+    """The forward a call of the patched `layer` takes, from the input's shape, dtype and device flag (no tensor needed):
+    ("train", kv_len) or stock with grad enabled, else ("decode", W), ("prefill", W) or stock; W = the attention window or
+    None.  Masks: decode and prefill read the stack pre-hook's verdict on the call's 2-D mask, the training route the layer's
+    own 4-D mask (layer_mask_kv_len: cached on the tensor, so a checkpoint recompute sees its own forward's).  `pr`: the
+    layout's projections (read once per call)."""
+    st = layer._u2_prefill
+    stack, lo, att = st.stack, st.layout, layer.self_attn
+    if not (stack.train if grad else stack.prefill):
+        return "stock", None
+    pe = kwargs.get("position_embeddings")
+    # every route: no `past_key_value` (singular: the 4.46 .. 4.5x protocol, never patched), a (B, S >= 1, E) GPU input in the
+    # weights' type (bf16 weights under an fp16 autocast hand fp16 activations on), stock projections without hooks
+    if args or "past_key_value" in kwargs or kwargs.get("output_attentions") or not is_cuda or len(shape) != 3 \
+            or shape[1] < 1 or pr[0].weight.dtype != dtype or pe is None or pe[0].shape[-1] != att.head_dim \
+            or not _is_stock(layer, pr) or not lo.ready(layer, att):
+        return "stock", None
+    if grad:
+        # no KV cache, no active attention dropout, widths the row kernels take, a mask the attention computes
+        if not lo.TRAINS or dtype not in TRAIN_DTYPES or att.head_dim not in TRAIN_HEAD_DIMS or kwargs.get("past_key_values") \
+                is not None or (att.training and float(getattr(att, "attention_dropout", 0.0) or 0.0) > 0) \
+                or shape[2] % 8 or shape[2] > 4096 or layer.mlp.gate_proj.weight.shape[0] % 8 \
+                or layer.input_layernorm.weight.dtype not in TRAIN_DTYPES:
+            return "stock", None
+        ok, kv_len = decoder_train.layer_mask_kv_len(kwargs.get("attention_mask"), shape[0], shape[1])
+        return ("train", kv_len) if ok else ("stock", None)
+    if dtype not in INFER_DTYPES or att.head_dim not in INFER_HEAD_DIMS or not stack.mask_ok:
+        return "stock", None
+    W = lo.window(layer)
+    cache = kwargs.get("past_key_values")
+    if shape[1] == 1:   # one new position per sequence, batch <= 16, against a plain DynamicCache
+        ok = shape[0] <= 16 and stack.decode and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
+        return ("decode", W) if ok else ("stock", None)
+    # an empty cache; a prefill longer than the window would need the band inside the attention kernel: stock layers
+    if (W is None or shape[1] <= W) and (cache is None or cache.get_seq_length(att.layer_idx) == 0):
+        return "prefill", W
+    return "stock", None
+
+
 def _layer_forward(self, hidden_states, *args, **kwargs):
     st = self._u2_prefill
-    lo = st["layout"]
     x = hidden_states
-    pe = kwargs.get("position_embeddings")
-    cache = kwargs.get("past_key_values")
-    att = self.self_attn
-    pr = lo.projections(self)
-    if torch.is_grad_enabled() and getattr(st["owner"], "_u2_train", False):
-        # the opt-in training route (decoder_train.py): forward + backward on the library's kernels, or None -> stock below
-        from .decoder_train import try_train_forward
-        out = try_train_forward(self, hidden_states, args, kwargs)
+    pr = st.layout.projections(self)
+    how, arg = route(self, x.shape, x.dtype, x.is_cuda, args, kwargs, torch.is_grad_enabled(), pr)
+    if how == "decode":
+        out = _decode_step(self, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, pr)
         if out is not None:
             return out
-    # `past_key_value` (singular) is the layer protocol of transformers 4.46 .. 4.5x, whose layers also return tuples: never
-    # patched (enable_fused_prefill checks the signature), and a caller that passes it anyway gets the stock layer
-    common = (st["owner"].__dict__.get("_u2_prefill_on", True) and not args and "past_key_value" not in kwargs and not kwargs.get("output_attentions")
-              and not torch.is_grad_enabled() and x.is_cuda and x.dtype in ops.ELEM_OF and x.dim() == 3
-              and pr[0].weight.dtype == x.dtype      # (bf16 weights under an fp16 autocast hand fp16 activations on: stock layers)
-              and pe is not None and pe[0].shape[-1] == att.head_dim and st["owner"]._u2_prefill_mask_ok and _is_stock(self, pr)
-              and lo.ready(self, att) and att.head_dim in (64, 96, 128))
-    W = lo.window(self) if common else None
-    if common and x.shape[1] == 1 and x.shape[0] <= 16 and st["owner"]._u2_fused_decode \
-            and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None:
-        out = _decode_step(self, x, pe, cache, W, pr)
-        if out is not None:
-            return out
-    # (a prefill longer than the window would need the band inside the attention kernel: stock layers)
-    fused = common and x.shape[1] > 1 and (W is None or x.shape[1] <= W) \
-        and (cache is None or cache.get_seq_length(att.layer_idx) == 0)
-    if not fused:
-        return st["orig"](hidden_states, *args, **kwargs)
+    elif how == "prefill":
+        return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"))
+    elif how == "train":
+        return _train_step(self, st.layout, x, kwargs["position_embeddings"], arg)
+    return st.orig(hidden_states, *args, **kwargs)
+
+
+def _train_step(layer, lo, x, pe, kv_len):
+    """The training route (decoder_train.layer_forward_train) on the layer's rows and rotary tables."""
+    B, S, _ = x.shape
+    _ensure_gemm_scratch(x.device)
+    with ops.on_device(x):
+        cos, sin = _rotary_rows(pe, B, S, layer.self_attn.head_dim, x.dtype)
+        return decoder_train.layer_forward_train(layer, lo, _rows(x), cos.detach(), sin.detach(), B, S, kv_len)
+
+
+def _prefill_step(self, lo, x, pe, cache):
     B, S, E = x.shape
     rows = B * S
+    att = self.self_attn
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     _ensure_gemm_scratch(x.device)
     with ops.on_device(x):
         Wqkv, bqkv = lo.qkv(self)
         Wgu, bgu = lo.gate_up(self)
-        x2 = x.reshape(rows, E)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        cos, sin = pe
-        cos = cos.expand(B, S, d).reshape(rows, d)
-        sin = sin.expand(B, S, d).reshape(rows, d)
+        x2 = _rows(x)
+        cos, sin = _rotary_rows(pe, B, S, d)
         xn = ops.rmsnorm(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
         qkv = ops.gemm(xn, Wqkv, bias=bqkv)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
@@ -264,9 +352,7 @@ def _append_layer_class():
     DynamicLayer's: those reassign `.keys` / `.values`, after which the next update re-homes them."""
     global _APPEND_LAYER
     if _APPEND_LAYER is None:
-        from transformers.cache_utils import DynamicLayer
-
-        class AppendLayer(DynamicLayer):
+        class AppendLayer(_DYN_LAYER):
             _kb = _vb = None
 
             def _room(self, n: int, like: torch.Tensor) -> int:
@@ -304,26 +390,23 @@ def _append_layer_class():
     return _APPEND_LAYER
 
 
+def _plain_layers(cache):
+    """The `layers` list of `cache` if it is a plain HF DynamicCache (no offloading), else None."""
+    layers = getattr(cache, "layers", None)
+    if type(cache) is not _DYN_CACHE or not isinstance(layers, list) or getattr(cache, "offloading", False):
+        return None
+    return layers
+
+
 def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False):
     """The cache layer if `cache` is a plain HF DynamicCache (no offloading) whose layer `layer_idx` is a non-empty DynamicLayer
     -- the case the fused decode step handles (its `update` is a torch.cat: dense (B, H_kv, T, d) tensors come back).
     sliding=True (a layer with an attention window): a DynamicSlidingWindowLayer is taken as well."""
-    try:
-        from transformers.cache_utils import DynamicCache, DynamicLayer
-    except ImportError:
-        return None
-    kinds = (DynamicLayer, _APPEND_LAYER)
-    if sliding:
-        try:
-            from transformers.cache_utils import DynamicSlidingWindowLayer
-            kinds = kinds + (DynamicSlidingWindowLayer,)
-        except ImportError:
-            pass
-    layers = getattr(cache, "layers", None)
-    if type(cache) is not DynamicCache or not isinstance(layers, list) or getattr(cache, "offloading", False) \
-            or layer_idx >= len(layers):
+    layers = _plain_layers(cache)
+    if layers is None or layer_idx >= len(layers):
         return None
     lay = layers[layer_idx]
+    kinds = (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
     return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
 
 
@@ -333,10 +416,10 @@ def _decode_state(self, B: int, device, pr):
     import ctypes as C
     from . import _lib
     st = self._u2_prefill
-    lo = st["layout"]
+    lo = st.layout
     att, mlp = self.self_attn, self.mlp
     key = tuple(pr[i].weight.data_ptr() for i in lo.KEY) + (B,)
-    d = st.get("dec")
+    d = st.dec
     if d is None or d["key"] != key:
         cfg = att.config
         Hq, Hkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
@@ -355,11 +438,10 @@ def _decode_state(self, B: int, device, pr):
                      p(None if kn is None else kn.weight)),
              "post": (p(att.o_proj.weight), p(att.o_proj.bias), p(self.post_attention_layernorm.weight), p(Wgu), p(bgu),
                       p(mlp.down_proj.weight), p(mlp.down_proj.bias))}
-        st["dec"] = d
-    owner = st["owner"]
+        st.dec = d
     # (per model, batch size AND stream: two generate() calls in flight on different streams must not share the step's scratch)
     stream = torch.cuda.current_stream(device).cuda_stream
-    pool = owner.__dict__.setdefault("_u2_decode_scratch", {})
+    pool = st.stack.scratch
     edt = self.input_layernorm.weight.dtype      # bf16, or fp16 for a decoder loaded in float16 (the f16 build of the library)
     sc = pool.get((B, device, stream))
     if sc is not None and sc["qkv"].dtype != edt:
@@ -375,7 +457,7 @@ def _decode_state(self, B: int, device, pr):
     return d, sc
 
 
-def _decode_step(self, x, pe, cache, window=None, pr=None):
+def _decode_step(self, x, pe, cache, window, pr):
     """One decode step of a layer (B <= 16 new tokens, one each, against the KV cache): the step `generate` repeats up to 768
     times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
     few-rows GEMM (gemm.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
@@ -387,20 +469,13 @@ def _decode_step(self, x, pe, cache, window=None, pr=None):
     from . import _lib
     att = self.self_attn
     B, _, E = x.shape
-    d, sc = _decode_state(self, B, x.device, self._u2_prefill["layout"].projections(self) if pr is None else pr)
+    d, sc = _decode_state(self, B, x.device, pr)
     if not d["ok"]:
         return None                                   # (the caller takes the stock layer)
     hd = d["hd"]
     with ops.on_device(x) as (h, stream):
-        x2 = x.reshape(B, E)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        cos, sin = pe
-        cos = cos.expand(B, 1, hd).reshape(B, hd)
-        sin = sin.expand(B, 1, hd).reshape(B, hd)
-        if cos.dtype != sin.dtype or cos.dtype not in (torch.float32, x.dtype) or cos.stride(1) != 1 or sin.stride(1) != 1 \
-                or cos.stride(0) != sin.stride(0):
-            cos, sin = cos.float().contiguous(), sin.float().contiguous()
+        x2 = _rows(x)
+        cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
         T1 = cache.get_seq_length(att.layer_idx) + 1
         if sc["ws"] is None or sc["T"] < T1:
             Tcap = max(2048, 2 * T1)                      # (grows geometrically: the workspace depends on T through the key splits)
@@ -410,34 +485,26 @@ def _decode_step(self, x, pe, cache, window=None, pr=None):
         ws, nws = sc["ws"].data_ptr(), sc["ws"].numel()
         lay = cache.layers[att.layer_idx]
         out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
-        if type(lay) is _APPEND_LAYER and lay._kb is not None and lay._kb.shape[0] == B:
-            # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers
+        inplace = type(lay) is _APPEND_LAYER and lay._kb is not None and lay._kb.shape[0] == B
+        if inplace:   # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers
             T0 = lay._room(1, sc["kc"])
-            kb, vb = lay._kb, lay._vb
-            _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], x2.data_ptr(), *d["pre"], cos.data_ptr(), sin.data_ptr(),
-                                                  int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(),
-                                                  kb.data_ptr(), vb.data_ptr(), kb.stride(1), T0, ws, nws, stream),
-                       "u2tok_decoder_decode_pre")
-            lay._commit(T0 + 1)
-            Kw, Vw = kb[:, :, :T0 + 1], vb[:, :, :T0 + 1]
-            if window is not None:
-                Kw, Vw = Kw[:, :, -window:], Vw[:, :, -window:]
-            _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), Kw.data_ptr(), Vw.data_ptr(),
-                                                   Kw.shape[2], kb.stride(1), *d["post"], out.data_ptr(), ws, nws, stream),
-                       "u2tok_decoder_decode_post")
-            return out
+            kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
+        else:         # into the step's scratch rows, for the cache's own `update`
+            T0, kd, vd, kvs = 0, sc["kc"], sc["vc"], 0
         _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], x2.data_ptr(), *d["pre"], cos.data_ptr(), sin.data_ptr(),
                                               int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(),
-                                              sc["kc"].data_ptr(), sc["vc"].data_ptr(), 0, 0, ws, nws, stream),
+                                              kd.data_ptr(), vd.data_ptr(), kvs, T0, ws, nws, stream),
                    "u2tok_decoder_decode_pre")
-        K, V = cache.update(sc["kc"], sc["vc"], att.layer_idx)   # DynamicLayer: torch.cat -> dense (B, H_kv, T, d)
-        if not K.is_contiguous():
-            K = K.contiguous()
-        if not V.is_contiguous():
-            V = V.contiguous()
-        kvs = 0
-        if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
-            K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
+        if inplace:
+            lay._commit(T0 + 1)
+            K, V = kd[:, :, :T0 + 1], vd[:, :, :T0 + 1]
+            if window is not None:
+                K, V = K[:, :, -window:], V[:, :, -window:]
+        else:
+            K, V = cache.update(kd, vd, att.layer_idx)   # DynamicLayer: torch.cat -> dense (B, H_kv, T, d)
+            K, V = K.contiguous(), V.contiguous()
+            if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
+                K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
         _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
                                                K.shape[2], kvs, *d["post"], out.data_ptr(), ws, nws, stream),
                    "u2tok_decoder_decode_post")
@@ -447,18 +514,14 @@ def _decode_step(self, x, pe, cache, window=None, pr=None):
 def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor):
     """For a plain HF DynamicCache whose layer `layer_idx` is still empty: put an append-in-place layer there with room for S
     positions (and as many again for the decode steps) and return it; None for every other cache (its `update` is used)."""
-    try:
-        from transformers.cache_utils import DynamicCache, DynamicLayer
-    except ImportError:  # (older transformers: no per-layer cache objects)
-        return None
-    layers = getattr(cache, "layers", None)
-    if type(cache) is not DynamicCache or not isinstance(layers, list) or getattr(cache, "offloading", False):
+    layers = _plain_layers(cache)
+    if layers is None:
         return None
     cls = _append_layer_class()
-    if getattr(cache, "layer_class_to_replicate", None) is DynamicLayer:
+    if getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER:
         while len(layers) <= layer_idx:
-            layers.append(DynamicLayer())
-    if layer_idx >= len(layers) or type(layers[layer_idx]) not in (DynamicLayer, cls) or layers[layer_idx].get_seq_length() != 0:
+            layers.append(_DYN_LAYER())
+    if layer_idx >= len(layers) or type(layers[layer_idx]) not in (_DYN_LAYER, cls) or layers[layer_idx].get_seq_length() != 0:
         return None
     try:
         lay = cls()
@@ -476,7 +539,7 @@ def _mask_hook(module, args, kwargs):
     reference evaluates at batch 1, eval/mrg.py:74); a 2-D mask with zeros sends the whole call to the stock layers."""
     m = kwargs.get("attention_mask")
     ok = m is None or (torch.is_tensor(m) and m.dim() == 2 and bool(m.to(torch.bool).all()))
-    module._u2_prefill_mask_ok = ok
+    module._u2_stack.mask_ok = ok
     return None
 
 
@@ -518,44 +581,43 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     activation, partial rotary, a head dim outside 64 / 96 / 128) -- is skipped instead of refused.
     train=True (opt-in): a patched Llama / Qwen3 layer called with grad enabled takes the training route of decoder_train.py
     (forward and backward on the library's kernels) when its conditions hold.  prefill=False: no fused prefill / decode (the
-    layers are patched for the training route only).  Both flags are set anew by every call.
+    layers are patched for the training route only).  The three switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
-    base = model.get_model() if hasattr(model, "get_model") else getattr(model, "model", model)
+    base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
         raise RuntimeError("enable_fused_prefill: no decoder layers found (expected an HF Llama / Qwen3 / Phi-3 model)")
-    n = 0
+    todo = []
     for layer in layers:
-        if hasattr(layer, "_u2_prefill"):
+        if is_patched(layer):
             continue
         layout = _layout_of(layer)
         if layout is None:
             if strict:
                 raise RuntimeError(f"enable_fused_prefill: unsupported decoder layer {type(layer).__name__}")
             continue   # (another layer layout: stays stock)
-        if not _layer_protocol_ok(layer, base):
-            continue
-        layer._u2_prefill = {"orig": layer.forward, "owner": base, "layout": layout}
+        if _layer_protocol_ok(layer, base):
+            todo.append((layer, layout))
+    stack = base.__dict__.get("_u2_stack")
+    if stack is None:
+        stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
+    stack.decode, stack.train, stack.prefill = bool(decode), bool(train), bool(prefill)
+    for layer, layout in todo:
+        layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
-        n += 1
-    base._u2_fused_decode = bool(decode)
-    base._u2_train = bool(train)
-    base._u2_prefill_on = bool(prefill)
-    if not hasattr(base, "_u2_prefill_hook"):
-        base._u2_prefill_mask_ok = True
-        base._u2_prefill_hook = base.register_forward_pre_hook(_mask_hook, with_kwargs=True)
-    return n
+    return len(todo)
 
 
 def disable_fused_prefill(model) -> None:
-    base = model.get_model() if hasattr(model, "get_model") else getattr(model, "model", model)
+    base = _stack_of(model)
     for layer in base.layers:
         st = layer.__dict__.pop("_u2_prefill", None)
         if st is not None:
-            layer.forward = st["orig"]
-    hook = base.__dict__.pop("_u2_prefill_hook", None)
-    if hook is not None:
-        hook.remove()
-    base.__dict__.pop("_u2_decode_scratch", None)
-    base.__dict__.pop("_u2_train", None)
-    base.__dict__.pop("_u2_prefill_on", None)
+            layer.forward = st.orig
+    stack = base.__dict__.pop("_u2_stack", None)
+    if stack is not None:
+        stack.hook.remove()
+
+
+def _stack_of(model):
+    return model.get_model() if hasattr(model, "get_model") else getattr(model, "model", model)
