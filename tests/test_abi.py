@@ -68,3 +68,41 @@ def test_null_arguments_are_rejected_not_dereferenced(lib):
                                None) == -1
     assert lib.u2tok_topk_sorted(None, None, 1, 8, 4, None) == -1
     assert lib.u2tok_im2col_patches(None, 0, None, 1, 32, 64, 64, 4, 16, 16, None) == -1
+
+
+def test_flash_attention_d64_bwd_rejects_bad_arguments(lib):
+    """u2tok_flash_attention_d64_bwd returns before any launch or memory access on arguments it cannot take."""
+    ERR_ARG, ERR_WS = -1, -3
+    P = 1 << 20   # a 256-byte aligned address that is never dereferenced
+    H, S = 4, 8
+    # q, k, v, ld_qkv, bs_qkv, out, d_out, ld_o, bs_o, dq, dk, dv, ld_d, bs_d, nb, S, H, scale, lse, lse_ld, ws, ws_bytes, stream
+    args = [P, P + 512, P + 1024, 3 * H * 64, S * 3 * H * 64, P, P, H * 64, S * H * 64, P, P + 512, P + 1024, 3 * H * 64,
+            S * 3 * H * 64, 1, S, H, 0.125, None, 0, P, 1 << 20, None]
+
+    def call(**kw):
+        a = list(args)
+        for i, v in kw.items():
+            a[int(i[1:])] = v
+        return lib.u2tok_flash_attention_d64_bwd(*a)
+
+    for i in (0, 1, 2, 5, 6, 9, 10, 11, 20):                  # every pointer but lse and the stream
+        assert call(**{f"a{i}": None}) == ERR_ARG, i
+    assert call(a3=3 * H * 64 + 4) == ERR_ARG                 # ld_qkv not a multiple of 8 elements
+    assert call(a7=H * 64 + 4) == ERR_ARG                     # ld_o likewise
+    assert call(a12=3 * H * 64 + 2) == ERR_ARG                # ld_d not a multiple of 4 elements
+    assert call(a3=H * 64 - 8) == ERR_ARG                     # ld < H * 64
+    assert call(a7=H * 64 - 8) == ERR_ARG
+    assert call(a12=H * 64 - 8) == ERR_ARG
+    assert call(a0=P + 8) == ERR_ARG                          # q not 16-byte aligned
+    assert call(a20=P + 128) == ERR_ARG                       # workspace not 256-byte aligned
+    assert call(a14=0) == ERR_ARG and call(a15=0) == ERR_ARG and call(a16=0) == ERR_ARG
+    assert call(a17=0.0) == ERR_ARG                           # scale must be positive
+    assert call(a14=16384, a16=4) == ERR_ARG                  # nb * H > 65535
+    assert call(a18=P, a19=S - 1) == ERR_ARG                  # lse_ld < S
+    assert call(a18=P + 2, a19=S) == ERR_ARG                  # lse not 4-byte aligned
+    assert call(a21=16) == ERR_WS                             # short workspace
+    need = lib.u2tok_flash_attention_d64_bwd_workspace_bytes(1, S, H)
+    assert need == 2 * 256 * ((H * 64 * 4 + 255) // 256) and call(a21=need - 1) == ERR_WS
+    assert lib.u2tok_flash_attention_d64_bwd_workspace_bytes(0, S, H) == 0
+    assert lib.u2tok_flash_attention_d64_bwd_workspace_bytes(1, 0, H) == 0
+    assert lib.u2tok_flash_attention_d64_bwd_workspace_bytes(1, S, 0) == 0

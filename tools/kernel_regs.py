@@ -37,7 +37,7 @@ if __name__ == "__main__":
     for obj in sys.argv[1:]:
         for k in kernels(obj):
             n = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip()
-            n = re.sub(r"\(.*", "", n).replace("void u2::", "")
+            n = re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).replace("void u2::", "")
             g = lambda key: str(k.get(key, "-"))  # noqa: E731
             print(f"{n[:64]:64s} vgpr={g('vgpr_count'):>3s} agpr={g('agpr_count'):>3s} sgpr={g('sgpr_count'):>3s} "
                   f"lds={g('group_segment_fixed_size'):>6s} scratch={g('private_segment_fixed_size')} "

@@ -212,9 +212,11 @@ int flash_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16
                         const bf16_t* qx, const bf16_t* kx, const bf16_t* vx, bf16_t* outx, int64_t x_bs, int64_t ox_bs,
                         int n_extra, float* lse, int64_t lse_ld, hipStream_t stream,  // lse: optional row statistics out
                         int q_prescaled = 0);  // 1: q and qx already carry scale * log2 e (S >= 512: the double pipeline)
-// Backward of the same attention (attn_bwd.hip): dq / dk / dv of out = softmax(q k^T scale) v for head dim 64, all S rows
-// of a batch in ONE row-major view (q, k, v: row r of batch b at + b*bs_qkv + r*ld_qkv, head h at column h*64; o / dout with
-// ld_o / bs_o; dq / dk / dv with ld_d / bs_d).  lse: optional row statistics of the forward kernel.  Workspace: the row statistics (lse, D).
+// Backward of the same attention: dq / dk / dv of out = softmax(q k^T scale) v for head dim 64, all S rows of a batch in ONE
+// row-major view (q, k, v: row r of batch b at + b*bs_qkv + r*ld_qkv, head h at column h*64; o / dout with ld_o / bs_o;
+// dq / dk / dv with ld_d / bs_d).  lse: optional row statistics of the forward kernel.  Workspace: the row statistics (lse, D).
+// The non-causal, equal-heads instantiation of the one flash backward pair of attn_bwd.hip (bwd_dq_kernel, bwd_dkv_kernel);
+// attention_gqa_bwd below is its causal, grouped-query one.  Each entry point keeps its own argument checks.
 size_t flash_attention_d64_bwd_workspace_bytes(int nb, int S, int H);
 int flash_attention_d64_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
                             const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
@@ -241,8 +243,9 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
                  hipStream_t stream);
 // The decoder training route (u2tokenizer_amd/decoder_train.py).  attention_gqa_ex (tokattn.hip): attention_ex's causal GQA
 // call with per-sequence key lengths kv_len (key j of sequence b visible iff j < kv_len[b]) and optional row statistics lse
-// ((nb * H, lse_ld), log2 units); both null: attention_ex itself.  attention_gqa_bwd (attn_gqa_bwd.hip): its flash backward,
-// d = 64 / 128, Sq = Skv = S, layout of flash_attention_d64_bwd with Hq query and Hkv kv heads.  rmsnorm_bwd,
+// ((nb * H, lse_ld), log2 units); both null: attention_ex itself.  attention_gqa_bwd (attn_bwd.hip, the causal instantiations
+// of the pair behind flash_attention_d64_bwd): its flash backward, d = 64 / 128, Sq = Skv = S, layout of flash_attention_d64_bwd
+// with Hq query and Hkv kv heads.  rmsnorm_bwd,
 // qk_norm_rope_bwd, swiglu_bwd (backward.hip): the row operations' backward.
 int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
                      int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,

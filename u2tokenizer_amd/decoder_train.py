@@ -12,7 +12,8 @@ torch.autograd.Functions over the C-ABI blocks, each saving what its backward ne
     ONE packed dW backward, handed to autograd as one view per Parameter -- `.grad` of q_proj / k_proj / v_proj (or gate / up)
     receives its rows, accumulated in place into an existing `.grad` (a view into a flat optimizer bucket stays one);
   * the attention is the causal GQA kernel with per-sequence key lengths (u2tok_attention_gqa_ex, which also leaves the row
-    statistics) and its flash backward (u2tok_attention_gqa_bwd), which writes dq | dk | dv straight into one packed gradient;
+    statistics) and its flash backward (u2tok_attention_gqa_bwd: the causal instantiations of csrc/attn_bwd.hip's bwd_dq_kernel /
+    bwd_dkv_kernel, the pair the ViT's backward also runs), which writes dq | dk | dv straight into one packed gradient;
   * RMSNorm, head norm + rotary and SwiGLU have their backward kernels in csrc/backward.hip (fixed-order fp32 weight gradients);
   * torch moves data and adds the residual stream's two gradient contributions.
 
