@@ -460,6 +460,21 @@ int u2tok_qk_norm_rope_bwd(void* dqkv, const void* pre, const void* wq, const vo
 int u2tok_swiglu_bwd(const void* gu, const void* dact, void* dgu, int64_t rows, int32_t I, int64_t ld_gu, int64_t ld_da,
                      int64_t ld_dgu, u2tok_stream_t stream);
 
+/* ---- the loss head (u2tokenizer_amd/loss_head.py; opt-in): lm_head + cross-entropy without the rows x vocab logits ----------
+ * Both calls work on a block Z of logits: rows x Vs elements (16-byte aligned, leading dimension ldz >= Vs, ldz % 8 == 0,
+ * Vs % 8 == 0) holding the vocabulary columns [v0, v0 + Vs); row offsets are 64-bit.  labels: int64[rows].
+ * u2tok_ce_lse_update reads the block once and folds it into the per-row running state (fp32[rows] each): m = running maximum,
+ * l = running sum of exp(z - m), zt = the label's logit (written when v0 <= label < v0 + Vs, else left alone).  Before the first
+ * slice the caller sets m = -inf, l = 0; after the last, the row's log-sum-exp is m + log(l).  No atomics, fixed summation order:
+ * bit-repeatable. */
+int u2tok_ce_lse_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, float* m, float* l,
+                        float* zt, u2tok_stream_t stream);
+/* In place:  Z[r][j] <- elem(coef[r] * (exp(float(Z[r][j]) - lse[r]) - [v0 + j == labels[r]])),  lse[r] the NATURAL-log sum of
+ * exponentials of the whole row (m + log(l) above), coef[r] the upstream gradient of the row's loss: the element-type rounding
+ * of the fp32 gradient of the fp32 logits, which is what F.cross_entropy(logits.float(), ...) hands back to lm_head. */
+int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, const float* lse,
+                          const float* coef, u2tok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,10 @@ projector, 4-layer tokenizer at E = 4096, embedding splice), the stock HF Qwen3-
 bf16, gradient checkpointing as the reference's scripts enable it) forward + backward on the 1024 spliced embeddings, and one
 Zero1AdamW step (bucketed flat gradients, fused HIP AdamW kernel; one rank: no collective) with global gradient clipping.
 
-    python tools/train_step_full.py [steps]        prints one JSON line {"ms_step": ..., "ms_fwd_bwd": ..., "ms_optimizer": ...}
+    python tools/train_step_full.py [steps] [--fused-loss-head]
+                                                   prints one JSON line {"ms_step": ..., "ms_fwd_bwd": ..., "ms_optimizer": ...}
+--fused-loss-head: `config.u2_fused_loss_head` -- lm_head + cross-entropy on the loss head of u2tokenizer_amd/loss_head.py (labelled
+rows only, no rows x vocab logits) instead of the stock HF head.
 """
 import json
 import sys
@@ -46,11 +49,12 @@ def build_model(device, layers=36):
     return m, cfg
 
 
-def run(steps=3, layers=36, device=None):
-    from u2tokenizer_amd import dp, ops
+def run(steps=3, layers=36, device=None, fused_loss_head=False):
+    from u2tokenizer_amd import dp, loss_head, ops
     device = device or torch.device("cuda", 0)
     ops.device_check()
     m, cfg = build_model(device, layers)
+    m.config.u2_fused_loss_head = bool(fused_loss_head)
     m.train()
     m.gradient_checkpointing_enable()
     m.config.use_cache = False
@@ -87,6 +91,7 @@ def run(steps=3, layers=36, device=None):
     return {"ms_step": round(fb + op, 1), "ms_forward_backward": round(fb, 1), "ms_optimizer": round(op, 1),
             "parameters": nparam, "decoder_layers": layers, "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
             "grad_norm": opt.last_grad_norm, "losses": [round(x, 4) for x in losses],
+            "fused_loss_head": bool(fused_loss_head), "loss_head_calls": loss_head.stats["calls"],
             "what": "one stage-1 step on ONE GPU at BASELINE configs[3] size: u2Qwen3-8B-shaped model (HIP path + stock HF "
                     "36-layer decoder with gradient checkpointing), batch 1, 1024 spliced embeddings, loss.backward(), "
                     "Zero1AdamW.step() (flat bf16 gradient buckets, fused AdamW kernel, clipping at 1.0; one rank = no "
@@ -94,5 +99,6 @@ def run(steps=3, layers=36, device=None):
 
 
 if __name__ == "__main__":
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    print(json.dumps(run(n)), flush=True)
+    args = [a for a in sys.argv[1:] if a != "--fused-loss-head"]
+    n = int(args[0]) if args else 3
+    print(json.dumps(run(n, fused_loss_head="--fused-loss-head" in sys.argv[1:])), flush=True)

@@ -160,6 +160,8 @@ SIGNATURES = {
     "u2tok_flash_attention_d64_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "u2tok_flash_attention_d64_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
                                              _i32, _i32, _i32, _f32, _vp, _i64, _vp, _sz, _vp]),
+    "u2tok_ce_lse_update": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "u2tok_ce_grad_inplace": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
 }
 
 ERRORS = {-1: "U2TOK_ERR_ARG (bad dimension / null pointer / unsupported combination)",

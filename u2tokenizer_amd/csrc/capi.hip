@@ -362,6 +362,14 @@ int u2tok_rowdot_bf16(const void* a, const void* b, float* out, int64_t rows, in
                       u2tok_stream_t stream) {
   return rowdot_bf16(BF(a), BF(b), out, rows, C, lda, ldb, ST(stream));
 }
+int u2tok_ce_lse_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, float* m, float* l,
+                        float* zt, u2tok_stream_t stream) {
+  return ce_lse_update(BF(Z), ldz, rows, Vs, v0, labels, m, l, zt, ST(stream));
+}
+int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, const float* lse,
+                          const float* coef, u2tok_stream_t stream) {
+  return ce_grad_inplace(BFW(Z), ldz, rows, Vs, v0, labels, lse, coef, ST(stream));
+}
 int u2tok_adamw_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, const uint8_t* group, void* out_bf16,
                      int64_t n, const float* lr, const float* weight_decay, int32_t ngroups, float beta1, float beta2, float eps,
                      int32_t step, float grad_scale, const float* grad_coef, u2tok_stream_t stream) {

@@ -187,6 +187,11 @@ int softmax_bwd(const bf16_t* P, const float* dP, bf16_t* dS, int64_t nrows, int
 int relbias_grad(const bf16_t* dS, float* dtable, int nz, int S, int H, int64_t ldp, int max_len, hipStream_t stream);
 int rowdot_bf16(const bf16_t* a, const bf16_t* b, float* out, int64_t rows, int C, int64_t lda, int64_t ldb,
                 hipStream_t stream);
+// loss head (loss.hip): online log-sum-exp over one vocabulary slice of the logits, and the cross-entropy gradient written over them
+int ce_lse_update(const bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, float* m, float* l, float* zt,
+                  hipStream_t stream);
+int ce_grad_inplace(bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, const float* lse, const float* coef,
+                    hipStream_t stream);
 // sharded AdamW step (dp.py): see backward.hip
 struct AdamWArgs {
   float lr[8], wd[8];  // per parameter group

@@ -76,6 +76,48 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill)
             checked.add(grad)
 
+    def _loss_head_ok(self, kwargs=None) -> bool:
+        """Whether a call with labels takes the loss head of loss_head.py (`config.u2_fused_loss_head`, default False) instead
+        of lm_head + ForCausalLMLoss: lm_head exactly nn.Linear, no bias, no hooks (a LoRA-wrapped or probed head keeps the stock
+        path, as prefill._is_stock has it for the layers), bf16 on the GPU in a shape the head computes, the stock causal-LM
+        loss, all positions scored (no `logits_to_keep`) and a ModelOutput asked for."""
+        if not bool(getattr(self.config, "u2_fused_loss_head", False)):
+            return False
+        kwargs = kwargs or {}
+        keep = kwargs.get("logits_to_keep", 0)
+        if not (keep is None or (isinstance(keep, int) and keep == 0)) or kwargs.get("return_dict", True) is False:
+            return False
+        from transformers.loss.loss_utils import ForCausalLMLoss
+        return self._plain_lm_head() and self.loss_function is ForCausalLMLoss
+
+    def _plain_lm_head(self) -> bool:
+        """lm_head is exactly nn.Linear without bias or hooks, bf16 on the GPU, in a shape the loss head computes: reading its
+        `.weight` instead of calling it is then the same computation."""
+        from .loss_head import supported
+        from .prefill import _HOOK_TABLES
+        head = self.lm_head
+        return (type(head) is nn.Linear and head.bias is None and not any(getattr(head, t, None) for t in _HOOK_TABLES)
+                and head.weight.is_cuda and supported(head.in_features, head.out_features, head.weight.dtype))
+
+    def token_logprobs(self, images: Optional[torch.Tensor], input_ids: torch.LongTensor, labels: torch.LongTensor,
+                       attention_mask: Optional[torch.Tensor] = None, question_ids: Optional[torch.LongTensor] = None,
+                       **kwargs) -> torch.Tensor:
+        """log p(label) of every position, (B, S) fp32, 0 where the label is -100: the multimodal preparation, the decoder, then
+        the loss head on the labels as `prepare_inputs_for_multimodal` returns them (shifted by one inside) -- what a DPO trainer
+        takes from the policy (with grad) and from the reference model (under no_grad) as gather(log_softmax(logits)) * mask
+        (dpo_u2trainer.py:295-309), without the logits.  The head must qualify (_plain_lm_head; the config switch is not
+        needed): there is no fallback."""
+        from . import loss_head
+        self._maybe_fuse()
+        if not self._plain_lm_head():
+            raise RuntimeError("token_logprobs: needs a plain nn.Linear lm_head (no bias, hooks or adapters), bf16 on the GPU, with "
+                               "vocab % 8 == 0 and hidden % 64 == 0")
+        (input_ids, position_ids, attention_mask, _, inputs_embeds, labels) = self.prepare_inputs_for_multimodal(
+            input_ids, None, attention_mask, None, labels, images, question_ids)
+        hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                            inputs_embeds=inputs_embeds, use_cache=False, **kwargs).last_hidden_state
+        return loss_head.token_logprobs(hidden, self.lm_head.weight, labels)
+
     def forward(self, images: Optional[torch.FloatTensor] = None, input_ids: torch.LongTensor = None,
                 labels: Optional[torch.LongTensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 question_ids: Optional[torch.LongTensor] = None, position_ids: Optional[torch.LongTensor] = None,
@@ -95,6 +137,17 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                      ("return_dict", return_dict)):
             if v is not None:
                 kwargs[k] = v
+        if labels is not None and self._loss_head_ok(kwargs):
+            from . import loss_head
+            outputs = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                                 past_key_values=past_key_values, inputs_embeds=inputs_embeds, use_cache=use_cache, **kwargs)
+            shifted = kwargs.get("shift_labels")
+            loss = loss_head.linear_cross_entropy(
+                outputs.last_hidden_state, self.lm_head.weight, labels if shifted is None else shifted,
+                ignore_index=kwargs.get("ignore_index", -100), num_items_in_batch=kwargs.get("num_items_in_batch"),
+                shift=shifted is None)
+            return CausalLMOutputWithPast(loss=loss, logits=None, past_key_values=outputs.past_key_values,
+                                          hidden_states=outputs.hidden_states, attentions=outputs.attentions)
         return super().forward(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                use_cache=use_cache, **kwargs)

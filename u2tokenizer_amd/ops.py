@@ -313,11 +313,13 @@ def gemm_swiglu(a: torch.Tensor, w_gate_up: torch.Tensor, out: Optional[torch.Te
 
 
 @_guarded
-def gemm_kmajor(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool, alpha=1.0, out_f32=False) -> torch.Tensor:
+def gemm_kmajor(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool, alpha=1.0, out_f32=False,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Products with K-major operands (no transposes in HBM; u2tok_gemm_bf16 flags 128 / 256):
          a_kmajor = False:  C (M, N) = A (M, K) @ B (K, N)          -- dX = dY W
          a_kmajor = True:   C (M, N) = A (K, M)^T @ B (K, N)        -- dW = dY^T X
-    Dense 2-D bf16 operands; the K-major dimensions (N, and M when a_kmajor) must be multiples of 8."""
+    Dense 2-D bf16 operands; the K-major dimensions (N, and M when a_kmajor) must be multiples of 8.  out: a dense (M, N) tensor
+    of the result's type to write into (e.g. a block of rows of a larger gradient)."""
     h = _lib.load_library()
     a = _need(a, ELEM, "A").contiguous()
     b = _need(b, ELEM, "B").contiguous()
@@ -325,7 +327,11 @@ def gemm_kmajor(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool, alpha=1.0, 
     M = a.shape[1] if a_kmajor else a.shape[0]
     if (a.shape[0] if a_kmajor else a.shape[1]) != K:
         raise RuntimeError(f"gemm_kmajor: contraction sizes differ ({tuple(a.shape)}, {tuple(b.shape)}, a_kmajor={a_kmajor})")
-    out = torch.empty((M, N), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
+    dtype = torch.float32 if out_f32 else elem_dtype()
+    if out is None:
+        out = torch.empty((M, N), dtype=dtype, device=a.device)
+    elif out.shape != (M, N) or out.dtype != dtype or not out.is_contiguous() or out.device != a.device:
+        raise RuntimeError(f"gemm_kmajor: out must be a dense ({M}, {N}) {dtype} tensor on {a.device}")
     flags = GEMM_B_KMAJOR | (GEMM_A_KMAJOR if a_kmajor else 0) | (GEMM_OUT_F32 if out_f32 else 0)
     st = h.u2tok_gemm_bf16(_ptr(a), _ptr(b), _ptr(out), None, None, M, N, K, a.shape[1], N, N, N, 1, 1,
                            0, 0, 0, 0, 0, 0, 0, 0, float(alpha), flags, _stream())
@@ -992,3 +998,41 @@ def swiglu_bwd(gate_up: torch.Tensor, d_act: torch.Tensor) -> torch.Tensor:
     _lib.check(h.u2tok_swiglu_bwd(_ptr(gate_up), _ptr(d_act), _ptr(dgu), rows, two_i // 2, gate_up.stride(0), two_i // 2, two_i,
                                   _stream()), "u2tok_swiglu_bwd")
     return dgu
+
+
+def _ce_block(z: torch.Tensor, labels: torch.Tensor, who: str):
+    _need(z, ELEM, "z")
+    if z.dim() != 2 or z.stride(1) != 1:
+        raise RuntimeError(f"{who}: z (rows, Vs) with a contiguous last dim")
+    if labels.dtype != torch.int64 or labels.shape != (z.shape[0],) or not labels.is_contiguous():
+        raise RuntimeError(f"{who}: labels must be a dense int64 (rows,) tensor")
+    return z.shape[0], z.shape[1], z.stride(0)
+
+
+def _ce_f32(t: torch.Tensor, rows: int, name: str) -> torch.Tensor:
+    _need(t, torch.float32, name)
+    if t.shape != (rows,) or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a dense fp32 ({rows},) tensor")
+    return t
+
+
+@_guarded
+def ce_lse_update(z: torch.Tensor, v0: int, labels: torch.Tensor, m: torch.Tensor, l: torch.Tensor, zt: torch.Tensor) -> None:
+    """One vocabulary slice of the loss head (u2tok_ce_lse_update): z (rows, Vs) logits of the columns [v0, v0 + Vs) folded into the
+    rows' running (m, l) = (max, sum exp(z - m)), updated in place -- m = -inf, l = 0 before the first slice -- and zt = the label's
+    logit where this slice holds it.  The row's natural-log sum of exponentials is m + log(l) after the last slice."""
+    h = _lib.load_library()
+    rows, Vs, ldz = _ce_block(z, labels, "ce_lse_update")
+    _lib.check(h.u2tok_ce_lse_update(_ptr(z), ldz, rows, Vs, int(v0), _ptr(labels), _ptr(_ce_f32(m, rows, "m")),
+                                     _ptr(_ce_f32(l, rows, "l")), _ptr(_ce_f32(zt, rows, "zt")), _stream()), "u2tok_ce_lse_update")
+
+
+@_guarded
+def ce_grad_inplace(z: torch.Tensor, v0: int, labels: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """z[r][j] <- coef[r] (exp(z[r][j] - lse[r]) - [v0 + j == labels[r]]) rounded to the element type, in place
+    (u2tok_ce_grad_inplace; lse: natural log).  Returns z."""
+    h = _lib.load_library()
+    rows, Vs, ldz = _ce_block(z, labels, "ce_grad_inplace")
+    _lib.check(h.u2tok_ce_grad_inplace(_ptr(z), ldz, rows, Vs, int(v0), _ptr(labels), _ptr(_ce_f32(lse, rows, "lse")),
+                                       _ptr(_ce_f32(coef, rows, "coef")), _stream()), "u2tok_ce_grad_inplace")
+    return z
