@@ -362,6 +362,24 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const void* x, con
                               int32_t T, int64_t kv_stride, const void* Wo, const void* bo, const void* w_post_norm, const void* Wgu,
                               const void* bgu, const void* Wdown, const void* bdown, void* out, void* workspace,
                               size_t workspace_bytes, u2tok_stream_t stream);
+/* The second half with the BATCHED decode attention (u2tok_decode_attention: one launch for all B sequences and heads, plus one
+ * merge) in place of a launch pair per sequence, and a first visible cache position per sequence: kv_start (device int32[B] or
+ * NULL) -- query b attends over positions kv_start[b] .. T - 1, the cache of a LEFT-padded batch.  Same workspace. */
+int u2tok_decoder_decode_post_range(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
+                                    int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo, const void* bo,
+                                    const void* w_post_norm, const void* Wgu, const void* bgu, const void* Wdown, const void* bdown,
+                                    void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* Batched decode attention: out[b] = softmax(q[b] K[b]^T scale over keys kv_start[b] <= j < T) V[b] for B sequences of ONE query
+ * row each.  q / out: (B, Hq * D) rows, ldq / ldo elements apart (head h at column h * D); K / V: (B, Hkv, T, D), kv_stride
+ * elements between (batch, kv head) entries (0: dense, T * D) -- an append-in-place buffer or the dense cache; D in {64, 96, 128},
+ * Hq / Hkv <= 16, B <= 65535.  One workgroup per (sequence, kv head, key split) stages each K / V tile once for the whole group of
+ * query heads; the splits are fixed ranges of [0, T) (tiles wholly below kv_start[b] are skipped, a split without a visible key is
+ * empty), their fp32 partial results are merged in a fixed order: no atomics, bit-repeatable.  A sequence without a visible key
+ * gets zeros.  workspace: u2tok_decode_attention_workspace_bytes(B, Hq, Hkv, T, D) bytes (0: no splits), 16-byte aligned. */
+size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D);
+int u2tok_decode_attention(const void* q, const void* K, const void* V, void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T,
+                           int32_t D, int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int32_t* kv_start,
+                           void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
 /* in-place rotate-half RoPE (rope.py:6-13,77-80): rows indexed (outer, s, inner), position = s; inverse != 0 rotates
  * the other way (the backward of the rotation) */
@@ -430,6 +448,14 @@ int u2tok_attention_gqa_ex(const void* q, const void* k, const void* v, void* ou
                            int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                            int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_len,
                            float* lse, int64_t lse_ld, u2tok_stream_t stream);
+/* The same with a first visible key per sequence: kv_start (device int32[nb] or NULL) -- key j of sequence b is visible iff
+ * kv_start[b] <= j < kv_len[b] (and j <= i + Skv - Sq when causal): HF's mask of a LEFT-padded 2-D attention mask (kv_start) or a
+ * right-padded one (kv_len).  A query row that sees no key (a padding position) gets exact zeros, and 0 in lse.  Either pointer may
+ * be NULL; all three NULL: exactly u2tok_attention_gqa. */
+int u2tok_attention_gqa_range(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                              int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                              int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
+                              const int32_t* kv_len, float* lse, int64_t lse_ld, u2tok_stream_t stream);
 /* Its backward (causal, Sq = Skv = S, d = 64 or 128): dq, dk, dv from q, k, v, out, d_out and (optional) lse of
  * u2tok_attention_gqa_ex, honouring kv_len.  Layout of u2tok_flash_attention_d64_bwd with Hq query heads (q / dq: head h at
  * column h*d) and Hkv kv heads (k, v / dk, dv: head h at column h*d of their pointers): with q | k | v column views of one

@@ -134,6 +134,10 @@ SIGNATURES = {
                                         _sz, _vp]),
     "u2tok_decoder_decode_post": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                          _vp]),
+    "u2tok_decoder_decode_post_range": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _sz, _vp]),
+    "u2tok_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "u2tok_decode_attention": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),
     "u2tok_rope_apply": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "u2tok_gelu_fwd": (_i32, [_vp, _vp, _i64, _vp]),
     "u2tok_gelu_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp]),
@@ -143,6 +147,8 @@ SIGNATURES = {
     "u2tok_layernorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp]),
     "u2tok_attention_gqa_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                                       _i64, _i64, _f32, _i32, _vp, _vp, _i64, _vp]),
+    "u2tok_attention_gqa_range": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "u2tok_attention_gqa_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "u2tok_attention_gqa_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
                                        _i32, _i32, _f32, _vp, _vp, _i64, _vp, _sz, _vp]),

@@ -323,6 +323,23 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* c, const void* x, const
   return decoder_decode_post(dec_cfg(c), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, BF(Wo), BF(bo), BF(w_post_norm), BF(Wgu), BF(bgu),
                              BF(Wdown), BF(bdown), BFW(out), workspace, workspace_bytes, ST(stream));
 }
+int u2tok_decoder_decode_post_range(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V,
+                                    int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo, const void* bo,
+                                    const void* w_post_norm, const void* Wgu, const void* bgu, const void* Wdown, const void* bdown,
+                                    void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  if (!dec_ok(c)) return U2_ERR_ARG;
+  return decoder_decode_post_range(dec_cfg(c), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, kv_start, BF(Wo), BF(bo), BF(w_post_norm),
+                                   BF(Wgu), BF(bgu), BF(Wdown), BF(bdown), BFW(out), workspace, workspace_bytes, ST(stream));
+}
+size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
+  return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);
+}
+int u2tok_decode_attention(const void* q, const void* K, const void* V, void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T,
+                           int32_t D, int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int32_t* kv_start,
+                           void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return decode_attention(BF(q), BF(K), BF(V), BFW(out), B, Hq, Hkv, T, D, ldq, kv_stride, ldo, scale, kv_start, workspace,
+                          workspace_bytes, ST(stream));
+}
 int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, int64_t ld_in, int64_t ld_out,
                       u2tok_stream_t stream) {
   return swiglu_bf16(BF(gate_up), BFW(out), rows, I, ld_in, ld_out, ST(stream));
@@ -401,6 +418,13 @@ int u2tok_attention_gqa_ex(const void* q, const void* k, const void* v, void* ou
                            float* lse, int64_t lse_ld, u2tok_stream_t stream) {
   return attention_gqa_ex(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
                           scale, causal, kv_len, lse, lse_ld, ST(stream));
+}
+int u2tok_attention_gqa_range(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                              int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                              int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
+                              const int32_t* kv_len, float* lse, int64_t lse_ld, u2tok_stream_t stream) {
+  return attention_gqa_range(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
+                             scale, causal, kv_start, kv_len, lse, lse_ld, ST(stream));
 }
 size_t u2tok_attention_gqa_bwd_workspace_bytes(int32_t nb, int32_t S, int32_t Hq) {
   return attention_gqa_bwd_workspace_bytes(nb, S, Hq);

@@ -213,7 +213,9 @@ size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
   const size_t rows = (size_t)c.B;
   size_t n = rows * ((size_t)3 * c.E + (size_t)c.Hq * c.D + (size_t)3 * c.I) * sizeof(bf16_t);  // xn, h, hn | ctx | gu (2 I), act
   n = (n + 255) & ~(size_t)255;
-  return n + tok_attention_workspace_bytes(c.Hkv, c.Hq / c.Hkv, 1, T, c.D) + 256;
+  // the attention's key-split partials: the per-sequence form (decoder_decode_post) or the batched kernel (decoder_decode_post_range)
+  return n + std::max(tok_attention_workspace_bytes(c.Hkv, c.Hq / c.Hkv, 1, T, c.D), decode_attention_workspace_bytes(c.B, c.Hq, c.Hkv, T, c.D)) +
+         256;
 }
 
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
@@ -236,9 +238,11 @@ int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_n
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
-int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                        int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
-                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
+// (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence)
+static int decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                       int64_t kv_stride, bool batched, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
+                       const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
   if (c.B <= 0 || c.B > 16 || T <= 0 || !x || !qkv || !K || !V || !Wo || !w_post_norm || !Wgu || !Wdown || !out || !ws) return U2_ERR_ARG;
   if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
@@ -254,7 +258,11 @@ int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, 
   const float scale = c.scale;
   if (kv_stride == 0) kv_stride = (int64_t)T * c.D;
   if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
-  for (int b = 0; b < c.B; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
+  if (batched) {
+    const int e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, scale, kv_start, aws, aws_bytes, st);
+    if (e != U2_OK) return e;
+  }
+  for (int b = 0; b < c.B && !batched; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
     const int e = attention_ex(qkv + (size_t)b * nq, K + (size_t)b * c.Hkv * kv_stride, V + (size_t)b * c.Hkv * kv_stride,
                                ctx + (size_t)b * qd, c.Hkv, 1, T, g, 1, c.D, /*ldq*/ (int64_t)g * c.D, /*ldk*/ c.D, /*ldv*/ c.D,
                                /*ldo*/ (int64_t)g * c.D, /*q_bs*/ (int64_t)g * c.D, /*k_bs*/ kv_stride, /*v_bs*/ kv_stride,
@@ -280,6 +288,20 @@ int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, 
     if (e != U2_OK) return e;
   }
   return dec_linear(act, c.I, Wdown, bdown, out, c.E, c.B, c.I, c.E, h, c.E, st);
+}
+
+int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                        int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
+                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  return decode_post(c, x, qkv, K, V, T, kv_stride, false, nullptr, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, out, ws, ws_bytes, st);
+}
+
+int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                              int64_t kv_stride, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
+                              const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
+                              size_t ws_bytes, hipStream_t st) {
+  if (c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3)) return U2_ERR_ARG;
+  return decode_post(c, x, qkv, K, V, T, kv_stride, true, kv_start, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, out, ws, ws_bytes, st);
 }
 
 }  // namespace u2

@@ -255,6 +255,11 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
 int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
                      int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                      int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld, hipStream_t stream);
+// attention_gqa_range: attention_gqa_ex plus a first visible key per sequence (kv_start; the padded inference routes of prefill.py).
+int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
+                        int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
+                        int64_t o_bs, float scale, int causal, const int* kv_start, const int* kv_len, float* lse, int64_t lse_ld,
+                        hipStream_t stream);
 size_t attention_gqa_bwd_workspace_bytes(int nb, int S, int Hq);
 int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
                       const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
@@ -288,5 +293,19 @@ int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_n
 int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
                         int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
                         const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
+// decoder_decode_post with the batched decode attention (decode_attn.hip) in place of the per-sequence loop; kv_start: optional (B)
+// first visible cache position per sequence (a left-padded batch)
+int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                              int64_t kv_stride, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
+                              const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
+                              size_t ws_bytes, hipStream_t st);
+// ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
+// One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
+// q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between
+// (batch, kv head) entries; key j of sequence b is visible iff j >= kv_start[b] (NULL: all).
+size_t decode_attention_workspace_bytes(int B, int Hq, int Hkv, int T, int D);
+int decode_attention(const bf16_t* q, const bf16_t* K, const bf16_t* V, bf16_t* out, int B, int Hq, int Hkv, int T, int D,
+                     int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int* kv_start, void* ws, size_t ws_bytes,
+                     hipStream_t stream);
 
 }  // namespace u2

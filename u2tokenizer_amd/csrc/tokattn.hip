@@ -59,6 +59,7 @@ struct TokAttnArgs {
   int causal;    // 1: key j is visible to query i iff j <= i + (Skv - Sq)   (decoder prefill)
   // tok_attn_kernel<DH, true> only (u2tok_attention_gqa_ex, the decoder's training route):
   const int* kv_len;  // optional (nb): key j of sequence b is visible only if j < kv_len[b] (right padding)
+  const int* kv_start;  // optional (nb): ... and only if j >= kv_start[b] (left padding); a row that sees no key writes zeros
   float* lse;         // optional (nb * H, lse_ld): log2 sum_j exp2(s_ij scale log2 e) of each query row, for the backward
   int64_t lse_ld;
 };
@@ -125,7 +126,14 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       kt1_ = min(kt1_, (kvl + BK - 1) / BK);
     }
   }
-  const int kt0 = sp * a.tps, kt1 = kt1_;
+  int kvs = 0, kt0_ = sp * a.tps;  // (EX) keys below kv_start[b] are invisible: whole tiles below it are skipped, the partial one masked
+  if constexpr (EX) {
+    if (a.kv_start) {
+      kvs = max(0, min(a.kv_start[b], Skv));
+      kt0_ = max(kt0_, kvs / BK);
+    }
+  }
+  const int kt0 = kt0_, kt1 = kt1_;
   const int kbeg = kt0 * BK;
 
   const int hkv = h / a.kv_group;
@@ -270,6 +278,11 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
         for (int i = 0; i < NX; ++i)
           if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) >= kvl) x[i] = -INFINITY;
       }
+      if (kt * BK < kvs) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+          if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) < kvs) x[i] = -INFINITY;
+      }
     }
     float mt = x[0];
 #pragma unroll
@@ -280,7 +293,8 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
     mt *= xs;
     if (__any(mt > m_run + TOKATTN_RESCALE_THR)) {  // wave-uniform; always taken on the first tile
       const float m_new = fmaxf(m_run, mt);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      if constexpr (EX) alpha = m_new == -INFINITY ? 1.f : alpha;  // (a row that has seen no key yet: never -inf - (-inf))
       m_run = m_new;
       l_run *= alpha;
 #pragma unroll
@@ -289,9 +303,11 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       }
     }
     float ps = 0.f;
+    float m_sub = m_run;  // (EX: a row without a visible key so far keeps m_run = -inf; its scores are -inf and exp2(-inf - 0) = 0)
+    if constexpr (EX) m_sub = m_run == -INFINITY ? 0.f : m_run;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-      x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], xs, -m_run));
+      x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[i], xs, -m_sub));
       ps += x[i];
     }
     l_run += ps;
@@ -338,10 +354,11 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
   l_tot += __shfl_xor(l_tot, 32, 64);
   if (qrow >= Sq) return;
   if constexpr (EX) {
-    if (a.lse && g == 0) a.lse[((int64_t)b * a.H + h) * a.lse_ld + qrow] = m_run + __builtin_log2f(l_tot);
+    if (a.lse && g == 0) a.lse[((int64_t)b * a.H + h) * a.lse_ld + qrow] = l_tot > 0.f ? m_run + __builtin_log2f(l_tot) : 0.f;
   }
   if (a.ns == 1) {
-    const float inv = 1.f / l_tot;
+    float inv = 1.f / l_tot;
+    if constexpr (EX) inv = l_tot > 0.f ? inv : 0.f;  // (no visible key: o = 0, l = 0 -> exact zeros)
     bf16_t* op = a.out + (int64_t)b * a.o_bs + (int64_t)qrow * a.ldo + h * DH + 4 * g;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
@@ -813,7 +830,7 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
   const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
   a.kv_group = H / Hkv;
   a.causal = causal ? 1 : 0;
-  a.kv_len = nullptr; a.lse = nullptr; a.lse_ld = 0;
+  a.kv_len = nullptr; a.kv_start = nullptr; a.lse = nullptr; a.lse_ld = 0;
   int ns = force_splits > 0 ? std::min(force_splits, ntile) : tok_attn_pick_splits(nb, H, Sq, Skv, d, ws ? ws_bytes : 0);
   if (causal) ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
   const size_t per = (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
@@ -872,11 +889,22 @@ int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* 
                      int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                      int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld,
                      hipStream_t stream) {
-  if (!kv_len && !lse)
+  return attention_gqa_range(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, causal, nullptr,
+                             kv_len, lse, lse_ld, stream);
+}
+
+// ... and with a first visible key per sequence (kv_start: left padding, the inference routes of prefill.py): key j of sequence b is
+// visible iff kv_start[b] <= j < kv_len[b] (and j <= i + Skv - Sq when causal); a query row without a visible key gets zeros (lse 0).
+int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
+                        int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
+                        int64_t o_bs, float scale, int causal, const int* kv_start, const int* kv_len, float* lse, int64_t lse_ld,
+                        hipStream_t stream) {
+  if (!kv_len && !lse && !kv_start)
     return attention_ex(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, nullptr, 0,
                         causal, 1, nullptr, 0, stream);
   if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
-  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq)) return U2_ERR_ARG;
+  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)kv_start & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq))
+    return U2_ERR_ARG;
   if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
     return U2_ERR_ARG;
   TokAttnArgs a;
@@ -887,7 +915,7 @@ int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* 
   a.rel_bias = nullptr; a.max_len = 0;
   a.kv_group = H / Hkv;
   a.causal = causal ? 1 : 0;
-  a.kv_len = kv_len; a.lse = lse; a.lse_ld = lse_ld;
+  a.kv_len = kv_len; a.kv_start = kv_start; a.lse = lse; a.lse_ld = lse_ld;
   a.ns = 1;
   a.tps = (int)cdiv(Skv, tok_attn_bk(d));
   a.opart = nullptr; a.ml = nullptr;

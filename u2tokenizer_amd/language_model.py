@@ -61,7 +61,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         """Patch the decoder layers for the HIP routes of prefill.py, once per grad mode, when the decoder sits on the GPU in a
         type that mode's route computes: without grad `config.u2_fused_prefill` (default True) asks for the prefill and decode
         steps (bf16, or fp16 on the f16 build), with grad `config.u2_fused_decoder_training` (default False)
-        for the training route of decoder_train.py (bf16).  Both switches are passed on as the config has them."""
+        for the training route of decoder_train.py (bf16).  Both switches, and `config.u2_fused_padded_batches` (default False:
+        padded batches on the no-grad routes), are passed on as the config has them."""
         grad = torch.is_grad_enabled()
         train = bool(getattr(self.config, "u2_fused_decoder_training", False))
         prefill = bool(getattr(self.config, "u2_fused_prefill", True))
@@ -73,7 +74,9 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
             return
         from .prefill import INFER_DTYPES, TRAIN_DTYPES, enable_fused_prefill
         if p.dtype in (TRAIN_DTYPES if grad else INFER_DTYPES):
-            enable_fused_prefill(self, strict=False, train=train, prefill=prefill)
+            # (`config.u2_fused_padded_batches`, default False: padded batches on the fused prefill / decode steps)
+            padded = {"padded": True} if bool(getattr(self.config, "u2_fused_padded_batches", False)) else {}
+            enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 
     def _loss_head_ok(self, kwargs=None) -> bool:

@@ -898,6 +898,62 @@ def attention_gqa_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
 
 
 @_guarded
+def attention_gqa_range(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
+                        kv_start: Optional[torch.Tensor] = None, kv_len: Optional[torch.Tensor] = None,
+                        causal: bool = True) -> torch.Tensor:
+    """attention_gqa with a key range per sequence (u2tok_attention_gqa_range): key j of sequence b is visible iff
+    kv_start[b] <= j < kv_len[b] (int32 (nb,) on the GPU each; None: 0 / all keys) and, when causal, j <= i + Skv - Sq -- the mask
+    of a left-padded (kv_start) or right-padded (kv_len) batch.  A query row that sees no key gets zeros.  Both None: the
+    kernel, and the bits, of attention_gqa."""
+    h = _lib.load_library()
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _need(t, ELEM, n)
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise RuntimeError(f"attention_gqa_range: {n} must be (nb, S, H * d) with a contiguous last dim")
+    nb, Sq, Eq = q.shape
+    Skv = k.shape[1]
+    d = Eq // heads
+    if Eq % heads or k.shape != (nb, Skv, kv_heads * d) or v.shape != k.shape or heads % kv_heads:
+        raise RuntimeError(f"attention_gqa_range: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}")
+    kv_start, kv_len = _kv_len_arg(kv_start, nb, q.device), _kv_len_arg(kv_len, nb, q.device)
+    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    _lib.check(h.u2tok_attention_gqa_range(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
+                                           k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
+                                           float(scale), int(bool(causal)), _ptr(kv_start), _ptr(kv_len), None, 0, _stream()),
+               "u2tok_attention_gqa_range")
+    return out
+
+
+@_guarded
+def decode_attention(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int, kv_heads: int, scale: float,
+                     kv_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decode step's attention for a whole batch in one launch (u2tok_decode_attention): q (B, heads * d) rows (unit
+    stride inside a row), K / V (B, kv_heads, T, d) -- dense, or views [:, :, :T] of larger (B, kv_heads, cap, d) buffers --,
+    kv_start int32 (B,) on the GPU or None: query b attends over keys kv_start[b] .. T - 1.  d in {64, 96, 128},
+    heads / kv_heads <= 16.  -> (B, heads * d)."""
+    h = _lib.load_library()
+    for t, n in ((q, "q"), (K, "K"), (V, "V")):
+        _need(t, ELEM, n)
+    if q.dim() != 2 or q.stride(1) != 1 or K.dim() != 4 or V.shape != K.shape or V.stride() != K.stride():
+        raise RuntimeError(f"decode_attention: q {tuple(q.shape)} must be (B, heads * d) rows, K / V equal (B, kv_heads, T, d) views")
+    B, Eq = q.shape
+    d = Eq // heads
+    T = K.shape[2]
+    kvs = K.stride(1) if kv_heads > 1 else K.stride(0) if B > 1 else T * d      # elements between (batch, kv head) entries
+    if Eq % heads or heads % kv_heads or K.shape != (B, kv_heads, T, d) or K.stride(3) != 1 or K.stride(2) != d \
+            or (B > 1 and K.stride(0) != kv_heads * kvs):
+        raise RuntimeError(f"decode_attention: shapes {tuple(q.shape)}, {tuple(K.shape)} / strides {K.stride()}, heads {heads}/{kv_heads}")
+    kv_start = _kv_len_arg(kv_start, B, q.device)
+    out = torch.empty((B, Eq), dtype=elem_dtype(), device=q.device)
+    nbytes = h.u2tok_decode_attention_workspace_bytes(B, heads, kv_heads, T, d)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+    _lib.check(h.u2tok_decode_attention(_ptr(q), _ptr(K), _ptr(V), _ptr(out), B, heads, kv_heads, T, d, q.stride(0),
+                                        kvs, Eq, float(scale), _ptr(kv_start),
+                                        _ptr(ws) if nbytes else None, nbytes, _stream()), "u2tok_decode_attention")
+    return out
+
+
+@_guarded
 def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, heads: int, kv_heads: int, scale: float,
                       kv_len: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
                       d_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -16,6 +16,10 @@ on the library's MFMA GEMMs (include/u2tok.h: u2tok_gemm_bf16), the fused attent
 DECODE step (one new position per sequence, batch <= 16, a plain HF DynamicCache) as two library calls around the cache update
 (`_decode_step`: weight-streaming few-rows products, attention with the keys split over workgroups).  Everything else --
 training, CPU tensors, sliding-window layers, padded batches, other cache types -- takes the layer's original forward.
+`enable_fused_prefill(model, padded=True)` (opt-in) keeps LEFT- and RIGHT-padded batches on the fused prefill (`pad_rule`: a key
+range per sequence inside the attention kernel, u2tok_attention_gqa_range) and left-padded batches on the fused decode step (the
+batched decode attention of csrc/decode_attn.hip, u2tok_decoder_decode_post_range) -- what `generate` on a batch of prompts of
+different lengths calls.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -46,6 +50,39 @@ _DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
 # kernels the training route needs (bf16 only, no head dim 96)
 INFER_DTYPES, INFER_HEAD_DIMS = (torch.bfloat16, torch.float16), (64, 96, 128)
 TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
+
+# layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
+# would pass every parity check); the padded counts are the calls whose mask carried a key range
+stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
+
+
+def pad_rule(mask):
+    """What the fused inference routes make of a call's 2-D attention mask (next to decoder_train.train_mask_rule):
+    ("none", None, None) for no mask or all ones; ("right", None, kv_len) when every row is ones then zeros; ("left", kv_start,
+    None) when every row is zeros then ones -- at least one one per row, kv_start / kv_len int32 (B,) on the mask's device: key j
+    of sequence b is visible iff kv_start[b] <= j < kv_len[b] --; None (stock layers) for holes, an empty row, padding on both
+    sides or a mask that is not 2-D.  One host synchronisation (four flags in one transfer), none without a mask."""
+    if mask is None:
+        return "none", None, None
+    if not torch.is_tensor(mask) or mask.dim() != 2 or mask.shape[1] == 0:
+        return None
+    m = mask != 0
+    S = m.shape[1]
+    n = m.sum(1)
+    pos = torch.arange(S, device=m.device)
+    first = torch.where(m, pos, S).amin(1)          # first / last one of each row (S / -1: an empty row)
+    last = torch.where(m, pos, -1).amax(1)
+    whole = (n > 0) & (last - first + 1 == n)         # one run of ones, no holes
+    full, runs, at0, at_end = torch.stack((n.eq(S).all(), whole.all(), first.eq(0).all(), last.eq(S - 1).all())).tolist()
+    if full:
+        return "none", None, None
+    if not runs:
+        return None
+    if at0:
+        return "right", None, (last + 1).to(torch.int32)
+    if at_end:
+        return "left", first.to(torch.int32), None
+    return None
 
 
 def _pack(linears):
@@ -203,7 +240,10 @@ class _StackState:
     decode: bool = True
     train: bool = False
     prefill: bool = True
+    padded: bool = False
     mask_ok: bool = True
+    pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
+    pad_shape: tuple = None    # ... and that mask's (B, columns)
     scratch: dict = field(default_factory=dict)
 
 
@@ -265,17 +305,39 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             return "stock", None
         ok, kv_len = decoder_train.layer_mask_kv_len(kwargs.get("attention_mask"), shape[0], shape[1])
         return ("train", kv_len) if ok else ("stock", None)
-    if dtype not in INFER_DTYPES or att.head_dim not in INFER_HEAD_DIMS or not stack.mask_ok:
+    if dtype not in INFER_DTYPES or att.head_dim not in INFER_HEAD_DIMS:
         return "stock", None
     W = lo.window(layer)
     cache = kwargs.get("past_key_values")
+    kind = None         # a padded call (stack.padded): "left" / "right" when the kernels take its key ranges
+    if not stack.mask_ok:
+        # a mask with zeros: stock, unless the padded routes are on, the mask is one run of ones per row as wide as this call's
+        # keys (prefill: S columns, decode: cache + 1) and the layer has no attention window
+        pad = stack.pad if stack.padded else None
+        if pad is None or pad[0] == "none" or W is not None or stack.pad_shape[0] != shape[0]:
+            return "stock", None
+        kind = pad[0]
+        keys = shape[1] + (cache.get_seq_length(att.layer_idx) if cache is not None else 0)
+        if stack.pad_shape[1] != keys or (shape[1] == 1 and kind != "left"):
+            return "stock", None
     if shape[1] == 1:   # one new position per sequence, batch <= 16, against a plain DynamicCache
         ok = shape[0] <= 16 and stack.decode and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
+        if kind is not None and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
+            ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
     # an empty cache; a prefill longer than the window would need the band inside the attention kernel: stock layers
     if (W is None or shape[1] <= W) and (cache is None or cache.get_seq_length(att.layer_idx) == 0):
         return "prefill", W
     return "stock", None
+
+
+def _pad_range(st):
+    """(kind, kv_start, kv_len) of the call a layer routed to a fused step is part of: the stack's verdict when the mask carried a
+    range (route() has checked that it fits this call), else ("none", None, None)."""
+    stack = st.stack
+    if stack.mask_ok or not stack.padded or stack.pad is None:
+        return "none", None, None
+    return stack.pad
 
 
 def _layer_forward(self, hidden_states, *args, **kwargs):
@@ -286,8 +348,10 @@ def _layer_forward(self, hidden_states, *args, **kwargs):
     if how == "decode":
         out = _decode_step(self, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, pr)
         if out is not None:
+            stats["decode" if st.stack.mask_ok else "padded_decode"] += 1
             return out
     elif how == "prefill":
+        stats["prefill" if st.stack.mask_ok else "padded_prefill"] += 1
         return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"))
     elif how == "train":
         return _train_step(self, st.layout, x, kwargs["position_embeddings"], arg)
@@ -327,7 +391,12 @@ def _prefill_step(self, lo, x, pe, cache):
         kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
         q3 = qkv.view(B, S, -1)
         k3, v3 = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
-        ctx = ops.attention_gqa(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), causal=True)
+        kind, kv_start, kv_len = _pad_range(self._u2_prefill)
+        if kind == "none":
+            ctx = ops.attention_gqa(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), causal=True)
+        else:   # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros
+            ctx = ops.attention_gqa_range(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), kv_start=kv_start,
+                                          kv_len=kv_len, causal=True)
         h = ops.gemm(ctx.view(rows, Hq * d), att.o_proj.weight, bias=att.o_proj.bias, residual=x2)
         hn = ops.rmsnorm(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
         if bgu is None and ops.gemm_swiglu_supported(rows, E, Wgu.shape[0] // 2):
@@ -505,9 +574,15 @@ def _decode_step(self, x, pe, cache, window, pr):
             K, V = K.contiguous(), V.contiguous()
             if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
                 K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
-        _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
-                                               K.shape[2], kvs, *d["post"], out.data_ptr(), ws, nws, stream),
-                   "u2tok_decoder_decode_post")
+        kind, kv_start, _ = _pad_range(self._u2_prefill)
+        if kind == "left":   # a left-padded batch: the batched decode attention with each sequence's first visible position
+            _lib.check(h.u2tok_decoder_decode_post_range(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(),
+                                                         V.data_ptr(), K.shape[2], kvs, kv_start.data_ptr(), *d["post"],
+                                                         out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post_range")
+        else:
+            _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
+                                                   K.shape[2], kvs, *d["post"], out.data_ptr(), ws, nws, stream),
+                       "u2tok_decoder_decode_post")
     return out
 
 
@@ -538,8 +613,14 @@ def _mask_hook(module, args, kwargs):
     """Forward pre-hook of the decoder stack: the fused layers assume no padding (the path's prompts are left-aligned and the
     reference evaluates at batch 1, eval/mrg.py:74); a 2-D mask with zeros sends the whole call to the stock layers."""
     m = kwargs.get("attention_mask")
+    stack = module._u2_stack
+    if stack.padded:   # pad_rule's verdict for route(): one synchronisation, as the `.all()` below is
+        pad = pad_rule(m)
+        stack.pad, stack.pad_shape = pad, (tuple(m.shape) if pad is not None and m is not None else None)
+        stack.mask_ok = pad is not None and pad[0] == "none"
+        return None
     ok = m is None or (torch.is_tensor(m) and m.dim() == 2 and bool(m.to(torch.bool).all()))
-    module._u2_stack.mask_ok = ok
+    stack.mask_ok = ok
     return None
 
 
@@ -574,14 +655,18 @@ def _layer_protocol_ok(layer, base=None) -> bool:
     return ok
 
 
-def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True) -> int:
+def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
+                         padded: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
     activation, partial rotary, a head dim outside 64 / 96 / 128) -- is skipped instead of refused.
     train=True (opt-in): a patched Llama / Qwen3 layer called with grad enabled takes the training route of decoder_train.py
     (forward and backward on the library's kernels) when its conditions hold.  prefill=False: no fused prefill / decode (the
-    layers are patched for the training route only).  The three switches are set anew by every call.
+    layers are patched for the training route only).  padded=True (opt-in): a batch whose 2-D attention mask is left- or
+    right-padded (`pad_rule`) keeps the fused prefill, a left-padded one the fused decode step too (`generate` on a batch of
+    prompts of different lengths); off, any mask with a zero sends the call to the stock layers.  The four switches are set anew
+    by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -601,7 +686,8 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     stack = base.__dict__.get("_u2_stack")
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
-    stack.decode, stack.train, stack.prefill = bool(decode), bool(train), bool(prefill)
+    stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
+    stack.pad = stack.pad_shape = None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
