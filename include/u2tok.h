@@ -456,6 +456,19 @@ int u2tok_attention_gqa_range(const void* q, const void* k, const void* v, void*
                               int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                               int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
                               const int32_t* kv_len, float* lse, int64_t lse_ld, u2tok_stream_t stream);
+/* The same reading K / V where a KV cache keeps them, and with an attention window (the decoder's continued prefill: new positions
+ * against a filled cache, a prefill longer than the window of a sliding-window layer).  k_hs / v_hs: elements between the kv heads of
+ * one sequence -- d for the column-packed (nb, Skv, Hkv * d) view of the calls above; for the view [:, :, :Skv] of a cache buffer
+ * (B, Hkv, capacity, d): ldk = d, k_hs = capacity * d, k_bs = Hkv * capacity * d (multiples of 8; nothing is copied).  window = W > 0
+ * (causal only): key j is visible to query i iff i + Skv - Sq - W < j <= i + Skv - Sq -- W keys, the query's own included, HF's
+ * sliding-window rule --, intersected with kv_start[b] <= j < kv_len[b] when those are given; 0: no window.  A row that sees no key
+ * gets exact zeros (lse 0).  d = 64, 96 or 128.  k_hs = v_hs = d and window = 0: exactly u2tok_attention_gqa_range (all range
+ * pointers NULL as well: exactly u2tok_attention_gqa). */
+int u2tok_attention_gqa_band(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                             int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                             int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
+                             const int32_t* kv_len, float* lse, int64_t lse_ld, int64_t k_hs, int64_t v_hs, int32_t window,
+                             u2tok_stream_t stream);
 /* Its backward (causal, Sq = Skv = S, d = 64 or 128): dq, dk, dv from q, k, v, out, d_out and (optional) lse of
  * u2tok_attention_gqa_ex, honouring kv_len.  Layout of u2tok_flash_attention_d64_bwd with Hq query heads (q / dq: head h at
  * column h*d) and Hkv kv heads (k, v / dk, dv: head h at column h*d of their pointers): with q | k | v column views of one

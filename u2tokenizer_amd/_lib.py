@@ -149,6 +149,8 @@ SIGNATURES = {
                                       _i64, _i64, _f32, _i32, _vp, _vp, _i64, _vp]),
     "u2tok_attention_gqa_range": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "u2tok_attention_gqa_band": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _f32, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_attention_gqa_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "u2tok_attention_gqa_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
                                        _i32, _i32, _f32, _vp, _vp, _i64, _vp, _sz, _vp]),

@@ -426,6 +426,14 @@ int u2tok_attention_gqa_range(const void* q, const void* k, const void* v, void*
   return attention_gqa_range(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
                              scale, causal, kv_start, kv_len, lse, lse_ld, ST(stream));
 }
+int u2tok_attention_gqa_band(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
+                             int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
+                             int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
+                             const int32_t* kv_len, float* lse, int64_t lse_ld, int64_t k_hs, int64_t v_hs, int32_t window,
+                             u2tok_stream_t stream) {
+  return attention_gqa_band(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
+                            k_hs, v_hs, window, scale, causal, kv_start, kv_len, lse, lse_ld, ST(stream));
+}
 size_t u2tok_attention_gqa_bwd_workspace_bytes(int32_t nb, int32_t S, int32_t Hq) {
   return attention_gqa_bwd_workspace_bytes(nb, S, Hq);
 }

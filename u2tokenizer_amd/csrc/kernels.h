@@ -260,6 +260,12 @@ int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_
                         int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                         int64_t o_bs, float scale, int causal, const int* kv_start, const int* kv_len, float* lse, int64_t lse_ld,
                         hipStream_t stream);
+// attention_gqa_band: attention_gqa_range with the kv heads k_hs / v_hs elements apart (a KV cache's (B, Hkv, capacity, d) buffers read
+// in place) and the lower edge of an attention window (key j visible to query i only if j > i + Skv - Sq - window; 0: none).
+int attention_gqa_band(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
+                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
+                       int64_t k_hs, int64_t v_hs, int window, float scale, int causal, const int* kv_start, const int* kv_len,
+                       float* lse, int64_t lse_ld, hipStream_t stream);
 size_t attention_gqa_bwd_workspace_bytes(int nb, int S, int Hq);
 int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
                       const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,

@@ -62,6 +62,9 @@ struct TokAttnArgs {
   const int* kv_start;  // optional (nb): ... and only if j >= kv_start[b] (left padding); a row that sees no key writes zeros
   float* lse;         // optional (nb * H, lse_ld): log2 sum_j exp2(s_ij scale log2 e) of each query row, for the backward
   int64_t lse_ld;
+  // tok_attn_kernel<DH, true, true> only (u2tok_attention_gqa_band, the decoder's continued prefill):
+  int64_t k_hs, v_hs;  // elements between the kv heads of one sequence (DH: the column-packed view; cap * DH: a KV cache's (B, Hkv, cap, DH))
+  int window;          // W > 0 (causal): key j is visible to query i only if j > i + (Skv - Sq) - W; 0: no lower edge
 };
 
 constexpr float TOKATTN_RESCALE_THR = 8.0f;
@@ -78,7 +81,11 @@ __device__ __forceinline__ int t96_pos(int row, int L) { return L ^ ((row >> 1) 
 
 typedef short ta_v4s_t __attribute__((ext_vector_type(4)));
 
-template <int DH, bool EX = false>  // EX: per-sequence key lengths and row statistics (TokAttnArgs::kv_len / lse)
+// EX: per-sequence key lengths and row statistics (TokAttnArgs::kv_len / lse).  BAND (with EX): kv head strides and the lower
+// edge of a sliding window (k_hs / v_hs / window).  A row of a band can meet a wholly masked tile BEFORE its first visible key (the
+// band of the block's last row starts 63 keys after that of its first): its running max stays -inf through that tile, which is
+// the state EX already keeps for a row that has seen no key (alpha = 1, exponent base 0: every probability exp2(-inf) = 0).
+template <int DH, bool EX = false, bool BAND = false>
 __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const TokAttnArgs a) {
   constexpr int BK = DH <= 128 ? 64 : 32;  // keys per tile (narrow heads: twice the keys per barrier / DMA wait / softmax step)
   constexpr int NKB = BK / 16;        // 16-key blocks of S^T per tile
@@ -133,12 +140,27 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
       kt0_ = max(kt0_, kvs / BK);
     }
   }
+  int win = 0;  // (BAND) keys at or below i + c_off - win are invisible to query i: tiles wholly below the band of the block's FIRST
+                // row are skipped, the partial ones masked per row
+  if constexpr (BAND) {
+    static_assert(EX, "the band rides on the range kernel");
+    if (a.causal && a.window > 0) {
+      win = a.window;
+      kt0_ = max(kt0_, max(0, q0 + c_off - win + 1) / BK);
+    }
+  }
   const int kt0 = kt0_, kt1 = kt1_;
   const int kbeg = kt0 * BK;
 
   const int hkv = h / a.kv_group;
-  const bf16_t* kb_ = a.k + (int64_t)b * a.k_bs + hkv * DH;
-  const bf16_t* vb_ = a.v + (int64_t)b * a.v_bs + hkv * DH;
+  const bf16_t *kb_, *vb_;
+  if constexpr (BAND) {  // (a KV cache keeps a head's T rows together: the next head is capacity * DH elements on)
+    kb_ = a.k + (int64_t)b * a.k_bs + (int64_t)hkv * a.k_hs;
+    vb_ = a.v + (int64_t)b * a.v_bs + (int64_t)hkv * a.v_hs;
+  } else {
+    kb_ = a.k + (int64_t)b * a.k_bs + hkv * DH;
+    vb_ = a.v + (int64_t)b * a.v_bs + hkv * DH;
+  }
 
   // ---- Q fragments (B operand): Q[q][32 ks + 8 g .. + 7]
   const int qrow = q0 + 16 * w + l15;
@@ -282,6 +304,13 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
 #pragma unroll
         for (int i = 0; i < NX; ++i)
           if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) < kvs) x[i] = -INFINITY;
+      }
+    }
+    if constexpr (BAND) {
+      if (win > 0 && kt * BK <= q0 + 16 * w + 15 + c_off - win) {  // (wave-uniform) the tile starts below the band of this wave's last row
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+          if (kt * BK + (i >> 2) * 16 + 4 * g + (i & 3) <= qrow + c_off - win) x[i] = -INFINITY;
       }
     }
     float mt = x[0];
@@ -831,6 +860,7 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
   a.kv_group = H / Hkv;
   a.causal = causal ? 1 : 0;
   a.kv_len = nullptr; a.kv_start = nullptr; a.lse = nullptr; a.lse_ld = 0;
+  a.k_hs = a.v_hs = d; a.window = 0;
   int ns = force_splits > 0 ? std::min(force_splits, ntile) : tok_attn_pick_splits(nb, H, Sq, Skv, d, ws ? ws_bytes : 0);
   if (causal) ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
   const size_t per = (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
@@ -916,6 +946,7 @@ int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_
   a.kv_group = H / Hkv;
   a.causal = causal ? 1 : 0;
   a.kv_len = kv_len; a.kv_start = kv_start; a.lse = lse; a.lse_ld = lse_ld;
+  a.k_hs = a.v_hs = d; a.window = 0;
   a.ns = 1;
   a.tps = (int)cdiv(Skv, tok_attn_bk(d));
   a.opart = nullptr; a.ml = nullptr;
@@ -934,6 +965,54 @@ int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_
   else if (d == 96) U2_TAX(96);
   else U2_TAX(64);
 #undef U2_TAX
+  return launch_status();
+}
+
+// ... and with the kv heads of a sequence k_hs / v_hs elements apart (d: the column-packed view of the calls above; capacity * d: the
+// views [:, :, :Skv] of a KV cache's (B, Hkv, capacity, d) buffers, read where they lie with ldk = d) and an attention window: with
+// window = W > 0 (causal only) key j is visible to query i iff i + Skv - Sq - W < j <= i + Skv - Sq -- W keys, the query's own
+// included -- intersected with the key range.  Tiles wholly below the band of a query block are skipped.  d = 64 / 96 / 128.
+// k_hs = v_hs = d and window = 0: exactly attention_gqa_range (and, without a range, attention_gqa).
+int attention_gqa_band(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
+                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
+                       int64_t k_hs, int64_t v_hs, int window, float scale, int causal, const int* kv_start, const int* kv_len,
+                       float* lse, int64_t lse_ld, hipStream_t stream) {
+  if (k_hs == d && v_hs == d && window == 0)
+    return attention_gqa_range(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, causal, kv_start,
+                               kv_len, lse, lse_ld, stream);
+  if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
+  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)kv_start & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq))
+    return U2_ERR_ARG;
+  if ((d != 64 && d != 96 && d != 128) || window < 0 || (window > 0 && !causal) || k_hs <= 0 || v_hs <= 0 || ((k_hs | v_hs) & 7))
+    return U2_ERR_ARG;
+  if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
+    return U2_ERR_ARG;
+  TokAttnArgs a;
+  a.q = q; a.k = k; a.v = v; a.out = out;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
+  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
+  a.scale_log2e = scale * 1.44269504088896340736f;
+  a.rel_bias = nullptr; a.max_len = 0;
+  a.kv_group = H / Hkv;
+  a.causal = causal ? 1 : 0;
+  a.kv_len = kv_len; a.kv_start = kv_start; a.lse = lse; a.lse_ld = lse_ld;
+  a.k_hs = k_hs; a.v_hs = v_hs; a.window = window;
+  a.ns = 1;
+  a.tps = (int)cdiv(Skv, tok_attn_bk(d));
+  a.opart = nullptr; a.ml = nullptr;
+  const int64_t grid = (int64_t)nb * H * a.nqb;
+  if (grid > 0x7fffffff) return U2_ERR_ARG;
+  ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
+               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));
+#define U2_TAB(D_)                                                                                                     \
+  do {                                                                                                                 \
+    constexpr size_t smem_ = 4 * 64 * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                                               \
+    hipLaunchKernelGGL((tok_attn_kernel<D_, true, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);          \
+  } while (0)
+  if (d == 128) U2_TAB(128);
+  else if (d == 96) U2_TAB(96);
+  else U2_TAB(64);
+#undef U2_TAB
   return launch_status();
 }
 

@@ -61,8 +61,9 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         """Patch the decoder layers for the HIP routes of prefill.py, once per grad mode, when the decoder sits on the GPU in a
         type that mode's route computes: without grad `config.u2_fused_prefill` (default True) asks for the prefill and decode
         steps (bf16, or fp16 on the f16 build), with grad `config.u2_fused_decoder_training` (default False)
-        for the training route of decoder_train.py (bf16).  Both switches, and `config.u2_fused_padded_batches` (default False:
-        padded batches on the no-grad routes), are passed on as the config has them."""
+        for the training route of decoder_train.py (bf16).  Both switches, `config.u2_fused_padded_batches` (default False:
+        padded batches on the no-grad routes) and `config.u2_fused_continued_prefill` (default False: new positions against a
+        filled cache, prefills past the attention window), are passed on as the config has them."""
         grad = torch.is_grad_enabled()
         train = bool(getattr(self.config, "u2_fused_decoder_training", False))
         prefill = bool(getattr(self.config, "u2_fused_prefill", True))
@@ -76,6 +77,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         if p.dtype in (TRAIN_DTYPES if grad else INFER_DTYPES):
             # (`config.u2_fused_padded_batches`, default False: padded batches on the fused prefill / decode steps)
             padded = {"padded": True} if bool(getattr(self.config, "u2_fused_padded_batches", False)) else {}
+            if bool(getattr(self.config, "u2_fused_continued_prefill", False)):
+                padded["continued"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 

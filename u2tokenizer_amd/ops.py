@@ -925,6 +925,53 @@ def attention_gqa_range(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads
 
 
 @_guarded
+def attention_gqa_band(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
+                       window: Optional[int] = None, kv_start: Optional[torch.Tensor] = None,
+                       kv_len: Optional[torch.Tensor] = None, causal: bool = True) -> torch.Tensor:
+    """attention_gqa_range reading K / V where a KV cache keeps them, with an attention window (u2tok_attention_gqa_band).
+    k / v: (nb, Skv, kv_heads * d) views as there, or 4-D (B, kv_heads, T, d) cache views -- dense, or [:, :, :T] of larger
+    (B, kv_heads, cap, d) buffers: stride(3) == 1, stride(2) == d, stride(0) == kv_heads * stride(1), equal strides for both;
+    nothing is copied.  window = W (causal only; None / 0: none): key j is visible to query i iff
+    i + Skv - Sq - W < j <= i + Skv - Sq -- W keys, the query's own included --, intersected with the key range.  A query row that
+    sees no key gets zeros.  d in {64, 96, 128} for a window or a 4-D view.  No window, 3-D views: the kernel, and the bits, of
+    attention_gqa_range (no range either: of attention_gqa)."""
+    h = _lib.load_library()
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _need(t, ELEM, n)
+    if q.dim() != 3 or q.stride(2) != 1:
+        raise RuntimeError("attention_gqa_band: q must be (nb, S, H * d) with a contiguous last dim")
+    nb, Sq, Eq = q.shape
+    d = Eq // heads
+    if k.dim() == 4:
+        if v.shape != k.shape or v.stride() != k.stride() or k.stride(3) != 1 or k.stride(2) != d \
+                or k.stride(0) != kv_heads * k.stride(1):
+            raise RuntimeError(f"attention_gqa_band: k / v {tuple(k.shape)} strides {k.stride()}, {v.stride()} must be equal "
+                               "(B, kv_heads, T, d) views of (B, kv_heads, cap, d) buffers")
+        Skv = k.shape[2]
+        ok = k.shape == (nb, kv_heads, Skv, d)
+        ldk, kbs, khs = d, k.stride(0), k.stride(1)
+        ldv, vbs = ldk, kbs
+    else:
+        for t, n in ((k, "k"), (v, "v")):
+            if t.dim() != 3 or t.stride(2) != 1:
+                raise RuntimeError(f"attention_gqa_band: {n} must be (nb, S, H * d) with a contiguous last dim or a 4-D cache view")
+        Skv = k.shape[1]
+        ok = k.shape == (nb, Skv, kv_heads * d) and v.shape == k.shape
+        ldk, kbs, khs = k.stride(1), k.stride(0), d
+        ldv, vbs = v.stride(1), v.stride(0)
+    W = int(window or 0)
+    if Eq % heads or not ok or heads % kv_heads or W < 0 or (W and not causal):
+        raise RuntimeError(f"attention_gqa_band: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}, "
+                           f"window {window}")
+    kv_start, kv_len = _kv_len_arg(kv_start, nb, q.device), _kv_len_arg(kv_len, nb, q.device)
+    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    _lib.check(h.u2tok_attention_gqa_band(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1), ldk, ldv,
+                                          Eq, q.stride(0), kbs, vbs, Sq * Eq, float(scale), int(bool(causal)), _ptr(kv_start),
+                                          _ptr(kv_len), None, 0, khs, khs, W, _stream()), "u2tok_attention_gqa_band")
+    return out
+
+
+@_guarded
 def decode_attention(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: int, kv_heads: int, scale: float,
                      kv_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The decode step's attention for a whole batch in one launch (u2tok_decode_attention): q (B, heads * d) rows (unit

@@ -20,13 +20,20 @@ training, CPU tensors, sliding-window layers, padded batches, other cache types 
 range per sequence inside the attention kernel, u2tok_attention_gqa_range) and left-padded batches on the fused decode step (the
 batched decode attention of csrc/decode_attn.hip, u2tok_decoder_decode_post_range) -- what `generate` on a batch of prompts of
 different lengths calls.
+`enable_fused_prefill(model, continued=True)` (opt-in) keeps two more inference calls on the HIP layers, both through one extension
+of the attention kernel (u2tok_attention_gqa_band: K / V read in the cache's own (B, H_kv, capacity, d) layout, the lower edge of
+an attention window per query row): more than one new position against a cache that already holds keys (a second turn, a prompt
+fed in chunks, `generate(..., past_key_values=cache)`, the verification step of assisted decoding; `_extend_kv`) and a prefill
+longer than the window of a sliding-window layer.  Taken: no cache or a plain DynamicCache of DynamicLayer / append-in-place /
+DynamicSlidingWindowLayer layers, no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers
+without a window; stock: a right-padded continuation, holes, window + padding, offloaded / static / quantized caches.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
 Phi-3 layers (`Phi3Attention.qkv_proj`, `Phi3MLP.gate_up_proj`: gate rows first, then up) already hold that packed layout and
 are used as they are (`_PackedLayout`).  Their configs carry `sliding_window` = W (every Phi-3-4k build: 2047; query i sees
-keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a longer prefill takes the stock layers, and a
-decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
+keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a longer prefill takes the stock layers (with
+continued=True: the band inside the attention kernel), and a decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
 DynamicSlidingWindowLayer that `generate` builds for such a config.
 
 `route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
@@ -54,6 +61,9 @@ TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
 # would pass every parity check); the padded counts are the calls whose mask carried a key range
 stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
+# ... and of the continued prefill (new positions against a filled cache, or a prefill past the window), in a dict of its own:
+# `stats` keeps exactly its four routes
+extend_stats = {"extend": 0, "padded_extend": 0}
 
 
 def pad_rule(mask):
@@ -241,6 +251,7 @@ class _StackState:
     train: bool = False
     prefill: bool = True
     padded: bool = False
+    continued: bool = False
     mask_ok: bool = True
     pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
     pad_shape: tuple = None    # ... and that mask's (B, columns)
@@ -281,9 +292,10 @@ def _rotary_rows(pe, B: int, S: int, d: int, elem=None):
 
 def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     """The forward a call of the patched `layer` takes, from the input's shape, dtype and device flag (no tensor needed):
-    ("train", kv_len) or stock with grad enabled, else ("decode", W), ("prefill", W) or stock; W = the attention window or
-    None.  Masks: decode and prefill read the stack pre-hook's verdict on the call's 2-D mask, the training route the layer's
-    own 4-D mask (layer_mask_kv_len: cached on the tensor, so a checkpoint recompute sees its own forward's).  `pr`: the
+    ("train", kv_len) or stock with grad enabled, else ("decode", W), ("prefill", W), ("extend", W) or stock; W = the attention
+    window or None.  "extend" (stack.continued, opt-in): more than one position that the plain prefill refuses -- the layer's
+    cache already holds positions, or the call is longer than the window -- with a cache `_extend_layer_ok` takes.  Masks: decode,
+    prefill and extend read the stack pre-hook's verdict on the call's 2-D mask, the training route the layer's own 4-D mask (layer_mask_kv_len: cached on the tensor, so a checkpoint recompute sees its own forward's).  `pr`: the
     layout's projections (read once per call)."""
     st = layer._u2_prefill
     stack, lo, att = st.stack, st.layout, layer.self_attn
@@ -320,14 +332,19 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
         keys = shape[1] + (cache.get_seq_length(att.layer_idx) if cache is not None else 0)
         if stack.pad_shape[1] != keys or (shape[1] == 1 and kind != "left"):
             return "stock", None
+        if keys != shape[1] and kind != "left":   # (a right-padded continuation: the new keys would not follow the old ones)
+            return "stock", None
     if shape[1] == 1:   # one new position per sequence, batch <= 16, against a plain DynamicCache
         ok = shape[0] <= 16 and stack.decode and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
         if kind is not None and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
             ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
-    # an empty cache; a prefill longer than the window would need the band inside the attention kernel: stock layers
+    # an empty cache and no more positions than the window: the plain causal prefill
     if (W is None or shape[1] <= W) and (cache is None or cache.get_seq_length(att.layer_idx) == 0):
         return "prefill", W
+    # continued=True: the band and the cache's layout inside the attention kernel (u2tok_attention_gqa_band)
+    if stack.continued and (cache is None or _extend_layer_ok(cache, att.layer_idx, W is not None)):
+        return "extend", W
     return "stock", None
 
 
@@ -353,6 +370,9 @@ def _layer_forward(self, hidden_states, *args, **kwargs):
     elif how == "prefill":
         stats["prefill" if st.stack.mask_ok else "padded_prefill"] += 1
         return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"))
+    elif how == "extend":
+        extend_stats["extend" if st.stack.mask_ok else "padded_extend"] += 1
+        return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, True)
     elif how == "train":
         return _train_step(self, st.layout, x, kwargs["position_embeddings"], arg)
     return st.orig(hidden_states, *args, **kwargs)
@@ -367,7 +387,9 @@ def _train_step(layer, lo, x, pe, kv_len):
         return decoder_train.layer_forward_train(layer, lo, _rows(x), cos.detach(), sin.detach(), B, S, kv_len)
 
 
-def _prefill_step(self, lo, x, pe, cache):
+def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
+    """The prefill step of a layer.  extend (the "extend" route): the keys come from the cache -- `_extend_kv` --, or, with no
+    position cached yet, the call is longer than `window` and its own keys get the band."""
     B, S, E = x.shape
     rows = B * S
     att = self.self_attn
@@ -382,21 +404,27 @@ def _prefill_step(self, lo, x, pe, cache):
         xn = ops.rmsnorm(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
         qkv = ops.gemm(xn, Wqkv, bias=bqkv)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
-        # keys / values in the cache's own (B, H_kv, S, d) layout: straight into an append-in-place layer of a plain DynamicCache
-        # (room for the decode steps behind them), else as dense tensors for the cache's own `update`
-        lay = _prefill_append_layer(cache, att.layer_idx, B, Hkv, S, d, x) if cache is not None else None
-        r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
-                             qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
-                             kv_out=None if lay is None else (lay._kb, lay._vb))
-        kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
         q3 = qkv.view(B, S, -1)
-        k3, v3 = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
         kind, kv_start, kv_len = _pad_range(self._u2_prefill)
-        if kind == "none":
-            ctx = ops.attention_gqa(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), causal=True)
-        else:   # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros
-            ctx = ops.attention_gqa_range(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), kv_start=kv_start,
-                                          kv_len=kv_len, causal=True)
+        lay = kc = vc = commit = None
+        if extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0:
+            ctx, commit = _extend_kv(att, cache, qkv, qn, kn, cos, sin, B, S, Hq, Hkv, d, window, kv_start)
+        else:
+            # keys / values in the cache's own (B, H_kv, S, d) layout: straight into an append-in-place layer of a plain
+            # DynamicCache (room for the decode steps behind them), else as dense tensors for the cache's own `update`
+            lay = _prefill_append_layer(cache, att.layer_idx, B, Hkv, S, d, x) if cache is not None else None
+            r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
+                                 qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
+                                 kv_out=None if lay is None else (lay._kb, lay._vb))
+            kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
+            k3, v3 = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
+            if extend:   # longer than the window: query i sees its own key and the window - 1 before it
+                ctx = ops.attention_gqa_band(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), window=window, causal=True)
+            elif kind == "none":
+                ctx = ops.attention_gqa(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), causal=True)
+            else:   # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros
+                ctx = ops.attention_gqa_range(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), kv_start=kv_start,
+                                              kv_len=kv_len, causal=True)
         h = ops.gemm(ctx.view(rows, Hq * d), att.o_proj.weight, bias=att.o_proj.bias, residual=x2)
         hn = ops.rmsnorm(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
         if bgu is None and ops.gemm_swiglu_supported(rows, E, Wgu.shape[0] // 2):
@@ -404,11 +432,42 @@ def _prefill_step(self, lo, x, pe, cache):
         else:
             act = ops.swiglu(ops.gemm(hn, Wgu, bias=bgu))
         out = ops.gemm(act, self.mlp.down_proj.weight, bias=self.mlp.down_proj.bias, residual=h)
-        if lay is not None:
+        if commit is not None:
+            commit()
+        elif lay is not None:
             lay._commit(S)
         elif cache is not None:
             cache.update(kc, vc, att.layer_idx)
     return out.view(B, S, E)
+
+
+def _extend_kv(att, cache, qkv, qn, kn, cos, sin, B, S, Hq, Hkv, d, window, kv_start):
+    """Rotary embedding and attention of S new positions against a cache layer that holds T0 > 0: -> (ctx, commit).  An
+    append-in-place layer: the new keys / values land behind the old ones in its buffers and the attention reads the views
+    [:, :, :T0 + S] (a window layer: the last min(T0 + S, S + W - 1) positions) where they lie; `commit` (called once every
+    launch of the layer is enqueued, as the prefill does) makes them the layer's.  Every other layer `route` takes: dense new
+    keys / values through the cache's own `update`, attention over what it returns -- a DynamicSlidingWindowLayer its kept
+    W - 1 positions and the new S; the kernel's masks are relative to the last key, so that is the operand as it is.
+    kv_start: the first visible key of each sequence of a left-padded batch (layers without a window only), or None."""
+    lay = cache.layers[att.layer_idx]
+    eps = qn.variance_epsilon if qn is not None else 1e-6
+    wq, wk = None if qn is None else qn.weight, None if kn is None else kn.weight
+    q3 = qkv.view(B, S, -1)[..., :Hq * d]
+    if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:
+        T0 = lay._room(S, lay.keys)
+        ops.qk_norm_rope(qkv, wq, wk, cos, sin, Hq, Hkv, d, eps, kv_cache_seq=S, kv_out=(lay._kb, lay._vb), kv_pos=T0)
+        T1 = T0 + S
+        lo_ = 0 if window is None else max(0, T1 - (S + window - 1))
+        K, V = lay._kb[:, :, lo_:T1], lay._vb[:, :, lo_:T1]
+        commit = lambda: lay._commit(T1)
+    else:
+        _, kc, vc = ops.qk_norm_rope(qkv, wq, wk, cos, sin, Hq, Hkv, d, eps, kv_cache_seq=S)
+        K, V = cache.update(kc, vc, att.layer_idx)
+        if K.stride() != V.stride() or K.stride(3) != 1 or K.stride(2) != d or K.stride(0) != Hkv * K.stride(1):
+            K, V = K.contiguous(), V.contiguous()
+        commit = lambda: None
+    ctx = ops.attention_gqa_band(q3, K, V, Hq, Hkv, float(att.scaling), window=window, kv_start=kv_start, causal=True)
+    return ctx, commit
 
 
 _APPEND_LAYER = None
@@ -477,6 +536,19 @@ def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False):
     lay = layers[layer_idx]
     kinds = (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
     return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
+
+
+def _extend_layer_ok(cache, layer_idx: int, sliding: bool) -> bool:
+    """Whether the continued prefill takes this layer of `cache`: a plain HF DynamicCache (no offloading) whose layer is a
+    DynamicLayer, the append-in-place layer or -- sliding=True: a layer with an attention window -- a DynamicSlidingWindowLayer,
+    empty or filled; a layer the cache would still create lazily as a DynamicLayer counts.  Static, quantized and offloaded
+    caches and other layer classes: no."""
+    layers = _plain_layers(cache)
+    if layers is None:
+        return False
+    if layer_idx >= len(layers):
+        return getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER
+    return type(layers[layer_idx]) in (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
 
 
 def _decode_state(self, B: int, device, pr):
@@ -656,7 +728,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
-                         padded: bool = False) -> int:
+                         padded: bool = False, continued: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -665,8 +737,14 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     (forward and backward on the library's kernels) when its conditions hold.  prefill=False: no fused prefill / decode (the
     layers are patched for the training route only).  padded=True (opt-in): a batch whose 2-D attention mask is left- or
     right-padded (`pad_rule`) keeps the fused prefill, a left-padded one the fused decode step too (`generate` on a batch of
-    prompts of different lengths); off, any mask with a zero sends the call to the stock layers.  The four switches are set anew
-    by every call.
+    prompts of different lengths); off, any mask with a zero sends the call to the stock layers.  continued=True (opt-in): more
+    than one new position against a cache that already holds positions (the second turn of a conversation, a prompt fed in
+    chunks, `generate(..., past_key_values=cache)`, the verification step of assisted decoding) and a prefill longer than the
+    window of a sliding-window layer stay on the HIP layers (`_extend_kv`, u2tok_attention_gqa_band) -- for no cache or a plain
+    DynamicCache of DynamicLayer / append-in-place / DynamicSlidingWindowLayer layers, head dims 64 / 96 / 128, any batch size,
+    no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers without a window; a
+    right-padded continuation, holes, window + padding and every other cache take the stock layers.  The five switches are set
+    anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -687,6 +765,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
     stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
+    stack.continued = bool(continued)
     stack.pad = stack.pad_shape = None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
