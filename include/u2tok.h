@@ -369,6 +369,35 @@ int u2tok_decoder_decode_post_range(const u2tok_decode_config* cfg, const void* 
                                     int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo, const void* bo,
                                     const void* w_post_norm, const void* Wgu, const void* bgu, const void* Wdown, const void* bdown,
                                     void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- the decode step on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
+ * attention and the KV cache stay in the element type).  A product is exactly x . (scale[n] * e4m3(W8[n][:])) with fp32
+ * accumulation -- the codes are widened to the element type in registers, where every e4m3 value is exact --, so all the loss is
+ * the quantiser's (u2tokenizer_amd/ops.py: quantize_rows_fp8).  The weight bytes of a step, which bound it, are halved.
+ * u2tok_gemm_rows_w8: C (M <= 16, N) = epilogue(scale[n] * sum_k A[m][k] e4m3(W8[n][k])); W8 (N, K) bytes, ldw bytes between rows;
+ * flags of u2tok_gemm_bf16: 1 (bias[n]), 8 (+ R, ldr), 16 (fp32 C), or 512 ALONE (W8 = gate rows | up rows, N = 2 I, I % 8 == 0,
+ * C (M, I) = bf16(silu(bf16(gate))) * bf16(up): the values of the product followed by u2tok_swiglu_bf16, bit for bit).
+ * K % 64 == 0, lda % 8 == 0, ldw % 16 == 0, A and W8 16-byte aligned, scale non-null; U2TOK_ERR_ARG otherwise, nothing launched.
+ * Bit-repeatable (partial sums are added in a fixed order). */
+int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
+                       int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
+                       u2tok_stream_t stream);
+/* u2tok_decoder_decode_pre / _post / _post_range with the four weights as e4m3 codes (contiguous (N, K) bytes) and a scale
+ * array behind each: same config, workspace, attention, norms, rotary and cache arguments.  E, Hq * D and I must be multiples
+ * of 64, the weights 16-byte aligned and every scale non-null: U2TOK_ERR_ARG otherwise, before anything is launched. */
+int u2tok_decoder_decode_pre_w8(const u2tok_decode_config* cfg, const void* x, const void* w_in_norm, const void* Wqkv8,
+                                const float* scale_qkv, const void* bqkv, const void* wq_norm, const void* wk_norm, const void* cos,
+                                const void* sin, int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache,
+                                int64_t kv_stride, int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+int u2tok_decoder_decode_post_w8(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
+                                 int32_t T, int64_t kv_stride, const void* Wo8, const float* scale_o, const void* bo,
+                                 const void* w_post_norm, const void* Wgu8, const float* scale_gu, const void* bgu, const void* Wdown8,
+                                 const float* scale_down, const void* bdown, void* out, void* workspace, size_t workspace_bytes,
+                                 u2tok_stream_t stream);
+int u2tok_decoder_decode_post_range_w8(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
+                                       int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo8, const float* scale_o,
+                                       const void* bo, const void* w_post_norm, const void* Wgu8, const float* scale_gu,
+                                       const void* bgu, const void* Wdown8, const float* scale_down, const void* bdown, void* out,
+                                       void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 /* Batched decode attention: out[b] = softmax(q[b] K[b]^T scale over keys kv_start[b] <= j < T) V[b] for B sequences of ONE query
  * row each.  q / out: (B, Hq * D) rows, ldq / ldo elements apart (head h at column h * D); K / V: (B, Hkv, T, D), kv_stride
  * elements between (batch, kv head) entries (0: dense, T * D) -- an append-in-place buffer or the dense cache; D in {64, 96, 128},

@@ -136,6 +136,13 @@ SIGNATURES = {
                                          _vp]),
     "u2tok_decoder_decode_post_range": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _sz, _vp]),
+    "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "u2tok_decoder_decode_pre_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32,
+                                           _vp, _sz, _vp]),
+    "u2tok_decoder_decode_post_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _sz, _vp]),
+    "u2tok_decoder_decode_post_range_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "u2tok_decode_attention": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),
     "u2tok_rope_apply": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),

@@ -199,14 +199,33 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // step `generate` repeats up to 768 times per report is bound by the host's launch rate when every kernel is its own Python
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
-static int dec_linear(const bf16_t* x, int64_t ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int64_t ldy, int rows, int in,
-                      int out, const bf16_t* R, int64_t ldr, hipStream_t st) {
+// One projection of the step: the element type's product through the plan, or -- `sc`: a scale per weight row, w = e4m3 codes
+// (the _w8 entry points) -- the few-rows product on 1-byte weights (gemm_w8.hip).  pair: w = gate | up, y (rows, out / 2).
+static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const bf16_t* b, bf16_t* y, int64_t ldy, int rows,
+                      int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
+  if (sc) {
+    RowsW8Args a;
+    a.A = x; a.W = reinterpret_cast<const uint8_t*>(w); a.scale = sc; a.C = y; a.bias = b; a.R = R;
+    a.M = rows; a.N = out; a.K = in;
+    a.lda = ldx; a.ldw = in; a.ldc = ldy; a.ldr = ldr;
+    a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
+    return gemm_rows_w8(a, st);
+  }
   GemmDesc g;
-  g.A = x; g.B = w; g.C = y; g.bias = b; g.R = R;
+  g.A = x; g.B = reinterpret_cast<const bf16_t*>(w); g.C = y; g.bias = b; g.R = R;
   g.M = rows; g.N = out; g.K = in;
   g.lda = ldx; g.ldb = in; g.ldc = ldy; g.ldr = ldr;
-  g.flags = (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
+  g.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
   return gemm_bf16(g, st);
+}
+
+// What the e4m3 products ask of a step before anything is launched: a scale per product, K % 64 == 0 for all four, 16-byte
+// aligned weights, 4-byte aligned scales.
+static bool w8_step_ok(const DecodeCfg& c, const void* const* w, const float* const* sc, int n) {
+  if ((c.E & 63) || ((c.Hq * c.D) & 63) || (c.I & 63)) return false;
+  for (int i = 0; i < n; ++i)
+    if (!w[i] || !sc[i] || ((uintptr_t)w[i] & 15) || ((uintptr_t)sc[i] & 3)) return false;
+  return true;
 }
 
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
@@ -220,30 +239,55 @@ size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
 
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
 // (B, Hkv, 1, D) receive the new cache entries
-int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const bf16_t* Wqkv, const bf16_t* bqkv,
-                       const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
-                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
+static int decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const void* Wqkv, const float* sqkv,
+                      const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
+                      int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
+                      hipStream_t st) {
   if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !w_in_norm || !Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
   int e = rmsnorm_bf16(x, w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  e = dec_linear(xn, c.E, Wqkv, bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, st);
+  e = dec_linear(xn, c.E, Wqkv, sqkv, bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
   if (e != U2_OK) return e;
   return qk_norm_rope(qkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, nq, cs_ld, c.qk_eps, kc, vc, 1, kv_stride,
                       s_off, st);
+}
+
+int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const bf16_t* Wqkv, const bf16_t* bqkv,
+                       const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
+                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+  return decode_pre(c, x, w_in_norm, Wqkv, nullptr, bqkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off,
+                    ws, ws_bytes, st);
+}
+
+int decoder_decode_pre_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const uint8_t* Wqkv8, const float* sqkv,
+                          const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp,
+                          int cs_is_f32, int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws,
+                          size_t ws_bytes, hipStream_t st) {
+  const void* w[1] = {Wqkv8};
+  const float* sc[1] = {sqkv};
+  if (!w8_step_ok(c, w, sc, 1)) return U2_ERR_ARG;
+  return decode_pre(c, x, w_in_norm, Wqkv8, sqkv, bqkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off,
+                    ws, ws_bytes, st);
 }
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
 // (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence)
 static int decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                       int64_t kv_stride, bool batched, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
-                       const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
+                       int64_t kv_stride, bool batched, const int* kv_start, const void* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
+                       const void* Wgu, const bf16_t* bgu, const void* Wdown, const bf16_t* bdown, const DecodeScales* sc, bf16_t* out,
+                       void* ws, size_t ws_bytes, hipStream_t st) {
   if (c.B <= 0 || c.B > 16 || T <= 0 || !x || !qkv || !K || !V || !Wo || !w_post_norm || !Wgu || !Wdown || !out || !ws) return U2_ERR_ARG;
+  if (sc) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
+    const void* w[3] = {Wo, Wgu, Wdown};
+    const float* s3[3] = {sc->o, sc->gu, sc->down};
+    if (!w8_step_ok(c, w, s3, 3)) return U2_ERR_ARG;
+  }
+  const float *so = sc ? sc->o : nullptr, *sgu = sc ? sc->gu : nullptr, *sdown = sc ? sc->down : nullptr;
   if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
   bf16_t* p = reinterpret_cast<bf16_t*>(ws);
@@ -269,31 +313,27 @@ static int decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, c
                                /*o_bs*/ (int64_t)g * c.D, scale, nullptr, 0, 0, 0, aws, aws_bytes, st);
     if (e != U2_OK) return e;
   }
-  int e = dec_linear(ctx, qd, Wo, bo, h, c.E, c.B, qd, c.E, x, c.E, st);
+  int e = dec_linear(ctx, qd, Wo, so, bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
   if (e != U2_OK) return e;
   e = rmsnorm_bf16(h, w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
   if (!bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
-    GemmDesc g;
-    g.A = hn; g.B = Wgu; g.C = act;
-    g.M = c.B; g.N = 2 * c.I; g.K = c.E;
-    g.lda = c.E; g.ldb = c.E; g.ldc = c.I;
-    g.flags = GEMM_SWIGLU;
-    e = gemm_bf16(g, st);
+    e = dec_linear(hn, c.E, Wgu, sgu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
-    e = dec_linear(hn, c.E, Wgu, bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, st);
+    e = dec_linear(hn, c.E, Wgu, sgu, bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
     if (e != U2_OK) return e;
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  return dec_linear(act, c.I, Wdown, bdown, out, c.E, c.B, c.I, c.E, h, c.E, st);
+  return dec_linear(act, c.I, Wdown, sdown, bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
 }
 
 int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
                         int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
                         const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
-  return decode_post(c, x, qkv, K, V, T, kv_stride, false, nullptr, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, out, ws, ws_bytes, st);
+  return decode_post(c, x, qkv, K, V, T, kv_stride, false, nullptr, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, nullptr, out, ws,
+                     ws_bytes, st);
 }
 
 int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
@@ -301,7 +341,18 @@ int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t*
                               const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
                               size_t ws_bytes, hipStream_t st) {
   if (c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3)) return U2_ERR_ARG;
-  return decode_post(c, x, qkv, K, V, T, kv_stride, true, kv_start, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, out, ws, ws_bytes, st);
+  return decode_post(c, x, qkv, K, V, T, kv_stride, true, kv_start, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, nullptr, out, ws,
+                     ws_bytes, st);
+}
+
+// The second half on e4m3 weights: kv_start / batched as the two entry points above (batched: decoder_decode_post_range's form)
+int decoder_decode_post_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                           int64_t kv_stride, bool batched, const int* kv_start, const uint8_t* Wo8, const bf16_t* bo,
+                           const bf16_t* w_post_norm, const uint8_t* Wgu8, const bf16_t* bgu, const uint8_t* Wdown8, const bf16_t* bdown,
+                           const DecodeScales& sc, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (batched && (c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3))) return U2_ERR_ARG;
+  return decode_post(c, x, qkv, K, V, T, kv_stride, batched, kv_start, Wo8, bo, w_post_norm, Wgu8, bgu, Wdown8, bdown, &sc, out, ws,
+                     ws_bytes, st);
 }
 
 }  // namespace u2

@@ -101,6 +101,22 @@ void gemm_plan_format(const GemmPlan& p, char* buf, size_t n);  // " | <kernel> 
 int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);  // gemm_skinny.hip
 int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);      // gemm_bt.hip
 
+// The few-rows product on e4m3 weights (gemm_w8.hip; arithmetic: rows16_w8.h): C = epilogue(scale[n] * A . e4m3(W)^T), M <= 16,
+// K % 64 == 0, 16-byte aligned A / W rows.  gemm_rows_w8_check: the argument check alone (U2_ERR_ARG, nothing launched).
+struct RowsW8Args {        // outside GemmDesc and the plan
+  const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
+  const uint8_t* W = nullptr;    // [N][K] e4m3 codes, leading dim ldw (bytes)
+  const float* scale = nullptr;  // [N]
+  void* C = nullptr;             // [M][N] elements or fp32 (GEMM_OUT_F32); [M][N / 2] elements with GEMM_SWIGLU
+  const bf16_t* bias = nullptr;  // [N] (GEMM_BIAS_N)
+  const bf16_t* R = nullptr;     // [M][N], leading dim ldr (GEMM_RESIDUAL)
+  int M = 0, N = 0, K = 0;
+  int64_t lda = 0, ldw = 0, ldc = 0, ldr = 0;
+  int flags = 0;                 // GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32, or GEMM_SWIGLU alone
+};
+int gemm_rows_w8_check(const RowsW8Args& a);
+int gemm_rows_w8(const RowsW8Args& a, hipStream_t stream);
+
 // ------------------------------------------------------------------ row ops (rowops.hip)
 // y[b][r][:] = LayerNorm(x[b][r][:] (+ res[b][r][:])) * w + bias   (bf16 in/out, fp32 math)
 int layernorm_bf16(const bf16_t* x, const bf16_t* res, const bf16_t* w, const bf16_t* bias, bf16_t* y,
@@ -305,6 +321,18 @@ int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t*
                               int64_t kv_stride, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
                               const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
                               size_t ws_bytes, hipStream_t st);
+// The same step with the four weights as e4m3 codes and a scale per weight row (gemm_w8.hip); biases, norms, rotary, attention,
+// cache and workspace as above.  E, Hq * D and I multiples of 64, 16-byte aligned weights, non-null scales: U2_ERR_ARG otherwise,
+// before anything is launched.
+struct DecodeScales { const float *o, *gu, *down; };
+int decoder_decode_pre_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const uint8_t* Wqkv8, const float* sqkv,
+                          const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp,
+                          int cs_is_f32, int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws,
+                          size_t ws_bytes, hipStream_t st);
+int decoder_decode_post_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                           int64_t kv_stride, bool batched, const int* kv_start, const uint8_t* Wo8, const bf16_t* bo,
+                           const bf16_t* w_post_norm, const uint8_t* Wgu8, const bf16_t* bgu, const uint8_t* Wdown8, const bf16_t* bdown,
+                           const DecodeScales& sc, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
 // ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
 // One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
 // q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between

@@ -63,7 +63,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         steps (bf16, or fp16 on the f16 build), with grad `config.u2_fused_decoder_training` (default False)
         for the training route of decoder_train.py (bf16).  Both switches, `config.u2_fused_padded_batches` (default False:
         padded batches on the no-grad routes) and `config.u2_fused_continued_prefill` (default False: new positions against a
-        filled cache, prefills past the attention window), are passed on as the config has them."""
+        filled cache, prefills past the attention window) and `config.u2_fused_decode_fp8` (default False: the decode step's four
+        products on e4m3 copies of the weights, prefill.py `_w8_state`), are passed on as the config has them."""
         grad = torch.is_grad_enabled()
         train = bool(getattr(self.config, "u2_fused_decoder_training", False))
         prefill = bool(getattr(self.config, "u2_fused_prefill", True))
@@ -79,6 +80,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
             padded = {"padded": True} if bool(getattr(self.config, "u2_fused_padded_batches", False)) else {}
             if bool(getattr(self.config, "u2_fused_continued_prefill", False)):
                 padded["continued"] = True
+            if bool(getattr(self.config, "u2_fused_decode_fp8", False)):   # (default False: decode steps on e4m3 weight copies)
+                padded["fp8_decode"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 

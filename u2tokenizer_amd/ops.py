@@ -689,6 +689,92 @@ def swiglu(gate_up: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------- FP8 (e4m3) weight-only products
+FP8_MAX = 448.0   # largest finite e4m3 (OCP, torch.float8_e4m3fn); the codes 0x7F / 0xFF are NaN
+
+
+def quantize_rows_fp8(w: torch.Tensor):
+    """Per-row e4m3 quantisation of a 2-D weight (N, K) in bf16 / fp16 / fp32 -> (W8 (N, K) torch.float8_e4m3fn, contiguous,
+    scale (N,) fp32) with scale[n] = amax_n / 448 (1.0 for an all-zero row) and W8 = clamp(W / scale, +-448) rounded to e4m3.
+    The clamp is what keeps the NaN codes out: torch converts |v| > 448 to NaN, and W / scale can exceed 448 by a rounding.
+    Plain torch, any device; not a hot path (the decode route quantises a layer once, prefill.py)."""
+    if w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError(f"quantize_rows_fp8: expected a 2-D bf16 / fp16 / fp32 weight, got {tuple(w.shape)} {w.dtype}")
+    wf = w.detach().float()
+    amax = wf.abs().amax(1)
+    if not bool(torch.isfinite(amax).all()):
+        raise RuntimeError("quantize_rows_fp8: the weight holds inf / nan")
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    w8 = (wf / scale[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).contiguous()
+    return w8, scale
+
+
+def dequantize_rows_fp8(w8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 (N, K) = e4m3(W8) * scale[n]: what the e4m3 products multiply by, exactly."""
+    return w8.float() * scale.float()[:, None]
+
+
+def snap_fp8_(module):
+    """In place, for every nn.Linear weight in `module` (or a 2-D tensor): move each row onto values the row quantiser keeps
+    EXACTLY -- the row's scale becomes a power of two (the smallest one >= amax / 448), its values e4m3 multiples of it, and the
+    largest element is forced to +-448 scale, so that quantize_rows_fp8 finds that same scale.  Then
+    dequantize_rows_fp8(*quantize_rows_fp8(w)) == w bit for bit, and w is exact in bf16 (fp16 while 2^-9 scale >= 2^-24): a
+    model with snapped weights and its e4m3 decode step compute the same function.  For tests and the A/B tool."""
+    ws = [module] if torch.is_tensor(module) else [m.weight.data for m in module.modules() if isinstance(m, torch.nn.Linear)]
+    for w in ws:
+        wf = w.detach().float()
+        amax = wf.abs().amax(1)
+        live = amax > 0
+        sc = torch.where(live, torch.exp2(torch.ceil(torch.log2(torch.where(live, amax, torch.ones_like(amax)) / FP8_MAX))),
+                         torch.ones_like(amax))
+        q = (wf / sc[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).float()
+        top = wf.abs().argmax(1, keepdim=True)
+        sign = torch.where(wf.gather(1, top) < 0, -1.0, 1.0)
+        q.scatter_(1, top, torch.where(live[:, None], sign * FP8_MAX, torch.zeros_like(sign)))
+        w.copy_((q * sc[:, None]).to(w.dtype))
+    return module
+
+
+@_guarded
+def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias=None, residual=None, out_f32=False,
+                 swiglu=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(M <= 16, N) = epilogue(scale[n] * a @ e4m3(w8)^T) for w8 (N, K) torch.float8_e4m3fn and scale (N,) fp32
+    (u2tok_gemm_rows_w8: the decode step's weight-streaming product on 1-byte weights, fp32 accumulation).  swiglu: w8 = gate
+    rows | up rows -> (M, N / 2) = silu(gate) * up.  `out` / `residual` may be row-strided views (unit column stride)."""
+    h = _lib.load_library()
+    _need(a, ELEM, "A")
+    if w8.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32 or not w8.is_cuda or not scale.is_cuda:
+        raise RuntimeError("gemm_rows_w8: expected float8_e4m3fn weights and fp32 scales on the GPU")
+    a2 = a.reshape(-1, a.shape[-1])
+    if a2.stride(1) != 1:
+        a2 = a2.contiguous()
+    w8, scale = w8.contiguous(), scale.contiguous()
+    M, K = a2.shape
+    N = w8.shape[0]
+    if w8.shape[1] != K or scale.numel() != N:
+        raise RuntimeError(f"gemm_rows_w8: shapes A {tuple(a2.shape)}, W8 {tuple(w8.shape)}, scale {tuple(scale.shape)}")
+    cols = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
+    if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
+        raise RuntimeError("gemm_rows_w8: out must be (M, columns) with unit column stride in the output type")
+    flags = GEMM_SWIGLU if swiglu else (GEMM_OUT_F32 if out_f32 else 0)
+    ldr = 0
+    if bias is not None:
+        flags |= GEMM_BIAS_N
+        bias = _need(bias, ELEM, "bias").contiguous()
+    if residual is not None:
+        flags |= GEMM_RESIDUAL
+        _need(residual, ELEM, "residual")
+        if residual.shape != (M, N) or residual.stride(1) != 1:
+            raise RuntimeError("gemm_rows_w8: residual must be (M, N) with unit column stride")
+        ldr = residual.stride(0)
+    st = h.u2tok_gemm_rows_w8(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K,
+                              out.stride(0), ldr, flags, _stream())
+    _lib.check(st, "u2tok_gemm_rows_w8")
+    return out
+
+
 @_guarded
 def rope_apply(x: torch.Tensor, n_outer, S, n_inner, H, d, max_len=512, inverse=False):
     h = _lib.load_library()

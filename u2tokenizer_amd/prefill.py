@@ -64,6 +64,8 @@ stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
 # ... and of the continued prefill (new positions against a filled cache, or a prefill past the window), in a dict of its own:
 # `stats` keeps exactly its four routes
 extend_stats = {"extend": 0, "padded_extend": 0}
+# ... and the decode steps (counted in `stats` as well) that really ran on e4m3 weights (fp8_decode=True, `_w8_state`)
+w8_stats = {"decode": 0, "padded_decode": 0}
 
 
 def pad_rule(mask):
@@ -252,6 +254,7 @@ class _StackState:
     prefill: bool = True
     padded: bool = False
     continued: bool = False
+    fp8: bool = False
     mask_ok: bool = True
     pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
     pad_shape: tuple = None    # ... and that mask's (B, columns)
@@ -265,6 +268,7 @@ class _LayerState:
     stack: _StackState
     layout: type
     dec: dict = None
+    w8: dict = None            # fp8_decode=True: the e4m3 copies of the four packed weights and their scales (`_w8_state`)
 
     def __getitem__(self, key):   # (read as a mapping too -- layer._u2_prefill["layout"] -- as when this state was a dict)
         return getattr(self, key)
@@ -598,6 +602,38 @@ def _decode_state(self, B: int, device, pr):
     return d, sc
 
 
+def _w8_state(self, d, pr):
+    """The e4m3 copies of a layer's four packed decode weights (q|k|v, o, gate|up, down: ops.quantize_rows_fp8, a scale per
+    row) with the argument tuples of the _w8 entry points, or None for a layer they do not take (E, Hq D or I not a multiple of
+    64: the layer keeps the 16-bit step).  Built at the first qualifying step, kept in the layer's patch state -- half the layer's
+    weights again in HBM --, rebuilt when a source weight's data_ptr() or _version changed (an optimiser step, load_state_dict,
+    weight.mul_), freed with the patch state by disable_fused_prefill.  Parameters, state dict,
+    prefill and training never see the copies; biases stay in the element type."""
+    st = self._u2_prefill
+    c = d["cfg"]
+    if c.E % 64 or (c.Hq * c.D) % 64 or c.I % 64:
+        return None
+    key = tuple((m.weight.data_ptr(), m.weight._version) for m in pr)
+    w8 = st.w8
+    if w8 is None or w8["key"] != key:
+        Wqkv, _, Wgu, _ = d["keep"]
+        pairs = tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, self.self_attn.o_proj.weight, Wgu, self.mlp.down_proj.weight))
+        w8 = st.w8 = {"d": None, "key": key, "pairs": pairs}
+    if w8["d"] is not d:   # (the decode constants were rebuilt -- another batch size, a moved weight: their pointers anew)
+        (q8, qs), (o8, os_), (g8, gs), (d8, ds) = ((w.data_ptr(), sc.data_ptr()) for w, sc in w8["pairs"])
+        nrm, _, bqkv, qn, kn = d["pre"]
+        _, bo, pn, _, bgu, _, bdown = d["post"]
+        w8.update(d=d, pre=(nrm, q8, qs, bqkv, qn, kn), post=(o8, os_, bo, pn, g8, gs, bgu, d8, ds, bdown))
+    return w8
+
+
+def w8_weights(layer):
+    """The four (W8, scale) pairs -- packed q|k|v, o, packed gate|up, down -- a patched layer's e4m3 decode step reads, or None
+    (not patched, fp8_decode off, no qualifying step yet, a layer that keeps the 16-bit step)."""
+    st = layer.__dict__.get("_u2_prefill")
+    return None if st is None or st.w8 is None else st.w8["pairs"]
+
+
 def _decode_step(self, x, pe, cache, window, pr):
     """One decode step of a layer (B <= 16 new tokens, one each, against the KV cache): the step `generate` repeats up to 768
     times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
@@ -614,6 +650,8 @@ def _decode_step(self, x, pe, cache, window, pr):
     if not d["ok"]:
         return None                                   # (the caller takes the stock layer)
     hd = d["hd"]
+    stack = self._u2_prefill.stack
+    w8 = _w8_state(self, d, pr) if stack.fp8 else None   # fp8_decode=True: the step's four products on e4m3 weights
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
@@ -632,9 +670,9 @@ def _decode_step(self, x, pe, cache, window, pr):
             kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
         else:         # into the step's scratch rows, for the cache's own `update`
             T0, kd, vd, kvs = 0, sc["kc"], sc["vc"], 0
-        _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], x2.data_ptr(), *d["pre"], cos.data_ptr(), sin.data_ptr(),
-                                              int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(),
-                                              kd.data_ptr(), vd.data_ptr(), kvs, T0, ws, nws, stream),
+        pre, pre_args = (h.u2tok_decoder_decode_pre, d["pre"]) if w8 is None else (h.u2tok_decoder_decode_pre_w8, w8["pre"])
+        _lib.check(pre(d["cfg_ref"], x2.data_ptr(), *pre_args, cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
+                       cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(), vd.data_ptr(), kvs, T0, ws, nws, stream),
                    "u2tok_decoder_decode_pre")
         if inplace:
             lay._commit(T0 + 1)
@@ -647,14 +685,17 @@ def _decode_step(self, x, pe, cache, window, pr):
             if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
                 K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
         kind, kv_start, _ = _pad_range(self._u2_prefill)
+        post_args = d["post"] if w8 is None else w8["post"]
         if kind == "left":   # a left-padded batch: the batched decode attention with each sequence's first visible position
-            _lib.check(h.u2tok_decoder_decode_post_range(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(),
-                                                         V.data_ptr(), K.shape[2], kvs, kv_start.data_ptr(), *d["post"],
-                                                         out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post_range")
+            post = h.u2tok_decoder_decode_post_range if w8 is None else h.u2tok_decoder_decode_post_range_w8
+            _lib.check(post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(), K.shape[2], kvs,
+                            kv_start.data_ptr(), *post_args, out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post_range")
         else:
-            _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
-                                                   K.shape[2], kvs, *d["post"], out.data_ptr(), ws, nws, stream),
-                       "u2tok_decoder_decode_post")
+            post = h.u2tok_decoder_decode_post if w8 is None else h.u2tok_decoder_decode_post_w8
+            _lib.check(post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(), K.shape[2], kvs,
+                            *post_args, out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
+    if w8 is not None:
+        w8_stats["decode" if stack.mask_ok else "padded_decode"] += 1
     return out
 
 
@@ -728,7 +769,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
-                         padded: bool = False, continued: bool = False) -> int:
+                         padded: bool = False, continued: bool = False, fp8_decode: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -743,8 +784,13 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     window of a sliding-window layer stay on the HIP layers (`_extend_kv`, u2tok_attention_gqa_band) -- for no cache or a plain
     DynamicCache of DynamicLayer / append-in-place / DynamicSlidingWindowLayer layers, head dims 64 / 96 / 128, any batch size,
     no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers without a window; a
-    right-padded continuation, holes, window + padding and every other cache take the stock layers.  The five switches are set
-    anew by every call.
+    right-padded continuation, holes, window + padding and every other cache take the stock layers.
+    fp8_decode=True (opt-in): a layer whose decode step qualifies today and whose E, Hq D and I are multiples of 64 runs the
+    step's four weight-streaming products on e4m3 copies of its weights with one fp32 scale per row (`_w8_state`,
+    u2tok_decoder_decode_*_w8: half the weight bytes per step, half the layer weights again in HBM; `w8_stats` counts these
+    steps, `w8_weights(layer)` shows the copies); the products are exact on the quantised weights, the quantiser is what costs
+    accuracy -- unmeasured on trained weights.  Every other layer and every other route read the original weights.  The six
+    switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -765,8 +811,12 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
     stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
-    stack.continued = bool(continued)
+    stack.continued, stack.fp8 = bool(continued), bool(fp8_decode)
     stack.pad = stack.pad_shape = None
+    if not stack.fp8:   # (the copies go with the switch)
+        for layer in layers:
+            if is_patched(layer):
+                layer._u2_prefill.w8 = None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
