@@ -346,30 +346,37 @@ int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, i
  *         (B, Hkv, capacity, D; kv_stride = capacity * D, 0: a dense (B, Hkv, 1, D) pair with s_off = 0)
  *   post: attention of the B query rows over the first T positions of K / V (same layout; keys split over workgroups, merged
  *         in a fixed order) -> out projection + residual x -> RMSNorm -> packed gate|up -> SiLU(gate) * up -> down + residual
+ *         batched = 0: a launch pair per sequence, kv_start must be NULL.  batched != 0: the batched decode attention
+ *         (u2tok_decode_attention: one launch for all B sequences and heads, plus one merge; Hq / Hkv <= 16) with a first visible
+ *         cache position per sequence, kv_start (device int32[B]; NULL: all zeros) -- query b attends over positions
+ *         kv_start[b] .. T - 1, the cache of a LEFT-padded batch.
  * B <= 16, D in {64, 96, 128}, E % 32 == 0, I % 32 == 0; biases may be NULL; same rounding points as the HF modules in bf16.
  * A sliding-window layer (Phi-3: the last W positions) passes K / V advanced to its first visible position and T = W.
- * One workspace for both calls: u2tok_decoder_decode_workspace_bytes(cfg, T) bytes. */
+ * One workspace for both calls: u2tok_decoder_decode_workspace_bytes(cfg, T) bytes.
+ * The layer's parameters travel in one descriptor, filled once per layer; the library keeps no pointer to it.  With the four
+ * scales NULL the four W* are contiguous (N, K) matrices in the element type.  With all four set the step is weight-only FP8:
+ * the W* are OCP e4m3 codes (contiguous (N, K) bytes) with one fp32 scale per weight row, every product is u2tok_gemm_rows_w8's
+ * (below), and activations, biases, norms, attention and the KV cache stay in the element type; E, Hq * D and I must then be
+ * multiples of 64, the weights 16-byte and the scales 4-byte aligned.  Some but not all scales set, and every other argument the
+ * step does not take: U2TOK_ERR_ARG before anything is launched. */
 typedef struct u2tok_decode_config {
   int32_t B, E, Hq, Hkv, D, I; /* new tokens (= batch), hidden size, query / key-value heads, head dim, MLP width */
   float eps, qk_eps, scale;    /* RMSNorm eps, q / k norm eps, softmax scale */
 } u2tok_decode_config;
+typedef struct u2tok_decode_layer {
+  const void *w_in_norm, *Wqkv, *bqkv, *wq_norm, *wk_norm;       /* first half */
+  const void *Wo, *bo, *w_post_norm, *Wgu, *bgu, *Wdown, *bdown; /* second half */
+  const float *scale_qkv, *scale_o, *scale_gu, *scale_down;      /* all NULL: weights in the element type;
+                                                                    all set: the four W* are e4m3 codes, a scale per row */
+} u2tok_decode_layer;
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* cfg, int32_t T);
-int u2tok_decoder_decode_pre(const u2tok_decode_config* cfg, const void* x, const void* w_in_norm, const void* Wqkv,
-                             const void* bqkv, const void* wq_norm, const void* wk_norm, const void* cos, const void* sin,
-                             int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache, int64_t kv_stride,
-                             int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
-int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
-                              int32_t T, int64_t kv_stride, const void* Wo, const void* bo, const void* w_post_norm, const void* Wgu,
-                              const void* bgu, const void* Wdown, const void* bdown, void* out, void* workspace,
-                              size_t workspace_bytes, u2tok_stream_t stream);
-/* The second half with the BATCHED decode attention (u2tok_decode_attention: one launch for all B sequences and heads, plus one
- * merge) in place of a launch pair per sequence, and a first visible cache position per sequence: kv_start (device int32[B] or
- * NULL) -- query b attends over positions kv_start[b] .. T - 1, the cache of a LEFT-padded batch.  Same workspace. */
-int u2tok_decoder_decode_post_range(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
-                                    int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo, const void* bo,
-                                    const void* w_post_norm, const void* Wgu, const void* bgu, const void* Wdown, const void* bdown,
-                                    void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
-/* ---- the decode step on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
+int u2tok_decoder_decode_pre(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* cos,
+                             const void* sin, int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache,
+                             int64_t kv_stride, int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* qkv,
+                              const void* K, const void* V, int32_t T, int64_t kv_stride, int32_t batched, const int32_t* kv_start,
+                              void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- products on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
  * attention and the KV cache stay in the element type).  A product is exactly x . (scale[n] * e4m3(W8[n][:])) with fp32
  * accumulation -- the codes are widened to the element type in registers, where every e4m3 value is exact --, so all the loss is
  * the quantiser's (u2tokenizer_amd/ops.py: quantize_rows_fp8).  The weight bytes of a step, which bound it, are halved.
@@ -381,23 +388,6 @@ int u2tok_decoder_decode_post_range(const u2tok_decode_config* cfg, const void* 
 int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
                        int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
                        u2tok_stream_t stream);
-/* u2tok_decoder_decode_pre / _post / _post_range with the four weights as e4m3 codes (contiguous (N, K) bytes) and a scale
- * array behind each: same config, workspace, attention, norms, rotary and cache arguments.  E, Hq * D and I must be multiples
- * of 64, the weights 16-byte aligned and every scale non-null: U2TOK_ERR_ARG otherwise, before anything is launched. */
-int u2tok_decoder_decode_pre_w8(const u2tok_decode_config* cfg, const void* x, const void* w_in_norm, const void* Wqkv8,
-                                const float* scale_qkv, const void* bqkv, const void* wq_norm, const void* wk_norm, const void* cos,
-                                const void* sin, int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache,
-                                int64_t kv_stride, int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
-int u2tok_decoder_decode_post_w8(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
-                                 int32_t T, int64_t kv_stride, const void* Wo8, const float* scale_o, const void* bo,
-                                 const void* w_post_norm, const void* Wgu8, const float* scale_gu, const void* bgu, const void* Wdown8,
-                                 const float* scale_down, const void* bdown, void* out, void* workspace, size_t workspace_bytes,
-                                 u2tok_stream_t stream);
-int u2tok_decoder_decode_post_range_w8(const u2tok_decode_config* cfg, const void* x, const void* qkv, const void* K, const void* V,
-                                       int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo8, const float* scale_o,
-                                       const void* bo, const void* w_post_norm, const void* Wgu8, const float* scale_gu,
-                                       const void* bgu, const void* Wdown8, const float* scale_down, const void* bdown, void* out,
-                                       void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 /* Batched decode attention: out[b] = softmax(q[b] K[b]^T scale over keys kv_start[b] <= j < T) V[b] for B sequences of ONE query
  * row each.  q / out: (B, Hq * D) rows, ldq / ldo elements apart (head h at column h * D); K / V: (B, Hkv, T, D), kv_stride
  * elements between (batch, kv head) entries (0: dense, T * D) -- an append-in-place buffer or the dense cache; D in {64, 96, 128},

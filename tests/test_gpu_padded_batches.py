@@ -297,3 +297,35 @@ def test_padded_batches_stay_stock_with_the_switch_off(ops):
     prefill.disable_fused_prefill(mg)
     assert torch.equal(got.logits, want.logits) and torch.equal(got1.logits, want1.logits)
     assert prefill.stats == n0
+
+
+# ------------------------------------------------------------------------------------------------- 9. the step's second half
+def test_decode_post_null_kv_start_is_all_zeros_and_both_forms_repeat(ops):
+    """u2tok_decoder_decode_post called directly at the smallest shape that still splits the keys (T = 300: five tiles of 64
+    keys, the split picker wants four), 16-bit weights: batched = 1 gives the same bits for kv_start = NULL and kv_start = zeros,
+    and either attention form gives the same bits twice.  (The two forms are not compared: the model tests above and in
+    tests/test_gpu_prefill.py hold each to the float64 gate.)"""
+    import ctypes as C
+    from u2tokenizer_amd import _lib
+    B, E, Hq, Hkv, d, inter, T = 2, 128, 4, 2, 64, 256, 300
+    x, qkv = rnd(B, E, seed=31).to(D), rnd(B, (Hq + 2 * Hkv) * d, seed=32).to(D)
+    K, V = rnd(B, Hkv, T, d, seed=33).to(D), rnd(B, Hkv, T, d, seed=34).to(D)
+    Wo, wn = rnd(E, Hq * d, scale=0.06, seed=35).to(D), (1 + rnd(E, scale=0.1, seed=36).float()).to(bf).to(D)
+    Wgu, Wd = rnd(2 * inter, E, scale=0.09, seed=37).to(D), rnd(E, inter, scale=0.06, seed=38).to(D)
+    cfg = _lib.DecodeConfig(B=B, E=E, Hq=Hq, Hkv=Hkv, D=d, I=inter, eps=1e-6, qk_eps=1e-6, scale=d ** -0.5)
+    lay = _lib.DecodeLayer(Wo=Wo.data_ptr(), w_post_norm=wn.data_ptr(), Wgu=Wgu.data_ptr(), Wdown=Wd.data_ptr())
+    zeros = torch.zeros(B, dtype=torch.int32, device=D)
+    with ops.on_device(x) as (h, stream):
+        ws = torch.empty(h.u2tok_decoder_decode_workspace_bytes(C.byref(cfg), T), dtype=torch.uint8, device=D)
+
+        def post(batched, kv_start=None):
+            out = torch.full((B, E), float("nan"), dtype=bf, device=D)
+            _lib.check(h.u2tok_decoder_decode_post(C.byref(cfg), C.byref(lay), x.data_ptr(), qkv.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                                   T, 0, batched, None if kv_start is None else kv_start.data_ptr(), out.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_post")
+            return out
+
+        loop, batched, with_zeros = (post(0), post(0)), (post(1), post(1)), post(1, zeros)
+    assert torch.isfinite(loop[0]).all() and torch.isfinite(batched[0]).all()
+    assert torch.equal(loop[0], loop[1]) and torch.equal(batched[0], batched[1])
+    assert torch.equal(batched[0], with_zeros)

@@ -231,30 +231,50 @@ def test_gemm_rows_w8_rejects_bad_arguments(lib):
 
 
 def test_decode_w8_entry_points_reject_bad_arguments(lib):
+    """u2tok_decoder_decode_pre / _post return U2TOK_ERR_ARG before any launch or memory access on a layer descriptor or a
+    kv_start they do not take"""
     P = 1 << 20
-    cfg = _lib.DecodeConfig(B=2, E=128, Hq=4, Hkv=2, D=64, I=256, eps=1e-6, qk_eps=1e-6, scale=0.125)
-    ref = C.byref(cfg)
-    # cfg, x, w_in_norm, Wqkv8, scale_qkv, bqkv, wq_norm, wk_norm, cos, sin, f32, cs_ld, qkv, kc, vc, kv_stride, s_off, ws, bytes, stream
-    pre = [ref, P, P, P, P, None, None, None, P, P, 1, 64, P, P, P, 0, 0, P, 1 << 20, None]
-    # cfg, x, qkv, K, V, T, kv_stride, Wo8, so, bo, w_post_norm, Wgu8, sgu, bgu, Wdown8, sdown, bdown, out, ws, bytes, stream
-    post = [ref, P, P, P, P, 8, 0, P, P, None, P, P, P, None, P, P, None, P, P, 1 << 24, None]
+    SCALES = ("scale_qkv", "scale_o", "scale_gu", "scale_down")
 
-    def bad(fn, base, i, v):
-        a = list(base)
-        a[i] = v
-        return fn(*a)
+    def config(**kw):
+        c = _lib.DecodeConfig(B=2, E=128, Hq=4, Hkv=2, D=64, I=256, eps=1e-6, qk_eps=1e-6, scale=0.125)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
 
-    assert bad(lib.u2tok_decoder_decode_pre_w8, pre, 4, None) == -1          # null scale
-    assert bad(lib.u2tok_decoder_decode_pre_w8, pre, 3, P + 8) == -1         # misaligned weights
-    for fn, base in ((lib.u2tok_decoder_decode_post_w8, post), (lib.u2tok_decoder_decode_post_range_w8, post[:7] + [None] + post[7:])):
-        off = len(base) - len(post)
-        for i in (8, 12, 15):
-            assert bad(fn, base, i + off, None) == -1, i                     # null scales
-        assert bad(fn, base, 11 + off, P + 4) == -1
+    def layer(**kw):   # e4m3 codes with a scale behind each, no biases, no q / k norms
+        fields = dict(w_in_norm=P, Wqkv=P, Wo=P, w_post_norm=P, Wgu=P, Wdown=P, **{n: P for n in SCALES})
+        fields.update(kw)
+        return _lib.DecodeLayer(**fields)
+
+    def pre(lay, cfg=None):
+        # cfg, layer, x, cos, sin, f32, cs_ld, qkv, kc, vc, kv_stride, s_off, ws, bytes, stream
+        return lib.u2tok_decoder_decode_pre(C.byref(cfg or config()), C.byref(lay), P, P, P, 1, 64, P, P, P, 0, 0, P, 1 << 20, None)
+
+    def post(lay, batched, cfg=None, kv_start=None):
+        # cfg, layer, x, qkv, K, V, T, kv_stride, batched, kv_start, out, ws, bytes, stream
+        return lib.u2tok_decoder_decode_post(C.byref(cfg or config()), C.byref(lay), P, P, P, P, 8, 0, batched, kv_start, P, P, 1 << 24,
+                                             None)
+
+    assert pre(layer(scale_qkv=None)) == -1                                  # null scale
+    assert pre(layer(Wqkv=P + 8)) == -1                                      # misaligned weights
+    for batched in (0, 1):
+        for name in ("scale_o", "scale_gu", "scale_down"):
+            assert post(layer(**{name: None}), batched) == -1, name          # null scales
+        assert post(layer(Wgu=P + 4), batched) == -1
     for name, v in (("E", 96), ("I", 96), ("D", 96), ("Hq", 3)):             # E / I / Hq D not multiples of 64 (K = 96), or no config
-        c2 = _lib.DecodeConfig(B=2, E=128, Hq=4, Hkv=2, D=64, I=256, eps=1e-6, qk_eps=1e-6, scale=0.125)
-        setattr(c2, name, v)
-        if name == "D":
-            c2.Hq, c2.Hkv = 1, 1
-        assert lib.u2tok_decoder_decode_pre_w8(C.byref(c2), *pre[1:]) == -1, name
-        assert lib.u2tok_decoder_decode_post_w8(C.byref(c2), *post[1:]) == -1, name
+        c2 = config(**{name: v}, **(dict(Hq=1, Hkv=1) if name == "D" else {}))
+        assert pre(layer(), c2) == -1, name
+        for batched in (0, 1):
+            assert post(layer(), batched, c2) == -1, name
+    # what only the descriptor can say: some of the four scales (a set one on a 16-bit layer, a missing one on an e4m3 layer:
+    # each half refuses whichever scale it is, its own or the other half's), kv_start without the batched attention
+    for name in SCALES:
+        for lay in (layer(**{n: None for n in SCALES if n != name}), layer(**{name: None})):
+            assert pre(lay) == -1, name
+            assert post(lay, 0) == -1 and post(lay, 1) == -1, name
+    for lay in (layer(), layer(**{n: None for n in SCALES})):
+        assert post(lay, 0, kv_start=P) == -1
+        # the batched attention's own limits: 16 query heads per kv head at the most, kv_start an int32 array
+        assert post(lay, 1, config(Hq=64, Hkv=2)) == -1
+        assert post(lay, 1, kv_start=P + 2) == -1

@@ -6,8 +6,8 @@
            took before the switch existed); both sides step on their own cache, pair by pair
   kernel   u2tok_decode_attention (kv_start = NULL) against the per-sequence loop of u2tok_decoder_decode_post -- one
            u2tok_attention_gqa_split call per sequence, as decoder.hip issues them -- at B = 1 / 4 / 8 / 16, T = 1100 / 1792,
-           d = 128, 8 kv heads of 4 query heads; and the two whole second halves of the step (u2tok_decoder_decode_post against
-           u2tok_decoder_decode_post_range), which differ in nothing else
+           d = 128, 8 kv heads of 4 query heads; and the two whole second halves of the step (u2tok_decoder_decode_post with
+           batched = 0 against batched = 1), which differ in nothing else
   prefill  a B = 4, S = 1024 left-padded prefill through the range kernel against the stock layers, with the share of 64-key
            tiles the kernel skips
 
@@ -168,18 +168,17 @@ def _kernel_ab(h, stream, B, T, reps, dev, iters, rn, qkv, K, V, out, scale):
     ws = torch.empty(h.u2tok_decoder_decode_workspace_bytes(C.byref(cfg), T), dtype=torch.uint8, device=dev)
     x, y = rn(B, E), torch.empty((B, E), dtype=bf, device=dev)
     Wo, wn, Wgu, Wd = rn(E, Hq * d, k=0.02), rn(E).add_(1), rn(2 * inter, E, k=0.02), rn(E, inter, k=0.02)
-    tail = (Wo.data_ptr(), None, wn.data_ptr(), Wgu.data_ptr(), None, Wd.data_ptr(), None, y.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    lay = _lib.DecodeLayer(Wo=Wo.data_ptr(), w_post_norm=wn.data_ptr(), Wgu=Wgu.data_ptr(), Wdown=Wd.data_ptr())
 
-    def post_old():
-        for _ in range(iters):
-            _lib.check(h.u2tok_decoder_decode_post(C.byref(cfg), x.data_ptr(), qkv.data_ptr(), K.data_ptr(), V.data_ptr(), T, 0, *tail), "post")
+    def post(batched):
+        def run():
+            for _ in range(iters):
+                _lib.check(h.u2tok_decoder_decode_post(C.byref(cfg), C.byref(lay), x.data_ptr(), qkv.data_ptr(), K.data_ptr(),
+                                                       V.data_ptr(), T, 0, batched, None, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       stream), "u2tok_decoder_decode_post")
+        return run
 
-    def post_new():
-        for _ in range(iters):
-            _lib.check(h.u2tok_decoder_decode_post_range(C.byref(cfg), x.data_ptr(), qkv.data_ptr(), K.data_ptr(), V.data_ptr(), T, 0,
-                                                         None, *tail), "post_range")
-
-    rp = _pairs(post_old, post_new, reps)
+    rp = _pairs(post(0), post(1), reps)
     us = lambda v: round(v * 1e3 / iters, 2)  # noqa: E731
     return {"B": B, "T": T, "attention_loop_us": us(r["a_ms"]), "attention_batched_us": us(r["b_ms"]), "attention_spread_us": us(r["spread_ms"]),
             "loop_over_batched": round(r["a_ms"] / r["b_ms"], 2), "max_abs_diff": agree,

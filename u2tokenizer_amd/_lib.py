@@ -62,6 +62,11 @@ class DecodeConfig(C.Structure):   # u2tok_decode_config
                 ("eps", C.c_float), ("qk_eps", C.c_float), ("scale", C.c_float)]
 
 
+class DecodeLayer(C.Structure):    # u2tok_decode_layer: raw addresses -- whoever fills one keeps the tensors alive
+    _fields_ = [(n, C.c_void_p) for n in ("w_in_norm", "Wqkv", "bqkv", "wq_norm", "wk_norm", "Wo", "bo", "w_post_norm", "Wgu", "bgu",
+                                          "Wdown", "bdown", "scale_qkv", "scale_o", "scale_gu", "scale_down")]
+
+
 class TokTaps(C.Structure):
     _fields_ = [("svr_in", C.POINTER(C.c_void_p)), ("svr_out", C.POINTER(C.c_void_p)), ("visual_in", C.c_void_p),
                 ("visual_out", C.c_void_p), ("tta_in", C.POINTER(C.c_void_p)), ("tta_out", C.POINTER(C.c_void_p))]
@@ -130,19 +135,11 @@ SIGNATURES = {
                                      _i64, _i32, _vp]),
     "u2tok_swiglu_bf16": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp]),
     "u2tok_decoder_decode_workspace_bytes": (_sz, [_vp, _i32]),
-    "u2tok_decoder_decode_pre": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp,
-                                        _sz, _vp]),
-    "u2tok_decoder_decode_post": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                         _vp]),
-    "u2tok_decoder_decode_post_range": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               _sz, _vp]),
+    # cfg, layer, x, cos, sin, cos_sin_f32, cs_ld, qkv, k_cache, v_cache, kv_stride, s_off, workspace, workspace_bytes, stream
+    "u2tok_decoder_decode_pre": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
+    # cfg, layer, x, qkv, K, V, T, kv_stride, batched, kv_start, out, workspace, workspace_bytes, stream
+    "u2tok_decoder_decode_post": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "u2tok_decoder_decode_pre_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32,
-                                           _vp, _sz, _vp]),
-    "u2tok_decoder_decode_post_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _vp, _sz, _vp]),
-    "u2tok_decoder_decode_post_range_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                  _vp, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "u2tok_decode_attention": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),
     "u2tok_rope_apply": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),

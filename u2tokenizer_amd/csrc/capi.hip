@@ -16,7 +16,7 @@ static_assert(U2TOK_OK == U2_OK && U2TOK_ERR_ARG == U2_ERR_ARG && U2TOK_ERR_LAUN
 
 extern "C" {
 
-int u2tok_version(void) { return 100; /* 0.1.0 */ }
+int u2tok_version(void) { return 200; /* 0.2.0 */ }
 const char* u2tok_arch(void) { return "gfx950"; }
 const char* u2tok_elem(void) { return U2_ELEM_ASM; }
 
@@ -307,31 +307,29 @@ static bool dec_ok(const u2tok_decode_config* c) {
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* c, int32_t T) {
   return dec_ok(c) && T > 0 ? decoder_decode_workspace_bytes(dec_cfg(c), T) : 0;
 }
-int u2tok_decoder_decode_pre(const u2tok_decode_config* c, const void* x, const void* w_in_norm, const void* Wqkv, const void* bqkv,
-                             const void* wq_norm, const void* wk_norm, const void* cos, const void* sin, int32_t cos_sin_f32,
-                             int64_t cs_ld, void* qkv, void* k_cache, void* v_cache, int64_t kv_stride, int32_t s_off,
-                             void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  if (!dec_ok(c)) return U2_ERR_ARG;
-  return decoder_decode_pre(dec_cfg(c), BF(x), BF(w_in_norm), BF(Wqkv), BF(bqkv), BF(wq_norm), BF(wk_norm), cos, sin, cos_sin_f32,
-                            cs_ld, BFW(qkv), BFW(k_cache), BFW(v_cache), kv_stride, s_off, workspace, workspace_bytes, ST(stream));
+static DecodeLayer dec_layer(const u2tok_decode_layer* l) {
+  DecodeLayer d;
+  d.w_in_norm = BF(l->w_in_norm); d.Wqkv = l->Wqkv; d.bqkv = BF(l->bqkv); d.wq_norm = BF(l->wq_norm); d.wk_norm = BF(l->wk_norm);
+  d.Wo = l->Wo; d.bo = BF(l->bo); d.w_post_norm = BF(l->w_post_norm);
+  d.Wgu = l->Wgu; d.bgu = BF(l->bgu); d.Wdown = l->Wdown; d.bdown = BF(l->bdown);
+  d.scale_qkv = l->scale_qkv; d.scale_o = l->scale_o; d.scale_gu = l->scale_gu; d.scale_down = l->scale_down;
+  return d;
 }
-int u2tok_decoder_decode_post(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V, int32_t T,
-                              int64_t kv_stride, const void* Wo, const void* bo, const void* w_post_norm, const void* Wgu, const void* bgu,
-                              const void* Wdown, const void* bdown, void* out, void* workspace, size_t workspace_bytes,
-                              u2tok_stream_t stream) {
-  if (!dec_ok(c)) return U2_ERR_ARG;
-  return decoder_decode_post(dec_cfg(c), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, BF(Wo), BF(bo), BF(w_post_norm), BF(Wgu), BF(bgu),
-                             BF(Wdown), BF(bdown), BFW(out), workspace, workspace_bytes, ST(stream));
+int u2tok_decoder_decode_pre(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* cos, const void* sin,
+                             int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache, int64_t kv_stride,
+                             int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  if (!dec_ok(c) || !l) return U2_ERR_ARG;
+  return decoder_decode_pre(dec_cfg(c), dec_layer(l), BF(x), cos, sin, cos_sin_f32, cs_ld, BFW(qkv), BFW(k_cache), BFW(v_cache),
+                            kv_stride, s_off, workspace, workspace_bytes, ST(stream));
 }
-int u2tok_decoder_decode_post_range(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V,
-                                    int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo, const void* bo,
-                                    const void* w_post_norm, const void* Wgu, const void* bgu, const void* Wdown, const void* bdown,
-                                    void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  if (!dec_ok(c)) return U2_ERR_ARG;
-  return decoder_decode_post_range(dec_cfg(c), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, kv_start, BF(Wo), BF(bo), BF(w_post_norm),
-                                   BF(Wgu), BF(bgu), BF(Wdown), BF(bdown), BFW(out), workspace, workspace_bytes, ST(stream));
+int u2tok_decoder_decode_post(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* qkv, const void* K,
+                              const void* V, int32_t T, int64_t kv_stride, int32_t batched, const int32_t* kv_start, void* out,
+                              void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  if (!dec_ok(c) || !l) return U2_ERR_ARG;
+  return decoder_decode_post(dec_cfg(c), dec_layer(l), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out),
+                             workspace, workspace_bytes, ST(stream));
 }
-// ---- the decode step on e4m3 weights (gemm_w8.hip; DecodeScales: kernels.h)
+// ---- the few-rows product on e4m3 weights (gemm_w8.hip)
 int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
                        int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
   RowsW8Args a;
@@ -340,42 +338,6 @@ int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* 
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
   a.flags = flags;
   return gemm_rows_w8(a, ST(stream));
-}
-int u2tok_decoder_decode_pre_w8(const u2tok_decode_config* c, const void* x, const void* w_in_norm, const void* Wqkv8,
-                                const float* scale_qkv, const void* bqkv, const void* wq_norm, const void* wk_norm, const void* cos,
-                                const void* sin, int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache,
-                                int64_t kv_stride, int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  if (!dec_ok(c)) return U2_ERR_ARG;
-  return decoder_decode_pre_w8(dec_cfg(c), BF(x), BF(w_in_norm), reinterpret_cast<const uint8_t*>(Wqkv8), scale_qkv, BF(bqkv),
-                               BF(wq_norm), BF(wk_norm), cos, sin, cos_sin_f32, cs_ld, BFW(qkv), BFW(k_cache), BFW(v_cache), kv_stride,
-                               s_off, workspace, workspace_bytes, ST(stream));
-}
-static int dec_post_w8(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V, int32_t T,
-                       int64_t kv_stride, bool batched, const int32_t* kv_start, const void* Wo8, const float* scale_o, const void* bo,
-                       const void* w_post_norm, const void* Wgu8, const float* scale_gu, const void* bgu, const void* Wdown8,
-                       const float* scale_down, const void* bdown, void* out, void* workspace, size_t workspace_bytes,
-                       u2tok_stream_t stream) {
-  if (!dec_ok(c)) return U2_ERR_ARG;
-  const DecodeScales sc{scale_o, scale_gu, scale_down};
-  return decoder_decode_post_w8(dec_cfg(c), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched, kv_start,
-                                reinterpret_cast<const uint8_t*>(Wo8), BF(bo), BF(w_post_norm), reinterpret_cast<const uint8_t*>(Wgu8),
-                                BF(bgu), reinterpret_cast<const uint8_t*>(Wdown8), BF(bdown), sc, BFW(out), workspace, workspace_bytes,
-                                ST(stream));
-}
-int u2tok_decoder_decode_post_w8(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V, int32_t T,
-                                 int64_t kv_stride, const void* Wo8, const float* scale_o, const void* bo, const void* w_post_norm,
-                                 const void* Wgu8, const float* scale_gu, const void* bgu, const void* Wdown8, const float* scale_down,
-                                 const void* bdown, void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  return dec_post_w8(c, x, qkv, K, V, T, kv_stride, false, nullptr, Wo8, scale_o, bo, w_post_norm, Wgu8, scale_gu, bgu, Wdown8,
-                     scale_down, bdown, out, workspace, workspace_bytes, stream);
-}
-int u2tok_decoder_decode_post_range_w8(const u2tok_decode_config* c, const void* x, const void* qkv, const void* K, const void* V,
-                                       int32_t T, int64_t kv_stride, const int32_t* kv_start, const void* Wo8, const float* scale_o,
-                                       const void* bo, const void* w_post_norm, const void* Wgu8, const float* scale_gu, const void* bgu,
-                                       const void* Wdown8, const float* scale_down, const void* bdown, void* out, void* workspace,
-                                       size_t workspace_bytes, u2tok_stream_t stream) {
-  return dec_post_w8(c, x, qkv, K, V, T, kv_stride, true, kv_start, Wo8, scale_o, bo, w_post_norm, Wgu8, scale_gu, bgu, Wdown8,
-                     scale_down, bdown, out, workspace, workspace_bytes, stream);
 }
 size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
   return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);

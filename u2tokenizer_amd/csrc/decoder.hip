@@ -200,7 +200,7 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
 // One projection of the step: the element type's product through the plan, or -- `sc`: a scale per weight row, w = e4m3 codes
-// (the _w8 entry points) -- the few-rows product on 1-byte weights (gemm_w8.hip).  pair: w = gate | up, y (rows, out / 2).
+// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_w8.hip).  pair: w = gate | up, y (rows, out / 2).
 static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const bf16_t* b, bf16_t* y, int64_t ldy, int rows,
                       int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
   if (sc) {
@@ -228,66 +228,53 @@ static bool w8_step_ok(const DecodeCfg& c, const void* const* w, const float* co
   return true;
 }
 
+// How many of a layer's four scales are set: 0 (weights in the element type) or 4 (e4m3 codes), anything between is refused
+static int scales_set(const DecodeLayer& l) { return !!l.scale_qkv + !!l.scale_o + !!l.scale_gu + !!l.scale_down; }
+
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
   const size_t rows = (size_t)c.B;
   size_t n = rows * ((size_t)3 * c.E + (size_t)c.Hq * c.D + (size_t)3 * c.I) * sizeof(bf16_t);  // xn, h, hn | ctx | gu (2 I), act
   n = (n + 255) & ~(size_t)255;
-  // the attention's key-split partials: the per-sequence form (decoder_decode_post) or the batched kernel (decoder_decode_post_range)
+  // the attention's key-split partials: decoder_decode_post's per-sequence form or its batched kernel
   return n + std::max(tok_attention_workspace_bytes(c.Hkv, c.Hq / c.Hkv, 1, T, c.D), decode_attention_workspace_bytes(c.B, c.Hq, c.Hkv, T, c.D)) +
          256;
 }
 
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
 // (B, Hkv, 1, D) receive the new cache entries
-static int decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const void* Wqkv, const float* sqkv,
-                      const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
-                      int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
-                      hipStream_t st) {
-  if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !w_in_norm || !Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
+int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+  if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
+  const int ns = scales_set(l);
+  if (ns != 0 && (ns != 4 || !w8_step_ok(c, &l.Wqkv, &l.scale_qkv, 1))) return U2_ERR_ARG;
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
-  int e = rmsnorm_bf16(x, w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
+  int e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  e = dec_linear(xn, c.E, Wqkv, sqkv, bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
+  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
   if (e != U2_OK) return e;
-  return qk_norm_rope(qkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, nq, cs_ld, c.qk_eps, kc, vc, 1, kv_stride,
+  return qk_norm_rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, nq, cs_ld, c.qk_eps, kc, vc, 1, kv_stride,
                       s_off, st);
-}
-
-int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const bf16_t* Wqkv, const bf16_t* bqkv,
-                       const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
-                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  return decode_pre(c, x, w_in_norm, Wqkv, nullptr, bqkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off,
-                    ws, ws_bytes, st);
-}
-
-int decoder_decode_pre_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const uint8_t* Wqkv8, const float* sqkv,
-                          const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp,
-                          int cs_is_f32, int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws,
-                          size_t ws_bytes, hipStream_t st) {
-  const void* w[1] = {Wqkv8};
-  const float* sc[1] = {sqkv};
-  if (!w8_step_ok(c, w, sc, 1)) return U2_ERR_ARG;
-  return decode_pre(c, x, w_in_norm, Wqkv8, sqkv, bqkv, wq_norm, wk_norm, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off,
-                    ws, ws_bytes, st);
 }
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
 // (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence)
-static int decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                       int64_t kv_stride, bool batched, const int* kv_start, const void* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
-                       const void* Wgu, const bf16_t* bgu, const void* Wdown, const bf16_t* bdown, const DecodeScales* sc, bf16_t* out,
-                       void* ws, size_t ws_bytes, hipStream_t st) {
-  if (c.B <= 0 || c.B > 16 || T <= 0 || !x || !qkv || !K || !V || !Wo || !w_post_norm || !Wgu || !Wdown || !out || !ws) return U2_ERR_ARG;
-  if (sc) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
-    const void* w[3] = {Wo, Wgu, Wdown};
-    const float* s3[3] = {sc->o, sc->gu, sc->down};
-    if (!w8_step_ok(c, w, s3, 3)) return U2_ERR_ARG;
+int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
+                        int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
+                        hipStream_t st) {
+  if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
+      !ws)
+    return U2_ERR_ARG;
+  if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
+  const int ns = scales_set(l);
+  if (ns != 0) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
+    const void* w[3] = {l.Wo, l.Wgu, l.Wdown};
+    const float* s3[3] = {l.scale_o, l.scale_gu, l.scale_down};
+    if (ns != 4 || !w8_step_ok(c, w, s3, 3)) return U2_ERR_ARG;
   }
-  const float *so = sc ? sc->o : nullptr, *sgu = sc ? sc->gu : nullptr, *sdown = sc ? sc->down : nullptr;
   if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
   bf16_t* p = reinterpret_cast<bf16_t*>(ws);
@@ -313,46 +300,20 @@ static int decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, c
                                /*o_bs*/ (int64_t)g * c.D, scale, nullptr, 0, 0, 0, aws, aws_bytes, st);
     if (e != U2_OK) return e;
   }
-  int e = dec_linear(ctx, qd, Wo, so, bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
+  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
   if (e != U2_OK) return e;
-  e = rmsnorm_bf16(h, w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
+  e = rmsnorm_bf16(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  if (!bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
-    e = dec_linear(hn, c.E, Wgu, sgu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
+  if (!l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
-    e = dec_linear(hn, c.E, Wgu, sgu, bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
     if (e != U2_OK) return e;
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  return dec_linear(act, c.I, Wdown, sdown, bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
-}
-
-int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                        int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
-                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
-  return decode_post(c, x, qkv, K, V, T, kv_stride, false, nullptr, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, nullptr, out, ws,
-                     ws_bytes, st);
-}
-
-int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                              int64_t kv_stride, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
-                              const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
-                              size_t ws_bytes, hipStream_t st) {
-  if (c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3)) return U2_ERR_ARG;
-  return decode_post(c, x, qkv, K, V, T, kv_stride, true, kv_start, Wo, bo, w_post_norm, Wgu, bgu, Wdown, bdown, nullptr, out, ws,
-                     ws_bytes, st);
-}
-
-// The second half on e4m3 weights: kv_start / batched as the two entry points above (batched: decoder_decode_post_range's form)
-int decoder_decode_post_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                           int64_t kv_stride, bool batched, const int* kv_start, const uint8_t* Wo8, const bf16_t* bo,
-                           const bf16_t* w_post_norm, const uint8_t* Wgu8, const bf16_t* bgu, const uint8_t* Wdown8, const bf16_t* bdown,
-                           const DecodeScales& sc, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (batched && (c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3))) return U2_ERR_ARG;
-  return decode_post(c, x, qkv, K, V, T, kv_stride, batched, kv_start, Wo8, bo, w_post_norm, Wgu8, bgu, Wdown8, bdown, &sc, out, ws,
-                     ws_bytes, st);
+  return dec_linear(act, c.I, l.Wdown, l.scale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
 }
 
 }  // namespace u2

@@ -307,32 +307,24 @@ struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
   int B, E, Hq, Hkv, D, I;
   float eps, qk_eps, scale;
 };
+// A layer's decode-step parameters (u2tok_decode_layer).  No scale set: the four W* are in the element type; all four set: they
+// are e4m3 codes with a scale per weight row (gemm_w8.hip), which asks E, Hq * D and I multiples of 64, 16-byte aligned weights
+// and 4-byte aligned scales.  Some set: U2_ERR_ARG, like every other refusal before anything is launched.
+struct DecodeLayer {
+  const void *Wqkv, *Wo, *Wgu, *Wdown;
+  const bf16_t *w_in_norm, *bqkv, *wq_norm, *wk_norm;  // first half
+  const bf16_t *bo, *w_post_norm, *bgu, *bdown;        // second half
+  const float *scale_qkv, *scale_o, *scale_gu, *scale_down;
+};
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T);
-int decoder_decode_pre(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const bf16_t* Wqkv, const bf16_t* bqkv,
-                       const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp, int cs_is_f32,
+int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
                        int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
                        hipStream_t st);
-int decoder_decode_post(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                        int64_t kv_stride, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm, const bf16_t* Wgu, const bf16_t* bgu,
-                        const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
-// decoder_decode_post with the batched decode attention (decode_attn.hip) in place of the per-sequence loop; kv_start: optional (B)
-// first visible cache position per sequence (a left-padded batch)
-int decoder_decode_post_range(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                              int64_t kv_stride, const int* kv_start, const bf16_t* Wo, const bf16_t* bo, const bf16_t* w_post_norm,
-                              const bf16_t* Wgu, const bf16_t* bgu, const bf16_t* Wdown, const bf16_t* bdown, bf16_t* out, void* ws,
-                              size_t ws_bytes, hipStream_t st);
-// The same step with the four weights as e4m3 codes and a scale per weight row (gemm_w8.hip); biases, norms, rotary, attention,
-// cache and workspace as above.  E, Hq * D and I multiples of 64, 16-byte aligned weights, non-null scales: U2_ERR_ARG otherwise,
-// before anything is launched.
-struct DecodeScales { const float *o, *gu, *down; };
-int decoder_decode_pre_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* w_in_norm, const uint8_t* Wqkv8, const float* sqkv,
-                          const bf16_t* bqkv, const bf16_t* wq_norm, const bf16_t* wk_norm, const void* cosp, const void* sinp,
-                          int cs_is_f32, int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws,
-                          size_t ws_bytes, hipStream_t st);
-int decoder_decode_post_w8(const DecodeCfg& c, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                           int64_t kv_stride, bool batched, const int* kv_start, const uint8_t* Wo8, const bf16_t* bo,
-                           const bf16_t* w_post_norm, const uint8_t* Wgu8, const bf16_t* bgu, const uint8_t* Wdown8, const bf16_t* bdown,
-                           const DecodeScales& sc, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
+// batched: the batched decode attention (decode_attn.hip) in place of the per-sequence loop, with kv_start the optional (B) first
+// visible cache position per sequence (a left-padded batch); kv_start without batched: U2_ERR_ARG
+int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
+                        int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
+                        hipStream_t st);
 // ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
 // One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
 // q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between

@@ -18,8 +18,8 @@ DECODE step (one new position per sequence, batch <= 16, a plain HF DynamicCache
 training, CPU tensors, sliding-window layers, padded batches, other cache types -- takes the layer's original forward.
 `enable_fused_prefill(model, padded=True)` (opt-in) keeps LEFT- and RIGHT-padded batches on the fused prefill (`pad_rule`: a key
 range per sequence inside the attention kernel, u2tok_attention_gqa_range) and left-padded batches on the fused decode step (the
-batched decode attention of csrc/decode_attn.hip, u2tok_decoder_decode_post_range) -- what `generate` on a batch of prompts of
-different lengths calls.
+batched decode attention of csrc/decode_attn.hip, u2tok_decoder_decode_post with batched = 1) -- what `generate` on a batch of
+prompts of different lengths calls.
 `enable_fused_prefill(model, continued=True)` (opt-in) keeps two more inference calls on the HIP layers, both through one extension
 of the attention kernel (u2tok_attention_gqa_band: K / V read in the cache's own (B, H_kv, capacity, d) layout, the lower edge of
 an attention window per query row): more than one new position against a cache that already holds keys (a second turn, a prompt
@@ -577,12 +577,12 @@ def _decode_state(self, B: int, device, pr):
         ok = (E % 32 == 0 and inter % 32 == 0 and att.o_proj.weight.is_contiguous() and mlp.down_proj.weight.is_contiguous()
               and self.post_attention_layernorm.variance_epsilon == self.input_layernorm.variance_epsilon)
         p = ops._ptr
-        d = {"key": key, "ok": ok, "cfg": c, "cfg_ref": C.byref(c), "keep": (Wqkv, bqkv, Wgu, bgu), "nq": (Hq + 2 * Hkv) * hd,
-             "Hkv": Hkv, "hd": hd, "E": E,
-             "pre": (p(self.input_layernorm.weight), p(Wqkv), p(bqkv), p(None if qn is None else qn.weight),
-                     p(None if kn is None else kn.weight)),
-             "post": (p(att.o_proj.weight), p(att.o_proj.bias), p(self.post_attention_layernorm.weight), p(Wgu), p(bgu),
-                      p(mlp.down_proj.weight), p(mlp.down_proj.bias))}
+        lay = _lib.DecodeLayer(w_in_norm=p(self.input_layernorm.weight), Wqkv=p(Wqkv), bqkv=p(bqkv),
+                               wq_norm=p(None if qn is None else qn.weight), wk_norm=p(None if kn is None else kn.weight),
+                               Wo=p(att.o_proj.weight), bo=p(att.o_proj.bias), w_post_norm=p(self.post_attention_layernorm.weight),
+                               Wgu=p(Wgu), bgu=p(bgu), Wdown=p(mlp.down_proj.weight), bdown=p(mlp.down_proj.bias))
+        d = {"key": key, "ok": ok, "cfg": c, "cfg_ref": C.byref(c), "layer": lay, "layer_ref": C.byref(lay),
+             "keep": (Wqkv, bqkv, Wgu, bgu), "nq": (Hq + 2 * Hkv) * hd, "Hkv": Hkv, "hd": hd, "E": E}
         st.dec = d
     # (per model, batch size AND stream: two generate() calls in flight on different streams must not share the step's scratch)
     stream = torch.cuda.current_stream(device).cuda_stream
@@ -604,8 +604,8 @@ def _decode_state(self, B: int, device, pr):
 
 def _w8_state(self, d, pr):
     """The e4m3 copies of a layer's four packed decode weights (q|k|v, o, gate|up, down: ops.quantize_rows_fp8, a scale per
-    row) with the argument tuples of the _w8 entry points, or None for a layer they do not take (E, Hq D or I not a multiple of
-    64: the layer keeps the 16-bit step).  Built at the first qualifying step, kept in the layer's patch state -- half the layer's
+    row) with the layer's descriptor on them (`layer` / `layer_ref`: the 16-bit step's with codes and scales in place of the
+    four weights), or None for a layer they do not take (E, Hq D or I not a multiple of 64: the layer keeps the 16-bit step).  Built at the first qualifying step, kept in the layer's patch state -- half the layer's
     weights again in HBM --, rebuilt when a source weight's data_ptr() or _version changed (an optimiser step, load_state_dict,
     weight.mul_), freed with the patch state by disable_fused_prefill.  Parameters, state dict,
     prefill and training never see the copies; biases stay in the element type."""
@@ -620,10 +620,12 @@ def _w8_state(self, d, pr):
         pairs = tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, self.self_attn.o_proj.weight, Wgu, self.mlp.down_proj.weight))
         w8 = st.w8 = {"d": None, "key": key, "pairs": pairs}
     if w8["d"] is not d:   # (the decode constants were rebuilt -- another batch size, a moved weight: their pointers anew)
-        (q8, qs), (o8, os_), (g8, gs), (d8, ds) = ((w.data_ptr(), sc.data_ptr()) for w, sc in w8["pairs"])
-        nrm, _, bqkv, qn, kn = d["pre"]
-        _, bo, pn, _, bgu, _, bdown = d["post"]
-        w8.update(d=d, pre=(nrm, q8, qs, bqkv, qn, kn), post=(o8, os_, bo, pn, g8, gs, bgu, d8, ds, bdown))
+        import ctypes as C
+        from . import _lib
+        lay = _lib.DecodeLayer.from_buffer_copy(d["layer"])   # norms and biases as the 16-bit step has them
+        (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
+            (w.data_ptr(), sc.data_ptr()) for w, sc in w8["pairs"])
+        w8.update(d=d, layer=lay, layer_ref=C.byref(lay))
     return w8
 
 
@@ -670,10 +672,10 @@ def _decode_step(self, x, pe, cache, window, pr):
             kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
         else:         # into the step's scratch rows, for the cache's own `update`
             T0, kd, vd, kvs = 0, sc["kc"], sc["vc"], 0
-        pre, pre_args = (h.u2tok_decoder_decode_pre, d["pre"]) if w8 is None else (h.u2tok_decoder_decode_pre_w8, w8["pre"])
-        _lib.check(pre(d["cfg_ref"], x2.data_ptr(), *pre_args, cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
-                       cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(), vd.data_ptr(), kvs, T0, ws, nws, stream),
-                   "u2tok_decoder_decode_pre")
+        layer_ref = (d if w8 is None else w8)["layer_ref"]
+        _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                                              int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
+                                              vd.data_ptr(), kvs, T0, ws, nws, stream), "u2tok_decoder_decode_pre")
         if inplace:
             lay._commit(T0 + 1)
             K, V = kd[:, :, :T0 + 1], vd[:, :, :T0 + 1]
@@ -685,15 +687,10 @@ def _decode_step(self, x, pe, cache, window, pr):
             if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
                 K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
         kind, kv_start, _ = _pad_range(self._u2_prefill)
-        post_args = d["post"] if w8 is None else w8["post"]
-        if kind == "left":   # a left-padded batch: the batched decode attention with each sequence's first visible position
-            post = h.u2tok_decoder_decode_post_range if w8 is None else h.u2tok_decoder_decode_post_range_w8
-            _lib.check(post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(), K.shape[2], kvs,
-                            kv_start.data_ptr(), *post_args, out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post_range")
-        else:
-            post = h.u2tok_decoder_decode_post if w8 is None else h.u2tok_decoder_decode_post_w8
-            _lib.check(post(d["cfg_ref"], x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(), K.shape[2], kvs,
-                            *post_args, out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
+        left = kind == "left"   # a left-padded batch: the batched decode attention with each sequence's first visible position
+        _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
+                                               K.shape[2], kvs, int(left), kv_start.data_ptr() if left else None, out.data_ptr(), ws,
+                                               nws, stream), "u2tok_decoder_decode_post")
     if w8 is not None:
         w8_stats["decode" if stack.mask_ok else "padded_decode"] += 1
     return out
@@ -786,8 +783,8 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers without a window; a
     right-padded continuation, holes, window + padding and every other cache take the stock layers.
     fp8_decode=True (opt-in): a layer whose decode step qualifies today and whose E, Hq D and I are multiples of 64 runs the
-    step's four weight-streaming products on e4m3 copies of its weights with one fp32 scale per row (`_w8_state`,
-    u2tok_decoder_decode_*_w8: half the weight bytes per step, half the layer weights again in HBM; `w8_stats` counts these
+    step's four weight-streaming products on e4m3 copies of its weights with one fp32 scale per row (`_w8_state`, the scales
+    of its u2tok_decode_layer set: half the weight bytes per step, half the layer weights again in HBM; `w8_stats` counts these
     steps, `w8_weights(layer)` shows the copies); the products are exact on the quantised weights, the quantiser is what costs
     accuracy -- unmeasured on trained weights.  Every other layer and every other route read the original weights.  The six
     switches are set anew by every call.
