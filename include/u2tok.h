@@ -498,6 +498,13 @@ int u2tok_attention_gqa_bwd(const void* q, const void* k, const void* v, int64_t
                             const void* d_out, int64_t ld_o, int64_t bs_o, void* dq, void* dk, void* dv, int64_t ld_d, int64_t bs_d,
                             int32_t nb, int32_t S, int32_t Hq, int32_t Hkv, int32_t d, float scale, const int32_t* kv_len,
                             const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* The same backward at head dim 96 (Phi-3: 32 heads of 96), the argument list of u2tok_attention_gqa_bwd without d: the same
+ * launcher, checks, layout and workspace (u2tok_attention_gqa_bwd_workspace_bytes()); u2tok_attention_gqa_bwd itself takes
+ * 64 and 128 only. */
+int u2tok_attention_gqa_bwd_d96(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t bs_qkv, const void* out,
+                                const void* d_out, int64_t ld_o, int64_t bs_o, void* dq, void* dk, void* dv, int64_t ld_d,
+                                int64_t bs_d, int32_t nb, int32_t S, int32_t Hq, int32_t Hkv, float scale, const int32_t* kv_len,
+                                const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 /* RMSNorm backward (forward: u2tok_rmsnorm_bf16; x, dy, dres, dx dense (rows, C), C % 8 == 0, C <= 4096):
  *   dx = d/dx + dres (dres: the residual stream's gradient, or NULL);  dw (fp32, C) = sum_rows dy bf16(x rstd), added to dw when
  *   accumulate, in a fixed order.  workspace: u2tok_rmsnorm_bwd_workspace_bytes(). */

@@ -158,6 +158,8 @@ SIGNATURES = {
     "u2tok_attention_gqa_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "u2tok_attention_gqa_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
                                        _i32, _i32, _f32, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "u2tok_attention_gqa_bwd_d96": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32,
+                                           _i32, _i32, _f32, _vp, _vp, _i64, _vp, _sz, _vp]),
     "u2tok_rmsnorm_bwd_workspace_bytes": (_sz, [_i32, _i32]),
     "u2tok_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _sz, _i32, _vp]),
     "u2tok_qk_norm_rope_bwd_workspace_bytes": (_sz, [_i64, _i32]),

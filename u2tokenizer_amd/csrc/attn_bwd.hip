@@ -2,8 +2,8 @@
 //   out = softmax(q k^T * scale [+ mask]) v   ->   dq, dk, dv   from q, k, v, out, d_out (+ optionally the forward's lse)
 //   * the ViT blocks' d = 64 self-attention (MONAI SABlock, vit.py:100-105): equal heads, no mask
 //     (CAUSAL = false);
-//   * the decoder's causal grouped-query attention (training route of u2tokenizer_amd/decoder_train.py), d = 64 / 128
-//     (CAUSAL = true),
+//   * the decoder's causal grouped-query attention (training route of u2tokenizer_amd/decoder_train.py), d = 64 / 96 / 128
+//     (CAUSAL = true; 96 -- Phi-3's head dim -- through u2tok_attention_gqa_bwd_d96),
 // without the (S x S) probability / score-gradient tensors the unfused backward round-trips through HBM (ViT: 1.6 GB fp32 +
 // 0.8 GB bf16, several times per layer at S = 2049).  Two kernels, no atomics, bit-repeatable:
 //
@@ -22,7 +22,8 @@
 //                    the same row-major Q / dO tiles that feed S and dP.  lse / D come from the first kernel through the
 //                    workspace.
 //
-// Head dim DH = 64 or 128: tiles of 64 rows x DH, DH / 16 k steps, DH / 32 accumulator blocks (d = 128: the K, V fragments
+// Head dim DH = 64, 96 or 128: tiles of 64 rows x DH, DH / 16 k steps, DH / 32 accumulator blocks (d = 96: 192-byte rows with a
+// tile placement of their own, tile_off<96>, two waves per SIMD without scratch; d = 128: the K, V fragments
 // and the dK, dV accumulators are 192 registers -- the dK / dV kernel runs one wave per SIMD with the whole register file
 // instead of spilling at two).
 // The mask (CAUSAL): query i of sequence b sees key j iff j <= i and j < kv_len[b] (HF's causal mask built from a
@@ -68,6 +69,17 @@ __device__ __forceinline__ uint32_t tile_off(int row, int chunk) {
   const int p = (row >> 1) & 7;
   const int x = ((p & 1) << 2) | (p & 2) | ((p >> 2) & 1);
   return (uint32_t)(row * (DH * 2) + (((chunk & ~7) | ((chunk & 7) ^ x)) << 4));
+}
+// DH = 96: rows of 192 bytes = 12 chunks, which the XOR over 8 chunks would send out of the row (chunks 8-11 ^ 4..7 -> 12-15).
+// A 192-byte row starts 12 slots after its predecessor, so chunk c of row r sits in the 16-byte slot
+// 4 ((c >> 2) - r mod 4) + (c & 3) of the 256-byte bank row: the group of four chunks picks the 64-byte quarter and rows r,
+// r + 4, r + 8, r + 12 meet in one quarter.  XOR of the chunk's low two bits with (row >> 2) & 3 separates those four and stays
+// inside the group of four chunks: the 16 rows of a ds_read_b128 lane group at one chunk cover the 16 slots (4 rows mod 4 x 4
+// XOR values -- for 16 consecutive rows and for the hardware's groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} alike), and
+// a transpose read's 4 aligned rows (one XOR value, four quarters) x 4 chunks of one group cover them too.  Both conflict-free.
+template <>
+__device__ __forceinline__ uint32_t tile_off<96>(int row, int chunk) {
+  return (uint32_t)(row * 192 + ((chunk & ~3) << 4) + (((chunk & 3) ^ ((row >> 2) & 3)) << 4));
 }
 
 __device__ __forceinline__ float dot8(const uint4 a, const uint4 b) {
@@ -115,21 +127,32 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* tile, int lane, int nb, in
 // Staging of a [64][DH] tile, global -> registers (issued a tile ahead, under the MFMAs) -> LDS: the 256 threads carry
 // DH / 32 pieces of 16 bytes each, piece i of thread tid = chunk (i * 256 + tid) % (DH / 8) of row (i * 256 + tid) / (DH / 8).
 // Rows past the end re-read row S - 1; what they contribute is masked or never written.
+// DH = 96 (12 chunks per row, 768 = 3 x 256 pieces): thread tid carries chunks (tid & 3) + {0, 4, 8} of row tid >> 2 -- one
+// row, one global and one LDS address per thread with constant offsets between the pieces, where (i * 256 + tid) / 12 costs
+// three of each (the registers that decided between two waves per SIMD and scratch in the dK / dV kernel).
 // (Functions over array references, not lambdas capturing the arrays: with the lambdas the pieces went through scratch.)
 template <int DH>
 __device__ __forceinline__ void tile_load(bf16x8 (&r)[DH / 32], const bf16_t* base, int64_t ld, int row0, int S, int tid) {
 #pragma unroll
   for (int i = 0; i < DH / 32; ++i) {
-    const int cidx = i * 256 + tid;
-    r[i] = *reinterpret_cast<const bf16x8*>(base + (int64_t)min(row0 + cidx / (DH / 8), S - 1) * ld + cidx % (DH / 8) * 8);
+    if constexpr (DH == 96) {  // one row address per thread, the pieces 64 bytes apart
+      r[i] = *reinterpret_cast<const bf16x8*>(base + (int64_t)min(row0 + (tid >> 2), S - 1) * ld + (4 * i + (tid & 3)) * 8);
+    } else {
+      const int cidx = i * 256 + tid;
+      r[i] = *reinterpret_cast<const bf16x8*>(base + (int64_t)min(row0 + cidx / (DH / 8), S - 1) * ld + cidx % (DH / 8) * 8);
+    }
   }
 }
 template <int DH>
 __device__ __forceinline__ void tile_store(char* tile, const bf16x8 (&r)[DH / 32], int tid) {
 #pragma unroll
   for (int i = 0; i < DH / 32; ++i) {
-    const int cidx = i * 256 + tid;
-    *reinterpret_cast<bf16x8*>(tile + tile_off<DH>(cidx / (DH / 8), cidx % (DH / 8))) = r[i];
+    if constexpr (DH == 96) {
+      *reinterpret_cast<bf16x8*>(tile + tile_off<DH>(tid >> 2, 4 * i + (tid & 3))) = r[i];
+    } else {
+      const int cidx = i * 256 + tid;
+      *reinterpret_cast<bf16x8*>(tile + tile_off<DH>(cidx / (DH / 8), cidx % (DH / 8))) = r[i];
+    }
   }
 }
 
@@ -528,13 +551,13 @@ void launch_pair(Args& a, int nb, bool have_lse, double unit, double row_bytes, 
 }
 
 // The one launcher: validates what both entry points require, splits the workspace, fills Args, picks the instantiation.
-// causal = false is built for d = 64 and equal heads only (the ViT).
+// causal = false is built for d = 64 and equal heads only (the ViT); causal: d = 64 / 96 / 128 (96 through its own entry point).
 int attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
                   const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d, int64_t bs_d,
                   int nb, int S, int Hq, int Hkv, int d, float scale, bool causal, const int* kv_len, const float* lse_in,
                   int64_t lse_ld, void* workspace, size_t ws_bytes, hipStream_t stream) {
   if (!q || !k || !v || !o || !dout || !dq || !dk || !dv || !workspace) return U2_ERR_ARG;
-  if (d != 64 && (d != 128 || !causal)) return U2_ERR_ARG;
+  if (d != 64 && ((d != 96 && d != 128) || !causal)) return U2_ERR_ARG;
   if (nb <= 0 || S <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || (!causal && Hq != Hkv) || !(scale > 0.f)) return U2_ERR_ARG;
   if ((int64_t)nb * Hq * ((S + 127) / 128) > 0x7fffffff) return U2_ERR_ARG;
   if ((ld_qkv & 7) || (bs_qkv & 7) || (ld_o & 7) || (bs_o & 7) || (ld_d & 3) || (bs_d & 3)) return U2_ERR_ARG;
@@ -564,6 +587,7 @@ int attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_
   int e = U2_OK;
   if (!causal) launch_pair<64, false>(a, nb, lse_in != nullptr, unit, row_bytes, stream, &e);
   else if (d == 64) launch_pair<64, true>(a, nb, lse_in != nullptr, unit, row_bytes, stream, &e);
+  else if (d == 96) launch_pair<96, true>(a, nb, lse_in != nullptr, unit, row_bytes, stream, &e);
   else launch_pair<128, true>(a, nb, lse_in != nullptr, unit, row_bytes, stream, &e);
   return e;
 }
@@ -589,7 +613,17 @@ int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t
                       int64_t lse_ld, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   // (the batches of one view must not overlap; the ViT's entry point never asked)
   if (nb > 1 && (bs_qkv < (int64_t)S * ld_qkv || bs_o < (int64_t)S * ld_o || bs_d < (int64_t)S * ld_d)) return U2_ERR_ARG;
+  if (d != 64 && d != 128) return U2_ERR_ARG;  // (head dim 96 has its own entry point below)
   return attention_bwd(q, k, v, ld_qkv, bs_qkv, o, dout, ld_o, bs_o, dq, dk, dv, ld_d, bs_d, nb, S, Hq, Hkv, d, scale, true, kv_len,
+                       lse_in, lse_ld, workspace, workspace_bytes, stream);
+}
+
+int attention_gqa_bwd_d96(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
+                          const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
+                          int64_t bs_d, int nb, int S, int Hq, int Hkv, float scale, const int* kv_len, const float* lse_in,
+                          int64_t lse_ld, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (nb > 1 && (bs_qkv < (int64_t)S * ld_qkv || bs_o < (int64_t)S * ld_o || bs_d < (int64_t)S * ld_d)) return U2_ERR_ARG;
+  return attention_bwd(q, k, v, ld_qkv, bs_qkv, o, dout, ld_o, bs_o, dq, dk, dv, ld_d, bs_d, nb, S, Hq, Hkv, 96, scale, true, kv_len,
                        lse_in, lse_ld, workspace, workspace_bytes, stream);
 }
 

@@ -452,6 +452,13 @@ int u2tok_attention_gqa_bwd(const void* q, const void* k, const void* v, int64_t
   return attention_gqa_bwd(BF(q), BF(k), BF(v), ld_qkv, bs_qkv, BF(out), BF(d_out), ld_o, bs_o, BFW(dq), BFW(dk), BFW(dv), ld_d,
                            bs_d, nb, S, Hq, Hkv, d, scale, kv_len, lse, lse_ld, workspace, workspace_bytes, ST(stream));
 }
+int u2tok_attention_gqa_bwd_d96(const void* q, const void* k, const void* v, int64_t ld_qkv, int64_t bs_qkv, const void* out,
+                                const void* d_out, int64_t ld_o, int64_t bs_o, void* dq, void* dk, void* dv, int64_t ld_d,
+                                int64_t bs_d, int32_t nb, int32_t S, int32_t Hq, int32_t Hkv, float scale, const int32_t* kv_len,
+                                const float* lse, int64_t lse_ld, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return attention_gqa_bwd_d96(BF(q), BF(k), BF(v), ld_qkv, bs_qkv, BF(out), BF(d_out), ld_o, bs_o, BFW(dq), BFW(dk), BFW(dv), ld_d,
+                               bs_d, nb, S, Hq, Hkv, scale, kv_len, lse, lse_ld, workspace, workspace_bytes, ST(stream));
+}
 size_t u2tok_rmsnorm_bwd_workspace_bytes(int32_t rows, int32_t C) { return rmsnorm_bwd_workspace_bytes(rows, C); }
 int u2tok_rmsnorm_bwd(const void* x, const void* w, const void* dy, const void* dres, void* dx, float* dw, int32_t rows, int32_t C,
                       float eps, void* workspace, size_t workspace_bytes, int32_t accumulate, u2tok_stream_t stream) {

@@ -287,6 +287,11 @@ int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t
                       const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
                       int64_t bs_d, int nb, int S, int Hq, int Hkv, int d, float scale, const int* kv_len, const float* lse_in,
                       int64_t lse_ld, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// (head dim 96, Phi-3: the <96, true> instantiations through the same launcher and workspace; attention_gqa_bwd refuses 96)
+int attention_gqa_bwd_d96(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
+                          const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
+                          int64_t bs_d, int nb, int S, int Hq, int Hkv, float scale, const int* kv_len, const float* lse_in,
+                          int64_t lse_ld, void* workspace, size_t workspace_bytes, hipStream_t stream);
 size_t rmsnorm_bwd_workspace_bytes(int rows, int C);
 int rmsnorm_bwd(const bf16_t* x, const bf16_t* w, const bf16_t* dy, const bf16_t* dres, bf16_t* dx, float* dw, int rows, int C,
                 float eps, float* ws, size_t ws_bytes, int accumulate, hipStream_t st);

@@ -1,7 +1,8 @@
 """Training route of the decoder layers (opt-in): the layer's forward AND backward on the library's kernels.
 
 `enable_fused_prefill(model, train=True)` (prefill.py) -- or `config.u2_fused_decoder_training = True` on a u2 causal LM --
-makes a patched Llama / Qwen3 decoder layer that is called with grad enabled run as
+makes a patched Llama / Qwen3 decoder layer that is called with grad enabled (with `train_phi3=True` /
+`config.u2_fused_phi3_training = True` on top: a Phi-3 layer as well, and head dim 96 for all three) run as
 
     RMSNormFn -> PackedLinearFn (q|k|v) -> HeadNormRopeFn -> GqaAttentionFn -> PackedLinearFn (o, + residual)
     -> RMSNormFn -> PackedLinearFn (gate|up) -> SwiGLUFn -> PackedLinearFn (down, + residual)
@@ -13,13 +14,15 @@ torch.autograd.Functions over the C-ABI blocks, each saving what its backward ne
     receives its rows, accumulated in place into an existing `.grad` (a view into a flat optimizer bucket stays one);
   * the attention is the causal GQA kernel with per-sequence key lengths (u2tok_attention_gqa_ex, which also leaves the row
     statistics) and its flash backward (u2tok_attention_gqa_bwd: the causal instantiations of csrc/attn_bwd.hip's bwd_dq_kernel /
-    bwd_dkv_kernel, the pair the ViT's backward also runs), which writes dq | dk | dv straight into one packed gradient;
+    bwd_dkv_kernel, the pair the ViT's backward also runs; head dim 96 through u2tok_attention_gqa_bwd_d96), which writes
+    dq | dk | dv straight into one packed gradient;
   * RMSNorm, head norm + rotary and SwiGLU have their backward kernels in csrc/backward.hip (fixed-order fp32 weight gradients);
   * torch moves data and adds the residual stream's two gradient contributions.
 
 When a layer takes the route (prefill.route, decided on every call; everything else keeps the stock forward): bf16 on the
-GPU, every projection exactly nn.Linear with no hooks, no active attention dropout, head dim 64 or 128, no KV cache, no
-sliding window, and an attention mask that is causal with at most right padding.  The mask is read from the LAYER's own
+GPU, every projection exactly nn.Linear with no hooks, no active attention or residual dropout, head dim 64 or 128 (train_phi3:
+96 too), no KV cache, no sliding window on Llama / Qwen3 (train_phi3, Phi-3's `sliding_window` = W: calls of S <= W positions,
+where the window hides nothing), and an attention mask that is causal with at most right padding.  The mask is read from the LAYER's own
 `attention_mask` argument (the 4-D mask HF builds, or None; layer_mask_kv_len below) and the verdict is stored on that
 tensor: the recompute of non-reentrant gradient checkpointing calls the layer with the same argument objects, so it sees the
 key lengths of ITS forward, not those of whatever forward of the model ran last.
@@ -225,7 +228,11 @@ class SwiGLUFn(Function):
 # ------------------------------------------------------------------------------------------------ the layer
 def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
     """The layer's forward through the Functions above on its rows x2 (B S, E) -> (B, S, E); `lo` is the layer's layout
-    (prefill.py: its packed q|k|v and gate|up), cos / sin the rotary rows (B S, d), kv_len the key lengths or None."""
+    (prefill.py: its packed q|k|v and gate|up and the projections that own them -- three and two nn.Linear for Llama / Qwen3,
+    Phi-3's single qkv_proj / gate_up_proj, whose Parameter receives the packed dW whole), cos / sin the rotary rows (B S, d),
+    kv_len the key lengths or None.  Phi-3's stock layer rounds where Llama's does: the activation is up * bf16(silu(gate)) on
+    the halves of the gate_up_proj output (gate rows first), its two residual dropouts are inactive on this route (lo.ready)
+    and it has no head norm (HeadNormRopeFn's wq = None form)."""
     att, mlp = layer.self_attn, layer.mlp
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
@@ -233,7 +240,7 @@ def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
     Wqkv, bqkv = lo.qkv(layer)
     Wgu, bgu = lo.gate_up(layer)
     xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
-    qkv = packed_linear(xn, (att.q_proj, att.k_proj, att.v_proj), Wqkv, bqkv)
+    qkv = packed_linear(xn, lo.qkv_linears(layer), Wqkv.detach(), None if bqkv is None else bqkv.detach())
     qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
     qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv,
                                d, float(qn.variance_epsilon) if qn is not None else 1e-6)
@@ -241,7 +248,7 @@ def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
     h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
                       att.o_proj.bias.detach(), res=x2)
     hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
-    gu = packed_linear(hn, (mlp.gate_proj, mlp.up_proj), Wgu, bgu)
+    gu = packed_linear(hn, lo.gate_up_linears(layer), Wgu.detach(), None if bgu is None else bgu.detach())
     act = SwiGLUFn.apply(gu)
     out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
                         None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)

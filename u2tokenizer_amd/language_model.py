@@ -64,9 +64,12 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         for the training route of decoder_train.py (bf16).  Both switches, `config.u2_fused_padded_batches` (default False:
         padded batches on the no-grad routes) and `config.u2_fused_continued_prefill` (default False: new positions against a
         filled cache, prefills past the attention window) and `config.u2_fused_decode_fp8` (default False: the decode step's four
-        products on e4m3 copies of the weights, prefill.py `_w8_state`), are passed on as the config has them."""
+        products on e4m3 copies of the weights, prefill.py `_w8_state`), are passed on as the config has them, and so is
+        `config.u2_fused_phi3_training` (default False; it implies the training route: head dim 96 and the packed Phi-3 layout
+        on it, `enable_fused_prefill(..., train=True, train_phi3=True)`)."""
         grad = torch.is_grad_enabled()
-        train = bool(getattr(self.config, "u2_fused_decoder_training", False))
+        train_phi3 = bool(getattr(self.config, "u2_fused_phi3_training", False))   # (implies the training route)
+        train = bool(getattr(self.config, "u2_fused_decoder_training", False)) or train_phi3
         prefill = bool(getattr(self.config, "u2_fused_prefill", True))
         checked = self.__dict__.setdefault("_u2_fuse_checked", set())
         if grad in checked or not (train if grad else prefill):
@@ -82,6 +85,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                 padded["continued"] = True
             if bool(getattr(self.config, "u2_fused_decode_fp8", False)):   # (default False: decode steps on e4m3 weight copies)
                 padded["fp8_decode"] = True
+            if train_phi3:   # (default False: head dim 96 and the packed Phi-3 layout on the training route)
+                padded["train_phi3"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 
@@ -212,7 +217,8 @@ class u2Phi3ForCausalLM(_u2CausalLMMixin, Phi3ForCausalLM):
     same HIP path; the Phi-3 decoder layers (packed qkv_proj / gate_up_proj modules, used as they are) take the fused prefill
     and decode steps of prefill.py like the other two builds, behind the same `config.u2_fused_prefill` switch: head dim
     96 (Phi-3-mini) or 64 / 128, SiLU, rotary over the whole head.  With `sliding_window` = W a prefill of more than W
-    positions takes the stock layers; decode steps attend over the last W positions."""
+    positions takes the stock layers; decode steps attend over the last W positions.  `config.u2_fused_phi3_training = True`
+    (default False) trains the layers on the route of decoder_train.py (calls of S <= W positions)."""
     config_class = u2Phi3Config
 
     def __init__(self, config):

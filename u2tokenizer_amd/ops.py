@@ -1092,7 +1092,8 @@ def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor,
                       d_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal GQA flash backward (u2tok_attention_gqa_bwd): qkv (nb, S, (heads + 2 kv_heads) d) packed q | k | v (after the
     rotary embedding), out / d_out (nb, S, heads * d) -> the packed gradient d_qkv (nb, S, (heads + 2 kv_heads) d): dq | dk | dv
-    (written into `d_qkv` if given).  d = 64 or 128; kv_len / lse as attention_gqa_ex."""
+    (written into `d_qkv` if given).  d = 64 or 128, and 96 through u2tok_attention_gqa_bwd_d96; kv_len / lse as
+    attention_gqa_ex."""
     h = _lib.load_library()
     _need(qkv, ELEM, "qkv")
     nb, S, W = qkv.shape
@@ -1115,10 +1116,13 @@ def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor,
     ld, ldo = qkv.stride(1), heads * d
     qp, dp = qkv.data_ptr(), d_qkv.data_ptr()
     es = qkv.element_size()
-    _lib.check(h.u2tok_attention_gqa_bwd(qp, qp + heads * d * es, qp + (heads + kv_heads) * d * es, ld, S * ld, _ptr(out),
-                                         _ptr(d_out), ldo, S * ldo, dp, dp + heads * d * es, dp + (heads + kv_heads) * d * es, W,
-                                         S * W, nb, S, heads, kv_heads, d, float(scale), _ptr(kv_len), _ptr(lse), S if lse is not None else 0,
-                                         _ptr(ws), nbytes, _stream()), "u2tok_attention_gqa_bwd")
+    views = (qp, qp + heads * d * es, qp + (heads + kv_heads) * d * es, ld, S * ld, _ptr(out), _ptr(d_out), ldo, S * ldo,
+             dp, dp + heads * d * es, dp + (heads + kv_heads) * d * es, W, S * W, nb, S, heads, kv_heads)
+    rest = (float(scale), _ptr(kv_len), _ptr(lse), S if lse is not None else 0, _ptr(ws), nbytes, _stream())
+    if d == 96:
+        _lib.check(h.u2tok_attention_gqa_bwd_d96(*views, *rest), "u2tok_attention_gqa_bwd_d96")
+    else:
+        _lib.check(h.u2tok_attention_gqa_bwd(*views, d, *rest), "u2tok_attention_gqa_bwd")
     return d_qkv
 
 

@@ -36,6 +36,9 @@ keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a l
 continued=True: the band inside the attention kernel), and a decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
 DynamicSlidingWindowLayer that `generate` builds for such a config.
 
+`enable_fused_prefill(model, train=True)` (opt-in) sends a Llama / Qwen3 layer called with grad enabled through the training route of
+decoder_train.py at head dims 64 / 128; with `train_phi3=True` on top also at head dim 96 and for the packed Phi-3 layout
+(S <= W positions on a layer with a window).
 `route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
 step, the prefill or the stock forward.  The patch state is one `_LayerState` per layer and one `_StackState` per decoder stack.
 """
@@ -54,9 +57,11 @@ _DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
                                           ("DynamicCache", "DynamicLayer", "DynamicSlidingWindowLayer"))
 
 # What the kernels compute, per route: element types and head dims of the prefill / decode kernels, and of the backward
-# kernels the training route needs (bf16 only, no head dim 96)
+# kernels the training route needs (bf16 only; head dim 96 -- the flash backward's <96> kernels behind
+# u2tok_attention_gqa_bwd_d96 -- with the train_phi3 switch, which also admits the packed Phi-3 layout)
 INFER_DTYPES, INFER_HEAD_DIMS = (torch.bfloat16, torch.float16), (64, 96, 128)
 TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
+TRAIN_PHI3_HEAD_DIMS = (64, 96, 128)
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
 # would pass every parity check); the padded counts are the calls whose mask carried a key range
@@ -158,6 +163,19 @@ class _SplitLayout:
         return _pack((layer.mlp.gate_proj, layer.mlp.up_proj))
 
     @staticmethod
+    def qkv_linears(layer):
+        att = layer.self_attn
+        return (att.q_proj, att.k_proj, att.v_proj)
+
+    @staticmethod
+    def gate_up_linears(layer):
+        return (layer.mlp.gate_proj, layer.mlp.up_proj)
+
+    @staticmethod
+    def inter(layer) -> int:
+        return layer.mlp.gate_proj.weight.shape[0]
+
+    @staticmethod
     def window(layer):
         return None
 
@@ -169,7 +187,7 @@ class _SplitLayout:
 class _PackedLayout:
     """Phi-3: one qkv_proj (q, k, v rows) and one gate_up_proj (gate rows, then up rows) -- the packed layout itself."""
     KEY = (0, 1, 2, 3)
-    TRAINS = False
+    TRAINS = False       # ... and this one only with the train_phi3 switch (route)
 
     @staticmethod
     def projections(layer):
@@ -184,6 +202,18 @@ class _PackedLayout:
     def gate_up(layer):
         lin = layer.mlp.gate_up_proj
         return lin.weight, lin.bias
+
+    @staticmethod
+    def qkv_linears(layer):
+        return (layer.self_attn.qkv_proj,)
+
+    @staticmethod
+    def gate_up_linears(layer):
+        return (layer.mlp.gate_up_proj,)
+
+    @staticmethod
+    def inter(layer) -> int:
+        return layer.mlp.gate_up_proj.weight.shape[0] // 2
 
     @staticmethod
     def window(layer):
@@ -251,6 +281,7 @@ class _StackState:
     hook: object
     decode: bool = True
     train: bool = False
+    train_phi3: bool = False
     prefill: bool = True
     padded: bool = False
     continued: bool = False
@@ -313,11 +344,18 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             or not _is_stock(layer, pr) or not lo.ready(layer, att):
         return "stock", None
     if grad:
-        # no KV cache, no active attention dropout, widths the row kernels take, a mask the attention computes
-        if not lo.TRAINS or dtype not in TRAIN_DTYPES or att.head_dim not in TRAIN_HEAD_DIMS or kwargs.get("past_key_values") \
+        # a layout and a head dim the route computes (train_phi3: the packed Phi-3 layout and head dim 96 too), no KV cache, no
+        # active attention dropout, widths the row kernels take, no more positions than the attention window, a mask the
+        # attention computes
+        phi3 = stack.train_phi3
+        if not (lo.TRAINS or phi3) or dtype not in TRAIN_DTYPES \
+                or att.head_dim not in (TRAIN_PHI3_HEAD_DIMS if phi3 else TRAIN_HEAD_DIMS) or kwargs.get("past_key_values") \
                 is not None or (att.training and float(getattr(att, "attention_dropout", 0.0) or 0.0) > 0) \
-                or shape[2] % 8 or shape[2] > 4096 or layer.mlp.gate_proj.weight.shape[0] % 8 \
+                or shape[2] % 8 or shape[2] > 4096 or lo.inter(layer) % 8 \
                 or layer.input_layernorm.weight.dtype not in TRAIN_DTYPES:
+            return "stock", None
+        W = lo.window(layer)
+        if W is not None and shape[1] > W:   # (a call longer than the window: the band is not in the backward kernels)
             return "stock", None
         ok, kv_len = decoder_train.layer_mask_kv_len(kwargs.get("attention_mask"), shape[0], shape[1])
         return ("train", kv_len) if ok else ("stock", None)
@@ -766,7 +804,8 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
-                         padded: bool = False, continued: bool = False, fp8_decode: bool = False) -> int:
+                         padded: bool = False, continued: bool = False, fp8_decode: bool = False,
+                         train_phi3: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -786,8 +825,12 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     step's four weight-streaming products on e4m3 copies of its weights with one fp32 scale per row (`_w8_state`, the scales
     of its u2tok_decode_layer set: half the weight bytes per step, half the layer weights again in HBM; `w8_stats` counts these
     steps, `w8_weights(layer)` shows the copies); the products are exact on the quantised weights, the quantiser is what costs
-    accuracy -- unmeasured on trained weights.  Every other layer and every other route read the original weights.  The six
-    switches are set anew by every call.
+    accuracy -- unmeasured on trained weights.  Every other layer and every other route read the original weights.
+    train_phi3=True (opt-in, with train=True; nothing without it): the training route also takes head dim 96 (either layout;
+    the flash backward's <96> kernels, u2tok_attention_gqa_bwd_d96) and the packed Phi-3 layout at head dims 64 / 96 / 128
+    (qkv_proj / gate_up_proj as they are: one Parameter, one packed dW each) -- Phi-3-mini trains on the HIP layers.  The other
+    conditions of the route hold as they are; a layer with an attention window W trains while the call has S <= W positions,
+    a longer call takes the stock layers.  The seven switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -808,7 +851,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
     stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
-    stack.continued, stack.fp8 = bool(continued), bool(fp8_decode)
+    stack.continued, stack.fp8, stack.train_phi3 = bool(continued), bool(fp8_decode), bool(train_phi3)
     stack.pad = stack.pad_shape = None
     if not stack.fp8:   # (the copies go with the switch)
         for layer in layers:
