@@ -540,6 +540,29 @@ int u2tok_ce_lse_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, in
 int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, const float* lse,
                           const float* coef, u2tok_stream_t stream);
 
+/* ---- the sampling warper (u2tokenizer_amd/sampling.py; opt-in): temperature, top-k and top-p in one launch, without a sort -------
+ * logits / out: rows x V fp32 (4-byte aligned, leading dimensions ld_in, ld_out >= V, 64-bit row offsets); out may be logits.  The same
+ * code in both builds (no 16-bit element is involved).  top_k = 0: no top-k stage; top_p = 1: no top-p stage.  Per row:
+ *   1. z = x / temperature, one correctly rounded fp32 division (temperature = 1: z = x);
+ *   2. top-k, k = min(max(top_k, min_keep), V): z_i < (k-th largest z) is removed; ties with the k-th value stay; -0.0 = +0.0;
+ *      exact (counts only);
+ *   3. top-p over the survivors, with softmax probabilities (removed and -inf entries: 0): rank by value, among equal values the
+ *      HIGHER INDEX ranks higher (the order of a stable ascending sort, read from its end); token i stays iff the mass of the tokens
+ *      ranked strictly above it is < top_p, or fewer than min_keep tokens rank above it (transformers' `cumsum <= 1 - top_p` rule
+ *      written from the top);
+ *   4. out_i = z_i where kept, -inf elsewhere (-inf inputs stay -inf).
+ * The masses are summed as integers (exp(z - max) at 2^-40): the result does not depend on scheduling -- the same input gives the
+ * same bits.  A row holding NaN, +inf or nothing but -inf gets unspecified values in all of its V elements; the other rows of the
+ * call are not affected.
+ * workspace: u2tok_sample_warp_workspace_bytes(rows, V) bytes, 4-byte aligned (0 for rows < 1 or V < 2); afterwards it holds one record of
+ * eight uint32 per row: the boundary token's (key << 32 | index) composite (low word, high word), the bit from which it is resolved,
+ * the histogram passes taken, the top-k key bound, the number of tokens ranked at or above the boundary, two zeros.
+ * U2TOK_ERR_ARG: rows < 1, V < 2, temperature <= 0, top_p outside (0, 1], min_keep < 1, top_k < 0, ld < V, a null or misaligned
+ * pointer; U2TOK_ERR_WORKSPACE: workspace_bytes too small. */
+size_t u2tok_sample_warp_workspace_bytes(int32_t rows, int32_t V);
+int u2tok_sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
+                      int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,6 +395,11 @@ int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_
                           const float* coef, u2tok_stream_t stream) {
   return ce_grad_inplace(BFW(Z), ldz, rows, Vs, v0, labels, lse, coef, ST(stream));
 }
+size_t u2tok_sample_warp_workspace_bytes(int32_t rows, int32_t V) { return sample_warp_workspace_bytes(rows, V); }
+int u2tok_sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
+                      int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return sample_warp(logits, ld_in, out, ld_out, rows, V, temperature, top_k, top_p, min_keep, workspace, workspace_bytes, ST(stream));
+}
 int u2tok_adamw_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, const uint8_t* group, void* out_bf16,
                      int64_t n, const float* lr, const float* weight_decay, int32_t ngroups, float beta1, float beta2, float eps,
                      int32_t step, float grad_scale, const float* grad_coef, u2tok_stream_t stream) {

@@ -208,6 +208,10 @@ int ce_lse_update(const bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, co
                   hipStream_t stream);
 int ce_grad_inplace(bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, const float* lse, const float* coef,
                     hipStream_t stream);
+// sampling warper (sample.hip): temperature / top-k / top-p filtering of fp32 logits, one launch, no sort
+size_t sample_warp_workspace_bytes(int rows, int V);
+int sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int rows, int V, float temperature, int top_k,
+                float top_p, int min_keep, void* ws, size_t ws_bytes, hipStream_t stream);
 // sharded AdamW step (dp.py): see backward.hip
 struct AdamWArgs {
   float lr[8], wd[8];  // per parameter group

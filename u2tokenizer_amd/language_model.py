@@ -166,6 +166,16 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                use_cache=use_cache, **kwargs)
 
+    def _get_logits_processor(self, *args, **kwargs):
+        """transformers' processor list; with `config.u2_fused_sampling` (default False) its temperature / top-k / top-p run becomes one
+        FusedSamplingWarper (sampling.py: one HIP launch, no sort; beam sampling's min_tokens_to_keep = 2 included).  With the switch off
+        the list is returned untouched."""
+        processors = super()._get_logits_processor(*args, **kwargs)
+        if bool(getattr(self.config, "u2_fused_sampling", False)):
+            from .sampling import fuse_warpers
+            processors = fuse_warpers(processors)
+        return processors
+
     @torch.no_grad()
     def generate(self, images: Optional[torch.Tensor] = None, inputs: Optional[torch.Tensor] = None,
                  question_ids: Optional[torch.Tensor] = None, **kwargs) -> Any:

@@ -1229,3 +1229,28 @@ def ce_grad_inplace(z: torch.Tensor, v0: int, labels: torch.Tensor, lse: torch.T
     _lib.check(h.u2tok_ce_grad_inplace(_ptr(z), ldz, rows, Vs, int(v0), _ptr(labels), _ptr(_ce_f32(lse, rows, "lse")),
                                        _ptr(_ce_f32(coef, rows, "coef")), _stream()), "u2tok_ce_grad_inplace")
     return z
+
+
+@_guarded(infer=False)
+def sample_warp(scores: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_keep: int = 1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Temperature, top-k and top-p filtering of fp32 logits in one launch (u2tok_sample_warp; include/u2tok.h states the
+    semantics): scores (rows, V) fp32 with unit stride in the last dimension, V >= 2; top_k = 0 / top_p = 1 switch that stage
+    off.  -> out (rows, V) fp32: scores / temperature where kept, -inf elsewhere; `out` may be `scores` itself."""
+    h = _lib.load_library()
+    _need(scores, torch.float32, "scores")
+    if scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] < 1 or scores.shape[1] < 2:
+        raise RuntimeError(f"sample_warp: scores must be (rows >= 1, V >= 2) with a contiguous last dim, got {tuple(scores.shape)}")
+    rows, V = scores.shape
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=scores.device)
+    else:
+        _need(out, torch.float32, "out")
+        if out.shape != scores.shape or out.stride(1) != 1 or out.device != scores.device:
+            raise RuntimeError("sample_warp: out must be an fp32 (rows, V) tensor on the scores' device with a contiguous last dim")
+    nbytes = h.u2tok_sample_warp_workspace_bytes(rows, V)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=scores.device)
+    _lib.check(h.u2tok_sample_warp(_ptr(scores), scores.stride(0) if rows > 1 else V, _ptr(out), out.stride(0) if rows > 1 else V,
+                                   rows, V, float(temperature), int(top_k), float(top_p), int(min_keep), _ptr(ws), nbytes,
+                                   _stream()), "u2tok_sample_warp")
+    return out
