@@ -534,6 +534,17 @@ int u2tok_swiglu_bwd(const void* gu, const void* dact, void* dgu, int64_t rows, 
  * bit-repeatable. */
 int u2tok_ce_lse_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, float* m, float* l,
                         float* zt, u2tok_stream_t stream);
+/* u2tok_ce_lse_update with further per-row statistics folded into the same single read of the block (each optional; with all four
+ * pointers NULL this IS u2tok_ce_lse_update).  m, l, zt carry the same bits as u2tok_ce_lse_update writes, whatever else is asked for.
+ *   amax, aidx (fp32[rows], int64[rows]; both or neither): the running maximum logit and the FIRST global column v0 + j that holds
+ *     it -- larger value first, then smaller index, so the order in which slices are fed does not matter.  The caller sets
+ *     amax = -inf, aidx = INT64_MAX before the first slice; a row of -inf only ends at its first column.
+ *   zsum (fp32[rows]): the running sum of the row's logits; the caller sets 0.
+ *   l2 (fp32[rows]): the running sum of exp(2 (z - m)) against the same running maximum m; the caller sets 0.  After the last
+ *     slice log sum exp(2 z) = 2 m + log(l2).
+ * NaN logits are outside the contract.  No atomics, fixed order of every reduction: bit-repeatable. */
+int u2tok_ce_stats_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, float* m, float* l,
+                          float* zt, float* amax, int64_t* aidx, float* zsum, float* l2, u2tok_stream_t stream);
 /* In place:  Z[r][j] <- elem(coef[r] * (exp(float(Z[r][j]) - lse[r]) - [v0 + j == labels[r]])),  lse[r] the NATURAL-log sum of
  * exponentials of the whole row (m + log(l) above), coef[r] the upstream gradient of the row's loss: the element-type rounding
  * of the fp32 gradient of the fp32 logits, which is what F.cross_entropy(logits.float(), ...) hands back to lm_head. */

@@ -175,6 +175,7 @@ SIGNATURES = {
     "u2tok_flash_attention_d64_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
                                              _i32, _i32, _i32, _f32, _vp, _i64, _vp, _sz, _vp]),
     "u2tok_ce_lse_update": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "u2tok_ce_stats_update": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "u2tok_ce_grad_inplace": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "u2tok_sample_warp_workspace_bytes": (_sz, [_i32, _i32]),
     # logits, ld_in, out, ld_out, rows, V, temperature, top_k, top_p, min_keep, workspace, workspace_bytes, stream

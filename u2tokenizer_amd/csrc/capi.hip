@@ -391,6 +391,10 @@ int u2tok_ce_lse_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, in
                         float* zt, u2tok_stream_t stream) {
   return ce_lse_update(BF(Z), ldz, rows, Vs, v0, labels, m, l, zt, ST(stream));
 }
+int u2tok_ce_stats_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, float* m, float* l,
+                          float* zt, float* amax, int64_t* aidx, float* zsum, float* l2, u2tok_stream_t stream) {
+  return ce_stats_update(BF(Z), ldz, rows, Vs, v0, labels, m, l, zt, amax, aidx, zsum, l2, ST(stream));
+}
 int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, const float* lse,
                           const float* coef, u2tok_stream_t stream) {
   return ce_grad_inplace(BFW(Z), ldz, rows, Vs, v0, labels, lse, coef, ST(stream));

@@ -206,6 +206,9 @@ int rowdot_bf16(const bf16_t* a, const bf16_t* b, float* out, int64_t rows, int 
 // loss head (loss.hip): online log-sum-exp over one vocabulary slice of the logits, and the cross-entropy gradient written over them
 int ce_lse_update(const bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, float* m, float* l, float* zt,
                   hipStream_t stream);
+// the same pass with further per-row statistics: (amax, aidx) both or neither, zsum, l2 each or nullptr
+int ce_stats_update(const bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, float* m, float* l, float* zt,
+                    float* amax, int64_t* aidx, float* zsum, float* l2, hipStream_t stream);
 int ce_grad_inplace(bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const int64_t* labels, const float* lse, const float* coef,
                     hipStream_t stream);
 // sampling warper (sample.hip): temperature / top-k / top-p filtering of fp32 logits, one launch, no sort

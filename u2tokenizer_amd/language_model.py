@@ -94,7 +94,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         """Whether a call with labels takes the loss head of loss_head.py (`config.u2_fused_loss_head`, default False) instead
         of lm_head + ForCausalLMLoss: lm_head exactly nn.Linear, no bias, no hooks (a LoRA-wrapped or probed head keeps the stock
         path, as prefill._is_stock has it for the layers), bf16 on the GPU in a shape the head computes, the stock causal-LM
-        loss, all positions scored (no `logits_to_keep`) and a ModelOutput asked for."""
+        loss, all positions scored (no `logits_to_keep`) and a ModelOutput asked for.  On that route
+        `config.u2_fused_loss_head_predictions` (default False) puts the positions' argmax where the logits would be."""
         if not bool(getattr(self.config, "u2_fused_loss_head", False)):
             return False
         kwargs = kwargs or {}
@@ -132,6 +133,25 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                             inputs_embeds=inputs_embeds, use_cache=False, **kwargs).last_hidden_state
         return loss_head.token_logprobs(hidden, self.lm_head.weight, labels)
 
+    def token_stats(self, images: Optional[torch.Tensor], input_ids: torch.LongTensor, labels: torch.LongTensor,
+                    attention_mask: Optional[torch.Tensor] = None, question_ids: Optional[torch.LongTensor] = None,
+                    want=(), **kwargs):
+        """`token_logprobs` with the further per-position statistics of the logits named in `want` ("argmax", "logit_sum",
+        "lse2"), all from the one walk over the vocabulary: a loss_head.TokenStats, (B, S) each, whose `logprob` is
+        `token_logprobs`' result.  With want=("logit_sum", "lse2") it carries everything a DPO trainer's concatenated forward
+        reads from the logits (loss_head.dpo_outputs).  The same preparation and the same rule: the head must qualify
+        (_plain_lm_head), there is no fallback."""
+        from . import loss_head
+        self._maybe_fuse()
+        if not self._plain_lm_head():
+            raise RuntimeError("token_stats: needs a plain nn.Linear lm_head (no bias, hooks or adapters), bf16 on the GPU, with "
+                               "vocab % 8 == 0 and hidden % 64 == 0")
+        (input_ids, position_ids, attention_mask, _, inputs_embeds, labels) = self.prepare_inputs_for_multimodal(
+            input_ids, None, attention_mask, None, labels, images, question_ids)
+        hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                            inputs_embeds=inputs_embeds, use_cache=False, **kwargs).last_hidden_state
+        return loss_head.token_stats(hidden, self.lm_head.weight, labels, want=want)
+
     def forward(self, images: Optional[torch.FloatTensor] = None, input_ids: torch.LongTensor = None,
                 labels: Optional[torch.LongTensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 question_ids: Optional[torch.LongTensor] = None, position_ids: Optional[torch.LongTensor] = None,
@@ -156,11 +176,22 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
             outputs = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                  past_key_values=past_key_values, inputs_embeds=inputs_embeds, use_cache=use_cache, **kwargs)
             shifted = kwargs.get("shift_labels")
-            loss = loss_head.linear_cross_entropy(
-                outputs.last_hidden_state, self.lm_head.weight, labels if shifted is None else shifted,
-                ignore_index=kwargs.get("ignore_index", -100), num_items_in_batch=kwargs.get("num_items_in_batch"),
-                shift=shifted is None)
-            return CausalLMOutputWithPast(loss=loss, logits=None, past_key_values=outputs.past_key_values,
+            predictions = None
+            if bool(getattr(self.config, "u2_fused_loss_head_predictions", False)):
+                # (default False) the output's `logits` = the (B, S) int64 argmax of every scored position, from the same walk:
+                # position t holds the prediction for label t + 1, `ignore_index` where that label is ignored -- what an SFT
+                # evaluation compares as predictions[:, :-1] against labels[:, 1:] (loss_head.predictions_for_metrics)
+                st = loss_head.token_stats(
+                    outputs.last_hidden_state, self.lm_head.weight, labels if shifted is None else shifted, want=("argmax",),
+                    ignore_index=kwargs.get("ignore_index", -100), shift=shifted is None)
+                loss = loss_head.reduce_nll(-st.logprob, st.labelled, kwargs.get("num_items_in_batch"))
+                predictions = st.argmax
+            else:
+                loss = loss_head.linear_cross_entropy(
+                    outputs.last_hidden_state, self.lm_head.weight, labels if shifted is None else shifted,
+                    ignore_index=kwargs.get("ignore_index", -100), num_items_in_batch=kwargs.get("num_items_in_batch"),
+                    shift=shifted is None)
+            return CausalLMOutputWithPast(loss=loss, logits=predictions, past_key_values=outputs.past_key_values,
                                           hidden_states=outputs.hidden_states, attentions=outputs.attentions)
         return super().forward(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,

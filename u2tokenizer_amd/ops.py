@@ -1221,6 +1221,28 @@ def ce_lse_update(z: torch.Tensor, v0: int, labels: torch.Tensor, m: torch.Tenso
 
 
 @_guarded
+def ce_stats_update(z: torch.Tensor, v0: int, labels: torch.Tensor, m: torch.Tensor, l: torch.Tensor, zt: torch.Tensor,
+                    amax: Optional[torch.Tensor] = None, aidx: Optional[torch.Tensor] = None, zsum: Optional[torch.Tensor] = None,
+                    l2: Optional[torch.Tensor] = None) -> None:
+    """ce_lse_update with further per-row running statistics folded into the same read of the slice (u2tok_ce_stats_update), each
+    optional: (amax, aidx) fp32 / int64 (rows,), together -- the maximum logit and the first global column that holds it, -inf and
+    INT64_MAX before the first slice; zsum -- the sum of the logits, 0 before; l2 -- sum exp(2 (z - m)) against the same running
+    maximum, 0 before (log sum exp(2 z) = 2 m + log(l2) after the last slice).  m, l, zt come out bit-equal to ce_lse_update's."""
+    h = _lib.load_library()
+    rows, Vs, ldz = _ce_block(z, labels, "ce_stats_update")
+    if (amax is None) != (aidx is None):
+        raise RuntimeError("ce_stats_update: amax and aidx go together")
+    if aidx is not None:
+        _need(aidx, torch.int64, "aidx")
+        if aidx.shape != (rows,) or not aidx.is_contiguous():
+            raise RuntimeError(f"aidx: expected a dense int64 ({rows},) tensor")
+    opt = [None if t is None else _ptr(_ce_f32(t, rows, name)) for t, name in ((amax, "amax"), (zsum, "zsum"), (l2, "l2"))]
+    _lib.check(h.u2tok_ce_stats_update(_ptr(z), ldz, rows, Vs, int(v0), _ptr(labels), _ptr(_ce_f32(m, rows, "m")),
+                                       _ptr(_ce_f32(l, rows, "l")), _ptr(_ce_f32(zt, rows, "zt")), opt[0],
+                                       None if aidx is None else _ptr(aidx), opt[1], opt[2], _stream()), "u2tok_ce_stats_update")
+
+
+@_guarded
 def ce_grad_inplace(z: torch.Tensor, v0: int, labels: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     """z[r][j] <- coef[r] (exp(z[r][j] - lse[r]) - [v0 + j == labels[r]]) rounded to the element type, in place
     (u2tok_ce_grad_inplace; lse: natural log).  Returns z."""
