@@ -350,7 +350,11 @@ int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, i
  *         (u2tok_decode_attention: one launch for all B sequences and heads, plus one merge; Hq / Hkv <= 16) with a first visible
  *         cache position per sequence, kv_start (device int32[B]; NULL: all zeros) -- query b attends over positions
  *         kv_start[b] .. T - 1, the cache of a LEFT-padded batch.
- * B <= 16, D in {64, 96, 128}, E % 32 == 0, I % 32 == 0; biases may be NULL; same rounding points as the HF modules in bf16.
+ * B <= 64, D in {64, 96, 128}, E % 32 == 0, I % 32 == 0; biases may be NULL; same rounding points as the HF modules in bf16.
+ * 16 < B <= 64: the four products are u2tok_gemm_rows' / u2tok_gemm_rows_w8_wide's (below) -- the weights are still streamed once
+ * per step, and the products of sequence b have exactly the bits they have in a step of the sequences 16 (b / 16) .. min(B,
+ * 16 (b / 16) + 16) - 1 alone (the attention's key splits are a function of (B, Hkv, T), as for every B) --; post then requires batched != 0 (a launch pair per sequence would be 128 launches per layer), kv_start NULL
+ * or per sequence as before.  B > 64, and B > 16 with batched = 0: U2TOK_ERR_ARG before anything is launched.
  * A sliding-window layer (Phi-3: the last W positions) passes K / V advanced to its first visible position and T = W.
  * One workspace for both calls: u2tok_decoder_decode_workspace_bytes(cfg, T) bytes.
  * The layer's parameters travel in one descriptor, filled once per layer; the library keeps no pointer to it.  With the four
@@ -384,10 +388,25 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const u2tok_decode
  * flags of u2tok_gemm_bf16: 1 (bias[n]), 8 (+ R, ldr), 16 (fp32 C), or 512 ALONE (W8 = gate rows | up rows, N = 2 I, I % 8 == 0,
  * C (M, I) = bf16(silu(bf16(gate))) * bf16(up): the values of the product followed by u2tok_swiglu_bf16, bit for bit).
  * K % 64 == 0, lda % 8 == 0, ldw % 16 == 0, A and W8 16-byte aligned, scale non-null; U2TOK_ERR_ARG otherwise, nothing launched.
- * Bit-repeatable (partial sums are added in a fixed order). */
+ * Bit-repeatable (partial sums are added in a fixed order).
+ * u2tok_gemm_rows_w8_wide: the same product for 1 <= M <= 64, every other argument and refusal as above.  M <= 16: the same launch.
+ * 16 < M <= 64: each weight fragment is loaded once and feeds one MFMA per block of 16 rows; row m has exactly the bits it has as
+ * row m % 16 of the M <= 16 product on rows 16 (m / 16) .. min(M, 16 (m / 16) + 16) - 1 (same K slices, same accumulator chains,
+ * same order of the partial sums, same epilogue).  (u2tok_gemm_rows_w8 itself keeps refusing M > 16, as published.) */
 int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
                        int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
                        u2tok_stream_t stream);
+int u2tok_gemm_rows_w8_wide(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
+                            int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
+                            u2tok_stream_t stream);
+/* The few-rows (weight-streaming) product on weights in the element type, called directly instead of through u2tok_gemm_bf16's
+ * plan: C (M, N) = epilogue(sum_k A[m][k] W[n][k]), 1 <= M <= 64, W (N, K) with ldw elements between rows, K % 32 == 0, one batch
+ * entry; flags 1 (bias[n]), 8 (+ R, ldr), 16 (fp32 C), or 512 ALONE (W = gate rows | up rows, N = 2 I, I % 8 == 0, C (M, I) =
+ * bf16(silu(bf16(gate))) * bf16(up)); lda % 8 == 0, ldw % 8 == 0, A and W 16-byte aligned; U2TOK_ERR_ARG otherwise, nothing
+ * launched.  M <= 16: the kernel u2tok_gemm_bf16 picks for such a product, bit for bit.  16 < M <= 64: the block-of-16 contract
+ * of u2tok_gemm_rows_w8_wide.  Bit-repeatable. */
+int u2tok_gemm_rows(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K,
+                    int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream);
 /* Batched decode attention: out[b] = softmax(q[b] K[b]^T scale over keys kv_start[b] <= j < T) V[b] for B sequences of ONE query
  * row each.  q / out: (B, Hq * D) rows, ldq / ldo elements apart (head h at column h * D); K / V: (B, Hkv, T, D), kv_stride
  * elements between (batch, kv head) entries (0: dense, T * D) -- an append-in-place buffer or the dense cache; D in {64, 96, 128},

@@ -195,7 +195,7 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 }
 
 // ------------------------------------------------------------------------------------------------ one decode step of a layer
-// The two halves of a decoder layer's decode step (B <= 16 new tokens against the KV cache), each ONE call for the host: the
+// The two halves of a decoder layer's decode step (B <= 64 new tokens against the KV cache), each ONE call for the host: the
 // step `generate` repeats up to 768 times per report is bound by the host's launch rate when every kernel is its own Python
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
@@ -216,7 +216,7 @@ static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* 
   g.M = rows; g.N = out; g.K = in;
   g.lda = ldx; g.ldb = in; g.ldc = ldy; g.ldr = ldr;
   g.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-  return gemm_bf16(g, st);
+  return rows > 16 ? gemm_rows(g, st) : gemm_bf16(g, st);
 }
 
 // What the e4m3 products ask of a step before anything is launched: a scale per product, K % 64 == 0 for all four, 16-byte
@@ -245,7 +245,7 @@ size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
                        int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
                        hipStream_t st) {
-  if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
+  if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
   const int ns = scales_set(l);
   if (ns != 0 && (ns != 4 || !w8_step_ok(c, &l.Wqkv, &l.scale_qkv, 1))) return U2_ERR_ARG;
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
@@ -261,11 +261,12 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
-// (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence)
+// (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence -- B <= 16
+// only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG)
 int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
                         int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
                         hipStream_t st) {
-  if (c.B <= 0 || c.B > 16 || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
+  if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
       !ws)
     return U2_ERR_ARG;
   if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;

@@ -491,6 +491,46 @@ static int gemm_step(const GemmDesc& d, const GemmStep& s, void* partial, hipStr
   return launch_status();
 }
 
+// The few-rows product outside the plan (kernels.h): what the decode step of more than 16 sequences calls directly -- the plan of an
+// M = 17 .. 64 product is a tile kernel's, pinned for the training path.
+int gemm_rows_check(const GemmDesc& d) {
+  const bool pair = d.flags & GEMM_SWIGLU;
+  if (!d.A || !d.B || !d.C || d.M <= 0 || d.M > 64 || d.N <= 0 || d.K <= 0 || (d.K & 31) || d.nz != 1) return U2_ERR_ARG;
+  if (d.flags & ~(GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_SWIGLU)) return U2_ERR_ARG;
+  if (pair && (d.flags != GEMM_SWIGLU || (d.N & 15))) return U2_ERR_ARG;  // gate | up: N = 2 I, I % 8 == 0
+  if (((d.flags & GEMM_BIAS_N) && !d.bias) || ((d.flags & GEMM_RESIDUAL) && (!d.R || d.ldr < d.N))) return U2_ERR_ARG;
+  if (d.lda < d.K || (d.lda & 7) || d.ldb < d.K || (d.ldb & 7) || d.ldc < (pair ? d.N >> 1 : d.N)) return U2_ERR_ARG;
+  if ((((uintptr_t)d.A | (uintptr_t)d.B) & 15) || ((uintptr_t)d.C & ((d.flags & GEMM_OUT_F32) ? 3 : 1))) return U2_ERR_ARG;
+  return U2_OK;
+}
+
+int gemm_rows(const GemmDesc& d, hipStream_t stream) {
+  const int e = gemm_rows_check(d);
+  if (e != U2_OK) return e;
+  if (d.M > 16) {
+    RowsW8Args a;
+    a.A = d.A; a.W = reinterpret_cast<const uint8_t*>(d.B); a.C = d.C; a.bias = d.bias; a.R = d.R;
+    a.M = d.M; a.N = d.N; a.K = d.K;
+    a.lda = d.lda; a.ldw = d.ldb; a.ldc = d.ldc; a.ldr = d.ldr;
+    a.flags = d.flags;
+    return gemm_rows64_launch(a, false, stream);
+  }
+  GemmDesc g;  // (the fields the product has, everything else as constructed: alpha = 1, no column split)
+  g.A = d.A; g.B = d.B; g.C = d.C; g.bias = d.bias; g.R = d.R;
+  g.M = d.M; g.N = d.N; g.K = d.K;
+  g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.ldr = d.ldr;
+  g.flags = d.flags;
+  const bool pair = d.flags & GEMM_SWIGLU;
+  const double out_b = pair ? 2.0 * d.M * (d.N >> 1) : ((d.flags & GEMM_OUT_F32) ? 4.0 : 2.0) * d.M * d.N;
+  ProfScope ps(PROF_GEMM, 2.0 * d.M * d.N * d.K, stream,
+               2.0 * d.M * d.K + 2.0 * d.N * d.K + out_b + ((d.flags & GEMM_RESIDUAL) ? 2.0 * d.M * d.N : 0.0));
+  const int nw = rows16_slices(d.K >> 5);
+  void (*const k[2][3])(GemmDesc) = {{gemm_rows16_kernel<16, true>, gemm_rows16_kernel<8, true>, gemm_rows16_kernel<4, true>},
+                                     {gemm_rows16_kernel<16>, gemm_rows16_kernel<8>, gemm_rows16_kernel<4>}};
+  hipLaunchKernelGGL(k[!pair][2 - nw / 8], dim3((unsigned)cdiv(d.N, 16)), dim3(nw * 64), 0, stream, g);
+  return launch_status();
+}
+
 int gemm_bf16(GemmDesc d, hipStream_t stream) {
   const int flags = d.flags;
   const Scratch sc = ctx().scratch_of(stream);

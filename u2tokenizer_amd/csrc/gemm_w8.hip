@@ -1,4 +1,4 @@
-// The few-rows product (M <= 16 rows against N x K weights; gemm.hip: gemm_rows16_kernel) on e4m3 weights with one fp32 scale per
+// The few-rows product (M <= 16 rows against N x K weights; gemm.hip: gemm_rows16_kernel; 17 .. 64 rows: gemm_rows64.hip) on e4m3 weights with one fp32 scale per
 // weight row -- the decode step's four weight-streaming products read half the bytes (DESIGN f3: the step is bound by them).
 // Weight-only: activations stay in the element type, the MFMA is the element type's v_mfma_f32_16x16x32 on weights widened in
 // registers (rows16_w8.h), so the product is exactly x . dequant(W8) in fp32 accumulation.  A launcher of its own (RowsW8Args),
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows16_w8_kernel(RowsW8Args a) {
 
 int gemm_rows_w8_check(const RowsW8Args& a) {
   const bool pair = a.flags & GEMM_SWIGLU;
-  if (!a.A || !a.W || !a.scale || !a.C || a.M <= 0 || a.M > 16 || a.N <= 0 || a.K <= 0 || (a.K & 63)) return U2_ERR_ARG;
+  if (!a.A || !a.W || !a.scale || !a.C || a.M <= 0 || a.M > 64 || a.N <= 0 || a.K <= 0 || (a.K & 63)) return U2_ERR_ARG;
   if (a.flags & ~(GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_SWIGLU)) return U2_ERR_ARG;
   if (pair && (a.flags != GEMM_SWIGLU || (a.N & 15))) return U2_ERR_ARG;  // gate | up: N = 2 I, I % 8 == 0
   if (((a.flags & GEMM_BIAS_N) && !a.bias) || ((a.flags & GEMM_RESIDUAL) && (!a.R || a.ldr < a.N))) return U2_ERR_ARG;
@@ -69,6 +69,7 @@ int gemm_rows_w8_check(const RowsW8Args& a) {
 int gemm_rows_w8(const RowsW8Args& a, hipStream_t stream) {
   const int e = gemm_rows_w8_check(a);
   if (e != U2_OK) return e;
+  if (a.M > 16) return gemm_rows64_launch(a, true, stream);  // 17 .. 64 rows: the same arithmetic per block of 16 (rows64.h)
   const bool pair = a.flags & GEMM_SWIGLU;
   const int nw = rows16_slices(a.K >> 6);  // from the double steps, as rows16_slices picks it from the steps of the 16-bit product
   const dim3 grid((unsigned)(pair ? cdiv(a.N >> 1, 8) : cdiv(a.N, 16)));

@@ -101,8 +101,9 @@ void gemm_plan_format(const GemmPlan& p, char* buf, size_t n);  // " | <kernel> 
 int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);  // gemm_skinny.hip
 int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);      // gemm_bt.hip
 
-// The few-rows product on e4m3 weights (gemm_w8.hip; arithmetic: rows16_w8.h): C = epilogue(scale[n] * A . e4m3(W)^T), M <= 16,
-// K % 64 == 0, 16-byte aligned A / W rows.  gemm_rows_w8_check: the argument check alone (U2_ERR_ARG, nothing launched).
+// The few-rows product on e4m3 weights (gemm_w8.hip; arithmetic: rows16_w8.h): C = epilogue(scale[n] * A . e4m3(W)^T), M <= 64
+// (M > 16: gemm_rows64.hip, each block of 16 rows with the bits of the M <= 16 product on it), K % 64 == 0, 16-byte aligned A / W
+// rows.  gemm_rows_w8_check: the argument check alone (U2_ERR_ARG, nothing launched).
 struct RowsW8Args {        // outside GemmDesc and the plan
   const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
   const uint8_t* W = nullptr;    // [N][K] e4m3 codes, leading dim ldw (bytes)
@@ -116,6 +117,13 @@ struct RowsW8Args {        // outside GemmDesc and the plan
 };
 int gemm_rows_w8_check(const RowsW8Args& a);
 int gemm_rows_w8(const RowsW8Args& a, hipStream_t stream);
+// The few-rows product on element-type weights outside the plan (gemm.hip): d.A (M, K), d.B (N, K), 1 <= M <= 64, K % 32 == 0, one
+// batch entry, flags GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 or GEMM_SWIGLU alone; every other field of d as constructed.
+// M <= 16: gemm_rows16_kernel as the plan launches it; M > 16: gemm_rows64.hip.  gemm_rows_check: the argument check alone.
+int gemm_rows_check(const GemmDesc& d);
+int gemm_rows(const GemmDesc& d, hipStream_t stream);
+// 16 < a.M <= 64 (gemm_rows64.hip; arguments checked by the two callers above); w8 = false: a.W / a.ldw are elements, no scale
+int gemm_rows64_launch(const RowsW8Args& a, bool w8, hipStream_t stream);
 
 // ------------------------------------------------------------------ row ops (rowops.hip)
 // y[b][r][:] = LayerNorm(x[b][r][:] (+ res[b][r][:])) * w + bias   (bf16 in/out, fp32 math)

@@ -64,7 +64,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         for the training route of decoder_train.py (bf16).  Both switches, `config.u2_fused_padded_batches` (default False:
         padded batches on the no-grad routes) and `config.u2_fused_continued_prefill` (default False: new positions against a
         filled cache, prefills past the attention window) and `config.u2_fused_decode_fp8` (default False: the decode step's four
-        products on e4m3 copies of the weights, prefill.py `_w8_state`), are passed on as the config has them, and so is
+        products on e4m3 copies of the weights, prefill.py `_w8_state`) and `config.u2_fused_wide_decode` (default False: decode
+        steps of 17 .. 64 sequences on the fused step), are passed on as the config has them, and so is
         `config.u2_fused_phi3_training` (default False; it implies the training route: head dim 96 and the packed Phi-3 layout
         on it, `enable_fused_prefill(..., train=True, train_phi3=True)`)."""
         grad = torch.is_grad_enabled()
@@ -85,6 +86,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                 padded["continued"] = True
             if bool(getattr(self.config, "u2_fused_decode_fp8", False)):   # (default False: decode steps on e4m3 weight copies)
                 padded["fp8_decode"] = True
+            if bool(getattr(self.config, "u2_fused_wide_decode", False)):   # (default False: decode steps of 17 .. 64 sequences)
+                padded["wide_decode"] = True
             if train_phi3:   # (default False: head dim 96 and the packed Phi-3 layout on the training route)
                 padded["train_phi3"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)

@@ -738,8 +738,9 @@ def snap_fp8_(module):
 @_guarded
 def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias=None, residual=None, out_f32=False,
                  swiglu=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(M <= 16, N) = epilogue(scale[n] * a @ e4m3(w8)^T) for w8 (N, K) torch.float8_e4m3fn and scale (N,) fp32
-    (u2tok_gemm_rows_w8: the decode step's weight-streaming product on 1-byte weights, fp32 accumulation).  swiglu: w8 = gate
+    """(M <= 64, N) = epilogue(scale[n] * a @ e4m3(w8)^T) for w8 (N, K) torch.float8_e4m3fn and scale (N,) fp32
+    (u2tok_gemm_rows_w8, for M > 16 u2tok_gemm_rows_w8_wide: the decode step's weight-streaming product on 1-byte weights, fp32
+    accumulation; each block of 16 rows has the bits of the M <= 16 product on it).  swiglu: w8 = gate
     rows | up rows -> (M, N / 2) = silu(gate) * up.  `out` / `residual` may be row-strided views (unit column stride)."""
     h = _lib.load_library()
     _need(a, ELEM, "A")
@@ -769,9 +770,50 @@ def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias
         if residual.shape != (M, N) or residual.stride(1) != 1:
             raise RuntimeError("gemm_rows_w8: residual must be (M, N) with unit column stride")
         ldr = residual.stride(0)
-    st = h.u2tok_gemm_rows_w8(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K,
-                              out.stride(0), ldr, flags, _stream())
-    _lib.check(st, "u2tok_gemm_rows_w8")
+    fn = h.u2tok_gemm_rows_w8_wide if M > 16 else h.u2tok_gemm_rows_w8
+    st = fn(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K, out.stride(0), ldr,
+            flags, _stream())
+    _lib.check(st, "u2tok_gemm_rows_w8_wide" if M > 16 else "u2tok_gemm_rows_w8")
+    return out
+
+
+@_guarded
+def gemm_rows(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, out_f32=False, swiglu=False,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(M <= 64, N) = epilogue(a @ w^T) for w (N, K) in the element type through the few-rows (weight-streaming) kernels, called
+    directly (u2tok_gemm_rows) instead of through the plan of `gemm`: M <= 16 the kernel the plan picks, 16 < M <= 64 the
+    multi-block kernel whose every block of 16 rows has the bits of the M <= 16 product on it.  K % 32 == 0.  swiglu: w = gate
+    rows | up rows -> (M, N / 2) = silu(gate) * up.  `w`, `out` and `residual` may be row-strided views (unit column stride)."""
+    h = _lib.load_library()
+    _need(a, ELEM, "A"), _need(w, ELEM, "W")
+    a2 = a.reshape(-1, a.shape[-1])
+    if a2.stride(1) != 1:
+        a2 = a2.contiguous()
+    if w.dim() != 2 or w.stride(1) != 1:
+        w = w.contiguous()
+    M, K = a2.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise RuntimeError(f"gemm_rows: shapes A {tuple(a2.shape)}, W {tuple(w.shape)}")
+    cols = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
+    if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
+        raise RuntimeError("gemm_rows: out must be (M, columns) with unit column stride in the output type")
+    flags = GEMM_SWIGLU if swiglu else (GEMM_OUT_F32 if out_f32 else 0)
+    ldr = 0
+    if bias is not None:
+        flags |= GEMM_BIAS_N
+        bias = _need(bias, ELEM, "bias").contiguous()
+    if residual is not None:
+        flags |= GEMM_RESIDUAL
+        _need(residual, ELEM, "residual")
+        if residual.shape != (M, N) or residual.stride(1) != 1:
+            raise RuntimeError("gemm_rows: residual must be (M, N) with unit column stride")
+        ldr = residual.stride(0)
+    st = h.u2tok_gemm_rows(_ptr(a2), _ptr(w), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), w.stride(0),
+                           out.stride(0), ldr, flags, _stream())
+    _lib.check(st, "u2tok_gemm_rows")
     return out
 
 

@@ -13,7 +13,7 @@ padding) runs the layer as
 
 on the library's MFMA GEMMs (include/u2tok.h: u2tok_gemm_bf16), the fused attention kernel of tokattn.hip
 (u2tok_attention_gqa: grouped-query heads, causal mask, scores never in HBM) and the row kernels of decoder.hip, and for a
-DECODE step (one new position per sequence, batch <= 16, a plain HF DynamicCache) as two library calls around the cache update
+DECODE step (one new position per sequence, batch <= 16 -- `wide_decode=True`, opt-in: <= 64 --, a plain HF DynamicCache) as two library calls around the cache update
 (`_decode_step`: weight-streaming few-rows products, attention with the keys split over workgroups).  Everything else --
 training, CPU tensors, sliding-window layers, padded batches, other cache types -- takes the layer's original forward.
 `enable_fused_prefill(model, padded=True)` (opt-in) keeps LEFT- and RIGHT-padded batches on the fused prefill (`pad_rule`: a key
@@ -71,6 +71,8 @@ stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
 extend_stats = {"extend": 0, "padded_extend": 0}
 # ... and the decode steps (counted in `stats` as well) that really ran on e4m3 weights (fp8_decode=True, `_w8_state`)
 w8_stats = {"decode": 0, "padded_decode": 0}
+# ... and the decode steps (counted in `stats` as well) of more than 16 sequences (wide_decode=True), per layer call
+wide_stats = {"decode": 0, "padded_decode": 0}
 
 
 def pad_rule(mask):
@@ -286,6 +288,7 @@ class _StackState:
     padded: bool = False
     continued: bool = False
     fp8: bool = False
+    wide: bool = False
     mask_ok: bool = True
     pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
     pad_shape: tuple = None    # ... and that mask's (B, columns)
@@ -376,9 +379,11 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             return "stock", None
         if keys != shape[1] and kind != "left":   # (a right-padded continuation: the new keys would not follow the old ones)
             return "stock", None
-    if shape[1] == 1:   # one new position per sequence, batch <= 16, against a plain DynamicCache
-        ok = shape[0] <= 16 and stack.decode and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
-        if kind is not None and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
+    if shape[1] == 1:   # one new position per sequence, batch <= 16 (wide_decode=True: <= 64), against a plain DynamicCache
+        wide = shape[0] > 16   # (17 .. 64 sequences: the few-rows product on up to four blocks of 16 rows, always the batched attention)
+        ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode \
+            and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
+        if (kind is not None or wide) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
             ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
     # an empty cache and no more positions than the window: the plain causal prefill
@@ -675,14 +680,17 @@ def w8_weights(layer):
 
 
 def _decode_step(self, x, pe, cache, window, pr):
-    """One decode step of a layer (B <= 16 new tokens, one each, against the KV cache): the step `generate` repeats up to 768
+    """One decode step of a layer (B <= 16 new tokens -- wide_decode=True: B <= 64 --, one each, against the KV cache): the step `generate` repeats up to 768
     times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
     few-rows GEMM (gemm.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
     fused kernel with the KEYS split over workgroups (batch x kv-head entries of (T, d) keys, the query heads of a group as its
     heads).  TWO library calls per layer (u2tok_decoder_decode_pre / _post, 10 launches) around the cache's own `update`: with a
     Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels).
     window = W (a sliding-window layer): the query attends over the last min(T, W) positions -- an offset into the cache
-    buffers, the same kernels."""
+    buffers, the same kernels.
+    B > 16 (the route's wide_decode switch): the same two calls; the library runs the four products on its 17 .. 64-row form of
+    the few-rows kernel (csrc/gemm_rows64.hip: the weights are still read once per step, and each block of 16 sequences gets the
+    bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch."""
     from . import _lib
     att = self.self_attn
     B, _, E = x.shape
@@ -727,10 +735,12 @@ def _decode_step(self, x, pe, cache, window, pr):
         kind, kv_start, _ = _pad_range(self._u2_prefill)
         left = kind == "left"   # a left-padded batch: the batched decode attention with each sequence's first visible position
         _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
-                                               K.shape[2], kvs, int(left), kv_start.data_ptr() if left else None, out.data_ptr(), ws,
-                                               nws, stream), "u2tok_decoder_decode_post")
+                                               K.shape[2], kvs, int(left or B > 16), kv_start.data_ptr() if left else None,
+                                               out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
     if w8 is not None:
         w8_stats["decode" if stack.mask_ok else "padded_decode"] += 1
+    if B > 16:
+        wide_stats["decode" if stack.mask_ok else "padded_decode"] += 1
     return out
 
 
@@ -805,7 +815,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
-                         train_phi3: bool = False) -> int:
+                         train_phi3: bool = False, wide_decode: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -830,7 +840,14 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     the flash backward's <96> kernels, u2tok_attention_gqa_bwd_d96) and the packed Phi-3 layout at head dims 64 / 96 / 128
     (qkv_proj / gate_up_proj as they are: one Parameter, one packed dW each) -- Phi-3-mini trains on the HIP layers.  The other
     conditions of the route hold as they are; a layer with an attention window W trains while the call has S <= W positions,
-    a longer call takes the stock layers.  The seven switches are set anew by every call.
+    a longer call takes the stock layers.
+    wide_decode=True (opt-in): a decode step of 17 .. 64 sequences (`generate` over a dataset, DPO's generate_during_eval) keeps
+    the fused step under the conditions of today's -- plus at most 16 query heads per kv head, because such a step always takes
+    the batched decode attention; a left-padded one still needs padded=True, a right-padded one stays stock -- instead of the
+    stock layers: the weights are streamed once per step however many sequences share it, each block of 16 sequences computes
+    the bits it would in a step of its own (csrc/rows64.h), and it composes with fp8_decode, Phi-3 layers and the
+    append-in-place cache.  `wide_stats` counts these steps per layer call.  Off, batch 17 takes the stock layers as before.
+    The eight switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -852,6 +869,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
     stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
     stack.continued, stack.fp8, stack.train_phi3 = bool(continued), bool(fp8_decode), bool(train_phi3)
+    stack.wide = bool(wide_decode)
     stack.pad = stack.pad_shape = None
     if not stack.fp8:   # (the copies go with the switch)
         for layer in layers:
