@@ -69,7 +69,7 @@ u2tok_ctx_t u2tok_ctx_get_current(void);     /* NULL when the thread uses the de
     stream for the TTA k|v projections},
     "vit_vt_epilogue" {1: the ViT's q|k|v product leaves V^T (the flash kernel's operand) from its own V tiles, 0: a transpose launch},
     "tok_flash" {1: the tokenizer's attention cores run the fused kernel of u2tok_tok_attention, 0: GEMM -> softmax -> GEMM},
-    "tok_wide" {1: head dims 256 / 512 of that kernel run its 8-wave form (a wave pair per 16-query block, two waves per SIMD),
+    "tok_wide" {1: head dims 256 / 512 (not 384) of that kernel run its 8-wave form (a wave pair per 16-query block, two waves per SIMD),
     0: the 4-wave form},
     "profile" {0, 1} */
 int u2tok_set_option(const char* name, int value);
@@ -268,6 +268,7 @@ int u2tok_gather_rows(const void* x, const int64_t* idx, void* out, int32_t B, i
 /* ws: B*3*16*ceil(E/256) floats (only read/written when gate_w != null) */
 int u2tok_multiscale_pool(const void* x, void* out, int32_t B, int32_t k, int32_t E, const void* gate_w,
                           const void* gate_b, float* ws, u2tok_stream_t stream);
+/* attention over the chunk axis (svr.py:31-36) of rows in (b t n) order: T <= 16, d = E / H in {64, 128, 256, 384, 512} */
 int u2tok_temporal_attention(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T,
                              int32_t N, int32_t H, int32_t d, int64_t ld_qkv, int64_t ld_out, float scale,
                              const void* rel_bias, int32_t max_len, u2tok_stream_t stream);
@@ -289,9 +290,9 @@ int u2tok_flash_attention_d64_lse(const void* q, const void* k, const void* vt, 
 /* Fused attention core of the tokenizer's attention modules -- RelativeMultiheadAttention (rma.py:60-75: + relative_bias
  * [j - i + max_len - 1][h], bf16 (2 max_len - 1, H)), RotaryMultiheadAttention (rope.py:82-86), MultiHeadCrossAttention /
  * LinearAggregation (tta.py:55-61; rel_bias NULL):  out = softmax(q k^T scale + bias) v  per (batch, head), scores and
- * probabilities never in HBM.  Row r of batch b at ptr + b*?_bs + r*ld?, head h at column h*d, d in {64, 96, 128, 256, 512};
- * q / k / v 16-byte aligned with strides % 8 == 0, out 8-byte aligned with strides % 4 == 0; with rel_bias: Sq, Skv <=
- * max_len.  splits: 0 = heuristic, n > 0 = cut the keys into n ranges (fp32 partial sums in `workspace`:
+ * probabilities never in HBM.  Row r of batch b at ptr + b*?_bs + r*ld?, head h at column h*d, d in {64, 96, 128, 256, 384, 512}
+ * (384 = E / 8 at E = 3072; it runs the 4-wave kernel whatever "tok_wide" says); q / k / v 16-byte aligned with strides
+ * % 8 == 0, out 8-byte aligned with strides % 4 == 0; with rel_bias: Sq, Skv <= max_len.  splits: 0 = heuristic, n > 0 = cut the keys into n ranges (fp32 partial sums in `workspace`:
  * u2tok_tok_attention_workspace_bytes, 16-byte aligned; NULL = unsplit).  U2TOK_ERR_ARG for shapes it does not take. */
 size_t u2tok_tok_attention_workspace_bytes(int32_t nb, int32_t H, int32_t Sq, int32_t Skv, int32_t d);
 int u2tok_tok_attention(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t H,
@@ -305,8 +306,9 @@ int u2tok_tok_attention(const void* q, const void* k, const void* v, void* out, 
  * layer of the PREFILL as RMSNorm -> packed q|k|v GEMM -> head norm + rotary -> causal grouped-query attention -> out
  * projection (+ residual) -> RMSNorm -> packed gate|up GEMM -> SiLU(gate) * up -> down projection (+ residual). */
 /* softmax(q k^T scale [causal: key j <= query i + Skv - Sq]) v with grouped-query heads: query head h (column h*d of q / out)
- * reads key / value head h / (Hq / Hkv) (column of k / v); d in {64, 96, 128, 256, 512}; layout conventions of
- * u2tok_tok_attention. */
+ * reads key / value head h / (Hq / Hkv) (column of k / v); d in {64, 96, 128, 256, 384, 512}; layout conventions of
+ * u2tok_tok_attention.  (u2tok_attention_gqa_ex / _range with a key range or row statistics, and _band, do not take 384:
+ * U2TOK_ERR_ARG.) */
 int u2tok_attention_gqa(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t Hq,
                         int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs,
                         int64_t v_bs, int64_t o_bs, float scale, int32_t causal, u2tok_stream_t stream);

@@ -1,7 +1,7 @@
 // Attention cores that do not go through the batched-GEMM path:
 //   * temporal_attention : the across-chunk half of SpatioTemporalAttentionLayer (svr.py:31-36), sequence
 //     length T = number of chunks (<= 16 here; longer sequences take the batched-GEMM path, pipeline.hip),
-//     head dim d = E/8 in {64, 128, 256, 512}.  Reads q/k/v in the (b t n) row
+//     head dim d = E/8 in {64, 128, 256, 384, 512}.  Reads q/k/v in the (b t n) row
 //     order the projections produced them in, so neither of the reference's two permute().contiguous()
 //     round trips (svr.py:32,36) touches HBM.
 //   * flash_attention_d64: MONAI SABlock attention of the ViT blocks (vit.py:100-105): S = 2049 tokens,
@@ -16,7 +16,7 @@ namespace u2 {
 // operand, Q as B: lane holds S[t1 = lane & 15][t2 = 4*(lane >> 4) + r]); softmax across the 4 lane
 // groups with two xor-shuffles; P through a 1 KB LDS patch; PV on the VALU with each lane owning a
 // contiguous d/64 slice of the head (coalesced 16-byte row reads of V, lane-local accumulation).
-template <int VPL>  // bf16 elements of the head owned per lane: d = 64 * VPL
+template <int VPL>  // bf16 elements of the head owned per lane: d = 64 * VPL (1, 2, 4, 6, 8)
 __global__ __launch_bounds__(256) void temporal_attention_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                  const bf16_t* __restrict__ v, bf16_t* __restrict__ out, int B,
                                                                  int T, int N, int H, int64_t ld_qkv, int64_t ld_out,
@@ -91,6 +91,10 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(const bf16_t* _
       const uint4 u = *reinterpret_cast<const uint4*>(p);
       vv[0] = bf16lo(u.x); vv[1] = bf16hi(u.x); vv[2] = bf16lo(u.y); vv[3] = bf16hi(u.y);
       vv[4] = bf16lo(u.z); vv[5] = bf16hi(u.z); vv[6] = bf16lo(u.w); vv[7] = bf16hi(u.w);
+    } else if constexpr (VPL == 6) {  // d = 384: 12 bytes per lane, 4-byte aligned only (lane * 12) -- three dwords
+      const uint32_t* pw = reinterpret_cast<const uint32_t*>(p);
+      const uint32_t u0 = pw[0], u1 = pw[1], u2_ = pw[2];
+      vv[0] = bf16lo(u0); vv[1] = bf16hi(u0); vv[2] = bf16lo(u1); vv[3] = bf16hi(u1); vv[4] = bf16lo(u2_); vv[5] = bf16hi(u2_);
     } else if constexpr (VPL == 4) {
       const uint2 u = *reinterpret_cast<const uint2*>(p);
       vv[0] = bf16lo(u.x); vv[1] = bf16hi(u.x); vv[2] = bf16lo(u.y); vv[3] = bf16hi(u.y);
@@ -115,6 +119,11 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(const bf16_t* _
       if constexpr (VPL == 8) {
         *reinterpret_cast<uint4*>(p) = uint4{pack2_bf16(o[t1][0], o[t1][1]), pack2_bf16(o[t1][2], o[t1][3]),
                                              pack2_bf16(o[t1][4], o[t1][5]), pack2_bf16(o[t1][6], o[t1][7])};
+      } else if constexpr (VPL == 6) {
+        uint32_t* pw = reinterpret_cast<uint32_t*>(p);
+        pw[0] = pack2_bf16(o[t1][0], o[t1][1]);
+        pw[1] = pack2_bf16(o[t1][2], o[t1][3]);
+        pw[2] = pack2_bf16(o[t1][4], o[t1][5]);
       } else if constexpr (VPL == 4) {
         *reinterpret_cast<uint2*>(p) = uint2{pack2_bf16(o[t1][0], o[t1][1]), pack2_bf16(o[t1][2], o[t1][3])};
       } else if constexpr (VPL == 2) {
@@ -130,7 +139,7 @@ int temporal_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t
                        int d, int64_t ld_qkv, int64_t ld_out, float scale, const bf16_t* rel_bias, int max_len,
                        hipStream_t stream) {
   if (!q || !k || !v || !out || B <= 0 || T <= 0 || T > 16 || N <= 0 || H <= 0) return U2_ERR_ARG;
-  if (d != 64 && d != 128 && d != 256 && d != 512) return U2_ERR_ARG;
+  if (d != 64 && d != 128 && d != 256 && d != 384 && d != 512) return U2_ERR_ARG;
   if ((ld_qkv & 7) || (ld_out & 7) || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15)) return U2_ERR_ARG;
   if (rel_bias && T > max_len) return U2_ERR_ARG;
   const int64_t ninst = (int64_t)B * N * H;
@@ -140,6 +149,7 @@ int temporal_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t
   hipLaunchKernelGGL((temporal_attention_kernel<VPL>), grid, dim3(256), 0, stream, q, k, v, out, B, T, N, H, ld_qkv, \
                      ld_out, scale, rel_bias, max_len)
   if (d == 512) U2_TA(8);
+  else if (d == 384) U2_TA(6);
   else if (d == 256) U2_TA(4);
   else if (d == 128) U2_TA(2);
   else U2_TA(1);

@@ -260,7 +260,7 @@ int flash_attention_d64_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, i
                             void* workspace, size_t workspace_bytes, hipStream_t stream);
 // Fused attention core of the tokenizer's attention modules (tokattn.hip; rma.py:60-75, tta.py:55-61, rope.py:82-86):
 // out = softmax(q k^T scale + rel_bias[j - i + max_len - 1][h]) v per (batch, head); row r of batch b at + b*?_bs + r*ld?, head
-// h at column h*d; d in {64, 128, 256, 512}.  Few (batch, head, 64-query) units -> the key range is cut into splits whose
+// h at column h*d; d in {64, 96, 128, 256, 384, 512}.  Few (batch, head, 64-query) units -> the key range is cut into splits whose
 // fp32 partial results go through `ws` (tok_attention_workspace_bytes; may be null: unsplit).  force_splits > 0 overrides
 // the heuristic (tests).  tok_attention_supported: shapes / strides the kernel takes (callers fall back to the GEMM chain).
 size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d);

@@ -161,7 +161,7 @@ int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
 int chunk_axis_attention(Arena& ar, const bf16_t* qkv, bf16_t* out, int Bx, int Tx, int Nx, int H, int d, float scale,
                          const bf16_t* rel_bias, int max_len, bool dry, hipStream_t st) {
   const int E = H * d;
-  if (Tx <= 16 && (d == 64 || d == 128 || d == 256 || d == 512)) {
+  if (Tx <= 16 && (d == 64 || d == 128 || d == 256 || d == 384 || d == 512)) {
     U2_RUN(temporal_attention(qkv, qkv + E, qkv + 2 * E, out, Bx, Tx, Nx, H, d, 3 * E, E, scale, rel_bias, max_len, st));
     return U2_OK;
   }

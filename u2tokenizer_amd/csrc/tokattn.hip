@@ -1,8 +1,8 @@
 // Fused attention core of the tokenizer's own attention modules:
 //   RelativeMultiheadAttention (rma.py:60-75): softmax(Q K^T / sqrt(d) + relative_bias[j - i + L - 1][h]) V
 //   RotaryMultiheadAttention   (rope.py:82-86), MultiHeadCrossAttention / LinearAggregation (tta.py:55-61): no bias
-// with S_q <= 512 query rows, S_kv up to a few thousand keys and a WIDE head (d = E / 8 = 256 or 512; 64 / 128 for the small
-// test configurations).  The reference materialises the (S_q x S_kv) scores and probabilities; the round-1/2 path did the
+// with S_q <= 512 query rows, S_kv up to a few thousand keys and a WIDE head (d = E / 8 = 256, 384 or 512; 64 / 128 for the
+// small test configurations).  The reference materialises the (S_q x S_kv) scores and probabilities; the round-1/2 path did the
 // same in three launches (batched GEMM -> fp32 scores in HBM -> softmax_rows -> batched GEMM on 64 x 64 tiles).  Here one
 // flash-style kernel streams K and V tiles through LDS and keeps scores, probabilities and the running softmax state in
 // registers.
@@ -29,7 +29,12 @@
 //   V tile (transpose reads; a 16-lane group reads a [4 keys][16 d] block, lane a supplies row a >> 2 / 8-byte piece a & 3):
 //       chunks rotated inside each 256-byte segment by 2 (key & 3) + 8 ((key >> 2) & 1) so that the 8 rows x 32 bytes a
 //       half wave touches fall into 16 different 16-byte slots (the layout family of gemm.hip's K-major operands).
-//   d = 96 (Phi-3-mini): 192-byte rows of 12 chunks, so neither form applies (chunks 8..11 would leave the row, and with no
+//   d = 384 (E = 3072: Phi-3-mini / Llama-3.2-3B as the decoder): 768-byte rows = 48 chunks = three whole 16-chunk segments.  Both
+//       forms above only move a chunk inside its segment and the row pitch is a multiple of the 256-byte bank period, as at 256 / 512:
+//       the same 16 distinct slots per lane group (tests/test_tok_attn_d384_host.py restates it).  What differs is bookkeeping: 48 is no
+//       power of two, so a DMA piece's (row, chunk) is a division by 48 of compile-time-plus-lane values; 6 pieces per thread and
+//       tile, 12 k steps, 24 d blocks (96 accumulator registers); 2 x (24 + 24) KB of LDS, one workgroup per CU.  4-wave form only.
+//   d = 96 (Phi-3-mini's decoder): 192-byte rows of 12 chunks, so neither form applies (chunks 8..11 would leave the row, and with no
 //   permutation the 192-byte row pitch puts one logical chunk of 16 consecutive rows on only 4 slots).  Both tiles use
 //   chunk L ^ ((row >> 1) & 2): the halves of each 4-chunk quad swap on rows with bit 2 set.  A row moves the slot by
 //   -4 row (mod 16), which sorts a lane group's rows into 4 classes by row & 3; the swap gives the two rows of a class
@@ -86,7 +91,7 @@ typedef short ta_v4s_t __attribute__((ext_vector_type(4)));
 // band of the block's last row starts 63 keys after that of its first): its running max stays -inf through that tile, which is
 // the state EX already keeps for a row that has seen no key (alpha = 1, exponent base 0: every probability exp2(-inf) = 0).
 template <int DH, bool EX = false, bool BAND = false>
-__global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const TokAttnArgs a) {
+__global__ __launch_bounds__(256, DH >= 384 ? 1 : 2) void tok_attn_kernel(const TokAttnArgs a) {
   constexpr int BK = DH <= 128 ? 64 : 32;  // keys per tile (narrow heads: twice the keys per barrier / DMA wait / softmax step)
   constexpr int NKB = BK / 16;        // 16-key blocks of S^T per tile
   constexpr int NPF = BK / 32;        // P fragments (32 keys = one MFMA k step of P V) per tile
@@ -98,6 +103,8 @@ __global__ __launch_bounds__(256, DH >= 512 ? 1 : 2) void tok_attn_kernel(const 
   constexpr int KS = DH / 32;         // k steps of Q K^T
   constexpr int DB = DH / 16;         // 16-wide d blocks of O^T
   static_assert(NP >= 1 && BK * CPR % 256 == 0, "tile");
+  // the per-segment swizzles below move a chunk inside its SEG-chunk segment: a row must be whole segments (d = 96 has its own form)
+  static_assert(DH == 96 || CPR % SEG == 0, "row = whole segments");
   extern __shared__ __attribute__((aligned(16))) char lds[];  // [stage][K tile | V tile] x 2, then the bias window
   float* const sbias = reinterpret_cast<float*>(lds + 4 * TILE);
 
@@ -826,7 +833,7 @@ size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d) {
 bool tok_attention_supported(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* out, int Sq, int Skv, int d,
                              int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                              int64_t o_bs, const bf16_t* rel_bias, int max_len) {
-  if (d != 64 && d != 96 && d != 128 && d != 256 && d != 512) return false;
+  if (d != 64 && d != 96 && d != 128 && d != 256 && d != 384 && d != 512) return false;
   if ((ldq | ldk | ldv | q_bs | k_bs | v_bs) & 7) return false;
   if ((ldo | o_bs) & 3) return false;
   if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 7)) return false;
@@ -890,9 +897,10 @@ int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
     if (mubuf) hipLaunchKernelGGL((tok_attn2_kernel<D_, true>), dim3((unsigned)grid), dim3(512), smem_, stream, a);    \
     else hipLaunchKernelGGL((tok_attn2_kernel<D_, false>), dim3((unsigned)grid), dim3(512), smem_, stream, a);         \
   } while (0)
-  const bool wide = d >= 256 && !causal && opts().tok_wide;  // two waves per SIMD (tok_attn2_kernel)
+  const bool wide = (d == 256 || d == 512) && !causal && opts().tok_wide;  // two waves per SIMD (tok_attn2_kernel; not built for 384)
   const bool mubuf = opts().tok_wide == 2 && (int64_t)Skv * ldk < (1ll << 29) && (int64_t)Skv * ldv < (1ll << 29);
   if (d == 512) { if (wide) U2_TA2(512); else U2_TA(512); }
+  else if (d == 384) U2_TA(384);
   else if (d == 256) { if (wide) U2_TA2(256); else U2_TA(256); }
   else if (d == 128) U2_TA(128);
   else if (d == 96) U2_TA(96);
@@ -935,6 +943,7 @@ int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_
   if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
   if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)kv_start & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq))
     return U2_ERR_ARG;
+  if (d == 384) return U2_ERR_ARG;  // (the range / statistics form is not built at the tokenizer's 384: no decoder has that head dim)
   if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
     return U2_ERR_ARG;
   TokAttnArgs a;

@@ -483,7 +483,7 @@ def multiscale_pool(x, gate_w=None, gate_b=None):
 
 @_guarded
 def temporal_attention(q, k, v, B, T, N, H, scale, rel_bias=None, max_len=512):
-    """q/k/v: (B*T*N, E) rows in (b t n) order."""
+    """q/k/v: (B*T*N, E) rows in (b t n) order; T <= 16, head dim E / H in {64, 128, 256, 384, 512}."""
     h = _lib.load_library()
     E = q.shape[-1]
     out = torch.empty((B * T * N, E), dtype=elem_dtype(), device=q.device)
@@ -562,7 +562,8 @@ def tok_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
                   splits: int = 0) -> torch.Tensor:
     """Fused attention core of the tokenizer's attention modules (u2tok_tok_attention; rma.py:60-75, tta.py:55-61):
     q (nb, Sq, E), k / v (nb, Skv, E) bf16 -- any views whose last dim is contiguous (e.g. column slices of a packed q|k|v
-    buffer) -> softmax(q k^T scale + rel_bias[j - i + max_len - 1][h]) v as (nb, Sq, E).  splits: 0 = heuristic key split."""
+    buffer) -> softmax(q k^T scale + rel_bias[j - i + max_len - 1][h]) v as (nb, Sq, E).  splits: 0 = heuristic key split.
+    Head dim E / heads in {64, 96, 128, 256, 384, 512}."""
     h = _lib.load_library()
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _need(t, ELEM, n)
@@ -590,7 +591,7 @@ def tok_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
 def attention_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
                   causal: bool = True, split_keys: bool = False) -> torch.Tensor:
     """softmax(q k^T scale [+ causal mask]) v with grouped-query heads (u2tok_attention_gqa): q (nb, Sq, heads * d),
-    k / v (nb, Skv, kv_heads * d) -- views with a contiguous last dim -> (nb, Sq, heads * d); d in {64, 96, 128, 256, 512}.
+    k / v (nb, Skv, kv_heads * d) -- views with a contiguous last dim -> (nb, Sq, heads * d); d in {64, 96, 128, 256, 384, 512}.
     split_keys (not causal): key ranges on separate workgroups, merged in a fixed order (u2tok_attention_gqa_split) -- few
     query rows over a long KV cache (decode steps)."""
     h = _lib.load_library()
