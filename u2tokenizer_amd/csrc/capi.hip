@@ -256,26 +256,41 @@ int u2tok_flash_attention_d64_lse(const void* q, const void* k, const void* vt, 
 size_t u2tok_tok_attention_workspace_bytes(int32_t nb, int32_t H, int32_t Sq, int32_t Skv, int32_t d) {
   return tok_attention_workspace_bytes(nb, H, Sq, Skv, d);
 }
+// the arguments every attention entry point below shares
+static AttnCall attn_call(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t Hq,
+                          int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs,
+                          int64_t v_bs, int64_t o_bs, float scale) {
+  AttnCall c;
+  c.q = BF(q); c.k = BF(k); c.v = BF(v); c.out = BFW(out);
+  c.nb = nb; c.Sq = Sq; c.Skv = Skv; c.H = Hq; c.Hkv = Hkv; c.d = d;
+  c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo; c.q_bs = q_bs; c.k_bs = k_bs; c.v_bs = v_bs; c.o_bs = o_bs;
+  c.scale = scale;
+  return c;
+}
 int u2tok_tok_attention(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t H,
                         int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
                         int64_t o_bs, float scale, const void* rel_bias, int32_t max_len, int32_t splits, void* workspace,
                         size_t workspace_bytes, u2tok_stream_t stream) {
-  return tok_attention(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, H, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale,
-                       BF(rel_bias), max_len, splits, workspace, workspace_bytes, ST(stream));
+  AttnCall c = attn_call(q, k, v, out, nb, Sq, Skv, H, H, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale);
+  c.rel_bias = BF(rel_bias); c.max_len = max_len;
+  c.force_splits = splits; c.ws = workspace; c.ws_bytes = workspace_bytes;
+  return attention(c, ST(stream));
 }
 
 int u2tok_attention_gqa(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv, int32_t Hq,
                         int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs,
                         int64_t v_bs, int64_t o_bs, float scale, int32_t causal, u2tok_stream_t stream) {
-  return attention_ex(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale,
-                      nullptr, 0, causal, 1, nullptr, 0, ST(stream));
+  AttnCall c = attn_call(q, k, v, out, nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale);
+  c.causal = causal;  // (no workspace: no key splits)
+  return attention(c, ST(stream));
 }
 int u2tok_attention_gqa_split(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
                               int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                               int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, void* workspace, size_t workspace_bytes,
                               u2tok_stream_t stream) {
-  return attention_ex(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale,
-                      nullptr, 0, 0, 0, workspace, workspace_bytes, ST(stream));
+  AttnCall c = attn_call(q, k, v, out, nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale);
+  c.ws = workspace; c.ws_bytes = workspace_bytes;  // (the heuristic's splits)
+  return attention(c, ST(stream));
 }
 int u2tok_rmsnorm_bf16(const void* x, const void* w, void* y, int64_t rows, int32_t C, int64_t ldx, int64_t ldy, float eps,
                        u2tok_stream_t stream) {
@@ -453,23 +468,27 @@ int u2tok_attention_gqa_ex(const void* q, const void* k, const void* v, void* ou
                            int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                            int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_len,
                            float* lse, int64_t lse_ld, u2tok_stream_t stream) {
-  return attention_gqa_ex(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
-                          scale, causal, kv_len, lse, lse_ld, ST(stream));
+  return u2tok_attention_gqa_range(q, k, v, out, nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, causal,
+                                   nullptr, kv_len, lse, lse_ld, stream);
 }
 int u2tok_attention_gqa_range(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
                               int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                               int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
                               const int32_t* kv_len, float* lse, int64_t lse_ld, u2tok_stream_t stream) {
-  return attention_gqa_range(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
-                             scale, causal, kv_start, kv_len, lse, lse_ld, ST(stream));
+  AttnCall c = attn_call(q, k, v, out, nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale);
+  c.causal = causal; c.kv_start = kv_start; c.kv_len = kv_len; c.lse = lse; c.lse_ld = lse_ld;
+  return attention(c, ST(stream));
 }
 int u2tok_attention_gqa_band(const void* q, const void* k, const void* v, void* out, int32_t nb, int32_t Sq, int32_t Skv,
                              int32_t Hq, int32_t Hkv, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs,
                              int64_t k_bs, int64_t v_bs, int64_t o_bs, float scale, int32_t causal, const int32_t* kv_start,
                              const int32_t* kv_len, float* lse, int64_t lse_ld, int64_t k_hs, int64_t v_hs, int32_t window,
                              u2tok_stream_t stream) {
-  return attention_gqa_band(BF(q), BF(k), BF(v), BFW(out), nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs,
-                            k_hs, v_hs, window, scale, causal, kv_start, kv_len, lse, lse_ld, ST(stream));
+  if (!k_hs || !v_hs) return U2_ERR_ARG;  // (a caller names its head strides: 0 is the descriptor's own "column-packed")
+  AttnCall c = attn_call(q, k, v, out, nb, Sq, Skv, Hq, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale);
+  c.causal = causal; c.kv_start = kv_start; c.kv_len = kv_len; c.lse = lse; c.lse_ld = lse_ld;
+  c.k_hs = k_hs; c.v_hs = v_hs; c.window = window;
+  return attention(c, ST(stream));
 }
 size_t u2tok_attention_gqa_bwd_workspace_bytes(int32_t nb, int32_t S, int32_t Hq) {
   return attention_gqa_bwd_workspace_bytes(nb, S, Hq);

@@ -261,7 +261,7 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
-// (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention_ex launch pair per sequence -- B <= 16
+// (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention() launch pair per sequence -- B <= 16
 // only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG)
 int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
                         int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
@@ -295,10 +295,13 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     if (e != U2_OK) return e;
   }
   for (int b = 0; b < c.B && !batched; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
-    const int e = attention_ex(qkv + (size_t)b * nq, K + (size_t)b * c.Hkv * kv_stride, V + (size_t)b * c.Hkv * kv_stride,
-                               ctx + (size_t)b * qd, c.Hkv, 1, T, g, 1, c.D, /*ldq*/ (int64_t)g * c.D, /*ldk*/ c.D, /*ldv*/ c.D,
-                               /*ldo*/ (int64_t)g * c.D, /*q_bs*/ (int64_t)g * c.D, /*k_bs*/ kv_stride, /*v_bs*/ kv_stride,
-                               /*o_bs*/ (int64_t)g * c.D, scale, nullptr, 0, 0, 0, aws, aws_bytes, st);
+    AttnCall a;
+    a.q = qkv + (size_t)b * nq; a.k = K + (size_t)b * c.Hkv * kv_stride; a.v = V + (size_t)b * c.Hkv * kv_stride;
+    a.out = ctx + (size_t)b * qd;
+    a.nb = c.Hkv; a.Sq = 1; a.Skv = T; a.H = g; a.Hkv = 1; a.d = c.D;
+    a.ldq = a.ldo = a.q_bs = a.o_bs = (int64_t)g * c.D; a.ldk = a.ldv = c.D; a.k_bs = a.v_bs = kv_stride;
+    a.scale = scale; a.ws = aws; a.ws_bytes = aws_bytes;
+    const int e = attention(a, st);
     if (e != U2_OK) return e;
   }
   int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);

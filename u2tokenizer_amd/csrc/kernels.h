@@ -258,45 +258,43 @@ int flash_attention_d64_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, i
                             const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,
                             int64_t bs_d, int nb, int S, int H, float scale, const float* lse, int64_t lse_ld,
                             void* workspace, size_t workspace_bytes, hipStream_t stream);
-// Fused attention core of the tokenizer's attention modules (tokattn.hip; rma.py:60-75, tta.py:55-61, rope.py:82-86):
-// out = softmax(q k^T scale + rel_bias[j - i + max_len - 1][h]) v per (batch, head); row r of batch b at + b*?_bs + r*ld?, head
-// h at column h*d; d in {64, 96, 128, 256, 384, 512}.  Few (batch, head, 64-query) units -> the key range is cut into splits whose
-// fp32 partial results go through `ws` (tok_attention_workspace_bytes; may be null: unsplit).  force_splits > 0 overrides
-// the heuristic (tests).  tok_attention_supported: shapes / strides the kernel takes (callers fall back to the GEMM chain).
+// Fused attention forward (tokattn.hip): out = softmax(q k^T scale + bias / masks) v per (batch, head); row r of batch b at
+// + b*?_bs + r*ld?, query head h at column h*d of q / out, kv head h / (H / Hkv) of k / v.  One descriptor for every caller: the
+// tokenizer's attention modules (rma.py:60-75, tta.py:55-61, rope.py:82-86), the decoder's prefill, decode, training and continued
+// prefill routes.  The optional fields' defaults are the plain call; what is set picks the kernel form:
+//   plain  d in {64, 96, 128, 256, 384, 512}; rel_bias (not causal) and key splits (not causal) only here
+//   range  kv_start / kv_len / lse set: d in {64, 96, 128, 256, 512}
+//   band   k_hs / v_hs != d or a window: d in {64, 96, 128}
+struct AttnCall {
+  const bf16_t *q = nullptr, *k = nullptr, *v = nullptr;
+  bf16_t* out = nullptr;
+  int nb = 0, Sq = 0, Skv = 0, H = 0, Hkv = 0, d = 0;  // Hkv = H: plain multi-head
+  int64_t ldq = 0, ldk = 0, ldv = 0, ldo = 0, q_bs = 0, k_bs = 0, v_bs = 0, o_bs = 0;
+  float scale = 1.f;
+  const bf16_t* rel_bias = nullptr;  // + rel_bias[j - i + max_len - 1][h]
+  int max_len = 0;
+  int causal = 0;  // key j visible to query i iff j <= i + Skv - Sq
+  // Few (batch, head, 64-query) units -> the key range is cut into splits whose fp32 partial results go through `ws`
+  // (tok_attention_workspace_bytes, 16-byte aligned; null: unsplit).  force_splits > 0 overrides the heuristic (tests).
+  int force_splits = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  // key j of sequence b visible iff kv_start[b] <= j < kv_len[b] (device int (nb) each; null: 0 / Skv); a row that sees no key gets
+  // zeros.  lse: row statistics for attention_gqa_bwd, (nb * H, lse_ld) fp32 in log2 units.
+  const int *kv_start = nullptr, *kv_len = nullptr;
+  float* lse = nullptr;
+  int64_t lse_ld = 0;
+  int64_t k_hs = 0, v_hs = 0;  // elements between the kv heads of a sequence (0: d, column-packed; capacity * d: a KV cache's (B, Hkv, capacity, d))
+  int window = 0;              // W > 0 (causal): ... and only if j > i + Skv - Sq - W
+};
+int attention(const AttnCall& c, hipStream_t stream);
+// tok_attention_supported: the plain form takes these shapes / strides (pipeline.hip falls back to the GEMM chain otherwise)
+bool tok_attention_supported(const AttnCall& c);
 size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d);
-bool tok_attention_supported(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* out, int Sq, int Skv, int d,
-                             int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                             int64_t o_bs, const bf16_t* rel_bias, int max_len);
-int tok_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int d,
-                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                  float scale, const bf16_t* rel_bias, int max_len, int force_splits, void* ws, size_t ws_bytes,
-                  hipStream_t stream);
-// The same kernel for the decoder prefill: grouped-query heads (query head h reads key / value head h / (H / Hkv)) and a causal
-// mask (key j visible to query i iff j <= i + Skv - Sq); no relative bias and no key splits with causal.
-int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
-                 int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                 float scale, const bf16_t* rel_bias, int max_len, int causal, int force_splits, void* ws, size_t ws_bytes,
-                 hipStream_t stream);
-// The decoder training route (u2tokenizer_amd/decoder_train.py).  attention_gqa_ex (tokattn.hip): attention_ex's causal GQA
-// call with per-sequence key lengths kv_len (key j of sequence b visible iff j < kv_len[b]) and optional row statistics lse
-// ((nb * H, lse_ld), log2 units); both null: attention_ex itself.  attention_gqa_bwd (attn_bwd.hip, the causal instantiations
-// of the pair behind flash_attention_d64_bwd): its flash backward, d = 64 / 128, Sq = Skv = S, layout of flash_attention_d64_bwd
-// with Hq query and Hkv kv heads.  rmsnorm_bwd,
+// The decoder training route (u2tokenizer_amd/decoder_train.py).  attention_gqa_bwd (attn_bwd.hip, the causal instantiations
+// of the pair behind flash_attention_d64_bwd): the flash backward of attention()'s causal GQA call with kv_len and lse, d = 64 / 128,
+// Sq = Skv = S, layout of flash_attention_d64_bwd with Hq query and Hkv kv heads.  rmsnorm_bwd,
 // qk_norm_rope_bwd, swiglu_bwd (backward.hip): the row operations' backward.
-int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
-                     int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                     int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld, hipStream_t stream);
-// attention_gqa_range: attention_gqa_ex plus a first visible key per sequence (kv_start; the padded inference routes of prefill.py).
-int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
-                        int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                        int64_t o_bs, float scale, int causal, const int* kv_start, const int* kv_len, float* lse, int64_t lse_ld,
-                        hipStream_t stream);
-// attention_gqa_band: attention_gqa_range with the kv heads k_hs / v_hs elements apart (a KV cache's (B, Hkv, capacity, d) buffers read
-// in place) and the lower edge of an attention window (key j visible to query i only if j > i + Skv - Sq - window; 0: none).
-int attention_gqa_band(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
-                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                       int64_t k_hs, int64_t v_hs, int window, float scale, int causal, const int* kv_start, const int* kv_len,
-                       float* lse, int64_t lse_ld, hipStream_t stream);
 size_t attention_gqa_bwd_workspace_bytes(int nb, int S, int Hq);
 int attention_gqa_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld_qkv, int64_t bs_qkv, const bf16_t* o,
                       const bf16_t* dout, int64_t ld_o, int64_t bs_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, int64_t ld_d,

@@ -75,15 +75,7 @@ int linear(const bf16_t* x, int64_t ldx, const bf16_t* w, const bf16_t* b, bf16_
   return gemm_bf16(linear_desc(x, ldx, w, b, y, ldy, rows, in, out, extra_flags, R, ldr, nsplit, alpha_lo), st);
 }
 
-struct AttnCore {
-  const bf16_t *q, *k, *v;
-  int64_t ldq, ldk, ldv, q_bs, k_bs, v_bs;
-  bf16_t* out;
-  int64_t ldo, o_bs;
-  int nb, Sq, Skv, H, d;
-  float scale;
-  const bf16_t* rel_bias;
-  int max_len;
+struct AttnCore : AttnCall {   // equal heads, no masks; the key-split scratch (ws) comes from the arena
   bool unfused = false;  // force the GEMM chain (the ViT's debug path)
 };
 
@@ -94,14 +86,14 @@ struct AttnCore {
 int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
   if (!a.unfused && (dry || opts().tok_flash)) {
     const size_t mark = ar.off;
-    const size_t wsb = tok_attention_workspace_bytes(a.nb, a.H, a.Sq, a.Skv, a.d);
-    char* tws = wsb ? ar.get<char>(wsb) : nullptr;
+    AttnCall c = a;
+    c.Hkv = a.H;
+    c.ws_bytes = tok_attention_workspace_bytes(a.nb, a.H, a.Sq, a.Skv, a.d);
+    c.ws = c.ws_bytes ? ar.get<char>(c.ws_bytes) : nullptr;
     U2_CHECK_WS(ar);
     // (a dry run sizes the arena for BOTH forms: which one a real call takes depends on pointers it does not have)
-    if (!dry && tok_attention_supported(a.q, a.k, a.v, a.out, a.Sq, a.Skv, a.d, a.ldq, a.ldk, a.ldv, a.ldo, a.q_bs, a.k_bs,
-                                        a.v_bs, a.o_bs, a.rel_bias, a.max_len)) {
-      const int e = tok_attention(a.q, a.k, a.v, a.out, a.nb, a.Sq, a.Skv, a.H, a.d, a.ldq, a.ldk, a.ldv, a.ldo, a.q_bs,
-                                  a.k_bs, a.v_bs, a.o_bs, a.scale, a.rel_bias, a.max_len, 0, tws, wsb, st);
+    if (!dry && tok_attention_supported(c)) {
+      const int e = attention(c, st);
       ar.off = mark;
       return e;
     }
@@ -167,8 +159,10 @@ int chunk_axis_attention(Arena& ar, const bf16_t* qkv, bf16_t* out, int Bx, int 
   }
   for (int b = 0; b < Bx; ++b) {
     const bf16_t* base = qkv + (int64_t)b * Tx * Nx * 3 * E;
-    AttnCore a{base, base + E, base + 2 * E, (int64_t)Nx * 3 * E, (int64_t)Nx * 3 * E, (int64_t)Nx * 3 * E, 3 * E, 3 * E,
-               3 * E, out + (int64_t)b * Tx * Nx * E, (int64_t)Nx * E, E, Nx, Tx, Tx, H, d, scale, rel_bias, max_len};
+    AttnCore a;
+    a.q = base; a.k = base + E; a.v = base + 2 * E; a.out = out + (int64_t)b * Tx * Nx * E;
+    a.ldq = a.ldk = a.ldv = (int64_t)Nx * 3 * E; a.q_bs = a.k_bs = a.v_bs = 3 * E; a.ldo = (int64_t)Nx * E; a.o_bs = E;
+    a.nb = Nx; a.Sq = a.Skv = Tx; a.H = H; a.d = d; a.scale = scale; a.rel_bias = rel_bias; a.max_len = max_len;
     const int e = attention_core(ar, a, dry, st);
     if (e != U2_OK) return e;
   }
@@ -263,8 +257,10 @@ int vit_forward(const VitConfig& c, const void* const* W, const void* volume, bf
         if (e1 != hipSuccess || e2 != hipSuccess) return U2_ERR_LAUNCH;
       }
       {
-        AttnCore a{qc, qc + Hd, qc + 2 * Hd, 3 * Hd, 3 * Hd, 3 * Hd, (int64_t)S * 3 * Hd, (int64_t)S * 3 * Hd,
-                   (int64_t)S * 3 * Hd, ac, Hd, (int64_t)S * Hd, nc, S, S, c.heads, 64, scale, nullptr, 0, true};
+        AttnCore a;
+        a.q = qc; a.k = qc + Hd; a.v = qc + 2 * Hd; a.out = ac;
+        a.ldq = a.ldk = a.ldv = 3 * Hd; a.q_bs = a.k_bs = a.v_bs = (int64_t)S * 3 * Hd; a.ldo = Hd; a.o_bs = (int64_t)S * Hd;
+        a.nb = nc; a.Sq = a.Skv = S; a.H = c.heads; a.d = 64; a.scale = scale; a.unfused = true;
         const int e = attention_core(ar, a, dry, st);
         if (e != U2_OK) return e;
       }
@@ -416,8 +412,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
       const int e = chunk_axis_attention(ar, qkv, ctx, 1, B * T, N, H, d, scale, nullptr, c.max_seq_len, dry, st);
       if (e != U2_OK) return e;
     } else {
-      AttnCore a{qkv, qkv + E, qkv + 2 * E, 3 * E, 3 * E, 3 * E, (int64_t)N * 3 * E, (int64_t)N * 3 * E,
-                 (int64_t)N * 3 * E, ctx, E, (int64_t)N * E, B * T, N, N, H, d, scale, sp.rb, c.max_seq_len};
+      AttnCore a;
+      a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.out = ctx;
+      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = (int64_t)N * 3 * E; a.ldo = E; a.o_bs = (int64_t)N * E;
+      a.nb = B * T; a.Sq = a.Skv = N; a.H = H; a.d = d; a.scale = scale; a.rel_bias = sp.rb; a.max_len = c.max_seq_len;
       const int e = attention_core(ar, a, dry, st);
       if (e != U2_OK) return e;
     }
@@ -430,8 +428,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
       U2_RUN(rope_apply(qkv + E, B, T, N, H, d, 3 * E, c.max_seq_len, 0, st));
     }
     if (c.attn_type == 2 && B == 1) {  // sequence = the N tokens of a chunk, batch = chunk
-      AttnCore a{qkv, qkv + E, qkv + 2 * E, 3 * E, 3 * E, 3 * E, (int64_t)N * 3 * E, (int64_t)N * 3 * E,
-                 (int64_t)N * 3 * E, ctx, E, (int64_t)N * E, T, N, N, H, d, scale, nullptr, 0};
+      AttnCore a;
+      a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.out = ctx;
+      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = (int64_t)N * 3 * E; a.ldo = E; a.o_bs = (int64_t)N * E;
+      a.nb = T; a.Sq = a.Skv = N; a.H = H; a.d = d; a.scale = scale;
       const int e = attention_core(ar, a, dry, st);
       if (e != U2_OK) return e;
     } else if (c.attn_type == 2) {
@@ -446,8 +446,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
                                (size_t)N * 3 * E * 2, (size_t)N * 3 * E * 2, T, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return U2_ERR_LAUNCH;
       const int64_t S2 = (int64_t)B * N;
-      AttnCore a{g, g + E, g + 2 * E, 3 * E, 3 * E, 3 * E, S2 * 3 * E, S2 * 3 * E, S2 * 3 * E, gc, E, S2 * E,
-                 T, (int)S2, (int)S2, H, d, scale, nullptr, 0};
+      AttnCore a;
+      a.q = g; a.k = g + E; a.v = g + 2 * E; a.out = gc;
+      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = S2 * 3 * E; a.ldo = E; a.o_bs = S2 * E;
+      a.nb = T; a.Sq = a.Skv = (int)S2; a.H = H; a.d = d; a.scale = scale;
       const int e = attention_core(ar, a, dry, st);
       if (e != U2_OK) return e;
       if (!dry)
@@ -601,8 +603,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
     } else if (!dry) {
       if (hipStreamWaitEvent(st, side->done[kv_ready], 0) != hipSuccess) return U2_ERR_LAUNCH;
     }
-    AttnCore ac{qproj, kv, kv + E, E, 2 * E, 2 * E, (int64_t)Q * E, (int64_t)Ls * 2 * E, (int64_t)Ls * 2 * E,
-                qctx, E, (int64_t)Q * E, B, Q, Ls, H, d, scale, nullptr, 0};
+    AttnCore ac;
+    ac.q = qproj; ac.k = kv; ac.v = kv + E; ac.out = qctx;
+    ac.ldq = ac.ldo = E; ac.ldk = ac.ldv = 2 * E; ac.q_bs = ac.o_bs = (int64_t)Q * E; ac.k_bs = ac.v_bs = (int64_t)Ls * 2 * E;
+    ac.nb = B; ac.Sq = Q; ac.Skv = Ls; ac.H = H; ac.d = d; ac.scale = scale;
     const int e = attention_core(ar, ac, dry, st);
     if (e != U2_OK) return e;
     U2_RUN(linear(qctx, E, a.wd, a.bd, dst, E, qrows, E, E, 0, nullptr, 0, st));
@@ -634,8 +638,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
         U2_RUN(rope_apply(qproj, B, Q, 1, H, d, 3 * E, c.max_seq_len, 0, st));
         U2_RUN(rope_apply(qproj + E, B, Q, 1, H, d, 3 * E, c.max_seq_len, 0, st));
       }
-      AttnCore ac{qproj, qproj + E, qproj + 2 * E, 3 * E, 3 * E, 3 * E, (int64_t)Q * 3 * E, (int64_t)Q * 3 * E,
-                  (int64_t)Q * 3 * E, qctx, E, (int64_t)Q * E, B, Q, Q, H, d, scale, sa.rb, c.max_seq_len};
+      AttnCore ac;
+      ac.q = qproj; ac.k = qproj + E; ac.v = qproj + 2 * E; ac.out = qctx;
+      ac.ldq = ac.ldk = ac.ldv = 3 * E; ac.q_bs = ac.k_bs = ac.v_bs = (int64_t)Q * 3 * E; ac.ldo = E; ac.o_bs = (int64_t)Q * E;
+      ac.nb = B; ac.Sq = ac.Skv = Q; ac.H = H; ac.d = d; ac.scale = scale; ac.rel_bias = sa.rb; ac.max_len = c.max_seq_len;
       const int e = attention_core(ar, ac, dry, st);
       if (e != U2_OK) return e;
     }
@@ -661,8 +667,10 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
     } else if (!dry) {
       if (hipStreamWaitEvent(st, side->done[2 * L], 0) != hipSuccess) return U2_ERR_LAUNCH;
     }
-    AttnCore ac{qproj, k_lin, V, E, E, E, (int64_t)Q * E, (int64_t)Lv * E, (int64_t)Lv * E,
-                out, E, (int64_t)Q * E, B, Q, Lv, H, d, scale, nullptr, 0};
+    AttnCore ac;
+    ac.q = qproj; ac.k = k_lin; ac.v = V; ac.out = out;
+    ac.ldq = ac.ldk = ac.ldv = ac.ldo = E; ac.q_bs = ac.o_bs = (int64_t)Q * E; ac.k_bs = ac.v_bs = (int64_t)Lv * E;
+    ac.nb = B; ac.Sq = Q; ac.Skv = Lv; ac.H = H; ac.d = d; ac.scale = scale;
     const int e = attention_core(ar, ac, dry, st);
     if (e != U2_OK) return e;
   }

@@ -810,218 +810,139 @@ __global__ __launch_bounds__(256) void tok_attn_combine_ns_kernel(const TokAttnA
 
 static inline int tok_attn_bk(int d) { return d <= 128 ? 64 : 32; }  // keys per tile (tok_attn_kernel: BK)
 
-// ns for a call: enough workgroups to cover the 256 CUs, at least two tiles per split, partial sums within the scratch.
-static int tok_attn_pick_splits(int nb, int H, int Sq, int Skv, int d, size_t ws_bytes) {
+// partial results of one key split: fp32 outputs + (running max, sum) per row and head
+static size_t tok_attn_split_bytes(int nb, int H, int Sq, int d) { return (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8); }
+
+// splits the heuristic asks for: enough workgroups to cover the 256 CUs, at least two tiles per split (1: unsplit)
+static int tok_attn_want_splits(int nb, int H, int Sq, int Skv, int d) {
   const int64_t base = (int64_t)nb * H * cdiv(Sq, 64);
   const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
   if (base >= 192 || ntile < 4) return 1;
-  int ns = (int)std::min<int64_t>(cdiv(256, base), ntile / 2);
-  const size_t per = (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
-  if (per == 0 || ws_bytes / per < 2) return 1;
-  ns = (int)std::min<size_t>((size_t)ns, ws_bytes / per);
-  return std::max(ns, 1);
+  return (int)std::min<int64_t>(cdiv(256, base), ntile / 2);
 }
 
 size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d) {
-  const int64_t base = (int64_t)nb * H * cdiv(Sq, 64);
-  const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
-  if (base >= 192 || ntile < 4) return 0;
-  const int ns = (int)std::min<int64_t>(cdiv(256, base), ntile / 2);
-  return (size_t)ns * nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
+  const int ns = tok_attn_want_splits(nb, H, Sq, Skv, d);
+  return ns > 1 ? ns * tok_attn_split_bytes(nb, H, Sq, d) : 0;
 }
 
-bool tok_attention_supported(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* out, int Sq, int Skv, int d,
-                             int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                             int64_t o_bs, const bf16_t* rel_bias, int max_len) {
-  if (d != 64 && d != 96 && d != 128 && d != 256 && d != 384 && d != 512) return false;
-  if ((ldq | ldk | ldv | q_bs | k_bs | v_bs) & 7) return false;
-  if ((ldo | o_bs) & 3) return false;
-  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 7)) return false;
-  if (rel_bias && (Sq > max_len || Skv > max_len || (int)cdiv(Skv, 64) * 64 + 63 > TOKATTN_BIAS_SLOTS)) return false;
+bool tok_attention_supported(const AttnCall& c) {
+  if (c.d != 64 && c.d != 96 && c.d != 128 && c.d != 256 && c.d != 384 && c.d != 512) return false;
+  if ((c.ldq | c.ldk | c.ldv | c.q_bs | c.k_bs | c.v_bs) & 7) return false;
+  if ((c.ldo | c.o_bs) & 3) return false;
+  if ((((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v) & 15) || ((uintptr_t)c.out & 7)) return false;
+  if (c.rel_bias && (c.Sq > c.max_len || c.Skv > c.max_len || (int)cdiv(c.Skv, 64) * 64 + 63 > TOKATTN_BIAS_SLOTS)) return false;
   return true;
 }
 
-int tok_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int d,
-                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                  float scale, const bf16_t* rel_bias, int max_len, int force_splits, void* ws, size_t ws_bytes,
-                  hipStream_t stream) {
-  return attention_ex(q, k, v, out, nb, Sq, Skv, H, H, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, rel_bias, max_len, 0,
-                      force_splits, ws, ws_bytes, stream);
+// Which instantiation of tok_attn_kernel a call gets.  PLAIN: <DH>, with key splits, the relative bias and the 8-wave form.
+// RANGE: <DH, true> (kv_start / kv_len / lse).  BAND: <DH, true, true> (kv head strides, window).  A call that sets none of a
+// form's fields is exactly the form before it -- the same kernel, the same bits.
+enum AttnForm { ATTN_PLAIN, ATTN_RANGE, ATTN_BAND };
+
+static AttnForm attn_form(const AttnCall& c) {
+  if ((c.k_hs && c.k_hs != c.d) || (c.v_hs && c.v_hs != c.d) || c.window != 0) return ATTN_BAND;
+  return c.kv_len || c.kv_start || c.lse ? ATTN_RANGE : ATTN_PLAIN;
 }
 
-int attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
-                 int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                 float scale, const bf16_t* rel_bias, int max_len, int causal, int force_splits, void* ws, size_t ws_bytes,
-                 hipStream_t stream) {
-  if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
-  if (causal && (Skv < Sq || rel_bias)) return U2_ERR_ARG;
-  if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, rel_bias, max_len))
-    return U2_ERR_ARG;
-  TokAttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
-  a.scale_log2e = scale * 1.44269504088896340736f;
-  a.rel_bias = rel_bias; a.max_len = max_len;
-  const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
-  a.kv_group = H / Hkv;
-  a.causal = causal ? 1 : 0;
-  a.kv_len = nullptr; a.kv_start = nullptr; a.lse = nullptr; a.lse_ld = 0;
-  a.k_hs = a.v_hs = d; a.window = 0;
-  int ns = force_splits > 0 ? std::min(force_splits, ntile) : tok_attn_pick_splits(nb, H, Sq, Skv, d, ws ? ws_bytes : 0);
-  if (causal) ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
-  const size_t per = (size_t)nb * Sq * ((size_t)H * d * 4 + (size_t)H * 8);
-  if (ns > 1 && (!ws || ws_bytes < (size_t)ns * per || ((uintptr_t)ws & 15))) {
-    if (force_splits > 0) return U2_ERR_WORKSPACE;
-    ns = 1;
+static bool attn_call_ok(const AttnCall& c, AttnForm form) {
+  if (!c.q || !c.k || !c.v || !c.out || c.nb <= 0 || c.Sq <= 0 || c.Skv <= 0 || c.H <= 0 || c.Hkv <= 0 || c.H % c.Hkv) return false;
+  if (c.causal && (c.Skv < c.Sq || c.rel_bias)) return false;
+  if ((((uintptr_t)c.kv_len | (uintptr_t)c.kv_start | (uintptr_t)c.lse) & 3) || (c.lse && c.lse_ld < c.Sq)) return false;
+  if (c.window < 0 || (c.window > 0 && !c.causal) || c.k_hs < 0 || c.v_hs < 0 || ((c.k_hs | c.v_hs) & 7)) return false;
+  // (no entry point asks for a relative bias or key splits under a key range or a band: neither kernel form has them)
+  if (form != ATTN_PLAIN && (c.rel_bias || c.force_splits > 0)) return false;
+  // (the range / statistics form is not built at the tokenizer's 384: no decoder has that head dim)
+  if (form == ATTN_RANGE && c.d == 384) return false;
+  if (form == ATTN_BAND && c.d != 64 && c.d != 96 && c.d != 128) return false;
+  return tok_attention_supported(c);
+}
+
+// One launch at head dim DH.  wide (plain form at 256 / 512 only): 0, or opts().tok_wide for the 8-wave tok_attn2_kernel, two waves
+// per SIMD (2: with buffer-addressed loads).
+template <int DH, bool EX, bool BAND>
+static void tok_attn_launch_d(const TokAttnArgs& a, int wide, unsigned grid, hipStream_t stream) {
+  if constexpr (!EX && (DH == 256 || DH == 512)) {
+    if (wide) {
+      constexpr size_t smem2 = 4 * 32 * DH * 2 + 16384 + TOKATTN_BIAS_SLOTS * 4;
+      if (wide == 2) hipLaunchKernelGGL((tok_attn2_kernel<DH, true>), dim3(grid), dim3(512), smem2, stream, a);
+      else hipLaunchKernelGGL((tok_attn2_kernel<DH, false>), dim3(grid), dim3(512), smem2, stream, a);
+      return;
+    }
   }
+  constexpr size_t smem = 4 * (DH <= 128 ? 64 : 32) * DH * 2 + TOKATTN_BIAS_SLOTS * 4;
+  hipLaunchKernelGGL((tok_attn_kernel<DH, EX, BAND>), dim3(grid), dim3(256), smem, stream, a);
+}
+
+// The head-dim dispatch of every form, over the head dims the form is built for (attn_call_ok has refused the others)
+template <bool EX, bool BAND>
+static void tok_attn_launch(const TokAttnArgs& a, int d, int wide, unsigned grid, hipStream_t stream) {
+  if constexpr (!BAND) {
+    if (d == 512) return tok_attn_launch_d<512, EX, BAND>(a, wide, grid, stream);
+    if constexpr (!EX)
+      if (d == 384) return tok_attn_launch_d<384, EX, BAND>(a, wide, grid, stream);
+    if (d == 256) return tok_attn_launch_d<256, EX, BAND>(a, wide, grid, stream);
+  }
+  if (d == 128) return tok_attn_launch_d<128, EX, BAND>(a, wide, grid, stream);
+  if (d == 96) return tok_attn_launch_d<96, EX, BAND>(a, wide, grid, stream);
+  tok_attn_launch_d<64, EX, BAND>(a, wide, grid, stream);
+}
+
+int attention(const AttnCall& c, hipStream_t stream) {
+  const AttnForm form = attn_form(c);
+  if (!attn_call_ok(c, form)) return U2_ERR_ARG;
+  const int nb = c.nb, Sq = c.Sq, Skv = c.Skv, H = c.H, d = c.d;
+  const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
+  int ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
+  if (form == ATTN_PLAIN && !c.causal) {
+    const size_t fit = c.ws ? c.ws_bytes / tok_attn_split_bytes(nb, H, Sq, d) : 0;  // splits whose partial results the scratch holds
+    ns = c.force_splits > 0 ? std::min(c.force_splits, ntile)
+                            : std::max((int)std::min<size_t>(tok_attn_want_splits(nb, H, Sq, Skv, d), fit), 1);
+    if (ns > 1 && (fit < (size_t)ns || ((uintptr_t)c.ws & 15))) {
+      if (c.force_splits > 0) return U2_ERR_WORKSPACE;
+      ns = 1;
+    }
+  }
+  TokAttnArgs a;
+  a.q = c.q; a.k = c.k; a.v = c.v; a.out = c.out;
+  a.ldq = c.ldq; a.ldk = c.ldk; a.ldv = c.ldv; a.ldo = c.ldo; a.q_bs = c.q_bs; a.k_bs = c.k_bs; a.v_bs = c.v_bs; a.o_bs = c.o_bs;
+  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
+  a.scale_log2e = c.scale * 1.44269504088896340736f;
+  a.rel_bias = c.rel_bias; a.max_len = c.max_len;
+  a.kv_group = H / c.Hkv;
+  a.causal = c.causal ? 1 : 0;
+  a.kv_len = c.kv_len; a.kv_start = c.kv_start; a.lse = c.lse; a.lse_ld = c.lse_ld;
+  a.k_hs = c.k_hs ? c.k_hs : d; a.v_hs = c.v_hs ? c.v_hs : d; a.window = c.window;
   a.tps = (int)cdiv(ntile, ns);
   a.ns = (int)cdiv(ntile, a.tps);  // no empty splits
   a.opart = nullptr; a.ml = nullptr;
   if (a.ns > 1) {
-    a.opart = reinterpret_cast<float*>(ws);
+    a.opart = reinterpret_cast<float*>(c.ws);
     a.ml = a.opart + (size_t)a.ns * nb * Sq * H * d;
   }
   const int64_t grid = (int64_t)nb * H * a.nqb * a.ns;
   if (grid > 0x7fffffff) return U2_ERR_ARG;
-  ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
-               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));  // q, k, v read + o written, once
-#define U2_TA(D_)                                                                                                      \
-  do {                                                                                                                 \
-    constexpr size_t smem_ = 4 * ((D_) <= 128 ? 64 : 32) * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                          \
-    hipLaunchKernelGGL((tok_attn_kernel<D_>), dim3((unsigned)grid), dim3(256), smem_, stream, a);                      \
-  } while (0)
-#define U2_TA2(D_)                                                                                                     \
-  do {                                                                                                                 \
-    constexpr size_t smem_ = 4 * 32 * (D_) * 2 + 16384 + TOKATTN_BIAS_SLOTS * 4;                                       \
-    if (mubuf) hipLaunchKernelGGL((tok_attn2_kernel<D_, true>), dim3((unsigned)grid), dim3(512), smem_, stream, a);    \
-    else hipLaunchKernelGGL((tok_attn2_kernel<D_, false>), dim3((unsigned)grid), dim3(512), smem_, stream, a);         \
-  } while (0)
-  const bool wide = (d == 256 || d == 512) && !causal && opts().tok_wide;  // two waves per SIMD (tok_attn2_kernel; not built for 384)
-  const bool mubuf = opts().tok_wide == 2 && (int64_t)Skv * ldk < (1ll << 29) && (int64_t)Skv * ldv < (1ll << 29);
-  if (d == 512) { if (wide) U2_TA2(512); else U2_TA(512); }
-  else if (d == 384) U2_TA(384);
-  else if (d == 256) { if (wide) U2_TA2(256); else U2_TA(256); }
-  else if (d == 128) U2_TA(128);
-  else if (d == 96) U2_TA(96);
-  else U2_TA(64);
-#undef U2_TA
-#undef U2_TA2
-  if (a.ns > 1) {
-    const int64_t total = (int64_t)nb * Sq * (H * d / 4);
-    const dim3 cg((unsigned)cdiv(total, 256));
+  ProfScope ps(PROF_TOKATTN, (c.causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
+               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * c.Hkv));  // q, k, v read + o written, once
+  if (form == ATTN_PLAIN) {
+    int wide = (d == 256 || d == 512) && !c.causal ? opts().tok_wide : 0;  // (tok_attn2_kernel is not built for 384)
+    if (wide == 2 && ((int64_t)Skv * c.ldk >= (1ll << 29) || (int64_t)Skv * c.ldv >= (1ll << 29))) wide = 1;  // (past its buffer offsets)
+    tok_attn_launch<false, false>(a, d, wide, (unsigned)grid, stream);
+    if (a.ns > 1) {
+      const int64_t total = (int64_t)nb * Sq * (H * d / 4);
+      const dim3 cg((unsigned)cdiv(total, 256));
 #define U2_CMB(NS_) case NS_: hipLaunchKernelGGL(tok_attn_combine_ns_kernel<NS_>, cg, dim3(256), 0, stream, a, d); break
-    switch (a.ns <= 8 ? a.ns : 0) {
-      U2_CMB(2); U2_CMB(3); U2_CMB(4); U2_CMB(5); U2_CMB(6); U2_CMB(7); U2_CMB(8);
-      default: hipLaunchKernelGGL(tok_attn_combine_kernel, cg, dim3(256), 0, stream, a, d);
-    }
+      switch (a.ns <= 8 ? a.ns : 0) {
+        U2_CMB(2); U2_CMB(3); U2_CMB(4); U2_CMB(5); U2_CMB(6); U2_CMB(7); U2_CMB(8);
+        default: hipLaunchKernelGGL(tok_attn_combine_kernel, cg, dim3(256), 0, stream, a, d);
+      }
 #undef U2_CMB
-
+    }
+  } else if (form == ATTN_RANGE) {
+    tok_attn_launch<true, false>(a, d, 0, (unsigned)grid, stream);
+  } else {
+    tok_attn_launch<true, true>(a, d, 0, (unsigned)grid, stream);
   }
-  return launch_status();
-}
-
-// The decoder training route's forward: attention_ex's causal / plain GQA call without key splits, plus per-sequence key lengths
-// (kv_len) and the row statistics the backward reuses (lse).  Both NULL: exactly u2tok_attention_gqa (the same kernel).
-int attention_gqa_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
-                     int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                     int64_t o_bs, float scale, int causal, const int* kv_len, float* lse, int64_t lse_ld,
-                     hipStream_t stream) {
-  return attention_gqa_range(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, causal, nullptr,
-                             kv_len, lse, lse_ld, stream);
-}
-
-// ... and with a first visible key per sequence (kv_start: left padding, the inference routes of prefill.py): key j of sequence b is
-// visible iff kv_start[b] <= j < kv_len[b] (and j <= i + Skv - Sq when causal); a query row without a visible key gets zeros (lse 0).
-int attention_gqa_range(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv,
-                        int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs,
-                        int64_t o_bs, float scale, int causal, const int* kv_start, const int* kv_len, float* lse, int64_t lse_ld,
-                        hipStream_t stream) {
-  if (!kv_len && !lse && !kv_start)
-    return attention_ex(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, nullptr, 0,
-                        causal, 1, nullptr, 0, stream);
-  if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
-  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)kv_start & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq))
-    return U2_ERR_ARG;
-  if (d == 384) return U2_ERR_ARG;  // (the range / statistics form is not built at the tokenizer's 384: no decoder has that head dim)
-  if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
-    return U2_ERR_ARG;
-  TokAttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
-  a.scale_log2e = scale * 1.44269504088896340736f;
-  a.rel_bias = nullptr; a.max_len = 0;
-  a.kv_group = H / Hkv;
-  a.causal = causal ? 1 : 0;
-  a.kv_len = kv_len; a.kv_start = kv_start; a.lse = lse; a.lse_ld = lse_ld;
-  a.k_hs = a.v_hs = d; a.window = 0;
-  a.ns = 1;
-  a.tps = (int)cdiv(Skv, tok_attn_bk(d));
-  a.opart = nullptr; a.ml = nullptr;
-  const int64_t grid = (int64_t)nb * H * a.nqb;
-  if (grid > 0x7fffffff) return U2_ERR_ARG;
-  ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
-               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));
-#define U2_TAX(D_)                                                                                                     \
-  do {                                                                                                                 \
-    constexpr size_t smem_ = 4 * ((D_) <= 128 ? 64 : 32) * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                          \
-    hipLaunchKernelGGL((tok_attn_kernel<D_, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);                \
-  } while (0)
-  if (d == 512) U2_TAX(512);
-  else if (d == 256) U2_TAX(256);
-  else if (d == 128) U2_TAX(128);
-  else if (d == 96) U2_TAX(96);
-  else U2_TAX(64);
-#undef U2_TAX
-  return launch_status();
-}
-
-// ... and with the kv heads of a sequence k_hs / v_hs elements apart (d: the column-packed view of the calls above; capacity * d: the
-// views [:, :, :Skv] of a KV cache's (B, Hkv, capacity, d) buffers, read where they lie with ldk = d) and an attention window: with
-// window = W > 0 (causal only) key j is visible to query i iff i + Skv - Sq - W < j <= i + Skv - Sq -- W keys, the query's own
-// included -- intersected with the key range.  Tiles wholly below the band of a query block are skipped.  d = 64 / 96 / 128.
-// k_hs = v_hs = d and window = 0: exactly attention_gqa_range (and, without a range, attention_gqa).
-int attention_gqa_band(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int nb, int Sq, int Skv, int H, int Hkv, int d,
-                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
-                       int64_t k_hs, int64_t v_hs, int window, float scale, int causal, const int* kv_start, const int* kv_len,
-                       float* lse, int64_t lse_ld, hipStream_t stream) {
-  if (k_hs == d && v_hs == d && window == 0)
-    return attention_gqa_range(q, k, v, out, nb, Sq, Skv, H, Hkv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, causal, kv_start,
-                               kv_len, lse, lse_ld, stream);
-  if (!q || !k || !v || !out || nb <= 0 || Sq <= 0 || Skv <= 0 || H <= 0 || Hkv <= 0 || H % Hkv) return U2_ERR_ARG;
-  if ((causal && Skv < Sq) || ((uintptr_t)kv_len & 3) || ((uintptr_t)kv_start & 3) || ((uintptr_t)lse & 3) || (lse && lse_ld < Sq))
-    return U2_ERR_ARG;
-  if ((d != 64 && d != 96 && d != 128) || window < 0 || (window > 0 && !causal) || k_hs <= 0 || v_hs <= 0 || ((k_hs | v_hs) & 7))
-    return U2_ERR_ARG;
-  if (!tok_attention_supported(q, k, v, out, Sq, Skv, d, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, nullptr, 0))
-    return U2_ERR_ARG;
-  TokAttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-  a.nb = nb; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nqb = (int)cdiv(Sq, 64);
-  a.scale_log2e = scale * 1.44269504088896340736f;
-  a.rel_bias = nullptr; a.max_len = 0;
-  a.kv_group = H / Hkv;
-  a.causal = causal ? 1 : 0;
-  a.kv_len = kv_len; a.kv_start = kv_start; a.lse = lse; a.lse_ld = lse_ld;
-  a.k_hs = k_hs; a.v_hs = v_hs; a.window = window;
-  a.ns = 1;
-  a.tps = (int)cdiv(Skv, tok_attn_bk(d));
-  a.opart = nullptr; a.ml = nullptr;
-  const int64_t grid = (int64_t)nb * H * a.nqb;
-  if (grid > 0x7fffffff) return U2_ERR_ARG;
-  ProfScope ps(PROF_TOKATTN, (causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
-               2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * Hkv));
-#define U2_TAB(D_)                                                                                                     \
-  do {                                                                                                                 \
-    constexpr size_t smem_ = 4 * 64 * (D_) * 2 + TOKATTN_BIAS_SLOTS * 4;                                               \
-    hipLaunchKernelGGL((tok_attn_kernel<D_, true, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);          \
-  } while (0)
-  if (d == 128) U2_TAB(128);
-  else if (d == 96) U2_TAB(96);
-  else U2_TAB(64);
-#undef U2_TAB
   return launch_status();
 }
 

@@ -557,6 +557,37 @@ def flash_attention_d64_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.T
     return dqkv
 
 
+def _kv_len_arg(kv_len, nb: int, device):
+    if kv_len is None:
+        return None
+    if kv_len.dtype != torch.int32 or kv_len.device != device or kv_len.shape != (nb,) or not kv_len.is_contiguous():
+        raise RuntimeError(f"kv_len must be a contiguous int32 ({nb},) tensor on {device}")
+    return kv_len
+
+
+def _attn_call(who: str, q, k, v, heads: int, kv_heads, scale: float, kv_start=None, kv_len=None, cache=None):
+    """What the attention wrappers below share: the checks of q (nb, Sq, heads * d), k / v (nb, Skv, kv_heads * d) -- kv_heads
+    None: tok_attention's equal heads -- and of the key range tensors, the output, and the arguments every C entry point begins
+    with (q ... o_bs, scale) -> (out, args).  cache: attention_gqa_band's 4-D k / v, checked there, as (Skv, ldk, k_bs)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _need(t, ELEM, n)
+        if (t is q or cache is None) and (t.dim() != 3 or t.stride(2) != 1):
+            raise RuntimeError(f"{who}: {n} must be (nb, S, H * d) with a contiguous last dim")
+    nb, Sq, Eq = q.shape
+    d = Eq // heads
+    hk = heads if kv_heads is None else kv_heads
+    Skv, ldk, kbs = cache or (k.shape[1], k.stride(1), k.stride(0))
+    ldv, vbs = (ldk, kbs) if cache else (v.stride(1), v.stride(0))
+    if Eq % heads or k.shape != ((nb, hk, Skv, d) if cache else (nb, Skv, hk * d)) or v.shape != k.shape or heads % hk:
+        raise RuntimeError(f"{who}: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{hk}")
+    for t in (kv_start, kv_len):
+        _kv_len_arg(t, nb, q.device)
+    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    args = [_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads] + ([] if kv_heads is None else [kv_heads]) + \
+           [d, q.stride(1), ldk, ldv, Eq, q.stride(0), kbs, vbs, Sq * Eq, float(scale)]
+    return out, args
+
+
 @_guarded
 def tok_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, rel_bias=None, max_len=512,
                   splits: int = 0) -> torch.Tensor:
@@ -565,23 +596,13 @@ def tok_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     buffer) -> softmax(q k^T scale + rel_bias[j - i + max_len - 1][h]) v as (nb, Sq, E).  splits: 0 = heuristic key split.
     Head dim E / heads in {64, 96, 128, 256, 384, 512}."""
     h = _lib.load_library()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _need(t, ELEM, n)
-        if t.dim() != 3 or t.stride(2) != 1:
-            raise RuntimeError(f"tok_attention: {n} must be (nb, S, E) with a contiguous last dim")
-    nb, Sq, E = q.shape
-    Skv = k.shape[1]
-    if k.shape != (nb, Skv, E) or v.shape != (nb, Skv, E) or E % heads:
-        raise RuntimeError(f"tok_attention: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}")
-    d = E // heads
-    out = torch.empty((nb, Sq, E), dtype=elem_dtype(), device=q.device)
-    nbytes = h.u2tok_tok_attention_workspace_bytes(nb, heads, Sq, Skv, d)
+    out, args = _attn_call("tok_attention", q, k, v, heads, None, scale)
+    nb, Sq, E = out.shape
+    nbytes = h.u2tok_tok_attention_workspace_bytes(nb, heads, Sq, k.shape[1], E // heads)
     if splits > 1:
         nbytes = max(nbytes, splits * nb * Sq * (E * 4 + heads * 8))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-    _lib.check(h.u2tok_tok_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, d, q.stride(1), k.stride(1),
-                                     v.stride(1), E, q.stride(0), k.stride(0), v.stride(0), Sq * E, float(scale),
-                                     _ptr(rel_bias), max_len, int(splits), _ptr(ws), ws.numel(), _stream()),
+    _lib.check(h.u2tok_tok_attention(*args, _ptr(rel_bias), max_len, int(splits), _ptr(ws), ws.numel(), _stream()),
                "u2tok_tok_attention")
     return out
 
@@ -595,27 +616,14 @@ def attention_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     split_keys (not causal): key ranges on separate workgroups, merged in a fixed order (u2tok_attention_gqa_split) -- few
     query rows over a long KV cache (decode steps)."""
     h = _lib.load_library()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _need(t, ELEM, n)
-        if t.dim() != 3 or t.stride(2) != 1:
-            raise RuntimeError(f"attention_gqa: {n} must be (nb, S, H * d) with a contiguous last dim")
-    nb, Sq, Eq = q.shape
-    Skv = k.shape[1]
-    d = Eq // heads
-    if Eq % heads or k.shape != (nb, Skv, kv_heads * d) or v.shape != k.shape or heads % kv_heads:
-        raise RuntimeError(f"attention_gqa: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}")
-    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    out, args = _attn_call("attention_gqa", q, k, v, heads, kv_heads, scale)
     if split_keys and not causal:
-        nbytes = h.u2tok_tok_attention_workspace_bytes(nb, heads, Sq, Skv, d)
+        nb, Sq, Eq = out.shape
+        nbytes = h.u2tok_tok_attention_workspace_bytes(nb, heads, Sq, k.shape[1], Eq // heads)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-        _lib.check(h.u2tok_attention_gqa_split(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
-                                               k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
-                                               float(scale), _ptr(ws) if nbytes else None, nbytes, _stream()),
-                   "u2tok_attention_gqa_split")
+        _lib.check(h.u2tok_attention_gqa_split(*args, _ptr(ws) if nbytes else None, nbytes, _stream()), "u2tok_attention_gqa_split")
         return out
-    _lib.check(h.u2tok_attention_gqa(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
-                                     k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
-                                     float(scale), int(bool(causal)), _stream()), "u2tok_attention_gqa")
+    _lib.check(h.u2tok_attention_gqa(*args, int(bool(causal)), _stream()), "u2tok_attention_gqa")
     return out
 
 
@@ -992,14 +1000,6 @@ def weight_table(tensors) -> "C.Array":
 
 
 # ---------------------------------------------------------------------------------- decoder training route (decoder_train.py)
-def _kv_len_arg(kv_len, nb: int, device):
-    if kv_len is None:
-        return None
-    if kv_len.dtype != torch.int32 or kv_len.device != device or kv_len.shape != (nb,) or not kv_len.is_contiguous():
-        raise RuntimeError(f"kv_len must be a contiguous int32 ({nb},) tensor on {device}")
-    return kv_len
-
-
 @_guarded
 def attention_gqa_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, scale: float,
                      kv_len: Optional[torch.Tensor] = None, with_lse: bool = False, causal: bool = True):
@@ -1007,22 +1007,11 @@ def attention_gqa_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     j < kv_len[b] (int32 (nb,) on the GPU, >= 1; None: all).  with_lse: also returns the row statistics the backward reuses,
     (nb * heads, Sq) fp32 in log2 units -> (out, lse | None)."""
     h = _lib.load_library()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _need(t, ELEM, n)
-        if t.dim() != 3 or t.stride(2) != 1:
-            raise RuntimeError(f"attention_gqa_ex: {n} must be (nb, S, H * d) with a contiguous last dim")
-    nb, Sq, Eq = q.shape
-    Skv = k.shape[1]
-    d = Eq // heads
-    if Eq % heads or k.shape != (nb, Skv, kv_heads * d) or v.shape != k.shape or heads % kv_heads:
-        raise RuntimeError(f"attention_gqa_ex: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}")
-    kv_len = _kv_len_arg(kv_len, nb, q.device)
-    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
+    out, args = _attn_call("attention_gqa_ex", q, k, v, heads, kv_heads, scale, kv_len=kv_len)
+    nb, Sq, _ = out.shape
     lse = torch.empty((nb * heads, Sq), dtype=torch.float32, device=q.device) if with_lse else None
-    _lib.check(h.u2tok_attention_gqa_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
-                                        k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
-                                        float(scale), int(bool(causal)), _ptr(kv_len), _ptr(lse), Sq if with_lse else 0,
-                                        _stream()), "u2tok_attention_gqa_ex")
+    _lib.check(h.u2tok_attention_gqa_ex(*args, int(bool(causal)), _ptr(kv_len), _ptr(lse), Sq if with_lse else 0, _stream()),
+               "u2tok_attention_gqa_ex")
     return out, lse
 
 
@@ -1035,20 +1024,8 @@ def attention_gqa_range(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads
     of a left-padded (kv_start) or right-padded (kv_len) batch.  A query row that sees no key gets zeros.  Both None: the
     kernel, and the bits, of attention_gqa."""
     h = _lib.load_library()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _need(t, ELEM, n)
-        if t.dim() != 3 or t.stride(2) != 1:
-            raise RuntimeError(f"attention_gqa_range: {n} must be (nb, S, H * d) with a contiguous last dim")
-    nb, Sq, Eq = q.shape
-    Skv = k.shape[1]
-    d = Eq // heads
-    if Eq % heads or k.shape != (nb, Skv, kv_heads * d) or v.shape != k.shape or heads % kv_heads:
-        raise RuntimeError(f"attention_gqa_range: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}")
-    kv_start, kv_len = _kv_len_arg(kv_start, nb, q.device), _kv_len_arg(kv_len, nb, q.device)
-    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
-    _lib.check(h.u2tok_attention_gqa_range(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1),
-                                           k.stride(1), v.stride(1), Eq, q.stride(0), k.stride(0), v.stride(0), Sq * Eq,
-                                           float(scale), int(bool(causal)), _ptr(kv_start), _ptr(kv_len), None, 0, _stream()),
+    out, args = _attn_call("attention_gqa_range", q, k, v, heads, kv_heads, scale, kv_start, kv_len)
+    _lib.check(h.u2tok_attention_gqa_range(*args, int(bool(causal)), _ptr(kv_start), _ptr(kv_len), None, 0, _stream()),
                "u2tok_attention_gqa_range")
     return out
 
@@ -1065,38 +1042,20 @@ def attention_gqa_band(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads:
     sees no key gets zeros.  d in {64, 96, 128} for a window or a 4-D view.  No window, 3-D views: the kernel, and the bits, of
     attention_gqa_range (no range either: of attention_gqa)."""
     h = _lib.load_library()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _need(t, ELEM, n)
-    if q.dim() != 3 or q.stride(2) != 1:
-        raise RuntimeError("attention_gqa_band: q must be (nb, S, H * d) with a contiguous last dim")
-    nb, Sq, Eq = q.shape
-    d = Eq // heads
+    d = q.shape[-1] // heads
+    cache, khs = None, d
     if k.dim() == 4:
         if v.shape != k.shape or v.stride() != k.stride() or k.stride(3) != 1 or k.stride(2) != d \
                 or k.stride(0) != kv_heads * k.stride(1):
             raise RuntimeError(f"attention_gqa_band: k / v {tuple(k.shape)} strides {k.stride()}, {v.stride()} must be equal "
                                "(B, kv_heads, T, d) views of (B, kv_heads, cap, d) buffers")
-        Skv = k.shape[2]
-        ok = k.shape == (nb, kv_heads, Skv, d)
-        ldk, kbs, khs = d, k.stride(0), k.stride(1)
-        ldv, vbs = ldk, kbs
-    else:
-        for t, n in ((k, "k"), (v, "v")):
-            if t.dim() != 3 or t.stride(2) != 1:
-                raise RuntimeError(f"attention_gqa_band: {n} must be (nb, S, H * d) with a contiguous last dim or a 4-D cache view")
-        Skv = k.shape[1]
-        ok = k.shape == (nb, Skv, kv_heads * d) and v.shape == k.shape
-        ldk, kbs, khs = k.stride(1), k.stride(0), d
-        ldv, vbs = v.stride(1), v.stride(0)
+        cache, khs = (k.shape[2], d, k.stride(0)), k.stride(1)
     W = int(window or 0)
-    if Eq % heads or not ok or heads % kv_heads or W < 0 or (W and not causal):
-        raise RuntimeError(f"attention_gqa_band: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, heads {heads}/{kv_heads}, "
-                           f"window {window}")
-    kv_start, kv_len = _kv_len_arg(kv_start, nb, q.device), _kv_len_arg(kv_len, nb, q.device)
-    out = torch.empty((nb, Sq, Eq), dtype=elem_dtype(), device=q.device)
-    _lib.check(h.u2tok_attention_gqa_band(_ptr(q), _ptr(k), _ptr(v), _ptr(out), nb, Sq, Skv, heads, kv_heads, d, q.stride(1), ldk, ldv,
-                                          Eq, q.stride(0), kbs, vbs, Sq * Eq, float(scale), int(bool(causal)), _ptr(kv_start),
-                                          _ptr(kv_len), None, 0, khs, khs, W, _stream()), "u2tok_attention_gqa_band")
+    if W < 0 or (W and not causal):
+        raise RuntimeError(f"attention_gqa_band: window {window}" + ("" if causal else " without the causal mask"))
+    out, args = _attn_call("attention_gqa_band", q, k, v, heads, kv_heads, scale, kv_start, kv_len, cache)
+    _lib.check(h.u2tok_attention_gqa_band(*args, int(bool(causal)), _ptr(kv_start), _ptr(kv_len), None, 0, khs, khs, W, _stream()),
+               "u2tok_attention_gqa_band")
     return out
 
 
