@@ -595,6 +595,31 @@ size_t u2tok_sample_warp_workspace_bytes(int32_t rows, int32_t V);
 int u2tok_sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
                       int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
+/* ---- rank-r adapter (LoRA) products of the decoder training route (csrc/lora.hip; u2tokenizer_amd/decoder_train.py: LoraDeltaFn) ----
+ * Three bandwidth-bound kernels for r in {16, 32, 64}, outside u2tok_gemm_bf16's plan.  All operands are 16-bit elements of the
+ * build's type with unit column stride and a leading dimension in elements (multiples of 8; base pointers 16-byte aligned); the big
+ * operand also takes an element offset (a multiple of 8), so that a column segment of a packed q|k|v or gate|up activation or
+ * gradient is read and written in place.  fp32 accumulation on v_mfma_f32_16x16x32, alpha applied to the fp32 sum, ONE rounding at the
+ * store; no atomics, every sum in a fixed order: two calls give the same bits (u2tok_lora_wgrad: for the same workspace_bytes).
+ * U2TOK_ERR_ARG, nothing launched: r outside {16, 32, 64}, a shape outside the contract below, a null or misaligned pointer,
+ * a leading dimension shorter than its row.
+ *
+ * u2tok_lora_down:  U (M, r) = alpha X (M, K) A (r, K)^T, K % 32 == 0.  X = X + x_off, rows ldx apart.
+ * u2tok_lora_up:    Y (M, N) = [Y +] alpha U (M, r) W (N, r)^T, N % 16 == 0.  Y = Y + y_off, rows ldy apart; accumulate != 0 reads Y:
+ *                   float(Y) + alpha acc in fp32 (one fused multiply-add), rounded once; accumulate == 0 never reads Y.  Columns
+ *                   of Y's buffer outside [y_off, y_off + N) are neither read nor written.
+ * u2tok_lora_wgrad: G (r, C) = alpha U (M, r)^T X (M, C), the contraction over the M rows, C % 8 == 0.  X = X + x_off.  G: elements
+ *                   (out_f32 == 0) or fp32 (out_f32 != 0), rows ldg apart.  workspace (optional, 16-byte aligned): with room for s >= 2
+ *                   fp32 (r, C) tiles the rows are cut into up to s fixed ranges across workgroups and a second launch adds the
+ *                   ranges' tiles in order; 512 / ceil(C / 64) tiles are as many as are ever used.  Without one, a 64-column strip
+ *                   of X is one workgroup's. */
+int u2tok_lora_down(const void* X, int64_t x_off, int64_t ldx, const void* A, int64_t lda, void* U, int64_t ldu, int32_t M, int32_t K,
+                    int32_t r, float alpha, u2tok_stream_t stream);
+int u2tok_lora_up(const void* U, int64_t ldu, const void* W, int64_t ldw, void* Y, int64_t y_off, int64_t ldy, int32_t M, int32_t N,
+                  int32_t r, float alpha, int32_t accumulate, u2tok_stream_t stream);
+int u2tok_lora_wgrad(const void* U, int64_t ldu, const void* X, int64_t x_off, int64_t ldx, void* G, int64_t ldg, int32_t M, int32_t C,
+                     int32_t r, float alpha, int32_t out_f32, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

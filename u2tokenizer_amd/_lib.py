@@ -183,6 +183,12 @@ SIGNATURES = {
     "u2tok_sample_warp_workspace_bytes": (_sz, [_i32, _i32]),
     # logits, ld_in, out, ld_out, rows, V, temperature, top_k, top_p, min_keep, workspace, workspace_bytes, stream
     "u2tok_sample_warp": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _sz, _vp]),
+    # X, x_off, ldx, A, lda, U, ldu, M, K, r, alpha, stream
+    "u2tok_lora_down": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    # U, ldu, W, ldw, Y, y_off, ldy, M, N, r, alpha, accumulate, stream
+    "u2tok_lora_up": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    # U, ldu, X, x_off, ldx, G, ldg, M, C, r, alpha, out_f32, workspace, workspace_bytes, stream
+    "u2tok_lora_wgrad": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _sz, _vp]),
 }
 
 ERRORS = {-1: "U2TOK_ERR_ARG (bad dimension / null pointer / unsupported combination)",

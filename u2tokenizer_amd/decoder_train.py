@@ -18,6 +18,9 @@ torch.autograd.Functions over the C-ABI blocks, each saving what its backward ne
     dq | dk | dv straight into one packed gradient;
   * RMSNorm, head norm + rotary and SwiGLU have their backward kernels in csrc/backward.hip (fixed-order fp32 weight gradients);
   * torch moves data and adds the residual stream's two gradient contributions.
+  * with `train_lora=True` / `config.u2_fused_lora_training = True` on top, a LoRA-wrapped projection (lora.adapter_of) adds its
+    branch after the packed product it belongs to (LoraDeltaFn, on the rank-r kernels of csrc/lora.hip); the frozen base weights
+    need no dW product.
 
 When a layer takes the route (prefill.route, decided on every call; everything else keeps the stock forward): bf16 on the
 GPU, every projection exactly nn.Linear with no hooks, no active attention or residual dropout, head dim 64 or 128 (train_phi3:
@@ -36,10 +39,13 @@ from torch.autograd import Function
 
 from . import ops
 from .autograd import _bind_context
+from .lora import adapter_of
 
 # layers whose forward took the training route (tests read it: a route that silently fell back to the stock layers would
 # otherwise pass every gradient check)
 stats = {"layers": 0}
+# ... and, of those, the layers that ran with at least one LoRA adapter on the rank-r kernels, and the adapters they ran
+lora_stats = {"layers": 0, "adapters": 0}
 
 
 def train_mask_rule(mask: Optional[torch.Tensor]):
@@ -145,6 +151,89 @@ def packed_linear(x, linears, W, b, res=None):
 
 
 @_bind_context
+class LoraDeltaFn(Function):
+    """y[:, o_i : o_i + N_i] += s_i (xd_i A_i^T) B_i^T for the n adapters of one packed product: `y` (rows, sum N) is the output
+    of PackedLinearFn, `meta` = ((o_i, N_i, s_i), ...), then xd_0 .. xd_n-1 (rows, K: the product's input after each adapter's own
+    dropout), A_0 .. A_n-1 (r, K) and B_0 .. B_n-1 (N_i, r), the adapters' Parameters.
+
+    IN PLACE on y's memory, returned as a NEW tensor over it: PackedLinearFn hands its output on as a view made inside a Function,
+    which autograd lets no later Function mark dirty, and a copy would double the branch's traffic.  The caller drops the old
+    tensor (lora_delta rebinds the name), and nothing has saved it: PackedLinearFn saves its inputs, not its output.  The version
+    counter the two tensors share is bumped, so autograd would refuse a backward that did read the old values.
+    Rounding points: A and B in the element type (fp32 adapter weights get a 16-bit compute copy per call: they are r x K small),
+    xd in the element type, u_i = xd_i A_i^T rounded to the element type (u2tok_lora_down), and ONE rounding of y: float(y) +
+    s_i u_i B_i^T in fp32 (u2tok_lora_up, accumulate form) -- the stock wrapped layer rounds u, u B^T, the scaling and the sum.
+    Backward: dy passes through to the base product; du_i = s_i dy_i B_i (u2tok_lora_down on a contiguous B^T), dB_i^T = s_i
+    u_i^T dy_i and dA_i = du_i^T xd_i (u2tok_lora_wgrad; fp32 results for fp32 Parameters), d xd_i = du_i A_i (u2tok_lora_up on a
+    contiguous A^T), which autograd carries back through torch's dropout."""
+
+    @staticmethod
+    def forward(ctx, y, meta, *ts):
+        n = len(meta)
+        xds, As, Bs = ts[:n], ts[n:2 * n], ts[2 * n:]
+        y = y.detach()
+        saved = []
+        for (o, N, s), xd, A, B in zip(meta, xds, As, Bs):
+            A16, B16 = A.detach().to(y.dtype), B.detach().to(y.dtype)
+            u = ops.lora_down(xd, A16)
+            ops.lora_up(u, B16, y[:, o:o + N], alpha=s, accumulate=True)
+            saved += [xd, u, A16, B16]
+        torch.autograd.graph.increment_version(y)   # (the kernels wrote through raw pointers: tell autograd)
+        ctx.save_for_backward(*saved)
+        ctx.meta = meta
+        ctx.f32 = [(A.dtype == torch.float32, B.dtype == torch.float32) for A, B in zip(As, Bs)]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        meta, n = ctx.meta, len(ctx.meta)
+        need = ctx.needs_input_grad
+        if dy.stride(1) != 1:
+            dy = dy.contiguous()
+        dxd, dA, dB = [None] * n, [None] * n, [None] * n
+        saved = ctx.saved_tensors   # (read once: under checkpointing the first read runs the recompute)
+        for i, (o, N, s) in enumerate(meta):
+            xd, u, A16, B16 = saved[4 * i:4 * i + 4]
+            a32, b32 = ctx.f32[i]
+            dyi = dy[:, o:o + N]
+            if need[2 + 2 * n + i]:
+                dB[i] = ops.lora_wgrad(u, dyi, alpha=s, out_f32=b32).t()
+            if need[2 + i] or need[2 + n + i]:
+                du = ops.lora_down(dyi, B16.t().contiguous(), alpha=s)
+                if need[2 + n + i]:
+                    dA[i] = ops.lora_wgrad(du, xd, out_f32=a32)
+                if need[2 + i]:
+                    dxd[i] = ops.lora_up(du, A16.t().contiguous())
+        return (dy, None, *dxd, *dA, *dB)
+
+
+def lora_delta(y, x2, modules, B: int, S: int):
+    """Add the adapter branches of the wrapped ones among `modules` (the projections of one packed product, in packing order: q, k,
+    v / o / gate, up / down -- the order in which the stock layer calls them, so that the same seed draws the same dropout masks)
+    to the product's output `y` (B S, sum N); x2 (B S, K) the product's input.  Each adapter's OWN dropout module is called on the
+    input in its stock (B, S, K) shape and in the adapter weights' dtype, as the stock wrapped projection calls it.  Without a
+    wrapped projection y comes back as it is."""
+    meta, xds, As, Bs = [], [], [], []
+    o = 0
+    for m in modules:
+        N = m.weight.shape[0]
+        if type(m) is not torch.nn.Linear:
+            ad = adapter_of(m)
+            if ad is None:   # (route() admitted the layer: the module changed under the call)
+                raise RuntimeError(f"decoder training route: {type(m).__name__} is not an adapter the route computes")
+            xa = x2.view(B, S, -1)
+            if ad.A.weight.dtype != xa.dtype:
+                xa = xa.to(ad.A.weight.dtype)
+            xd = ad.dropout(xa).to(x2.dtype).reshape(B * S, -1)
+            meta.append((o, N, ad.scaling))
+            xds.append(xd), As.append(ad.A.weight), Bs.append(ad.B.weight)
+        o += N
+    if not meta:
+        return y
+    return LoraDeltaFn.apply(y, tuple(meta), *xds, *As, *Bs)
+
+
+@_bind_context
 class RMSNormFn(Function):
     """y = bf16(x rstd) * w  (LlamaRMSNorm / Qwen3RMSNorm); backward u2tok_rmsnorm_bwd."""
 
@@ -237,19 +326,27 @@ def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     stats["layers"] += 1   # (counted on entry: a checkpoint recompute stops early, once the tensors it needs are back)
+    n_ad = sum(type(m) is not torch.nn.Linear for m in lo.projections(layer))
+    if n_ad:
+        lora_stats["layers"] += 1
+        lora_stats["adapters"] += n_ad
     Wqkv, bqkv = lo.qkv(layer)
     Wgu, bgu = lo.gate_up(layer)
     xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
     qkv = packed_linear(xn, lo.qkv_linears(layer), Wqkv.detach(), None if bqkv is None else bqkv.detach())
+    qkv = lora_delta(qkv, xn, lo.qkv_linears(layer), B, S)
     qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
     qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv,
                                d, float(qn.variance_epsilon) if qn is not None else 1e-6)
     ctx = GqaAttentionFn.apply(qkv, kv_len, B, S, Hq, Hkv, d, float(att.scaling))
     h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
                       att.o_proj.bias.detach(), res=x2)
+    h = lora_delta(h, ctx, (att.o_proj,), B, S)
     hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
     gu = packed_linear(hn, lo.gate_up_linears(layer), Wgu.detach(), None if bgu is None else bgu.detach())
+    gu = lora_delta(gu, hn, lo.gate_up_linears(layer), B, S)
     act = SwiGLUFn.apply(gu)
     out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
                         None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)
+    out = lora_delta(out, act, (mlp.down_proj,), B, S)
     return out.view(B, S, -1)

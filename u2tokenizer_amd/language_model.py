@@ -67,10 +67,12 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         products on e4m3 copies of the weights, prefill.py `_w8_state`) and `config.u2_fused_wide_decode` (default False: decode
         steps of 17 .. 64 sequences on the fused step), are passed on as the config has them, and so is
         `config.u2_fused_phi3_training` (default False; it implies the training route: head dim 96 and the packed Phi-3 layout
-        on it, `enable_fused_prefill(..., train=True, train_phi3=True)`)."""
+        on it, `enable_fused_prefill(..., train=True, train_phi3=True)`) and `config.u2_fused_lora_training` (default False; it
+        implies the training route too: LoRA-wrapped projections on it, `enable_fused_prefill(..., train_lora=True)`)."""
         grad = torch.is_grad_enabled()
         train_phi3 = bool(getattr(self.config, "u2_fused_phi3_training", False))   # (implies the training route)
-        train = bool(getattr(self.config, "u2_fused_decoder_training", False)) or train_phi3
+        train_lora = bool(getattr(self.config, "u2_fused_lora_training", False))   # (implies the training route as well)
+        train = bool(getattr(self.config, "u2_fused_decoder_training", False)) or train_phi3 or train_lora
         prefill = bool(getattr(self.config, "u2_fused_prefill", True))
         checked = self.__dict__.setdefault("_u2_fuse_checked", set())
         if grad in checked or not (train if grad else prefill):
@@ -90,6 +92,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                 padded["wide_decode"] = True
             if train_phi3:   # (default False: head dim 96 and the packed Phi-3 layout on the training route)
                 padded["train_phi3"] = True
+            if train_lora:   # (default False: LoRA-wrapped projections on the training route, decoder_train.LoraDeltaFn)
+                padded["train_lora"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 

@@ -826,6 +826,91 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, out
     return out
 
 
+# ---------------------------------------------------------------------------------- rank-r adapter (LoRA) products
+def _segment(t: torch.Tensor, name: str):
+    """A 2-D view with unit column stride -> (tensor, element offset 0, row stride): the kernels take a column segment of a packed
+    buffer as the view's own address and the buffer's row stride."""
+    _need(t, ELEM, name)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise RuntimeError(f"{name}: expected a 2-D tensor with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+@_guarded
+def lora_down(x: torch.Tensor, a: torch.Tensor, alpha: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """U (M, r) = alpha x (M, K) a (r, K)^T (u2tok_lora_down): r in {16, 32, 64}, K % 32 == 0.  x may be a column segment of a wider
+    buffer (a row-strided view); a and out likewise row-strided.  Anything the kernel does not take raises."""
+    h = _lib.load_library()
+    x, a = _segment(x, "x"), _segment(a, "a")
+    M, K = x.shape
+    r = a.shape[0]
+    if a.shape[1] != K:
+        raise RuntimeError(f"lora_down: shapes x {tuple(x.shape)}, a {tuple(a.shape)}")
+    if out is None:
+        out = torch.empty((M, r), dtype=elem_dtype(), device=x.device)
+    _segment(out, "out")
+    if out.shape != (M, r):
+        raise RuntimeError("lora_down: out must be (M, r)")
+    st = h.u2tok_lora_down(_ptr(x), 0, x.stride(0), _ptr(a), a.stride(0), _ptr(out), out.stride(0), M, K, r, float(alpha), _stream())
+    _lib.check(st, "u2tok_lora_down")
+    return out
+
+
+@_guarded
+def lora_up(u: torch.Tensor, w: torch.Tensor, y: Optional[torch.Tensor] = None, alpha: float = 1.0,
+            accumulate: bool = False) -> torch.Tensor:
+    """y (M, N) = [y +] alpha u (M, r) w (N, r)^T (u2tok_lora_up), in place on `y` -- which may be a column segment of a wider buffer,
+    whose other columns are not touched; accumulate: float(y) + the product, rounded once.  y None (accumulate False): a new
+    tensor.  r in {16, 32, 64}, N % 16 == 0."""
+    h = _lib.load_library()
+    u, w = _segment(u, "u"), _segment(w, "w")
+    M, r = u.shape
+    N = w.shape[0]
+    if w.shape[1] != r:
+        raise RuntimeError(f"lora_up: shapes u {tuple(u.shape)}, w {tuple(w.shape)}")
+    if y is None:
+        if accumulate:
+            raise RuntimeError("lora_up: accumulate needs y")
+        y = torch.empty((M, N), dtype=elem_dtype(), device=u.device)
+    _segment(y, "y")
+    if y.shape != (M, N):
+        raise RuntimeError("lora_up: y must be (M, N)")
+    st = h.u2tok_lora_up(_ptr(u), u.stride(0), _ptr(w), w.stride(0), _ptr(y), 0, y.stride(0), M, N, r, float(alpha), int(accumulate),
+                         _stream())
+    _lib.check(st, "u2tok_lora_up")
+    return y
+
+
+def lora_wgrad_workspace_bytes(M: int, C: int, r: int) -> int:
+    """The most u2tok_lora_wgrad uses: one fp32 (r, C) tile per row range, min(ceil(M / 128), 512 // ceil(C / 64)) ranges (0: one)."""
+    s = min(-(-M // 128), max(1, 512 // -(-C // 64)))
+    return s * r * C * 4 if s > 1 else 0
+
+
+@_guarded
+def lora_wgrad(u: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, out_f32: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """G (r, C) = alpha u (M, r)^T x (M, C), the contraction over the rows (u2tok_lora_wgrad); G in the element type or fp32.  x may
+    be a column segment of a wider buffer.  r in {16, 32, 64}, C % 8 == 0."""
+    h = _lib.load_library()
+    u, x = _segment(u, "u"), _segment(x, "x")
+    M, r = u.shape
+    C = x.shape[1]
+    if x.shape[0] != M:
+        raise RuntimeError(f"lora_wgrad: shapes u {tuple(u.shape)}, x {tuple(x.shape)}")
+    dt = torch.float32 if out_f32 else elem_dtype()
+    if out is None:
+        out = torch.empty((r, C), dtype=dt, device=u.device)
+    if out.shape != (r, C) or out.stride(1) != 1 or out.dtype != dt:
+        raise RuntimeError("lora_wgrad: out must be (r, C) with unit column stride in the output type")
+    nb = lora_wgrad_workspace_bytes(M, C, r)
+    ws = torch.empty(nb, dtype=torch.uint8, device=u.device) if nb else None
+    st = h.u2tok_lora_wgrad(_ptr(u), u.stride(0), _ptr(x), 0, x.stride(0), _ptr(out), out.stride(0), M, C, r, float(alpha),
+                            int(out_f32), _ptr(ws), nb, _stream())
+    _lib.check(st, "u2tok_lora_wgrad")
+    return out
+
+
 @_guarded
 def rope_apply(x: torch.Tensor, n_outer, S, n_inner, H, d, max_len=512, inverse=False):
     h = _lib.load_library()

@@ -51,6 +51,7 @@ import torch
 from transformers import cache_utils
 
 from . import decoder_train, ops
+from .lora import adapter_of
 
 # the HF cache classes the fused steps work with (None where this transformers lacks one: before 4.56 no per-layer caches)
 _DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
@@ -106,6 +107,7 @@ def pad_rule(mask):
 
 def _pack(linears):
     """Lay the weights (and biases, if any) of `linears` back to back in one buffer; returns (W, b | None)."""
+    linears = [getattr(lin, "base_layer", lin) for lin in linears]   # (an adapter-wrapped projection: its base layer)
     ws = [lin.weight for lin in linears]
     es = ws[0].element_size()
     st0 = ws[0].untyped_storage()
@@ -276,6 +278,20 @@ def _is_stock(layer, projections) -> bool:
     return True
 
 
+def _is_stock_or_lora(layer, projections) -> bool:
+    """_is_stock for the training route under the train_lora switch: a projection may also be an adapter the route computes
+    (lora.adapter_of: the layout of peft's lora.Linear, read attribute by attribute; anything it does not understand is refused,
+    hooks on the wrapper, its base layer, A or B included)."""
+    for m in projections:
+        if type(m) is not torch.nn.Linear and adapter_of(m) is None:
+            return False
+    for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
+        for t in _HOOK_TABLES:
+            if getattr(m, t, None):
+                return False
+    return True
+
+
 @dataclass(slots=True, eq=False)
 class _StackState:
     """enable_fused_prefill's state on a decoder stack: the route switches, the pre-hook's verdict on the call's 2-D mask,
@@ -284,6 +300,7 @@ class _StackState:
     decode: bool = True
     train: bool = False
     train_phi3: bool = False
+    train_lora: bool = False
     prefill: bool = True
     padded: bool = False
     continued: bool = False
@@ -344,7 +361,8 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     # weights' type (bf16 weights under an fp16 autocast hand fp16 activations on), stock projections without hooks
     if args or "past_key_value" in kwargs or kwargs.get("output_attentions") or not is_cuda or len(shape) != 3 \
             or shape[1] < 1 or pr[0].weight.dtype != dtype or pe is None or pe[0].shape[-1] != att.head_dim \
-            or not _is_stock(layer, pr) or not lo.ready(layer, att):
+            or not (_is_stock_or_lora(layer, pr) if grad and stack.train_lora else _is_stock(layer, pr)) \
+            or not lo.ready(layer, att):
         return "stock", None
     if grad:
         # a layout and a head dim the route computes (train_phi3: the packed Phi-3 layout and head dim 96 too), no KV cache, no
@@ -815,7 +833,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
-                         train_phi3: bool = False, wide_decode: bool = False) -> int:
+                         train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -847,7 +865,14 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     stock layers: the weights are streamed once per step however many sequences share it, each block of 16 sequences computes
     the bits it would in a step of its own (csrc/rows64.h), and it composes with fp8_decode, Phi-3 layers and the
     append-in-place cache.  `wide_stats` counts these steps per layer call.  Off, batch 17 takes the stock layers as before.
-    The eight switches are set anew by every call.
+    train_lora=True (opt-in; it implies train=True): the training route also takes a layer whose projections are LoRA-wrapped --
+    u2tokenizer_amd.lora.LoRALinear or a module of the same layout (peft's lora.Linear, duck-typed: `lora.adapter_of` lists what
+    qualifies: one active unmerged adapter, r in {16, 32, 64}, bias-free nn.Linear A / B in bf16 or fp32, no DoRA or other variant,
+    no hooks) -- and adds the adapter branch on the rank-r kernels of csrc/lora.hip (decoder_train.LoraDeltaFn); the frozen base
+    weights get no gradient product.  It composes with train_phi3 (one adapter over the packed qkv_proj / gate_up_proj).  Off, a
+    wrapped projection keeps the stock forward under every switch, as before; the prefill and decode routes always do (merge
+    the adapters first: lora.merge_lora).  `decoder_train.lora_stats` counts these layers and their adapters.
+    The nine switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -867,7 +892,8 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     stack = base.__dict__.get("_u2_stack")
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
-    stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train), bool(prefill), bool(padded)
+    stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train) or bool(train_lora), bool(prefill), bool(padded)
+    stack.train_lora = bool(train_lora)
     stack.continued, stack.fp8, stack.train_phi3 = bool(continued), bool(fp8_decode), bool(train_phi3)
     stack.wide = bool(wide_decode)
     stack.pad = stack.pad_shape = None
