@@ -369,11 +369,32 @@ typedef struct u2tok_decode_config {
   int32_t B, E, Hq, Hkv, D, I; /* new tokens (= batch), hidden size, query / key-value heads, head dim, MLP width */
   float eps, qk_eps, scale;    /* RMSNorm eps, q / k norm eps, softmax scale */
 } u2tok_decode_config;
+/* Unmerged adapters (LoRA) of the step, `layer->lora` (NULL: none).  Each of the four products carries the segments of
+ * u2tok_lora_rows (below) that are added to it: q|k|v up to 3 (a packed qkv_proj: one), o up to 1, gate|up up to 2 (a packed
+ * gate_up_proj: one), down up to 1; n_* = 0 leaves the product alone.  The group product runs after the product it belongs to --
+ * q|k|v: before the head norm and the rotary embedding, so the cache receives adapted keys and values; o and down: after the
+ * residual epilogue, Y = rnd(float(Y) + scale u B^T) --, on base weights in the element type or in e4m3 alike.  With a gate or up
+ * segment the pair product takes its unfused form (product, group, SiLU(gate) * up).  `scratch` (16-byte aligned) is the branch's
+ * own: 24576 bytes for u (64 rows of 192 elements) followed by the largest u2tok_lora_rows_workspace_bytes of the four groups;
+ * u2tok_decoder_decode_workspace_bytes keeps its values.  A segment list u2tok_lora_rows refuses, a count outside its range or a
+ * short scratch: U2TOK_ERR_ARG / U2TOK_ERR_WORKSPACE from pre (q|k|v) or post (o, gate|up, down) before anything is launched. */
+typedef struct u2tok_lora_seg {
+  const void *A, *B;     /* A (r, K), B (N, r): contiguous, element type, 16-byte aligned */
+  int32_t r, col0, N;    /* rank; the segment's columns [col0, col0 + N) of Y */
+  float scale;
+} u2tok_lora_seg;
+typedef struct u2tok_decode_lora {
+  u2tok_lora_seg qkv[3], o[1], gu[2], down[1];
+  int32_t n_qkv, n_o, n_gu, n_down;
+  void* scratch;
+  size_t scratch_bytes;
+} u2tok_decode_lora;
 typedef struct u2tok_decode_layer {
   const void *w_in_norm, *Wqkv, *bqkv, *wq_norm, *wk_norm;       /* first half */
   const void *Wo, *bo, *w_post_norm, *Wgu, *bgu, *Wdown, *bdown; /* second half */
   const float *scale_qkv, *scale_o, *scale_gu, *scale_down;      /* all NULL: weights in the element type;
                                                                     all set: the four W* are e4m3 codes, a scale per row */
+  const u2tok_decode_lora* lora;                                 /* unmerged adapters of the step; NULL: none */
 } u2tok_decode_layer;
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* cfg, int32_t T);
 int u2tok_decoder_decode_pre(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* cos,
@@ -619,6 +640,24 @@ int u2tok_lora_up(const void* U, int64_t ldu, const void* W, int64_t ldw, void* 
                   int32_t r, float alpha, int32_t accumulate, u2tok_stream_t stream);
 int u2tok_lora_wgrad(const void* U, int64_t ldu, const void* X, int64_t x_off, int64_t ldx, void* G, int64_t ldg, int32_t M, int32_t C,
                      int32_t r, float alpha, int32_t out_f32, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+
+/* ---- the adapter branch of one packed product for a few rows, as a group (csrc/lora_rows.hip): what a decode step adds for its
+ * unmerged adapters, in two launches however many of the product's projections are wrapped.  1 <= n <= 3 segments (u2tok_lora_seg,
+ * above) share the input X (M, K), 1 <= M <= 64, K % 32 == 0; r_i in {16, 32, 64} (they may differ), N_i % 16 == 0, col0_i % 16 == 0,
+ * column ranges disjoint (gaps allowed).  X, U and Y are row-strided (ldx / ldu / ldy elements, multiples of 8; 16-byte aligned):
+ *   u_i = rnd(X A_i^T), stored to U at columns sum_{j<i} r_j (ldu >= sum r_j);
+ *   Y[:, col0_i : col0_i + N_i] = rnd(float(Y) + scale_i u_i B_i^T), one fused multiply-add on the fp32 sum, rounded once
+ * -- the rounding points of u2tok_lora_down followed by u2tok_lora_up's accumulate form.  Launch 1 cuts K into slices of
+ * max(8, ceil(K / 32 / 64)) 32-wide steps -- a function of K alone -- and leaves an fp32 16 x r_i tile per (slice, segment, block of
+ * 16 rows) in the workspace; launch 2 adds the tiles in slice order, rounds u and runs the rank-r products onto Y.  No atomics: two
+ * calls give the same bits, and a block of 16 rows has exactly the bits it has in a call on those rows alone.  Columns of Y outside
+ * the segments and rows >= M of U and Y are neither read nor written.
+ * U2TOK_ERR_ARG, nothing launched: M, K, n, a rank, N or col0 outside the contract, overlapping segments, ldy shorter than a segment's
+ * end, a null or misaligned pointer (the workspace included); U2TOK_ERR_WORKSPACE: fewer than
+ * u2tok_lora_rows_workspace_bytes(M, K, segs, n) = ceil(M / 16) * slices * sum r_i * 64 bytes (0 for arguments the call refuses). */
+size_t u2tok_lora_rows_workspace_bytes(int32_t M, int32_t K, const u2tok_lora_seg* segs, int32_t n);
+int u2tok_lora_rows(const void* X, int64_t ldx, const u2tok_lora_seg* segs, int32_t n, void* U, int64_t ldu, void* Y, int64_t ldy,
+                    int32_t M, int32_t K, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
 #ifdef __cplusplus
 }

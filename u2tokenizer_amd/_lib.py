@@ -62,9 +62,23 @@ class DecodeConfig(C.Structure):   # u2tok_decode_config
                 ("eps", C.c_float), ("qk_eps", C.c_float), ("scale", C.c_float)]
 
 
+class LoraSeg(C.Structure):        # u2tok_lora_seg: one segment of a few-rows adapter group (u2tok_lora_rows)
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("r", C.c_int32), ("col0", C.c_int32), ("N", C.c_int32), ("scale", C.c_float)]
+
+
+class DecodeLora(C.Structure):     # u2tok_decode_lora: the unmerged adapters of a layer's decode step
+    _fields_ = [("qkv", LoraSeg * 3), ("o", LoraSeg * 1), ("gu", LoraSeg * 2), ("down", LoraSeg * 1),
+                ("n_qkv", C.c_int32), ("n_o", C.c_int32), ("n_gu", C.c_int32), ("n_down", C.c_int32),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+DECODE_LORA_U_BYTES = 64 * 192 * 2   # the head of DecodeLora.scratch: u, 64 rows of 192 elements
+
+
 class DecodeLayer(C.Structure):    # u2tok_decode_layer: raw addresses -- whoever fills one keeps the tensors alive
     _fields_ = [(n, C.c_void_p) for n in ("w_in_norm", "Wqkv", "bqkv", "wq_norm", "wk_norm", "Wo", "bo", "w_post_norm", "Wgu", "bgu",
-                                          "Wdown", "bdown", "scale_qkv", "scale_o", "scale_gu", "scale_down")]
+                                          "Wdown", "bdown", "scale_qkv", "scale_o", "scale_gu", "scale_down",
+                                          "lora")]   # lora: the address of a DecodeLora, or None
 
 
 class TokTaps(C.Structure):
@@ -189,6 +203,10 @@ SIGNATURES = {
     "u2tok_lora_up": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     # U, ldu, X, x_off, ldx, G, ldg, M, C, r, alpha, out_f32, workspace, workspace_bytes, stream
     "u2tok_lora_wgrad": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _sz, _vp]),
+    # M, K, segs, n
+    "u2tok_lora_rows_workspace_bytes": (_sz, [_i32, _i32, _vp, _i32]),
+    # X, ldx, segs, n, U, ldu, Y, ldy, M, K, workspace, workspace_bytes, stream
+    "u2tok_lora_rows": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _sz, _vp]),
 }
 
 ERRORS = {-1: "U2TOK_ERR_ARG (bad dimension / null pointer / unsupported combination)",

@@ -322,12 +322,14 @@ static bool dec_ok(const u2tok_decode_config* c) {
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* c, int32_t T) {
   return dec_ok(c) && T > 0 ? decoder_decode_workspace_bytes(dec_cfg(c), T) : 0;
 }
+static_assert(sizeof(u2tok_decode_lora) == sizeof(DecodeLora) && sizeof(u2tok_lora_seg) == sizeof(LoraSeg), "one layout");
 static DecodeLayer dec_layer(const u2tok_decode_layer* l) {
   DecodeLayer d;
   d.w_in_norm = BF(l->w_in_norm); d.Wqkv = l->Wqkv; d.bqkv = BF(l->bqkv); d.wq_norm = BF(l->wq_norm); d.wk_norm = BF(l->wk_norm);
   d.Wo = l->Wo; d.bo = BF(l->bo); d.w_post_norm = BF(l->w_post_norm);
   d.Wgu = l->Wgu; d.bgu = BF(l->bgu); d.Wdown = l->Wdown; d.bdown = BF(l->bdown);
   d.scale_qkv = l->scale_qkv; d.scale_o = l->scale_o; d.scale_gu = l->scale_gu; d.scale_down = l->scale_down;
+  d.lora = reinterpret_cast<const DecodeLora*>(l->lora);
   return d;
 }
 int u2tok_decoder_decode_pre(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* cos, const void* sin,

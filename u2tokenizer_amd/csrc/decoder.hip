@@ -219,6 +219,17 @@ static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* 
   return rows > 16 ? gemm_rows(g, st) : gemm_bf16(g, st);
 }
 
+// The adapter group of one product of the step (DecodeLora; lora_rows.hip): u at the head of the branch's scratch, the group's
+// workspace behind it.  check_only: the refusals alone, for the checks that precede the step's first launch.
+static int dec_lora(const DecodeLora* lr, const LoraSeg* segs, int n, int nmax, const bf16_t* x, int64_t ldx, bf16_t* y, int64_t ldy, int rows,
+                    int in, bool check_only, hipStream_t st) {
+  if (!lr || n == 0) return U2_OK;
+  if (n < 0 || n > nmax || !lr->scratch || ((uintptr_t)lr->scratch & 15)) return U2_ERR_ARG;
+  if (lr->scratch_bytes < DECODE_LORA_U_BYTES) return U2_ERR_WORKSPACE;
+  return lora_rows(x, ldx, segs, n, reinterpret_cast<bf16_t*>(lr->scratch), DECODE_LORA_U_LD, y, ldy, rows, in,
+                   reinterpret_cast<char*>(lr->scratch) + DECODE_LORA_U_BYTES, lr->scratch_bytes - DECODE_LORA_U_BYTES, check_only, st);
+}
+
 // What the e4m3 products ask of a step before anything is launched: a scale per product, K % 64 == 0 for all four, 16-byte
 // aligned weights, 4-byte aligned scales.
 static bool w8_step_ok(const DecodeCfg& c, const void* const* w, const float* const* sc, int n) {
@@ -251,9 +262,14 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
-  int e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
+  const DecodeLora* lr = l.lora;
+  int e = lr ? dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, true, st) : U2_OK;
+  if (e != U2_OK) return e;
+  e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
   e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
+  if (e != U2_OK) return e;
+  if (lr) e = dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, false, st);   // (before the head norm and the rotary embedding)
   if (e != U2_OK) return e;
   return qk_norm_rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, nq, cs_ld, c.qk_eps, kc, vc, 1, kv_stride,
                       s_off, st);
@@ -290,6 +306,13 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
   const float scale = c.scale;
   if (kv_stride == 0) kv_stride = (int64_t)T * c.D;
   if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
+  const DecodeLora* lr = l.lora;
+  if (lr) {  // (the adapter groups: every refusal before the attention is launched)
+    int e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, true, st);
+    if (e == U2_OK) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, true, st);
+    if (e == U2_OK) e = dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, true, st);
+    if (e != U2_OK) return e;
+  }
   if (batched) {
     const int e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, scale, kv_start, aws, aws_bytes, st);
     if (e != U2_OK) return e;
@@ -306,18 +329,25 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
   }
   int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
   if (e != U2_OK) return e;
+  if (lr) e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, false, st);   // (after the residual epilogue: the same terms)
+  if (e != U2_OK) return e;
   e = rmsnorm_bf16(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  if (!l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
+  const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
+  if (!gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
     e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
     e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
     if (e != U2_OK) return e;
+    if (gu_lora) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, false, st);
+    if (e != U2_OK) return e;
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  return dec_linear(act, c.I, l.Wdown, l.scale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
+  e = dec_linear(act, c.I, l.Wdown, l.scale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
+  if (e != U2_OK || !lr) return e;
+  return dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, false, st);
 }
 
 }  // namespace u2

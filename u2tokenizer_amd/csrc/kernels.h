@@ -328,11 +328,32 @@ struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
 // A layer's decode-step parameters (u2tok_decode_layer).  No scale set: the four W* are in the element type; all four set: they
 // are e4m3 codes with a scale per weight row (gemm_w8.hip), which asks E, Hq * D and I multiples of 64, 16-byte aligned weights
 // and 4-byte aligned scales.  Some set: U2_ERR_ARG, like every other refusal before anything is launched.
+// One segment of a few-rows adapter group (lora_rows.hip; the layout of u2tok_lora_seg): A (r, K) and B (N, r) contiguous, the
+// segment's columns [col0, col0 + N) of the product it is added to
+struct LoraSeg {
+  const bf16_t *A, *B;
+  int r, col0, N;
+  float scale;
+};
+size_t lora_rows_workspace_bytes(int M, int K, const LoraSeg* segs, int n);
+// check_only: every refusal of the call (U2_ERR_ARG / U2_ERR_WORKSPACE), nothing launched
+int lora_rows(const bf16_t* X, int64_t ldx, const LoraSeg* segs, int n, bf16_t* U, int64_t ldu, bf16_t* Y, int64_t ldy, int M, int K,
+              void* ws, size_t ws_bytes, bool check_only, hipStream_t st);
+// The unmerged adapters of a layer's decode step (the layout of u2tok_decode_lora): the segment lists of the four products (n_* = 0:
+// none) and the branch's own scratch -- DECODE_LORA_U_BYTES for u (64 rows x 192 columns), then the group products' workspace
+struct DecodeLora {
+  LoraSeg qkv[3], o[1], gu[2], down[1];
+  int n_qkv, n_o, n_gu, n_down;
+  void* scratch;
+  size_t scratch_bytes;
+};
+constexpr size_t DECODE_LORA_U_LD = 192, DECODE_LORA_U_BYTES = 64 * DECODE_LORA_U_LD * sizeof(bf16_t);
 struct DecodeLayer {
   const void *Wqkv, *Wo, *Wgu, *Wdown;
   const bf16_t *w_in_norm, *bqkv, *wq_norm, *wk_norm;  // first half
   const bf16_t *bo, *w_post_norm, *bgu, *bdown;        // second half
   const float *scale_qkv, *scale_o, *scale_gu, *scale_down;
+  const DecodeLora* lora = nullptr;                    // unmerged adapters (NULL: none)
 };
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T);
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,

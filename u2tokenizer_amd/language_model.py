@@ -68,7 +68,9 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         steps of 17 .. 64 sequences on the fused step), are passed on as the config has them, and so is
         `config.u2_fused_phi3_training` (default False; it implies the training route: head dim 96 and the packed Phi-3 layout
         on it, `enable_fused_prefill(..., train=True, train_phi3=True)`) and `config.u2_fused_lora_training` (default False; it
-        implies the training route too: LoRA-wrapped projections on it, `enable_fused_prefill(..., train_lora=True)`)."""
+        implies the training route too: LoRA-wrapped projections on it, `enable_fused_prefill(..., train_lora=True)`) and
+        `config.u2_fused_lora_inference` (default False: LoRA-wrapped projections on the prefill, continued prefill and decode steps,
+        `enable_fused_prefill(..., lora=True)`; `u2_fused_lora_training` alone does not turn it on)."""
         grad = torch.is_grad_enabled()
         train_phi3 = bool(getattr(self.config, "u2_fused_phi3_training", False))   # (implies the training route)
         train_lora = bool(getattr(self.config, "u2_fused_lora_training", False))   # (implies the training route as well)
@@ -94,6 +96,8 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                 padded["train_phi3"] = True
             if train_lora:   # (default False: LoRA-wrapped projections on the training route, decoder_train.LoraDeltaFn)
                 padded["train_lora"] = True
+            if bool(getattr(self.config, "u2_fused_lora_inference", False)):   # (default False: unmerged adapters on the no-grad routes)
+                padded["lora"] = True
             enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
             checked.add(grad)
 

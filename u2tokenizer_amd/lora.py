@@ -175,6 +175,30 @@ def adapter_of(m) -> Optional[Adapter]:
     computed as itself); no hooks on the wrapper, the base layer, A or B; none of
     _VARIANTS set for the adapter.  Any attribute that cannot be read as expected gives None: a layout that is not understood is
     never computed as if it were."""
+    return _read(m, off=False)
+
+
+def base_only_of(m) -> Optional[nn.Linear]:
+    """The base layer of a wrapper that computes its base layer ALONE -- `merged` or `disable_adapters` set (peft's forward returns
+    base_layer(x) then: the null-reference pass of DPO, a merged model that kept its wrappers) -- and that satisfies every other rule
+    of `adapter_of` (same base type, same hook rules, same _VARIANTS rules, a readable single active adapter), else None.  The no-grad
+    routes of prefill.py count such a projection as its base nn.Linear."""
+    a = _read(m, off=True)
+    return None if a is None else a.base
+
+
+def dropout_inactive(drop) -> bool:
+    """Whether an adapter's dropout module is the identity in this call: nn.Identity, p == 0, or not in training mode (peft applies
+    dropout in train mode even under no_grad; the no-grad routes leave such a call to the stock forward)."""
+    if type(drop) is nn.Identity:
+        return True
+    if type(drop) is nn.Dropout:
+        return drop.p == 0 or not drop.training
+    return False
+
+
+def _read(m, off: bool) -> Optional[Adapter]:
+    """adapter_of's reading of the layout; off: the wrapper must be merged or disabled (base_only_of) instead of neither."""
     try:
         base = m.base_layer
         if type(base) is not nn.Linear:
@@ -183,7 +207,7 @@ def adapter_of(m) -> Optional[Adapter]:
         if not isinstance(act, (list, tuple)) or len(act) != 1:
             return None
         name = act[0]
-        if bool(m.merged) or bool(m.disable_adapters):
+        if (bool(m.merged) or bool(m.disable_adapters)) != off:
             return None
         if set(m.lora_A.keys()) != set(m.lora_B.keys()) or name not in m.lora_A:
             return None

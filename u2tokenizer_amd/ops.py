@@ -911,6 +911,49 @@ def lora_wgrad(u: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, out_f32: bo
     return out
 
 
+def lora_segs(segs):
+    """(A (r, K), B (N, r), col0, scale) tuples -> a ctypes array of u2tok_lora_seg (raw addresses: the caller keeps the tensors)."""
+    arr = (_lib.LoraSeg * len(segs))()
+    for e, (a, b, col0, scale) in zip(arr, segs):
+        if not (a.is_contiguous() and b.is_contiguous()) or a.dim() != 2 or b.dim() != 2 or b.shape[1] != a.shape[0]:
+            raise RuntimeError(f"lora_rows: a segment needs contiguous A (r, K) and B (N, r), got {tuple(a.shape)}, {tuple(b.shape)}")
+        e.A, e.B, e.r, e.col0, e.N, e.scale = a.data_ptr(), b.data_ptr(), a.shape[0], int(col0), b.shape[0], float(scale)
+    return arr
+
+
+def lora_rows_workspace_bytes(M: int, K: int, segs) -> int:
+    """u2tok_lora_rows_workspace_bytes for (A, B, col0, scale) tuples; 0 for a group the call refuses.  No GPU needed."""
+    arr = segs if isinstance(segs, C.Array) else lora_segs(segs)
+    return int(_lib.load_library().u2tok_lora_rows_workspace_bytes(M, K, C.addressof(arr), len(arr)))
+
+
+@_guarded
+def lora_rows(x: torch.Tensor, segs, y: torch.Tensor, u: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adapter branch of one packed product for M <= 64 rows as a group (u2tok_lora_rows, two launches): for each segment
+    (A (r, K), B (N, r), col0, scale) of `segs` (1 .. 3, disjoint columns), u_i = rnd(x A_i^T) and y[:, col0:col0 + N] = rnd(float(y)
+    + scale u_i B_i^T) in place.  x (M, K) and y may be row-strided views; returns u (M, sum r_i)."""
+    h = _lib.load_library()
+    x, y = _segment(x, "x"), _segment(y, "y")
+    M, K = x.shape
+    for a, b, _, _ in segs:
+        _need(a, ELEM, "A"), _need(b, ELEM, "B")
+        if a.dim() != 2 or a.shape[1] != K:
+            raise RuntimeError(f"lora_rows: shapes x {tuple(x.shape)}, A {tuple(a.shape)}")
+    arr = lora_segs(segs)
+    rsum = sum(a.shape[0] for a, _, _, _ in segs)
+    if u is None:
+        u = torch.empty((M, rsum), dtype=elem_dtype(), device=x.device)
+    _segment(u, "u")
+    if y.shape[0] != M or u.shape != (M, rsum):
+        raise RuntimeError("lora_rows: y must have M rows and u be (M, sum r)")
+    nb = int(h.u2tok_lora_rows_workspace_bytes(M, K, C.addressof(arr), len(arr)))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
+    st = h.u2tok_lora_rows(_ptr(x), x.stride(0), C.addressof(arr), len(arr), _ptr(u), u.stride(0), _ptr(y), y.stride(0), M, K, _ptr(ws), nb,
+                           _stream())
+    _lib.check(st, "u2tok_lora_rows")
+    return u
+
+
 @_guarded
 def rope_apply(x: torch.Tensor, n_outer, S, n_inner, H, d, max_len=512, inverse=False):
     h = _lib.load_library()

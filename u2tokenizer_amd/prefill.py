@@ -39,6 +39,10 @@ DynamicSlidingWindowLayer that `generate` builds for such a config.
 `enable_fused_prefill(model, train=True)` (opt-in) sends a Llama / Qwen3 layer called with grad enabled through the training route of
 decoder_train.py at head dims 64 / 128; with `train_phi3=True` on top also at head dim 96 and for the packed Phi-3 layout
 (S <= W positions on a layer with a window).
+`enable_fused_prefill(model, lora=True)` (opt-in) keeps a layer whose projections are LoRA-wrapped (lora.py) on the prefill, the
+continued prefill and the decode step with the adapters UNMERGED (`_lora_admit`, `_lora_state`): the adapter branch follows each of the
+four products -- on many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of
+csrc/lora_rows.hip inside the two library calls --, and a wrapper that is merged or disabled runs as its base layer.
 `route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
 step, the prefill or the stock forward.  The patch state is one `_LayerState` per layer and one `_StackState` per decoder stack.
 """
@@ -51,7 +55,7 @@ import torch
 from transformers import cache_utils
 
 from . import decoder_train, ops
-from .lora import adapter_of
+from .lora import adapter_of, base_only_of, dropout_inactive
 
 # the HF cache classes the fused steps work with (None where this transformers lacks one: before 4.56 no per-layer caches)
 _DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
@@ -74,6 +78,9 @@ extend_stats = {"extend": 0, "padded_extend": 0}
 w8_stats = {"decode": 0, "padded_decode": 0}
 # ... and the decode steps (counted in `stats` as well) of more than 16 sequences (wide_decode=True), per layer call
 wide_stats = {"decode": 0, "padded_decode": 0}
+# ... and the layer calls of the no-grad routes (counted above as well) that computed at least one unmerged adapter (lora=True), per
+# route, and the adapters they computed
+lora_stats = {"prefill": 0, "extend": 0, "decode": 0, "adapters": 0}
 
 
 def pad_rule(mask):
@@ -147,9 +154,15 @@ def _ensure_gemm_scratch(device) -> None:
 _HOOK_TABLES = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
 
 
+def _base(lin):
+    """The nn.Linear whose weight and bias a projection's product reads: the module, or an adapter wrapper's base layer."""
+    return getattr(lin, "base_layer", lin)
+
+
 class _SplitLayout:
     """Llama / Qwen3: separate q / k / v and gate / up projections, packed into one buffer each on first use."""
     KEY = (0, 3, 4, 6)   # projections whose weights locate the packed buffers: q (q|k|v), o, gate (gate|up), down
+    GROUPS = ((0, 1, 2), (3,), (4, 5), (6,))   # the projections of the four products: q|k|v, o, gate|up, down
     TRAINS = True        # the training route computes this layout
 
     @staticmethod
@@ -191,6 +204,7 @@ class _SplitLayout:
 class _PackedLayout:
     """Phi-3: one qkv_proj (q, k, v rows) and one gate_up_proj (gate rows, then up rows) -- the packed layout itself."""
     KEY = (0, 1, 2, 3)
+    GROUPS = ((0,), (1,), (2,), (3,))
     TRAINS = False       # ... and this one only with the train_phi3 switch (route)
 
     @staticmethod
@@ -199,12 +213,12 @@ class _PackedLayout:
 
     @staticmethod
     def qkv(layer):
-        lin = layer.self_attn.qkv_proj
+        lin = _base(layer.self_attn.qkv_proj)
         return lin.weight, lin.bias
 
     @staticmethod
     def gate_up(layer):
-        lin = layer.mlp.gate_up_proj
+        lin = _base(layer.mlp.gate_up_proj)
         return lin.weight, lin.bias
 
     @staticmethod
@@ -292,6 +306,30 @@ def _is_stock_or_lora(layer, projections) -> bool:
     return True
 
 
+def _lora_admit(layer, projections):
+    """_is_stock for the no-grad routes under the `lora` switch: per projection None -- exactly nn.Linear, or a wrapper that computes
+    its base layer alone (lora.base_only_of: merged or disabled, DPO's null-reference pass) -- or the lora.Adapter the route computes
+    (lora.adapter_of, and a dropout that is the identity in this call: peft applies dropout in train mode even under no_grad); None
+    instead of the tuple sends the call to the stock forward (rank outside RANKS, DoRA and the other variants, hooks, more than one
+    active adapter, an unreadable attribute, active dropout)."""
+    ads = []
+    for m in projections:
+        a = None
+        if type(m) is not torch.nn.Linear:
+            a = adapter_of(m)
+            if a is None:
+                if base_only_of(m) is None:
+                    return None
+            elif not dropout_inactive(a.dropout):
+                return None
+        ads.append(a)
+    for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
+        for t in _HOOK_TABLES:
+            if getattr(m, t, None):
+                return None
+    return tuple(ads)
+
+
 @dataclass(slots=True, eq=False)
 class _StackState:
     """enable_fused_prefill's state on a decoder stack: the route switches, the pre-hook's verdict on the call's 2-D mask,
@@ -306,6 +344,7 @@ class _StackState:
     continued: bool = False
     fp8: bool = False
     wide: bool = False
+    lora: bool = False
     mask_ok: bool = True
     pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
     pad_shape: tuple = None    # ... and that mask's (B, columns)
@@ -320,6 +359,8 @@ class _LayerState:
     layout: type
     dec: dict = None
     w8: dict = None            # fp8_decode=True: the e4m3 copies of the four packed weights and their scales (`_w8_state`)
+    ads: tuple = None          # lora=True: the call's adapters per projection (`_lora_admit`, set by route() for the step that follows)
+    lora: dict = None          # ... and their cached 16-bit operands, the decode step's descriptor (`_lora_state`)
 
     def __getitem__(self, key):   # (read as a mapping too -- layer._u2_prefill["layout"] -- as when this state was a dict)
         return getattr(self, key)
@@ -361,7 +402,7 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     # weights' type (bf16 weights under an fp16 autocast hand fp16 activations on), stock projections without hooks
     if args or "past_key_value" in kwargs or kwargs.get("output_attentions") or not is_cuda or len(shape) != 3 \
             or shape[1] < 1 or pr[0].weight.dtype != dtype or pe is None or pe[0].shape[-1] != att.head_dim \
-            or not (_is_stock_or_lora(layer, pr) if grad and stack.train_lora else _is_stock(layer, pr)) \
+            or not _admit(layer, st, pr, grad) \
             or not lo.ready(layer, att):
         return "stock", None
     if grad:
@@ -413,6 +454,23 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     return "stock", None
 
 
+def _admit(layer, st, pr, grad: bool) -> bool:
+    """Whether the projections are what the call's route computes: stock modules without hooks; with grad and train_lora also the
+    adapters of the training route; without grad and with the `lora` switch the adapters `_lora_admit` takes, left in st.ads."""
+    stack = st.stack
+    st.ads = None
+    if grad:
+        return _is_stock_or_lora(layer, pr) if stack.train_lora else _is_stock(layer, pr)
+    if not stack.lora:
+        return _is_stock(layer, pr)
+    ads = _lora_admit(layer, pr)
+    if ads is None:
+        return False
+    if any(a is not None for a in ads):
+        st.ads = ads
+    return True
+
+
 def _pad_range(st):
     """(kind, kv_start, kv_len) of the call a layer routed to a fused step is part of: the stack's verdict when the mask carried a
     range (route() has checked that it fits this call), else ("none", None, None)."""
@@ -452,12 +510,29 @@ def _train_step(layer, lo, x, pe, kv_len):
         return decoder_train.layer_forward_train(layer, lo, _rows(x), cos.detach(), sin.detach(), B, S, kv_len)
 
 
+def _lora_add(y, x2, segs):
+    """The adapter branch of one packed product on many rows, for its wrapped projections: u = rnd(x A^T) (u2tok_lora_down), then
+    y[:, col0:col0 + N] = rnd(float(y) + scale u B^T) in place (u2tok_lora_up, accumulate form) -- the kernels and the rounding
+    points of the training route (decoder_train.LoraDeltaFn)."""
+    for A16, B16, col0, scale in segs:
+        u = ops.lora_down(x2, A16)
+        ops.lora_up(u, B16, y[:, col0:col0 + B16.shape[0]], alpha=scale, accumulate=True)
+
+
 def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
     """The prefill step of a layer.  extend (the "extend" route): the keys come from the cache -- `_extend_kv` --, or, with no
-    position cached yet, the call is longer than `window` and its own keys get the band."""
+    position cached yet, the call is longer than `window` and its own keys get the band.  With unmerged adapters admitted for the
+    call (the `lora` switch: st.ads) each of the four products is followed by its adapters' branch (`_lora_add`); the q|k|v branch
+    precedes the rotary embedding, so the cache receives adapted keys and values."""
     B, S, E = x.shape
     rows = B * S
     att = self.self_attn
+    st = self._u2_prefill
+    ls = _lora_state(st, lo, lo.projections(self), x.dtype, x.device) if st.ads is not None else None
+    g_qkv, g_o, g_gu, g_down = ls["groups"] if ls is not None else ((), (), (), ())
+    if ls is not None:
+        lora_stats["extend" if extend else "prefill"] += 1
+        lora_stats["adapters"] += ls["n"]
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     _ensure_gemm_scratch(x.device)
@@ -468,6 +543,7 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
         cos, sin = _rotary_rows(pe, B, S, d)
         xn = ops.rmsnorm(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
         qkv = ops.gemm(xn, Wqkv, bias=bqkv)
+        _lora_add(qkv, xn, g_qkv)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
         q3 = qkv.view(B, S, -1)
         kind, kv_start, kv_len = _pad_range(self._u2_prefill)
@@ -490,13 +566,19 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
             else:   # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros
                 ctx = ops.attention_gqa_range(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), kv_start=kv_start,
                                               kv_len=kv_len, causal=True)
-        h = ops.gemm(ctx.view(rows, Hq * d), att.o_proj.weight, bias=att.o_proj.bias, residual=x2)
+        o_proj, down_proj = _base(att.o_proj), _base(self.mlp.down_proj)
+        ctx2 = ctx.view(rows, Hq * d)
+        h = ops.gemm(ctx2, o_proj.weight, bias=o_proj.bias, residual=x2)
+        _lora_add(h, ctx2, g_o)   # (after the residual epilogue: the same terms)
         hn = ops.rmsnorm(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
-        if bgu is None and ops.gemm_swiglu_supported(rows, E, Wgu.shape[0] // 2):
+        if not g_gu and bgu is None and ops.gemm_swiglu_supported(rows, E, Wgu.shape[0] // 2):
             act = ops.gemm_swiglu(hn, Wgu)  # SiLU(gate) * up in the epilogue of the pair product: no (rows, 2 I) tensor
-        else:
-            act = ops.swiglu(ops.gemm(hn, Wgu, bias=bgu))
-        out = ops.gemm(act, self.mlp.down_proj.weight, bias=self.mlp.down_proj.bias, residual=h)
+        else:   # (a gate or up adapter: its branch lands on the pair product before the SiLU)
+            gu = ops.gemm(hn, Wgu, bias=bgu)
+            _lora_add(gu, hn, g_gu)
+            act = ops.swiglu(gu)
+        out = ops.gemm(act, down_proj.weight, bias=down_proj.bias, residual=h)
+        _lora_add(out, act, g_down)
         if commit is not None:
             commit()
         elif lay is not None:
@@ -635,13 +717,14 @@ def _decode_state(self, B: int, device, pr):
         E, inter = Wqkv.shape[1], Wgu.shape[0] // 2
         c = _lib.DecodeConfig(B=B, E=E, Hq=Hq, Hkv=Hkv, D=hd, I=inter, eps=float(self.input_layernorm.variance_epsilon),
                               qk_eps=float(qn.variance_epsilon) if qn is not None else 1e-6, scale=float(att.scaling))
-        ok = (E % 32 == 0 and inter % 32 == 0 and att.o_proj.weight.is_contiguous() and mlp.down_proj.weight.is_contiguous()
+        o_proj, down_proj = _base(att.o_proj), _base(mlp.down_proj)
+        ok = (E % 32 == 0 and inter % 32 == 0 and o_proj.weight.is_contiguous() and down_proj.weight.is_contiguous()
               and self.post_attention_layernorm.variance_epsilon == self.input_layernorm.variance_epsilon)
         p = ops._ptr
         lay = _lib.DecodeLayer(w_in_norm=p(self.input_layernorm.weight), Wqkv=p(Wqkv), bqkv=p(bqkv),
                                wq_norm=p(None if qn is None else qn.weight), wk_norm=p(None if kn is None else kn.weight),
-                               Wo=p(att.o_proj.weight), bo=p(att.o_proj.bias), w_post_norm=p(self.post_attention_layernorm.weight),
-                               Wgu=p(Wgu), bgu=p(bgu), Wdown=p(mlp.down_proj.weight), bdown=p(mlp.down_proj.bias))
+                               Wo=p(o_proj.weight), bo=p(o_proj.bias), w_post_norm=p(self.post_attention_layernorm.weight),
+                               Wgu=p(Wgu), bgu=p(bgu), Wdown=p(down_proj.weight), bdown=p(down_proj.bias))
         d = {"key": key, "ok": ok, "cfg": c, "cfg_ref": C.byref(c), "layer": lay, "layer_ref": C.byref(lay),
              "keep": (Wqkv, bqkv, Wgu, bgu), "nq": (Hq + 2 * Hkv) * hd, "Hkv": Hkv, "hd": hd, "E": E}
         st.dec = d
@@ -678,7 +761,7 @@ def _w8_state(self, d, pr):
     w8 = st.w8
     if w8 is None or w8["key"] != key:
         Wqkv, _, Wgu, _ = d["keep"]
-        pairs = tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, self.self_attn.o_proj.weight, Wgu, self.mlp.down_proj.weight))
+        pairs = tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, _base(self.self_attn.o_proj).weight, Wgu, _base(self.mlp.down_proj).weight))
         w8 = st.w8 = {"d": None, "key": key, "pairs": pairs}
     if w8["d"] is not d:   # (the decode constants were rebuilt -- another batch size, a moved weight: their pointers anew)
         import ctypes as C
@@ -688,6 +771,74 @@ def _w8_state(self, d, pr):
             (w.data_ptr(), sc.data_ptr()) for w, sc in w8["pairs"])
         w8.update(d=d, layer=lay, layer_ref=C.byref(lay))
     return w8
+
+
+def _op16(w, dtype, device):
+    """An adapter weight as the kernels read it: itself when it already is a dense tensor of the element type on the device, else a
+    16-bit compute copy (fp32 adapters: peft's default under autocast_adapter_dtype)."""
+    w = w.detach()
+    if w.dtype == dtype and w.device == device and w.is_contiguous():
+        return w
+    return w.to(device=device, dtype=dtype).contiguous()
+
+
+def _lora_state(st, lo, pr, dtype, device):
+    """The call's unmerged adapters (st.ads: `_lora_admit`) as the kernels read them, kept in the layer's patch state after the pattern
+    of `_w8_state`: per product (q|k|v, o, gate|up, down) the segments (A16 (r, K), B16 (N, r), col0, scaling) of its wrapped
+    projections -- the 16-bit compute copies of fp32 adapters among them --, and for the decode step the descriptor built from them
+    (`_lora_decode`).  Rebuilt when an adapter weight's data_ptr() or _version, a scaling, the active adapter (its A / B modules) or a
+    `merged` / `disable_adapters` flag (an entry of st.ads turning None) changed, and on nothing else: no step converts anything.
+    Freed with the patch state by disable_fused_prefill, and when the switch goes off."""
+    ads = st.ads
+    key = (dtype, device) + tuple(None if a is None else (id(a.A), a.A.weight.data_ptr(), a.A.weight._version, id(a.B),
+                                                          a.B.weight.data_ptr(), a.B.weight._version, a.scaling, a.r) for a in ads)
+    ls = st.lora
+    if ls is None or ls["key"] != key:
+        groups = []
+        for idx in lo.GROUPS:
+            col0, segs = 0, []
+            for i in idx:
+                a = ads[i]
+                if a is not None:
+                    segs.append((_op16(a.A.weight, dtype, device), _op16(a.B.weight, dtype, device), col0, a.scaling))
+                col0 += _base(pr[i]).out_features
+            groups.append(tuple(segs))
+        ls = st.lora = {"key": key, "groups": tuple(groups), "n": sum(len(g) for g in groups), "desc": None, "need": {}, "lay": None}
+        lora_state_builds[0] += 1
+    return ls
+
+
+lora_state_builds = [0]   # how often `_lora_state` built its operands (tests: once per change, never per step)
+_LORA_PRODUCTS = ("qkv", "o", "gu", "down")
+
+
+def _lora_decode(ls, src, B: int, sc, h):
+    """The decode step's layer descriptor with the adapters on: a copy of `src["layer"]` (the 16-bit step's or the e4m3 one's) whose
+    `lora` points at the u2tok_decode_lora of the layer's segments; its scratch (u, then the largest group workspace for B rows) is
+    the calling stream's, shared by all layers like the step's other scratch."""
+    import ctypes as C
+    from . import _lib
+    desc = ls["desc"]
+    if desc is None:
+        desc = ls["desc"] = _lib.DecodeLora()
+        for name, segs in zip(_LORA_PRODUCTS, ls["groups"]):
+            for e, (A16, B16, col0, scale) in zip(getattr(desc, name), segs):
+                e.A, e.B, e.r, e.col0, e.N, e.scale = A16.data_ptr(), B16.data_ptr(), A16.shape[0], col0, B16.shape[0], scale
+            setattr(desc, "n_" + name, len(segs))
+    need = ls["need"].get(B)
+    if need is None:
+        need = ls["need"][B] = _lib.DECODE_LORA_U_BYTES + max(
+            h.u2tok_lora_rows_workspace_bytes(B, segs[0][0].shape[1], C.addressof(getattr(desc, name)), len(segs))
+            for name, segs in zip(_LORA_PRODUCTS, ls["groups"]) if segs)
+    buf = sc.get("lora")
+    if buf is None or buf.numel() < need:
+        buf = sc["lora"] = torch.empty(need, dtype=torch.uint8, device=sc["qkv"].device)
+    desc.scratch, desc.scratch_bytes = buf.data_ptr(), buf.numel()
+    if ls["lay"] is None or ls["lay"][0] is not src["layer"]:
+        lay = _lib.DecodeLayer.from_buffer_copy(src["layer"])
+        lay.lora = C.addressof(desc)
+        ls["lay"] = (src["layer"], lay, C.byref(lay))
+    return ls["lay"][2]
 
 
 def w8_weights(layer):
@@ -718,6 +869,8 @@ def _decode_step(self, x, pe, cache, window, pr):
     hd = d["hd"]
     stack = self._u2_prefill.stack
     w8 = _w8_state(self, d, pr) if stack.fp8 else None   # fp8_decode=True: the step's four products on e4m3 weights
+    st = self._u2_prefill
+    ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None   # lora=True: the unmerged adapters
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
@@ -736,7 +889,8 @@ def _decode_step(self, x, pe, cache, window, pr):
             kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
         else:         # into the step's scratch rows, for the cache's own `update`
             T0, kd, vd, kvs = 0, sc["kc"], sc["vc"], 0
-        layer_ref = (d if w8 is None else w8)["layer_ref"]
+        src = d if w8 is None else w8
+        layer_ref = src["layer_ref"] if ls is None else _lora_decode(ls, src, B, sc, h)   # (the adapter groups ride in the two calls)
         _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                                               int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
                                               vd.data_ptr(), kvs, T0, ws, nws, stream), "u2tok_decoder_decode_pre")
@@ -759,6 +913,9 @@ def _decode_step(self, x, pe, cache, window, pr):
         w8_stats["decode" if stack.mask_ok else "padded_decode"] += 1
     if B > 16:
         wide_stats["decode" if stack.mask_ok else "padded_decode"] += 1
+    if ls is not None:
+        lora_stats["decode"] += 1
+        lora_stats["adapters"] += ls["n"]
     return out
 
 
@@ -833,7 +990,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
-                         train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False) -> int:
+                         train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
     of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
@@ -870,9 +1027,19 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     qualifies: one active unmerged adapter, r in {16, 32, 64}, bias-free nn.Linear A / B in bf16 or fp32, no DoRA or other variant,
     no hooks) -- and adds the adapter branch on the rank-r kernels of csrc/lora.hip (decoder_train.LoraDeltaFn); the frozen base
     weights get no gradient product.  It composes with train_phi3 (one adapter over the packed qkv_proj / gate_up_proj).  Off, a
-    wrapped projection keeps the stock forward under every switch, as before; the prefill and decode routes always do (merge
-    the adapters first: lora.merge_lora).  `decoder_train.lora_stats` counts these layers and their adapters.
-    The nine switches are set anew by every call.
+    wrapped projection keeps the stock forward with grad enabled, as before.  `decoder_train.lora_stats` counts these layers and
+    their adapters.  train_lora alone leaves the no-grad routes as they are: a wrapped projection is stock there.
+    lora=True (opt-in): the prefill, the continued prefill and the decode step also take a layer whose projections are LoRA-wrapped
+    (`_lora_admit`: what `lora.adapter_of` understands, with a dropout that is the identity in the call -- nn.Identity, p = 0 or eval
+    mode --; a wrapper with `merged` or `disable_adapters` set, `lora.base_only_of`, counts as its base layer alone and gives the bits
+    of the unwrapped model: DPO's null-reference pass) and add the adapter branch UNMERGED after each of the four products: on many
+    rows the down / up kernels of the training route, on a decode step the two-launch group product of csrc/lora_rows.hip inside the
+    two library calls (`_lora_state` keeps the 16-bit operands and the descriptor; nothing is converted per step).  In-training
+    evaluation, `generate` during evaluation and several adapters over one base stay on the HIP layers without merging; it composes
+    with padded, continued, fp8_decode (the adapters keep 16 bits beside the e4m3 codes), wide_decode, train_lora and the Phi-3
+    layout.  `lora_stats` counts these layer calls and their adapters.  Off, a wrapped projection keeps the stock forward on the
+    no-grad routes (merge the adapters first: lora.merge_lora).
+    The ten switches are set anew by every call.
     `disable_fused_prefill` restores the stock forwards."""
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
@@ -895,12 +1062,16 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train) or bool(train_lora), bool(prefill), bool(padded)
     stack.train_lora = bool(train_lora)
     stack.continued, stack.fp8, stack.train_phi3 = bool(continued), bool(fp8_decode), bool(train_phi3)
-    stack.wide = bool(wide_decode)
+    stack.wide, stack.lora = bool(wide_decode), bool(lora)
     stack.pad = stack.pad_shape = None
     if not stack.fp8:   # (the copies go with the switch)
         for layer in layers:
             if is_patched(layer):
                 layer._u2_prefill.w8 = None
+    if not stack.lora:
+        for layer in layers:
+            if is_patched(layer):
+                layer._u2_prefill.lora = layer._u2_prefill.ads = None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
