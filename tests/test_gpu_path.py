@@ -332,7 +332,7 @@ def test_vit_qkv_product_writes_v_transposed_bit_identically():
 
 def test_vit_cls_rows_ride_in_the_big_tile_launch_bit_identically():
     """Round 5: the 8 cls rows behind the 16384 patch rows of every ViT product (q|k|v, out-projection, fc1, fc2) are computed inside
-    the big-tile launch -- by the few-rows kernel's own arithmetic (csrc/rows16.h: same K slices, same order) -- instead of 48
+    the big-tile launch -- by the few-rows kernel's own arithmetic (csrc/rows.h: same K slices, same order) -- instead of 48
     launches of their own per volume (option gemm_tail_fused).  The tower's output is BIT-identical either way, and the profile
     shows the 48 GEMM launches gone."""
     import ctypes as C

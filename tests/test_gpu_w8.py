@@ -1,7 +1,7 @@
 """GPU: the FP8 (e4m3) weight-only decode step (opt-in, `enable_fused_prefill(model, fp8_decode=True)`), in both element builds:
 the few-rows product on 1-byte weights (u2tok_gemm_rows_w8) against float64 under the per-element bound of
 tests/test_w8_host.py, every finite e4m3 code through one-hot activations (the conversion and the K mapping of
-csrc/rows16_w8.h), the gate | up pair form against the two-step form bit for bit, and the route -- decode steps of models whose
+csrc/rows.h), the gate | up pair form against the two-step form bit for bit, and the route -- decode steps of models whose
 weights the quantiser keeps exactly (ops.snap_fp8_: the e4m3 step and the 16-bit model compute the same function) under the
 project's gate, staleness of the quantised copies, teardown, layers that keep the 16-bit step, and `generate`."""
 import pytest

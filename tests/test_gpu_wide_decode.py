@@ -1,5 +1,5 @@
 """GPU: decode steps of 17 .. 64 sequences on the fused step (opt-in, `enable_fused_prefill(model, wide_decode=True)`), in both
-element builds.  The few-rows product for 17 .. 64 rows (u2tok_gemm_rows, u2tok_gemm_rows_w8_wide; csrc/rows64.h) block by block
+element builds.  The few-rows product for 17 .. 64 rows (u2tok_gemm_rows, u2tok_gemm_rows_w8_wide; csrc/rows.h) block by block
 against the M <= 16 product BIT FOR BIT -- the contract: a sequence's products do not depend on how many sequences share the
 step --, against float64 under the per-element bound of tests/test_w8_host.py, its refusals with poisoned outputs, the two entry
 points of the step at B = 40 against the same calls on the row slices, the step through whole decoders under the project's

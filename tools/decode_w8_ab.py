@@ -19,6 +19,7 @@ with the layer count, the ratio does not.  No trained checkpoint is involved: qu
 import argparse
 import csv
 import json
+import re
 import shutil
 import statistics
 import subprocess
@@ -180,8 +181,9 @@ def _trace_table(d, layers):
     per_layer = ((HQ + 2 * HKV) * HD * E + E * HQ * HD + 2 * INTER * E + E * INTER)      # weight elements of the four products
     out = {}
     rows = list(csv.DictReader(files[0].open()))
-    for key, pat, nbytes in (("bf16", "gemm_rows16_kernel", 2), ("w8", "gemm_rows16_w8_kernel", 1)):
-        sel = [r for r in rows if pat in r["Name"]]
+    # gemm_rows16_kernel<NW, NB, PAIR, W8> (csrc/gemm_rows.hip): the weight form is the last template argument
+    for key, pat, nbytes in (("bf16", r"gemm_rows16_kernel<[^>]*, false>", 2), ("w8", r"gemm_rows16_kernel<[^>]*, true>", 1)):
+        sel = [r for r in rows if re.search(pat, r["Name"])]
         ns = sum(float(r["TotalDurationNs"]) for r in sel)
         calls = sum(int(r["Calls"]) for r in sel)
         total = per_layer * nbytes * layers * STEPS

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What the 8 cls rows behind the 16384 patch rows cost each ViT product (the in-launch tail of the big-tile kernels, rows16.h):
+"""What the 8 cls rows behind the 16384 patch rows cost each ViT product (the in-launch tail of the big-tile kernels, rows.h):
 microseconds per launch at M = 16384 and at M = 16392, operand sets in rotation.
 
     python tools/tail_probe.py

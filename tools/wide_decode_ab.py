@@ -11,7 +11,11 @@ Per variant: 16 greedy steps (after one outside the clock) on append-in-place ca
 per-step ms from device events around the 16 steps, host time of the calls included, as `generate` pays it; medians over the
 rounds, "spread" = the largest deviation of a round's a - c difference from the median difference.  The route counters are checked.
 
-    python tools/wide_decode_ab.py [--layers 4] [--rounds 3] [--out profiles/wide_decode_ab.json]
+    python tools/wide_decode_ab.py [--layers 4] [--rounds 3] [--variants wide,stock,chunks] [--batches 16,32,48,64]
+                                   [--lengths 1024,2048] [--out profiles/wide_decode_ab.json]
+
+--variants / --batches / --lengths cut the run down, e.g. `--variants wide --batches 16,64 --lengths 1024` to compare the fused
+step between two builds of the library (one run per build); the a - c columns are left out when a or c is.
 
 The parent process never opens the GPU: each weight form is a child process of its own under its own time limit, started only if
 the one before it ended clean; nothing is tried twice.  The decoder has --layers layers (36 in Qwen3-8B): per-step times scale
@@ -98,24 +102,29 @@ def child(a):
         assert prefill.w8_stats["decode"] - w0["decode"] == (calls if fp8 and how != "stock" else 0), how
         return ms
 
-    for T in LENGTHS:
-        for B in BATCHES:
-            for how in ("wide", "chunks", "stock"):     # warm-up (builds the e4m3 copies, sizes the workspaces)
+    hows = [h for h in ("wide", "stock", "chunks") if h in a.variants.split(",")]
+    for T in (int(v) for v in a.lengths.split(",")):
+        for B in (int(v) for v in a.batches.split(",")):
+            for how in hows:     # warm-up (builds the e4m3 copies, sizes the workspaces)
                 run(how, B, T)
-            t = {"wide": [], "stock": [], "chunks": []}
+            t = {how: [] for how in hows}
             for _ in range(a.rounds):
-                for how in ("wide", "stock", "chunks"):
+                for how in hows:
                     t[how].append(run(how, B, T))
             med = {k: statistics.median(v) for k, v in t.items()}
-            diff = [x - y for x, y in zip(t["wide"], t["chunks"])]
-            md = statistics.median(diff)
-            res.append({"weights": a.child, "B": B, "T": T, "layers": a.layers, "steps": STEPS, "rounds": a.rounds,
-                        "wide_ms_per_step": round(med["wide"], 4), "stock_ms_per_step": round(med["stock"], 4),
-                        "chunks_ms_per_step": round(med["chunks"], 4), "wide_minus_chunks_ms": round(md, 4),
-                        "spread_ms": round(max(abs(x - md) for x in diff), 4),
-                        "stock_over_wide": round(med["stock"] / med["wide"], 3),
-                        "chunks_over_wide": round(med["chunks"] / med["wide"], 3),
-                        "wide_tokens_per_s": round(B / med["wide"] * 1e3, 1)})
+            row = {"weights": a.child, "B": B, "T": T, "layers": a.layers, "steps": STEPS, "rounds": a.rounds}
+            row.update({f"{k}_ms_per_step": round(v, 4) for k, v in med.items()})
+            row.update({f"{k}_ms_per_step_min_max": [round(min(v), 4), round(max(v), 4)] for k, v in t.items()})
+            if "wide" in med and "chunks" in med:
+                diff = [x - y for x, y in zip(t["wide"], t["chunks"])]
+                md = statistics.median(diff)
+                row.update({"wide_minus_chunks_ms": round(md, 4), "spread_ms": round(max(abs(x - md) for x in diff), 4),
+                            "chunks_over_wide": round(med["chunks"] / med["wide"], 3)})
+            if "wide" in med and "stock" in med:
+                row["stock_over_wide"] = round(med["stock"] / med["wide"], 3)
+            if "wide" in med:
+                row["wide_tokens_per_s"] = round(B / med["wide"] * 1e3, 1)
+            res.append(row)
             print(json.dumps(res[-1]), flush=True)
     prefill.disable_fused_prefill(m)
     print("RESULT " + json.dumps(res), flush=True)
@@ -137,12 +146,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--variants", default="wide,stock,chunks")
+    ap.add_argument("--batches", default=",".join(str(b) for b in BATCHES))
+    ap.add_argument("--lengths", default=",".join(str(t) for t in LENGTHS))
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, choices=["bf16", "w8"])
     a = ap.parse_args()
     if a.child:
         return child(a)
-    me = [sys.executable, str(Path(__file__).resolve()), "--layers", str(a.layers), "--rounds", str(a.rounds)]
+    me = [sys.executable, str(Path(__file__).resolve()), "--layers", str(a.layers), "--rounds", str(a.rounds), "--variants", a.variants,
+          "--batches", a.batches, "--lengths", a.lengths]
     res = {"what": "decode step of B sequences at the Qwen3-8B layer shape, synthetic weights: a = one fused step of B sequences "
                    "(wide_decode=True), b = the stock layers, c = ceil(B / 16) fused steps of <= 16 sequences; interleaved rounds "
                    "of 16 greedy steps on append-in-place caches of T positions; ms per step, host time included; spread = largest "

@@ -346,15 +346,20 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* c, const u2tok_decode_l
   return decoder_decode_post(dec_cfg(c), dec_layer(l), BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out),
                              workspace, workspace_bytes, ST(stream));
 }
-// ---- the few-rows product on e4m3 weights (gemm_w8.hip; M > 16: gemm_rows64.hip)
-static int rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
-                   int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
-  RowsW8Args a;
-  a.A = BF(A); a.W = reinterpret_cast<const uint8_t*>(W8); a.scale = scale; a.C = C; a.bias = BF(bias); a.R = BF(R);
+// ---- the few-rows product (gemm_rows.hip): scale set = e4m3 weights, null = weights in the element type
+static int rows(const void* A, const void* W, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+  RowsArgs a;
+  a.A = BF(A); a.W = W; a.scale = scale; a.C = C; a.bias = BF(bias); a.R = BF(R);
   a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
   a.flags = flags;
-  return gemm_rows_w8(a, ST(stream));
+  return gemm_rows(a, ST(stream));
+}
+static int rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                   int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+  if (!scale) return U2_ERR_ARG;  // (no scale would mean 16-bit weights to gemm_rows)
+  return rows(A, W8, scale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
 }
 int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
                        int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
@@ -366,15 +371,10 @@ int u2tok_gemm_rows_w8_wide(const void* A, const void* W8, const float* scale, v
                             u2tok_stream_t stream) {
   return rows_w8(A, W8, scale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
 }
-// ---- the few-rows product on element-type weights, outside u2tok_gemm_bf16's plan (gemm.hip: gemm_rows)
+// (on element-type weights, outside u2tok_gemm_bf16's plan)
 int u2tok_gemm_rows(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K, int64_t lda,
                     int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
-  GemmDesc d;
-  d.A = BF(A); d.B = BF(W); d.C = C; d.bias = BF(bias); d.R = BF(R);
-  d.M = M; d.N = N; d.K = K;
-  d.lda = lda; d.ldb = ldw; d.ldc = ldc; d.ldr = ldr;
-  d.flags = flags;
-  return gemm_rows(d, ST(stream));
+  return rows(A, W, nullptr, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
 }
 size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
   return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);

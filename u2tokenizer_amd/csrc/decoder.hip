@@ -200,23 +200,21 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
 // One projection of the step: the element type's product through the plan, or -- `sc`: a scale per weight row, w = e4m3 codes
-// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_w8.hip).  pair: w = gate | up, y (rows, out / 2).
+// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_rows.hip).  pair: w = gate | up, y (rows, out / 2).
 static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const bf16_t* b, bf16_t* y, int64_t ldy, int rows,
                       int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
-  if (sc) {
-    RowsW8Args a;
-    a.A = x; a.W = reinterpret_cast<const uint8_t*>(w); a.scale = sc; a.C = y; a.bias = b; a.R = R;
-    a.M = rows; a.N = out; a.K = in;
-    a.lda = ldx; a.ldw = in; a.ldc = ldy; a.ldr = ldr;
-    a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-    return gemm_rows_w8(a, st);
-  }
-  GemmDesc g;
+  RowsArgs a;
+  a.A = x; a.W = w; a.scale = sc; a.C = y; a.bias = b; a.R = R;
+  a.M = rows; a.N = out; a.K = in;
+  a.lda = ldx; a.ldw = in; a.ldc = ldy; a.ldr = ldr;
+  a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
+  if (sc || rows > 16) return gemm_rows(a, st);
+  GemmDesc g;  // 16-bit weights, M <= 16: the plan (the same kernel, or a tile kernel when rows16_ok says no)
   g.A = x; g.B = reinterpret_cast<const bf16_t*>(w); g.C = y; g.bias = b; g.R = R;
   g.M = rows; g.N = out; g.K = in;
   g.lda = ldx; g.ldb = in; g.ldc = ldy; g.ldr = ldr;
-  g.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-  return rows > 16 ? gemm_rows(g, st) : gemm_bf16(g, st);
+  g.flags = a.flags;
+  return gemm_bf16(g, st);
 }
 
 // The adapter group of one product of the step (DecodeLora; lora_rows.hip): u at the head of the branch's scratch, the group's

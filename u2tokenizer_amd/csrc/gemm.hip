@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "kernels.h"
-#include "rows16.h"
+#include "rows.h"
 
 namespace u2 {
 
@@ -408,58 +408,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmDesc d) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ M <= 16 rows
-// The ViT keeps its 8 cls rows behind the 16384 patch rows (pipeline.hip); the big-tile kernel takes the 64 full 256-row
-// tiles and leaves those 8 rows to a second launch -- 36 of them per volume (qkv, out-proj, fc2 of 12 blocks).  On the
-// 64 x 64 tile kernel such a product is a chain of K / 64 dependent stage-and-wait steps on a few dozen workgroups:
-// ~20 us each, latency-bound.  Here a workgroup owns 16 output columns; its NW waves split K, every wave loads its
-// weight fragments (the MFMA A operand: 16 rows x 64 contiguous bytes per instruction) and activation fragments straight
-// from memory -- all loads of a wave are issued before its first MFMA, so the whole product costs about one memory latency
-// -- and the waves' partial tiles are added through LDS in a fixed order (bit-repeatable).  v_mfma_f32_16x16x32_bf16 with
-// the weights as A: a lane ends up with 4 consecutive output columns of one row, as in the tile kernels.
-// PAIR (GEMM_SWIGLU: B = [gate rows | up rows], N = 2 I, C (M, I) = bf16(silu(gate)) * up -- the form the big-tile kernel has for
-// the prefill): the workgroup's 16 weight rows are 8 gate rows and the SAME 8 up rows, so the lanes of column groups 0 / 1 hold
-// the gates and those of groups 2 / 3 (32 lanes further) the matching ups; the decode step's SwiGLU launch goes away.
-template <int NW, bool PAIR = false>
-__global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(GemmDesc d) {
-  __shared__ float red[NW][64][4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int l15 = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * 16;
-  const int nsteps = d.K >> 5;  // K % 32 == 0 (launcher)
-  const int per = (nsteps + NW - 1) / NW, s0 = wv * per, s1 = min(nsteps, s0 + per);
-  const int I2 = d.N >> 1;
-  const int nrow = PAIR ? min((l15 < 8 ? 0 : I2) + (int)blockIdx.x * 8 + (l15 & 7), d.N - 1) : min(n0 + l15, d.N - 1);
-  const int mrow = min(l15, d.M - 1);
-  const bf16_t* wp = d.B + (int64_t)nrow * d.ldb + g * 8;
-  const bf16_t* xp = d.A + (int64_t)mrow * d.lda + g * 8;
-  const f32x4 acc = rows16_slice(wp, xp, s0, s1);   // (rows16.h: shared with the big-tile kernel's in-launch tail)
-  // lane holds C[m = l15][n = n0 + 4 g + r]
-  red[wv][lane][0] = acc[0]; red[wv][lane][1] = acc[1]; red[wv][lane][2] = acc[2]; red[wv][lane][3] = acc[3];
-  __syncthreads();
-  if (wv != 0 || (!PAIR && l15 >= d.M)) return;
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int w = 0; w < NW; ++w)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += red[w][lane][r];
-  const int m = l15;
-  if constexpr (PAIR) {  // (wave 0, all 64 lanes: lanes of rows >= M carry copies of row M - 1 and write nothing)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float gate = bf16_to_f32(f32_to_bf16(v[r] * d.alpha));
-      const float up = bf16_to_f32(f32_to_bf16(__shfl_xor(v[r], 32, 64) * d.alpha));  // column group g + 2 of the same row
-      const int n = (int)blockIdx.x * 8 + 4 * g + r;
-      if (g < 2 && l15 < d.M && n < I2) {
-        const float sg = gate / (1.0f + __expf(-gate));
-        reinterpret_cast<bf16_t*>(d.C)[(int64_t)m * d.ldc + n] = f32_to_bf16(bf16_to_f32(f32_to_bf16(sg)) * up);
-      }
-    }
-    return;
-  }
-  rows16_store(d, v, m, n0 + 4 * g, reinterpret_cast<char*>(d.C), d.R);
-}
-
 // One step of a plan (gemm_plan.hip) on the rows it covers; `partial`: the stream's scratch.
 static int gemm_step(const GemmDesc& d, const GemmStep& s, void* partial, hipStream_t stream) {
   GemmDesc g = d;
@@ -471,11 +419,16 @@ static int gemm_step(const GemmDesc& d, const GemmStep& s, void* partial, hipStr
   g.tail_rows = s.tail_rows, g.tiles_m = s.tiles_m, g.tiles_n = s.tiles_n, g.mubuf = s.mubuf;
   const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
   int e;
-  if (s.kind == GK_ROWS16) {
-    void (*const k[2][3])(GemmDesc) = {{gemm_rows16_kernel<16, true>, gemm_rows16_kernel<8, true>, gemm_rows16_kernel<4, true>},
-                                       {gemm_rows16_kernel<16>, gemm_rows16_kernel<8>, gemm_rows16_kernel<4>}};
-    hipLaunchKernelGGL(k[!s.pair][2 - s.form / 8], grid, dim3(s.form * 64), 0, stream, g);
-    e = launch_status();
+  if (s.kind == GK_ROWS16) {  // (gemm_rows.hip)
+    RowsArgs a;
+    static_cast<RowsEpi&>(a) = rows_epi(g);
+    a.A = g.A; a.W = g.B; a.C = g.C; a.R = g.R;
+    a.M = g.M; a.K = g.K;
+    a.lda = g.lda; a.ldw = g.ldb;
+    // the launcher derives waves, pair form and grid from the product; the plan (what gemm_plan_format prints) must say the same
+    if (s.form != rows16_slices(g.K >> 5) || s.pair != bool(g.flags & GEMM_SWIGLU) || s.grid[0] != (int)cdiv(s.pair ? g.N >> 1 : g.N, s.pair ? 8 : 16))
+      return U2_ERR_ARG;
+    e = gemm_rows_launch(a, stream);
   } else if (s.kind == GK_TILE) {
     void (*const k[2][3])(GemmDesc) = {
         {gemm_bf16_nt_kernel<128, 128, true, true>, gemm_bf16_nt_kernel<128, 128, false, true>, gemm_bf16_nt_kernel<128, 128>},
@@ -488,46 +441,6 @@ static int gemm_step(const GemmDesc& d, const GemmStep& s, void* partial, hipStr
   if (e != U2_OK || s.ksplit == 1) return e;
   // split-K: the epilogue over g.partial[ksplit][nz][M][N]
   hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)cdiv((int64_t)g.nz * g.M * ((g.N + 3) >> 2), 256)), dim3(256), 0, stream, g);
-  return launch_status();
-}
-
-// The few-rows product outside the plan (kernels.h): what the decode step of more than 16 sequences calls directly -- the plan of an
-// M = 17 .. 64 product is a tile kernel's, pinned for the training path.
-int gemm_rows_check(const GemmDesc& d) {
-  const bool pair = d.flags & GEMM_SWIGLU;
-  if (!d.A || !d.B || !d.C || d.M <= 0 || d.M > 64 || d.N <= 0 || d.K <= 0 || (d.K & 31) || d.nz != 1) return U2_ERR_ARG;
-  if (d.flags & ~(GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_SWIGLU)) return U2_ERR_ARG;
-  if (pair && (d.flags != GEMM_SWIGLU || (d.N & 15))) return U2_ERR_ARG;  // gate | up: N = 2 I, I % 8 == 0
-  if (((d.flags & GEMM_BIAS_N) && !d.bias) || ((d.flags & GEMM_RESIDUAL) && (!d.R || d.ldr < d.N))) return U2_ERR_ARG;
-  if (d.lda < d.K || (d.lda & 7) || d.ldb < d.K || (d.ldb & 7) || d.ldc < (pair ? d.N >> 1 : d.N)) return U2_ERR_ARG;
-  if ((((uintptr_t)d.A | (uintptr_t)d.B) & 15) || ((uintptr_t)d.C & ((d.flags & GEMM_OUT_F32) ? 3 : 1))) return U2_ERR_ARG;
-  return U2_OK;
-}
-
-int gemm_rows(const GemmDesc& d, hipStream_t stream) {
-  const int e = gemm_rows_check(d);
-  if (e != U2_OK) return e;
-  if (d.M > 16) {
-    RowsW8Args a;
-    a.A = d.A; a.W = reinterpret_cast<const uint8_t*>(d.B); a.C = d.C; a.bias = d.bias; a.R = d.R;
-    a.M = d.M; a.N = d.N; a.K = d.K;
-    a.lda = d.lda; a.ldw = d.ldb; a.ldc = d.ldc; a.ldr = d.ldr;
-    a.flags = d.flags;
-    return gemm_rows64_launch(a, false, stream);
-  }
-  GemmDesc g;  // (the fields the product has, everything else as constructed: alpha = 1, no column split)
-  g.A = d.A; g.B = d.B; g.C = d.C; g.bias = d.bias; g.R = d.R;
-  g.M = d.M; g.N = d.N; g.K = d.K;
-  g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.ldr = d.ldr;
-  g.flags = d.flags;
-  const bool pair = d.flags & GEMM_SWIGLU;
-  const double out_b = pair ? 2.0 * d.M * (d.N >> 1) : ((d.flags & GEMM_OUT_F32) ? 4.0 : 2.0) * d.M * d.N;
-  ProfScope ps(PROF_GEMM, 2.0 * d.M * d.N * d.K, stream,
-               2.0 * d.M * d.K + 2.0 * d.N * d.K + out_b + ((d.flags & GEMM_RESIDUAL) ? 2.0 * d.M * d.N : 0.0));
-  const int nw = rows16_slices(d.K >> 5);
-  void (*const k[2][3])(GemmDesc) = {{gemm_rows16_kernel<16, true>, gemm_rows16_kernel<8, true>, gemm_rows16_kernel<4, true>},
-                                     {gemm_rows16_kernel<16>, gemm_rows16_kernel<8>, gemm_rows16_kernel<4>}};
-  hipLaunchKernelGGL(k[!pair][2 - nw / 8], dim3((unsigned)cdiv(d.N, 16)), dim3(nw * 64), 0, stream, g);
   return launch_status();
 }
 

@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "kernels.h"
-#include "rows16.h"
+#include "rows.h"
 
 namespace u2 {
 
@@ -297,7 +297,7 @@ typedef int bt_i32x4 __attribute__((ext_vector_type(4)));
 // a shape and are gone).  VT (256 x 192, deep): output tiles at columns >= d.vt_n0 run the loop with the MFMA operands exchanged and
 // leave their TRANSPOSED tile in d.vt (vt_epilogue) instead of C -- the ViT's q|k|v product writes V^T for the flash kernel itself.
 // TAIL: d.tail_rows rows behind the M rows of the tiles (the cls rows of the ViT: 8 behind 16384) are computed IN this launch, before the
-// first tile, by the few-rows arithmetic of rows16.h -- workgroup b takes the 16-column blocks b, b + grid, ...; its four waves run the
+// first tile, by the few-rows arithmetic of rows.h -- workgroup b takes the 16-column blocks b, b + grid, ...; its four waves run the
 // slices the few-rows kernel's 4 / 8 / 16 waves would, so the values are those of a gemm_rows16 launch bit for bit, which it replaces
 // (48 launches of ~7-10 us per volume; the workgroups concerned start their tiles ~2 us later).
 template <int NWV>
@@ -309,12 +309,14 @@ __device__ __forceinline__ void bt_tail_block(const GemmDesc& d, int n0, float (
   const bf16_t* Rt = (d.flags & GEMM_RESIDUAL) ? d.R + (int64_t)d.M * d.ldr : nullptr;
   const int nsteps = d.K >> 5, per = (nsteps + NWV - 1) / NWV;
   const int nrow = min(n0 + l15, d.N - 1), mrow = min(l15, d.tail_rows - 1);
-  const bf16_t* wp = d.B + (int64_t)nrow * d.ldb + g * 8;
-  const bf16_t* xp = At + (int64_t)mrow * d.lda + g * 8;
+  const char* wp = reinterpret_cast<const char*>(d.B + (int64_t)nrow * d.ldb + g * 8);
+  const bf16_t* const xp[1] = {At + (int64_t)mrow * d.lda + g * 8};
+  const RowsEpi e = rows_epi(d);
   for (int vw = wv; vw < NWV; vw += 4) {   // the slices of "waves" wv, wv + 4, ...
     const int s0 = vw * per, s1 = min(nsteps, s0 + per);
-    const f32x4 acc = rows16_slice(wp, xp, s0, s1);
-    red[vw][lane][0] = acc[0]; red[vw][lane][1] = acc[1]; red[vw][lane][2] = acc[2]; red[vw][lane][3] = acc[3];
+    f32x4 acc[1];
+    rows_slice<1, false>(wp, xp, s0, s1, acc);
+    red[vw][lane][0] = acc[0][0]; red[vw][lane][1] = acc[0][1]; red[vw][lane][2] = acc[0][2]; red[vw][lane][3] = acc[0][3];
   }
   __syncthreads();
   if (wv == 0 && l15 < d.tail_rows) {
@@ -323,7 +325,7 @@ __device__ __forceinline__ void bt_tail_block(const GemmDesc& d, int n0, float (
     for (int w = 0; w < NWV; ++w)
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] += red[w][lane][r];
-    rows16_store(d, v, l15, n0 + 4 * g, Ct, Rt);
+    rows_store(e, v, l15, n0 + 4 * g, Ct, Rt);
   }
   __syncthreads();  // red is free again
 }

@@ -3,7 +3,7 @@
 // (tests/test_gemm_plan.py compiles this file with a small driver and checks the routes on the CPU).
 #include <cstdio>
 #include <algorithm>
-#include "kernels.h"
+#include "rows.h"  // rows16_slices
 
 namespace u2 {
 
@@ -43,14 +43,14 @@ namespace {
 
 void push(GemmPlan& p, const GemmStep& s) { p.step[p.nsteps++] = s; }
 
-// ------------------------------------------------------------------------------------------------ M <= 16 rows (gemm.hip)
+// ------------------------------------------------------------------------------------------------ M <= 16 rows (gemm_rows.hip)
 // one batch entry, K-contiguous operands, K % 32 == 0
 bool rows16_ok(const GemmDesc& d) {
   return d.M <= 16 && d.nz == 1 && !(d.K & 31) && !d.ldbk && !(d.flags & (GEMM_A_KMAJOR | GEMM_B_KMAJOR));
 }
 
 GemmStep rows16_step(const GemmDesc& d, int row0) {
-  GemmStep s{GK_ROWS16, d.K >= 64 * 32 ? 16 : d.K >= 16 * 32 ? 8 : 4, row0, d.M};  // waves splitting the K / 32 steps
+  GemmStep s{GK_ROWS16, rows16_slices(d.K >> 5), row0, d.M};  // waves splitting the K / 32 steps
   s.pair = d.flags & GEMM_SWIGLU;
   s.grid[0] = (int)cdiv(d.N, 16);
   return s;

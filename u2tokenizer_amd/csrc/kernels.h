@@ -67,7 +67,7 @@ struct GemmDesc {
   int vt_n0 = 0, vt_rows = 0;
   int64_t vt_ld = 0, vt_bs = 0;
   // in-launch tail (filled by the big-tile launcher): rows [M, M + tail_rows) of A / C / R (<= 16: the ViT's cls rows behind the
-  // patch rows) are computed inside the same launch by the few-rows arithmetic (rows16.h) instead of a launch of their own
+  // patch rows) are computed inside the same launch by the few-rows arithmetic (rows.h) instead of a launch of their own
   int tail_rows = 0;
   // classic tile kernel (filled by its launcher): 1 = the LDS-DMA pieces leave as buffer_load ... lds (both operands of a batch entry
   // span < 2 GB), 0 = FLAT-encoded global_load_lds (option gemm_mubuf 0, or larger operands)
@@ -89,7 +89,7 @@ struct GemmStep {  // one kernel instantiation over rows [row0, row0 + rows) of 
   int row0 = 0, rows = 0;
   bool pair = false, ta = false, tb = false, mubuf = false, gelu = false, vt = false;  // template arguments
   int ksplit = 1, kt_per = 0;  // K slices (> 1: fp32 partial sums in the stream's scratch, then gemm_splitk_reduce_kernel)
-  int tail_rows = 0;           // GK_BIG: rows [row0 + rows, + tail_rows) computed in the same launch (rows16.h)
+  int tail_rows = 0;           // GK_BIG: rows [row0 + rows, + tail_rows) computed in the same launch (rows.h)
   int tiles_m = 0, tiles_n = 0;
   int grid[3] = {1, 1, 1};
 };
@@ -101,29 +101,32 @@ void gemm_plan_format(const GemmPlan& p, char* buf, size_t n);  // " | <kernel> 
 int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);  // gemm_skinny.hip
 int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);      // gemm_bt.hip
 
-// The few-rows product on e4m3 weights (gemm_w8.hip; arithmetic: rows16_w8.h): C = epilogue(scale[n] * A . e4m3(W)^T), M <= 64
-// (M > 16: gemm_rows64.hip, each block of 16 rows with the bits of the M <= 16 product on it), K % 64 == 0, 16-byte aligned A / W
-// rows.  gemm_rows_w8_check: the argument check alone (U2_ERR_ARG, nothing launched).
-struct RowsW8Args {        // outside GemmDesc and the plan
-  const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
-  const uint8_t* W = nullptr;    // [N][K] e4m3 codes, leading dim ldw (bytes)
-  const float* scale = nullptr;  // [N]
-  void* C = nullptr;             // [M][N] elements or fp32 (GEMM_OUT_F32); [M][N / 2] elements with GEMM_SWIGLU
-  const bf16_t* bias = nullptr;  // [N] (GEMM_BIAS_N)
-  const bf16_t* R = nullptr;     // [M][N], leading dim ldr (GEMM_RESIDUAL)
-  int M = 0, N = 0, K = 0;
-  int64_t lda = 0, ldw = 0, ldc = 0, ldr = 0;
-  int flags = 0;                 // GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32, or GEMM_SWIGLU alone
+// The few-rows (weight-streaming) product (gemm_rows.hip; arithmetic: rows.h): C = epilogue(A . W^T) for 1 <= M <= 64 rows on
+// weights in the element type (K % 32 == 0) or, with `scale` set, C = epilogue(scale[n] * A . e4m3(W)^T) on e4m3 codes
+// (K % 64 == 0); 16-byte aligned A / W rows.  Each block of 16 rows has the bits of the M <= 16 product on it.
+struct RowsEpi {                 // what the epilogue of a lane's 4 columns reads (rows.h: rows_store)
+  const bf16_t* bias = nullptr;  // [N] (GEMM_BIAS_N) or [M] (GEMM_BIAS_M)
+  int N = 0, flags = 0;
+  int nsplit = 0;                // columns n < nsplit take alpha_lo instead of alpha (GemmDesc)
+  int64_t ldc = 0, ldr = 0;
+  float alpha = 1.f, alpha_lo = 1.f;
 };
-int gemm_rows_w8_check(const RowsW8Args& a);
-int gemm_rows_w8(const RowsW8Args& a, hipStream_t stream);
-// The few-rows product on element-type weights outside the plan (gemm.hip): d.A (M, K), d.B (N, K), 1 <= M <= 64, K % 32 == 0, one
-// batch entry, flags GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 or GEMM_SWIGLU alone; every other field of d as constructed.
-// M <= 16: gemm_rows16_kernel as the plan launches it; M > 16: gemm_rows64.hip.  gemm_rows_check: the argument check alone.
-int gemm_rows_check(const GemmDesc& d);
-int gemm_rows(const GemmDesc& d, hipStream_t stream);
-// 16 < a.M <= 64 (gemm_rows64.hip; arguments checked by the two callers above); w8 = false: a.W / a.ldw are elements, no scale
-int gemm_rows64_launch(const RowsW8Args& a, bool w8, hipStream_t stream);
+struct RowsArgs : RowsEpi {
+  const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
+  const void* W = nullptr;       // [N][K], leading dim ldw: e4m3 codes and bytes when `scale` is set, else elements of the element type
+  const float* scale = nullptr;  // [N], or null: 16-bit weights
+  void* C = nullptr;             // [M][N] elements or fp32 (GEMM_OUT_F32); [M][N / 2] elements with GEMM_SWIGLU
+  const bf16_t* R = nullptr;     // [M][N], leading dim ldr (GEMM_RESIDUAL)
+  int M = 0, K = 0;
+  int64_t lda = 0, ldw = 0;
+};
+// gemm_rows: the product outside the plan -- what the decode step calls directly (the plan of an M = 17 .. 64 product is a tile
+// kernel's, pinned for the training path): flags GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 or GEMM_SWIGLU alone, alpha = 1 and no
+// column split.  gemm_rows_check: its argument check alone (U2_ERR_ARG, nothing launched).  gemm_rows_launch: the launch alone, for
+// a step of the plan (gemm.hip: gemm_step), whose product gemm_validate and rows16_ok have checked and gemm_bf16 brackets.
+int gemm_rows_check(const RowsArgs& a);
+int gemm_rows(const RowsArgs& a, hipStream_t stream);
+int gemm_rows_launch(const RowsArgs& a, hipStream_t stream);
 
 // ------------------------------------------------------------------ row ops (rowops.hip)
 // y[b][r][:] = LayerNorm(x[b][r][:] (+ res[b][r][:])) * w + bias   (bf16 in/out, fp32 math)
@@ -326,7 +329,7 @@ struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
   float eps, qk_eps, scale;
 };
 // A layer's decode-step parameters (u2tok_decode_layer).  No scale set: the four W* are in the element type; all four set: they
-// are e4m3 codes with a scale per weight row (gemm_w8.hip), which asks E, Hq * D and I multiples of 64, 16-byte aligned weights
+// are e4m3 codes with a scale per weight row (gemm_rows.hip), which asks E, Hq * D and I multiples of 64, 16-byte aligned weights
 // and 4-byte aligned scales.  Some set: U2_ERR_ARG, like every other refusal before anything is launched.
 // One segment of a few-rows adapter group (lora_rows.hip; the layout of u2tok_lora_seg): A (r, K) and B (N, r) contiguous, the
 // segment's columns [col0, col0 + N) of the product it is added to

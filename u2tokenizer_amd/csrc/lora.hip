@@ -2,13 +2,13 @@
 // {16, 32, 64} rows or columns (include/u2tok.h: u2tok_lora_down / u2tok_lora_up / u2tok_lora_wgrad).  They do not go through the
 // GEMM plan: a rank-16 panel on a 128 x 128 tile wastes 7/8 of every MFMA, and the K-major forms want dimensions a 16-wide operand
 // meets only by accident.  Common rules: 16-bit operands in the build's element type, fp32 accumulation on v_mfma_f32_16x16x32
-// (mfma16 of common.h, the fragment maps of rows16.h: the small operand is the A operand, so a lane ends up with 4 consecutive
+// (mfma16 of common.h, the fragment maps of rows.h: the small operand is the A operand, so a lane ends up with 4 consecutive
 // values of the small dimension or of the output row), ONE rounding at the store, no atomics and a fixed order of every sum (two
 // calls give the same bits), row-strided operands with unit column stride, so that a column segment of a packed q|k|v or gate|up
 // buffer is read and written in place.
 //
 //   down   U (M, r) = alpha X (M, K) A (r, K)^T.  One workgroup per 16 rows of X; K is cut into `nw` contiguous slices of 32-wide
-//          steps, one wave and one accumulator chain per slice (rows16.h with the roles exchanged: U^T = A X^T), 8 / (r / 16) steps
+//          steps, one wave and one accumulator chain per slice (rows.h with the roles exchanged: U^T = A X^T), 8 / (r / 16) steps
 //          of loads in flight per lane; the slices' 16 x r tiles are added through LDS in slice order.  X is read once, 64
 //          contiguous bytes per row and step; A (r x K, L2 resident) once per workgroup.
 //   up     Y (M, N) = [Y +] alpha U (M, r) W (N, r)^T.  No reduction across waves: a wave owns 16 rows x 64 columns at a time.  The

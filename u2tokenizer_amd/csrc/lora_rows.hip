@@ -26,7 +26,7 @@ struct RowsSeg {
   int tile0, blk0;        // first 16 x 16 fp32 tile of a slice row in the workspace / first workgroup of launch 2
   float scale;
 };
-struct RowsArgs {
+struct LoraRowsArgs {
   RowsSeg s[3];
   int n;
 };
@@ -62,7 +62,7 @@ __device__ __forceinline__ void rows_down_slice(const bf16_t* __restrict__ xp, c
   for (int t = 0; t < R16; ++t) out[t * 64 + lane] = acc[t];
 }
 
-__global__ __launch_bounds__(64) void lora_rows_down_kernel(const bf16_t* __restrict__ X, int64_t ldx, RowsArgs a, f32x4* __restrict__ ws,
+__global__ __launch_bounds__(64) void lora_rows_down_kernel(const bf16_t* __restrict__ X, int64_t ldx, LoraRowsArgs a, f32x4* __restrict__ ws,
                                                             int M, int nsteps, int per, int nslices, int rsum16) {
   const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
   const int sl = blockIdx.x, m0 = blockIdx.z * 16;
@@ -125,7 +125,7 @@ __device__ __forceinline__ void rows_up_unit(const bf16_t* us, const bf16_t* __r
   }
 }
 
-__global__ __launch_bounds__(64 * ROWS_UP_WAVES) void lora_rows_up_kernel(RowsArgs a, const f32x4* __restrict__ ws, bf16_t* __restrict__ U,
+__global__ __launch_bounds__(64 * ROWS_UP_WAVES) void lora_rows_up_kernel(LoraRowsArgs a, const f32x4* __restrict__ ws, bf16_t* __restrict__ U,
                                                                           int64_t ldu, bf16_t* Y, int64_t ldy, int M, int nslices,
                                                                           int rsum16) {
   __shared__ __attribute__((aligned(16))) bf16_t us[16 * ROWS_US];
@@ -200,7 +200,7 @@ int lora_rows(const bf16_t* X, int64_t ldx, const LoraSeg* segs, int n, bf16_t* 
   if (ws_bytes < lora_rows_workspace_bytes(M, K, segs, n)) return U2_ERR_WORKSPACE;
   if (check_only) return U2_OK;
   const int nsteps = K / 32, per = rows_per_slice(nsteps), nslices = (nsteps + per - 1) / per, mb = (M + 15) / 16;
-  RowsArgs a;
+  LoraRowsArgs a;
   a.n = n;
   int ucol = 0, blk = 0;
   for (int i = 0; i < 3; ++i) {

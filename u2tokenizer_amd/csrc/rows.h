@@ -1,0 +1,155 @@
+// The arithmetic of the few-rows product (1 .. 64 rows against N x K weights in the element type or as e4m3 codes), shared by
+// gemm_rows16_kernel (gemm_rows.hip) and by the big-tile kernel's in-launch tail (gemm_bt.hip, round 5: the ViT's 8 cls rows ride in
+// the launch of the 16384 patch rows instead of a launch of their own) -- ONE definition, so that a row's value does not depend on
+// which of them computed it, on the weight form's kernel, or on how many row blocks share the pass over K:
+//   * K is cut into NW contiguous slices of `per` steps; a slice is ONE accumulator chain of v_mfma_f32_16x16x32 per block of 16
+//     rows, in step order (weights as the A operand: a lane ends up with 4 consecutive output columns of one row);
+//   * the NW partial 16 x 16 tiles of a row block are added in slice order 0 .. NW - 1, then the epilogue of the product is applied.
+// THE CONTRACT for 17 .. 64 rows (NB = 2 .. 4 blocks of 16 rows in ONE pass over K -- a weight fragment is loaded once and feeds NB
+// MFMAs, one per row block; the decode step of 17 .. 64 sequences streams its weights once, as the step of 16 does): row m of an M-row
+// product has the bits it has as row m % 16 of the M <= 16 product on rows 16 (m / 16) .. min(M, 16 (m / 16) + 16) - 1.  Per
+// 16 x 16 tile nothing differs; only the schedule is another (rows_in_flight).
+//
+// 16-bit weights: a step covers 32 k; lane group g = lane / 16 owns k = 32 s + 8 g .. + 7: one 16-byte load of 8 elements, one MFMA.
+//
+// OCP e4m3 (1-byte) weights: the same product with the weight operand read as 8-bit codes, widened to the element type in registers
+// (every e4m3 value is exact in bf16 and in fp16) and ONE fp32 scale per weight row applied to the cross-wave sum:
+// C[m][n] = epilogue(scale[n] * sum_k x[m][k] * e4m3(W8[n][k])), fp32 accumulation.  Nothing in here is lossy beyond the 16-bit
+// product's own roundings; the quantiser (ops.quantize_rows_fp8) is.
+// THE K MAPPING (weights and activations use the same one, so any k reaches the MFMA on both sides in the same slot):
+//   * K is cut into K / 64 DOUBLE STEPS; double step s covers k = 64 s .. 64 s + 63;
+//   * lane group g = lane / 16 (0 .. 3) of a double step owns k = 64 s + 16 g .. 64 s + 16 g + 15: ONE 16-byte weight load (16
+//     codes) and two 16-byte activation loads;
+//   * its first 8 values (k = 64 s + 16 g + 0 .. 7) are the group's 8 K slots of MFMA 1 of the double step, the next 8
+//     (k = 64 s + 16 g + 8 .. 15) those of MFMA 2 -- v_mfma_f32_16x16x32 sums its 32 slots, whichever k sits in them.
+//   * the double steps are cut into NW contiguous slices (one per wave, `per` double steps each); a slice is one accumulator chain
+//     in double-step order, MFMA 1 before MFMA 2; the NW partial tiles are added in slice order 0 .. NW - 1.
+#pragma once
+#include <type_traits>
+#include "kernels.h"
+
+namespace u2 {
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+// 8 e4m3 codes (two dwords, ascending k) -> one MFMA fragment of 8 elements: v_cvt_pk_f32_fp8 x 4, the element type's pack x 4
+__device__ __forceinline__ bf16x8 w8_widen(uint32_t lo, uint32_t hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  const u32x4 p = {pack2_bf16(a.x, a.y), pack2_bf16(b.x, b.y), pack2_bf16(c.x, c.y), pack2_bf16(d.x, d.y)};
+  return __builtin_bit_cast(bf16x8, p);
+#else
+  (void)lo; (void)hi;
+  return bf16x8{};
+#endif
+}
+
+// Steps (W8: double steps) whose loads are in flight before the first MFMA.  One row block: 8 = 16 loads (W8: 8 weight + 16
+// activation loads) per lane.  NB > 1: 4 steps = 4 (1 + NB) loads, 2 double steps = 2 weight + 4 NB activation loads, because 8 x
+// (1 weight + 4 activation fragments) do not fit the 128 VGPRs a lane of a 16-wave workgroup has.
+constexpr int rows_in_flight(int NB, bool W8) { return NB == 1 ? 8 : W8 ? 2 : 4; }
+// The loop form.  Whole blocks of U steps run without a guard per step (a guarded step lets the compiler sink its loads behind the
+// MFMAs before it), then the rest of the slice (< U) is one guarded block; where codes are converted, a scheduling barrier keeps
+// every load of a block ahead of its first conversion.  On weights streamed from memory the 16-bit NB > 1 loops are 2 to 11 % faster in
+// this form than with every block clamped and guarded (profiles/few_rows_variants.json).  NOT for e4m3 codes with NB > 1
+// (rows_guarded): there every block is clamped and guarded and nothing is fenced, because the two-body form with the fence holds
+// 2 + 4 NB fragments AND the widened codes at once -- 96 .. 116 VGPRs instead of 42 .. 82, occupancy 4 .. 5 waves per SIMD
+// instead of 7 .. 8 in the compiler's resource report; without the fence still 5 .. 6 instead of 7 .. 8.
+constexpr bool rows_guarded(int NB, bool W8) { return W8 && NB > 1; }
+
+// Steps [s0, s1) of one slice for NB row blocks.  wp = the lane's weight row + 16 g bytes (a step is 64 bytes of a weight row in
+// either form: 8 elements or 16 codes per lane group); xp[b] = its activation row of block b + 8 g (W8: 16 g) elements.  A weight
+// fragment feeds the NB blocks in block order; a code is widened once for all of them.  The bounds are the same for all lanes of a
+// wave; they are moved to scalar registers here, so that the guards below are scalar branches and never EXEC masks around an MFMA
+// (MFMA ignores EXEC: as lane values the guards have left a guarded MFMA without its skip-if-EXEC-is-empty branch, a step counted twice).
+template <int NB, bool W8>
+__device__ __forceinline__ void rows_slice(const char* wp, const bf16_t* const (&xp)[NB], int s0_, int s1_, f32x4 (&acc)[NB]) {
+  const int s0 = __builtin_amdgcn_readfirstlane(s0_), s1 = __builtin_amdgcn_readfirstlane(s1_);
+  constexpr int U = rows_in_flight(NB, W8), NX = W8 ? 2 : 1;  // NX: activation fragments (= MFMAs per row block) of a step
+  constexpr bool G = rows_guarded(NB, W8);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto block = [&](int sb, auto whole) {
+    u32x4 wf[U];
+    bf16x8 xf[U][NB][NX];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int st = decltype(whole)::value ? sb + u : min(sb + u, s1 - 1);
+      wf[u] = *reinterpret_cast<const u32x4*>(wp + st * 64);
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int h = 0; h < NX; ++h) xf[u][b][h] = *reinterpret_cast<const bf16x8*>(xp[b] + st * (32 * NX) + 8 * h);
+    }
+    if constexpr (W8 && !G) __builtin_amdgcn_sched_barrier(0);  // every load above is issued before the first conversion / MFMA below
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (decltype(whole)::value || sb + u < s1) {
+        bf16x8 w[NX];
+        if constexpr (W8) w[0] = w8_widen(wf[u].x, wf[u].y), w[1] = w8_widen(wf[u].z, wf[u].w);
+        else w[0] = __builtin_bit_cast(bf16x8, wf[u]);
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+          for (int h = 0; h < NX; ++h) acc[b] = mfma16(w[h], xf[u][b][h], acc[b]);
+      }
+  };
+  int sb = s0;
+  if constexpr (G) {
+    for (; sb < s1; sb += U) block(sb, std::false_type{});
+  } else {
+    for (; sb + U <= s1; sb += U) block(sb, std::true_type{});
+    if (sb < s1) block(sb, std::false_type{});
+  }
+}
+
+// epilogue for the lane's 4 columns n = n_first .. n_first + 3 of row m (row index inside C / R / bias_m as handed over)
+__device__ __forceinline__ void rows_store(const RowsEpi& e, const float (&v)[4], int m, int n_first, char* C, const bf16_t* R) {
+  const bool out_f32 = e.flags & GEMM_OUT_F32;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = n_first + r;
+    if (n >= e.N) break;
+    float x = v[r] * (n < e.nsplit ? e.alpha_lo : e.alpha);
+    if (e.flags & GEMM_BIAS_M) x += bf16_to_f32(e.bias[m]);
+    if (e.flags & GEMM_BIAS_N) x += bf16_to_f32(e.bias[n]);
+    if (e.flags & GEMM_GELU) x = gelu_epi(x);
+    if (e.flags & GEMM_RESIDUAL) x += bf16_to_f32(R[(int64_t)m * e.ldr + n]);
+    if (out_f32) reinterpret_cast<float*>(C)[(int64_t)m * e.ldc + n] = x;
+    else reinterpret_cast<bf16_t*>(C)[(int64_t)m * e.ldc + n] = f32_to_bf16(x);
+  }
+}
+
+// The pair epilogue (GEMM_SWIGLU): C[m][n] = SiLU(gate) * up with the rounding points of swiglu_kernel -- gate and up each rounded
+// to the element type, silu rounded before the product, the product rounded on store.  v: the lane's 4 sums; mult(r): the
+// multiplier of sum r (alpha, or the weight row's scale), applied before the first rounding.  The lanes of column groups 0 / 1 hold
+// the gates of columns n_first .. n_first + 3 < I of row m, those 32 lanes further the matching ups; called by all 64 lanes,
+// `writes` picks the gate lanes of real rows.
+template <class Mult>
+__device__ __forceinline__ void rows_pair_store(const float (&v)[4], Mult mult, bool writes, int m, int n_first, int I, bf16_t* C,
+                                                int64_t ldc) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float t = v[r] * mult(r);
+    const float gate = bf16_to_f32(f32_to_bf16(t));
+    const float up = bf16_to_f32(f32_to_bf16(__shfl_xor(t, 32, 64)));  // column group g + 2 of the same row
+    const int n = n_first + r;
+    if (writes && n < I) {
+      const float sg = gate / (1.0f + __expf(-gate));
+      C[(int64_t)m * ldc + n] = f32_to_bf16(bf16_to_f32(f32_to_bf16(sg)) * up);
+    }
+  }
+}
+
+__host__ __device__ inline int rows16_slices(int nsteps) { return nsteps >= 64 ? 16 : nsteps >= 16 ? 8 : 4; }  // (the launcher's choice of NW)
+
+// the epilogue fields of a plan's product
+__host__ __device__ inline RowsEpi rows_epi(const GemmDesc& d) {
+  RowsEpi e;
+  e.bias = d.bias; e.N = d.N; e.flags = d.flags; e.nsplit = d.nsplit;
+  e.ldc = d.ldc; e.ldr = d.ldr; e.alpha = d.alpha; e.alpha_lo = d.alpha_lo;
+  return e;
+}
+
+}  // namespace u2

@@ -744,6 +744,31 @@ def snap_fp8_(module):
     return module
 
 
+def _rows_call(who, a, N, bias, residual, out_f32, swiglu, out):
+    """What gemm_rows and gemm_rows_w8 share: A as (M, K) rows with unit column stride, `out`, the flags, the residual and its
+    row stride -> (a2, out, bias, ldr, flags) for a weight of N rows"""
+    a2 = a.reshape(-1, a.shape[-1])
+    if a2.stride(1) != 1:
+        a2 = a2.contiguous()
+    M, cols = a2.shape[0], N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
+    if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
+        raise RuntimeError(f"{who}: out must be (M, columns) with unit column stride in the output type")
+    flags = GEMM_SWIGLU if swiglu else (GEMM_OUT_F32 if out_f32 else 0)
+    ldr = 0
+    if bias is not None:
+        flags |= GEMM_BIAS_N
+        bias = _need(bias, ELEM, "bias").contiguous()
+    if residual is not None:
+        flags |= GEMM_RESIDUAL
+        _need(residual, ELEM, "residual")
+        if residual.shape != (M, N) or residual.stride(1) != 1:
+            raise RuntimeError(f"{who}: residual must be (M, N) with unit column stride")
+        ldr = residual.stride(0)
+    return a2, out, bias, ldr, flags
+
+
 @_guarded
 def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias=None, residual=None, out_f32=False,
                  swiglu=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -755,34 +780,17 @@ def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias
     _need(a, ELEM, "A")
     if w8.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32 or not w8.is_cuda or not scale.is_cuda:
         raise RuntimeError("gemm_rows_w8: expected float8_e4m3fn weights and fp32 scales on the GPU")
-    a2 = a.reshape(-1, a.shape[-1])
-    if a2.stride(1) != 1:
-        a2 = a2.contiguous()
     w8, scale = w8.contiguous(), scale.contiguous()
-    M, K = a2.shape
     N = w8.shape[0]
-    if w8.shape[1] != K or scale.numel() != N:
-        raise RuntimeError(f"gemm_rows_w8: shapes A {tuple(a2.shape)}, W8 {tuple(w8.shape)}, scale {tuple(scale.shape)}")
-    cols = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
-    if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
-        raise RuntimeError("gemm_rows_w8: out must be (M, columns) with unit column stride in the output type")
-    flags = GEMM_SWIGLU if swiglu else (GEMM_OUT_F32 if out_f32 else 0)
-    ldr = 0
-    if bias is not None:
-        flags |= GEMM_BIAS_N
-        bias = _need(bias, ELEM, "bias").contiguous()
-    if residual is not None:
-        flags |= GEMM_RESIDUAL
-        _need(residual, ELEM, "residual")
-        if residual.shape != (M, N) or residual.stride(1) != 1:
-            raise RuntimeError("gemm_rows_w8: residual must be (M, N) with unit column stride")
-        ldr = residual.stride(0)
-    fn = h.u2tok_gemm_rows_w8_wide if M > 16 else h.u2tok_gemm_rows_w8
-    st = fn(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K, out.stride(0), ldr,
-            flags, _stream())
-    _lib.check(st, "u2tok_gemm_rows_w8_wide" if M > 16 else "u2tok_gemm_rows_w8")
+    if w8.shape[1] != a.shape[-1] or scale.numel() != N:
+        raise RuntimeError(f"gemm_rows_w8: shapes A {tuple(a.reshape(-1, a.shape[-1]).shape)}, W8 {tuple(w8.shape)}, "
+                           f"scale {tuple(scale.shape)}")
+    a2, out, bias, ldr, flags = _rows_call("gemm_rows_w8", a, N, bias, residual, out_f32, swiglu, out)
+    M, K = a2.shape
+    name = "u2tok_gemm_rows_w8_wide" if M > 16 else "u2tok_gemm_rows_w8"
+    st = getattr(h, name)(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K,
+                          out.stride(0), ldr, flags, _stream())
+    _lib.check(st, name)
     return out
 
 
@@ -795,31 +803,13 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, out
     rows | up rows -> (M, N / 2) = silu(gate) * up.  `w`, `out` and `residual` may be row-strided views (unit column stride)."""
     h = _lib.load_library()
     _need(a, ELEM, "A"), _need(w, ELEM, "W")
-    a2 = a.reshape(-1, a.shape[-1])
-    if a2.stride(1) != 1:
-        a2 = a2.contiguous()
     if w.dim() != 2 or w.stride(1) != 1:
         w = w.contiguous()
-    M, K = a2.shape
     N = w.shape[0]
-    if w.shape[1] != K:
-        raise RuntimeError(f"gemm_rows: shapes A {tuple(a2.shape)}, W {tuple(w.shape)}")
-    cols = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
-    if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
-        raise RuntimeError("gemm_rows: out must be (M, columns) with unit column stride in the output type")
-    flags = GEMM_SWIGLU if swiglu else (GEMM_OUT_F32 if out_f32 else 0)
-    ldr = 0
-    if bias is not None:
-        flags |= GEMM_BIAS_N
-        bias = _need(bias, ELEM, "bias").contiguous()
-    if residual is not None:
-        flags |= GEMM_RESIDUAL
-        _need(residual, ELEM, "residual")
-        if residual.shape != (M, N) or residual.stride(1) != 1:
-            raise RuntimeError("gemm_rows: residual must be (M, N) with unit column stride")
-        ldr = residual.stride(0)
+    if w.shape[1] != a.shape[-1]:
+        raise RuntimeError(f"gemm_rows: shapes A {tuple(a.reshape(-1, a.shape[-1]).shape)}, W {tuple(w.shape)}")
+    a2, out, bias, ldr, flags = _rows_call("gemm_rows", a, N, bias, residual, out_f32, swiglu, out)
+    M, K = a2.shape
     st = h.u2tok_gemm_rows(_ptr(a2), _ptr(w), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), w.stride(0),
                            out.stride(0), ldr, flags, _stream())
     _lib.check(st, "u2tok_gemm_rows")

@@ -851,14 +851,14 @@ def w8_weights(layer):
 def _decode_step(self, x, pe, cache, window, pr):
     """One decode step of a layer (B <= 16 new tokens -- wide_decode=True: B <= 64 --, one each, against the KV cache): the step `generate` repeats up to 768
     times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
-    few-rows GEMM (gemm.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
+    few-rows GEMM (gemm_rows.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
     fused kernel with the KEYS split over workgroups (batch x kv-head entries of (T, d) keys, the query heads of a group as its
     heads).  TWO library calls per layer (u2tok_decoder_decode_pre / _post, 10 launches) around the cache's own `update`: with a
     Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels).
     window = W (a sliding-window layer): the query attends over the last min(T, W) positions -- an offset into the cache
     buffers, the same kernels.
     B > 16 (the route's wide_decode switch): the same two calls; the library runs the four products on its 17 .. 64-row form of
-    the few-rows kernel (csrc/gemm_rows64.hip: the weights are still read once per step, and each block of 16 sequences gets the
+    the few-rows kernel (csrc/gemm_rows.hip: the weights are still read once per step, and each block of 16 sequences gets the
     bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch."""
     from . import _lib
     att = self.self_attn
@@ -1020,7 +1020,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     the fused step under the conditions of today's -- plus at most 16 query heads per kv head, because such a step always takes
     the batched decode attention; a left-padded one still needs padded=True, a right-padded one stays stock -- instead of the
     stock layers: the weights are streamed once per step however many sequences share it, each block of 16 sequences computes
-    the bits it would in a step of its own (csrc/rows64.h), and it composes with fp8_decode, Phi-3 layers and the
+    the bits it would in a step of its own (csrc/rows.h), and it composes with fp8_decode, Phi-3 layers and the
     append-in-place cache.  `wide_stats` counts these steps per layer call.  Off, batch 17 takes the stock layers as before.
     train_lora=True (opt-in; it implies train=True): the training route also takes a layer whose projections are LoRA-wrapped --
     u2tokenizer_amd.lora.LoRALinear or a module of the same layout (peft's lora.Linear, duck-typed: `lora.adapter_of` lists what
