@@ -1,0 +1,246 @@
+"""The cases of tests/test_gpu_decoder_route_bits.py: every host route of the decoder layers (prefill, continued prefill, decode
+step, training; u2tokenizer_amd/prefill.py) on two-layer decoders, pinned BIT FOR BIT in tests/golden/decoder_route_bits.json: per
+case the SHA-256 of each call's last hidden state, of every layer's cached keys and values, of the training cases' gradients, and
+the deltas of the route counters -- the route taken as well as the numbers.  Importable without a GPU (the host half of the test
+checks the case list and the inputs).
+
+Only the public surface is used -- the keywords of `enable_fused_prefill`, the counter dicts, u2tokenizer_amd.lora, transformers --
+so that the same file runs against the commit that recorded the fixture and against every later one.
+
+Models (2 layers each): Q = Qwen3, hidden 256, inter 512, 4 query / 2 kv heads of 64; L = Llama, hidden 256, inter 512, 2 / 1 heads
+of 128 with attention and MLP biases (no head norm, the unfused gate|up branch); P = Phi-3, hidden 384, inter 512, 4 / 4 heads of
+96, sliding_window 16.  A prefill has 70 positions (two 64-key tiles, the second ragged), a continuation 9, then 3 decode steps;
+all inputs are seeded `inputs_embeds`, the decode steps (B, 1, E), so that lm_head stays out.
+
+`python tests/decoder_route_cases.py --record --commit HASH --out FILE` runs every case on the GPU and writes the fixture; the test
+itself only ever reads it."""
+import argparse
+import hashlib
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+FIXTURE = Path(__file__).resolve().parent / "golden" / "decoder_route_bits.json"
+S0, CHUNK, STEPS, WINDOW = 70, 9, 3, 16
+bf, f16 = torch.bfloat16, torch.float16
+LORA_TARGETS = ("q_proj", "v_proj", "o_proj", "gate_proj", "down_proj")
+
+
+def _case(model, B=2, dtype=bf, flags=None, cache="dynamic", S=S0, chunk=0, steps=0, left=None, right=None, lora=None, off=None,
+          train=False, expect=()):
+    """model: Q / L / P.  cache: None, "dynamic" (an empty DynamicCache: the fused prefill puts its append-in-place layers there),
+    "config" (DynamicCache(config=...): sliding layers for P) or "stock" (a DynamicCache the STOCK forward filled with the prefill:
+    DynamicLayer, the dense `update` path).  left / right: pads per sequence.  lora: the wrapped projections' names; off: {name:
+    flag} wrappers that get `merged` / `disable_adapters` set.  expect: counters that must have moved (the host half reads them
+    off the fixture)."""
+    return dict(model=model, B=B, dtype=dtype, flags=flags or {}, cache=cache, S=S, chunk=chunk, steps=steps, left=left, right=right,
+                lora=lora, off=off or {}, train=train, expect=tuple(expect))
+
+
+CASES = {
+    # a / b / c: Qwen3 prefill without a cache, into an append-in-place cache + decode, decode on a stock-filled cache
+    "a-Q-prefill": _case("Q", cache=None, expect=("stats.prefill",)),
+    "b-Q-prefill-decode": _case("Q", steps=STEPS, expect=("stats.prefill", "stats.decode")),
+    "c-Q-decode-stock-cache": _case("Q", cache="stock", steps=STEPS, expect=("stats.decode",)),
+    "d-L-prefill": _case("L", cache=None, expect=("stats.prefill",)),
+    "d-L-prefill-decode": _case("L", steps=STEPS, expect=("stats.prefill", "stats.decode")),
+    "e-Q-f16": _case("Q", dtype=f16, steps=STEPS, expect=("stats.prefill", "stats.decode")),
+    "f-Q-left-padded": _case("Q", flags=dict(padded=True), left=(0, 5), steps=STEPS, expect=("stats.padded_prefill", "stats.padded_decode")),
+    "f-Q-right-padded-prefill": _case("Q", flags=dict(padded=True), right=(0, 5), expect=("stats.padded_prefill",)),
+    "g-Q-continued-append": _case("Q", flags=dict(continued=True), chunk=CHUNK, expect=("stats.prefill", "extend_stats.extend")),
+    "g-Q-continued-stock-cache": _case("Q", flags=dict(continued=True), cache="stock", chunk=CHUNK, expect=("extend_stats.extend",)),
+    "g-Q-continued-left-padded": _case("Q", flags=dict(continued=True, padded=True), left=(0, 5), chunk=CHUNK,
+                                       expect=("stats.padded_prefill", "extend_stats.padded_extend")),
+    "h-P-prefill-12": _case("P", S=12, cache=None, expect=("stats.prefill",)),
+    "i-P-prefill-24-band": _case("P", S=24, flags=dict(continued=True), cache=None, expect=("extend_stats.extend",)),
+    "j-P-decode-sliding": _case("P", S=12, cache="config", steps=STEPS, expect=("stats.prefill", "stats.decode")),
+    "j-P-decode-append": _case("P", S=12, steps=STEPS, expect=("stats.prefill", "stats.decode")),
+    # (... and with the window binding: 24 positions cached, the step attends over the last 16)
+    "j-P-decode-sliding-past-window": _case("P", S=24, flags=dict(continued=True), cache="config", steps=STEPS,
+                                            expect=("extend_stats.extend", "stats.decode")),
+    "j-P-decode-append-past-window": _case("P", S=24, flags=dict(continued=True), steps=STEPS,
+                                           expect=("extend_stats.extend", "stats.decode")),
+    "k-P-continued-append": _case("P", S=24, flags=dict(continued=True), chunk=CHUNK, expect=("extend_stats.extend",)),
+    "k-P-continued-sliding": _case("P", S=24, flags=dict(continued=True), cache="config", chunk=CHUNK, expect=("extend_stats.extend",)),
+    "l-Q-fp8-decode": _case("Q", flags=dict(fp8_decode=True), steps=STEPS, expect=("stats.prefill", "w8_stats.decode")),
+    "m-Q-wide": _case("Q", B=17, flags=dict(wide_decode=True), steps=2, expect=("stats.prefill", "wide_stats.decode")),
+    "m-Q-wide-left-padded": _case("Q", B=17, flags=dict(wide_decode=True, padded=True), left=tuple((3 * b) % 7 for b in range(17)),
+                                  steps=2, expect=("stats.padded_prefill", "wide_stats.padded_decode")),
+    "n-Q-lora": _case("Q", flags=dict(lora=True, continued=True), lora=LORA_TARGETS, chunk=CHUNK, steps=STEPS,
+                      expect=("lora_stats.prefill", "lora_stats.extend", "lora_stats.decode", "lora_stats.adapters")),
+    "o-Q-lora-fp8": _case("Q", flags=dict(lora=True, fp8_decode=True), lora=LORA_TARGETS, steps=STEPS,
+                          expect=("lora_stats.prefill", "lora_stats.decode", "w8_stats.decode")),
+    "p-P-lora-packed-qkv": _case("P", S=12, flags=dict(lora=True, continued=True), lora=("qkv_proj",), chunk=CHUNK, steps=STEPS,
+                                 expect=("lora_stats.prefill", "lora_stats.extend", "lora_stats.decode")),
+    "q-Q-lora-merged-and-disabled": _case("Q", flags=dict(lora=True), lora=LORA_TARGETS, off={"q_proj": "merged", "o_proj": "disable_adapters"},
+                                          steps=STEPS, expect=("lora_stats.prefill", "lora_stats.decode")),
+    "r-Q-train": _case("Q", flags=dict(train=True), right=(0, 9), cache=None, train=True, expect=("train.stats.layers",)),
+    "s-P-train-phi3": _case("P", S=12, flags=dict(train=True, train_phi3=True), cache=None, train=True, expect=("train.stats.layers",)),
+    "t-Q-train-lora": _case("Q", flags=dict(train_lora=True), lora=LORA_TARGETS, cache=None, train=True,
+                            expect=("train.stats.layers", "train.lora_stats.adapters")),
+}
+# the test functions (a few seconds each): the cases by what they exercise
+GROUPS = {
+    "plain": ("a-Q-prefill", "b-Q-prefill-decode", "c-Q-decode-stock-cache", "d-L-prefill", "d-L-prefill-decode", "e-Q-f16"),
+    "padded-continued": ("f-Q-left-padded", "f-Q-right-padded-prefill", "g-Q-continued-append", "g-Q-continued-stock-cache",
+                         "g-Q-continued-left-padded"),
+    "phi3": ("h-P-prefill-12", "i-P-prefill-24-band", "j-P-decode-sliding", "j-P-decode-append", "j-P-decode-sliding-past-window",
+             "j-P-decode-append-past-window", "k-P-continued-append", "k-P-continued-sliding"),
+    "fp8-wide": ("l-Q-fp8-decode", "m-Q-wide", "m-Q-wide-left-padded"),
+    "lora": ("n-Q-lora", "o-Q-lora-fp8", "p-P-lora-packed-qkv", "q-Q-lora-merged-and-disabled"),
+    "train": ("r-Q-train", "s-P-train-phi3", "t-Q-train-lora"),
+}
+
+
+def case_ids():
+    return list(CASES)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the inputs
+def build_model(kind):
+    """The fp32 model on the CPU with seeded weights."""
+    from transformers import LlamaConfig, LlamaForCausalLM, Phi3Config, Phi3ForCausalLM, Qwen3Config, Qwen3ForCausalLM
+    from u2tokenizer_amd import synth
+    common = dict(vocab_size=256, num_hidden_layers=2, intermediate_size=512, max_position_embeddings=512, tie_word_embeddings=False,
+                  pad_token_id=0, bos_token_id=1, eos_token_id=2)
+    if kind == "Q":
+        m = Qwen3ForCausalLM(Qwen3Config(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64, **common))
+    elif kind == "L":
+        m = LlamaForCausalLM(LlamaConfig(hidden_size=256, num_attention_heads=2, num_key_value_heads=1, head_dim=128,
+                                         attention_bias=True, mlp_bias=True, **common))
+    else:
+        m = Phi3ForCausalLM(Phi3Config(hidden_size=384, num_attention_heads=4, num_key_value_heads=4, sliding_window=WINDOW, **common))
+    synth.fill_module_(m, seed=29, prefix="decoder.")
+    return m.eval()
+
+
+def wrap(m, c):
+    """The case's adapters: rank 16, fp32 A / B, no dropout, seeded and non-zero; then the `off` flags."""
+    from u2tokenizer_amd import synth
+    from u2tokenizer_amd.lora import LoRALinear, add_lora
+    add_lora(m, r=16, alpha=32, dropout=0.0, target_modules=c["lora"], adapter_dtype=torch.float32)
+    for name, mod in m.named_modules():
+        if isinstance(mod, LoRALinear):
+            A, B = mod.lora_A["default"].weight, mod.lora_B["default"].weight
+            with torch.no_grad():
+                A.copy_(synth.synth_tensor(name + ".lora_A.weight", A.shape, 31).to(A.device))
+                B.copy_(0.3 * synth.synth_tensor(name + ".lora_B.weight", B.shape, 31).to(B.device))
+            flag = c["off"].get(name.rsplit(".", 1)[-1])
+            if flag:
+                setattr(mod, flag, True)
+    return m
+
+
+def embeds(c, name, n):
+    """Seeded (B, n, E) inputs of one call."""
+    from u2tokenizer_amd import synth
+    E = 384 if c["model"] == "P" else 256
+    return 0.5 * synth.synth_tensor(name, (c["B"], n, E), 37)
+
+
+def mask(c, n):
+    """The 2-D attention mask of a call that sees n keys in all (None: no padding in the case)."""
+    if c["left"] is None and c["right"] is None:
+        return None
+    m = torch.ones(c["B"], n, dtype=torch.int64)
+    for b in range(c["B"]):
+        if c["left"] is not None:
+            m[b, :c["left"][b]] = 0
+        else:
+            m[b, c["S"] - c["right"][b]:c["S"]] = 0
+    return m
+
+
+# ------------------------------------------------------------------------------------------------------------------ running a case
+def _sha(t):
+    t = t.detach().contiguous().cpu()
+    return hashlib.sha256(t.view(torch.int32 if t.dtype == torch.float32 else torch.int16).numpy().tobytes()).hexdigest()
+
+
+def _counters():
+    from u2tokenizer_amd import decoder_train, prefill
+    dicts = {"stats": prefill.stats, "extend_stats": prefill.extend_stats, "w8_stats": prefill.w8_stats, "wide_stats": prefill.wide_stats,
+             "lora_stats": prefill.lora_stats, "train.stats": decoder_train.stats, "train.lora_stats": decoder_train.lora_stats}
+    return {f"{n}.{k}": v for n, d in dicts.items() for k, v in d.items()}
+
+
+def run_case(cid):
+    """One case on the GPU -> {"digests": {what: SHA-256}, "stats": {counter: delta}}"""
+    from transformers.cache_utils import DynamicCache
+    from u2tokenizer_amd.prefill import disable_fused_prefill, enable_fused_prefill
+    c = CASES[cid]
+    dev = "cuda"
+    m = build_model(c["model"]).to(c["dtype"]).to(dev)
+    if c["lora"]:
+        wrap(m, c)
+    dig = {}
+    before = _counters()
+    kw = lambda n: {} if mask(c, n) is None else {"attention_mask": mask(c, n).to(dev)}   # noqa: E731
+    if c["train"]:
+        m.train()
+        enable_fused_prefill(m, **c["flags"])
+        x = embeds(c, "x_train", c["S"]).to(c["dtype"]).to(dev).requires_grad_(True)
+        with torch.enable_grad():
+            out = m.model(inputs_embeds=x, use_cache=False, **kw(c["S"])).last_hidden_state
+            out.backward(embeds(c, "cotangent", c["S"]).to(c["dtype"]).to(dev))
+        dig["out"] = _sha(out)
+        dig["grad.x"] = _sha(x.grad)
+        for name, p in m.model.named_parameters():
+            if p.grad is not None and (name.startswith("layers.0.") or ".lora_" in name):
+                dig["grad." + name] = _sha(p.grad)
+    else:
+        S, B = c["S"], c["B"]
+        cache = None if c["cache"] is None else DynamicCache(config=m.config) if c["cache"] == "config" else DynamicCache()
+        x = embeds(c, "x_prefill", S).to(c["dtype"]).to(dev)
+        with torch.no_grad():
+            if c["cache"] == "stock":   # (the stock layers fill the cache; its bits are not what the fixture is about)
+                m.model(inputs_embeds=x, past_key_values=cache, use_cache=True, **kw(S))
+                enable_fused_prefill(m, **c["flags"])
+            else:
+                enable_fused_prefill(m, **c["flags"])
+                dig["prefill"] = _sha(m.model(inputs_embeds=x, past_key_values=cache, use_cache=cache is not None, **kw(S)).last_hidden_state)
+            T = S
+            if c["chunk"]:
+                xc = embeds(c, "x_chunk", c["chunk"]).to(c["dtype"]).to(dev)
+                T += c["chunk"]
+                dig["chunk"] = _sha(m.model(inputs_embeds=xc, past_key_values=cache, use_cache=True, **kw(T)).last_hidden_state)
+            for t in range(c["steps"]):
+                xs = embeds(c, f"x_step{t}", 1).to(c["dtype"]).to(dev)
+                T += 1
+                dig[f"step{t}"] = _sha(m.model(inputs_embeds=xs, past_key_values=cache, use_cache=True, **kw(T)).last_hidden_state)
+            if cache is not None:
+                for i, lay in enumerate(cache.layers):
+                    assert lay.keys.shape[0] == B and cache.get_seq_length(i) == T, (cid, i, T)
+                    dig[f"keys{i}"], dig[f"values{i}"] = _sha(lay.keys), _sha(lay.values)
+    torch.cuda.synchronize()
+    disable_fused_prefill(m)
+    after = _counters()
+    return {"digests": dig, "stats": {k: after[k] - before[k] for k in after if after[k] != before[k]}}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--record", action="store_true", help="run every case on the GPU and write the fixture")
+    ap.add_argument("--commit", default="", help="the commit whose Python is recorded (written into the file)")
+    ap.add_argument("--out", default=str(FIXTURE))
+    a = ap.parse_args()
+    if not a.record:
+        print(f"{len(CASES)} cases; --record writes their digests")
+        return 0
+    sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+    from u2tokenizer_amd import ops
+    ops.device_check()
+    cases = {}
+    for cid in CASES:
+        cases[cid] = run_case(cid)
+        print(cid, cases[cid]["stats"], flush=True)
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text(json.dumps({"recorded_at_commit": a.commit, "cases": cases}, indent=0, sort_keys=True) + "\n")
+    print(f"wrote {len(cases)} cases to {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -16,7 +16,7 @@ import pytest
 import torch
 from torch import nn
 
-from test_decoder_route_host import _model, _route, _stock, recorder  # noqa: F401
+from test_decoder_route_host import _FakeCuda, _model, _route, _stock, recorder  # noqa: F401
 from test_decoder_train_bounds_host import U, _gen, worst
 from test_lora_bounds_host import U16, _chunked_f32, _rn, alpha_of, down_model, rnd16, up_model  # noqa: F401
 from u2tokenizer_amd import _lib, lora, prefill
@@ -363,8 +363,20 @@ def test_switch_defaults_off_and_config_switch():
     assert set(prefill.lora_stats) == {"prefill", "extend", "decode", "adapters"}
     from u2tokenizer_amd.language_model import u2Qwen3Config
     assert not getattr(u2Qwen3Config(), "u2_fused_lora_inference", False)
-    src = inspect.getsource(__import__("u2tokenizer_amd.language_model", fromlist=["x"]))
-    assert 'u2_fused_lora_inference' in src and 'padded["lora"] = True' in src
+    # the config attribute alone reaches the stack as `lora`, and as nothing else
+    from u2tokenizer_amd import language_model as LM
+    for on in (False, True):
+        cfg = LM.u2Qwen3Config(vocab_size=64, hidden_size=64, intermediate_size=128, num_hidden_layers=1, num_attention_heads=4,
+                               num_key_value_heads=2, head_dim=16)
+        cfg.u2_fused_lora_inference = on
+        lm = LM.u2Qwen3ForCausalLM(cfg).to(bf).eval()
+        layer = lm.model.layers[0]
+        p0 = next(layer.parameters())
+        layer.parameters = lambda *a, p0=p0, **k: iter([p0.detach().as_subclass(_FakeCuda)])
+        with torch.no_grad():
+            lm(inputs_embeds=torch.zeros(1, 3, 64, dtype=bf))
+        stack = lm.model._u2_stack
+        assert stack.lora is on and stack.prefill and not (stack.train or stack.train_lora or stack.padded or stack.fp8)
 
 
 # ------------------------------------------------------------------------------------------------------------- the cached state
@@ -383,11 +395,11 @@ def test_lora_state_rebuilds_on_each_listed_change_and_on_nothing_else(recorder)
         return ls, prefill.lora_state_builds[0] - n
 
     ls0, built = state()
-    assert built == 1 and ls0["n"] == 7 and [len(g) for g in ls0["groups"]] == [3, 1, 2, 1]
-    (A16, B16, col0, s), k_seg, v_seg = ls0["groups"][0]
+    assert built == 1 and ls0.n == 7 and [len(g) for g in ls0.groups] == [3, 1, 2, 1]
+    (A16, B16, col0, s), k_seg, v_seg = ls0.groups[0]
     q = layer.self_attn.q_proj
     assert A16.dtype == bf and B16.dtype == bf and A16.shape == (16, 128) and B16.shape == (128, 16) and s == 2.0
-    assert (col0, k_seg[2], v_seg[2]) == (0, 128, 192) and ls0["groups"][2][1][2] == 256                 # gate | up: col0 = I
+    assert (col0, k_seg[2], v_seg[2]) == (0, 128, 192) and ls0.groups[2][1][2] == 256                      # gate | up: col0 = I
     assert torch.equal(A16, q.lora_A["default"].weight.detach().to(bf))                                   # the 16-bit compute copy
     for _ in range(3):                                                                                    # nothing changed: kept
         ls, built = state()
@@ -395,23 +407,23 @@ def test_lora_state_rebuilds_on_each_listed_change_and_on_nothing_else(recorder)
     with torch.no_grad():
         q.lora_B["default"].weight.mul_(2)                                                                # _version
     ls1, built = state()
-    assert built == 1 and torch.equal(ls1["groups"][0][0][1], q.lora_B["default"].weight.detach().to(bf))
+    assert built == 1 and torch.equal(ls1.groups[0][0][1], q.lora_B["default"].weight.detach().to(bf))
     q.lora_A["default"].weight.data = q.lora_A["default"].weight.data.clone()                             # data_ptr()
     assert state()[1] == 1 and state()[1] == 0
     q.scaling["default"] = 0.5                                                                            # a scaling
     ls2, built = state()
-    assert built == 1 and ls2["groups"][0][0][3] == 0.5
+    assert built == 1 and ls2.groups[0][0][3] == 0.5
     for name, table in (("lora_A", q.lora_A), ("lora_B", q.lora_B)):                                      # the active adapter
         table["other"] = nn.Linear(*((128, 16) if name == "lora_A" else (16, 128)), bias=False)
     q.lora_dropout["other"], q.r["other"], q.scaling["other"], q.lora_alpha["other"] = nn.Identity(), 16, 1.0, 16
     assert state()[1] == 0                                                                                # (an inactive one: nothing)
     q.active_adapters = ["other"]
     ls3, built = state()
-    assert built == 1 and ls3["groups"][0][0][3] == 1.0
+    assert built == 1 and ls3.groups[0][0][3] == 1.0
     for flag in ("merged", "disable_adapters"):                                                           # the flags, on and off
         setattr(layer.mlp.down_proj, flag, True)
         ls4, built = state()
-        assert built == 1 and ls4["n"] == 6 and ls4["groups"][3] == ()
+        assert built == 1 and ls4.n == 6 and ls4.groups[3] == ()
         setattr(layer.mlp.down_proj, flag, False)
         assert state()[1] == 1 and state()[1] == 0
     with torch.no_grad():
@@ -422,7 +434,7 @@ def test_lora_state_rebuilds_on_each_listed_change_and_on_nothing_else(recorder)
     l2 = m2.model.layers[0]
     assert _routes(m2, recorder) == ("prefill", "decode")
     ls = prefill._lora_state(l2._u2_prefill, l2._u2_prefill.layout, l2._u2_prefill.layout.projections(l2), bf, dev)
-    assert ls["groups"][1][0][0].data_ptr() == l2.self_attn.o_proj.lora_A["default"].weight.data_ptr()
+    assert ls.groups[1][0][0].data_ptr() == l2.self_attn.o_proj.lora_A["default"].weight.data_ptr()
     # freed with the switch and with the patch
     prefill.enable_fused_prefill(m2)
     assert l2._u2_prefill.lora is None and l2._u2_prefill.ads is None

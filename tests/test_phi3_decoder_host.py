@@ -134,10 +134,11 @@ def test_enable_fused_prefill_patches_every_phi3_layer():
     assert m.model.layers[0].self_attn.head_dim == 96
     assert enable_fused_prefill(m, strict=True) == 3
     for lay in m.model.layers:
-        assert lay._u2_prefill["layout"] is _PackedLayout
-        W, b = _PackedLayout.qkv(lay)
+        assert lay._u2_prefill.layout is _PackedLayout
+        pr = _PackedLayout.projections(lay)
+        _, W, b = _PackedLayout.product(pr, 0)
         assert W is lay.self_attn.qkv_proj.weight and b is None   # used as they are: no repacking
-        assert _PackedLayout.gate_up(lay)[0] is lay.mlp.gate_up_proj.weight
+        assert _PackedLayout.product(pr, 2)[1] is lay.mlp.gate_up_proj.weight
         assert _PackedLayout.ready(lay, lay.self_attn)
     with torch.no_grad():   # on the host the patched layers hand every call to their stock forward
         ids = torch.arange(10)[None] % 128

@@ -110,14 +110,17 @@ def test_the_layout_accessors_name_the_parameters_that_own_the_packed_rows():
     layer = m.model.layers[0]
     lo = prefill._layout_of(layer)
     assert lo is prefill._PackedLayout and not lo.TRAINS and prefill.TRAIN_HEAD_DIMS == (64, 128)
-    assert lo.qkv_linears(layer) == (layer.self_attn.qkv_proj,) and lo.gate_up_linears(layer) == (layer.mlp.gate_up_proj,)
-    assert lo.inter(layer) == 256 and lo.qkv(layer)[0] is layer.self_attn.qkv_proj.weight
+    pr = lo.projections(layer)
+    assert lo.product(pr, 0)[0] == (layer.self_attn.qkv_proj,) and lo.product(pr, 2)[0] == (layer.mlp.gate_up_proj,)
+    assert lo.product(pr, 2)[1].shape[0] // 2 == lo.product(pr, 3)[1].shape[1] == 256     # I, from gate|up and from down
+    assert lo.product(pr, 0)[1] is layer.self_attn.qkv_proj.weight
     q = R._model()
     layer = q.model.layers[0]
     lo = prefill._layout_of(layer)
     att, mlp = layer.self_attn, layer.mlp
-    assert lo is prefill._SplitLayout and lo.inter(layer) == 256
-    assert lo.qkv_linears(layer) == (att.q_proj, att.k_proj, att.v_proj) and lo.gate_up_linears(layer) == (mlp.gate_proj, mlp.up_proj)
+    pr = lo.projections(layer)
+    assert lo is prefill._SplitLayout and lo.product(pr, 2)[1].shape[0] // 2 == lo.product(pr, 3)[1].shape[1] == 256
+    assert lo.product(pr, 0)[0] == (att.q_proj, att.k_proj, att.v_proj) and lo.product(pr, 2)[0] == (mlp.gate_proj, mlp.up_proj)
 
 
 @pytest.mark.parametrize("phi3_on,train_on", [(True, False), (True, True), (False, True), (False, False)])

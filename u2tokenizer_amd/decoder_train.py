@@ -317,36 +317,34 @@ class SwiGLUFn(Function):
 # ------------------------------------------------------------------------------------------------ the layer
 def layer_forward_train(layer, lo, x2, cos, sin, B: int, S: int, kv_len):
     """The layer's forward through the Functions above on its rows x2 (B S, E) -> (B, S, E); `lo` is the layer's layout
-    (prefill.py: its packed q|k|v and gate|up and the projections that own them -- three and two nn.Linear for Llama / Qwen3,
-    Phi-3's single qkv_proj / gate_up_proj, whose Parameter receives the packed dW whole), cos / sin the rotary rows (B S, d),
+    (prefill.py, `product`: the four products' weights and the projections that own them -- three and two nn.Linear behind q|k|v
+    and gate|up for Llama / Qwen3, Phi-3's single qkv_proj / gate_up_proj, whose Parameter receives the packed dW whole), cos /
+    sin the rotary rows (B S, d),
     kv_len the key lengths or None.  Phi-3's stock layer rounds where Llama's does: the activation is up * bf16(silu(gate)) on
     the halves of the gate_up_proj output (gate rows first), its two residual dropouts are inactive on this route (lo.ready)
     and it has no head norm (HeadNormRopeFn's wq = None form)."""
-    att, mlp = layer.self_attn, layer.mlp
+    att = layer.self_attn
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     stats["layers"] += 1   # (counted on entry: a checkpoint recompute stops early, once the tensors it needs are back)
-    n_ad = sum(type(m) is not torch.nn.Linear for m in lo.projections(layer))
+    pr = lo.projections(layer)
+    n_ad = sum(type(m) is not torch.nn.Linear for m in pr)
     if n_ad:
         lora_stats["layers"] += 1
         lora_stats["adapters"] += n_ad
-    Wqkv, bqkv = lo.qkv(layer)
-    Wgu, bgu = lo.gate_up(layer)
+
+    def product(g: int, x, res=None):
+        """product g of the layout (its modules, packed weight and bias: lo.product) on x, then its adapters' branch"""
+        lins, W, b = lo.product(pr, g)
+        return lora_delta(packed_linear(x, lins, W.detach(), None if b is None else b.detach(), res=res), x, lins, B, S)
+
     xn = RMSNormFn.apply(x2, layer.input_layernorm.weight, float(layer.input_layernorm.variance_epsilon))
-    qkv = packed_linear(xn, lo.qkv_linears(layer), Wqkv.detach(), None if bqkv is None else bqkv.detach())
-    qkv = lora_delta(qkv, xn, lo.qkv_linears(layer), B, S)
+    qkv = product(0, xn)
     qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
     qkv = HeadNormRopeFn.apply(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv,
                                d, float(qn.variance_epsilon) if qn is not None else 1e-6)
     ctx = GqaAttentionFn.apply(qkv, kv_len, B, S, Hq, Hkv, d, float(att.scaling))
-    h = packed_linear(ctx, (att.o_proj,), att.o_proj.weight.detach(), None if att.o_proj.bias is None else
-                      att.o_proj.bias.detach(), res=x2)
-    h = lora_delta(h, ctx, (att.o_proj,), B, S)
+    h = product(1, ctx, res=x2)
     hn = RMSNormFn.apply(h, layer.post_attention_layernorm.weight, float(layer.post_attention_layernorm.variance_epsilon))
-    gu = packed_linear(hn, lo.gate_up_linears(layer), Wgu.detach(), None if bgu is None else bgu.detach())
-    gu = lora_delta(gu, hn, lo.gate_up_linears(layer), B, S)
-    act = SwiGLUFn.apply(gu)
-    out = packed_linear(act, (mlp.down_proj,), mlp.down_proj.weight.detach(),
-                        None if mlp.down_proj.bias is None else mlp.down_proj.bias.detach(), res=h)
-    out = lora_delta(out, act, (mlp.down_proj,), B, S)
-    return out.view(B, S, -1)
+    act = SwiGLUFn.apply(product(2, hn))
+    return product(3, act, res=h).view(B, S, -1)

@@ -51,6 +51,21 @@ class u2Phi3Model(u2MetaModel, Phi3Model):
         super(u2Phi3Model, self).__init__(config)
 
 
+_ROUTE_ATTRS = {}
+
+
+def _route_attrs(grad: bool):
+    """The config attributes (with their defaults) that ask for the decoder route of a grad mode -- the training route with grad,
+    the prefill and decode steps without --, from prefill.SWITCHES: the switch itself and those that imply or need it.  Read once."""
+    attrs = _ROUTE_ATTRS.get(grad)
+    if attrs is None:
+        from .prefill import SWITCHES
+        kw = "train" if grad else "prefill"
+        attrs = _ROUTE_ATTRS[grad] = tuple((s.config, s.default) for s in SWITCHES
+                                           if s.config and (s.kw == kw or kw in s.implies + s.needs))
+    return attrs
+
+
 class _u2CausalLMMixin(u2MetaForCausalLM):
     """forward / generate / prepare_inputs_for_generation shared by the Llama, Qwen3 and Phi3 builds."""
 
@@ -59,52 +74,39 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
 
     def _maybe_fuse(self) -> None:
         """Patch the decoder layers for the HIP routes of prefill.py, once per grad mode, when the decoder sits on the GPU in a
-        type that mode's route computes: without grad `config.u2_fused_prefill` (default True) asks for the prefill and decode
-        steps (bf16, or fp16 on the f16 build), with grad `config.u2_fused_decoder_training` (default False)
-        for the training route of decoder_train.py (bf16).  Both switches, `config.u2_fused_padded_batches` (default False:
-        padded batches on the no-grad routes) and `config.u2_fused_continued_prefill` (default False: new positions against a
-        filled cache, prefills past the attention window) and `config.u2_fused_decode_fp8` (default False: the decode step's four
-        products on e4m3 copies of the weights, prefill.py `_w8_state`) and `config.u2_fused_wide_decode` (default False: decode
-        steps of 17 .. 64 sequences on the fused step), are passed on as the config has them, and so is
-        `config.u2_fused_phi3_training` (default False; it implies the training route: head dim 96 and the packed Phi-3 layout
-        on it, `enable_fused_prefill(..., train=True, train_phi3=True)`) and `config.u2_fused_lora_training` (default False; it
-        implies the training route too: LoRA-wrapped projections on it, `enable_fused_prefill(..., train_lora=True)`) and
-        `config.u2_fused_lora_inference` (default False: LoRA-wrapped projections on the prefill, continued prefill and decode steps,
-        `enable_fused_prefill(..., lora=True)`; `u2_fused_lora_training` alone does not turn it on)."""
+        type that mode's route computes: without grad the prefill and decode steps (bf16, or fp16 on the f16
+        build), with grad the training route of decoder_train.py (bf16).  The switches are the config attributes of
+        prefill.SWITCHES (`config.u2_fused_prefill`, default True; every other one default False), passed on as the config has
+        them with what each implies or needs."""
         grad = torch.is_grad_enabled()
-        train_phi3 = bool(getattr(self.config, "u2_fused_phi3_training", False))   # (implies the training route)
-        train_lora = bool(getattr(self.config, "u2_fused_lora_training", False))   # (implies the training route as well)
-        train = bool(getattr(self.config, "u2_fused_decoder_training", False)) or train_phi3 or train_lora
-        prefill = bool(getattr(self.config, "u2_fused_prefill", True))
         checked = self.__dict__.setdefault("_u2_fuse_checked", set())
-        if grad in checked or not (train if grad else prefill):
+        if grad in checked:
+            return
+        # (nothing below is remembered when it says no -- the config and the device may change --, so the no is cheap: the one to
+        #  three config attributes that ask for this mode's route, then the first parameter's device)
+        config = self.config
+        for attr, default in _route_attrs(grad):
+            if getattr(config, attr, default):
+                break
+        else:
             return
         p = next(self.model.layers[0].parameters(), None) if len(self.model.layers) else None
         if p is None or not p.is_cuda:
             return
-        from .prefill import INFER_DTYPES, TRAIN_DTYPES, enable_fused_prefill
-        if p.dtype in (TRAIN_DTYPES if grad else INFER_DTYPES):
-            # (`config.u2_fused_padded_batches`, default False: padded batches on the fused prefill / decode steps)
-            padded = {"padded": True} if bool(getattr(self.config, "u2_fused_padded_batches", False)) else {}
-            if bool(getattr(self.config, "u2_fused_continued_prefill", False)):
-                padded["continued"] = True
-            if bool(getattr(self.config, "u2_fused_decode_fp8", False)):   # (default False: decode steps on e4m3 weight copies)
-                padded["fp8_decode"] = True
-            if bool(getattr(self.config, "u2_fused_wide_decode", False)):   # (default False: decode steps of 17 .. 64 sequences)
-                padded["wide_decode"] = True
-            if train_phi3:   # (default False: head dim 96 and the packed Phi-3 layout on the training route)
-                padded["train_phi3"] = True
-            if train_lora:   # (default False: LoRA-wrapped projections on the training route, decoder_train.LoraDeltaFn)
-                padded["train_lora"] = True
-            if bool(getattr(self.config, "u2_fused_lora_inference", False)):   # (default False: unmerged adapters on the no-grad routes)
-                padded["lora"] = True
-            enable_fused_prefill(self, strict=False, train=train, prefill=prefill, **padded)
+        from . import prefill
+        if p.dtype in (prefill.TRAIN_DTYPES if grad else prefill.INFER_DTYPES):
+            on = {s.kw: bool(getattr(config, s.config, s.default)) for s in prefill.SWITCHES if s.config}
+            for s in prefill.SWITCHES:
+                if on.get(s.kw):
+                    on.update(dict.fromkeys(s.implies + s.needs, True))
+            defaults = {s.kw: s.default for s in prefill.SWITCHES}
+            prefill.enable_fused_prefill(self, strict=False, **{k: v for k, v in on.items() if v != defaults[k]})
             checked.add(grad)
 
     def _loss_head_ok(self, kwargs=None) -> bool:
         """Whether a call with labels takes the loss head of loss_head.py (`config.u2_fused_loss_head`, default False) instead
         of lm_head + ForCausalLMLoss: lm_head exactly nn.Linear, no bias, no hooks (a LoRA-wrapped or probed head keeps the stock
-        path, as prefill._is_stock has it for the layers), bf16 on the GPU in a shape the head computes, the stock causal-LM
+        path, as prefill._admit has it for the layers), bf16 on the GPU in a shape the head computes, the stock causal-LM
         loss, all positions scored (no `logits_to_keep`) and a ModelOutput asked for.  On that route
         `config.u2_fused_loss_head_predictions` (default False) puts the positions' argmax where the logits would be."""
         if not bool(getattr(self.config, "u2_fused_loss_head", False)):
@@ -120,7 +122,7 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
         """lm_head is exactly nn.Linear without bias or hooks, bf16 on the GPU, in a shape the loss head computes: reading its
         `.weight` instead of calling it is then the same computation."""
         from .loss_head import supported
-        from .prefill import _HOOK_TABLES
+        from .lora import _HOOK_TABLES
         head = self.lm_head
         return (type(head) is nn.Linear and head.bias is None and not any(getattr(head, t, None) for t in _HOOK_TABLES)
                 and head.weight.is_cuda and supported(head.in_features, head.out_features, head.weight.dtype))

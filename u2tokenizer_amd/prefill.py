@@ -11,38 +11,34 @@ padding) runs the layer as
     -> out-projection GEMM with the residual in its epilogue -> RMSNorm -> ONE gate|up GEMM with SiLU(gate) * up in its
     epilogue -> down-projection GEMM with the residual in its epilogue
 
-on the library's MFMA GEMMs (include/u2tok.h: u2tok_gemm_bf16), the fused attention kernel of tokattn.hip
-(u2tok_attention_gqa: grouped-query heads, causal mask, scores never in HBM) and the row kernels of decoder.hip, and for a
-DECODE step (one new position per sequence, batch <= 16 -- `wide_decode=True`, opt-in: <= 64 --, a plain HF DynamicCache) as two library calls around the cache update
-(`_decode_step`: weight-streaming few-rows products, attention with the keys split over workgroups).  Everything else --
-training, CPU tensors, sliding-window layers, padded batches, other cache types -- takes the layer's original forward.
-`enable_fused_prefill(model, padded=True)` (opt-in) keeps LEFT- and RIGHT-padded batches on the fused prefill (`pad_rule`: a key
-range per sequence inside the attention kernel, u2tok_attention_gqa_range) and left-padded batches on the fused decode step (the
-batched decode attention of csrc/decode_attn.hip, u2tok_decoder_decode_post with batched = 1) -- what `generate` on a batch of
-prompts of different lengths calls.
-`enable_fused_prefill(model, continued=True)` (opt-in) keeps two more inference calls on the HIP layers, both through one extension
-of the attention kernel (u2tok_attention_gqa_band: K / V read in the cache's own (B, H_kv, capacity, d) layout, the lower edge of
-an attention window per query row): more than one new position against a cache that already holds keys (a second turn, a prompt
-fed in chunks, `generate(..., past_key_values=cache)`, the verification step of assisted decoding; `_extend_kv`) and a prefill
-longer than the window of a sliding-window layer.  Taken: no cache or a plain DynamicCache of DynamicLayer / append-in-place /
-DynamicSlidingWindowLayer layers, no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers
-without a window; stock: a right-padded continuation, holes, window + padding, offloaded / static / quantized caches.
+on the library's MFMA GEMMs (include/u2tok.h: u2tok_gemm_bf16), the fused attention kernel of tokattn.hip (grouped-query heads,
+causal mask, scores never in HBM) and the row kernels of decoder.hip, and for a DECODE step (one new position per sequence, batch
+<= 16, a plain HF DynamicCache) as two library calls around the cache update (`_decode_step`: weight-streaming few-rows products,
+attention with the keys split over workgroups).  Everything else -- training, CPU tensors, padded batches, other cache types --
+takes the layer's original forward, unless one of the opt-in switches widens a route: SWITCHES below lists them, one record
+each (keyword of `enable_fused_prefill`, field of the stack's state, config attribute of a u2 causal LM, what it implies, what it
+does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that table.  What the switches share:
+  * padded: `pad_rule` turns the call's 2-D mask into a key range per sequence; the prefill hands it to the attention kernel, the
+    decode step to the batched decode attention of csrc/decode_attn.hip (u2tok_decoder_decode_post with batched = 1).
+  * continued: both of its calls go through the attention kernel's band form (K / V read in the cache's own (B, H_kv, capacity,
+    d) layout, the lower edge of an attention window per query row).  Taken: no cache or a plain DynamicCache of DynamicLayer /
+    append-in-place / DynamicSlidingWindowLayer layers, no mask or all ones, with `padded` also a LEFT-padded mask as wide as
+    cache + call on layers without a window; stock: a right-padded continuation, holes, window + padding, offloaded / static /
+    quantized caches.
+  * fp8_decode, lora: what they keep per layer beside the weights (e4m3 copies with a scale per row; 16-bit adapter operands)
+    lives in the layer's `_LayerState` with the decode step's descriptors, is rebuilt when a source changed and on nothing
+    else, and goes when the switch goes off.  With `lora` the adapter branch follows each of the four products UNMERGED -- on
+    many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of csrc/lora_rows.hip
+    inside the two library calls --, and a wrapper that is merged or disabled runs as its base layer.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
 Phi-3 layers (`Phi3Attention.qkv_proj`, `Phi3MLP.gate_up_proj`: gate rows first, then up) already hold that packed layout and
 are used as they are (`_PackedLayout`).  Their configs carry `sliding_window` = W (every Phi-3-4k build: 2047; query i sees
 keys i - W + 1 .. i): a prefill of S <= W positions is the plain causal one, a longer prefill takes the stock layers (with
-continued=True: the band inside the attention kernel), and a decode step attends over the last min(T, W) cached positions -- of a plain DynamicCache, the append-in-place layer or the
-DynamicSlidingWindowLayer that `generate` builds for such a config.
+`continued`: the band inside the attention kernel), and a decode step attends over the last min(T, W) cached positions -- of a
+plain DynamicCache, the append-in-place layer or the DynamicSlidingWindowLayer that `generate` builds for such a config.
 
-`enable_fused_prefill(model, train=True)` (opt-in) sends a Llama / Qwen3 layer called with grad enabled through the training route of
-decoder_train.py at head dims 64 / 128; with `train_phi3=True` on top also at head dim 96 and for the packed Phi-3 layout
-(S <= W positions on a layer with a window).
-`enable_fused_prefill(model, lora=True)` (opt-in) keeps a layer whose projections are LoRA-wrapped (lora.py) on the prefill, the
-continued prefill and the decode step with the adapters UNMERGED (`_lora_admit`, `_lora_state`): the adapter branch follows each of the
-four products -- on many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of
-csrc/lora_rows.hip inside the two library calls --, and a wrapper that is merged or disabled runs as its base layer.
 `route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
 step, the prefill or the stock forward.  The patch state is one `_LayerState` per layer and one `_StackState` per decoder stack.
 """
@@ -50,12 +46,13 @@ from __future__ import annotations
 
 import types
 from dataclasses import dataclass, field
+from typing import NamedTuple, Optional
 
 import torch
 from transformers import cache_utils
 
 from . import decoder_train, ops
-from .lora import adapter_of, base_only_of, dropout_inactive
+from .lora import _HOOK_TABLES, adapter_of, base_only_of, dropout_inactive
 
 # the HF cache classes the fused steps work with (None where this transformers lacks one: before 4.56 no per-layer caches)
 _DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
@@ -68,19 +65,89 @@ INFER_DTYPES, INFER_HEAD_DIMS = (torch.bfloat16, torch.float16), (64, 96, 128)
 TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
 TRAIN_PHI3_HEAD_DIMS = (64, 96, 128)
 
+
+class Switch(NamedTuple):
+    """One route switch: the keyword of `enable_fused_prefill`, the field of `_StackState` it sets (None: no state), the config
+    attribute of a u2 causal LM that sets it (None: keyword only), its default, the keywords it implies, the keywords it does
+    nothing without (the config attribute turns those on with it, the keyword does not), the fields of `_LayerState` that are
+    dropped when it goes off, and what it does."""
+    kw: str
+    field: Optional[str]
+    config: Optional[str]
+    default: bool
+    implies: tuple
+    needs: tuple
+    frees: tuple
+    doc: str
+
+
+SWITCHES = (
+    Switch("decode", "decode", None, True, (), (), (), "the fused decode step (off: decode steps take the stock layers)"),
+    Switch("strict", None, None, True, (), (), (),
+           "refuse a decoder layer of another layout, or a Phi-3 layer the kernels do not compute (another activation, partial "
+           "rotary, a head dim outside 64 / 96 / 128); off: such a layer is skipped and stays stock"),
+    Switch("train", "train", "u2_fused_decoder_training", False, (), (), (),
+           "a Llama / Qwen3 layer called with grad enabled takes the training route of decoder_train.py (head dims 64 / 128)"),
+    Switch("prefill", "prefill", "u2_fused_prefill", True, (), (), (),
+           "the fused prefill and decode step (off: the layers are patched for the training route only)"),
+    Switch("padded", "padded", "u2_fused_padded_batches", False, (), (), (),
+           "a LEFT- or RIGHT-padded batch (`pad_rule`) keeps the fused prefill, a left-padded one the fused decode step too -- what "
+           "`generate` on prompts of different lengths calls; off, any mask with a zero sends the call to the stock layers"),
+    Switch("continued", "continued", "u2_fused_continued_prefill", False, (), (), (),
+           "more than one new position against a filled cache (a second turn, a prompt fed in chunks, `generate(..., "
+           "past_key_values=cache)`, the verification step of assisted decoding) and a prefill longer than the window of a "
+           "sliding-window layer stay on the HIP layers (u2tok_attention_gqa_band)"),
+    Switch("fp8_decode", "fp8", "u2_fused_decode_fp8", False, (), (), ("w8",),
+           "a layer whose E, Hq D and I are multiples of 64 runs the decode step's four products on e4m3 copies of its weights with "
+           "one fp32 scale per row: half the weight bytes per step, half the layer's weights again in HBM; exact on the quantised "
+           "weights, the quantiser's cost in accuracy is unmeasured on trained weights; `w8_stats`, `w8_weights(layer)`"),
+    Switch("train_phi3", "train_phi3", "u2_fused_phi3_training", False, (), ("train",), (),
+           "with `train`: the training route also takes head dim 96 (either layout) and the packed Phi-3 layout at head dims 64 / 96 / 128; a layer "
+           "with a window W trains while the call has S <= W positions"),
+    Switch("wide_decode", "wide", "u2_fused_wide_decode", False, (), (), (),
+           "a decode step of 17 .. 64 sequences keeps the fused step (at most 16 query heads per kv head: always the batched decode "
+           "attention; a left-padded one still needs `padded`); the weights are streamed once per step, each block of 16 sequences "
+           "gets the bits of a step of its own (csrc/rows.h); `wide_stats`"),
+    Switch("train_lora", "train_lora", "u2_fused_lora_training", False, ("train",), (), (),
+           "the training route also takes LoRA-wrapped projections (`lora.adapter_of` lists what qualifies) and adds the adapter "
+           "branch on the rank-r kernels of csrc/lora.hip; the no-grad routes stay as they are; `decoder_train.lora_stats`"),
+    Switch("lora", "lora", "u2_fused_lora_inference", False, (), (), ("lora", "ads"),
+           "the prefill, the continued prefill and the decode step take LoRA-wrapped projections with the adapters UNMERGED (a "
+           "dropout that is the identity in the call; a merged or disabled wrapper counts as its base layer); `lora_stats`"),
+)
+
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
 # would pass every parity check); the padded counts are the calls whose mask carried a key range
 stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
 # ... and of the continued prefill (new positions against a filled cache, or a prefill past the window), in a dict of its own:
 # `stats` keeps exactly its four routes
 extend_stats = {"extend": 0, "padded_extend": 0}
-# ... and the decode steps (counted in `stats` as well) that really ran on e4m3 weights (fp8_decode=True, `_w8_state`)
+# ... and the decode steps (counted in `stats` as well) that really ran on e4m3 weights (fp8_decode)
 w8_stats = {"decode": 0, "padded_decode": 0}
-# ... and the decode steps (counted in `stats` as well) of more than 16 sequences (wide_decode=True), per layer call
+# ... and the decode steps (counted in `stats` as well) of more than 16 sequences (wide_decode), per layer call
 wide_stats = {"decode": 0, "padded_decode": 0}
-# ... and the layer calls of the no-grad routes (counted above as well) that computed at least one unmerged adapter (lora=True), per
+# ... and the layer calls of the no-grad routes (counted above as well) that computed at least one unmerged adapter (lora), per
 # route, and the adapters they computed
 lora_stats = {"prefill": 0, "extend": 0, "decode": 0, "adapters": 0}
+
+
+_NO_PAD = ("none", None, None)   # the mask verdict of a call without padding (`pad_rule`, `_mask_hook`): compared by identity first
+
+
+def _count(st, how: str, B: int) -> None:
+    """One routed layer call (how: "prefill", "extend" or "decode") in the five dicts above."""
+    stack = st.stack
+    pad = stack.pad   # (a routed call: the verdict is a tuple)
+    key = how if pad is _NO_PAD or pad[0] == "none" else "padded_" + how
+    (extend_stats if how == "extend" else stats)[key] += 1
+    if how == "decode" and (B > 16 or stack.fp8):
+        if stack.fp8 and st.w8 is not None:
+            w8_stats[key] += 1
+        if B > 16:
+            wide_stats[key] += 1
+    if st.ads is not None:
+        lora_stats[how] += 1
+        lora_stats["adapters"] += sum(a is not None for a in st.ads)
 
 
 def pad_rule(mask):
@@ -90,7 +157,7 @@ def pad_rule(mask):
     of sequence b is visible iff kv_start[b] <= j < kv_len[b] --; None (stock layers) for holes, an empty row, padding on both
     sides or a mask that is not 2-D.  One host synchronisation (four flags in one transfer), none without a mask."""
     if mask is None:
-        return "none", None, None
+        return _NO_PAD
     if not torch.is_tensor(mask) or mask.dim() != 2 or mask.shape[1] == 0:
         return None
     m = mask != 0
@@ -102,7 +169,7 @@ def pad_rule(mask):
     whole = (n > 0) & (last - first + 1 == n)         # one run of ones, no holes
     full, runs, at0, at_end = torch.stack((n.eq(S).all(), whole.all(), first.eq(0).all(), last.eq(S - 1).all())).tolist()
     if full:
-        return "none", None, None
+        return _NO_PAD
     if not runs:
         return None
     if at0:
@@ -151,18 +218,36 @@ def _ensure_gemm_scratch(device) -> None:
         _scratch[key] = buf
 
 
-_HOOK_TABLES = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
-
-
 def _base(lin):
     """The nn.Linear whose weight and bias a projection's product reads: the module, or an adapter wrapper's base layer."""
     return getattr(lin, "base_layer", lin)
 
 
-class _SplitLayout:
+class _Layout:
+    """A decoder layer's projections as the four products read them.  GROUPS: the projections (indices into `projections(layer)`)
+    of q|k|v, o, gate|up and down; everything else about the products follows from it (`product`)."""
+    GROUPS = ()
+
+    @classmethod
+    def product(cls, pr, g: int):
+        """Product g (0: q|k|v, 1: o, 2: gate|up, 3: down) of the projections `pr` -> (its modules, W, b): one module's own
+        weight and bias, several modules' packed ones (`_pack`)."""
+        idx = cls.GROUPS[g]
+        if len(idx) == 1:
+            m = pr[idx[0]]
+            lin = getattr(m, "base_layer", m)   # (`_base`, written out: four calls per layer call on the host-bound steps)
+            return (m,), lin.weight, lin.bias
+        lins = pr[idx[0]:idx[-1] + 1]           # (the projections of one product are neighbours in `projections`)
+        return (lins, *_pack(lins))
+
+    @staticmethod
+    def window(layer):
+        return None
+
+
+class _SplitLayout(_Layout):
     """Llama / Qwen3: separate q / k / v and gate / up projections, packed into one buffer each on first use."""
-    KEY = (0, 3, 4, 6)   # projections whose weights locate the packed buffers: q (q|k|v), o, gate (gate|up), down
-    GROUPS = ((0, 1, 2), (3,), (4, 5), (6,))   # the projections of the four products: q|k|v, o, gate|up, down
+    GROUPS = ((0, 1, 2), (3,), (4, 5), (6,))
     TRAINS = True        # the training route computes this layout
 
     @staticmethod
@@ -171,67 +256,18 @@ class _SplitLayout:
         return (att.q_proj, att.k_proj, att.v_proj, att.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj)
 
     @staticmethod
-    def qkv(layer):
-        att = layer.self_attn
-        return _pack((att.q_proj, att.k_proj, att.v_proj))
-
-    @staticmethod
-    def gate_up(layer):
-        return _pack((layer.mlp.gate_proj, layer.mlp.up_proj))
-
-    @staticmethod
-    def qkv_linears(layer):
-        att = layer.self_attn
-        return (att.q_proj, att.k_proj, att.v_proj)
-
-    @staticmethod
-    def gate_up_linears(layer):
-        return (layer.mlp.gate_proj, layer.mlp.up_proj)
-
-    @staticmethod
-    def inter(layer) -> int:
-        return layer.mlp.gate_proj.weight.shape[0]
-
-    @staticmethod
-    def window(layer):
-        return None
-
-    @staticmethod
     def ready(layer, att) -> bool:
         return getattr(att, "sliding_window", None) is None
 
 
-class _PackedLayout:
+class _PackedLayout(_Layout):
     """Phi-3: one qkv_proj (q, k, v rows) and one gate_up_proj (gate rows, then up rows) -- the packed layout itself."""
-    KEY = (0, 1, 2, 3)
     GROUPS = ((0,), (1,), (2,), (3,))
     TRAINS = False       # ... and this one only with the train_phi3 switch (route)
 
     @staticmethod
     def projections(layer):
         return (layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.mlp.gate_up_proj, layer.mlp.down_proj)
-
-    @staticmethod
-    def qkv(layer):
-        lin = _base(layer.self_attn.qkv_proj)
-        return lin.weight, lin.bias
-
-    @staticmethod
-    def gate_up(layer):
-        lin = _base(layer.mlp.gate_up_proj)
-        return lin.weight, lin.bias
-
-    @staticmethod
-    def qkv_linears(layer):
-        return (layer.self_attn.qkv_proj,)
-
-    @staticmethod
-    def gate_up_linears(layer):
-        return (layer.mlp.gate_up_proj,)
-
-    @staticmethod
-    def inter(layer) -> int:
-        return layer.mlp.gate_up_proj.weight.shape[0] // 2
 
     @staticmethod
     def window(layer):
@@ -275,65 +311,48 @@ def _layout_of(layer):
     return None
 
 
-def _is_stock(layer, projections) -> bool:
-    """The fused forwards read the projections' `.weight` / `.bias` and never CALL the submodules.  That is only the same
-    computation while every projection is exactly torch.nn.Linear and nothing hangs on the modules that are skipped: a
-    peft lora.Linear exposes `.weight` as its BASE weight (the reference trains the decoder with LoRA, train_stage1.py:342-353:
-    an unmerged adapter would be silently ignored), forward hooks (output_attentions recorders, activation probes) would not
-    fire.  Checked on every call: adapters and hooks come and go after enable_fused_prefill.  (`projections`: the layout's
-    projection modules, read once per call -- module attribute reads are what this costs per layer and step.)"""
+_HOOKS_F, _HOOKS_FP, _HOOKS_B, _HOOKS_BP = _HOOK_TABLES
+
+
+def _admit(layer, projections, lora: bool, grad: bool):
+    """Whether the projections are what the call's route computes.  The fused forwards read the projections' `.weight` / `.bias`
+    and never CALL the submodules.  That is only the same computation while every projection is exactly torch.nn.Linear and
+    nothing hangs on the modules that are skipped: a peft lora.Linear exposes `.weight` as its BASE weight (the reference trains
+    the decoder with LoRA, train_stage1.py:342-353: an unmerged adapter would be silently ignored), forward hooks
+    (output_attentions recorders, activation probes) would not fire.  Checked on every call: adapters and hooks come and go after
+    enable_fused_prefill (module attribute reads are what this costs per layer and step).
+    lora (the call's switch: train_lora with grad, lora without) decides what else a projection may be: with grad an adapter the
+    training route computes (lora.adapter_of: the layout of peft's lora.Linear, read attribute by attribute); without grad also a
+    wrapper that computes its base layer alone (lora.base_only_of: merged or disabled, DPO's null-reference pass), and the
+    adapter's dropout must be the identity in this call (peft applies dropout in train mode even under no_grad).
+    -> the lora.Adapter per projection (None for a plain or base-only one; () when there is none at all), or None: the stock
+    forward (hooks, rank outside RANKS, DoRA and the other variants, more than one active adapter, an unreadable attribute,
+    active dropout)."""
+    ads = ()
     for m in projections:
-        if type(m) is not torch.nn.Linear:
-            return False
-    for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
-        for t in _HOOK_TABLES:
-            if getattr(m, t, None):
-                return False
-    return True
-
-
-def _is_stock_or_lora(layer, projections) -> bool:
-    """_is_stock for the training route under the train_lora switch: a projection may also be an adapter the route computes
-    (lora.adapter_of: the layout of peft's lora.Linear, read attribute by attribute; anything it does not understand is refused,
-    hooks on the wrapper, its base layer, A or B included)."""
-    for m in projections:
-        if type(m) is not torch.nn.Linear and adapter_of(m) is None:
-            return False
-    for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
-        for t in _HOOK_TABLES:
-            if getattr(m, t, None):
-                return False
-    return True
-
-
-def _lora_admit(layer, projections):
-    """_is_stock for the no-grad routes under the `lora` switch: per projection None -- exactly nn.Linear, or a wrapper that computes
-    its base layer alone (lora.base_only_of: merged or disabled, DPO's null-reference pass) -- or the lora.Adapter the route computes
-    (lora.adapter_of, and a dropout that is the identity in this call: peft applies dropout in train mode even under no_grad); None
-    instead of the tuple sends the call to the stock forward (rank outside RANKS, DoRA and the other variants, hooks, more than one
-    active adapter, an unreadable attribute, active dropout)."""
-    ads = []
-    for m in projections:
-        a = None
-        if type(m) is not torch.nn.Linear:
-            a = adapter_of(m)
-            if a is None:
-                if base_only_of(m) is None:
-                    return None
-            elif not dropout_inactive(a.dropout):
+        if type(m) is torch.nn.Linear:
+            continue
+        a = adapter_of(m) if lora else None
+        if a is None:
+            if not lora or grad or base_only_of(m) is None:
                 return None
-        ads.append(a)
+            continue
+        if not grad and not dropout_inactive(a.dropout):
+            return None
+        ads = ads or [None] * len(projections)
+        ads[projections.index(m)] = a
     for m in (*projections, layer.self_attn, layer.mlp, layer.input_layernorm, layer.post_attention_layernorm):
-        for t in _HOOK_TABLES:
-            if getattr(m, t, None):
-                return None
-    return tuple(ads)
+        d = m.__dict__   # (nn.Module keeps its hook tables as instance attributes; 44 lookups per layer call, a third of the
+        #                   Python of a decode step: no inner loop)
+        if d.get(_HOOKS_F) or d.get(_HOOKS_FP) or d.get(_HOOKS_B) or d.get(_HOOKS_BP):
+            return None
+    return ads and tuple(ads)
 
 
 @dataclass(slots=True, eq=False)
 class _StackState:
-    """enable_fused_prefill's state on a decoder stack: the route switches, the pre-hook's verdict on the call's 2-D mask,
-    the hook, and the decode steps' scratch ((B, device, stream) -> buffers)."""
+    """enable_fused_prefill's state on a decoder stack: the route switches (SWITCHES), the pre-hook's verdict on the call's 2-D
+    mask, the hook, and the decode steps' scratch ((B, device, stream) -> buffers)."""
     hook: object
     decode: bool = True
     train: bool = False
@@ -345,25 +364,42 @@ class _StackState:
     fp8: bool = False
     wide: bool = False
     lora: bool = False
-    mask_ok: bool = True
-    pad: tuple = None          # padded=True: pad_rule's verdict on the call's mask ((kind, kv_start, kv_len) or None = stock)
-    pad_shape: tuple = None    # ... and that mask's (B, columns)
+    pad: tuple = _NO_PAD       # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
+    pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
     scratch: dict = field(default_factory=dict)
+
+    @property
+    def mask_ok(self) -> bool:
+        """No mask, or all ones."""
+        return self.pad is not None and self.pad[0] == "none"
+
+
+@dataclass(slots=True, eq=False)
+class _LoraOps:
+    """A layer's unmerged adapters as the kernels read them (`_lora_state`): per product (q|k|v, o, gate|up, down) the segments
+    (A16 (r, K), B16 (N, r), col0, scaling) of its wrapped projections, their number, and for the decode step the
+    u2tok_decode_lora built from them with the workspace bytes it needs per batch size."""
+    key: tuple
+    groups: tuple
+    n: int
+    desc: object = None
+    need: dict = field(default_factory=dict)
 
 
 @dataclass(slots=True, eq=False)
 class _LayerState:
-    """A patched layer: its original forward, its stack's state, its layout, the decode step's cached constants."""
+    """A patched layer: its original forward, its stack's state, its layout, and what the decode step keeps between calls: the
+    16-bit descriptor (`dec`), the optional e4m3 pairs (`w8`), the optional adapter operands (`lora`) and the DecodeLayer variants
+    built from them (`variants`: plain, e4m3, each with or without adapters -- `_decode_layer`), dropped together whenever one of
+    the three sources is rebuilt.  The ctypes structs and the references handed to the library live here."""
     orig: object
     stack: _StackState
     layout: type
-    dec: dict = None
-    w8: dict = None            # fp8_decode=True: the e4m3 copies of the four packed weights and their scales (`_w8_state`)
-    ads: tuple = None          # lora=True: the call's adapters per projection (`_lora_admit`, set by route() for the step that follows)
-    lora: dict = None          # ... and their cached 16-bit operands, the decode step's descriptor (`_lora_state`)
-
-    def __getitem__(self, key):   # (read as a mapping too -- layer._u2_prefill["layout"] -- as when this state was a dict)
-        return getattr(self, key)
+    ads: tuple = None          # lora: the call's adapters per projection (`_admit`, set by route() for the step that follows)
+    dec: object = None         # `_Decode16`
+    w8: tuple = None           # fp8_decode: (key, the four (W8, scale) pairs)
+    lora: _LoraOps = None
+    variants: list = field(default_factory=lambda: [None] * 4)
 
 
 def is_patched(layer) -> bool:
@@ -395,15 +431,17 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     layout's projections (read once per call)."""
     st = layer._u2_prefill
     stack, lo, att = st.stack, st.layout, layer.self_attn
+    st.ads = None
     if not (stack.train if grad else stack.prefill):
         return "stock", None
     pe = kwargs.get("position_embeddings")
     # every route: no `past_key_value` (singular: the 4.46 .. 4.5x protocol, never patched), a (B, S >= 1, E) GPU input in the
-    # weights' type (bf16 weights under an fp16 autocast hand fp16 activations on), stock projections without hooks
+    # weights' type (bf16 weights under an fp16 autocast hand fp16 activations on), projections the route computes, no hooks
     if args or "past_key_value" in kwargs or kwargs.get("output_attentions") or not is_cuda or len(shape) != 3 \
-            or shape[1] < 1 or pr[0].weight.dtype != dtype or pe is None or pe[0].shape[-1] != att.head_dim \
-            or not _admit(layer, st, pr, grad) \
-            or not lo.ready(layer, att):
+            or shape[1] < 1 or pr[0].weight.dtype != dtype or pe is None or pe[0].shape[-1] != att.head_dim:
+        return "stock", None
+    ads = _admit(layer, pr, stack.train_lora if grad else stack.lora, grad)
+    if ads is None or not lo.ready(layer, att):
         return "stock", None
     if grad:
         # a layout and a head dim the route computes (train_phi3: the packed Phi-3 layout and head dim 96 too), no KV cache, no
@@ -413,7 +451,7 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
         if not (lo.TRAINS or phi3) or dtype not in TRAIN_DTYPES \
                 or att.head_dim not in (TRAIN_PHI3_HEAD_DIMS if phi3 else TRAIN_HEAD_DIMS) or kwargs.get("past_key_values") \
                 is not None or (att.training and float(getattr(att, "attention_dropout", 0.0) or 0.0) > 0) \
-                or shape[2] % 8 or shape[2] > 4096 or lo.inter(layer) % 8 \
+                or shape[2] % 8 or shape[2] > 4096 or _base(pr[lo.GROUPS[3][0]]).weight.shape[1] % 8 \
                 or layer.input_layernorm.weight.dtype not in TRAIN_DTYPES:
             return "stock", None
         W = lo.window(layer)
@@ -421,16 +459,18 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             return "stock", None
         ok, kv_len = decoder_train.layer_mask_kv_len(kwargs.get("attention_mask"), shape[0], shape[1])
         return ("train", kv_len) if ok else ("stock", None)
+    if ads:
+        st.ads = ads   # (the step that follows computes them; no adapter at all: the base layers alone)
     if dtype not in INFER_DTYPES or att.head_dim not in INFER_HEAD_DIMS:
         return "stock", None
     W = lo.window(layer)
     cache = kwargs.get("past_key_values")
-    kind = None         # a padded call (stack.padded): "left" / "right" when the kernels take its key ranges
-    if not stack.mask_ok:
+    pad = stack.pad
+    ranged = pad is not _NO_PAD and (pad is None or pad[0] != "none")   # a padded call: "left" / "right" when the kernels take its key ranges
+    if ranged:
         # a mask with zeros: stock, unless the padded routes are on, the mask is one run of ones per row as wide as this call's
         # keys (prefill: S columns, decode: cache + 1) and the layer has no attention window
-        pad = stack.pad if stack.padded else None
-        if pad is None or pad[0] == "none" or W is not None or stack.pad_shape[0] != shape[0]:
+        if pad is None or not stack.padded or W is not None or stack.pad_shape[0] != shape[0]:
             return "stock", None
         kind = pad[0]
         keys = shape[1] + (cache.get_seq_length(att.layer_idx) if cache is not None else 0)
@@ -442,7 +482,7 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
         wide = shape[0] > 16   # (17 .. 64 sequences: the few-rows product on up to four blocks of 16 rows, always the batched attention)
         ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode \
             and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
-        if (kind is not None or wide) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
+        if (ranged or wide) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
             ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
     # an empty cache and no more positions than the window: the plain causal prefill
@@ -454,48 +494,20 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     return "stock", None
 
 
-def _admit(layer, st, pr, grad: bool) -> bool:
-    """Whether the projections are what the call's route computes: stock modules without hooks; with grad and train_lora also the
-    adapters of the training route; without grad and with the `lora` switch the adapters `_lora_admit` takes, left in st.ads."""
-    stack = st.stack
-    st.ads = None
-    if grad:
-        return _is_stock_or_lora(layer, pr) if stack.train_lora else _is_stock(layer, pr)
-    if not stack.lora:
-        return _is_stock(layer, pr)
-    ads = _lora_admit(layer, pr)
-    if ads is None:
-        return False
-    if any(a is not None for a in ads):
-        st.ads = ads
-    return True
-
-
-def _pad_range(st):
-    """(kind, kv_start, kv_len) of the call a layer routed to a fused step is part of: the stack's verdict when the mask carried a
-    range (route() has checked that it fits this call), else ("none", None, None)."""
-    stack = st.stack
-    if stack.mask_ok or not stack.padded or stack.pad is None:
-        return "none", None, None
-    return stack.pad
-
-
 def _layer_forward(self, hidden_states, *args, **kwargs):
     st = self._u2_prefill
     x = hidden_states
     pr = st.layout.projections(self)
-    how, arg = route(self, x.shape, x.dtype, x.is_cuda, args, kwargs, torch.is_grad_enabled(), pr)
+    shape = x.shape
+    how, arg = route(self, shape, x.dtype, x.is_cuda, args, kwargs, torch.is_grad_enabled(), pr)
     if how == "decode":
         out = _decode_step(self, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, pr)
         if out is not None:
-            stats["decode" if st.stack.mask_ok else "padded_decode"] += 1
+            _count(st, how, shape[0])
             return out
-    elif how == "prefill":
-        stats["prefill" if st.stack.mask_ok else "padded_prefill"] += 1
-        return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"))
-    elif how == "extend":
-        extend_stats["extend" if st.stack.mask_ok else "padded_extend"] += 1
-        return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, True)
+    elif how == "prefill" or how == "extend":
+        _count(st, how, shape[0])
+        return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, how == "extend")
     elif how == "train":
         return _train_step(self, st.layout, x, kwargs["position_embeddings"], arg)
     return st.orig(hidden_states, *args, **kwargs)
@@ -519,26 +531,78 @@ def _lora_add(y, x2, segs):
         ops.lora_up(u, B16, y[:, col0:col0 + B16.shape[0]], alpha=scale, accumulate=True)
 
 
+class _KVWrite:
+    """Where the new keys / values of a step go and what it attends over, for the prefill, the continued prefill and the decode
+    step.  `lay`: the append-in-place layer of a plain DynamicCache holding this batch, or None.  With it the rotary kernel writes
+    behind the `T0` old positions of the layer's buffers (`lay._kb`, `lay._vb`), the attention reads views of those buffers, and
+    `commit` makes them the layer's.  Without it: dense tensors through the cache's own `update` -- in `views` when the step
+    attends over the cache, else in `commit`.
+    fresh = (H_kv, d, like): the call is the first into this layer; an empty DynamicLayer of a plain DynamicCache is replaced by an
+    append-in-place one with room for the call and as many positions again (`_prefill_append_layer`)."""
+    __slots__ = ("cache", "idx", "n", "window", "lay", "T0")
+
+    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None):
+        self.cache, self.idx, self.n, self.window, self.T0 = cache, idx, n, window, 0
+        lay = None
+        if cache is not None:
+            if fresh is not None:
+                lay = _prefill_append_layer(cache, idx, B, fresh[0], n, fresh[1], fresh[2])
+            else:
+                lay = cache.layers[idx]
+                if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:   # (a reordered or re-batched layer: `_room` re-homes it)
+                    self.T0 = lay._room(n, lay.keys if like is None else like)
+                else:
+                    lay = None
+        self.lay = lay
+
+    def views(self, kc, vc, stride=0):
+        """(K, V, stride of one (batch, kv head) entry -- 0: dense) to attend over; kc / vc: the dense new keys / values for a cache
+        that is not written in place, stride: the buffers' for one that is.  A window W: the last n + W - 1 positions of an
+        in-place layer; of a dense cache the last W for a decode step (a longer call hands the band kernel what `update`
+        returned: its masks are relative to the last key, and a DynamicSlidingWindowLayer returns its kept W - 1 positions and the
+        new ones)."""
+        n, W, lay = self.n, self.window, self.lay
+        if lay is not None:
+            T1 = self.T0 + n
+            lo = 0 if W is None else max(0, T1 - (n + W - 1))
+            return lay._kb[:, :, lo:T1], lay._vb[:, :, lo:T1], stride
+        K, V = self.cache.update(kc, vc, self.idx)   # DynamicLayer: torch.cat -> dense (B, H_kv, T, d)
+        self.cache = None                            # (updated: nothing left for `commit`)
+        if n == 1:
+            K, V = K.contiguous(), V.contiguous()
+            if W is not None and K.shape[2] > W:     # (the last W positions: rows of each (batch, kv head) entry)
+                return K[:, :, -W:], V[:, :, -W:], K.stride(1)
+        elif K.stride() != V.stride() or K.stride(3) != 1 or K.stride(2) != K.shape[3] or K.stride(0) != K.shape[1] * K.stride(1):
+            K, V = K.contiguous(), V.contiguous()    # (not a view the band kernel reads where it lies)
+        return K, V, 0
+
+    def commit(self, kc=None, vc=None) -> None:
+        if self.lay is not None:
+            self.lay._commit(self.T0 + self.n)
+        elif self.cache is not None:
+            self.cache.update(kc, vc, self.idx)
+
+
 def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
-    """The prefill step of a layer.  extend (the "extend" route): the keys come from the cache -- `_extend_kv` --, or, with no
-    position cached yet, the call is longer than `window` and its own keys get the band.  With unmerged adapters admitted for the
-    call (the `lora` switch: st.ads) each of the four products is followed by its adapters' branch (`_lora_add`); the q|k|v branch
-    precedes the rotary embedding, so the cache receives adapted keys and values."""
+    """The prefill step of a layer.  extend (the "extend" route): the S new positions attend over a cache layer that holds T0 > 0
+    -- the band form reads K / V where the cache keeps them (`_KVWrite.views`) --, or, with no position cached yet, the call is
+    longer than `window` and its own keys get the band.  One attention entry: the C side picks the kernel form from which of
+    window, kv_start (the first visible key of each sequence of a left-padded batch) and kv_len the call has; none of them is the
+    plain causal kernel.  With unmerged adapters admitted for the call (the `lora` switch: st.ads) each of the four products is
+    followed by its adapters' branch (`_lora_add`); the q|k|v branch precedes the rotary embedding, so the cache receives adapted
+    keys and values.  The cache is committed once every launch of the layer is enqueued."""
     B, S, E = x.shape
     rows = B * S
     att = self.self_attn
     st = self._u2_prefill
-    ls = _lora_state(st, lo, lo.projections(self), x.dtype, x.device) if st.ads is not None else None
-    g_qkv, g_o, g_gu, g_down = ls["groups"] if ls is not None else ((), (), (), ())
-    if ls is not None:
-        lora_stats["extend" if extend else "prefill"] += 1
-        lora_stats["adapters"] += ls["n"]
+    pr = lo.projections(self)
+    g_qkv, g_o, g_gu, g_down = _lora_state(st, lo, pr, x.dtype, x.device).groups if st.ads is not None else ((), (), (), ())
     cfg = att.config
     Hq, Hkv, d = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
     _ensure_gemm_scratch(x.device)
     with ops.on_device(x):
-        Wqkv, bqkv = lo.qkv(self)
-        Wgu, bgu = lo.gate_up(self)
+        product = lo.product
+        (_, Wqkv, bqkv), (_, Wo, bo), (_, Wgu, bgu), (_, Wdown, bdown) = product(pr, 0), product(pr, 1), product(pr, 2), product(pr, 3)
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, S, d)
         xn = ops.rmsnorm(x2, self.input_layernorm.weight, self.input_layernorm.variance_epsilon)
@@ -546,29 +610,24 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
         _lora_add(qkv, xn, g_qkv)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
         q3 = qkv.view(B, S, -1)
-        kind, kv_start, kv_len = _pad_range(self._u2_prefill)
-        lay = kc = vc = commit = None
-        if extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0:
-            ctx, commit = _extend_kv(att, cache, qkv, qn, kn, cos, sin, B, S, Hq, Hkv, d, window, kv_start)
-        else:
-            # keys / values in the cache's own (B, H_kv, S, d) layout: straight into an append-in-place layer of a plain
-            # DynamicCache (room for the decode steps behind them), else as dense tensors for the cache's own `update`
-            lay = _prefill_append_layer(cache, att.layer_idx, B, Hkv, S, d, x) if cache is not None else None
-            r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
-                                 qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
-                                 kv_out=None if lay is None else (lay._kb, lay._vb))
-            kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
-            k3, v3 = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
-            if extend:   # longer than the window: query i sees its own key and the window - 1 before it
-                ctx = ops.attention_gqa_band(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), window=window, causal=True)
-            elif kind == "none":
-                ctx = ops.attention_gqa(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), causal=True)
-            else:   # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros
-                ctx = ops.attention_gqa_range(q3[..., :Hq * d], k3, v3, Hq, Hkv, float(att.scaling), kv_start=kv_start,
-                                              kv_len=kv_len, causal=True)
-        o_proj, down_proj = _base(att.o_proj), _base(self.mlp.down_proj)
+        _, kv_start, kv_len = st.stack.pad
+        filled = extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0
+        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x))
+        lay = kv.lay
+        r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
+                             qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
+                             kv_out=None if lay is None else (lay._kb, lay._vb), kv_pos=kv.T0)
+        kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
+        if filled:
+            K, V, _ = kv.views(kc, vc)
+        else:   # its own keys / values: columns of the q|k|v rows
+            K, V = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
+        # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros.  extend: query i sees
+        # its own key and the window - 1 before it
+        ctx = ops.attention_gqa_band(q3[..., :Hq * d], K, V, Hq, Hkv, float(att.scaling), window=window if extend else None,
+                                     kv_start=kv_start, kv_len=kv_len, causal=True)
         ctx2 = ctx.view(rows, Hq * d)
-        h = ops.gemm(ctx2, o_proj.weight, bias=o_proj.bias, residual=x2)
+        h = ops.gemm(ctx2, Wo, bias=bo, residual=x2)
         _lora_add(h, ctx2, g_o)   # (after the residual epilogue: the same terms)
         hn = ops.rmsnorm(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon)
         if not g_gu and bgu is None and ops.gemm_swiglu_supported(rows, E, Wgu.shape[0] // 2):
@@ -577,44 +636,10 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
             gu = ops.gemm(hn, Wgu, bias=bgu)
             _lora_add(gu, hn, g_gu)
             act = ops.swiglu(gu)
-        out = ops.gemm(act, down_proj.weight, bias=down_proj.bias, residual=h)
+        out = ops.gemm(act, Wdown, bias=bdown, residual=h)
         _lora_add(out, act, g_down)
-        if commit is not None:
-            commit()
-        elif lay is not None:
-            lay._commit(S)
-        elif cache is not None:
-            cache.update(kc, vc, att.layer_idx)
+        kv.commit(kc, vc)
     return out.view(B, S, E)
-
-
-def _extend_kv(att, cache, qkv, qn, kn, cos, sin, B, S, Hq, Hkv, d, window, kv_start):
-    """Rotary embedding and attention of S new positions against a cache layer that holds T0 > 0: -> (ctx, commit).  An
-    append-in-place layer: the new keys / values land behind the old ones in its buffers and the attention reads the views
-    [:, :, :T0 + S] (a window layer: the last min(T0 + S, S + W - 1) positions) where they lie; `commit` (called once every
-    launch of the layer is enqueued, as the prefill does) makes them the layer's.  Every other layer `route` takes: dense new
-    keys / values through the cache's own `update`, attention over what it returns -- a DynamicSlidingWindowLayer its kept
-    W - 1 positions and the new S; the kernel's masks are relative to the last key, so that is the operand as it is.
-    kv_start: the first visible key of each sequence of a left-padded batch (layers without a window only), or None."""
-    lay = cache.layers[att.layer_idx]
-    eps = qn.variance_epsilon if qn is not None else 1e-6
-    wq, wk = None if qn is None else qn.weight, None if kn is None else kn.weight
-    q3 = qkv.view(B, S, -1)[..., :Hq * d]
-    if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:
-        T0 = lay._room(S, lay.keys)
-        ops.qk_norm_rope(qkv, wq, wk, cos, sin, Hq, Hkv, d, eps, kv_cache_seq=S, kv_out=(lay._kb, lay._vb), kv_pos=T0)
-        T1 = T0 + S
-        lo_ = 0 if window is None else max(0, T1 - (S + window - 1))
-        K, V = lay._kb[:, :, lo_:T1], lay._vb[:, :, lo_:T1]
-        commit = lambda: lay._commit(T1)
-    else:
-        _, kc, vc = ops.qk_norm_rope(qkv, wq, wk, cos, sin, Hq, Hkv, d, eps, kv_cache_seq=S)
-        K, V = cache.update(kc, vc, att.layer_idx)
-        if K.stride() != V.stride() or K.stride(3) != 1 or K.stride(2) != d or K.stride(0) != Hkv * K.stride(1):
-            K, V = K.contiguous(), V.contiguous()
-        commit = lambda: None
-    ctx = ops.attention_gqa_band(q3, K, V, Hq, Hkv, float(att.scaling), window=window, kv_start=kv_start, causal=True)
-    return ctx, commit
 
 
 _APPEND_LAYER = None
@@ -698,36 +723,49 @@ def _extend_layer_ok(cache, layer_idx: int, sliding: bool) -> bool:
     return type(layers[layer_idx]) in (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
 
 
+@dataclass(slots=True, eq=False)
+class _Decode16:
+    """Per-layer constants of the decode step: the config struct, the 16-bit layer descriptor, the packed operands it points at."""
+    key: tuple
+    ok: bool
+    cfg: object
+    cfg_ref: object
+    layer: object
+    keep: tuple
+    nq: int
+    Hkv: int
+    hd: int
+
+
 def _decode_state(self, B: int, device, pr):
     """Per-layer constants of the decode step (weight pointers of the packed projections, the config struct), rebuilt when a
-    weight moved; per-model scratch (workspace, q|k|v row, new cache entries) shared by all layers."""
+    weight moved or the batch size changed; per-model scratch (workspace, q|k|v row, new cache entries) shared by all layers."""
     import ctypes as C
     from . import _lib
     st = self._u2_prefill
     lo = st.layout
-    att, mlp = self.self_attn, self.mlp
-    key = tuple(pr[i].weight.data_ptr() for i in lo.KEY) + (B,)
+    att = self.self_attn
+    g = lo.GROUPS   # (the first projection of each product locates its buffer)
+    key = (pr[g[0][0]].weight.data_ptr(), pr[g[1][0]].weight.data_ptr(), pr[g[2][0]].weight.data_ptr(), pr[g[3][0]].weight.data_ptr(), B)
     d = st.dec
-    if d is None or d["key"] != key:
+    if d is None or d.key != key:
         cfg = att.config
         Hq, Hkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, att.head_dim
-        Wqkv, bqkv = lo.qkv(self)
-        Wgu, bgu = lo.gate_up(self)
+        product = lo.product
+        (_, Wqkv, bqkv), (_, Wo, bo), (_, Wgu, bgu), (_, Wdown, bdown) = product(pr, 0), product(pr, 1), product(pr, 2), product(pr, 3)
         qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
         E, inter = Wqkv.shape[1], Wgu.shape[0] // 2
         c = _lib.DecodeConfig(B=B, E=E, Hq=Hq, Hkv=Hkv, D=hd, I=inter, eps=float(self.input_layernorm.variance_epsilon),
                               qk_eps=float(qn.variance_epsilon) if qn is not None else 1e-6, scale=float(att.scaling))
-        o_proj, down_proj = _base(att.o_proj), _base(mlp.down_proj)
-        ok = (E % 32 == 0 and inter % 32 == 0 and o_proj.weight.is_contiguous() and down_proj.weight.is_contiguous()
+        ok = (E % 32 == 0 and inter % 32 == 0 and Wo.is_contiguous() and Wdown.is_contiguous()
               and self.post_attention_layernorm.variance_epsilon == self.input_layernorm.variance_epsilon)
         p = ops._ptr
         lay = _lib.DecodeLayer(w_in_norm=p(self.input_layernorm.weight), Wqkv=p(Wqkv), bqkv=p(bqkv),
                                wq_norm=p(None if qn is None else qn.weight), wk_norm=p(None if kn is None else kn.weight),
-                               Wo=p(o_proj.weight), bo=p(o_proj.bias), w_post_norm=p(self.post_attention_layernorm.weight),
-                               Wgu=p(Wgu), bgu=p(bgu), Wdown=p(down_proj.weight), bdown=p(down_proj.bias))
-        d = {"key": key, "ok": ok, "cfg": c, "cfg_ref": C.byref(c), "layer": lay, "layer_ref": C.byref(lay),
-             "keep": (Wqkv, bqkv, Wgu, bgu), "nq": (Hq + 2 * Hkv) * hd, "Hkv": Hkv, "hd": hd, "E": E}
-        st.dec = d
+                               Wo=p(Wo), bo=p(bo), w_post_norm=p(self.post_attention_layernorm.weight),
+                               Wgu=p(Wgu), bgu=p(bgu), Wdown=p(Wdown), bdown=p(bdown))
+        d = st.dec = _Decode16(key, ok, c, C.byref(c), lay, (Wqkv, bqkv, Wgu, bgu), (Hq + 2 * Hkv) * hd, Hkv, hd)
+        st.variants = [None] * 4
     # (per model, batch size AND stream: two generate() calls in flight on different streams must not share the step's scratch)
     stream = torch.cuda.current_stream(device).cuda_stream
     pool = st.stack.scratch
@@ -739,38 +777,30 @@ def _decode_state(self, B: int, device, pr):
         if len(pool) >= 8:
             pool.clear()
         sc = {"B": B, "device": device, "ws": None, "T": 0,
-              "qkv": torch.empty((B, d["nq"]), dtype=edt, device=device),
-              "kc": torch.empty((B, d["Hkv"], 1, d["hd"]), dtype=edt, device=device),
-              "vc": torch.empty((B, d["Hkv"], 1, d["hd"]), dtype=edt, device=device)}
+              "qkv": torch.empty((B, d.nq), dtype=edt, device=device),
+              "kc": torch.empty((B, d.Hkv, 1, d.hd), dtype=edt, device=device),
+              "vc": torch.empty((B, d.Hkv, 1, d.hd), dtype=edt, device=device)}
         pool[(B, device, stream)] = sc
     return d, sc
 
 
-def _w8_state(self, d, pr):
-    """The e4m3 copies of a layer's four packed decode weights (q|k|v, o, gate|up, down: ops.quantize_rows_fp8, a scale per
-    row) with the layer's descriptor on them (`layer` / `layer_ref`: the 16-bit step's with codes and scales in place of the
-    four weights), or None for a layer they do not take (E, Hq D or I not a multiple of 64: the layer keeps the 16-bit step).  Built at the first qualifying step, kept in the layer's patch state -- half the layer's
-    weights again in HBM --, rebuilt when a source weight's data_ptr() or _version changed (an optimiser step, load_state_dict,
-    weight.mul_), freed with the patch state by disable_fused_prefill.  Parameters, state dict,
-    prefill and training never see the copies; biases stay in the element type."""
-    st = self._u2_prefill
-    c = d["cfg"]
+def _w8_state(st, d, pr) -> bool:
+    """fp8_decode: the e4m3 copies of a layer's four packed decode weights (q|k|v, o, gate|up, down: ops.quantize_rows_fp8, a
+    scale per row) in st.w8; False for a layer they do not take (E, Hq D or I not a multiple of 64: the layer keeps the 16-bit
+    step).  Built at the first qualifying step -- half the layer's weights again in HBM --, rebuilt when a source weight's
+    data_ptr() or _version changed (an optimiser step, load_state_dict, weight.mul_), freed with the patch state by
+    disable_fused_prefill and when the switch goes off.  Parameters, state dict, prefill and training never see the copies;
+    biases stay in the element type."""
+    c = d.cfg
     if c.E % 64 or (c.Hq * c.D) % 64 or c.I % 64:
-        return None
+        return False
     key = tuple((m.weight.data_ptr(), m.weight._version) for m in pr)
-    w8 = st.w8
-    if w8 is None or w8["key"] != key:
-        Wqkv, _, Wgu, _ = d["keep"]
-        pairs = tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, _base(self.self_attn.o_proj).weight, Wgu, _base(self.mlp.down_proj).weight))
-        w8 = st.w8 = {"d": None, "key": key, "pairs": pairs}
-    if w8["d"] is not d:   # (the decode constants were rebuilt -- another batch size, a moved weight: their pointers anew)
-        import ctypes as C
-        from . import _lib
-        lay = _lib.DecodeLayer.from_buffer_copy(d["layer"])   # norms and biases as the 16-bit step has them
-        (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
-            (w.data_ptr(), sc.data_ptr()) for w, sc in w8["pairs"])
-        w8.update(d=d, layer=lay, layer_ref=C.byref(lay))
-    return w8
+    if st.w8 is None or st.w8[0] != key:
+        Wqkv, _, Wgu, _ = d.keep
+        lo = st.layout
+        st.w8 = (key, tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1])))
+        st.variants = [None] * 4
+    return True
 
 
 def _op16(w, dtype, device):
@@ -782,18 +812,16 @@ def _op16(w, dtype, device):
     return w.to(device=device, dtype=dtype).contiguous()
 
 
-def _lora_state(st, lo, pr, dtype, device):
-    """The call's unmerged adapters (st.ads: `_lora_admit`) as the kernels read them, kept in the layer's patch state after the pattern
-    of `_w8_state`: per product (q|k|v, o, gate|up, down) the segments (A16 (r, K), B16 (N, r), col0, scaling) of its wrapped
-    projections -- the 16-bit compute copies of fp32 adapters among them --, and for the decode step the descriptor built from them
-    (`_lora_decode`).  Rebuilt when an adapter weight's data_ptr() or _version, a scaling, the active adapter (its A / B modules) or a
-    `merged` / `disable_adapters` flag (an entry of st.ads turning None) changed, and on nothing else: no step converts anything.
-    Freed with the patch state by disable_fused_prefill, and when the switch goes off."""
+def _lora_state(st, lo, pr, dtype, device) -> _LoraOps:
+    """The call's unmerged adapters (st.ads: `_admit`) as the kernels read them, in st.lora -- the 16-bit compute copies of fp32
+    adapters among them.  Rebuilt when an adapter weight's data_ptr() or _version, a scaling, the active adapter (its A / B modules)
+    or a `merged` / `disable_adapters` flag (an entry of st.ads turning None) changed, and on nothing else: no step converts
+    anything.  Freed with the patch state by disable_fused_prefill, and when the switch goes off."""
     ads = st.ads
     key = (dtype, device) + tuple(None if a is None else (id(a.A), a.A.weight.data_ptr(), a.A.weight._version, id(a.B),
                                                           a.B.weight.data_ptr(), a.B.weight._version, a.scaling, a.r) for a in ads)
     ls = st.lora
-    if ls is None or ls["key"] != key:
+    if ls is None or ls.key != key:
         groups = []
         for idx in lo.GROUPS:
             col0, segs = 0, []
@@ -803,7 +831,8 @@ def _lora_state(st, lo, pr, dtype, device):
                     segs.append((_op16(a.A.weight, dtype, device), _op16(a.B.weight, dtype, device), col0, a.scaling))
                 col0 += _base(pr[i]).out_features
             groups.append(tuple(segs))
-        ls = st.lora = {"key": key, "groups": tuple(groups), "n": sum(len(g) for g in groups), "desc": None, "need": {}, "lay": None}
+        ls = st.lora = _LoraOps(key, tuple(groups), sum(len(g) for g in groups))
+        st.variants = [None] * 4
         lora_state_builds[0] += 1
     return ls
 
@@ -812,40 +841,53 @@ lora_state_builds = [0]   # how often `_lora_state` built its operands (tests: o
 _LORA_PRODUCTS = ("qkv", "o", "gu", "down")
 
 
-def _lora_decode(ls, src, B: int, sc, h):
-    """The decode step's layer descriptor with the adapters on: a copy of `src["layer"]` (the 16-bit step's or the e4m3 one's) whose
-    `lora` points at the u2tok_decode_lora of the layer's segments; its scratch (u, then the largest group workspace for B rows) is
-    the calling stream's, shared by all layers like the step's other scratch."""
+def _lora_scratch(ls, B: int, sc, h) -> None:
+    """Point the adapters' u2tok_decode_lora (built here on first use) at the calling stream's scratch for B rows: u, then the
+    largest group workspace; shared by all layers like the step's other scratch."""
     import ctypes as C
     from . import _lib
-    desc = ls["desc"]
+    desc = ls.desc
     if desc is None:
-        desc = ls["desc"] = _lib.DecodeLora()
-        for name, segs in zip(_LORA_PRODUCTS, ls["groups"]):
+        desc = ls.desc = _lib.DecodeLora()
+        for name, segs in zip(_LORA_PRODUCTS, ls.groups):
             for e, (A16, B16, col0, scale) in zip(getattr(desc, name), segs):
                 e.A, e.B, e.r, e.col0, e.N, e.scale = A16.data_ptr(), B16.data_ptr(), A16.shape[0], col0, B16.shape[0], scale
             setattr(desc, "n_" + name, len(segs))
-    need = ls["need"].get(B)
+    need = ls.need.get(B)
     if need is None:
-        need = ls["need"][B] = _lib.DECODE_LORA_U_BYTES + max(
+        need = ls.need[B] = _lib.DECODE_LORA_U_BYTES + max(
             h.u2tok_lora_rows_workspace_bytes(B, segs[0][0].shape[1], C.addressof(getattr(desc, name)), len(segs))
-            for name, segs in zip(_LORA_PRODUCTS, ls["groups"]) if segs)
+            for name, segs in zip(_LORA_PRODUCTS, ls.groups) if segs)
     buf = sc.get("lora")
     if buf is None or buf.numel() < need:
         buf = sc["lora"] = torch.empty(need, dtype=torch.uint8, device=sc["qkv"].device)
     desc.scratch, desc.scratch_bytes = buf.data_ptr(), buf.numel()
-    if ls["lay"] is None or ls["lay"][0] is not src["layer"]:
-        lay = _lib.DecodeLayer.from_buffer_copy(src["layer"])
-        lay.lora = C.addressof(desc)
-        ls["lay"] = (src["layer"], lay, C.byref(lay))
-    return ls["lay"][2]
+
+
+def _decode_layer(st, fp8: bool, lora: bool):
+    """The reference to the step's u2tok_decode_layer: the 16-bit descriptor (st.dec) with, for fp8, codes and scales in place of the
+    four weights (norms and biases as the 16-bit step has them) and, for lora, the adapters' u2tok_decode_lora.  One variant per
+    combination, built on first use from the sources as they are now; a rebuilt source drops all four."""
+    i = fp8 + 2 * lora
+    v = st.variants[i]
+    if v is None:
+        import ctypes as C
+        from . import _lib
+        lay = _lib.DecodeLayer.from_buffer_copy(st.dec.layer)
+        if fp8:
+            (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
+                (w.data_ptr(), s.data_ptr()) for w, s in st.w8[1])
+        if lora:
+            lay.lora = C.addressof(st.lora.desc)
+        v = st.variants[i] = (lay, C.byref(lay))
+    return v[1]
 
 
 def w8_weights(layer):
     """The four (W8, scale) pairs -- packed q|k|v, o, packed gate|up, down -- a patched layer's e4m3 decode step reads, or None
     (not patched, fp8_decode off, no qualifying step yet, a layer that keeps the 16-bit step)."""
     st = layer.__dict__.get("_u2_prefill")
-    return None if st is None or st.w8 is None else st.w8["pairs"]
+    return None if st is None or st.w8 is None else st.w8[1]
 
 
 def _decode_step(self, x, pe, cache, window, pr):
@@ -859,63 +901,51 @@ def _decode_step(self, x, pe, cache, window, pr):
     buffers, the same kernels.
     B > 16 (the route's wide_decode switch): the same two calls; the library runs the four products on its 17 .. 64-row form of
     the few-rows kernel (csrc/gemm_rows.hip: the weights are still read once per step, and each block of 16 sequences gets the
-    bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch."""
+    bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch.
+    fp8_decode / lora: the same two calls on another variant of the layer descriptor (`_decode_layer`); the adapter groups ride in
+    the calls."""
     from . import _lib
     att = self.self_attn
     B, _, E = x.shape
     d, sc = _decode_state(self, B, x.device, pr)
-    if not d["ok"]:
+    if not d.ok:
         return None                                   # (the caller takes the stock layer)
-    hd = d["hd"]
-    stack = self._u2_prefill.stack
-    w8 = _w8_state(self, d, pr) if stack.fp8 else None   # fp8_decode=True: the step's four products on e4m3 weights
     st = self._u2_prefill
-    ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None   # lora=True: the unmerged adapters
+    fp8 = st.stack.fp8 and _w8_state(st, d, pr)   # (a bool either way: the index of the descriptor variant below)
+    ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
-        cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
+        cos, sin = _rotary_rows(pe, B, 1, d.hd, x.dtype)
         T1 = cache.get_seq_length(att.layer_idx) + 1
         if sc["ws"] is None or sc["T"] < T1:
             Tcap = max(2048, 2 * T1)                      # (grows geometrically: the workspace depends on T through the key splits)
-            d["cfg"].B = B
-            sc["ws"] = torch.empty(h.u2tok_decoder_decode_workspace_bytes(d["cfg_ref"], Tcap), dtype=torch.uint8, device=x.device)
+            d.cfg.B = B
+            sc["ws"] = torch.empty(h.u2tok_decoder_decode_workspace_bytes(d.cfg_ref, Tcap), dtype=torch.uint8, device=x.device)
             sc["T"] = Tcap
         ws, nws = sc["ws"].data_ptr(), sc["ws"].numel()
-        lay = cache.layers[att.layer_idx]
         out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
-        inplace = type(lay) is _APPEND_LAYER and lay._kb is not None and lay._kb.shape[0] == B
-        if inplace:   # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers
-            T0 = lay._room(1, sc["kc"])
-            kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
-        else:         # into the step's scratch rows, for the cache's own `update`
-            T0, kd, vd, kvs = 0, sc["kc"], sc["vc"], 0
-        src = d if w8 is None else w8
-        layer_ref = src["layer_ref"] if ls is None else _lora_decode(ls, src, B, sc, h)   # (the adapter groups ride in the two calls)
-        _lib.check(h.u2tok_decoder_decode_pre(d["cfg_ref"], layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
-                                              int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
-                                              vd.data_ptr(), kvs, T0, ws, nws, stream), "u2tok_decoder_decode_pre")
-        if inplace:
-            lay._commit(T0 + 1)
-            K, V = kd[:, :, :T0 + 1], vd[:, :, :T0 + 1]
-            if window is not None:
-                K, V = K[:, :, -window:], V[:, :, -window:]
+        # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers; else into the
+        # step's scratch rows, for the cache's own `update`
+        kv = _KVWrite(cache, att.layer_idx, B, 1, window, like=sc["kc"])
+        lay = kv.lay
+        if lay is None:
+            kd, vd, kvs = sc["kc"], sc["vc"], 0
         else:
-            K, V = cache.update(kd, vd, att.layer_idx)   # DynamicLayer: torch.cat -> dense (B, H_kv, T, d)
-            K, V = K.contiguous(), V.contiguous()
-            if window is not None and K.shape[2] > window:    # (the last W positions: rows of each (batch, kv head) entry)
-                K, V, kvs = K[:, :, -window:], V[:, :, -window:], K.stride(1)
-        kind, kv_start, _ = _pad_range(self._u2_prefill)
-        left = kind == "left"   # a left-padded batch: the batched decode attention with each sequence's first visible position
-        _lib.check(h.u2tok_decoder_decode_post(d["cfg_ref"], layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
+            kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
+        if ls is not None:
+            _lora_scratch(ls, B, sc, h)
+        v = st.variants[fp8 + 2 * (ls is not None)]
+        layer_ref = v[1] if v is not None else _decode_layer(st, fp8, ls is not None)
+        _lib.check(h.u2tok_decoder_decode_pre(d.cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                                              int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
+                                              vd.data_ptr(), kvs, kv.T0, ws, nws, stream), "u2tok_decoder_decode_pre")
+        K, V, kvs = kv.views(kd, vd, kvs)
+        kv.commit()
+        _, kv_start, _ = st.stack.pad
+        left = kv_start is not None   # a left-padded batch: the batched decode attention with each sequence's first visible position
+        _lib.check(h.u2tok_decoder_decode_post(d.cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
                                                K.shape[2], kvs, int(left or B > 16), kv_start.data_ptr() if left else None,
                                                out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
-    if w8 is not None:
-        w8_stats["decode" if stack.mask_ok else "padded_decode"] += 1
-    if B > 16:
-        wide_stats["decode" if stack.mask_ok else "padded_decode"] += 1
-    if ls is not None:
-        lora_stats["decode"] += 1
-        lora_stats["adapters"] += ls["n"]
     return out
 
 
@@ -943,17 +973,17 @@ def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: in
 
 
 def _mask_hook(module, args, kwargs):
-    """Forward pre-hook of the decoder stack: the fused layers assume no padding (the path's prompts are left-aligned and the
-    reference evaluates at batch 1, eval/mrg.py:74); a 2-D mask with zeros sends the whole call to the stock layers."""
+    """Forward pre-hook of the decoder stack: the verdict on the call's 2-D mask for route().  The fused layers assume no padding
+    (the path's prompts are left-aligned and the reference evaluates at batch 1, eval/mrg.py:74): a mask with zeros sends the
+    whole call to the stock layers, unless `padded` is on and `pad_rule` finds a key range per sequence.  One synchronisation
+    either way: off, the single `.all()`."""
     m = kwargs.get("attention_mask")
     stack = module._u2_stack
-    if stack.padded:   # pad_rule's verdict for route(): one synchronisation, as the `.all()` below is
+    if stack.padded:
         pad = pad_rule(m)
-        stack.pad, stack.pad_shape = pad, (tuple(m.shape) if pad is not None and m is not None else None)
-        stack.mask_ok = pad is not None and pad[0] == "none"
-        return None
-    ok = m is None or (torch.is_tensor(m) and m.dim() == 2 and bool(m.to(torch.bool).all()))
-    stack.mask_ok = ok
+    else:
+        pad = _NO_PAD if m is None or (torch.is_tensor(m) and m.dim() == 2 and bool(m.to(torch.bool).all())) else None
+    stack.pad, stack.pad_shape = pad, (tuple(m.shape) if pad is not None and m is not None else None)
     return None
 
 
@@ -992,55 +1022,12 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
-    u2Phi3ForCausalLM included) for the fused prefill and (decode=True) the fused decode step.  Idempotent; returns the number
-    of layers patched.  strict=False: a decoder layer of another layout -- or a Phi-3 layer the kernels do not compute (another
-    activation, partial rotary, a head dim outside 64 / 96 / 128) -- is skipped instead of refused.
-    train=True (opt-in): a patched Llama / Qwen3 layer called with grad enabled takes the training route of decoder_train.py
-    (forward and backward on the library's kernels) when its conditions hold.  prefill=False: no fused prefill / decode (the
-    layers are patched for the training route only).  padded=True (opt-in): a batch whose 2-D attention mask is left- or
-    right-padded (`pad_rule`) keeps the fused prefill, a left-padded one the fused decode step too (`generate` on a batch of
-    prompts of different lengths); off, any mask with a zero sends the call to the stock layers.  continued=True (opt-in): more
-    than one new position against a cache that already holds positions (the second turn of a conversation, a prompt fed in
-    chunks, `generate(..., past_key_values=cache)`, the verification step of assisted decoding) and a prefill longer than the
-    window of a sliding-window layer stay on the HIP layers (`_extend_kv`, u2tok_attention_gqa_band) -- for no cache or a plain
-    DynamicCache of DynamicLayer / append-in-place / DynamicSlidingWindowLayer layers, head dims 64 / 96 / 128, any batch size,
-    no mask or all ones, with padded=True also a LEFT-padded mask as wide as cache + call on layers without a window; a
-    right-padded continuation, holes, window + padding and every other cache take the stock layers.
-    fp8_decode=True (opt-in): a layer whose decode step qualifies today and whose E, Hq D and I are multiples of 64 runs the
-    step's four weight-streaming products on e4m3 copies of its weights with one fp32 scale per row (`_w8_state`, the scales
-    of its u2tok_decode_layer set: half the weight bytes per step, half the layer weights again in HBM; `w8_stats` counts these
-    steps, `w8_weights(layer)` shows the copies); the products are exact on the quantised weights, the quantiser is what costs
-    accuracy -- unmeasured on trained weights.  Every other layer and every other route read the original weights.
-    train_phi3=True (opt-in, with train=True; nothing without it): the training route also takes head dim 96 (either layout;
-    the flash backward's <96> kernels, u2tok_attention_gqa_bwd_d96) and the packed Phi-3 layout at head dims 64 / 96 / 128
-    (qkv_proj / gate_up_proj as they are: one Parameter, one packed dW each) -- Phi-3-mini trains on the HIP layers.  The other
-    conditions of the route hold as they are; a layer with an attention window W trains while the call has S <= W positions,
-    a longer call takes the stock layers.
-    wide_decode=True (opt-in): a decode step of 17 .. 64 sequences (`generate` over a dataset, DPO's generate_during_eval) keeps
-    the fused step under the conditions of today's -- plus at most 16 query heads per kv head, because such a step always takes
-    the batched decode attention; a left-padded one still needs padded=True, a right-padded one stays stock -- instead of the
-    stock layers: the weights are streamed once per step however many sequences share it, each block of 16 sequences computes
-    the bits it would in a step of its own (csrc/rows.h), and it composes with fp8_decode, Phi-3 layers and the
-    append-in-place cache.  `wide_stats` counts these steps per layer call.  Off, batch 17 takes the stock layers as before.
-    train_lora=True (opt-in; it implies train=True): the training route also takes a layer whose projections are LoRA-wrapped --
-    u2tokenizer_amd.lora.LoRALinear or a module of the same layout (peft's lora.Linear, duck-typed: `lora.adapter_of` lists what
-    qualifies: one active unmerged adapter, r in {16, 32, 64}, bias-free nn.Linear A / B in bf16 or fp32, no DoRA or other variant,
-    no hooks) -- and adds the adapter branch on the rank-r kernels of csrc/lora.hip (decoder_train.LoraDeltaFn); the frozen base
-    weights get no gradient product.  It composes with train_phi3 (one adapter over the packed qkv_proj / gate_up_proj).  Off, a
-    wrapped projection keeps the stock forward with grad enabled, as before.  `decoder_train.lora_stats` counts these layers and
-    their adapters.  train_lora alone leaves the no-grad routes as they are: a wrapped projection is stock there.
-    lora=True (opt-in): the prefill, the continued prefill and the decode step also take a layer whose projections are LoRA-wrapped
-    (`_lora_admit`: what `lora.adapter_of` understands, with a dropout that is the identity in the call -- nn.Identity, p = 0 or eval
-    mode --; a wrapper with `merged` or `disable_adapters` set, `lora.base_only_of`, counts as its base layer alone and gives the bits
-    of the unwrapped model: DPO's null-reference pass) and add the adapter branch UNMERGED after each of the four products: on many
-    rows the down / up kernels of the training route, on a decode step the two-launch group product of csrc/lora_rows.hip inside the
-    two library calls (`_lora_state` keeps the 16-bit operands and the descriptor; nothing is converted per step).  In-training
-    evaluation, `generate` during evaluation and several adapters over one base stay on the HIP layers without merging; it composes
-    with padded, continued, fp8_decode (the adapters keep 16 bits beside the e4m3 codes), wide_decode, train_lora and the Phi-3
-    layout.  `lora_stats` counts these layer calls and their adapters.  Off, a wrapped projection keeps the stock forward on the
-    no-grad routes (merge the adapters first: lora.merge_lora).
-    The ten switches are set anew by every call.
+    u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
+    patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
+    call sets all of them anew, so a switch that is not named goes back to its default, and what it kept per layer is freed.
     `disable_fused_prefill` restores the stock forwards."""
+    given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
+                 fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
@@ -1059,19 +1046,20 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     stack = base.__dict__.get("_u2_stack")
     if stack is None:
         stack = base._u2_stack = _StackState(base.register_forward_pre_hook(_mask_hook, with_kwargs=True))
-    stack.decode, stack.train, stack.prefill, stack.padded = bool(decode), bool(train) or bool(train_lora), bool(prefill), bool(padded)
-    stack.train_lora = bool(train_lora)
-    stack.continued, stack.fp8, stack.train_phi3 = bool(continued), bool(fp8_decode), bool(train_phi3)
-    stack.wide, stack.lora = bool(wide_decode), bool(lora)
-    stack.pad = stack.pad_shape = None
-    if not stack.fp8:   # (the copies go with the switch)
-        for layer in layers:
-            if is_patched(layer):
-                layer._u2_prefill.w8 = None
-    if not stack.lora:
-        for layer in layers:
-            if is_patched(layer):
-                layer._u2_prefill.lora = layer._u2_prefill.ads = None
+    on = {s.kw: bool(given[s.kw]) for s in SWITCHES}
+    for s in SWITCHES:
+        if on[s.kw]:
+            on.update(dict.fromkeys(s.implies, True))
+    for s in SWITCHES:
+        if s.field is not None:
+            setattr(stack, s.field, on[s.kw])
+        if s.frees and not on[s.kw]:   # (what the switch kept per layer goes with it, and the descriptors built from it)
+            for layer in layers:
+                if is_patched(layer):
+                    for f in s.frees:
+                        setattr(layer._u2_prefill, f, None)
+                    layer._u2_prefill.variants = [None] * 4
+    stack.pad, stack.pad_shape = _NO_PAD, None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
