@@ -364,16 +364,25 @@ int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, i
  * the W* are OCP e4m3 codes (contiguous (N, K) bytes) with one fp32 scale per weight row, every product is u2tok_gemm_rows_w8's
  * (below), and activations, biases, norms, attention and the KV cache stay in the element type; E, Hq * D and I must then be
  * multiples of 64, the weights 16-byte and the scales 4-byte aligned.  Some but not all scales set, and every other argument the
- * step does not take: U2TOK_ERR_ARG before anything is launched. */
+ * step does not take: U2TOK_ERR_ARG before anything is launched.
+ * With cfg->wform = 2 the step is weight-only MXFP4: the W* are e2m1 codes (contiguous (N, K / 2) bytes) and the four scale_*
+ * fields point at their e8m0 BLOCK scales (contiguous (N, K / 32) bytes, no alignment asked) instead of fp32 row scales; every
+ * product is u2tok_gemm_rows_w4's (below); E, Hq * D and I must then be multiples of 128 and the weights 16-byte aligned.  It runs
+ * at B <= 64, batched or not, with kv_start and with adapters as the other two forms do.  (The form is said by the config and the
+ * descriptor keeps its 17 pointers, so that a descriptor filled by a caller of an earlier version stays valid as it is.)  Some but
+ * not all, or none, of the block scales set, a wform other than 0 or 2, E, Hq * D or I not a multiple of 128: U2TOK_ERR_ARG from
+ * pre (q|k|v) or post before anything is launched. */
 typedef struct u2tok_decode_config {
   int32_t B, E, Hq, Hkv, D, I; /* new tokens (= batch), hidden size, query / key-value heads, head dim, MLP width */
   float eps, qk_eps, scale;    /* RMSNorm eps, q / k norm eps, softmax scale */
+  int32_t wform;               /* what the layer's scale_* are: 0 = fp32 row scales (all NULL: weights in the element type; all set:
+                                  e4m3 codes), 2 = e8m0 block-scale bytes (all set: e2m1 codes) */
 } u2tok_decode_config;
 /* Unmerged adapters (LoRA) of the step, `layer->lora` (NULL: none).  Each of the four products carries the segments of
  * u2tok_lora_rows (below) that are added to it: q|k|v up to 3 (a packed qkv_proj: one), o up to 1, gate|up up to 2 (a packed
  * gate_up_proj: one), down up to 1; n_* = 0 leaves the product alone.  The group product runs after the product it belongs to --
  * q|k|v: before the head norm and the rotary embedding, so the cache receives adapted keys and values; o and down: after the
- * residual epilogue, Y = rnd(float(Y) + scale u B^T) --, on base weights in the element type or in e4m3 alike.  With a gate or up
+ * residual epilogue, Y = rnd(float(Y) + scale u B^T) --, on base weights in the element type, in e4m3 or in e2m1 alike.  With a gate or up
  * segment the pair product takes its unfused form (product, group, SiLU(gate) * up).  `scratch` (16-byte aligned) is the branch's
  * own: 24576 bytes for u (64 rows of 192 elements) followed by the largest u2tok_lora_rows_workspace_bytes of the four groups;
  * u2tok_decoder_decode_workspace_bytes keeps its values.  A segment list u2tok_lora_rows refuses, a count outside its range or a
@@ -393,7 +402,9 @@ typedef struct u2tok_decode_layer {
   const void *w_in_norm, *Wqkv, *bqkv, *wq_norm, *wk_norm;       /* first half */
   const void *Wo, *bo, *w_post_norm, *Wgu, *bgu, *Wdown, *bdown; /* second half */
   const float *scale_qkv, *scale_o, *scale_gu, *scale_down;      /* all NULL: weights in the element type;
-                                                                    all set: the four W* are e4m3 codes, a scale per row */
+                                                                    all set: the four W* are e4m3 codes, a scale per row --
+                                                                    cfg->wform = 2: the four W* are e2m1 codes and these
+                                                                    are the addresses of their e8m0 block-scale BYTES */
   const u2tok_decode_lora* lora;                                 /* unmerged adapters of the step; NULL: none */
 } u2tok_decode_layer;
 size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* cfg, int32_t T);
@@ -422,6 +433,25 @@ int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* 
 int u2tok_gemm_rows_w8_wide(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
                             int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
                             u2tok_stream_t stream);
+/* ---- products on MXFP4 weights (OCP Microscaling FP4, weight-only).  An (N, K) weight is
+ *   codes : (N, K / 2) bytes of e2m1 codes (sign, 2 exponent bits, 1 mantissa bit: 0, .5, 1, 1.5, 2, 3, 4, 6 and their negatives), the
+ *           code of EVEN k in the LOW nibble of byte k / 2; ldw bytes between rows, ldw % 16 == 0, ldw >= K / 2, base 16-byte aligned;
+ *   scales: (N, K / 32) bytes, e8m0: byte e scales the 32 consecutive k = 32 j .. 32 j + 31 of one weight row by 2^(e - 127); lds
+ *           bytes between rows, lds >= K / 32;
+ *   K % 128 == 0.
+ * Activations, biases, norms, attention and the KV cache stay in the element type.  A product is exactly
+ * epilogue(sum_k A[m][k] * e2m1(code[n][k]) * 2^(e[n][k / 32] - 127)) with fp32 accumulation: codes are widened WITH their scale to
+ * the element type in registers (v_cvt_scalef32_pk_{bf16,f16}_fp4), and every e2m1 * 2^x is exact in bf16 and in fp16 for the
+ * scales the quantiser emits (u2tokenizer_amd/ops.py: quantize_blocks_fp4, x = e - 127 in [-23, 13]), so all the loss is the
+ * quantiser's.  For a scale byte outside that range the weight is whatever the conversion instruction rounds e2m1 * 2^x to in the
+ * element type (fp16: subnormals, zero or infinity; e = 255 is NaN in e8m0 and not interpreted here).
+ * u2tok_gemm_rows_w4: C (M, N), 1 <= M <= 64 in this one entry; flags of u2tok_gemm_rows_w8: 1 (bias[n]), 8 (+ R, ldr), 16 (fp32 C),
+ * or 512 ALONE (W4 = gate rows | up rows, N = 2 I, I % 8 == 0, C (M, I) = bf16(silu(bf16(gate))) * bf16(up)).  K % 128 != 0, a
+ * misaligned A / W4 / C, lda % 8 != 0 or a leading dimension below its row, a null S, M outside 1 .. 64, unknown flags:
+ * U2TOK_ERR_ARG, nothing launched.  16 < M <= 64: the block-of-16 contract of u2tok_gemm_rows_w8_wide.  Bit-repeatable. */
+int u2tok_gemm_rows_w4(const void* A, const void* W4, const uint8_t* S, void* C, const void* bias, const void* R, int32_t M,
+                       int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t lds, int64_t ldc, int64_t ldr, int32_t flags,
+                       u2tok_stream_t stream);
 /* The few-rows (weight-streaming) product on weights in the element type, called directly instead of through u2tok_gemm_bf16's
  * plan: C (M, N) = epilogue(sum_k A[m][k] W[n][k]), 1 <= M <= 64, W (N, K) with ldw elements between rows, K % 32 == 0, one batch
  * entry; flags 1 (bias[n]), 8 (+ R, ldr), 16 (fp32 C), or 512 ALONE (W = gate rows | up rows, N = 2 I, I % 8 == 0, C (M, I) =

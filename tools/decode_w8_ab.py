@@ -181,8 +181,8 @@ def _trace_table(d, layers):
     per_layer = ((HQ + 2 * HKV) * HD * E + E * HQ * HD + 2 * INTER * E + E * INTER)      # weight elements of the four products
     out = {}
     rows = list(csv.DictReader(files[0].open()))
-    # gemm_rows16_kernel<NW, NB, PAIR, W8> (csrc/gemm_rows.hip): the weight form is the last template argument
-    for key, pat, nbytes in (("bf16", r"gemm_rows16_kernel<[^>]*, false>", 2), ("w8", r"gemm_rows16_kernel<[^>]*, true>", 1)):
+    # gemm_rows16_kernel<NW, NB, PAIR, WForm> (csrc/gemm_rows.hip): the weight form is the last template argument, (u2::WForm)0 / 1
+    for key, pat, nbytes in (("bf16", r"gemm_rows16_kernel<[^>]*WForm\)0>", 2), ("w8", r"gemm_rows16_kernel<[^>]*WForm\)1>", 1)):
         sel = [r for r in rows if re.search(pat, r["Name"])]
         ns = sum(float(r["TotalDurationNs"]) for r in sel)
         calls = sum(int(r["Calls"]) for r in sel)

@@ -59,7 +59,8 @@ class TokConfig(C.Structure):
 
 class DecodeConfig(C.Structure):   # u2tok_decode_config
     _fields_ = [("B", C.c_int32), ("E", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32), ("I", C.c_int32),
-                ("eps", C.c_float), ("qk_eps", C.c_float), ("scale", C.c_float)]
+                ("eps", C.c_float), ("qk_eps", C.c_float), ("scale", C.c_float),
+                ("wform", C.c_int32)]      # 0: the layer's scale_* are fp32 row scales (or None); 2: e8m0 block-scale bytes (e2m1 codes)
 
 
 class LoraSeg(C.Structure):        # u2tok_lora_seg: one segment of a few-rows adapter group (u2tok_lora_rows)
@@ -155,6 +156,8 @@ SIGNATURES = {
     "u2tok_decoder_decode_post": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_gemm_rows_w8_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # A, W4, S, C, bias, R, M, N, K, lda, ldw, lds, ldc, ldr, flags, stream
+    "u2tok_gemm_rows_w4": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     # A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream
     "u2tok_gemm_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),

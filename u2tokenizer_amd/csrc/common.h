@@ -52,6 +52,7 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
 __device__ __forceinline__ float dot2_elem(uint32_t a, uint32_t b, float c) {  // c + a.lo b.lo + a.hi b.hi
   return __builtin_amdgcn_fdot2(__builtin_bit_cast(elem_x2_hw, a), __builtin_bit_cast(elem_x2_hw, b), c, false);
 }
+#define U2_CVT_SCALE_PK_ELEM_FP4 __builtin_amdgcn_cvt_scalef32_pk_f16_fp4   // (rows.h: w4_widen)
 #else
 #define U2_ELEM_ASM "bf16"
 #define U2_ELEM_IS_F16 0
@@ -76,6 +77,7 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) { return 
 __device__ __forceinline__ float dot2_elem(uint32_t a, uint32_t b, float c) {  // c + a.lo b.lo + a.hi b.hi
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(elem_x2_hw, a), __builtin_bit_cast(elem_x2_hw, b), c, false);
 }
+#define U2_CVT_SCALE_PK_ELEM_FP4 __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4
 #endif
 
 // VOXEL formats are data formats, not the build's element type: a bfloat16 volume is bfloat16 in either build.

@@ -200,15 +200,17 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
 // One projection of the step: the element type's product through the plan, or -- `sc`: a scale per weight row, w = e4m3 codes
-// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_rows.hip).  pair: w = gate | up, y (rows, out / 2).
-static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const bf16_t* b, bf16_t* y, int64_t ldy, int rows,
-                      int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
+// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_rows.hip), or -- `bs`: a scale byte per block of 32 k,
+// w = e2m1 codes (a DecodeLayer with block scales) -- on 4-bit weights.  pair: w = gate | up, y (rows, out / 2).
+static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const uint8_t* bs, const bf16_t* b, bf16_t* y,
+                      int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
   RowsArgs a;
   a.A = x; a.W = w; a.scale = sc; a.C = y; a.bias = b; a.R = R;
   a.M = rows; a.N = out; a.K = in;
-  a.lda = ldx; a.ldw = in; a.ldc = ldy; a.ldr = ldr;
+  a.lda = ldx; a.ldw = bs ? in >> 1 : in; a.ldc = ldy; a.ldr = ldr;
+  a.bscale = bs; a.lds = in >> 5;
   a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-  if (sc || rows > 16) return gemm_rows(a, st);
+  if (sc || bs || rows > 16) return gemm_rows(a, st);
   GemmDesc g;  // 16-bit weights, M <= 16: the plan (the same kernel, or a tile kernel when rows16_ok says no)
   g.A = x; g.B = reinterpret_cast<const bf16_t*>(w); g.C = y; g.bias = b; g.R = R;
   g.M = rows; g.N = out; g.K = in;
@@ -240,6 +242,19 @@ static bool w8_step_ok(const DecodeCfg& c, const void* const* w, const float* co
 // How many of a layer's four scales are set: 0 (weights in the element type) or 4 (e4m3 codes), anything between is refused
 static int scales_set(const DecodeLayer& l) { return !!l.scale_qkv + !!l.scale_o + !!l.scale_gu + !!l.scale_down; }
 
+// ... and of its four block-scale arrays: 0, or 4 (e2m1 codes) with no fp32 scale beside them
+static int bscales_set(const DecodeLayer& l) { return !!l.bscale_qkv + !!l.bscale_o + !!l.bscale_gu + !!l.bscale_down; }
+
+// What the e2m1 products ask of a step before anything is launched: all four block-scale arrays and none of the fp32 scales, K % 128
+// == 0 for all four, 16-byte aligned weights (the n of `w` this half reads).
+static bool w4_step_ok(const DecodeCfg& c, const DecodeLayer& l, const void* const* w, int n) {
+  if (bscales_set(l) != 4 || scales_set(l) != 0) return false;
+  if ((c.E & 127) || ((c.Hq * c.D) & 127) || (c.I & 127)) return false;
+  for (int i = 0; i < n; ++i)
+    if (!w[i] || ((uintptr_t)w[i] & 15)) return false;
+  return true;
+}
+
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
   const size_t rows = (size_t)c.B;
   size_t n = rows * ((size_t)3 * c.E + (size_t)c.Hq * c.D + (size_t)3 * c.I) * sizeof(bf16_t);  // xn, h, hn | ctx | gu (2 I), act
@@ -256,7 +271,9 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
                        hipStream_t st) {
   if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
   const int ns = scales_set(l);
-  if (ns != 0 && (ns != 4 || !w8_step_ok(c, &l.Wqkv, &l.scale_qkv, 1))) return U2_ERR_ARG;
+  if (bscales_set(l) != 0) {
+    if (!w4_step_ok(c, l, &l.Wqkv, 1)) return U2_ERR_ARG;
+  } else if (ns != 0 && (ns != 4 || !w8_step_ok(c, &l.Wqkv, &l.scale_qkv, 1))) return U2_ERR_ARG;
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
@@ -265,7 +282,7 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
   if (e != U2_OK) return e;
   e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
+  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, l.bscale_qkv, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
   if (e != U2_OK) return e;
   if (lr) e = dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, false, st);   // (before the head norm and the rotary embedding)
   if (e != U2_OK) return e;
@@ -285,7 +302,10 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     return U2_ERR_ARG;
   if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
   const int ns = scales_set(l);
-  if (ns != 0) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
+  if (bscales_set(l) != 0) {  // (the e2m1 products, likewise)
+    const void* w[3] = {l.Wo, l.Wgu, l.Wdown};
+    if (!w4_step_ok(c, l, w, 3)) return U2_ERR_ARG;
+  } else if (ns != 0) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
     const void* w[3] = {l.Wo, l.Wgu, l.Wdown};
     const float* s3[3] = {l.scale_o, l.scale_gu, l.scale_down};
     if (ns != 4 || !w8_step_ok(c, w, s3, 3)) return U2_ERR_ARG;
@@ -325,7 +345,7 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     const int e = attention(a, st);
     if (e != U2_OK) return e;
   }
-  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
+  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bscale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
   if (e != U2_OK) return e;
   if (lr) e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, false, st);   // (after the residual epilogue: the same terms)
   if (e != U2_OK) return e;
@@ -333,17 +353,17 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
   if (e != U2_OK) return e;
   const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
   if (!gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bscale_gu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bscale_gu, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
     if (e != U2_OK) return e;
     if (gu_lora) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, false, st);
     if (e != U2_OK) return e;
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  e = dec_linear(act, c.I, l.Wdown, l.scale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
+  e = dec_linear(act, c.I, l.Wdown, l.scale_down, l.bscale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
   if (e != U2_OK || !lr) return e;
   return dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, false, st);
 }

@@ -315,7 +315,7 @@ __device__ __forceinline__ void bt_tail_block(const GemmDesc& d, int n0, float (
   for (int vw = wv; vw < NWV; vw += 4) {   // the slices of "waves" wv, wv + 4, ...
     const int s0 = vw * per, s1 = min(nsteps, s0 + per);
     f32x4 acc[1];
-    rows_slice<1, false>(wp, xp, s0, s1, acc);
+    rows_slice<1, WForm::ELEM>(wp, xp, s0, s1, acc);
     red[vw][lane][0] = acc[0][0]; red[vw][lane][1] = acc[0][1]; red[vw][lane][2] = acc[0][2]; red[vw][lane][3] = acc[0][3];
   }
   __syncthreads();

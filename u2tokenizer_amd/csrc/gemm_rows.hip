@@ -1,9 +1,10 @@
-// The few-rows (weight-streaming) product: 1 .. 64 rows against N x K weights, in both weight forms -- the element type, and e4m3
-// codes with one fp32 scale per weight row (the decode step's four products read half the bytes; DESIGN f3: the step is bound by
-// them).  Weight-only: activations stay in the element type, the MFMA is the element type's v_mfma_f32_16x16x32 on weights widened
-// in registers (rows.h), so the e4m3 product is exactly x . dequant(W8) in fp32 accumulation.  Who calls it: the plan for M <= 16
-// (gemm.hip: gemm_step -- the ViT's cls rows, the decode step of up to 16 sequences), the decode step of 17 .. 64 sequences and on
-// e4m3 weights directly (decoder.hip), u2tok_gemm_rows*.  Arithmetic: rows.h -- every block of 16 rows gets the bits of the M <= 16
+// The few-rows (weight-streaming) product: 1 .. 64 rows against N x K weights, in three weight forms (rows.h: WForm) -- the element
+// type, e4m3 codes with one fp32 scale per weight row (the decode step's four products read half the bytes; DESIGN f3: the step is
+// bound by them), and OCP MXFP4: e2m1 codes with one e8m0 scale per block of 32 k, a quarter of the bytes, widened with their scale
+// by one conversion instruction per pair (DESIGN f11).  Weight-only: activations stay in the element type, the MFMA is the element
+// type's v_mfma_f32_16x16x32 on weights widened in registers (rows.h), so a product on codes is exactly x . dequant(W) in fp32
+// accumulation.  Who calls it: the plan for M <= 16 (gemm.hip: gemm_step -- the ViT's cls rows, the decode step of up to 16
+// sequences), the decode step of 17 .. 64 sequences and on e4m3 / e2m1 weights directly (decoder.hip), u2tok_gemm_rows*.  Arithmetic: rows.h -- every block of 16 rows gets the bits of the M <= 16
 // product on those rows, so a sequence's tokens do not depend on how many sequences share the step.
 #include "rows.h"
 
@@ -24,14 +25,15 @@ namespace u2 {
 // PAIR (GEMM_SWIGLU: W = [gate rows | up rows], N = 2 I, C (M, I) = bf16(silu(gate)) * up -- the form the big-tile kernel has for
 // the prefill): the workgroup's 16 weight rows are 8 gate rows and the SAME 8 up rows, so the lanes of column groups 0 / 1 hold
 // the gates and those of groups 2 / 3 (32 lanes further) the matching ups; the decode step's SwiGLU launch goes away.
-// a.W / a.ldw: bytes and codes with W8, else elements of the element type.
-template <int NW, int NB, bool PAIR, bool W8>
-__global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(RowsArgs a) {
+// a.W / a.ldw: bytes with codes (e4m3: one per byte, e2m1: two), else elements of the element type.
+template <int NW, int NB, bool PAIR, WForm F>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_min_waves(NW, NB, F)))) void gemm_rows16_kernel(RowsArgs a) {
   __shared__ float red[NB][NW][64][4];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (scalar: the row block of the epilogue too)
   const int l15 = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int nsteps = W8 ? a.K >> 6 : a.K >> 5;  // K % 64 == 0 / K % 32 == 0 (gemm_rows_check, rows16_ok)
+  constexpr bool W8 = F == WForm::E4M3, W4 = F == WForm::E2M1;
+  const int nsteps = W4 ? a.K >> 7 : W8 ? a.K >> 6 : a.K >> 5;  // K % 128 == 0 / K % 64 == 0 / K % 32 == 0 (gemm_rows_check, rows16_ok)
   const int per = (nsteps + NW - 1) / NW, s0 = wv * per, s1 = min(nsteps, s0 + per);
   const int I2 = a.N >> 1;
   // the weight row of column c of the workgroup's 16 (PAIR: gate row 8 blk + c for c < 8, up row I + 8 blk + c - 8)
@@ -39,13 +41,14 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(RowsArgs a) {
     if constexpr (PAIR) return min((c < 8 ? 0 : I2) + (int)blockIdx.x * 8 + (c & 7), a.N - 1);
     else return min(n0 + c, a.N - 1);
   };
-  constexpr int GE = W8 ? 16 : 8;  // elements of a lane group per step: 16 bytes of the weight row in either form
-  const char* wp = reinterpret_cast<const char*>(a.W) + (int64_t)wrow(l15) * a.ldw * (W8 ? 1 : 2) + g * 16;
+  constexpr int GE = W4 ? 32 : W8 ? 16 : 8;  // elements of a lane group per step: 16 bytes of the weight row in every form
+  const char* wp = reinterpret_cast<const char*>(a.W) + (int64_t)wrow(l15) * a.ldw * (W8 || W4 ? 1 : 2) + g * 16;
   const bf16_t* xp[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) xp[b] = a.A + (int64_t)min(16 * b + l15, a.M - 1) * a.lda + g * GE;
   f32x4 acc[NB];
-  rows_slice<NB, W8>(wp, xp, s0, s1, acc);
+  if constexpr (W4) rows_slice<NB, F>(wp, xp, s0, s1, acc, a.bscale + (int64_t)wrow(l15) * a.lds + g);
+  else rows_slice<NB, F>(wp, xp, s0, s1, acc);
   // lane holds C[m = 16 b + l15][column 4 g + r of the workgroup's 16] of every block b
 #pragma unroll
   for (int b = 0; b < NB; ++b) *reinterpret_cast<f32x4*>(red[b][wv][lane]) = acc[b];
@@ -64,6 +67,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(RowsArgs a) {
     auto mult = [&](int r) {
       const int c = 4 * g + r;  // (wrow(c) written out: through the nested lambda <4, 4, true, true> takes 8 more VGPRs and loses a wave)
       if constexpr (W8) return a.scale[min((c < 8 ? 0 : I2) + (int)blockIdx.x * 8 + (c & 7), a.N - 1)];
+      else if constexpr (W4) return 1.f;  // (the block scales went in with the conversion)
       else return a.alpha;
     };
     rows_pair_store(v, mult, g < 2 && l15 < mb, m, (int)blockIdx.x * 8 + 4 * g, I2, reinterpret_cast<bf16_t*>(a.C), a.ldc);
@@ -74,48 +78,51 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows16_kernel(RowsArgs a) {
     for (int r = 0; r < 4; ++r) v[r] *= a.scale[wrow(4 * g + r)];
   }
   RowsEpi e = a;
-  if constexpr (W8 || NB > 1) e.alpha = e.alpha_lo = 1.f, e.nsplit = 0;  // (only a plan's step, 16-bit and M <= 16, sets them: constants here)
+  if constexpr (W8 || W4 || NB > 1) e.alpha = e.alpha_lo = 1.f, e.nsplit = 0;  // (only a plan's step, 16-bit and M <= 16, sets them: constants here)
   rows_store(e, v, m, n0 + 4 * g, reinterpret_cast<char*>(a.C), a.R);
 }
 
-// What gemm_rows accepts: one function for both weight forms (a.scale set: e4m3 codes).
+// What gemm_rows accepts: one function for all weight forms (a.scale set: e4m3 codes; a.bscale set: e2m1 codes; both: refused).
 int gemm_rows_check(const RowsArgs& a) {
-  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr;
-  if (!a.A || !a.W || !a.C || a.M <= 0 || a.M > 64 || a.N <= 0 || a.K <= 0 || (a.K & (w8 ? 63 : 31))) return U2_ERR_ARG;
+  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr, w4 = a.bscale != nullptr;
+  if (w8 && w4) return U2_ERR_ARG;
+  if (!a.A || !a.W || !a.C || a.M <= 0 || a.M > 64 || a.N <= 0 || a.K <= 0 || (a.K & (w4 ? 127 : w8 ? 63 : 31))) return U2_ERR_ARG;
   if (a.flags & ~(GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_SWIGLU)) return U2_ERR_ARG;
   if (pair && (a.flags != GEMM_SWIGLU || (a.N & 15))) return U2_ERR_ARG;  // gate | up: N = 2 I, I % 8 == 0
   if (((a.flags & GEMM_BIAS_N) && !a.bias) || ((a.flags & GEMM_RESIDUAL) && (!a.R || a.ldr < a.N))) return U2_ERR_ARG;
-  if (a.lda < a.K || (a.lda & 7) || a.ldw < a.K || (a.ldw & (w8 ? 15 : 7)) || a.ldc < (pair ? a.N >> 1 : a.N)) return U2_ERR_ARG;
+  if (a.lda < a.K || (a.lda & 7) || a.ldw < (w4 ? a.K >> 1 : a.K) || (a.ldw & (w8 || w4 ? 15 : 7)) || a.ldc < (pair ? a.N >> 1 : a.N))
+    return U2_ERR_ARG;
+  if (w4 && a.lds < (a.K >> 5)) return U2_ERR_ARG;
   if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) || ((uintptr_t)a.scale & 3) || ((uintptr_t)a.C & ((a.flags & GEMM_OUT_F32) ? 3 : 1)))
     return U2_ERR_ARG;
   return U2_OK;
 }
 
 int gemm_rows_launch(const RowsArgs& a, hipStream_t stream) {
-  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr;
+  const bool pair = a.flags & GEMM_SWIGLU;
+  const int form = a.bscale ? 2 : a.scale ? 1 : 0;  // (WForm)
   const int nb = (a.M + 15) >> 4;
-  const int nw = rows16_slices(w8 ? a.K >> 6 : a.K >> 5);  // from the (double) steps alone, whatever M: the contract
-  // the 48 instantiations: [W8][PAIR][NW = 16, 8, 4][NB - 1]
-#define ROWS_NB(NW, PAIR, W8) \
-  {gemm_rows16_kernel<NW, 1, PAIR, W8>, gemm_rows16_kernel<NW, 2, PAIR, W8>, gemm_rows16_kernel<NW, 3, PAIR, W8>, gemm_rows16_kernel<NW, 4, PAIR, W8>}
-  void (*const k[2][2][3][4])(RowsArgs) = {
-      {{ROWS_NB(16, false, false), ROWS_NB(8, false, false), ROWS_NB(4, false, false)},
-       {ROWS_NB(16, true, false), ROWS_NB(8, true, false), ROWS_NB(4, true, false)}},
-      {{ROWS_NB(16, false, true), ROWS_NB(8, false, true), ROWS_NB(4, false, true)},
-       {ROWS_NB(16, true, true), ROWS_NB(8, true, true), ROWS_NB(4, true, true)}}};
+  const int nw = rows16_slices(a.K >> (5 + form));  // from the (double, quad) steps alone, whatever M: the contract
+  // the 72 instantiations: [WForm][PAIR][NW = 16, 8, 4][NB - 1]
+#define ROWS_NB(NW, PAIR, F) \
+  {gemm_rows16_kernel<NW, 1, PAIR, F>, gemm_rows16_kernel<NW, 2, PAIR, F>, gemm_rows16_kernel<NW, 3, PAIR, F>, gemm_rows16_kernel<NW, 4, PAIR, F>}
+#define ROWS_FORM(F) \
+  {{ROWS_NB(16, false, F), ROWS_NB(8, false, F), ROWS_NB(4, false, F)}, {ROWS_NB(16, true, F), ROWS_NB(8, true, F), ROWS_NB(4, true, F)}}
+  void (*const k[3][2][3][4])(RowsArgs) = {ROWS_FORM(WForm::ELEM), ROWS_FORM(WForm::E4M3), ROWS_FORM(WForm::E2M1)};
+#undef ROWS_FORM
 #undef ROWS_NB
   const dim3 grid((unsigned)(pair ? cdiv(a.N >> 1, 8) : cdiv(a.N, 16)));
-  hipLaunchKernelGGL(k[w8][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
+  hipLaunchKernelGGL(k[form][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
   return launch_status();
 }
 
 int gemm_rows(const RowsArgs& a, hipStream_t stream) {
   const int e = gemm_rows_check(a);
   if (e != U2_OK) return e;
-  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr;
+  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr, w4 = a.bscale != nullptr;
   const double out_b = pair ? 2.0 * a.M * (a.N >> 1) : ((a.flags & GEMM_OUT_F32) ? 4.0 : 2.0) * a.M * a.N;
   ProfScope ps(PROF_GEMM, 2.0 * a.M * a.N * a.K, stream,
-               2.0 * a.M * a.K + (w8 ? 1.0 : 2.0) * a.N * a.K + (w8 ? 4.0 * a.N : 0.0) + out_b +
+               2.0 * a.M * a.K + (w4 ? 0.5 : w8 ? 1.0 : 2.0) * a.N * a.K + (w8 ? 4.0 * a.N : w4 ? (double)a.N * (a.K >> 5) : 0.0) + out_b +
                    ((a.flags & GEMM_RESIDUAL) ? 2.0 * a.M * a.N : 0.0));
   return gemm_rows_launch(a, stream);
 }

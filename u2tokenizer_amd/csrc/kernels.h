@@ -113,12 +113,15 @@ struct RowsEpi {                 // what the epilogue of a lane's 4 columns read
 };
 struct RowsArgs : RowsEpi {
   const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
-  const void* W = nullptr;       // [N][K], leading dim ldw: e4m3 codes and bytes when `scale` is set, else elements of the element type
-  const float* scale = nullptr;  // [N], or null: 16-bit weights
+  const void* W = nullptr;       // [N][K], leading dim ldw: e4m3 codes and bytes when `scale` is set, e2m1 codes (two per byte, even k
+                                 // in the low nibble) and bytes when `bscale` is set, else elements of the element type
+  const float* scale = nullptr;  // [N], or null: not e4m3 weights
   void* C = nullptr;             // [M][N] elements or fp32 (GEMM_OUT_F32); [M][N / 2] elements with GEMM_SWIGLU
   const bf16_t* R = nullptr;     // [M][N], leading dim ldr (GEMM_RESIDUAL)
   int M = 0, K = 0;
   int64_t lda = 0, ldw = 0;
+  const uint8_t* bscale = nullptr;  // [N][K / 32] e8m0 block scales (2^(e - 127) for 32 consecutive k of a row), lds bytes between rows,
+  int64_t lds = 0;                  // or null: not e2m1 weights (behind every older field: those keep their kernel-argument offsets)
 };
 // gemm_rows: the product outside the plan -- what the decode step calls directly (the plan of an M = 17 .. 64 product is a tile
 // kernel's, pinned for the training path): flags GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 or GEMM_SWIGLU alone, alpha = 1 and no
@@ -357,6 +360,7 @@ struct DecodeLayer {
   const bf16_t *bo, *w_post_norm, *bgu, *bdown;        // second half
   const float *scale_qkv, *scale_o, *scale_gu, *scale_down;
   const DecodeLora* lora = nullptr;                    // unmerged adapters (NULL: none)
+  const uint8_t *bscale_qkv = nullptr, *bscale_o = nullptr, *bscale_gu = nullptr, *bscale_down = nullptr;  // e2m1 block scales (the C ABI carries them in its scale fields under wform = 2: capi.hip)
 };
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T);
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,

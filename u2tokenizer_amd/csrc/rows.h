@@ -1,4 +1,5 @@
-// The arithmetic of the few-rows product (1 .. 64 rows against N x K weights in the element type or as e4m3 codes), shared by
+// The arithmetic of the few-rows product (1 .. 64 rows against N x K weights in the element type, as e4m3 codes or as e2m1 codes with
+// block scales), shared by
 // gemm_rows16_kernel (gemm_rows.hip) and by the big-tile kernel's in-launch tail (gemm_bt.hip, round 5: the ViT's 8 cls rows ride in
 // the launch of the 16384 patch rows instead of a launch of their own) -- ONE definition, so that a row's value does not depend on
 // which of them computed it, on the weight form's kernel, or on how many row blocks share the pass over K:
@@ -24,6 +25,21 @@
 //     (k = 64 s + 16 g + 8 .. 15) those of MFMA 2 -- v_mfma_f32_16x16x32 sums its 32 slots, whichever k sits in them.
 //   * the double steps are cut into NW contiguous slices (one per wave, `per` double steps each); a slice is one accumulator chain
 //     in double-step order, MFMA 1 before MFMA 2; the NW partial tiles are added in slice order 0 .. NW - 1.
+//
+// OCP MXFP4 (e2m1 codes, two per byte, even k in the low nibble; one e8m0 scale byte per 32 consecutive k of a weight row) weights:
+// the same product with the weight operand read as 4-bit codes, widened to the element type in registers WITH the block's scale
+// (v_cvt_scalef32_pk_*_fp4: e2m1 x 2^(e - 127) is exact in bf16 and fp16 for every scale the quantiser emits, e - 127 in
+// [-23, 13]; outside that range the value is whatever the instruction rounds to).  Nothing is applied after the sum:
+// C[m][n] = epilogue(sum_k x[m][k] * e2m1(W4[n][k]) * 2^(S[n][k / 32] - 127)), fp32 accumulation, alpha = 1.
+// THE K MAPPING:
+//   * K is cut into K / 128 QUAD STEPS; quad step s covers k = 128 s .. 128 s + 127;
+//   * lane group g = lane / 16 of a quad step owns k = 128 s + 32 g .. 128 s + 32 g + 31: ONE 16-byte weight load (32 codes) -- exactly
+//     one MX block, hence ONE scale byte S[n][4 s + g] per lane and quad step -- and four 16-byte activation loads (64 contiguous
+//     bytes of the row);
+//   * its values 8 j .. 8 j + 7 (j = 0 .. 3; dword j of the load) are the group's 8 K slots of MFMA j of the quad step;
+//   * the scale enters as the conversion's fp32 operand ((uint32)e << 23);
+//   * the quad steps are cut into NW contiguous slices (rows16_slices of their number); a slice is one accumulator chain in
+//     quad-step order, MFMA 0 .. 3; the NW partial tiles are added in slice order 0 .. NW - 1.
 #pragma once
 #include <type_traits>
 #include "kernels.h"
@@ -31,6 +47,9 @@
 namespace u2 {
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+// The form of the weight operand: the element type, e4m3 codes with a scale per row, e2m1 codes with a scale per block of 32
+enum class WForm : int { ELEM = 0, E4M3 = 1, E2M1 = 2 };
 
 // 8 e4m3 codes (two dwords, ascending k) -> one MFMA fragment of 8 elements: v_cvt_pk_f32_fp8 x 4, the element type's pack x 4
 __device__ __forceinline__ bf16x8 w8_widen(uint32_t lo, uint32_t hi) {
@@ -45,10 +64,28 @@ __device__ __forceinline__ bf16x8 w8_widen(uint32_t lo, uint32_t hi) {
 #endif
 }
 
+// 8 e2m1 codes (one dword: ascending k, the even k of a byte in its low nibble) and their block's scale as an fp32 (2^x) -> one MFMA
+// fragment of 8 elements: v_cvt_scalef32_pk_{bf16,f16}_fp4 x 4, one per byte -- the instruction emits the low nibble first
+__device__ __forceinline__ bf16x8 w4_widen(uint32_t c, float s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const u32x4 p = {__builtin_bit_cast(uint32_t, U2_CVT_SCALE_PK_ELEM_FP4(c, s, 0)), __builtin_bit_cast(uint32_t, U2_CVT_SCALE_PK_ELEM_FP4(c, s, 1)),
+                   __builtin_bit_cast(uint32_t, U2_CVT_SCALE_PK_ELEM_FP4(c, s, 2)), __builtin_bit_cast(uint32_t, U2_CVT_SCALE_PK_ELEM_FP4(c, s, 3))};
+  return __builtin_bit_cast(bf16x8, p);
+#else
+  (void)c; (void)s;
+  return bf16x8{};
+#endif
+}
+
 // Steps (W8: double steps) whose loads are in flight before the first MFMA.  One row block: 8 = 16 loads (W8: 8 weight + 16
 // activation loads) per lane.  NB > 1: 4 steps = 4 (1 + NB) loads, 2 double steps = 2 weight + 4 NB activation loads, because 8 x
 // (1 weight + 4 activation fragments) do not fit the 128 VGPRs a lane of a 16-wave workgroup has.
-constexpr int rows_in_flight(int NB, bool W8) { return NB == 1 ? 8 : W8 ? 2 : 4; }
+// e2m1: quad steps of 1 weight + 4 NB activation + 1 scale load: TWO of them for one row block (2 + 8 + 2 loads: 64 .. 76 VGPRs, 6 .. 8
+// waves per SIMD; four -- 97 .. 117 VGPRs, 4 waves -- measured 5 to 10 % slower at 16 rows and on the K = 12288 product, equal within
+// 2 % elsewhere: DESIGN f11), ONE for NB > 1 (two for NB = 2 measured 5 to 10 % slower at 32 rows).
+constexpr int rows_in_flight(int NB, WForm F) {
+  return F == WForm::E2M1 ? (NB == 1 ? 2 : 1) : NB == 1 ? 8 : F == WForm::E4M3 ? 2 : 4;
+}
 // The loop form.  Whole blocks of U steps run without a guard per step (a guarded step lets the compiler sink its loads behind the
 // MFMAs before it), then the rest of the slice (< U) is one guarded block; where codes are converted, a scheduling barrier keeps
 // every load of a block ahead of its first conversion.  On weights streamed from memory the 16-bit NB > 1 loops are 2 to 11 % faster in
@@ -56,39 +93,53 @@ constexpr int rows_in_flight(int NB, bool W8) { return NB == 1 ? 8 : W8 ? 2 : 4;
 // (rows_guarded): there every block is clamped and guarded and nothing is fenced, because the two-body form with the fence holds
 // 2 + 4 NB fragments AND the widened codes at once -- 96 .. 116 VGPRs instead of 42 .. 82, occupancy 4 .. 5 waves per SIMD
 // instead of 7 .. 8 in the compiler's resource report; without the fence still 5 .. 6 instead of 7 .. 8.
-constexpr bool rows_guarded(int NB, bool W8) { return W8 && NB > 1; }
+// e2m1 with NB > 1: one quad step per block, so a block is whole or absent and the two forms are the same loop: the guarded one.
+constexpr bool rows_guarded(int NB, WForm F) { return F != WForm::ELEM && NB > 1; }
+// The waves per SIMD gemm_rows16_kernel asks the register allocator for.  NW / 4 is what its launch bounds say by themselves (the
+// element and e4m3 instantiations compile as without the attribute).  e2m1 with NB > 1 on 4 or 8 waves: 8, the occupancy of the e4m3
+// instantiations of the same (NW, NB) -- left alone the allocator keeps all 4 NB activation fragments of a quad step in flight and
+// ends at 6 .. 7 waves for NB = 3 / 4; held to 64 registers it still neither spills nor touches scratch (DESIGN f11).
+constexpr int rows_min_waves(int NW, int NB, WForm F) { return F == WForm::E2M1 && NB > 1 && NW < 16 ? 8 : NW / 4; }
 
 // Steps [s0, s1) of one slice for NB row blocks.  wp = the lane's weight row + 16 g bytes (a step is 64 bytes of a weight row in
-// either form: 8 elements or 16 codes per lane group); xp[b] = its activation row of block b + 8 g (W8: 16 g) elements.  A weight
+// every form: 8 elements, 16 or 32 codes per lane group); xp[b] = its activation row of block b + 8 g (e4m3: 16 g, e2m1: 32 g)
+// elements; sp (e2m1 alone) = the lane's scale row + g: a step's scale byte is sp[4 step].  A weight
 // fragment feeds the NB blocks in block order; a code is widened once for all of them.  The bounds are the same for all lanes of a
 // wave; they are moved to scalar registers here, so that the guards below are scalar branches and never EXEC masks around an MFMA
 // (MFMA ignores EXEC: as lane values the guards have left a guarded MFMA without its skip-if-EXEC-is-empty branch, a step counted twice).
-template <int NB, bool W8>
-__device__ __forceinline__ void rows_slice(const char* wp, const bf16_t* const (&xp)[NB], int s0_, int s1_, f32x4 (&acc)[NB]) {
+template <int NB, WForm F>
+__device__ __forceinline__ void rows_slice(const char* wp, const bf16_t* const (&xp)[NB], int s0_, int s1_, f32x4 (&acc)[NB],
+                                           const uint8_t* sp = nullptr) {
   const int s0 = __builtin_amdgcn_readfirstlane(s0_), s1 = __builtin_amdgcn_readfirstlane(s1_);
-  constexpr int U = rows_in_flight(NB, W8), NX = W8 ? 2 : 1;  // NX: activation fragments (= MFMAs per row block) of a step
-  constexpr bool G = rows_guarded(NB, W8);
+  constexpr bool W8 = F == WForm::E4M3, W4 = F == WForm::E2M1;
+  constexpr int U = rows_in_flight(NB, F), NX = W4 ? 4 : W8 ? 2 : 1;  // NX: activation fragments (= MFMAs per row block) of a step
+  constexpr bool G = rows_guarded(NB, F);
 #pragma unroll
   for (int b = 0; b < NB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto block = [&](int sb, auto whole) {
     u32x4 wf[U];
     bf16x8 xf[U][NB][NX];
+    uint32_t sf[U];  // (e2m1: the step's scale byte)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int st = decltype(whole)::value ? sb + u : min(sb + u, s1 - 1);
       wf[u] = *reinterpret_cast<const u32x4*>(wp + st * 64);
+      if constexpr (W4) sf[u] = sp[4 * st];
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int h = 0; h < NX; ++h) xf[u][b][h] = *reinterpret_cast<const bf16x8*>(xp[b] + st * (32 * NX) + 8 * h);
     }
-    if constexpr (W8 && !G) __builtin_amdgcn_sched_barrier(0);  // every load above is issued before the first conversion / MFMA below
+    if constexpr ((W8 || W4) && !G) __builtin_amdgcn_sched_barrier(0);  // every load above is issued before the first conversion / MFMA below
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (decltype(whole)::value || sb + u < s1) {
         bf16x8 w[NX];
         if constexpr (W8) w[0] = w8_widen(wf[u].x, wf[u].y), w[1] = w8_widen(wf[u].z, wf[u].w);
-        else w[0] = __builtin_bit_cast(bf16x8, wf[u]);
+        else if constexpr (W4) {
+          const float s = __uint_as_float(sf[u] << 23);
+          w[0] = w4_widen(wf[u].x, s), w[1] = w4_widen(wf[u].y, s), w[2] = w4_widen(wf[u].z, s), w[3] = w4_widen(wf[u].w, s);
+        } else w[0] = __builtin_bit_cast(bf16x8, wf[u]);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll

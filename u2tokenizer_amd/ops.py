@@ -744,8 +744,89 @@ def snap_fp8_(module):
     return module
 
 
+# ------------------------------------------------------------------- MXFP4 (e2m1 codes, e8m0 block scales) weight-only products
+FP4_BLOCK = 32                       # consecutive k of one weight row that share a scale (OCP Microscaling)
+FP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # |e2m1| by code & 7; bit 3 is the sign
+FP4_X_MIN, FP4_X_MAX = -23, 13       # block exponents the quantiser emits: every e2m1 * 2^x in it is exact in fp16 AND in bf16
+
+
+def _fp4_blocks(who, w):
+    if not torch.is_tensor(w) or w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError(f"{who}: expected a 2-D bf16 / fp16 / fp32 weight")
+    N, K = w.shape
+    if K % 128:
+        raise RuntimeError(f"{who}: K = {K} is not a multiple of 128")
+    wf = w.detach().float().reshape(N, K // FP4_BLOCK, FP4_BLOCK)
+    amax = wf.abs().amax(2)
+    if not bool(torch.isfinite(amax).all()):
+        raise RuntimeError(f"{who}: the weight holds inf / nan")
+    if bool((amax >= 2.0 ** 16).any()):
+        raise RuntimeError(f"{who}: a block's largest magnitude is 2^16 or more")
+    # floor(log2(amax)) exactly: amax = m 2^e with m in [0.5, 1)
+    x = torch.where(amax > 0, torch.frexp(amax).exponent - 3, torch.zeros_like(amax, dtype=torch.int32)).clamp_(FP4_X_MIN, FP4_X_MAX)
+    return wf, x
+
+
+def _fp4_round(v):
+    """|v| (fp32, >= 0) to the nearest e2m1 magnitude, ties to the even code, saturating at 6 -> twice that magnitude (0 .. 12)"""
+    v = v.clamp(max=6.0)
+    return torch.where(v < 2.0, torch.round(v * 2.0), torch.where(v < 4.0, torch.round(v) * 2.0, torch.round(v * 0.5) * 4.0))
+
+
+def quantize_blocks_fp4(w: torch.Tensor):
+    """OCP MXFP4 quantisation of a 2-D weight (N, K) in bf16 / fp16 / fp32, K % 128 == 0 -> (codes uint8 (N, K / 2): e2m1, the
+    code of even k in the low nibble; scales uint8 (N, K / 32): e8m0, 2^(e - 127) for 32 consecutive k of a row).  The OCP MX
+    rule: per block x = floor(log2(amax)) - 2 (0 for an all-zero block), clamped to [-23, 13] -- where every e2m1 * 2^x is exact
+    in fp16 and bf16 alike, so the codes do not depend on the build --, elements w / 2^x rounded to nearest-even on the e2m1 grid
+    {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6.  RuntimeError for inf / nan, a block with amax >= 2^16, a weight that is not
+    2-D, K % 128 != 0.  Plain torch, any device; not a hot path (the decode route quantises a layer once, prefill.py)."""
+    wf, x = _fp4_blocks("quantize_blocks_fp4", w)
+    N, nb, _ = wf.shape
+    v = torch.ldexp(wf, -x[:, :, None])                     # (exact: a power of two)
+    twice = _fp4_round(v.abs()).to(torch.int64)             # 0, 1, 2, 3, 4, 6, 8, 12
+    lut = torch.tensor([0, 1, 2, 3, 4, 0, 5, 0, 6, 0, 0, 0, 7], dtype=torch.uint8, device=w.device)
+    code = lut[twice]
+    code = torch.where((v < 0) & (code != 0), code | 8, code).reshape(N, nb * FP4_BLOCK)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return codes, (x + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_blocks_fp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 (N, K) = e2m1(code[n][k]) * 2^(scale[n][k / 32] - 127): what the e2m1 products multiply by, exactly."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or \
+            codes.shape[0] != scales.shape[0] or codes.shape[1] * 2 != scales.shape[1] * FP4_BLOCK:
+        raise RuntimeError(f"dequantize_blocks_fp4: expected uint8 codes (N, K / 2) and scales (N, K / 32), got "
+                           f"{tuple(codes.shape)} {codes.dtype}, {tuple(scales.shape)} {scales.dtype}")
+    N = codes.shape[0]
+    code = torch.stack((codes & 15, codes >> 4), 2).reshape(N, -1).to(torch.int64)
+    grid = torch.tensor(FP4_GRID + tuple(-g for g in FP4_GRID), dtype=torch.float32, device=codes.device)
+    x = (scales.to(torch.int32) - 127).repeat_interleave(FP4_BLOCK, 1)
+    return torch.ldexp(grid[code], x)
+
+
+def snap_fp4_(module):
+    """In place, for every nn.Linear weight in `module` with in_features % 128 == 0 (or a 2-D tensor): move each block of 32 onto
+    values the block quantiser keeps EXACTLY -- e2m1 multiples of the block's 2^x, the block's largest element at +-6 2^x or +-4 2^x
+    (where rounding with saturation puts it: amax / 2^x lies in [4, 8) unless x was clamped from below), so that quantize_blocks_fp4 finds that same x.  Then
+    dequantize_blocks_fp4(*quantize_blocks_fp4(w)) == w bit for bit, and w is exact in bf16 and in fp16: a model with snapped
+    weights and its e2m1 decode step compute the same function.  Other weights stay as they are.  For tests and the A/B tool."""
+    ws = [module] if torch.is_tensor(module) else [m.weight.data for m in module.modules() if isinstance(m, torch.nn.Linear)]
+    for w in ws:
+        if w.dim() != 2 or w.shape[1] % 128:
+            continue
+        wf, x = _fp4_blocks("snap_fp4_", w)
+        v = torch.ldexp(wf, -x[:, :, None])
+        q = torch.copysign(_fp4_round(v.abs()) * 0.5, v)
+        # the largest element: rounding with saturation puts it at 4 or 6 already, except in a block whose x was clamped from below
+        top = v.abs().argmax(2, keepdim=True)
+        vt = v.gather(2, top)
+        q.scatter_(2, top, torch.where(vt == 0, vt, torch.copysign(torch.where(vt.abs() > 5.0, 6.0, 4.0), vt)))
+        w.copy_(torch.ldexp(q, x[:, :, None]).reshape(w.shape).to(w.dtype))
+    return module
+
+
 def _rows_call(who, a, N, bias, residual, out_f32, swiglu, out):
-    """What gemm_rows and gemm_rows_w8 share: A as (M, K) rows with unit column stride, `out`, the flags, the residual and its
+    """What gemm_rows, gemm_rows_w8 and gemm_rows_w4 share: A as (M, K) rows with unit column stride, `out`, the flags, the residual and its
     row stride -> (a2, out, bias, ldr, flags) for a weight of N rows"""
     a2 = a.reshape(-1, a.shape[-1])
     if a2.stride(1) != 1:
@@ -791,6 +872,30 @@ def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias
     st = getattr(h, name)(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K,
                           out.stride(0), ldr, flags, _stream())
     _lib.check(st, name)
+    return out
+
+
+@_guarded
+def gemm_rows_w4(a: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, *, bias=None, residual=None, out_f32=False,
+                 swiglu=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(M <= 64, N) = epilogue(a @ dequantize_blocks_fp4(codes, scales)^T) for MXFP4 weights -- codes (N, K / 2) uint8, scales
+    (N, K / 32) uint8, K % 128 == 0 (u2tok_gemm_rows_w4: the decode step's weight-streaming product on 4-bit weights, fp32
+    accumulation; each block of 16 rows has the bits of the M <= 16 product on it).  swiglu: codes = gate rows | up rows ->
+    (M, N / 2) = silu(gate) * up.  `out` / `residual` may be row-strided views (unit column stride)."""
+    h = _lib.load_library()
+    _need(a, ELEM, "A")
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or not codes.is_cuda or not scales.is_cuda:
+        raise RuntimeError("gemm_rows_w4: expected uint8 codes and uint8 block scales on the GPU")
+    codes, scales = codes.contiguous(), scales.contiguous()
+    N, K = codes.shape[0], a.shape[-1]
+    if codes.dim() != 2 or scales.shape != (N, K // 32) or codes.shape[1] * 2 != K:
+        raise RuntimeError(f"gemm_rows_w4: shapes A {tuple(a.reshape(-1, K).shape)}, codes {tuple(codes.shape)}, "
+                           f"scales {tuple(scales.shape)}")
+    a2, out, bias, ldr, flags = _rows_call("gemm_rows_w4", a, N, bias, residual, out_f32, swiglu, out)
+    M = a2.shape[0]
+    st = h.u2tok_gemm_rows_w4(_ptr(a2), _ptr(codes), _ptr(scales), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0),
+                              K // 2, K // 32, out.stride(0), ldr, flags, _stream())
+    _lib.check(st, "u2tok_gemm_rows_w4")
     return out
 
 

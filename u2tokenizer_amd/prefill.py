@@ -25,7 +25,8 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     append-in-place / DynamicSlidingWindowLayer layers, no mask or all ones, with `padded` also a LEFT-padded mask as wide as
     cache + call on layers without a window; stock: a right-padded continuation, holes, window + padding, offloaded / static /
     quantized caches.
-  * fp8_decode, lora: what they keep per layer beside the weights (e4m3 copies with a scale per row; 16-bit adapter operands)
+  * fp8_decode, fp4_decode, lora: what they keep per layer beside the weights (e4m3 copies with a scale per row; e2m1 copies with a
+    scale per block of 32; 16-bit adapter operands)
     lives in the layer's `_LayerState` with the decode step's descriptors, is rebuilt when a source changed and on nothing
     else, and goes when the switch goes off.  With `lora` the adapter branch follows each of the four products UNMERGED -- on
     many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of csrc/lora_rows.hip
@@ -114,6 +115,12 @@ SWITCHES = (
     Switch("lora", "lora", "u2_fused_lora_inference", False, (), (), ("lora", "ads"),
            "the prefill, the continued prefill and the decode step take LoRA-wrapped projections with the adapters UNMERGED (a "
            "dropout that is the identity in the call; a merged or disabled wrapper counts as its base layer); `lora_stats`"),
+    Switch("fp4_decode", "fp4", "u2_fused_decode_fp4", False, (), (), ("w4",),
+           "a layer whose E, Hq D and I are multiples of 128 runs the decode step's four products on MXFP4 copies of its weights "
+           "(OCP e2m1 codes, one power-of-two scale per block of 32): a quarter of the weight bytes per step, a quarter of the "
+           "layer's weights again in HBM; exact on the quantised weights, the quantiser's cost in accuracy is unmeasured on trained "
+           "weights; with `fp8_decode` as well a layer takes e2m1 where it qualifies, else e4m3 where it qualifies, else 16 bits; "
+           "`w4_stats`, `w4_weights(layer)`"),
 )
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
@@ -124,6 +131,8 @@ stats = {"prefill": 0, "decode": 0, "padded_prefill": 0, "padded_decode": 0}
 extend_stats = {"extend": 0, "padded_extend": 0}
 # ... and the decode steps (counted in `stats` as well) that really ran on e4m3 weights (fp8_decode)
 w8_stats = {"decode": 0, "padded_decode": 0}
+# ... and those that ran on e2m1 weights (fp4_decode); a step moves the counter of the one form it ran in
+w4_stats = {"decode": 0, "padded_decode": 0}
 # ... and the decode steps (counted in `stats` as well) of more than 16 sequences (wide_decode), per layer call
 wide_stats = {"decode": 0, "padded_decode": 0}
 # ... and the layer calls of the no-grad routes (counted above as well) that computed at least one unmerged adapter (lora), per
@@ -135,13 +144,15 @@ _NO_PAD = ("none", None, None)   # the mask verdict of a call without padding (`
 
 
 def _count(st, how: str, B: int) -> None:
-    """One routed layer call (how: "prefill", "extend" or "decode") in the five dicts above."""
+    """One routed layer call (how: "prefill", "extend" or "decode") in the six dicts above."""
     stack = st.stack
     pad = stack.pad   # (a routed call: the verdict is a tuple)
     key = how if pad is _NO_PAD or pad[0] == "none" else "padded_" + how
     (extend_stats if how == "extend" else stats)[key] += 1
-    if how == "decode" and (B > 16 or stack.fp8):
-        if stack.fp8 and st.w8 is not None:
+    if how == "decode" and (B > 16 or stack.fp8 or stack.fp4):
+        if stack.fp4 and st.w4 is not None:
+            w4_stats[key] += 1
+        elif stack.fp8 and st.w8 is not None:   # (`_weight_form`: a layer keeps the copies of one form)
             w8_stats[key] += 1
         if B > 16:
             wide_stats[key] += 1
@@ -364,6 +375,7 @@ class _StackState:
     fp8: bool = False
     wide: bool = False
     lora: bool = False
+    fp4: bool = False
     pad: tuple = _NO_PAD       # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
     pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
     scratch: dict = field(default_factory=dict)
@@ -389,9 +401,10 @@ class _LoraOps:
 @dataclass(slots=True, eq=False)
 class _LayerState:
     """A patched layer: its original forward, its stack's state, its layout, and what the decode step keeps between calls: the
-    16-bit descriptor (`dec`), the optional e4m3 pairs (`w8`), the optional adapter operands (`lora`) and the DecodeLayer variants
-    built from them (`variants`: plain, e4m3, each with or without adapters -- `_decode_layer`), dropped together whenever one of
-    the three sources is rebuilt.  The ctypes structs and the references handed to the library live here."""
+    16-bit descriptor (`dec`), the optional e4m3 pairs (`w8`), the optional e2m1 pairs (`w4`), the optional adapter operands
+    (`lora`) and the DecodeLayer variants built from them (`variants`: plain, e4m3, each with or without adapters; `variants4`:
+    e2m1 without and with adapters -- `_decode_layer`), dropped together (`_drop_variants`) whenever one of the four sources is
+    rebuilt.  The ctypes structs and the references handed to the library live here."""
     orig: object
     stack: _StackState
     layout: type
@@ -400,6 +413,12 @@ class _LayerState:
     w8: tuple = None           # fp8_decode: (key, the four (W8, scale) pairs)
     lora: _LoraOps = None
     variants: list = field(default_factory=lambda: [None] * 4)
+    w4: tuple = None           # fp4_decode: (key, the four (codes, block scales) pairs)
+    variants4: list = field(default_factory=lambda: [None] * 2)
+
+
+def _drop_variants(st) -> None:
+    st.variants, st.variants4 = [None] * 4, [None] * 2
 
 
 def is_patched(layer) -> bool:
@@ -765,7 +784,7 @@ def _decode_state(self, B: int, device, pr):
                                Wo=p(Wo), bo=p(bo), w_post_norm=p(self.post_attention_layernorm.weight),
                                Wgu=p(Wgu), bgu=p(bgu), Wdown=p(Wdown), bdown=p(bdown))
         d = st.dec = _Decode16(key, ok, c, C.byref(c), lay, (Wqkv, bqkv, Wgu, bgu), (Hq + 2 * Hkv) * hd, Hkv, hd)
-        st.variants = [None] * 4
+        _drop_variants(st)
     # (per model, batch size AND stream: two generate() calls in flight on different streams must not share the step's scratch)
     stream = torch.cuda.current_stream(device).cuda_stream
     pool = st.stack.scratch
@@ -799,8 +818,37 @@ def _w8_state(st, d, pr) -> bool:
         Wqkv, _, Wgu, _ = d.keep
         lo = st.layout
         st.w8 = (key, tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1])))
-        st.variants = [None] * 4
+        _drop_variants(st)
     return True
+
+
+def _w4_state(st, d, pr) -> bool:
+    """fp4_decode: the MXFP4 copies of a layer's four packed decode weights (ops.quantize_blocks_fp4: e2m1 codes, an e8m0 scale per
+    block of 32) in st.w4; False for a layer they do not take (E, Hq D or I not a multiple of 128: the layer keeps the next form it
+    qualifies for).  Built, rebuilt and freed by the rules of `_w8_state` -- a quarter of the layer's weights again in HBM."""
+    c = d.cfg
+    if c.E % 128 or (c.Hq * c.D) % 128 or c.I % 128:
+        return False
+    key = tuple((m.weight.data_ptr(), m.weight._version) for m in pr)
+    if st.w4 is None or st.w4[0] != key:
+        Wqkv, _, Wgu, _ = d.keep
+        lo = st.layout
+        st.w4 = (key, tuple(ops.quantize_blocks_fp4(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1])))
+        _drop_variants(st)
+    return True
+
+
+def _weight_form(st, d, pr) -> int:
+    """The weight form of a layer's decode step under the stack's switches: 2 (e2m1) where fp4_decode is on and the layer
+    qualifies, else 1 (e4m3) where fp8_decode is on and it qualifies, else 0 (the element type).  Builds or refreshes the copies of
+    the form it returns; a copy of the other form a layer once built is dropped, so `_count` sees the one that ran."""
+    stack = st.stack
+    if stack.fp4 and _w4_state(st, d, pr):
+        st.w8 = None
+        return 2
+    if stack.fp8 and _w8_state(st, d, pr):
+        return 1
+    return 0
 
 
 def _op16(w, dtype, device):
@@ -832,7 +880,7 @@ def _lora_state(st, lo, pr, dtype, device) -> _LoraOps:
                 col0 += _base(pr[i]).out_features
             groups.append(tuple(segs))
         ls = st.lora = _LoraOps(key, tuple(groups), sum(len(g) for g in groups))
-        st.variants = [None] * 4
+        _drop_variants(st)
         lora_state_builds[0] += 1
     return ls
 
@@ -864,23 +912,32 @@ def _lora_scratch(ls, B: int, sc, h) -> None:
     desc.scratch, desc.scratch_bytes = buf.data_ptr(), buf.numel()
 
 
-def _decode_layer(st, fp8: bool, lora: bool):
-    """The reference to the step's u2tok_decode_layer: the 16-bit descriptor (st.dec) with, for fp8, codes and scales in place of the
-    four weights (norms and biases as the 16-bit step has them) and, for lora, the adapters' u2tok_decode_lora.  One variant per
-    combination, built on first use from the sources as they are now; a rebuilt source drops all four."""
-    i = fp8 + 2 * lora
-    v = st.variants[i]
+def _decode_layer(st, fp8: bool, lora: bool, fp4: bool = False):
+    """The step's u2tok_decode_layer as (struct, reference to it, config reference): the 16-bit descriptor (st.dec) with, for
+    fp8, codes and scales -- for fp4, e2m1 codes with the addresses of their block scales in the same four scale fields, and a
+    copy of the step's u2tok_decode_config that says so (wform = 2) -- in place of the four weights (norms and biases as the 16-bit
+    step has them) and, for lora, the adapters' u2tok_decode_lora.  One variant per combination, built on first use from the
+    sources as they are now; a rebuilt source drops all of them."""
+    vs, i = (st.variants4, int(lora)) if fp4 else (st.variants, fp8 + 2 * lora)
+    v = vs[i]
     if v is None:
         import ctypes as C
         from . import _lib
         lay = _lib.DecodeLayer.from_buffer_copy(st.dec.layer)
-        if fp8:
+        cfg, cfg_ref = st.dec.cfg, st.dec.cfg_ref
+        if fp4:
+            (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
+                (w.data_ptr(), s.data_ptr()) for w, s in st.w4[1])
+            cfg = _lib.DecodeConfig.from_buffer_copy(cfg)   # (the batch size is part of st.dec's key: a change rebuilds both)
+            cfg.wform = 2
+            cfg_ref = C.byref(cfg)
+        elif fp8:
             (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
                 (w.data_ptr(), s.data_ptr()) for w, s in st.w8[1])
         if lora:
             lay.lora = C.addressof(st.lora.desc)
-        v = st.variants[i] = (lay, C.byref(lay))
-    return v[1]
+        v = vs[i] = (lay, C.byref(lay), cfg_ref, cfg)
+    return v
 
 
 def w8_weights(layer):
@@ -888,6 +945,13 @@ def w8_weights(layer):
     (not patched, fp8_decode off, no qualifying step yet, a layer that keeps the 16-bit step)."""
     st = layer.__dict__.get("_u2_prefill")
     return None if st is None or st.w8 is None else st.w8[1]
+
+
+def w4_weights(layer):
+    """The four (codes uint8 (N, K / 2), block scales uint8 (N, K / 32)) pairs -- packed q|k|v, o, packed gate|up, down -- a patched
+    layer's e2m1 decode step reads, or None (not patched, fp4_decode off, no qualifying step yet, a layer that keeps another form)."""
+    st = layer.__dict__.get("_u2_prefill")
+    return None if st is None or st.w4 is None else st.w4[1]
 
 
 def _decode_step(self, x, pe, cache, window, pr):
@@ -902,7 +966,7 @@ def _decode_step(self, x, pe, cache, window, pr):
     B > 16 (the route's wide_decode switch): the same two calls; the library runs the four products on its 17 .. 64-row form of
     the few-rows kernel (csrc/gemm_rows.hip: the weights are still read once per step, and each block of 16 sequences gets the
     bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch.
-    fp8_decode / lora: the same two calls on another variant of the layer descriptor (`_decode_layer`); the adapter groups ride in
+    fp8_decode / fp4_decode / lora: the same two calls on another variant of the layer descriptor (`_decode_layer`); the adapter groups ride in
     the calls."""
     from . import _lib
     att = self.self_attn
@@ -911,7 +975,8 @@ def _decode_step(self, x, pe, cache, window, pr):
     if not d.ok:
         return None                                   # (the caller takes the stock layer)
     st = self._u2_prefill
-    fp8 = st.stack.fp8 and _w8_state(st, d, pr)   # (a bool either way: the index of the descriptor variant below)
+    form = _weight_form(st, d, pr)
+    fp4, fp8 = form == 2, form == 1   # (bools: the index of the descriptor variant below)
     ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
@@ -934,16 +999,16 @@ def _decode_step(self, x, pe, cache, window, pr):
             kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
         if ls is not None:
             _lora_scratch(ls, B, sc, h)
-        v = st.variants[fp8 + 2 * (ls is not None)]
-        layer_ref = v[1] if v is not None else _decode_layer(st, fp8, ls is not None)
-        _lib.check(h.u2tok_decoder_decode_pre(d.cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+        v = st.variants4[ls is not None] if fp4 else st.variants[fp8 + 2 * (ls is not None)]
+        _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, fp8, ls is not None, fp4)
+        _lib.check(h.u2tok_decoder_decode_pre(cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                                               int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
                                               vd.data_ptr(), kvs, kv.T0, ws, nws, stream), "u2tok_decoder_decode_pre")
         K, V, kvs = kv.views(kd, vd, kvs)
         kv.commit()
         _, kv_start, _ = st.stack.pad
         left = kv_start is not None   # a left-padded batch: the batched decode attention with each sequence's first visible position
-        _lib.check(h.u2tok_decoder_decode_post(d.cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
+        _lib.check(h.u2tok_decoder_decode_post(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
                                                K.shape[2], kvs, int(left or B > 16), kv_start.data_ptr() if left else None,
                                                out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
     return out
@@ -1020,14 +1085,16 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
-                         train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False) -> int:
+                         train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
+                         fp4_decode: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
     call sets all of them anew, so a switch that is not named goes back to its default, and what it kept per layer is freed.
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
-                 fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora)
+                 fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
+                 fp4_decode=fp4_decode)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
@@ -1058,7 +1125,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
                 if is_patched(layer):
                     for f in s.frees:
                         setattr(layer._u2_prefill, f, None)
-                    layer._u2_prefill.variants = [None] * 4
+                    _drop_variants(layer._u2_prefill)
     stack.pad, stack.pad_shape = _NO_PAD, None
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
