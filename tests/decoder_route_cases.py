@@ -1,5 +1,6 @@
 """The cases of tests/test_gpu_decoder_route_bits.py: every host route of the decoder layers (prefill, continued prefill, decode
-step, training; u2tokenizer_amd/prefill.py) on two-layer decoders, pinned BIT FOR BIT in tests/golden/decoder_route_bits.json: per
+step, training; u2tokenizer_amd/prefill.py) on two-layer decoders, pinned BIT FOR BIT in tests/golden/decoder_route_bits.json
+(and, the e2m1 decode step's, in tests/golden/decoder_route_bits_fp4.json): per
 case the SHA-256 of each call's last hidden state, of every layer's cached keys and values, of the training cases' gradients, and
 the deltas of the route counters -- the route taken as well as the numbers.  Importable without a GPU (the host half of the test
 checks the case list and the inputs).
@@ -12,7 +13,7 @@ of 128 with attention and MLP biases (no head norm, the unfused gate|up branch);
 96, sliding_window 16.  A prefill has 70 positions (two 64-key tiles, the second ragged), a continuation 9, then 3 decode steps;
 all inputs are seeded `inputs_embeds`, the decode steps (B, 1, E), so that lm_head stays out.
 
-`python tests/decoder_route_cases.py --record --commit HASH --out FILE` runs every case on the GPU and writes the fixture; the test
+`python tests/decoder_route_cases.py --record --commit HASH [--fp4] [--out FILE]` runs every case of one fixture on the GPU and writes the fixture; the test
 itself only ever reads it."""
 import argparse
 import hashlib
@@ -81,6 +82,30 @@ CASES = {
     "t-Q-train-lora": _case("Q", flags=dict(train_lora=True), lora=LORA_TARGETS, cache=None, train=True,
                             expect=("train.stats.layers", "train.lora_stats.adapters")),
 }
+# The e2m1 decode step (fp4_decode), in a fixture of its own (recorded at the commit that brought the form).  `counters`: the exact
+# deltas of w4_stats / w8_stats (layer calls: layers in that form x steps).  M = the three-layer stack of build_model.
+FP4_CASES = {
+    "u-Q-fp4-decode-B1": _case("Q", B=1, flags=dict(fp4_decode=True), steps=STEPS, expect=("stats.prefill", "w4_stats.decode")),
+    "u-Q-fp4-decode-left-padded": _case("Q", flags=dict(fp4_decode=True, padded=True), left=(0, 5), steps=STEPS,
+                                        expect=("stats.padded_prefill", "w4_stats.padded_decode")),
+    "u-Q-fp4-wide": _case("Q", B=17, flags=dict(fp4_decode=True, wide_decode=True), steps=2,
+                          expect=("stats.prefill", "w4_stats.decode", "wide_stats.decode")),
+    "u-Q-fp4-lora": _case("Q", flags=dict(fp4_decode=True, lora=True), lora=LORA_TARGETS, steps=STEPS,
+                          expect=("lora_stats.prefill", "lora_stats.decode", "w4_stats.decode")),
+    "u-M-fp4-fp8-mixed-stack": _case("M", flags=dict(fp4_decode=True, fp8_decode=True), steps=STEPS,
+                                     expect=("stats.prefill", "w4_stats.decode", "w8_stats.decode")),
+}
+FP4_COUNTERS = {
+    "u-Q-fp4-decode-B1": {"w4_stats.decode": 2 * STEPS},
+    "u-Q-fp4-decode-left-padded": {"w4_stats.padded_decode": 2 * STEPS},
+    "u-Q-fp4-wide": {"w4_stats.decode": 2 * 2},
+    "u-Q-fp4-lora": {"w4_stats.decode": 2 * STEPS},
+    "u-M-fp4-fp8-mixed-stack": {"w4_stats.decode": STEPS, "w8_stats.decode": STEPS},   # one layer each; the third keeps 16 bits
+}
+MIXED_INTER = (256, 320, 288)   # model M: a multiple of 128 (e2m1), of 64 only (e4m3), of 32 only (the element type)
+FIXTURE_FP4 = FIXTURE.with_name("decoder_route_bits_fp4.json")
+FIXTURES = {FIXTURE: CASES, FIXTURE_FP4: FP4_CASES}
+ALL_CASES = {**CASES, **FP4_CASES}
 # the test functions (a few seconds each): the cases by what they exercise
 GROUPS = {
     "plain": ("a-Q-prefill", "b-Q-prefill-decode", "c-Q-decode-stock-cache", "d-L-prefill", "d-L-prefill-decode", "e-Q-f16"),
@@ -92,10 +117,11 @@ GROUPS = {
     "lora": ("n-Q-lora", "o-Q-lora-fp8", "p-P-lora-packed-qkv", "q-Q-lora-merged-and-disabled"),
     "train": ("r-Q-train", "s-P-train-phi3", "t-Q-train-lora"),
 }
+FP4_GROUPS = {"fp4": tuple(FP4_CASES)}
 
 
-def case_ids():
-    return list(CASES)
+def case_ids(fixture=FIXTURE):
+    return list(FIXTURES[fixture])
 
 
 # ------------------------------------------------------------------------------------------------------------------ the inputs
@@ -105,7 +131,13 @@ def build_model(kind):
     from u2tokenizer_amd import synth
     common = dict(vocab_size=256, num_hidden_layers=2, intermediate_size=512, max_position_embeddings=512, tie_word_embeddings=False,
                   pad_token_id=0, bos_token_id=1, eos_token_id=2)
-    if kind == "Q":
+    if kind == "M":   # Qwen3 as Q with three layers whose MLPs have the inner sizes of MIXED_INTER: a stack of three weight forms
+        from transformers.models.qwen3.modeling_qwen3 import Qwen3MLP
+        cfg = Qwen3Config(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64, **{**common, "num_hidden_layers": 3})
+        m = Qwen3ForCausalLM(cfg)
+        for layer, inter in zip(m.model.layers, MIXED_INTER):
+            layer.mlp = Qwen3MLP(Qwen3Config(**{**cfg.to_dict(), "intermediate_size": inter}))
+    elif kind == "Q":
         m = Qwen3ForCausalLM(Qwen3Config(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64, **common))
     elif kind == "L":
         m = LlamaForCausalLM(LlamaConfig(hidden_size=256, num_attention_heads=2, num_key_value_heads=1, head_dim=128,
@@ -161,7 +193,8 @@ def _sha(t):
 
 def _counters():
     from u2tokenizer_amd import decoder_train, prefill
-    dicts = {"stats": prefill.stats, "extend_stats": prefill.extend_stats, "w8_stats": prefill.w8_stats, "wide_stats": prefill.wide_stats,
+    dicts = {"stats": prefill.stats, "extend_stats": prefill.extend_stats, "w8_stats": prefill.w8_stats, "w4_stats": prefill.w4_stats,
+             "wide_stats": prefill.wide_stats,
              "lora_stats": prefill.lora_stats, "train.stats": decoder_train.stats, "train.lora_stats": decoder_train.lora_stats}
     return {f"{n}.{k}": v for n, d in dicts.items() for k, v in d.items()}
 
@@ -170,7 +203,7 @@ def run_case(cid):
     """One case on the GPU -> {"digests": {what: SHA-256}, "stats": {counter: delta}}"""
     from transformers.cache_utils import DynamicCache
     from u2tokenizer_amd.prefill import disable_fused_prefill, enable_fused_prefill
-    c = CASES[cid]
+    c = ALL_CASES[cid]
     dev = "cuda"
     m = build_model(c["model"]).to(c["dtype"]).to(dev)
     if c["lora"]:
@@ -224,16 +257,19 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--record", action="store_true", help="run every case on the GPU and write the fixture")
     ap.add_argument("--commit", default="", help="the commit whose Python is recorded (written into the file)")
-    ap.add_argument("--out", default=str(FIXTURE))
+    ap.add_argument("--fp4", action="store_true", help="the cases of decoder_route_bits_fp4.json instead")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    fixture = FIXTURE_FP4 if a.fp4 else FIXTURE
+    a.out = a.out or str(fixture)
     if not a.record:
-        print(f"{len(CASES)} cases; --record writes their digests")
+        print(f"{len(FIXTURES[fixture])} cases; --record writes their digests")
         return 0
     sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
     from u2tokenizer_amd import ops
     ops.device_check()
     cases = {}
-    for cid in CASES:
+    for cid in FIXTURES[fixture]:
         cases[cid] = run_case(cid)
         print(cid, cases[cid]["stats"], flush=True)
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)

@@ -1,6 +1,7 @@
 """The decoder layers' host routes, BIT FOR BIT: every case of tests/decoder_route_cases.py -- prefill, continued prefill, decode
 steps and training on two-layer Qwen3, Llama and Phi-3 decoders, under every route switch -- against
-tests/golden/decoder_route_bits.json, recorded once (twice, with equal results) with the Python of the commit named inside it on
+tests/golden/decoder_route_bits.json (the e2m1 decode step's cases: decoder_route_bits_fp4.json, recorded likewise at the commit
+that brought that form), recorded once (twice, with equal results) with the Python of the commit named inside it on
 this build of the library, before prefill.py's routes were rewritten around one switch table, one admission function and one
 descriptor cache.  Per case: the SHA-256 of each call's last hidden state, of every layer's cached keys and values, of the
 training cases' output and gradients, and the deltas of the route counters.  The kernels and their order did not change, so a
@@ -18,19 +19,22 @@ import decoder_route_cases as C
 
 @pytest.fixture(scope="module")
 def fixture():
-    f = json.loads(C.FIXTURE.read_text())
-    assert len(f["recorded_at_commit"]) == 40
-    return f["cases"]
+    cases = {}
+    for path, ids in C.FIXTURES.items():
+        f = json.loads(path.read_text())
+        assert len(f["recorded_at_commit"]) == 40 and sorted(f["cases"]) == sorted(ids) == sorted(C.case_ids(path))
+        cases.update(f["cases"])
+    return cases
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("group", list(C.GROUPS))
+@pytest.mark.parametrize("group", list(C.GROUPS) + list(C.FP4_GROUPS))
 def test_route_bits(fixture, group):
     assert torch.cuda.is_available(), "these tests need the MI355X"
     from u2tokenizer_amd import ops
     ops.device_check()
     bad = {}
-    for cid in C.GROUPS[group]:
+    for cid in {**C.GROUPS, **C.FP4_GROUPS}[group]:
         got, want = C.run_case(cid), fixture[cid]
         moved = sorted(k for k in set(got["digests"]) | set(want["digests"]) if got["digests"].get(k) != want["digests"].get(k))
         if moved or got["stats"] != want["stats"]:
@@ -40,8 +44,11 @@ def test_route_bits(fixture, group):
 
 # ------------------------------------------------------------------------------------------------------------- host: cases and inputs
 def test_fixture_lists_exactly_the_cases(fixture):
-    assert sorted(fixture) == sorted(C.case_ids()) == sorted(c for g in C.GROUPS.values() for c in g)
-    for cid, c in C.CASES.items():
+    assert sorted(fixture) == sorted(C.ALL_CASES) == sorted(c for g in {**C.GROUPS, **C.FP4_GROUPS}.values() for c in g)
+    for cid, want in C.FP4_COUNTERS.items():                  # the e2m1 cases: the form each layer ran in, exactly
+        got = {k: v for k, v in fixture[cid]["stats"].items() if k.startswith(("w4_stats.", "w8_stats."))}
+        assert got == want, (cid, got)
+    for cid, c in C.ALL_CASES.items():
         f = fixture[cid]
         for counter in c["expect"]:                       # the route the case is about was taken when it was recorded
             assert f["stats"].get(counter, 0) > 0, (cid, counter)
@@ -60,9 +67,9 @@ def test_fixture_lists_exactly_the_cases(fixture):
 
 def test_inputs_are_what_the_cases_promise():
     assert C.S0 % 64 not in (0, C.S0) and C.S0 > 64                    # two key tiles, the second ragged
-    for cid, c in C.CASES.items():
+    for cid, c in C.ALL_CASES.items():
         x = C.embeds(c, "x_prefill", c["S"])
-        assert x.shape[0] == c["B"] and x.std() > 0.3 and not torch.equal(x[0], x[1])
+        assert x.shape[0] == c["B"] and x.std() > 0.3 and (c["B"] == 1 or not torch.equal(x[0], x[1]))
         for b, p in enumerate(c["left"] or ()):                        # pads where the case says, and not in every sequence
             m = C.mask(c, c["S"] + 3)
             assert (m[b, :p] == 0).all() and (m[b, p:] == 1).all()

@@ -1,14 +1,16 @@
 """The few-rows (weight-streaming) product, BIT FOR BIT: the SHA-256 of every case's output bytes against
 tests/golden/few_rows_bits.json, recorded once with the kernels of the commit named inside it (before csrc/rows.h and
-csrc/gemm_rows.hip replaced the three copies of this arithmetic).  Every other test of these kernels compares them with each
+csrc/gemm_rows.hip replaced the three copies of this arithmetic), and for e2m1 weights against tests/golden/few_rows_bits_e2m1.json,
+recorded with the commit that brought that form (before the weight form became a field of the kernels' arguments).  Every other test of these kernels compares them with each
 other or holds them to a float64 bound, so a change that moves all of them together -- a different contraction in the shared
 epilogue, another order of the partial sums -- passes there; here it does not.  A digest that moves is a changed bit: find the
 expression.  The fixture is never re-recorded by this file.
 
-Cases (tests/few_rows_cases.py): both builds x both weight forms x M in {1, 13, 16, 17, 33, 64} (NB = 1 .. 4 row blocks, ragged
-and full) x the (N, K) of SHAPES (NW = 4 / 8 / 16 waves, empty slices, remainder blocks, the seam between whole blocks and the
-remainder) x {plain, bias + residual through strided views, fp32 out, the pair form}; the plan's route (alpha, bias, GELU at
-M = 13) and the last rows of three big-tile products.  Together they reach all 48 instantiations of gemm_rows16_kernel.
+Cases (tests/few_rows_cases.py): both builds x three weight forms x M in {1, 13, 16, 17, 33, 64} (NB = 1 .. 4 row blocks, ragged
+and full) x the (N, K) of SHAPES / SHAPES_E2M1 (NW = 4 / 8 / 16 waves, empty slices, remainder blocks, the seam between whole
+blocks and the remainder; e2m1: one, 3, 16 and 64 quad steps) x {plain, bias + residual through strided views, fp32 out, the pair
+form}; the plan's route (alpha, bias, GELU at M = 13) and the last rows of three big-tile products.  Together they reach all 72
+instantiations of gemm_rows16_kernel.
 
 The host half (no GPU) checks that the inputs can tell two summation orders apart at all."""
 import json
@@ -30,9 +32,12 @@ def ops():
 
 @pytest.fixture(scope="module")
 def fixture():
-    f = json.loads(C.FIXTURE.read_text())
-    assert len(f["recorded_at_commit"]) == 40
-    return f["digests"]
+    digests = {}
+    for path in C.FIXTURES:
+        f = json.loads(path.read_text())
+        assert len(f["recorded_at_commit"]) == 40
+        digests.update(f["digests"])
+    return digests
 
 
 def _compare(got, fixture):
@@ -55,7 +60,10 @@ def test_plan_and_tail_bits(ops, fixture, elem):
 
 # ------------------------------------------------------------------------------------------------------------- host: the inputs
 def test_fixture_lists_exactly_the_cases():
-    assert sorted(json.loads(C.FIXTURE.read_text())["digests"]) == sorted(C.case_ids())
+    for path in C.FIXTURES:
+        assert sorted(json.loads(path.read_text())["digests"]) == sorted(C.case_ids(path))
+    ids = [k for path in C.FIXTURES for k in C.case_ids(path)]     # the union: every build x form x case, none twice
+    assert len(set(ids)) == len(ids) == sum(len(C.product_cases(f)) for f in C.FORMS) * len(C.DTYPES) + len(C.PLAN_CASES) * len(C.DTYPES)
 
 
 def test_inputs_are_what_the_case_file_promises():
@@ -75,6 +83,12 @@ def test_inputs_are_what_the_case_file_promises():
     share = torch.stack([((m >> b) & 1).float().mean() for b in range(23)])
     assert share.min() >= 0.4 and share.max() <= 0.6, share
     assert ((m & 0xFF) != 0).float().mean() >= 0.98
+    for N, K in C.SHAPES_E2M1:   # e2m1: every code in both nibbles, the block scales over 10 binades or more
+        codes, sc = C.weights_e2m1(N, K)
+        assert codes.shape == (N, K // 2) and sc.shape == (N, K // 32) and codes.dtype == sc.dtype == torch.uint8
+        for nib in (codes & 15, codes >> 4):                 # (-0, code 8, is the one code the quantiser never emits)
+            assert sorted(nib.unique().tolist()) == [c for c in range(16) if c != 8]
+        assert len(sc.unique()) >= 10
 
 
 def _sum_in_slices(x, w, nw, per, step, reverse):
@@ -99,11 +113,12 @@ def test_inputs_tell_two_summation_orders_apart(form):
     """Small integers would give the same fp32 sum in any order and hide a reordering.  For each K of the cases, 13 rows x 16
     columns: the sum over the kernel's K slices taken ascending and taken descending (fp32, on the CPU) differs in at least one
     output bit."""
-    w8 = form == "e4m3"
-    for N, K in C.SHAPES:
+    from u2tokenizer_amd import ops
+    for N, K in C.shapes(form):
         x = C.activations(K)[:13]
-        w = (C.weights_e4m3(N, K)[0].view(torch.float8_e4m3fn).float() if w8 else C.weights(N, K))[:16]
-        nw, per = C.slices(K, w8)
-        a = _sum_in_slices(x, w, nw, per, 64 if w8 else 32, False)
-        b = _sum_in_slices(x, w, nw, per, 64 if w8 else 32, True)
+        w = (C.weights_e4m3(N, K)[0].view(torch.float8_e4m3fn).float() if form == "e4m3"
+             else ops.dequantize_blocks_fp4(*C.weights_e2m1(N, K)) if form == "e2m1" else C.weights(N, K))[:16]
+        nw, per = C.slices(K, form=form)
+        a = _sum_in_slices(x, w, nw, per, C.STEP_K[form], False)
+        b = _sum_in_slices(x, w, nw, per, C.STEP_K[form], True)
         assert torch.isfinite(a).all() and (a != b).any(), (form, K)

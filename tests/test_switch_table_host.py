@@ -56,12 +56,12 @@ def test_keyword_alone_sets_its_field_and_what_it_implies(kw):
     st = m.model.layers[0]._u2_prefill
     for f in s.frees:
         setattr(st, f, ("kept",))
-    st.variants[0] = "kept"
+    st.variants[(0, False)] = "kept"
     prefill.enable_fused_prefill(m)
     assert _fields(m.model._u2_stack) == _expected(())
     for f in s.frees:
         assert getattr(st, f) is None
-    assert not s.frees or st.variants == [None] * 4    # (the descriptors built from it go with it)
+    assert not s.frees or st.variants == {}            # (the descriptors built from it go with it)
     prefill.disable_fused_prefill(m)
 
 

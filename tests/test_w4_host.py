@@ -337,9 +337,9 @@ def test_precedence_of_e2m1_over_e4m3_over_16_bits_per_layer(kind):
         assert prefill.w4_stats["decode"] == n4["decode"] + (want == 2) and prefill.w8_stats["decode"] == n8["decode"] + (want == 1)
         assert prefill.w4_stats["padded_decode"] == n4["padded_decode"] and prefill.w8_stats["padded_decode"] == n8["padded_decode"]
         # the switch goes off: the copies and the descriptors built from them go with it
-        st.variants4[0] = "kept"
+        st.variants[(2, False)] = "kept"
         prefill.enable_fused_prefill(m)
-        assert st.w4 is None and st.w8 is None and st.variants4 == [None] * 2 and st.variants == [None] * 4
+        assert st.w4 is None and st.w8 is None and st.variants == {}
         prefill.disable_fused_prefill(m)
 
 

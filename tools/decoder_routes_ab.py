@@ -7,7 +7,8 @@ Qwen3-8B layer shape with synthetic weights, and the microseconds `route` plus a
                                       [--pairs 3] [--rounds 3] [--layers 4] [--host-only]
 
 Cells: decode B = 1 and B = 8 at T = 1024 on append-in-place caches; B = 8 left-padded (padded); B = 1 fp8_decode; B = 32
-wide_decode; B = 1 lora (r = 16 on all seven projections); prefill B = 1, S = 1024; and `route_us`, which needs no GPU: a patched
+wide_decode; B = 1 lora (r = 16 on all seven projections); B = 1 fp4_decode; B = 32 fp4_decode + wide_decode; prefill B = 1,
+S = 1024; and `route_us`, which needs no GPU: a patched
 layer's forward on the decode route with `_decode_step` replaced by a stub, on the CPU with a tensor that reports `is_cuda`
 (--host-only runs this cell alone and opens no GPU anywhere).
 
@@ -38,6 +39,8 @@ DECODE_CELLS = {
     "decode_b1_fp8": (1, dict(fp8_decode=True), False, False),
     "decode_b32_wide": (32, dict(wide_decode=True), False, False),
     "decode_b1_lora": (1, dict(lora=True), False, True),
+    "decode_b1_fp4": (1, dict(fp4_decode=True), False, False),
+    "decode_b32_wide_fp4": (32, dict(fp4_decode=True, wide_decode=True), False, False),
 }
 GPU_CELLS = list(DECODE_CELLS) + ["prefill_b1_s1024"]
 HOST_CELL = "route_us"

@@ -323,86 +323,73 @@ size_t u2tok_decoder_decode_workspace_bytes(const u2tok_decode_config* c, int32_
   return dec_ok(c) && T > 0 ? decoder_decode_workspace_bytes(dec_cfg(c), T) : 0;
 }
 static_assert(sizeof(u2tok_decode_lora) == sizeof(DecodeLora) && sizeof(u2tok_lora_seg) == sizeof(LoraSeg), "one layout");
-// (wform = 2: the descriptor's four scale fields hold the e2m1 codes' block-scale bytes; a step in that form with none of them set
-//  must not be taken for a 16-bit one, whose weights are four times as long: `ok` says whether the descriptor may be used)
-static DecodeLayer dec_layer(const u2tok_decode_layer* l, const u2tok_decode_config* c, bool* ok) {
-  DecodeLayer d;
+// The one place that reads the ABI's spelling of a weight form: wform = 2 with all four scale fields set (the e2m1 codes' block-scale
+// bytes) is E2M1; wform = 0 with none set is ELEM, with all four set (fp32 row scales) E4M3; everything else is refused -- some of
+// the four set, and wform = 2 with none: a step of codes must not be taken for a 16-bit one, whose weights are four times as long.
+static int dec_args(const u2tok_decode_config* c, const u2tok_decode_layer* l, DecodeCfg& cfg, DecodeLayer& d) {
+  if (!dec_ok(c) || !l) return U2_ERR_ARG;
+  const int set = !!l->scale_qkv + !!l->scale_o + !!l->scale_gu + !!l->scale_down;
+  if ((set != 0 && set != 4) || (c->wform == 2 && set == 0)) return U2_ERR_ARG;
+  cfg = dec_cfg(c);
+  cfg.form = c->wform == 2 ? WForm::E2M1 : set ? WForm::E4M3 : WForm::ELEM;
   d.w_in_norm = BF(l->w_in_norm); d.Wqkv = l->Wqkv; d.bqkv = BF(l->bqkv); d.wq_norm = BF(l->wq_norm); d.wk_norm = BF(l->wk_norm);
   d.Wo = l->Wo; d.bo = BF(l->bo); d.w_post_norm = BF(l->w_post_norm);
   d.Wgu = l->Wgu; d.bgu = BF(l->bgu); d.Wdown = l->Wdown; d.bdown = BF(l->bdown);
+  d.scale_qkv = l->scale_qkv; d.scale_o = l->scale_o; d.scale_gu = l->scale_gu; d.scale_down = l->scale_down;
   d.lora = reinterpret_cast<const DecodeLora*>(l->lora);
-  *ok = true;
-  if (c->wform == 2) {
-    auto bytes = [](const float* p) { return reinterpret_cast<const uint8_t*>(p); };
-    d.scale_qkv = d.scale_o = d.scale_gu = d.scale_down = nullptr;
-    d.bscale_qkv = bytes(l->scale_qkv); d.bscale_o = bytes(l->scale_o); d.bscale_gu = bytes(l->scale_gu); d.bscale_down = bytes(l->scale_down);
-    *ok = l->scale_qkv && l->scale_o && l->scale_gu && l->scale_down;
-  } else {
-    d.scale_qkv = l->scale_qkv; d.scale_o = l->scale_o; d.scale_gu = l->scale_gu; d.scale_down = l->scale_down;
-  }
-  return d;
+  return U2_OK;
 }
 int u2tok_decoder_decode_pre(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* cos, const void* sin,
                              int32_t cos_sin_f32, int64_t cs_ld, void* qkv, void* k_cache, void* v_cache, int64_t kv_stride,
                              int32_t s_off, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  if (!dec_ok(c) || !l) return U2_ERR_ARG;
-  bool ok;
-  const DecodeLayer d = dec_layer(l, c, &ok);
-  if (!ok) return U2_ERR_ARG;
-  return decoder_decode_pre(dec_cfg(c), d, BF(x), cos, sin, cos_sin_f32, cs_ld, BFW(qkv), BFW(k_cache), BFW(v_cache),
-                            kv_stride, s_off, workspace, workspace_bytes, ST(stream));
+  DecodeCfg cfg;
+  DecodeLayer d;
+  const int e = dec_args(c, l, cfg, d);
+  if (e != U2_OK) return e;
+  return decoder_decode_pre(cfg, d, BF(x), cos, sin, cos_sin_f32, cs_ld, BFW(qkv), BFW(k_cache), BFW(v_cache), kv_stride, s_off,
+                            workspace, workspace_bytes, ST(stream));
 }
 int u2tok_decoder_decode_post(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* qkv, const void* K,
                               const void* V, int32_t T, int64_t kv_stride, int32_t batched, const int32_t* kv_start, void* out,
                               void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
-  if (!dec_ok(c) || !l) return U2_ERR_ARG;
-  bool ok;
-  const DecodeLayer d = dec_layer(l, c, &ok);
-  if (!ok) return U2_ERR_ARG;
-  return decoder_decode_post(dec_cfg(c), d, BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out),
-                             workspace, workspace_bytes, ST(stream));
+  DecodeCfg cfg;
+  DecodeLayer d;
+  const int e = dec_args(c, l, cfg, d);
+  if (e != U2_OK) return e;
+  return decoder_decode_post(cfg, d, BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out), workspace,
+                             workspace_bytes, ST(stream));
 }
-// ---- the few-rows product (gemm_rows.hip): scale set = e4m3 weights, null = weights in the element type
-static int rows(const void* A, const void* W, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
-                int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+// ---- the few-rows product (gemm_rows.hip): one filler for the four exports; a quantised form without its scales is refused here
+static int rows(WForm form, const void* A, const void* W, const void* scale, int64_t lds, void* C, const void* bias, const void* R,
+                int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+  if (form != WForm::ELEM && !scale) return U2_ERR_ARG;
   RowsArgs a;
-  a.A = BF(A); a.W = W; a.scale = scale; a.C = C; a.bias = BF(bias); a.R = BF(R);
-  a.M = M; a.N = N; a.K = K;
-  a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
-  a.flags = flags;
-  return gemm_rows(a, ST(stream));
-}
-static int rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
-                   int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
-  if (!scale) return U2_ERR_ARG;  // (no scale would mean 16-bit weights to gemm_rows)
-  return rows(A, W8, scale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
-}
-int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
-                       int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
-  if (M > 16) return U2_ERR_ARG;  // (this entry point keeps the range it was published with; 17 .. 64 rows: _wide)
-  return rows_w8(A, W8, scale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
-}
-int u2tok_gemm_rows_w8_wide(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
-                            int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
-                            u2tok_stream_t stream) {
-  return rows_w8(A, W8, scale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
-}
-// (e2m1 codes with e8m0 block scales: one entry for 1 .. 64 rows)
-int u2tok_gemm_rows_w4(const void* A, const void* W4, const uint8_t* S, void* C, const void* bias, const void* R, int32_t M, int32_t N,
-                       int32_t K, int64_t lda, int64_t ldw, int64_t lds, int64_t ldc, int64_t ldr, int32_t flags,
-                       u2tok_stream_t stream) {
-  if (!S) return U2_ERR_ARG;  // (no block scales would mean 16-bit weights to gemm_rows)
-  RowsArgs a;
-  a.A = BF(A); a.W = W4; a.bscale = S; a.C = C; a.bias = BF(bias); a.R = BF(R);
+  a.A = BF(A); a.W = W; a.scale = scale; a.form = form; a.C = C; a.bias = BF(bias); a.R = BF(R);
   a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.ldw = ldw; a.lds = lds; a.ldc = ldc; a.ldr = ldr;
   a.flags = flags;
   return gemm_rows(a, ST(stream));
 }
+int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                       int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+  if (M > 16) return U2_ERR_ARG;  // (this entry point keeps the range it was published with; 17 .. 64 rows: _wide)
+  return rows(WForm::E4M3, A, W8, scale, 0, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
+}
+int u2tok_gemm_rows_w8_wide(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M,
+                            int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags,
+                            u2tok_stream_t stream) {
+  return rows(WForm::E4M3, A, W8, scale, 0, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
+}
+// (e2m1 codes with e8m0 block scales: one entry for 1 .. 64 rows)
+int u2tok_gemm_rows_w4(const void* A, const void* W4, const uint8_t* S, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                       int32_t K, int64_t lda, int64_t ldw, int64_t lds, int64_t ldc, int64_t ldr, int32_t flags,
+                       u2tok_stream_t stream) {
+  return rows(WForm::E2M1, A, W4, S, lds, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
+}
 // (on element-type weights, outside u2tok_gemm_bf16's plan)
 int u2tok_gemm_rows(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K, int64_t lda,
                     int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
-  return rows(A, W, nullptr, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
+  return rows(WForm::ELEM, A, W, nullptr, 0, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
 }
 size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
   return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);

@@ -199,18 +199,16 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // step `generate` repeats up to 768 times per report is bound by the host's launch rate when every kernel is its own Python
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
-// One projection of the step: the element type's product through the plan, or -- `sc`: a scale per weight row, w = e4m3 codes
-// (a DecodeLayer with scales) -- the few-rows product on 1-byte weights (gemm_rows.hip), or -- `bs`: a scale byte per block of 32 k,
-// w = e2m1 codes (a DecodeLayer with block scales) -- on 4-bit weights.  pair: w = gate | up, y (rows, out / 2).
-static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const float* sc, const uint8_t* bs, const bf16_t* b, bf16_t* y,
+// One projection of the step on a weight (w, scale) in `form`: the element type's product through the plan, codes (the step's
+// DecodeCfg::form) through the few-rows product on 1-byte or 4-bit weights (gemm_rows.hip).  pair: w = gate | up, y (rows, out / 2).
+static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const void* scale, WForm form, const bf16_t* b, bf16_t* y,
                       int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
   RowsArgs a;
-  a.A = x; a.W = w; a.scale = sc; a.C = y; a.bias = b; a.R = R;
+  a.A = x; a.W = w; a.scale = scale; a.form = form; a.C = y; a.bias = b; a.R = R;
   a.M = rows; a.N = out; a.K = in;
-  a.lda = ldx; a.ldw = bs ? in >> 1 : in; a.ldc = ldy; a.ldr = ldr;
-  a.bscale = bs; a.lds = in >> 5;
+  a.lda = ldx; a.ldw = in / wform_facts(form).ldw_div; a.lds = in >> 5; a.ldc = ldy; a.ldr = ldr;
   a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-  if (sc || bs || rows > 16) return gemm_rows(a, st);
+  if (form != WForm::ELEM || rows > 16) return gemm_rows(a, st);
   GemmDesc g;  // 16-bit weights, M <= 16: the plan (the same kernel, or a tile kernel when rows16_ok says no)
   g.A = x; g.B = reinterpret_cast<const bf16_t*>(w); g.C = y; g.bias = b; g.R = R;
   g.M = rows; g.N = out; g.K = in;
@@ -230,28 +228,18 @@ static int dec_lora(const DecodeLora* lr, const LoraSeg* segs, int n, int nmax, 
                    reinterpret_cast<char*>(lr->scratch) + DECODE_LORA_U_BYTES, lr->scratch_bytes - DECODE_LORA_U_BYTES, check_only, st);
 }
 
-// What the e4m3 products ask of a step before anything is launched: a scale per product, K % 64 == 0 for all four, 16-byte
-// aligned weights, 4-byte aligned scales.
-static bool w8_step_ok(const DecodeCfg& c, const void* const* w, const float* const* sc, int n) {
-  if ((c.E & 63) || ((c.Hq * c.D) & 63) || (c.I & 63)) return false;
-  for (int i = 0; i < n; ++i)
-    if (!w[i] || !sc[i] || ((uintptr_t)w[i] & 15) || ((uintptr_t)sc[i] & 3)) return false;
-  return true;
-}
-
-// How many of a layer's four scales are set: 0 (weights in the element type) or 4 (e4m3 codes), anything between is refused
-static int scales_set(const DecodeLayer& l) { return !!l.scale_qkv + !!l.scale_o + !!l.scale_gu + !!l.scale_down; }
-
-// ... and of its four block-scale arrays: 0, or 4 (e2m1 codes) with no fp32 scale beside them
-static int bscales_set(const DecodeLayer& l) { return !!l.bscale_qkv + !!l.bscale_o + !!l.bscale_gu + !!l.bscale_down; }
-
-// What the e2m1 products ask of a step before anything is launched: all four block-scale arrays and none of the fp32 scales, K % 128
-// == 0 for all four, 16-byte aligned weights (the n of `w` this half reads).
-static bool w4_step_ok(const DecodeCfg& c, const DecodeLayer& l, const void* const* w, int n) {
-  if (bscales_set(l) != 4 || scales_set(l) != 0) return false;
-  if ((c.E & 127) || ((c.Hq * c.D) & 127) || (c.I & 127)) return false;
-  for (int i = 0; i < n; ++i)
-    if (!w[i] || ((uintptr_t)w[i] & 15)) return false;
+// What a quantised form asks of a step before anything is launched (WFormFacts): E, Hq D and I multiples of the form's step, and of
+// the n products from `first` on (q|k|v, o, gate|up, down: the ones this half runs) 16-byte aligned codes and a scale aligned to
+// its type.  The element type's products check themselves.
+static bool wform_step_ok(const DecodeCfg& c, const DecodeLayer& l, int first, int n) {
+  if (!wform_known(c.form)) return false;
+  if (c.form == WForm::ELEM) return true;
+  const WFormFacts& f = wform_facts(c.form);
+  if (c.E % f.k_mult || (c.Hq * c.D) % f.k_mult || c.I % f.k_mult) return false;
+  const void* const w[4] = {l.Wqkv, l.Wo, l.Wgu, l.Wdown};
+  const void* const sc[4] = {l.scale_qkv, l.scale_o, l.scale_gu, l.scale_down};
+  for (int i = first; i < first + n; ++i)
+    if (!w[i] || !sc[i] || ((uintptr_t)w[i] & 15) || (uintptr_t)sc[i] % f.scale_align) return false;
   return true;
 }
 
@@ -270,10 +258,7 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
                        int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
                        hipStream_t st) {
   if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
-  const int ns = scales_set(l);
-  if (bscales_set(l) != 0) {
-    if (!w4_step_ok(c, l, &l.Wqkv, 1)) return U2_ERR_ARG;
-  } else if (ns != 0 && (ns != 4 || !w8_step_ok(c, &l.Wqkv, &l.scale_qkv, 1))) return U2_ERR_ARG;
+  if (!wform_step_ok(c, l, 0, 1)) return U2_ERR_ARG;
   if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
@@ -282,7 +267,7 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
   if (e != U2_OK) return e;
   e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, l.bscale_qkv, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
+  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
   if (e != U2_OK) return e;
   if (lr) e = dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, false, st);   // (before the head norm and the rotary embedding)
   if (e != U2_OK) return e;
@@ -301,15 +286,7 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
       !ws)
     return U2_ERR_ARG;
   if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
-  const int ns = scales_set(l);
-  if (bscales_set(l) != 0) {  // (the e2m1 products, likewise)
-    const void* w[3] = {l.Wo, l.Wgu, l.Wdown};
-    if (!w4_step_ok(c, l, w, 3)) return U2_ERR_ARG;
-  } else if (ns != 0) {  // (the e4m3 products: everything they ask is checked here, before the attention is launched)
-    const void* w[3] = {l.Wo, l.Wgu, l.Wdown};
-    const float* s3[3] = {l.scale_o, l.scale_gu, l.scale_down};
-    if (ns != 4 || !w8_step_ok(c, w, s3, 3)) return U2_ERR_ARG;
-  }
+  if (!wform_step_ok(c, l, 1, 3)) return U2_ERR_ARG;  // (everything the quantised products ask, before the attention is launched)
   if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
   bf16_t* p = reinterpret_cast<bf16_t*>(ws);
@@ -345,7 +322,7 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     const int e = attention(a, st);
     if (e != U2_OK) return e;
   }
-  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, l.bscale_o, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
+  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
   if (e != U2_OK) return e;
   if (lr) e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, false, st);   // (after the residual epilogue: the same terms)
   if (e != U2_OK) return e;
@@ -353,17 +330,17 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
   if (e != U2_OK) return e;
   const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
   if (!gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bscale_gu, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, l.bscale_gu, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
+    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
     if (e != U2_OK) return e;
     if (gu_lora) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, false, st);
     if (e != U2_OK) return e;
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  e = dec_linear(act, c.I, l.Wdown, l.scale_down, l.bscale_down, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
+  e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
   if (e != U2_OK || !lr) return e;
   return dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, false, st);
 }

@@ -1,4 +1,4 @@
-// The few-rows (weight-streaming) product: 1 .. 64 rows against N x K weights, in three weight forms (rows.h: WForm) -- the element
+// The few-rows (weight-streaming) product: 1 .. 64 rows against N x K weights, in three weight forms (kernels.h: WForm) -- the element
 // type, e4m3 codes with one fp32 scale per weight row (the decode step's four products read half the bytes; DESIGN f3: the step is
 // bound by them), and OCP MXFP4: e2m1 codes with one e8m0 scale per block of 32 k, a quarter of the bytes, widened with their scale
 // by one conversion instruction per pair (DESIGN f11).  Weight-only: activations stay in the element type, the MFMA is the element
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_mi
 #pragma unroll
   for (int b = 0; b < NB; ++b) xp[b] = a.A + (int64_t)min(16 * b + l15, a.M - 1) * a.lda + g * GE;
   f32x4 acc[NB];
-  if constexpr (W4) rows_slice<NB, F>(wp, xp, s0, s1, acc, a.bscale + (int64_t)wrow(l15) * a.lds + g);
+  if constexpr (W4) rows_slice<NB, F>(wp, xp, s0, s1, acc, reinterpret_cast<const uint8_t*>(a.scale) + (int64_t)wrow(l15) * a.lds + g);
   else rows_slice<NB, F>(wp, xp, s0, s1, acc);
   // lane holds C[m = 16 b + l15][column 4 g + r of the workgroup's 16] of every block b
 #pragma unroll
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_mi
   if constexpr (PAIR) {  // (all 64 lanes: lanes of rows >= M carry copies of row M - 1 and write nothing)
     auto mult = [&](int r) {
       const int c = 4 * g + r;  // (wrow(c) written out: through the nested lambda <4, 4, true, true> takes 8 more VGPRs and loses a wave)
-      if constexpr (W8) return a.scale[min((c < 8 ? 0 : I2) + (int)blockIdx.x * 8 + (c & 7), a.N - 1)];
+      if constexpr (W8) return reinterpret_cast<const float*>(a.scale)[min((c < 8 ? 0 : I2) + (int)blockIdx.x * 8 + (c & 7), a.N - 1)];
       else if constexpr (W4) return 1.f;  // (the block scales went in with the conversion)
       else return a.alpha;
     };
@@ -75,34 +75,32 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_mi
   }
   if constexpr (W8) {  // the scaled sum is an fp32 value of its own before the epilogue sees it (alpha = 1 there)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] *= a.scale[wrow(4 * g + r)];
+    for (int r = 0; r < 4; ++r) v[r] *= reinterpret_cast<const float*>(a.scale)[wrow(4 * g + r)];
   }
   RowsEpi e = a;
   if constexpr (W8 || W4 || NB > 1) e.alpha = e.alpha_lo = 1.f, e.nsplit = 0;  // (only a plan's step, 16-bit and M <= 16, sets them: constants here)
   rows_store(e, v, m, n0 + 4 * g, reinterpret_cast<char*>(a.C), a.R);
 }
 
-// What gemm_rows accepts: one function for all weight forms (a.scale set: e4m3 codes; a.bscale set: e2m1 codes; both: refused).
+// What gemm_rows accepts: one function for all weight forms, the per-form numbers from WFormFacts (kernels.h).
 int gemm_rows_check(const RowsArgs& a) {
-  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr, w4 = a.bscale != nullptr;
-  if (w8 && w4) return U2_ERR_ARG;
-  if (!a.A || !a.W || !a.C || a.M <= 0 || a.M > 64 || a.N <= 0 || a.K <= 0 || (a.K & (w4 ? 127 : w8 ? 63 : 31))) return U2_ERR_ARG;
+  if (!wform_known(a.form)) return U2_ERR_ARG;
+  const WFormFacts& f = wform_facts(a.form);
+  const bool pair = a.flags & GEMM_SWIGLU;
+  if (!a.A || !a.W || !a.C || a.M <= 0 || a.M > 64 || a.N <= 0 || a.K <= 0 || a.K % f.k_mult) return U2_ERR_ARG;
   if (a.flags & ~(GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_SWIGLU)) return U2_ERR_ARG;
   if (pair && (a.flags != GEMM_SWIGLU || (a.N & 15))) return U2_ERR_ARG;  // gate | up: N = 2 I, I % 8 == 0
   if (((a.flags & GEMM_BIAS_N) && !a.bias) || ((a.flags & GEMM_RESIDUAL) && (!a.R || a.ldr < a.N))) return U2_ERR_ARG;
-  if (a.lda < a.K || (a.lda & 7) || a.ldw < (w4 ? a.K >> 1 : a.K) || (a.ldw & (w8 || w4 ? 15 : 7)) || a.ldc < (pair ? a.N >> 1 : a.N))
-    return U2_ERR_ARG;
-  if (w4 && a.lds < (a.K >> 5)) return U2_ERR_ARG;
-  if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) || ((uintptr_t)a.scale & 3) || ((uintptr_t)a.C & ((a.flags & GEMM_OUT_F32) ? 3 : 1)))
-    return U2_ERR_ARG;
+  if (a.lda < a.K || (a.lda & 7) || a.ldw < a.K / f.ldw_div || a.ldw % f.ldw_mult || a.ldc < (pair ? a.N >> 1 : a.N)) return U2_ERR_ARG;
+  if (f.scale_bytes && (!a.scale || (uintptr_t)a.scale % f.scale_align || (f.scale_k && a.lds < a.K / f.scale_k))) return U2_ERR_ARG;
+  if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) || ((uintptr_t)a.C & ((a.flags & GEMM_OUT_F32) ? 3 : 1))) return U2_ERR_ARG;
   return U2_OK;
 }
 
 int gemm_rows_launch(const RowsArgs& a, hipStream_t stream) {
   const bool pair = a.flags & GEMM_SWIGLU;
-  const int form = a.bscale ? 2 : a.scale ? 1 : 0;  // (WForm)
   const int nb = (a.M + 15) >> 4;
-  const int nw = rows16_slices(a.K >> (5 + form));  // from the (double, quad) steps alone, whatever M: the contract
+  const int nw = rows16_slices(a.K / wform_facts(a.form).k_mult);  // from the (double, quad) steps alone, whatever M: the contract
   // the 72 instantiations: [WForm][PAIR][NW = 16, 8, 4][NB - 1]
 #define ROWS_NB(NW, PAIR, F) \
   {gemm_rows16_kernel<NW, 1, PAIR, F>, gemm_rows16_kernel<NW, 2, PAIR, F>, gemm_rows16_kernel<NW, 3, PAIR, F>, gemm_rows16_kernel<NW, 4, PAIR, F>}
@@ -112,17 +110,18 @@ int gemm_rows_launch(const RowsArgs& a, hipStream_t stream) {
 #undef ROWS_FORM
 #undef ROWS_NB
   const dim3 grid((unsigned)(pair ? cdiv(a.N >> 1, 8) : cdiv(a.N, 16)));
-  hipLaunchKernelGGL(k[form][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
+  hipLaunchKernelGGL(k[(int)a.form][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
   return launch_status();
 }
 
 int gemm_rows(const RowsArgs& a, hipStream_t stream) {
   const int e = gemm_rows_check(a);
   if (e != U2_OK) return e;
-  const bool pair = a.flags & GEMM_SWIGLU, w8 = a.scale != nullptr, w4 = a.bscale != nullptr;
+  const WFormFacts& f = wform_facts(a.form);
+  const bool pair = a.flags & GEMM_SWIGLU;
   const double out_b = pair ? 2.0 * a.M * (a.N >> 1) : ((a.flags & GEMM_OUT_F32) ? 4.0 : 2.0) * a.M * a.N;
   ProfScope ps(PROF_GEMM, 2.0 * a.M * a.N * a.K, stream,
-               2.0 * a.M * a.K + (w4 ? 0.5 : w8 ? 1.0 : 2.0) * a.N * a.K + (w8 ? 4.0 * a.N : w4 ? (double)a.N * (a.K >> 5) : 0.0) + out_b +
+               2.0 * a.M * a.K + f.w_bytes * a.N * a.K + (double)f.scale_bytes * a.N * (f.scale_k ? a.K / f.scale_k : 1) + out_b +
                    ((a.flags & GEMM_RESIDUAL) ? 2.0 * a.M * a.N : 0.0));
   return gemm_rows_launch(a, stream);
 }

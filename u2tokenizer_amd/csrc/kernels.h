@@ -101,9 +101,26 @@ void gemm_plan_format(const GemmPlan& p, char* buf, size_t n);  // " | <kernel> 
 int gemm_skinny_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);  // gemm_skinny.hip
 int gemm_bt_launch(const GemmDesc& d, const GemmStep& s, hipStream_t stream);      // gemm_bt.hip
 
+// The form of a weight operand: the element type, e4m3 codes with an fp32 scale per row, e2m1 codes (two per byte, even k in the
+// low nibble) with an e8m0 scale byte per block of 32 k.  Decided once at the C boundary (capi.hip), then carried: RowsArgs::form,
+// DecodeCfg::form.  What a form asks of a product and of a decode step, and what it reads:
+struct WFormFacts {
+  int k_mult;        // K (the step's E, Hq D and I) is a multiple of it: the k of one step of the K loop (rows.h)
+  int ldw_div;       // a weight row is K / ldw_div units of ldw: bytes with codes, else elements
+  int ldw_mult;      // ... and ldw a multiple of it (16-byte aligned rows)
+  int scale_align;   // bytes
+  double w_bytes;    // per weight (the profiler's byte count)
+  int scale_bytes;   // per scale; 0: the form has none
+  int scale_k;       // k per scale (lds >= K / scale_k); 0: one per row
+};
+enum class WForm : int { ELEM = 0, E4M3 = 1, E2M1 = 2 };
+constexpr WFormFacts WFORM_FACTS[3] = {{32, 1, 8, 1, 2.0, 0, 0}, {64, 1, 16, 4, 1.0, 4, 0}, {128, 2, 16, 1, 0.5, 1, 32}};
+constexpr bool wform_known(WForm f) { return (unsigned)f <= (unsigned)WForm::E2M1; }
+constexpr const WFormFacts& wform_facts(WForm f) { return WFORM_FACTS[(int)f]; }
+
 // The few-rows (weight-streaming) product (gemm_rows.hip; arithmetic: rows.h): C = epilogue(A . W^T) for 1 <= M <= 64 rows on
-// weights in the element type (K % 32 == 0) or, with `scale` set, C = epilogue(scale[n] * A . e4m3(W)^T) on e4m3 codes
-// (K % 64 == 0); 16-byte aligned A / W rows.  Each block of 16 rows has the bits of the M <= 16 product on it.
+// weights in the element type, C = epilogue(scale[n] * A . e4m3(W)^T) on e4m3 codes, C = epilogue(A . (e2m1(W) 2^(scale - 127))^T)
+// on e2m1 codes; 16-byte aligned A / W rows.  Each block of 16 rows has the bits of the M <= 16 product on it.
 struct RowsEpi {                 // what the epilogue of a lane's 4 columns reads (rows.h: rows_store)
   const bf16_t* bias = nullptr;  // [N] (GEMM_BIAS_N) or [M] (GEMM_BIAS_M)
   int N = 0, flags = 0;
@@ -113,15 +130,14 @@ struct RowsEpi {                 // what the epilogue of a lane's 4 columns read
 };
 struct RowsArgs : RowsEpi {
   const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
-  const void* W = nullptr;       // [N][K], leading dim ldw: e4m3 codes and bytes when `scale` is set, e2m1 codes (two per byte, even k
-                                 // in the low nibble) and bytes when `bscale` is set, else elements of the element type
-  const float* scale = nullptr;  // [N], or null: not e4m3 weights
+  const void* W = nullptr;       // [N][K] in `form`, leading dim ldw (WFormFacts)
+  const void* scale = nullptr;   // E4M3: [N] fp32; E2M1: [N][K / 32] e8m0 bytes (2^(e - 127)), lds bytes between rows; ELEM: ignored
   void* C = nullptr;             // [M][N] elements or fp32 (GEMM_OUT_F32); [M][N / 2] elements with GEMM_SWIGLU
   const bf16_t* R = nullptr;     // [M][N], leading dim ldr (GEMM_RESIDUAL)
   int M = 0, K = 0;
   int64_t lda = 0, ldw = 0;
-  const uint8_t* bscale = nullptr;  // [N][K / 32] e8m0 block scales (2^(e - 127) for 32 consecutive k of a row), lds bytes between rows,
-  int64_t lds = 0;                  // or null: not e2m1 weights (behind every older field: those keep their kernel-argument offsets)
+  WForm form = WForm::ELEM;      // (the kernels are instantiated per form and do not read it)
+  int64_t lds = 0;
 };
 // gemm_rows: the product outside the plan -- what the decode step calls directly (the plan of an M = 17 .. 64 product is a tile
 // kernel's, pinned for the training path): flags GEMM_BIAS_N | GEMM_RESIDUAL | GEMM_OUT_F32 or GEMM_SWIGLU alone, alpha = 1 and no
@@ -330,10 +346,8 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
   int B, E, Hq, Hkv, D, I;
   float eps, qk_eps, scale;
+  WForm form = WForm::ELEM;  // of the layer's four W*
 };
-// A layer's decode-step parameters (u2tok_decode_layer).  No scale set: the four W* are in the element type; all four set: they
-// are e4m3 codes with a scale per weight row (gemm_rows.hip), which asks E, Hq * D and I multiples of 64, 16-byte aligned weights
-// and 4-byte aligned scales.  Some set: U2_ERR_ARG, like every other refusal before anything is launched.
 // One segment of a few-rows adapter group (lora_rows.hip; the layout of u2tok_lora_seg): A (r, K) and B (N, r) contiguous, the
 // segment's columns [col0, col0 + N) of the product it is added to
 struct LoraSeg {
@@ -354,13 +368,17 @@ struct DecodeLora {
   size_t scratch_bytes;
 };
 constexpr size_t DECODE_LORA_U_LD = 192, DECODE_LORA_U_BYTES = 64 * DECODE_LORA_U_LD * sizeof(bf16_t);
+// A layer's decode-step parameters, in the form DecodeCfg::form names (capi.hip decodes u2tok_decode_layer into it).  ELEM: the four
+// W* are in the element type and the scales are not read.  E4M3: codes with an fp32 scale per weight row.  E2M1: codes with an
+// e8m0 scale byte per block of 32 (gemm_rows.hip).  The quantised forms ask E, Hq * D and I multiples of 64 / 128, 16-byte aligned
+// weights and all four scales, aligned to their type (WFormFacts): U2_ERR_ARG otherwise, like every other refusal before anything
+// is launched.
 struct DecodeLayer {
   const void *Wqkv, *Wo, *Wgu, *Wdown;
   const bf16_t *w_in_norm, *bqkv, *wq_norm, *wk_norm;  // first half
   const bf16_t *bo, *w_post_norm, *bgu, *bdown;        // second half
-  const float *scale_qkv, *scale_o, *scale_gu, *scale_down;
+  const void *scale_qkv, *scale_o, *scale_gu, *scale_down;
   const DecodeLora* lora = nullptr;                    // unmerged adapters (NULL: none)
-  const uint8_t *bscale_qkv = nullptr, *bscale_o = nullptr, *bscale_gu = nullptr, *bscale_down = nullptr;  // e2m1 block scales (the C ABI carries them in its scale fields under wform = 2: capi.hip)
 };
 size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T);
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,

@@ -48,9 +48,6 @@ namespace u2 {
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-// The form of the weight operand: the element type, e4m3 codes with a scale per row, e2m1 codes with a scale per block of 32
-enum class WForm : int { ELEM = 0, E4M3 = 1, E2M1 = 2 };
-
 // 8 e4m3 codes (two dwords, ascending k) -> one MFMA fragment of 8 elements: v_cvt_pk_f32_fp8 x 4, the element type's pack x 4
 __device__ __forceinline__ bf16x8 w8_widen(uint32_t lo, uint32_t hi) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -825,13 +825,18 @@ def snap_fp4_(module):
     return module
 
 
-def _rows_call(who, a, N, bias, residual, out_f32, swiglu, out):
-    """What gemm_rows, gemm_rows_w8 and gemm_rows_w4 share: A as (M, K) rows with unit column stride, `out`, the flags, the residual and its
-    row stride -> (a2, out, bias, ldr, flags) for a weight of N rows"""
+def _rows_call(export, a, w_ops, ldw, N, bias, residual, out_f32, swiglu, out):
+    """What gemm_rows, gemm_rows_w8 and gemm_rows_w4 share: A as (M, K) rows with unit column stride, `out`, the flags, the residual
+    and its row stride, then the call of `export` (a u2tok_gemm_rows* name, or a function of M that gives one) for a weight of N
+    rows with the form's operands `w_ops` (the weight, then its scales) and leading dimensions `ldw` (ldw, then lds) in their
+    places, and its status -> out"""
+    who = (export if isinstance(export, str) else export(1))[len("u2tok_"):]   # (the wrapper's name, for its messages)
+    h = _lib.load_library()
+    _need(a, ELEM, "A")
     a2 = a.reshape(-1, a.shape[-1])
     if a2.stride(1) != 1:
         a2 = a2.contiguous()
-    M, cols = a2.shape[0], N // 2 if swiglu else N
+    (M, K), cols = a2.shape, N // 2 if swiglu else N
     if out is None:
         out = torch.empty((M, cols), dtype=torch.float32 if out_f32 else elem_dtype(), device=a.device)
     if out.shape != (M, cols) or out.stride(1) != 1 or out.dtype != (torch.float32 if out_f32 else elem_dtype()):
@@ -847,7 +852,11 @@ def _rows_call(who, a, N, bias, residual, out_f32, swiglu, out):
         if residual.shape != (M, N) or residual.stride(1) != 1:
             raise RuntimeError(f"{who}: residual must be (M, N) with unit column stride")
         ldr = residual.stride(0)
-    return a2, out, bias, ldr, flags
+    name = export if isinstance(export, str) else export(M)
+    st = getattr(h, name)(_ptr(a2), *map(_ptr, w_ops), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), *ldw,
+                          out.stride(0), ldr, flags, _stream())
+    _lib.check(st, name)
+    return out
 
 
 @_guarded
@@ -857,22 +866,15 @@ def gemm_rows_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, *, bias
     (u2tok_gemm_rows_w8, for M > 16 u2tok_gemm_rows_w8_wide: the decode step's weight-streaming product on 1-byte weights, fp32
     accumulation; each block of 16 rows has the bits of the M <= 16 product on it).  swiglu: w8 = gate
     rows | up rows -> (M, N / 2) = silu(gate) * up.  `out` / `residual` may be row-strided views (unit column stride)."""
-    h = _lib.load_library()
-    _need(a, ELEM, "A")
     if w8.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32 or not w8.is_cuda or not scale.is_cuda:
         raise RuntimeError("gemm_rows_w8: expected float8_e4m3fn weights and fp32 scales on the GPU")
     w8, scale = w8.contiguous(), scale.contiguous()
-    N = w8.shape[0]
-    if w8.shape[1] != a.shape[-1] or scale.numel() != N:
-        raise RuntimeError(f"gemm_rows_w8: shapes A {tuple(a.reshape(-1, a.shape[-1]).shape)}, W8 {tuple(w8.shape)}, "
+    N, K = w8.shape[0], a.shape[-1]
+    if w8.shape[1] != K or scale.numel() != N:
+        raise RuntimeError(f"gemm_rows_w8: shapes A {tuple(a.reshape(-1, K).shape)}, W8 {tuple(w8.shape)}, "
                            f"scale {tuple(scale.shape)}")
-    a2, out, bias, ldr, flags = _rows_call("gemm_rows_w8", a, N, bias, residual, out_f32, swiglu, out)
-    M, K = a2.shape
-    name = "u2tok_gemm_rows_w8_wide" if M > 16 else "u2tok_gemm_rows_w8"
-    st = getattr(h, name)(_ptr(a2), _ptr(w8), _ptr(scale), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), K,
-                          out.stride(0), ldr, flags, _stream())
-    _lib.check(st, name)
-    return out
+    return _rows_call(lambda M: "u2tok_gemm_rows_w8_wide" if M > 16 else "u2tok_gemm_rows_w8", a, (w8, scale), (K,), N, bias,
+                      residual, out_f32, swiglu, out)
 
 
 @_guarded
@@ -882,8 +884,6 @@ def gemm_rows_w4(a: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, *, 
     (N, K / 32) uint8, K % 128 == 0 (u2tok_gemm_rows_w4: the decode step's weight-streaming product on 4-bit weights, fp32
     accumulation; each block of 16 rows has the bits of the M <= 16 product on it).  swiglu: codes = gate rows | up rows ->
     (M, N / 2) = silu(gate) * up.  `out` / `residual` may be row-strided views (unit column stride)."""
-    h = _lib.load_library()
-    _need(a, ELEM, "A")
     if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or not codes.is_cuda or not scales.is_cuda:
         raise RuntimeError("gemm_rows_w4: expected uint8 codes and uint8 block scales on the GPU")
     codes, scales = codes.contiguous(), scales.contiguous()
@@ -891,12 +891,7 @@ def gemm_rows_w4(a: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, *, 
     if codes.dim() != 2 or scales.shape != (N, K // 32) or codes.shape[1] * 2 != K:
         raise RuntimeError(f"gemm_rows_w4: shapes A {tuple(a.reshape(-1, K).shape)}, codes {tuple(codes.shape)}, "
                            f"scales {tuple(scales.shape)}")
-    a2, out, bias, ldr, flags = _rows_call("gemm_rows_w4", a, N, bias, residual, out_f32, swiglu, out)
-    M = a2.shape[0]
-    st = h.u2tok_gemm_rows_w4(_ptr(a2), _ptr(codes), _ptr(scales), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0),
-                              K // 2, K // 32, out.stride(0), ldr, flags, _stream())
-    _lib.check(st, "u2tok_gemm_rows_w4")
-    return out
+    return _rows_call("u2tok_gemm_rows_w4", a, (codes, scales), (K // 2, K // 32), N, bias, residual, out_f32, swiglu, out)
 
 
 @_guarded
@@ -906,19 +901,12 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, out
     directly (u2tok_gemm_rows) instead of through the plan of `gemm`: M <= 16 the kernel the plan picks, 16 < M <= 64 the
     multi-block kernel whose every block of 16 rows has the bits of the M <= 16 product on it.  K % 32 == 0.  swiglu: w = gate
     rows | up rows -> (M, N / 2) = silu(gate) * up.  `w`, `out` and `residual` may be row-strided views (unit column stride)."""
-    h = _lib.load_library()
-    _need(a, ELEM, "A"), _need(w, ELEM, "W")
+    _need(w, ELEM, "W")
     if w.dim() != 2 or w.stride(1) != 1:
         w = w.contiguous()
-    N = w.shape[0]
     if w.shape[1] != a.shape[-1]:
         raise RuntimeError(f"gemm_rows: shapes A {tuple(a.reshape(-1, a.shape[-1]).shape)}, W {tuple(w.shape)}")
-    a2, out, bias, ldr, flags = _rows_call("gemm_rows", a, N, bias, residual, out_f32, swiglu, out)
-    M, K = a2.shape
-    st = h.u2tok_gemm_rows(_ptr(a2), _ptr(w), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), w.stride(0),
-                           out.stride(0), ldr, flags, _stream())
-    _lib.check(st, "u2tok_gemm_rows")
-    return out
+    return _rows_call("u2tok_gemm_rows", a, (w,), (w.stride(0),), w.shape[0], bias, residual, out_f32, swiglu, out)
 
 
 # ---------------------------------------------------------------------------------- rank-r adapter (LoRA) products

@@ -140,6 +140,25 @@ wide_stats = {"decode": 0, "padded_decode": 0}
 lora_stats = {"prefill": 0, "extend": 0, "decode": 0, "adapters": 0}
 
 
+class _QForm(NamedTuple):
+    """One quantised weight form of the decode step: its number (csrc/kernels.h: WForm), the `_StackState` field of its switch,
+    the `_LayerState` field that holds a layer's copies, what E, Hq D and I must be multiples of, the quantiser (a 2-D weight -> a
+    (codes, scales) pair), the counters of the steps that ran in it, and what u2tok_decode_config.wform says for it (None: the
+    step's own config, wform 0 -- the four scales being set says e4m3)."""
+    form: int
+    switch: str
+    copies: str
+    multiple: int
+    quantise: object
+    stats: dict
+    wform: Optional[int]
+
+
+# in order of precedence: a layer takes the first form that is switched on and that it qualifies for, else the element type (form 0)
+_QFORMS = (_QForm(2, "fp4", "w4", 128, ops.quantize_blocks_fp4, w4_stats, 2),
+           _QForm(1, "fp8", "w8", 64, ops.quantize_rows_fp8, w8_stats, None))
+_QFORM_OF = {q.form: q for q in _QFORMS}
+
 _NO_PAD = ("none", None, None)   # the mask verdict of a call without padding (`pad_rule`, `_mask_hook`): compared by identity first
 
 
@@ -150,10 +169,10 @@ def _count(st, how: str, B: int) -> None:
     key = how if pad is _NO_PAD or pad[0] == "none" else "padded_" + how
     (extend_stats if how == "extend" else stats)[key] += 1
     if how == "decode" and (B > 16 or stack.fp8 or stack.fp4):
-        if stack.fp4 and st.w4 is not None:
-            w4_stats[key] += 1
-        elif stack.fp8 and st.w8 is not None:   # (`_weight_form`: a layer keeps the copies of one form)
-            w8_stats[key] += 1
+        for q in _QFORMS:   # (`_weight_form`: a layer keeps the copies of one form)
+            if getattr(stack, q.switch) and getattr(st, q.copies) is not None:
+                q.stats[key] += 1
+                break
         if B > 16:
             wide_stats[key] += 1
     if st.ads is not None:
@@ -402,9 +421,9 @@ class _LoraOps:
 class _LayerState:
     """A patched layer: its original forward, its stack's state, its layout, and what the decode step keeps between calls: the
     16-bit descriptor (`dec`), the optional e4m3 pairs (`w8`), the optional e2m1 pairs (`w4`), the optional adapter operands
-    (`lora`) and the DecodeLayer variants built from them (`variants`: plain, e4m3, each with or without adapters; `variants4`:
-    e2m1 without and with adapters -- `_decode_layer`), dropped together (`_drop_variants`) whenever one of the four sources is
-    rebuilt.  The ctypes structs and the references handed to the library live here."""
+    (`lora`) and the DecodeLayer variants built from them (`variants`: one per (weight form, with adapters) that a step has asked
+    for -- `_decode_layer`), dropped together (`_drop_variants`) whenever one of the four sources is rebuilt.  The ctypes
+    structs and the references handed to the library live here."""
     orig: object
     stack: _StackState
     layout: type
@@ -412,13 +431,12 @@ class _LayerState:
     dec: object = None         # `_Decode16`
     w8: tuple = None           # fp8_decode: (key, the four (W8, scale) pairs)
     lora: _LoraOps = None
-    variants: list = field(default_factory=lambda: [None] * 4)
+    variants: dict = field(default_factory=dict)   # (form, lora) -> `_decode_layer`'s tuple
     w4: tuple = None           # fp4_decode: (key, the four (codes, block scales) pairs)
-    variants4: list = field(default_factory=lambda: [None] * 2)
 
 
 def _drop_variants(st) -> None:
-    st.variants, st.variants4 = [None] * 4, [None] * 2
+    st.variants.clear()
 
 
 def is_patched(layer) -> bool:
@@ -803,51 +821,40 @@ def _decode_state(self, B: int, device, pr):
     return d, sc
 
 
-def _w8_state(st, d, pr) -> bool:
-    """fp8_decode: the e4m3 copies of a layer's four packed decode weights (q|k|v, o, gate|up, down: ops.quantize_rows_fp8, a
-    scale per row) in st.w8; False for a layer they do not take (E, Hq D or I not a multiple of 64: the layer keeps the 16-bit
-    step).  Built at the first qualifying step -- half the layer's weights again in HBM --, rebuilt when a source weight's
-    data_ptr() or _version changed (an optimiser step, load_state_dict, weight.mul_), freed with the patch state by
-    disable_fused_prefill and when the switch goes off.  Parameters, state dict, prefill and training never see the copies;
-    biases stay in the element type."""
+def _quant_state(st, d, pr, q) -> bool:
+    """The copies of a layer's four packed decode weights (q|k|v, o, gate|up, down) in the quantised form `q` -- fp8_decode: e4m3
+    with a scale per row (ops.quantize_rows_fp8), half the layer's weights again in HBM; fp4_decode: MXFP4, e2m1 codes with an e8m0
+    scale per block of 32 (ops.quantize_blocks_fp4), a quarter -- in the layer state's field `q.copies`; False for a layer the form
+    does not take (E, Hq D or I not a multiple of `q.multiple`: the layer keeps the next form it qualifies for).  Built at the first
+    qualifying step, rebuilt when a source weight's data_ptr() or _version changed (an optimiser step, load_state_dict,
+    weight.mul_), freed with the patch state by disable_fused_prefill and when the switch goes off.  Parameters, state dict,
+    prefill and training never see the copies; biases stay in the element type."""
     c = d.cfg
-    if c.E % 64 or (c.Hq * c.D) % 64 or c.I % 64:
+    if c.E % q.multiple or (c.Hq * c.D) % q.multiple or c.I % q.multiple:
         return False
     key = tuple((m.weight.data_ptr(), m.weight._version) for m in pr)
-    if st.w8 is None or st.w8[0] != key:
+    have = getattr(st, q.copies)
+    if have is None or have[0] != key:
         Wqkv, _, Wgu, _ = d.keep
         lo = st.layout
-        st.w8 = (key, tuple(ops.quantize_rows_fp8(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1])))
-        _drop_variants(st)
-    return True
-
-
-def _w4_state(st, d, pr) -> bool:
-    """fp4_decode: the MXFP4 copies of a layer's four packed decode weights (ops.quantize_blocks_fp4: e2m1 codes, an e8m0 scale per
-    block of 32) in st.w4; False for a layer they do not take (E, Hq D or I not a multiple of 128: the layer keeps the next form it
-    qualifies for).  Built, rebuilt and freed by the rules of `_w8_state` -- a quarter of the layer's weights again in HBM."""
-    c = d.cfg
-    if c.E % 128 or (c.Hq * c.D) % 128 or c.I % 128:
-        return False
-    key = tuple((m.weight.data_ptr(), m.weight._version) for m in pr)
-    if st.w4 is None or st.w4[0] != key:
-        Wqkv, _, Wgu, _ = d.keep
-        lo = st.layout
-        st.w4 = (key, tuple(ops.quantize_blocks_fp4(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1])))
+        setattr(st, q.copies, (key, tuple(q.quantise(w) for w in (Wqkv, lo.product(pr, 1)[1], Wgu, lo.product(pr, 3)[1]))))
         _drop_variants(st)
     return True
 
 
 def _weight_form(st, d, pr) -> int:
-    """The weight form of a layer's decode step under the stack's switches: 2 (e2m1) where fp4_decode is on and the layer
-    qualifies, else 1 (e4m3) where fp8_decode is on and it qualifies, else 0 (the element type).  Builds or refreshes the copies of
-    the form it returns; a copy of the other form a layer once built is dropped, so `_count` sees the one that ran."""
+    """The weight form of a layer's decode step under the stack's switches: the first of `_QFORMS` that is on and that the layer
+    qualifies for -- 2 (e2m1) under fp4_decode, else 1 (e4m3) under fp8_decode --, else 0 (the element type).  Builds or refreshes
+    the copies of the form it returns; copies of another form a layer once built are dropped, so `_count` sees the one that ran."""
     stack = st.stack
-    if stack.fp4 and _w4_state(st, d, pr):
-        st.w8 = None
-        return 2
-    if stack.fp8 and _w8_state(st, d, pr):
-        return 1
+    if not (stack.fp4 or stack.fp8):
+        return 0
+    for q in _QFORMS:
+        if getattr(stack, q.switch) and _quant_state(st, d, pr, q):
+            for other in _QFORMS:
+                if other is not q:
+                    setattr(st, other.copies, None)
+            return q.form
     return 0
 
 
@@ -912,31 +919,29 @@ def _lora_scratch(ls, B: int, sc, h) -> None:
     desc.scratch, desc.scratch_bytes = buf.data_ptr(), buf.numel()
 
 
-def _decode_layer(st, fp8: bool, lora: bool, fp4: bool = False):
-    """The step's u2tok_decode_layer as (struct, reference to it, config reference): the 16-bit descriptor (st.dec) with, for
-    fp8, codes and scales -- for fp4, e2m1 codes with the addresses of their block scales in the same four scale fields, and a
-    copy of the step's u2tok_decode_config that says so (wform = 2) -- in place of the four weights (norms and biases as the 16-bit
-    step has them) and, for lora, the adapters' u2tok_decode_lora.  One variant per combination, built on first use from the
+def _decode_layer(st, form: int, lora: bool):
+    """The step's u2tok_decode_layer as (struct, reference to it, config reference, config): the 16-bit descriptor (st.dec) with,
+    for a quantised form, the codes and the addresses of their scales in place of the four weights and in the four scale fields
+    (norms and biases as the 16-bit step has them) -- for e2m1 with a copy of the step's u2tok_decode_config that says so
+    (wform = 2) -- and, for lora, the adapters' u2tok_decode_lora.  One variant per (form, lora), built on first use from the
     sources as they are now; a rebuilt source drops all of them."""
-    vs, i = (st.variants4, int(lora)) if fp4 else (st.variants, fp8 + 2 * lora)
-    v = vs[i]
+    v = st.variants.get((form, lora))
     if v is None:
         import ctypes as C
         from . import _lib
         lay = _lib.DecodeLayer.from_buffer_copy(st.dec.layer)
         cfg, cfg_ref = st.dec.cfg, st.dec.cfg_ref
-        if fp4:
+        if form:
+            q = _QFORM_OF[form]
             (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
-                (w.data_ptr(), s.data_ptr()) for w, s in st.w4[1])
-            cfg = _lib.DecodeConfig.from_buffer_copy(cfg)   # (the batch size is part of st.dec's key: a change rebuilds both)
-            cfg.wform = 2
-            cfg_ref = C.byref(cfg)
-        elif fp8:
-            (lay.Wqkv, lay.scale_qkv), (lay.Wo, lay.scale_o), (lay.Wgu, lay.scale_gu), (lay.Wdown, lay.scale_down) = (
-                (w.data_ptr(), s.data_ptr()) for w, s in st.w8[1])
+                (w.data_ptr(), s.data_ptr()) for w, s in getattr(st, q.copies)[1])
+            if q.wform is not None:
+                cfg = _lib.DecodeConfig.from_buffer_copy(cfg)   # (the batch size is part of st.dec's key: a change rebuilds both)
+                cfg.wform = q.wform
+                cfg_ref = C.byref(cfg)
         if lora:
             lay.lora = C.addressof(st.lora.desc)
-        v = vs[i] = (lay, C.byref(lay), cfg_ref, cfg)
+        v = st.variants[(form, lora)] = (lay, C.byref(lay), cfg_ref, cfg)
     return v
 
 
@@ -976,7 +981,6 @@ def _decode_step(self, x, pe, cache, window, pr):
         return None                                   # (the caller takes the stock layer)
     st = self._u2_prefill
     form = _weight_form(st, d, pr)
-    fp4, fp8 = form == 2, form == 1   # (bools: the index of the descriptor variant below)
     ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
@@ -999,8 +1003,8 @@ def _decode_step(self, x, pe, cache, window, pr):
             kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
         if ls is not None:
             _lora_scratch(ls, B, sc, h)
-        v = st.variants4[ls is not None] if fp4 else st.variants[fp8 + 2 * (ls is not None)]
-        _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, fp8, ls is not None, fp4)
+        v = st.variants.get((form, ls is not None))
+        _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, form, ls is not None)
         _lib.check(h.u2tok_decoder_decode_pre(cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                                               int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
                                               vd.data_ptr(), kvs, kv.T0, ws, nws, stream), "u2tok_decoder_decode_pre")
