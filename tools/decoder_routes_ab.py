@@ -160,9 +160,9 @@ def child(a):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the parent
-def _run(tree, args, limit):
+def _run(tree, args, limit, script=None):
     """one child on `tree` under its own time limit; -> its figures, or SystemExit (nothing further is started)"""
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--child"] + args
+    cmd = [sys.executable, str(Path(script or __file__).resolve()), "--child"] + args
     env = dict(os.environ, PYTHONPATH=str(tree))
     print("+", tree, flush=True)
     try:
@@ -172,6 +172,36 @@ def _run(tree, args, limit):
     if r.returncode != 0:
         raise SystemExit(f"decoder_routes_ab: exit status {r.returncode} on {tree}\n{r.stdout[-2000:]}{r.stderr[-3000:]} -- stopping here")
     return json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("RESULT "))[7:])
+
+
+def run_pairs(trees, args, pairs, limit, script=None):
+    """{"a": [figures per child], "b": [...]}: one child of `script` (this file by default) per tree in alternation -- a, b, a, b, ..."""
+    runs = {"a": [], "b": []}
+    for _ in range(pairs):
+        for side in ("a", "b"):
+            runs[side].append(_run(trees[side], args, limit, script))
+    return runs
+
+
+def compare(runs, yard, unit_of):
+    """-> ({cell: row}, [cells slower beyond the yardstick's margin]).  Per cell: median over the pairs of (b - a) and its spread; with
+    a yardstick (the "cells" of the same run with tree a on both sides) the margin and whether the cell passes."""
+    cells, failed = {}, []
+    for cell in runs["a"][0]:
+        va, vb = [r[cell] for r in runs["a"]], [r[cell] for r in runs["b"]]
+        diff = [y - x for x, y in zip(va, vb)]
+        md = statistics.median(diff)
+        row = {"unit": unit_of(cell), "a": [round(v, 4) for v in va], "b": [round(v, 4) for v in vb],
+               "a_median": round(statistics.median(va), 4), "b_median": round(statistics.median(vb), 4),
+               "median_b_minus_a": round(md, 4), "spread": round(max(abs(x - md) for x in diff), 4)}
+        if yard is not None and cell in yard:
+            row["margin"] = max(abs(yard[cell]["median_b_minus_a"]), yard[cell]["spread"])
+            row["passes"] = bool(md <= 0 or abs(md) <= row["margin"])
+            if not row["passes"]:
+                failed.append(cell)
+        cells[cell] = row
+        print(cell, json.dumps(row), flush=True)
+    return cells, failed
 
 
 def main():
@@ -193,26 +223,9 @@ def main():
         ap.error("--a and --b are required")
     trees = {"a": Path(a.a).resolve(), "b": Path(a.b).resolve()}
     args = ["--rounds", str(a.rounds), "--layers", str(a.layers)] + (["--host-only"] if a.host_only else [])
-    runs = {"a": [], "b": []}
-    for _ in range(a.pairs):
-        for side in ("a", "b"):
-            runs[side].append(_run(trees[side], args, a.limit))
+    runs = run_pairs(trees, args, a.pairs, a.limit)
     yard = json.loads(Path(a.yardstick).read_text())["cells"] if a.yardstick else None
-    cells, failed = {}, []
-    for cell in runs["a"][0]:
-        va, vb = [r[cell] for r in runs["a"]], [r[cell] for r in runs["b"]]
-        diff = [y - x for x, y in zip(va, vb)]
-        md = statistics.median(diff)
-        row = {"unit": "us per call" if cell == HOST_CELL else "ms per step", "a": [round(v, 4) for v in va], "b": [round(v, 4) for v in vb],
-               "a_median": round(statistics.median(va), 4), "b_median": round(statistics.median(vb), 4),
-               "median_b_minus_a": round(md, 4), "spread": round(max(abs(x - md) for x in diff), 4)}
-        if yard is not None and cell in yard:
-            row["margin"] = max(abs(yard[cell]["median_b_minus_a"]), yard[cell]["spread"])
-            row["passes"] = bool(md <= 0 or abs(md) <= row["margin"])
-            if not row["passes"]:
-                failed.append(cell)
-        cells[cell] = row
-        print(cell, json.dumps(row), flush=True)
+    cells, failed = compare(runs, yard, lambda cell: "us per call" if cell == HOST_CELL else "ms per step")
     res = {"what": "host side of the decoder routes, tree b against tree a on one build of the library: ms per step (host time of the "
                    "calls included) of 16-step rounds at the Qwen3-8B layer shape, us per call for route_us; one child per tree in "
                    "alternation; margin = the larger of |median difference| and spread of the yardstick run (tree a on both sides)",

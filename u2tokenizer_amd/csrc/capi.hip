@@ -187,7 +187,7 @@ int u2tok_gemm_bf16(const void* A, const void* B, void* C, const void* bias, con
 
 int u2tok_layernorm_bf16(const void* x, const void* res, const void* w, const void* b, void* y, int32_t rows,
                          int32_t C, float eps, u2tok_stream_t stream) {
-  return layernorm_bf16(BF(x), BF(res), BF(w), BF(b), BFW(y), 1, rows, C, 0, C, 0, C, 0, C, eps, ST(stream));
+  return layernorm_dense(BF(x), BF(res), BF(w), BF(b), BFW(y), rows, C, eps, ST(stream));
 }
 
 int u2tok_softmax_rows(const float* S, void* P, int32_t nz, int32_t rows, int32_t n, int64_t lds, int64_t ldp,

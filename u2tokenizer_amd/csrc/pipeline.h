@@ -11,6 +11,12 @@ typedef u2tok_spp_config SppConfig;
 typedef u2tok_tokenizer_config TokConfig;
 typedef u2tok_tokenizer_taps TokTaps;
 
+// y = LayerNorm(x (+ res)) * w + b over `rows` dense rows of C elements (res may be null)
+inline int layernorm_dense(const bf16_t* x, const bf16_t* res, const bf16_t* w, const bf16_t* b, bf16_t* y, int rows, int C,
+                           float eps, hipStream_t st) {
+  return layernorm_bf16(x, res, w, b, y, 1, rows, C, 0, C, 0, C, 0, C, eps, st);
+}
+
 // dry == true: no launches, pointers may be null, *peak receives the workspace bytes required.
 int vit_forward(const VitConfig& c, const void* const* W, const void* volume, bf16_t* out, void* ws, size_t ws_bytes,
                 bool dry, size_t* peak, hipStream_t st);

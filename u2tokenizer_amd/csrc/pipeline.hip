@@ -2,8 +2,9 @@
 //   ViT3DTower (vit.py:114-126,148-164) -> SpatialPoolingProjector (spatial_pooling_projector.py:34-52)
 //   -> u2Tokenizer (u2Tokenizer.py:40-47 = svr.py:166-188 + tta.py:126-140).
 // Everything is enqueued from C++ on one HIP stream (no per-op Python/ctypes round trip); intermediate
-// tensors live in a caller-provided workspace carved by a bump arena.  Each forward is written once and
-// can run "dry" (no launches) to size that workspace.
+// tensors live in a caller-provided workspace carved by a bump arena.  Each forward is written once, as stage functions over
+// weight records filled from its table in one place, and can run "dry" (no launches) to size that workspace.
+#include <vector>
 #include "pipeline.h"
 
 namespace u2 {
@@ -43,23 +44,26 @@ struct ScratchScope {
   ~ScratchScope() { if (on) cx.set_scratch(st, prev.p, prev.bytes); }
 };
 
-#define U2_RUN(expr)                  \
-  do {                                \
-    if (!dry) {                       \
-      const int e_ = (expr);          \
-      if (e_ != U2_OK) return e_;     \
-    }                                 \
-  } while (0)
-#define U2_CHECK_WS(ar) \
-  do {                  \
-    if (!(ar).ok()) return U2_ERR_WORKSPACE; \
-  } while (0)
-
+// The run context, `r` wherever it is in scope: the arena, whether this run only sizes it (dry), the stream to enqueue on
+struct Run { Arena& ar; bool dry; hipStream_t st; };
+// U2_TRY: a helper that works in both modes (sizes in a dry run, launches in a real one).  U2_RUN: a launch, skipped in a dry run.
+// U2_CHECK_WS: the requests so far fit the workspace.  Each returns the error from the enclosing function.
+#define U2_TRY(expr) do { const int e_ = (expr); if (e_ != U2_OK) return e_; } while (0)
+#define U2_RUN(expr) U2_TRY(r.dry ? U2_OK : (expr))
+#define U2_CHECK_WS(ar) U2_TRY((ar).ok() ? U2_OK : U2_ERR_WORKSPACE)
+inline int hip_status(hipError_t e) { return e == hipSuccess ? U2_OK : U2_ERR_LAUNCH; }
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// A weight table as the records' fill functions read it; a dry run has none and gets null pointers.
+struct Table {
+  const void* const* W;
+  const bf16_t* operator[](int i) const { return W ? reinterpret_cast<const bf16_t*>(W[i]) : nullptr; }
+};
+struct Lin { const bf16_t *w, *b; };  // weight and bias of a linear layer or a LayerNorm
 
 // y[rows][ldy] = x[rows][ldx] @ W[out][in]^T + b  (+GELU) (+R)
 static GemmDesc linear_desc(const bf16_t* x, int64_t ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int64_t ldy, int64_t rows,
-                            int in, int out, int extra_flags, const bf16_t* R, int64_t ldr, int nsplit, float alpha_lo) {
+                            int in, int out, int extra_flags, const bf16_t* R, int64_t ldr, int nsplit = 0, float alpha_lo = 1.f) {
   GemmDesc g;
   g.A = x; g.B = w; g.C = y; g.bias = b; g.R = R;
   g.M = (int)rows; g.N = out; g.K = in;
@@ -68,13 +72,25 @@ static GemmDesc linear_desc(const bf16_t* x, int64_t ldx, const bf16_t* w, const
   g.nsplit = nsplit; g.alpha_lo = alpha_lo;  // columns [0, nsplit) scaled by alpha_lo (before the bias)
   return g;
 }
-
-int linear(const bf16_t* x, int64_t ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int64_t ldy, int64_t rows,
-           int in, int out, int extra_flags, const bf16_t* R, int64_t ldr, hipStream_t st, int nsplit = 0,
-           float alpha_lo = 1.f) {
-  return gemm_bf16(linear_desc(x, ldx, w, b, y, ldy, rows, in, out, extra_flags, R, ldr, nsplit, alpha_lo), st);
+// ... of dense x rows (ldx = in), R with y's leading dimension.  Both modes: nothing to size.
+int linear(const Run& r, const bf16_t* x, Lin l, bf16_t* y, int64_t ldy, int64_t rows, int in, int out, int flags = 0,
+           const bf16_t* R = nullptr) {
+  if (r.dry) return U2_OK;
+  return gemm_bf16(linear_desc(x, in, l.w, l.b, y, ldy, rows, in, out, flags, R, R ? ldy : 0), r.st);
+}
+// parity taps and optional outputs: n elements of src copied out (dst null: not asked for)
+int tap(const Run& r, void* dst, const bf16_t* src, size_t n) {
+  if (r.dry || !dst) return U2_OK;
+  return hip_status(hipMemcpyAsync(dst, src, n * sizeof(bf16_t), hipMemcpyDeviceToDevice, r.st));
+}
+// (b, t, n) <-> (t, b, n) / [cls | patches] gathers: `count` runs of `run` elements, `dld` / `sld` elements apart
+int copy_runs(const Run& r, bf16_t* dst, size_t dld, const bf16_t* src, size_t sld, size_t run, size_t count) {
+  if (r.dry) return U2_OK;
+  return hip_status(hipMemcpy2DAsync(dst, dld * sizeof(bf16_t), src, sld * sizeof(bf16_t), run * sizeof(bf16_t), count,
+                                     hipMemcpyDeviceToDevice, r.st));
 }
 
+struct Heads { int H, d; float scale; int max_len; };  // of one forward; the bias tables have 2 max_len - 1 rows (rma.py:64-68)
 struct AttnCore : AttnCall {   // equal heads, no masks; the key-split scratch (ws) comes from the arena
   bool unfused = false;  // force the GEMM chain (the ViT's debug path)
 };
@@ -83,8 +99,9 @@ struct AttnCore : AttnCall {   // equal heads, no masks; the key-split scratch (
 // probabilities).  Default: the fused kernel of tokattn.hip (scores and probabilities never leave the registers; few
 // (batch, head, 64-query) units -> key splits whose fp32 partial sums live in the arena).  Option "tok_flash" = 0, or a shape
 // that kernel does not take: two batched MFMA GEMMs around fp32 scores and bf16 probabilities in HBM.
-int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
-  if (!a.unfused && (dry || opts().tok_flash)) {
+int attention_core(Run& r, const AttnCore& a) {
+  Arena& ar = r.ar;
+  if (!a.unfused && (r.dry || opts().tok_flash)) {
     const size_t mark = ar.off;
     AttnCall c = a;
     c.Hkv = a.H;
@@ -92,16 +109,11 @@ int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
     c.ws = c.ws_bytes ? ar.get<char>(c.ws_bytes) : nullptr;
     U2_CHECK_WS(ar);
     // (a dry run sizes the arena for BOTH forms: which one a real call takes depends on pointers it does not have)
-    if (!dry && tok_attention_supported(c)) {
-      const int e = attention(c, st);
-      ar.off = mark;
-      return e;
-    }
     ar.off = mark;
+    if (!r.dry && tok_attention_supported(c)) return attention(c, r.st);
   }
   const size_t mark = ar.off;
-  const int64_t ldS = round_up(a.Skv, 8), ldp = ldS;
-  const int64_t nz = (int64_t)a.nb * a.H;
+  const int64_t ldS = round_up(a.Skv, 8), ldp = ldS, nz = (int64_t)a.nb * a.H;
   if (nz > 65535) return U2_ERR_ARG;
   float* S = ar.get<float>((size_t)nz * a.Sq * ldS);
   bf16_t* P = ar.get<bf16_t>((size_t)nz * a.Sq * ldp);
@@ -119,10 +131,10 @@ int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
     g.sAb = a.q_bs; g.sAh = a.d; g.sBb = a.k_bs; g.sBh = a.d;
     g.sCb = (int64_t)a.H * a.Sq * ldS; g.sCh = (int64_t)a.Sq * ldS;
     g.flags = GEMM_OUT_F32;
-    U2_RUN(gemm_bf16(g, st));
+    U2_RUN(gemm_bf16(g, r.st));
   }
   U2_RUN(softmax_rows(S, P, (int)nz, a.Sq, a.Skv, ldS, ldp, (int64_t)a.Sq * ldS, (int64_t)a.Sq * ldp, a.scale,
-                      a.rel_bias, a.H, a.max_len, st));
+                      a.rel_bias, a.H, a.max_len, r.st));
   {
     GemmDesc g;
     g.A = P; g.C = a.out;
@@ -136,42 +148,126 @@ int attention_core(Arena& ar, const AttnCore& a, bool dry, hipStream_t st) {
       g.sBb = a.v_bs; g.sBh = a.d;
       g.flags = GEMM_B_KMAJOR;
     } else {
-      U2_RUN(transpose_bf16(a.v, Vt, a.nb, a.Skv, a.H * a.d, a.ldv, ldp, a.v_bs, (int64_t)a.H * a.d * ldp, 0, st));
+      U2_RUN(transpose_bf16(a.v, Vt, a.nb, a.Skv, a.H * a.d, a.ldv, ldp, a.v_bs, (int64_t)a.H * a.d * ldp, 0, r.st));
       g.B = Vt; g.K = (int)ldp; g.ldb = ldp;
       g.sBb = (int64_t)a.H * a.d * ldp; g.sBh = (int64_t)a.d * ldp;
     }
-    U2_RUN(gemm_bf16(g, st));
+    U2_RUN(gemm_bf16(g, r.st));
   }
   ar.off = mark;
   return U2_OK;
+}
+
+// The two call forms of attention_core.  Self: packed q | k | v rows (3 E = 3 H d wide) -> out rows of E; nb sequences of S rows,
+// rows `ld` and sequences `bs` elements apart in qkv, a third of either in out.
+int self_attention(Run& r, const Heads& hd, const bf16_t* qkv, bf16_t* out, int nb, int S, int64_t ld, int64_t bs,
+                   const bf16_t* rel_bias, bool unfused = false) {
+  const int E = hd.H * hd.d;
+  AttnCore a;
+  a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.out = out;
+  a.ldq = a.ldk = a.ldv = ld; a.q_bs = a.k_bs = a.v_bs = bs; a.ldo = ld / 3; a.o_bs = bs / 3;
+  a.nb = nb; a.Sq = a.Skv = S; a.H = hd.H; a.d = hd.d; a.scale = hd.scale; a.rel_bias = rel_bias; a.max_len = hd.max_len;
+  a.unfused = unfused;
+  return attention_core(r, a);
+}
+// Cross: dense q / out rows of E, nb sequences of Sq; nb sequences of Skv key and value rows of leading dimension ldkv -- the
+// halves of a packed k | v buffer (ldkv = 2 E) or two buffers (ldkv = E).  No bias table (tta.py:55-61).
+int cross_attention(Run& r, const Heads& hd, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldkv, bf16_t* out, int nb,
+                    int Sq, int Skv) {
+  const int E = hd.H * hd.d;
+  AttnCore a;
+  a.q = q; a.k = k; a.v = v; a.out = out;
+  a.ldq = a.ldo = E; a.ldk = a.ldv = ldkv; a.q_bs = a.o_bs = (int64_t)Sq * E; a.k_bs = a.v_bs = (int64_t)Skv * ldkv;
+  a.nb = nb; a.Sq = Sq; a.Skv = Skv; a.H = hd.H; a.d = hd.d; a.scale = hd.scale;
+  return attention_core(r, a);
 }
 
 // attention over the CHUNK axis of rows laid out (b, t, n) [leading dim 3E for q | k | v, E for the output]: Bx * Nx * H
 // independent sequences of Tx rows that are Nx rows apart (svr.py:31-36 without its two permute().contiguous() copies).
 // Tx <= 16 and a head dim the wave kernel is built for: one launch; otherwise the batched-GEMM core, one batch entry
 // at a time (sequence rows are Nx * 3E elements apart, the Nx positions and H heads are the GEMM batch).
-int chunk_axis_attention(Arena& ar, const bf16_t* qkv, bf16_t* out, int Bx, int Tx, int Nx, int H, int d, float scale,
-                         const bf16_t* rel_bias, int max_len, bool dry, hipStream_t st) {
-  const int E = H * d;
-  if (Tx <= 16 && (d == 64 || d == 128 || d == 256 || d == 384 || d == 512)) {
-    U2_RUN(temporal_attention(qkv, qkv + E, qkv + 2 * E, out, Bx, Tx, Nx, H, d, 3 * E, E, scale, rel_bias, max_len, st));
-    return U2_OK;
-  }
-  for (int b = 0; b < Bx; ++b) {
-    const bf16_t* base = qkv + (int64_t)b * Tx * Nx * 3 * E;
-    AttnCore a;
-    a.q = base; a.k = base + E; a.v = base + 2 * E; a.out = out + (int64_t)b * Tx * Nx * E;
-    a.ldq = a.ldk = a.ldv = (int64_t)Nx * 3 * E; a.q_bs = a.k_bs = a.v_bs = 3 * E; a.ldo = (int64_t)Nx * E; a.o_bs = E;
-    a.nb = Nx; a.Sq = a.Skv = Tx; a.H = H; a.d = d; a.scale = scale; a.rel_bias = rel_bias; a.max_len = max_len;
-    const int e = attention_core(ar, a, dry, st);
-    if (e != U2_OK) return e;
-  }
+int chunk_axis_attention(Run& r, const Heads& hd, const bf16_t* qkv, bf16_t* out, int Bx, int Tx, int Nx, const bf16_t* rel_bias) {
+  const int d = hd.d, E = hd.H * d;
+  if (Tx <= 16 && (d == 64 || d == 128 || d == 256 || d == 384 || d == 512))
+    return r.dry ? U2_OK
+                 : temporal_attention(qkv, qkv + E, qkv + 2 * E, out, Bx, Tx, Nx, hd.H, d, 3 * E, E, hd.scale, rel_bias, hd.max_len, r.st);
+  for (int b = 0; b < Bx; ++b)
+    U2_TRY(self_attention(r, hd, qkv + (int64_t)b * Tx * Nx * 3 * E, out + (int64_t)b * Tx * Nx * E, Nx, Tx, (int64_t)Nx * 3 * E,
+                          3 * E, rel_bias));
   return U2_OK;
 }
 
+// =========================================================================== ViT3DTower
+struct VitBlock { Lin norm1; const bf16_t* wqkv; Lin out, norm2, fc1, fc2; };  // (the SABlock qkv projection has no bias)
+struct VitWeights { const bf16_t *pos, *cls; Lin patch, norm; std::vector<VitBlock> blocks; };
+// The ViT weight table (include/u2tok.h, "ViT weight table"): read here and nowhere else
+VitWeights vit_weights(const VitConfig& c, Table t) {
+  VitWeights w{t[0], t[3], {t[1], t[2]}, {t[4 + 11 * c.depth], t[5 + 11 * c.depth]}, {}};
+  for (int l = 0, i = 4; l < c.depth; ++l, i += 11)
+    w.blocks.push_back({{t[i], t[i + 1]}, t[i + 2], {t[i + 3], t[i + 4]}, {t[i + 5], t[i + 6]}, {t[i + 7], t[i + 8]}, {t[i + 9], t[i + 10]}});
+  return w;
+}
+
+struct Vit {  // one ViT forward: geometry, buffers and the stages that are not in line in vit_forward
+  const VitConfig& c; Run r;
+  int nc, ntok, S, S_pad, Hd;
+  int64_t prow, rows;  // patch rows; cls row of chunk b is row prow + b
+  Heads hd;
+  bf16_t *x, *xn, *qkv, *att, *vt, *h1;
+
+  // unfused reference attention (debug option "vit_flash" = 0): gather [cls | patches] per chunk, two GEMMs + softmax
+  int unfused_attention() {
+    const size_t mark = r.ar.off;
+    bf16_t* qc = r.ar.get<bf16_t>((size_t)rows * 3 * Hd);
+    bf16_t* ac = r.ar.get<bf16_t>((size_t)rows * Hd);
+    U2_CHECK_WS(r.ar);
+    const size_t rq = (size_t)3 * Hd;  // a q | k | v row
+    U2_TRY(copy_runs(r, qc + rq, S * rq, qkv, ntok * rq, ntok * rq, nc));
+    U2_TRY(copy_runs(r, qc, S * rq, qkv + prow * rq, rq, rq, nc));
+    U2_TRY(self_attention(r, hd, qc, ac, nc, S, rq, (int64_t)S * rq, nullptr, true));
+    U2_TRY(copy_runs(r, att, (size_t)ntok * Hd, ac + Hd, (size_t)S * Hd, (size_t)ntok * Hd, nc));
+    U2_TRY(copy_runs(r, att + prow * Hd, Hd, ac, (size_t)S * Hd, Hd, nc));
+    r.ar.off = mark;
+    return U2_OK;
+  }
+
+  // One MONAI TransformerBlock / SABlock on the residual stream x
+  int block(const VitBlock& w) {
+    // x = x + out_proj(attn(qkv(norm1(x))))
+    U2_RUN(layernorm_dense(x, nullptr, w.norm1.w, w.norm1.b, xn, (int)rows, Hd, c.ln_eps, r.st));
+    // the double pipeline reads q already multiplied by softmax scale * log2 e: the product scales its q columns from the
+    // fp32 accumulator (one rounding, as for the unscaled q of vit.py:100-105; the SABlock qkv projection has no bias)
+    const bool q_pre = opts().vit_flash && ntok >= 512 && (opts().flash_mode == 0 || opts().flash_mode == 7);
+    // ... and, where the 256 x 192 deep form runs the product (round 5), the V tiles leave V^T for the flash kernel themselves:
+    // their K loop runs with the MFMA operands exchanged and the transposed accumulators are stored in that operand's key order
+    // (gemm_bt.hip: vt_epilogue) -- no row-major V of the patch rows, no transpose launch (12 per volume).  Same values, bit for bit.
+    GemmDesc gq = linear_desc(xn, Hd, w.wqkv, nullptr, qkv, 3 * Hd, rows, Hd, 3 * Hd, 0, nullptr, 0, q_pre ? Hd : 0,
+                              hd.scale * 1.44269504088896340736f);
+    const bool vt_fused = opts().vit_flash && opts().vit_vt_epilogue && S_pad == ntok && gemm_vt_supported(gq, 2 * Hd, ntok);
+    if (vt_fused) {
+      gq.vt = vt; gq.vt_n0 = 2 * Hd; gq.vt_rows = ntok; gq.vt_ld = S_pad; gq.vt_bs = (int64_t)Hd * S_pad;
+    }
+    U2_RUN(gemm_bf16(gq, r.st));
+    if (opts().vit_flash) {
+      if (!vt_fused)
+        U2_RUN(transpose_bf16(qkv + 2 * Hd, vt, nc, ntok, Hd, 3 * Hd, S_pad, (int64_t)ntok * 3 * Hd, (int64_t)Hd * S_pad, 1, r.st));
+      const bf16_t* xq = qkv + prow * 3 * Hd;  // q | k | v of the cls rows
+      U2_RUN(flash_attention_d64(qkv, qkv + Hd, vt, att, nc, ntok, hd.H, 3 * Hd, (int64_t)ntok * 3 * Hd, Hd,
+                                 (int64_t)ntok * Hd, S_pad, hd.scale, xq, xq + Hd, xq + 2 * Hd, att + prow * Hd, 3 * Hd, Hd,
+                                 1, nullptr, 0, r.st, q_pre ? 1 : 0));
+    } else {
+      U2_TRY(unfused_attention());
+    }
+    U2_TRY(linear(r, att, w.out, x, Hd, rows, Hd, Hd, 0, x));
+    // x = x + linear2(gelu(linear1(norm2(x))))
+    U2_RUN(layernorm_dense(x, nullptr, w.norm2.w, w.norm2.b, xn, (int)rows, Hd, c.ln_eps, r.st));
+    U2_TRY(linear(r, xn, w.fc1, h1, c.mlp_dim, rows, Hd, c.mlp_dim, GEMM_GELU));
+    return linear(r, h1, w.fc2, x, Hd, rows, c.mlp_dim, Hd, 0, x);
+  }
+};
+
 }  // namespace
 
-// =========================================================================== ViT3DTower
 // Row layout of the residual stream: the nc * ntok PATCH rows first (chunk-major), then the nc cls rows.  The
 // reference keeps [cls | patches] per chunk (vit.py:116-118); a transformer is indifferent to the order rows are
 // stored in, and this one makes every GEMM see M = nc*ntok (+ nc), the patch rows of a chunk tile exactly into
@@ -183,111 +279,40 @@ int vit_forward(const VitConfig& c, const void* const* W, const void* volume, bf
     if (c.img[i] <= 0 || c.patch[i] <= 0 || c.img[i] % c.patch[i]) return U2_ERR_ARG;
   if (!dry && (!W || !volume || !out)) return U2_ERR_ARG;
   const int nh = c.img[0] / c.patch[0], nw = c.img[1] / c.patch[1], nd = c.img[2] / c.patch[2];
-  const int ntok = nh * nw * nd, S = ntok + 1, Hd = c.hidden, Kp = c.patch[0] * c.patch[1] * c.patch[2];
-  const int nc = c.nchunk;
-  const int64_t prow = (int64_t)nc * ntok;  // patch rows; cls row of chunk b is row prow + b
-  const int64_t rows = prow + nc;
-  const int S_pad = (int)round_up(ntok, 64);
-  auto w = [&](int i) { return dry ? nullptr : reinterpret_cast<const bf16_t*>(W[i]); };
+  const int ntok = nh * nw * nd, S = ntok + 1, Hd = c.hidden, Kp = c.patch[0] * c.patch[1] * c.patch[2], nc = c.nchunk;
+  const int64_t prow = (int64_t)nc * ntok, rows = prow + nc;
+  const VitWeights w = vit_weights(c, Table{dry ? nullptr : W});
 
   ScratchScope scratch_scope(ctx(), st, nullptr, 0, !dry);
   Arena ar(ws, ws_bytes, dry);
-  bf16_t* x = ar.get<bf16_t>((size_t)rows * Hd);
-  bf16_t* xn = ar.get<bf16_t>((size_t)rows * Hd);
-  bf16_t* qkv = ar.get<bf16_t>((size_t)rows * 3 * Hd);
-  bf16_t* att = ar.get<bf16_t>((size_t)rows * Hd);
-  bf16_t* vt = ar.get<bf16_t>((size_t)nc * Hd * S_pad);
+  Vit v{c, Run{ar, dry, st}, nc, ntok, S, (int)round_up(ntok, 64), Hd, prow, rows, Heads{c.heads, 64, 1.0f / sqrtf(64.0f), 0}};
+  const Run& r = v.r;
+  bf16_t* x = v.x = ar.get<bf16_t>((size_t)rows * Hd);
+  v.xn = ar.get<bf16_t>((size_t)rows * Hd);
+  v.qkv = ar.get<bf16_t>((size_t)rows * 3 * Hd);
+  v.att = ar.get<bf16_t>((size_t)rows * Hd);
+  v.vt = ar.get<bf16_t>((size_t)nc * Hd * v.S_pad);
   // patches (only needed for the embedding) and the MLP hidden share one region
-  const size_t big = std::max((size_t)nc * ntok * Kp, (size_t)rows * c.mlp_dim);
-  bf16_t* h1 = ar.get<bf16_t>(big);
-  bf16_t* patches = h1;
+  bf16_t* patches = v.h1 = ar.get<bf16_t>(std::max((size_t)nc * ntok * Kp, (size_t)rows * c.mlp_dim));
   U2_CHECK_WS(ar);
 
   // ---- patch embedding: im2col + Linear + position embedding; cls token rows appended (vit.py:115-118)
   U2_RUN(im2col_patches(volume, c.vol_dtype, patches, nc, c.img[0], c.img[1], c.img[2], c.patch[0], c.patch[1],
                         c.patch[2], st));
-  U2_RUN(fill_rows(w(3), x + prow * Hd, nc, Hd, Hd, st));
-  {
-    GemmDesc g;
-    g.A = patches; g.B = w(1); g.C = x; g.bias = w(2); g.R = w(0);
-    g.M = ntok; g.N = Hd; g.K = Kp;
-    g.lda = Kp; g.ldb = Kp; g.ldc = Hd; g.ldr = Hd;
-    g.nz = nc; g.nbh = 1;
-    g.sAb = (int64_t)ntok * Kp; g.sCb = (int64_t)ntok * Hd;
-    g.flags = GEMM_BIAS_N | GEMM_RESIDUAL;
-    U2_RUN(gemm_bf16(g, st));
-  }
-  const float scale = 1.0f / sqrtf(64.0f);
-  for (int l = 0; l < c.depth; ++l) {
-    const int b0 = 4 + 11 * l;
-    // x = x + out_proj(attn(qkv(norm1(x))))   (MONAI TransformerBlock / SABlock)
-    U2_RUN(layernorm_bf16(x, nullptr, w(b0 + 0), w(b0 + 1), xn, 1, (int)rows, Hd, 0, Hd, 0, 0, 0, Hd, c.ln_eps, st));
-    // the double pipeline reads q already multiplied by softmax scale * log2 e: the product scales its q columns from the
-    // fp32 accumulator (one rounding, as for the unscaled q of vit.py:100-105; the SABlock qkv projection has no bias)
-    const bool q_pre = opts().vit_flash && ntok >= 512 && (opts().flash_mode == 0 || opts().flash_mode == 7);
-    // ... and, where the 256 x 192 deep form runs the product (round 5), the V tiles leave V^T for the flash kernel themselves:
-    // their K loop runs with the MFMA operands exchanged and the transposed accumulators are stored in that operand's key order
-    // (gemm_bt.hip: vt_epilogue) -- no row-major V of the patch rows, no transpose launch (12 per volume).  Same values, bit for bit.
-    GemmDesc gq = linear_desc(xn, Hd, w(b0 + 2), nullptr, qkv, 3 * Hd, rows, Hd, 3 * Hd, 0, nullptr, 0, q_pre ? Hd : 0,
-                              scale * 1.44269504088896340736f);
-    const bool vt_fused = opts().vit_flash && opts().vit_vt_epilogue && S_pad == ntok && gemm_vt_supported(gq, 2 * Hd, ntok);
-    if (vt_fused) {
-      gq.vt = vt; gq.vt_n0 = 2 * Hd; gq.vt_rows = ntok; gq.vt_ld = S_pad; gq.vt_bs = (int64_t)Hd * S_pad;
-    }
-    U2_RUN(gemm_bf16(gq, st));
-    if (opts().vit_flash) {
-      if (!vt_fused)
-        U2_RUN(transpose_bf16(qkv + 2 * Hd, vt, nc, ntok, Hd, 3 * Hd, S_pad, (int64_t)ntok * 3 * Hd, (int64_t)Hd * S_pad, 1, st));
-      const bf16_t* xq = qkv + prow * 3 * Hd;  // q | k | v of the cls rows
-      U2_RUN(flash_attention_d64(qkv, qkv + Hd, vt, att, nc, ntok, c.heads, 3 * Hd, (int64_t)ntok * 3 * Hd, Hd,
-                                 (int64_t)ntok * Hd, S_pad, scale, xq, xq + Hd, xq + 2 * Hd, att + prow * Hd, 3 * Hd, Hd,
-                                 1, nullptr, 0, st, q_pre ? 1 : 0));
-    } else {
-      // unfused reference path (debug option "vit_flash" = 0): gather [cls | patches] per chunk, two GEMMs + softmax
-      const size_t mark = ar.off;
-      bf16_t* qc = ar.get<bf16_t>((size_t)rows * 3 * Hd);
-      bf16_t* ac = ar.get<bf16_t>((size_t)rows * Hd);
-      U2_CHECK_WS(ar);
-      const size_t rb = (size_t)3 * Hd * sizeof(bf16_t), ob = (size_t)Hd * sizeof(bf16_t);
-      if (!dry) {
-        const hipError_t e1 = hipMemcpy2DAsync(qc + 3 * Hd, (size_t)S * rb, qkv, (size_t)ntok * rb, (size_t)ntok * rb, nc,
-                                               hipMemcpyDeviceToDevice, st);
-        const hipError_t e2 = hipMemcpy2DAsync(qc, (size_t)S * rb, qkv + prow * 3 * Hd, rb, rb, nc,
-                                               hipMemcpyDeviceToDevice, st);
-        if (e1 != hipSuccess || e2 != hipSuccess) return U2_ERR_LAUNCH;
-      }
-      {
-        AttnCore a;
-        a.q = qc; a.k = qc + Hd; a.v = qc + 2 * Hd; a.out = ac;
-        a.ldq = a.ldk = a.ldv = 3 * Hd; a.q_bs = a.k_bs = a.v_bs = (int64_t)S * 3 * Hd; a.ldo = Hd; a.o_bs = (int64_t)S * Hd;
-        a.nb = nc; a.Sq = a.Skv = S; a.H = c.heads; a.d = 64; a.scale = scale; a.unfused = true;
-        const int e = attention_core(ar, a, dry, st);
-        if (e != U2_OK) return e;
-      }
-      if (!dry) {
-        const hipError_t e1 = hipMemcpy2DAsync(att, (size_t)ntok * ob, ac + Hd, (size_t)S * ob, (size_t)ntok * ob, nc,
-                                               hipMemcpyDeviceToDevice, st);
-        const hipError_t e2 = hipMemcpy2DAsync(att + prow * Hd, ob, ac, (size_t)S * ob, ob, nc, hipMemcpyDeviceToDevice, st);
-        if (e1 != hipSuccess || e2 != hipSuccess) return U2_ERR_LAUNCH;
-      }
-      ar.off = mark;
-    }
-    U2_RUN(linear(att, Hd, w(b0 + 3), w(b0 + 4), x, Hd, rows, Hd, Hd, 0, x, Hd, st));
-    // x = x + linear2(gelu(linear1(norm2(x))))
-    U2_RUN(layernorm_bf16(x, nullptr, w(b0 + 5), w(b0 + 6), xn, 1, (int)rows, Hd, 0, Hd, 0, 0, 0, Hd, c.ln_eps, st));
-    U2_RUN(linear(xn, Hd, w(b0 + 7), w(b0 + 8), h1, c.mlp_dim, rows, Hd, c.mlp_dim, GEMM_GELU, nullptr, 0, st));
-    U2_RUN(linear(h1, c.mlp_dim, w(b0 + 9), w(b0 + 10), x, Hd, rows, c.mlp_dim, Hd, 0, x, Hd, st));
-  }
+  U2_RUN(fill_rows(w.cls, x + prow * Hd, nc, Hd, Hd, st));
+  GemmDesc g = linear_desc(patches, Kp, w.patch.w, w.patch.b, x, Hd, ntok, Kp, Hd, 0, w.pos, Hd);  // per chunk: + the same positions
+  g.nz = nc; g.sAb = (int64_t)ntok * Kp; g.sCb = (int64_t)ntok * Hd;
+  U2_RUN(gemm_bf16(g, st));
+  for (const VitBlock& b : w.blocks) U2_TRY(v.block(b));
   // final norm; the cls rows are dropped unless select_feature == "cls_patch" (vit.py:124,157-160), in which case
   // the output goes back to the reference's [cls | patches] order per chunk
-  const int nwt = 4 + 11 * c.depth;
   if (c.keep_cls) {
-    U2_RUN(layernorm_bf16(x, nullptr, w(nwt), w(nwt + 1), out + Hd, nc, ntok, Hd, (int64_t)ntok * Hd, Hd, 0, 0,
+    U2_RUN(layernorm_bf16(x, nullptr, w.norm.w, w.norm.b, out + Hd, nc, ntok, Hd, (int64_t)ntok * Hd, Hd, 0, 0,
                           (int64_t)S * Hd, Hd, c.ln_eps, st));
-    U2_RUN(layernorm_bf16(x + prow * Hd, nullptr, w(nwt), w(nwt + 1), out, nc, 1, Hd, Hd, Hd, 0, 0, (int64_t)S * Hd, Hd,
+    U2_RUN(layernorm_bf16(x + prow * Hd, nullptr, w.norm.w, w.norm.b, out, nc, 1, Hd, Hd, Hd, 0, 0, (int64_t)S * Hd, Hd,
                           c.ln_eps, st));
   } else {
-    U2_RUN(layernorm_bf16(x, nullptr, w(nwt), w(nwt + 1), out, 1, (int)prow, Hd, 0, Hd, 0, 0, 0, Hd, c.ln_eps, st));
+    U2_RUN(layernorm_dense(x, nullptr, w.norm.w, w.norm.b, out, (int)prow, Hd, c.ln_eps, st));
   }
   if (peak) *peak = ar.peak;
   U2_CHECK_WS(ar);
@@ -295,6 +320,7 @@ int vit_forward(const VitConfig& c, const void* const* W, const void* volume, bf
 }
 
 // =========================================================================== SpatialPoolingProjector
+// (weight table: layer l's weight and bias at 2 l, 2 l + 1 -- include/u2tok.h, "SPP weight table")
 int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_t* out, void* ws, size_t ws_bytes,
                 bool dry, size_t* peak, hipStream_t st) {
   if (c.nchunk <= 0 || c.pooling_size <= 0 || c.layer_num <= 0 || c.in_dim <= 0 || c.out_dim <= 0) return U2_ERR_ARG;
@@ -306,9 +332,10 @@ int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_
   if (g1 < w1 || g2 < w2 || g3 < w3) return U2_ERR_ARG;
   const int np = (g1 / w1) * (g2 / w2) * (g3 / w3);
   const int64_t rows = (int64_t)c.nchunk * np;
-  auto w = [&](int i) { return dry ? nullptr : reinterpret_cast<const bf16_t*>(W[i]); };
+  const Table w{dry ? nullptr : W};
   ScratchScope scratch_scope(ctx(), st, nullptr, 0, !dry);
   Arena ar(ws, ws_bytes, dry);
+  const Run r{ar, dry, st};
   bf16_t* pooled = ar.get<bf16_t>((size_t)rows * c.in_dim);
   bf16_t* ha = ar.get<bf16_t>((size_t)rows * c.out_dim);
   bf16_t* hb = ar.get<bf16_t>((size_t)rows * c.out_dim);
@@ -319,8 +346,8 @@ int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_
   for (int l = 0; l < c.layer_num; ++l) {
     const bool last = (l == c.layer_num - 1);
     bf16_t* dst = last ? out : ((l & 1) ? hb : ha);
-    const int fl = (!last && c.layer_type == 0) ? GEMM_GELU : 0;
-    U2_RUN(linear(cur, cur_dim, w(2 * l), w(2 * l + 1), dst, c.out_dim, rows, cur_dim, c.out_dim, fl, nullptr, 0, st));
+    U2_TRY(linear(r, cur, {w[2 * l], w[2 * l + 1]}, dst, c.out_dim, rows, cur_dim, c.out_dim,
+                  (!last && c.layer_type == 0) ? GEMM_GELU : 0));
     cur = dst;
     cur_dim = c.out_dim;
   }
@@ -330,173 +357,135 @@ int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_
 
 // =========================================================================== u2Tokenizer
 namespace {
-struct Att {
-  const bf16_t *wq, *bq, *wk, *bk, *wv, *bv, *wd, *bd, *rb;
+struct Att { Lin q, k, v, o; const bf16_t* rb; };  // an attention module's projections and its relative-bias table (null: none)
+struct SvrLayer { Att spatial, temporal; };
+struct TtaLayer { Att self, visual, text; Lin norm_self, norm_v, norm_t; };
+struct TokWeights {
+  const bf16_t* query;
+  Lin score, gate;  // token_selection.score_net; dynamic_pool.gate_fc (null when !enable_dmtp)
+  Att linagg;       // (wv / dense are in the table but never read: tta.py:47-48,62-65)
+  std::vector<SvrLayer> svr;  // per layer
+  std::vector<TtaLayer> tta;
 };
+// The tokenizer weight table (include/u2tok.h, "Tokenizer weight table"): read here and nowhere else.  Only the self attentions of
+// attn_type rma have a bias table; whatever the table holds in that slot of any other attention is dropped here.
+TokWeights tok_weights(const TokConfig& c, Table t) {
+  auto att = [&](int i, bool self) {
+    return Att{{t[i], t[i + 1]}, {t[i + 2], t[i + 3]}, {t[i + 4], t[i + 5]}, {t[i + 6], t[i + 7]}, self && c.attn_type == 0 ? t[i + 8] : nullptr};
+  };
+  const int L = c.num_layers, i_sel = 1 + 18 * L, i_tta = i_sel + 4, i_lin = i_tta + 33 * L;
+  TokWeights w{t[0], {t[i_sel], t[i_sel + 1]}, {nullptr, nullptr}, att(i_lin, false), {}, {}};
+  if (c.enable_dmtp) w.gate = {t[i_sel + 2], t[i_sel + 3]};
+  for (int l = 0, i = 1; l < L; ++l, i += 18) w.svr.push_back({att(i, true), att(i + 9, true)});
+  for (int l = 0, i = i_tta; l < L; ++l, i += 33)
+    w.tta.push_back({att(i, true), att(i + 9, false), att(i + 18, false), {t[i + 27], t[i + 28]}, {t[i + 29], t[i + 30]}, {t[i + 31], t[i + 32]}});
+  return w;
+}
+
 // The host module packs wq | wk | wv (and their biases) back to back in HBM (tokenizer.py: pack_weights); when it
 // did, the three projections of one input are ONE GEMM with N = 3E (2E for the k | v pair of a cross attention):
-// the activation panel is read once and the launch fills the machine 3x better at small M.
-inline bool kv_packed(const Att& a, int E) {
-  return a.wk && a.bk && a.wv == a.wk + (size_t)E * E && a.bv == a.bk + E;
-}
-inline bool qkv_packed(const Att& a, int E) {
-  return a.wq && a.bq && a.wk == a.wq + (size_t)E * E && a.bk == a.bq + E && kv_packed(a, E);
-}
-// q | k | v = x W^T + b into out[rows][3E]
-int qkv_proj(const bf16_t* x, const Att& a, bf16_t* out, int64_t rows, int E, bool dry, hipStream_t st) {
-  if (!dry && qkv_packed(a, E)) {
-    U2_RUN(linear(x, E, a.wq, a.bq, out, 3 * E, rows, E, 3 * E, 0, nullptr, 0, st));
-    return U2_OK;
-  }
-  U2_RUN(linear(x, E, a.wq, a.bq, out, 3 * E, rows, E, E, 0, nullptr, 0, st));
-  U2_RUN(linear(x, E, a.wk, a.bk, out + E, 3 * E, rows, E, E, 0, nullptr, 0, st));
-  U2_RUN(linear(x, E, a.wv, a.bv, out + 2 * E, 3 * E, rows, E, E, 0, nullptr, 0, st));
+// the activation panel is read once and the launch fills the machine 3x better at small M.  (A dry run's nulls are not packed.)
+// out[rows][n E] = x W^T + b for the n projections p: {q, k, v} or {k, v} of one attention
+int packed_proj(const Run& r, const bf16_t* x, std::initializer_list<Lin> p, bf16_t* out, int64_t rows, int E) {
+  const Lin* l = p.begin(); const int n = (int)p.size();
+  bool packed = l[0].w && l[0].b;
+  for (int i = 1; i < n; ++i) packed = packed && l[i].w == l[i - 1].w + (size_t)E * E && l[i].b == l[i - 1].b + E;
+  if (packed) return linear(r, x, l[0], out, n * E, rows, E, n * E);
+  for (int i = 0; i < n; ++i) U2_TRY(linear(r, x, l[i], out + i * E, n * E, rows, E, E));
   return U2_OK;
 }
-}  // namespace
+// q and k of packed q | k | v rows indexed (outer, s, inner) rotated in place, position = s
+int rope_qk(const Run& r, const Heads& hd, bf16_t* qkv, int64_t n_outer, int S, int n_inner) {
+  const int E = hd.H * hd.d;
+  U2_RUN(rope_apply(qkv, n_outer, S, n_inner, hd.H, hd.d, 3 * E, hd.max_len, 0, r.st));
+  U2_RUN(rope_apply(qkv + E, n_outer, S, n_inner, hd.H, hd.d, 3 * E, hd.max_len, 0, r.st));
+  return U2_OK;
+}
+template <typename P> inline P* slot(P* const* per_layer, int l) { return per_layer ? per_layer[l] : nullptr; }
 
-int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_token, const bf16_t* t_token,
-                      bf16_t* out, int64_t* topk_idx_out, bf16_t* svr_out, const TokTaps* taps, void* ws, size_t ws_bytes,
-                      bool dry, size_t* peak, hipStream_t st) {
-  if (c.B <= 0 || c.T <= 0 || c.N <= 0 || c.E <= 0 || c.Lt <= 0 || c.num_heads <= 0 || c.num_layers < 0) return U2_ERR_ARG;
-  if (c.E % c.num_heads || (c.E / c.num_heads) % 8 || c.top_k <= 0 || c.num_query <= 0) return U2_ERR_ARG;
-  if (c.attn_type < 0 || c.attn_type > 2) return U2_ERR_ARG;
-  // attn_type 2 = nn.MultiheadAttention read sequence-first (svr.py:16-18,28-35): attention runs across whatever sits
+struct Tok {  // one tokenizer forward: what its stages share, and the stages in the order tokenizer_forward calls them
+  const TokConfig& c; Run r; const TokWeights& w;
+  TokTaps taps;  // (all null without taps and in a dry run)
+  const bf16_t* t_token;
+  int B, T, N, E, L, Q, k;
+  Heads hd;
+  int64_t rows, qrows;                // B * T * N visual rows, B * Q query rows
+  bf16_t *xa, *xb, *qkv, *sctx;       // SVR: ping-pong token buffers, packed q | k | v, attention context
+  const bf16_t* V; int Lv;            // the Lv visual tokens per batch entry the aggregation attends to
+  bf16_t *qa, *qb, *qc, *qproj, *qctx, *qo;  // TTA: query ping-pong (+ qc), projections, context, sub-layer output
+  // k | v of the two cross attentions of every layer: one buffer each, filled on the side stream (or kv_inline, in line)
+  SideStream* side; bool overlap;
+  bf16_t *kv_inline, *kv_v[8], *kv_t[8], *k_lin;  // k_lin: key projection of the final linear aggregation
+
+  // attn_type 2 with B > 1, temporal: the sequence is the B*N (batch, token) pairs of one chunk index: gather rows (b, t, n) ->
+  // (t, b, n), attend, scatter
+  int temporal_across_batch() {
+    const size_t mark = r.ar.off;
+    bf16_t* g = r.ar.get<bf16_t>((size_t)rows * 3 * E);
+    bf16_t* gc = r.ar.get<bf16_t>((size_t)rows * E);
+    U2_CHECK_WS(r.ar);
+    const size_t S2 = (size_t)B * N;
+    for (int b = 0; b < B; ++b)
+      U2_TRY(copy_runs(r, g + (size_t)b * N * 3 * E, S2 * 3 * E, qkv + (size_t)b * T * N * 3 * E, (size_t)N * 3 * E, (size_t)N * 3 * E, T));
+    U2_TRY(self_attention(r, hd, g, gc, T, (int)S2, 3 * E, (int64_t)S2 * 3 * E, nullptr));
+    for (int b = 0; b < B; ++b)
+      U2_TRY(copy_runs(r, sctx + (size_t)b * T * N * E, (size_t)N * E, gc + (size_t)b * N * E, S2 * E, (size_t)N * E, T));
+    r.ar.off = mark;
+    return U2_OK;
+  }
+
+  // ---------------- SVR layer l (svr.py:23-40,50-62): x = temporal(spatial(x)), no residual / norm.  x: the layer's input, then its
+  // output.  attn_type 2 = nn.MultiheadAttention read sequence-first (svr.py:16-18,28-35): attention runs across whatever sits
   // in dim 0, INCLUDING the batch entries: "spatial" = across the B*T (batch, chunk) pairs at a token position,
-  // "temporal" = across the B*N (batch, token) pairs of a chunk index, TTA self-attention = across the B batch entries
-  // of a query index (a sequence of one key for B = 1).
-  if (!dry && (!W || !v_token || !t_token || !out)) return U2_ERR_ARG;
-  const int B = c.B, T = c.T, N = c.N, E = c.E, H = c.num_heads, d = E / H, L = c.num_layers, Q = c.num_query;
-  const int TN = T * N, k = c.top_k;
-  if (!c.enable_diffts && k > TN) return U2_ERR_ARG;                       // torch.topk would raise
-  if (N > c.max_seq_len || T > c.max_seq_len || Q > c.max_seq_len) return U2_ERR_ARG;  // rma.py:64-68 index range
-  const float scale = 1.0f / sqrtf((float)d);
-  auto wp = [&](int i) { return dry ? nullptr : reinterpret_cast<const bf16_t*>(W[i]); };
-  auto att_at = [&](int i) {
-    Att a{wp(i), wp(i + 1), wp(i + 2), wp(i + 3), wp(i + 4), wp(i + 5), wp(i + 6), wp(i + 7), wp(i + 8)};
-    if (c.attn_type != 0) a.rb = nullptr;
-    return a;
-  };
-  const int i_sel = 1 + 18 * L, i_gate = i_sel + 2, i_tta = i_gate + 2, i_lin = i_tta + 33 * L;
-
-  Arena ar(ws, ws_bytes, dry);
-  // split-K scratch for the skinny linear layers of this forward (M = 256 queries against E x E weights); registered
-  // for this stream only while the launches below are being enqueued
-  // (24 MB covers the E x E products; the TTA self-attention's packed q|k|v product takes the big-tile kernel in 4 K slices:
-  //  4 x rows x 3E fp32)
-  const size_t kSplitK = std::max<size_t>(24u << 20, (size_t)16 * B * c.num_query * 3 * E);
-  char* skw = ar.get<char>(kSplitK);
-  U2_CHECK_WS(ar);
-  Context& cx = ctx();
-  ScratchScope scratch_scope(cx, st, skw, kSplitK, !dry);
-  const int64_t rows = (int64_t)B * TN;
-  bf16_t* xa = ar.get<bf16_t>((size_t)rows * E);
-  bf16_t* xb = ar.get<bf16_t>((size_t)rows * E);
-  bf16_t* qkv = ar.get<bf16_t>((size_t)rows * 3 * E);
-  bf16_t* ctx = ar.get<bf16_t>((size_t)rows * E);
-  U2_CHECK_WS(ar);
-
-  // ---------------- SVR: SpatioTemporalSignificanceScoring (svr.py:50-62) -- x = attn(x), no residual/norm
-  const bf16_t* x = v_token;
-  for (int l = 0; l < L; ++l) {
-    const Att sp = att_at(1 + 18 * l), tp = att_at(1 + 18 * l + 9);
-    if (taps && !dry && taps->svr_in && taps->svr_in[l]) x = reinterpret_cast<const bf16_t*>(taps->svr_in[l]);
+  // "temporal" = across the B*N (batch, token) pairs of a chunk index.
+  int svr_layer(int l, const bf16_t*& x) {
+    const SvrLayer& a = w.svr[l];
+    if (const void* in = slot(taps.svr_in, l)) x = reinterpret_cast<const bf16_t*>(in);
     bf16_t* y = (x == xa) ? xb : xa;
     // spatial: sequences of N tokens inside each chunk (svr.py:27-30)
-    { const int e = qkv_proj(x, sp, qkv, rows, E, dry, st); if (e != U2_OK) return e; }
-    if (c.attn_type == 1) {
-      U2_RUN(rope_apply(qkv, (int64_t)B * T, N, 1, H, d, 3 * E, c.max_seq_len, 0, st));
-      U2_RUN(rope_apply(qkv + E, (int64_t)B * T, N, 1, H, d, 3 * E, c.max_seq_len, 0, st));
-    }
-    if (c.attn_type == 2) {  // sequence = the B*T (batch, chunk) pairs, batch = token position
-      const int e = chunk_axis_attention(ar, qkv, ctx, 1, B * T, N, H, d, scale, nullptr, c.max_seq_len, dry, st);
-      if (e != U2_OK) return e;
-    } else {
-      AttnCore a;
-      a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.out = ctx;
-      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = (int64_t)N * 3 * E; a.ldo = E; a.o_bs = (int64_t)N * E;
-      a.nb = B * T; a.Sq = a.Skv = N; a.H = H; a.d = d; a.scale = scale; a.rel_bias = sp.rb; a.max_len = c.max_seq_len;
-      const int e = attention_core(ar, a, dry, st);
-      if (e != U2_OK) return e;
-    }
-    U2_RUN(linear(ctx, E, sp.wd, sp.bd, y, E, rows, E, E, 0, nullptr, 0, st));
+    U2_TRY(packed_proj(r, x, {a.spatial.q, a.spatial.k, a.spatial.v}, qkv, rows, E));
+    if (c.attn_type == 1) U2_TRY(rope_qk(r, hd, qkv, (int64_t)B * T, N, 1));
+    if (c.attn_type == 2)  // sequence = the B*T (batch, chunk) pairs, batch = token position
+      U2_TRY(chunk_axis_attention(r, hd, qkv, sctx, 1, B * T, N, a.spatial.rb));
+    else
+      U2_TRY(self_attention(r, hd, qkv, sctx, B * T, N, 3 * E, (int64_t)N * 3 * E, a.spatial.rb));
+    U2_TRY(linear(r, sctx, a.spatial.o, y, E, rows, E, E));
     // temporal: sequences of T chunks at each token position (svr.py:32-36); rows stay in (b t n) order
     bf16_t* y2 = (y == xa) ? xb : xa;
-    { const int e = qkv_proj(y, tp, qkv, rows, E, dry, st); if (e != U2_OK) return e; }
-    if (c.attn_type == 1) {
-      U2_RUN(rope_apply(qkv, B, T, N, H, d, 3 * E, c.max_seq_len, 0, st));
-      U2_RUN(rope_apply(qkv + E, B, T, N, H, d, 3 * E, c.max_seq_len, 0, st));
-    }
-    if (c.attn_type == 2 && B == 1) {  // sequence = the N tokens of a chunk, batch = chunk
-      AttnCore a;
-      a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.out = ctx;
-      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = (int64_t)N * 3 * E; a.ldo = E; a.o_bs = (int64_t)N * E;
-      a.nb = T; a.Sq = a.Skv = N; a.H = H; a.d = d; a.scale = scale;
-      const int e = attention_core(ar, a, dry, st);
-      if (e != U2_OK) return e;
-    } else if (c.attn_type == 2) {
-      // sequence = the B*N (batch, token) pairs of one chunk index: gather rows (b, t, n) -> (t, b, n), attend, scatter
-      const size_t mark = ar.off;
-      bf16_t* g = ar.get<bf16_t>((size_t)rows * 3 * E);
-      bf16_t* gc = ar.get<bf16_t>((size_t)rows * E);
-      U2_CHECK_WS(ar);
-      if (!dry)
-        for (int b = 0; b < B; ++b)
-          if (hipMemcpy2DAsync(g + (size_t)b * N * 3 * E, (size_t)B * N * 3 * E * 2, qkv + (size_t)b * T * N * 3 * E,
-                               (size_t)N * 3 * E * 2, (size_t)N * 3 * E * 2, T, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return U2_ERR_LAUNCH;
-      const int64_t S2 = (int64_t)B * N;
-      AttnCore a;
-      a.q = g; a.k = g + E; a.v = g + 2 * E; a.out = gc;
-      a.ldq = a.ldk = a.ldv = 3 * E; a.q_bs = a.k_bs = a.v_bs = S2 * 3 * E; a.ldo = E; a.o_bs = S2 * E;
-      a.nb = T; a.Sq = a.Skv = (int)S2; a.H = H; a.d = d; a.scale = scale;
-      const int e = attention_core(ar, a, dry, st);
-      if (e != U2_OK) return e;
-      if (!dry)
-        for (int b = 0; b < B; ++b)
-          if (hipMemcpy2DAsync(ctx + (size_t)b * T * N * E, (size_t)N * E * 2, gc + (size_t)b * N * E, (size_t)B * N * E * 2,
-                               (size_t)N * E * 2, T, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return U2_ERR_LAUNCH;
-      ar.off = mark;
-    } else {
-      const int e = chunk_axis_attention(ar, qkv, ctx, B, T, N, H, d, scale, tp.rb, c.max_seq_len, dry, st);
-      if (e != U2_OK) return e;
-    }
-    U2_RUN(linear(ctx, E, tp.wd, tp.bd, y2, E, rows, E, E, 0, nullptr, 0, st));
+    U2_TRY(packed_proj(r, y, {a.temporal.q, a.temporal.k, a.temporal.v}, qkv, rows, E));
+    if (c.attn_type == 1) U2_TRY(rope_qk(r, hd, qkv, B, T, N));
+    if (c.attn_type == 2 && B == 1)  // sequence = the N tokens of a chunk, batch = chunk
+      U2_TRY(self_attention(r, hd, qkv, sctx, T, N, 3 * E, (int64_t)N * 3 * E, a.temporal.rb));
+    else if (c.attn_type == 2)
+      U2_TRY(temporal_across_batch());
+    else
+      U2_TRY(chunk_axis_attention(r, hd, qkv, sctx, B, T, N, a.temporal.rb));
+    U2_TRY(linear(r, sctx, a.temporal.o, y2, E, rows, E, E));
     x = y2;
-    if (taps && !dry && taps->svr_out && taps->svr_out[l] &&
-        hipMemcpyAsync(taps->svr_out[l], x, (size_t)rows * E * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return U2_ERR_LAUNCH;
+    return tap(r, slot(taps.svr_out, l), x, (size_t)rows * E);
   }
 
-  if (svr_out && !dry) {  // optional tap: the refined tokens the selection stage sees (parity tests)
-    if (hipMemcpyAsync(svr_out, x, (size_t)rows * E * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return U2_ERR_LAUNCH;
-  }
-
-  // ---------------- token selection (svr.py:171)
-  bf16_t* sel = ar.get<bf16_t>((size_t)B * k * E);
-  U2_CHECK_WS(ar);
-  if (c.enable_diffts) {
-    // DifferentiableTokenSelection (svr.py:101-117): weights = softmax_tokens(score_net(x)/tau); out = W^T X.
-    // Computed operand-swapped so the scores land transposed: scT[r][tok] = score_w[r] . x[tok] + b[r].
-    const size_t mark = ar.off;
+  // ---------------- token selection (svr.py:171): x -> sel (B, k, E)
+  // DifferentiableTokenSelection (svr.py:101-117): weights = softmax_tokens(score_net(x)/tau); out = W^T X.
+  // Computed operand-swapped so the scores land transposed: scT[r][tok] = score_w[r] . x[tok] + b[r].
+  int select_diffts(const bf16_t* x, bf16_t* sel) {
+    const int TN = T * N;
+    const size_t mark = r.ar.off;
     const int64_t ldS = round_up(TN, 8);
-    float* scT = ar.get<float>((size_t)B * k * ldS);
-    bf16_t* P = ar.get<bf16_t>((size_t)B * k * ldS);
+    float* scT = r.ar.get<float>((size_t)B * k * ldS);
+    bf16_t* P = r.ar.get<bf16_t>((size_t)B * k * ldS);
     const bool x_in_place = opts().kmajor_b && !(TN & 7);  // the aggregation reads X as a K-major B operand (rows = tokens)
-    bf16_t* Xt = x_in_place ? nullptr : ar.get<bf16_t>((size_t)B * E * ldS);
-    U2_CHECK_WS(ar);
+    bf16_t* Xt = x_in_place ? nullptr : r.ar.get<bf16_t>((size_t)B * E * ldS);
+    U2_CHECK_WS(r.ar);
     {
       GemmDesc g;
-      g.A = wp(i_sel); g.B = x; g.C = scT; g.bias = wp(i_sel + 1);
+      g.A = w.score.w; g.B = x; g.C = scT; g.bias = w.score.b;
       g.M = k; g.N = TN; g.K = E; g.lda = E; g.ldb = E; g.ldc = ldS;
       g.nz = B; g.sBb = (int64_t)TN * E; g.sCb = (int64_t)k * ldS;
       g.flags = GEMM_BIAS_M | GEMM_OUT_F32;
-      U2_RUN(gemm_bf16(g, st));
+      U2_RUN(gemm_bf16(g, r.st));
     }
-    U2_RUN(softmax_rows(scT, P, B, k, TN, ldS, ldS, (int64_t)k * ldS, (int64_t)k * ldS, 1.0f / c.diffts_tau, nullptr, 1,
-                        0, st));
+    U2_RUN(softmax_rows(scT, P, B, k, TN, ldS, ldS, (int64_t)k * ldS, (int64_t)k * ldS, 1.0f / c.diffts_tau, nullptr, 1, 0, r.st));
     {
       GemmDesc g;
       g.A = P; g.C = sel;
@@ -506,174 +495,177 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
         g.B = x; g.K = TN; g.ldb = E; g.sBb = (int64_t)TN * E;
         g.flags = GEMM_B_KMAJOR;
       } else {
-        U2_RUN(transpose_bf16(x, Xt, B, TN, E, E, ldS, (int64_t)TN * E, (int64_t)E * ldS, 0, st));
+        U2_RUN(transpose_bf16(x, Xt, B, TN, E, E, ldS, (int64_t)TN * E, (int64_t)E * ldS, 0, r.st));
         g.B = Xt; g.K = (int)ldS; g.ldb = ldS; g.sBb = (int64_t)E * ldS;
       }
-      U2_RUN(gemm_bf16(g, st));
+      U2_RUN(gemm_bf16(g, r.st));
     }
-    ar.off = mark;
-  } else {
-    // TokenSelection (svr.py:75-91): hard top-k over the flattened (t n) axis, sorted by score
-    const size_t mark = ar.off;
-    float* scores = ar.get<float>((size_t)rows);
-    int64_t* idx = topk_idx_out ? topk_idx_out : ar.get<int64_t>((size_t)B * k);
-    U2_CHECK_WS(ar);
-    U2_RUN(score_gemv(x, wp(i_sel), wp(i_sel + 1), scores, (int)rows, E, st));
-    U2_RUN(topk_sorted(scores, idx, B, TN, k, st));
-    U2_RUN(gather_rows(x, idx, sel, B, TN, k, E, st));
-    ar.off = mark;
-  }
-
-  // ---------------- multi-scale pooling (svr.py:173-184)
-  const bf16_t* V = sel;
-  int Lv = k;
-  if (c.use_multi_scale) {
-    Lv = k + k / 2 + k / 4;
-    bf16_t* pooled = ar.get<bf16_t>((size_t)B * Lv * E);
-    float* gws = ar.get<float>((size_t)B * 3 * 16 * cdiv(E, 256));
-    U2_CHECK_WS(ar);
-    U2_RUN(multiscale_pool(sel, pooled, B, k, E, c.enable_dmtp ? wp(i_gate) : nullptr,
-                           c.enable_dmtp ? wp(i_gate + 1) : nullptr, gws, st));
-    V = pooled;
-  }
-  if (taps && !dry) {  // parity taps: the visual tokens the aggregation stage attends to
-    if (taps->visual_out &&
-        hipMemcpyAsync(taps->visual_out, V, (size_t)B * Lv * E * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return U2_ERR_LAUNCH;
-    if (taps->visual_in) V = reinterpret_cast<const bf16_t*>(taps->visual_in);
-  }
-
-  // ---------------- TTA: TextConditionTokenAggregatorModel (tta.py:126-140)
-  const int64_t qrows = (int64_t)B * Q;
-  bf16_t* qa = ar.get<bf16_t>((size_t)qrows * E);
-  bf16_t* qb = ar.get<bf16_t>((size_t)qrows * E);
-  bf16_t* qc = ar.get<bf16_t>((size_t)qrows * E);
-  bf16_t* qproj = ar.get<bf16_t>((size_t)qrows * 3 * E);
-  bf16_t* qctx = ar.get<bf16_t>((size_t)qrows * E);
-  bf16_t* qo = ar.get<bf16_t>((size_t)qrows * E);
-  // k | v of the two cross attentions of every layer: one buffer each, filled on the side stream (or in line)
-  SideStream* side = (!dry && opts().tta_overlap && L > 0 && L <= 7) ? cx.side_for(st) : nullptr;
-  const bool overlap = dry ? (L > 0 && L <= 7) : side != nullptr;  // dry: size for the larger (overlapped) layout
-  const int Lmax = Lv > c.Lt ? Lv : c.Lt;
-  bf16_t* kv_inline = overlap ? nullptr : ar.get<bf16_t>((size_t)B * Lmax * 2 * E);
-  bf16_t* kv_v[8] = {};
-  bf16_t* kv_t[8] = {};
-  if (overlap)
-    for (int l = 0; l < L; ++l) {
-      kv_v[l] = ar.get<bf16_t>((size_t)B * Lv * 2 * E);
-      kv_t[l] = ar.get<bf16_t>((size_t)B * c.Lt * 2 * E);
-    }
-  bf16_t* k_lin = ar.get<bf16_t>((size_t)B * Lv * E);  // key projection of the final linear aggregation
-  U2_CHECK_WS(ar);
-  auto kv_proj = [&](const Att& a, const bf16_t* src, int Ls, bf16_t* kv, hipStream_t s_) -> int {
-    if (!dry && kv_packed(a, E)) {
-      U2_RUN(linear(src, E, a.wk, a.bk, kv, 2 * E, (int64_t)B * Ls, E, 2 * E, 0, nullptr, 0, s_));
-    } else {
-      U2_RUN(linear(src, E, a.wk, a.bk, kv, 2 * E, (int64_t)B * Ls, E, E, 0, nullptr, 0, s_));
-      U2_RUN(linear(src, E, a.wv, a.bv, kv + E, 2 * E, (int64_t)B * Ls, E, E, 0, nullptr, 0, s_));
-    }
+    r.ar.off = mark;
     return U2_OK;
-  };
-  if (overlap && !dry) {
+  }
+  // TokenSelection (svr.py:75-91): hard top-k over the flattened (t n) axis, sorted by score
+  int select_topk(const bf16_t* x, bf16_t* sel, int64_t* topk_idx_out) {
+    const size_t mark = r.ar.off;
+    float* scores = r.ar.get<float>((size_t)rows);
+    int64_t* idx = topk_idx_out ? topk_idx_out : r.ar.get<int64_t>((size_t)B * k);
+    U2_CHECK_WS(r.ar);
+    U2_RUN(score_gemv(x, w.score.w, w.score.b, scores, (int)rows, E, r.st));
+    U2_RUN(topk_sorted(scores, idx, B, T * N, k, r.st));
+    U2_RUN(gather_rows(x, idx, sel, B, T * N, k, E, r.st));
+    r.ar.off = mark;
+    return U2_OK;
+  }
+
+  // ---------------- multi-scale pooling (svr.py:173-184): sel -> V, Lv
+  int multiscale_pooling(const bf16_t* sel) {
+    V = sel, Lv = k;
+    if (c.use_multi_scale) {
+      Lv = k + k / 2 + k / 4;
+      bf16_t* pooled = r.ar.get<bf16_t>((size_t)B * Lv * E);
+      float* gws = r.ar.get<float>((size_t)B * 3 * 16 * cdiv(E, 256));
+      U2_CHECK_WS(r.ar);
+      U2_RUN(multiscale_pool(sel, pooled, B, k, E, w.gate.w, w.gate.b, gws, r.st));
+      V = pooled;
+    }
+    // parity taps: the visual tokens the aggregation stage attends to
+    U2_TRY(tap(r, taps.visual_out, V, (size_t)B * Lv * E));
+    if (taps.visual_in) V = reinterpret_cast<const bf16_t*>(taps.visual_in);
+    return U2_OK;
+  }
+
+  // ---------------- the TTA's buffers, and the side-stream prefetch of what depends on V and t_token alone: k | v of the two cross
+  // attentions of every layer and the aggregation's keys (at most 7 layers: a SideStream has 16 events)
+  int tta_prefetch() {
+    qa = r.ar.get<bf16_t>((size_t)qrows * E);
+    qb = r.ar.get<bf16_t>((size_t)qrows * E);
+    qc = r.ar.get<bf16_t>((size_t)qrows * E);
+    qproj = r.ar.get<bf16_t>((size_t)qrows * 3 * E);
+    qctx = r.ar.get<bf16_t>((size_t)qrows * E);
+    qo = r.ar.get<bf16_t>((size_t)qrows * E);
+    side = (!r.dry && opts().tta_overlap && L > 0 && L <= 7) ? ctx().side_for(r.st) : nullptr;
+    overlap = r.dry ? (L > 0 && L <= 7) : side != nullptr;  // dry: size for the larger (overlapped) layout
+    kv_inline = overlap ? nullptr : r.ar.get<bf16_t>((size_t)B * std::max(Lv, c.Lt) * 2 * E);
+    if (overlap)
+      for (int l = 0; l < L; ++l) {
+        kv_v[l] = r.ar.get<bf16_t>((size_t)B * Lv * 2 * E);
+        kv_t[l] = r.ar.get<bf16_t>((size_t)B * c.Lt * 2 * E);
+      }
+    k_lin = r.ar.get<bf16_t>((size_t)B * Lv * E);
+    U2_CHECK_WS(r.ar);
+    if (!overlap || r.dry) return U2_OK;
+    const Run rs{r.ar, false, side->s};
     // fork: everything `st` has enqueued so far (V and t_token are final) precedes the side stream's work
-    if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
-      return U2_ERR_LAUNCH;
+    U2_TRY(hip_status(hipEventRecord(side->fork, r.st)));
+    U2_TRY(hip_status(hipStreamWaitEvent(side->s, side->fork, 0)));
     for (int l = 0; l < L; ++l) {
-      const int base = i_tta + 33 * l;
-      Att va = att_at(base + 9), ta = att_at(base + 18);
-      { const int e = kv_proj(va, V, Lv, kv_v[l], side->s); if (e != U2_OK) return e; }
-      if (hipEventRecord(side->done[2 * l], side->s) != hipSuccess) return U2_ERR_LAUNCH;
-      { const int e = kv_proj(ta, t_token, c.Lt, kv_t[l], side->s); if (e != U2_OK) return e; }
-      if (hipEventRecord(side->done[2 * l + 1], side->s) != hipSuccess) return U2_ERR_LAUNCH;
+      U2_TRY(packed_proj(rs, V, {w.tta[l].visual.k, w.tta[l].visual.v}, kv_v[l], (int64_t)B * Lv, E));
+      U2_TRY(hip_status(hipEventRecord(side->done[2 * l], side->s)));
+      U2_TRY(packed_proj(rs, t_token, {w.tta[l].text.k, w.tta[l].text.v}, kv_t[l], (int64_t)B * c.Lt, E));
+      U2_TRY(hip_status(hipEventRecord(side->done[2 * l + 1], side->s)));
     }
-    const Att la = att_at(i_lin);
-    U2_RUN(linear(V, E, la.wk, la.bk, k_lin, E, (int64_t)B * Lv, E, E, 0, nullptr, 0, side->s));
-    if (hipEventRecord(side->done[2 * L], side->s) != hipSuccess) return U2_ERR_LAUNCH;
+    U2_TRY(linear(rs, V, w.linagg.k, k_lin, E, (int64_t)B * Lv, E, E));
+    return hip_status(hipEventRecord(side->done[2 * L], side->s));
   }
-  U2_RUN(fill_rows(wp(0), qa, B, (int64_t)Q * E, (int64_t)Q * E, st));  // query_tokens.expand(B,-1,-1)
-  bf16_t* qcur = qa;
-  // kv_ready: index of the side-stream event that publishes `kv` (-1: compute it here)
-  auto cross = [&](const Att& a, const bf16_t* src, int Ls, const bf16_t* qin, bf16_t* dst, bf16_t* kv,
-                   int kv_ready) -> int {
-    // MultiHeadCrossAttention.forward (tta.py:42-69), is_compress = False
-    U2_RUN(linear(qin, E, a.wq, a.bq, qproj, E, qrows, E, E, 0, nullptr, 0, st));
-    if (kv_ready < 0) {
-      const int e = kv_proj(a, src, Ls, kv, st);
-      if (e != U2_OK) return e;
-    } else if (!dry) {
-      if (hipStreamWaitEvent(st, side->done[kv_ready], 0) != hipSuccess) return U2_ERR_LAUNCH;
-    }
-    AttnCore ac;
-    ac.q = qproj; ac.k = kv; ac.v = kv + E; ac.out = qctx;
-    ac.ldq = ac.ldo = E; ac.ldk = ac.ldv = 2 * E; ac.q_bs = ac.o_bs = (int64_t)Q * E; ac.k_bs = ac.v_bs = (int64_t)Ls * 2 * E;
-    ac.nb = B; ac.Sq = Q; ac.Skv = Ls; ac.H = H; ac.d = d; ac.scale = scale;
-    const int e = attention_core(ar, ac, dry, st);
-    if (e != U2_OK) return e;
-    U2_RUN(linear(qctx, E, a.wd, a.bd, dst, E, qrows, E, E, 0, nullptr, 0, st));
-    return U2_OK;
-  };
-  for (int l = 0; l < L; ++l) {
-    const int base = i_tta + 33 * l;
-    const Att sa = att_at(base);
-    Att va = att_at(base + 9), ta = att_at(base + 18);
-    va.rb = ta.rb = nullptr;
-    const bf16_t *ns_w = wp(base + 27), *ns_b = wp(base + 28), *nv_w = wp(base + 29), *nv_b = wp(base + 30),
-                 *nt_w = wp(base + 31), *nt_b = wp(base + 32);
-    if (taps && !dry && taps->tta_in && taps->tta_in[l]) qcur = (bf16_t*)taps->tta_in[l];  // (only ever read)
+
+  // MultiHeadCrossAttention.forward (tta.py:42-69), is_compress = False: dst = dense(attn(wq qin, k | v of the Ls rows of src)).
+  // Prefetched: k | v are in kv once side-stream event `ready` has fired; otherwise they are computed into kv here.
+  int cross(const Att& a, const bf16_t* src, int Ls, const bf16_t* qin, bf16_t* dst, bf16_t* kv, int ready) {
+    U2_TRY(linear(r, qin, a.q, qproj, E, qrows, E, E));
+    if (overlap)
+      U2_RUN(hip_status(hipStreamWaitEvent(r.st, side->done[ready], 0)));
+    else
+      U2_TRY(packed_proj(r, src, {a.k, a.v}, kv, (int64_t)B * Ls, E));
+    U2_TRY(cross_attention(r, hd, qproj, kv, kv + E, 2 * E, qctx, B, Q, Ls));
+    return linear(r, qctx, a.o, dst, E, qrows, E, E);
+  }
+
+  // ---------------- TTA layer l (tta.py:93-107): three post-LN residual sub-layers on the query tokens.  qcur: input, then output.
+  int tta_layer(int l, bf16_t*& qcur) {
+    const TtaLayer& a = w.tta[l];
+    if (const void* in = slot(taps.tta_in, l)) qcur = (bf16_t*)in;  // (only ever read)
     bf16_t* s1 = (qcur == qa) ? qb : qa;
-    bf16_t* s2 = qc;
     // self attention on the query tokens + post-LN residual (tta.py:94-96)
     if (c.attn_type == 2 && B == 1) {
       // (B = 1, Q, E) read sequence-first: every query token is a batch entry with a sequence of ONE key, whose
       // softmax weight is exactly 1 -> the context is the value projection itself (tta.py:84,94)
-      U2_RUN(linear(qcur, E, sa.wv, sa.bv, qctx, E, qrows, E, E, 0, nullptr, 0, st));
-    } else if (c.attn_type == 2) {
-      // (B, Q, E) read sequence-first: the sequence is the B batch entries of one query index
-      { const int e = qkv_proj(qcur, sa, qproj, qrows, E, dry, st); if (e != U2_OK) return e; }
-      const int e = chunk_axis_attention(ar, qproj, qctx, 1, B, Q, H, d, scale, nullptr, c.max_seq_len, dry, st);
-      if (e != U2_OK) return e;
+      U2_TRY(linear(r, qcur, a.self.v, qctx, E, qrows, E, E));
     } else {
-      { const int e = qkv_proj(qcur, sa, qproj, qrows, E, dry, st); if (e != U2_OK) return e; }
-      if (c.attn_type == 1) {
-        U2_RUN(rope_apply(qproj, B, Q, 1, H, d, 3 * E, c.max_seq_len, 0, st));
-        U2_RUN(rope_apply(qproj + E, B, Q, 1, H, d, 3 * E, c.max_seq_len, 0, st));
-      }
-      AttnCore ac;
-      ac.q = qproj; ac.k = qproj + E; ac.v = qproj + 2 * E; ac.out = qctx;
-      ac.ldq = ac.ldk = ac.ldv = 3 * E; ac.q_bs = ac.k_bs = ac.v_bs = (int64_t)Q * 3 * E; ac.ldo = E; ac.o_bs = (int64_t)Q * E;
-      ac.nb = B; ac.Sq = ac.Skv = Q; ac.H = H; ac.d = d; ac.scale = scale; ac.rel_bias = sa.rb; ac.max_len = c.max_seq_len;
-      const int e = attention_core(ar, ac, dry, st);
-      if (e != U2_OK) return e;
+      U2_TRY(packed_proj(r, qcur, {a.self.q, a.self.k, a.self.v}, qproj, qrows, E));
+      if (c.attn_type == 1) U2_TRY(rope_qk(r, hd, qproj, B, Q, 1));
+      if (c.attn_type == 2)  // (B, Q, E) read sequence-first: the sequence is the B batch entries of one query index
+        U2_TRY(chunk_axis_attention(r, hd, qproj, qctx, 1, B, Q, a.self.rb));
+      else
+        U2_TRY(self_attention(r, hd, qproj, qctx, B, Q, 3 * E, (int64_t)Q * 3 * E, a.self.rb));
     }
-    U2_RUN(linear(qctx, E, sa.wd, sa.bd, qo, E, qrows, E, E, 0, nullptr, 0, st));
-    U2_RUN(layernorm_bf16(qcur, qo, ns_w, ns_b, s1, 1, (int)qrows, E, 0, E, 0, E, 0, E, c.ln_eps, st));
+    U2_TRY(linear(r, qctx, a.self.o, qo, E, qrows, E, E));
+    U2_RUN(layernorm_dense(qcur, qo, a.norm_self.w, a.norm_self.b, s1, (int)qrows, E, c.ln_eps, r.st));
     // visual cross attention (tta.py:97-100)
-    { const int e = cross(va, V, Lv, s1, qo, overlap ? kv_v[l] : kv_inline, overlap ? 2 * l : -1); if (e != U2_OK) return e; }
-    U2_RUN(layernorm_bf16(s1, qo, nv_w, nv_b, s2, 1, (int)qrows, E, 0, E, 0, E, 0, E, c.ln_eps, st));
+    U2_TRY(cross(a.visual, V, Lv, s1, qo, overlap ? kv_v[l] : kv_inline, 2 * l));
+    U2_RUN(layernorm_dense(s1, qo, a.norm_v.w, a.norm_v.b, qc, (int)qrows, E, c.ln_eps, r.st));
     // text cross attention (tta.py:101-103) -- no padding mask in the reference
-    { const int e = cross(ta, t_token, c.Lt, s2, qo, overlap ? kv_t[l] : kv_inline, overlap ? 2 * l + 1 : -1); if (e != U2_OK) return e; }
-    U2_RUN(layernorm_bf16(s2, qo, nt_w, nt_b, s1, 1, (int)qrows, E, 0, E, 0, E, 0, E, c.ln_eps, st));
+    U2_TRY(cross(a.text, t_token, c.Lt, qc, qo, overlap ? kv_t[l] : kv_inline, 2 * l + 1));
+    U2_RUN(layernorm_dense(qc, qo, a.norm_t.w, a.norm_t.b, s1, (int)qrows, E, c.ln_eps, r.st));
     qcur = s1;
-    if (taps && !dry && taps->tta_out && taps->tta_out[l] &&
-        hipMemcpyAsync(taps->tta_out[l], qcur, (size_t)qrows * E * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return U2_ERR_LAUNCH;
+    return tap(r, slot(taps.tta_out, l), qcur, (size_t)qrows * E);
   }
+
   // ---------------- LinearAggregation (tta.py:109-116): is_compress=True -> V un-projected, no out-proj
-  {
-    const Att la = att_at(i_lin);
-    U2_RUN(linear(qcur, E, la.wq, la.bq, qproj, E, qrows, E, E, 0, nullptr, 0, st));
-    if (!overlap) {
-      U2_RUN(linear(V, E, la.wk, la.bk, k_lin, E, (int64_t)B * Lv, E, E, 0, nullptr, 0, st));
-    } else if (!dry) {
-      if (hipStreamWaitEvent(st, side->done[2 * L], 0) != hipSuccess) return U2_ERR_LAUNCH;
-    }
-    AttnCore ac;
-    ac.q = qproj; ac.k = k_lin; ac.v = V; ac.out = out;
-    ac.ldq = ac.ldk = ac.ldv = ac.ldo = E; ac.q_bs = ac.o_bs = (int64_t)Q * E; ac.k_bs = ac.v_bs = (int64_t)Lv * E;
-    ac.nb = B; ac.Sq = Q; ac.Skv = Lv; ac.H = H; ac.d = d; ac.scale = scale;
-    const int e = attention_core(ar, ac, dry, st);
-    if (e != U2_OK) return e;
+  int linear_aggregation(const bf16_t* qcur, bf16_t* out) {
+    U2_TRY(linear(r, qcur, w.linagg.q, qproj, E, qrows, E, E));
+    if (overlap)
+      U2_RUN(hip_status(hipStreamWaitEvent(r.st, side->done[2 * L], 0)));
+    else
+      U2_TRY(linear(r, V, w.linagg.k, k_lin, E, (int64_t)B * Lv, E, E));
+    return cross_attention(r, hd, qproj, k_lin, V, E, out, B, Q, Lv);
   }
+};
+}  // namespace
+
+int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_token, const bf16_t* t_token,
+                      bf16_t* out, int64_t* topk_idx_out, bf16_t* svr_out, const TokTaps* taps, void* ws, size_t ws_bytes,
+                      bool dry, size_t* peak, hipStream_t st) {
+  if (c.B <= 0 || c.T <= 0 || c.N <= 0 || c.E <= 0 || c.Lt <= 0 || c.num_heads <= 0 || c.num_layers < 0) return U2_ERR_ARG;
+  if (c.E % c.num_heads || (c.E / c.num_heads) % 8 || c.top_k <= 0 || c.num_query <= 0) return U2_ERR_ARG;
+  if (c.attn_type < 0 || c.attn_type > 2) return U2_ERR_ARG;
+  if (!dry && (!W || !v_token || !t_token || !out)) return U2_ERR_ARG;
+  const int B = c.B, E = c.E, d = E / c.num_heads, L = c.num_layers, k = c.top_k;
+  if (!c.enable_diffts && k > c.T * c.N) return U2_ERR_ARG;                     // torch.topk would raise
+  if (c.N > c.max_seq_len || c.T > c.max_seq_len || c.num_query > c.max_seq_len) return U2_ERR_ARG;  // rma.py:64-68 index range
+  const TokWeights w = tok_weights(c, Table{dry ? nullptr : W});
+
+  Arena ar(ws, ws_bytes, dry);
+  // split-K scratch for the skinny linear layers of this forward (M = 256 queries against E x E weights); registered
+  // for this stream only while the launches below are being enqueued
+  // (24 MB covers the E x E products; the TTA self-attention's packed q|k|v product takes the big-tile kernel in 4 K slices:
+  //  4 x rows x 3E fp32)
+  const size_t kSplitK = std::max<size_t>(24u << 20, (size_t)16 * B * c.num_query * 3 * E);
+  char* skw = ar.get<char>(kSplitK);
+  U2_CHECK_WS(ar);
+  ScratchScope scratch_scope(ctx(), st, skw, kSplitK, !dry);
+  Tok t{c, Run{ar, dry, st}, w, (taps && !dry) ? *taps : TokTaps{}, t_token, B, c.T, c.N, E, L, c.num_query, k,
+        Heads{c.num_heads, d, 1.0f / sqrtf((float)d), c.max_seq_len}, (int64_t)B * c.T * c.N, (int64_t)B * c.num_query};
+  const Run& r = t.r;
+  t.xa = ar.get<bf16_t>((size_t)t.rows * E);
+  t.xb = ar.get<bf16_t>((size_t)t.rows * E);
+  t.qkv = ar.get<bf16_t>((size_t)t.rows * 3 * E);
+  t.sctx = ar.get<bf16_t>((size_t)t.rows * E);
+  U2_CHECK_WS(ar);
+
+  // The reference's forward (u2Tokenizer.py:40-47): SpatioTemporalSignificanceScoring (svr.py:50-62) ...
+  const bf16_t* x = v_token;
+  for (int l = 0; l < L; ++l) U2_TRY(t.svr_layer(l, x));
+  U2_TRY(tap(r, svr_out, x, (size_t)t.rows * E));  // optional: the refined tokens the selection stage sees (parity tests)
+  // ... token selection and pooling (svr.py:171-184) ...
+  bf16_t* sel = ar.get<bf16_t>((size_t)B * k * E);
+  U2_CHECK_WS(ar);
+  U2_TRY(c.enable_diffts ? t.select_diffts(x, sel) : t.select_topk(x, sel, topk_idx_out));
+  U2_TRY(t.multiscale_pooling(sel));
+  // ... TextConditionTokenAggregatorModel (tta.py:126-140)
+  U2_TRY(t.tta_prefetch());
+  U2_RUN(fill_rows(w.query, t.qa, B, (int64_t)t.Q * E, (int64_t)t.Q * E, st));  // query_tokens.expand(B,-1,-1)
+  bf16_t* qcur = t.qa;
+  for (int l = 0; l < L; ++l) U2_TRY(t.tta_layer(l, qcur));
+  U2_TRY(t.linear_aggregation(qcur, out));
   if (peak) *peak = ar.peak;
   U2_CHECK_WS(ar);
   return U2_OK;
