@@ -200,7 +200,8 @@ int u2tok_tokenizer_forward_taps(const u2tok_tokenizer_config* cfg, const void* 
                                  void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
 /* Replaces embed_tokens(ids) + the splice of u2_arch.py:109,113-116:
- * out[b][s] = (1 <= s <= nfeat) ? feats[b][s-1] : table[ids[b][s]].  nfeat = 0 / feats = null: plain lookup. */
+ * out[b][s] = (1 <= s <= nfeat) ? feats[b][s-1] : table[ids[b][s]].  nfeat = 0 / feats = null: plain lookup.
+ * An id outside [0, vocab) is clamped to the nearest table row (id < 0 -> row 0, id >= vocab -> row vocab - 1). */
 int u2tok_embed_splice(const void* table, const int64_t* ids, const void* feats, void* out, int32_t B, int32_t S,
                        int32_t E, int32_t nfeat, int64_t vocab, u2tok_stream_t stream);
 
@@ -250,6 +251,13 @@ int u2tok_gemm_bf16(const void* A, const void* B, void* C, const void* bias, con
                     int64_t sRh, float alpha, int32_t flags, u2tok_stream_t stream);
 int u2tok_layernorm_bf16(const void* x, const void* res, const void* w, const void* b, void* y, int32_t rows,
                          int32_t C, float eps, u2tok_stream_t stream);
+/* The strided form: y[b][r] = LN(x[b][r] (+ res[b][r])) w + b for b < nb, r < rows; row r of batch entry b at
+ * x + b*x_bs + r*x_ld (elements; res and y alike).  res = null: no residual, res_bs / res_ld unread.  C % 8 == 0, C <= 8192,
+ * every stride a multiple of 8 elements, every pointer 16-byte aligned; U2TOK_ERR_ARG otherwise.  Only the C columns of each
+ * row are written.  (The ViT's final norm is two such calls: patch rows, then one cls row per batch entry.) */
+int u2tok_layernorm_rows(const void* x, const void* res, const void* w, const void* b, void* y, int32_t nb, int32_t rows,
+                         int32_t C, int64_t x_bs, int64_t x_ld, int64_t res_bs, int64_t res_ld, int64_t y_bs, int64_t y_ld,
+                         float eps, u2tok_stream_t stream);
 int u2tok_softmax_rows(const float* S, void* P, int32_t nz, int32_t rows, int32_t n, int64_t lds, int64_t ldp,
                        float scale, const void* rel_bias, int32_t H, int32_t max_len, u2tok_stream_t stream);
 /* out[z][c][r] = in[z][r][c], pad columns zeroed.  perm16 != 0 (needs ld_out % 16 == 0): inside each group of 16

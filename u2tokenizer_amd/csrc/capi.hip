@@ -190,6 +190,13 @@ int u2tok_layernorm_bf16(const void* x, const void* res, const void* w, const vo
   return layernorm_dense(BF(x), BF(res), BF(w), BF(b), BFW(y), rows, C, eps, ST(stream));
 }
 
+int u2tok_layernorm_rows(const void* x, const void* res, const void* w, const void* b, void* y, int32_t nb, int32_t rows,
+                         int32_t C, int64_t x_bs, int64_t x_ld, int64_t res_bs, int64_t res_ld, int64_t y_bs, int64_t y_ld,
+                         float eps, u2tok_stream_t stream) {
+  return layernorm_bf16(BF(x), BF(res), BF(w), BF(b), BFW(y), nb, rows, C, x_bs, x_ld, res_bs, res_ld, y_bs, y_ld, eps,
+                        ST(stream));
+}
+
 int u2tok_softmax_rows(const float* S, void* P, int32_t nz, int32_t rows, int32_t n, int64_t lds, int64_t ldp,
                        float scale, const void* rel_bias, int32_t H, int32_t max_len, u2tok_stream_t stream) {
   return softmax_rows(S, BFW(P), nz, rows, n, lds, ldp, (int64_t)rows * lds, (int64_t)rows * ldp, scale, BF(rel_bias), H,
