@@ -422,6 +422,37 @@ int u2tok_decoder_decode_pre(const u2tok_decode_config* cfg, const u2tok_decode_
 int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* qkv,
                               const void* K, const void* V, int32_t T, int64_t kv_stride, int32_t batched, const int32_t* kv_start,
                               void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- one decode step of the WHOLE decoder stack in one call: for each of the n_layers layers exactly the launches of
+ * u2tok_decoder_decode_pre followed by u2tok_decoder_decode_post, in their order, on the caller's stream (no graph, nothing
+ * captured), so every value has the bits the per-layer calls give it.  Layer l reads the hidden state layer l - 1 wrote (layer 0: x,
+ * (B, E) rows) -- it goes through two (B, E) rows of the workspace --; after the last layer the stack's final RMSNorm
+ * (w_final_norm, final_eps) writes out (B, E); w_final_norm NULL: out receives the last hidden state as it is.
+ * Per layer: its config and descriptor (the weight form may differ from layer to layer; B and E may not), its append-in-place cache
+ * buffers k_cache / v_cache (B, Hkv, capacity, D) with kv_stride = capacity * D, the position s_off the step's k / v rows are
+ * written at, and the positions k_first .. k_first + T - 1 <= s_off the attention reads (a sliding-window layer: the last min(T, W)).
+ * cos / sin / cos_sin_f32 / cs_ld, batched and kv_start: as in the per-layer calls, the same for every layer.
+ * EVERY refusal of EVERY layer -- the argument checks of both halves, the weight forms' demands, the adapter groups', the
+ * products' and row kernels' own, workspace size, kv_stride -- is evaluated before the first launch: an error code means nothing
+ * was launched and no cache row was written.  The library keeps no pointer after the call returns.
+ * workspace: u2tok_decoder_decode_stack_workspace_bytes(L, n_layers) bytes (0: descriptors it refuses), 256-byte aligned; its
+ * first 4 bytes are the ticket of the tail norms: zeroed ONCE by whoever allocates the workspace, left zero by every call.
+ * tail_norm != 0: the three RMSNorms that follow a product with a residual -- o -> the post-attention norm, down of layer l -> the
+ * input norm of layer l + 1, the last down -> the final norm -- run in the tail of that product's launch (u2tok_gemm_rows_norm)
+ * instead of a launch of their own, with the same bits; a product followed by an adapter group, a product a tile kernel runs and a
+ * row wider than 4096 keep the separate launch. */
+typedef struct u2tok_decode_stack_layer {
+  const u2tok_decode_config* cfg;    /* per layer: wform may differ between layers */
+  const u2tok_decode_layer*  layer;
+  void *k_cache, *v_cache;           /* the layer's append-in-place buffers (B, Hkv, capacity, D) */
+  int64_t kv_stride;
+  int32_t s_off;                     /* position the step's k / v rows are written at */
+  int32_t k_first, T;                /* attention reads positions k_first .. k_first + T - 1 (window layers: the last min(T, W)) */
+} u2tok_decode_stack_layer;
+size_t u2tok_decoder_decode_stack_workspace_bytes(const u2tok_decode_stack_layer* L, int32_t n_layers);
+int u2tok_decoder_decode_stack(const u2tok_decode_stack_layer* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                               int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start,
+                               const void* w_final_norm /* NULL: none */, float final_eps, int32_t tail_norm, void* out,
+                               void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 /* ---- products on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
  * attention and the KV cache stay in the element type).  A product is exactly x . (scale[n] * e4m3(W8[n][:])) with fp32
  * accumulation -- the codes are widened to the element type in registers, where every e4m3 value is exact --, so all the loss is
@@ -468,6 +499,19 @@ int u2tok_gemm_rows_w4(const void* A, const void* W4, const uint8_t* S, void* C,
  * of u2tok_gemm_rows_w8_wide.  Bit-repeatable. */
 int u2tok_gemm_rows(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K,
                     int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream);
+/* The few-rows product with the RMSNorm of its finished rows in the SAME launch: C as u2tok_gemm_rows (wform = 0; scale ignored),
+ * u2tok_gemm_rows_w8_wide (wform = 1; scale: fp32 per weight row) or u2tok_gemm_rows_w4 (wform = 2; scale: the e8m0 block-scale
+ * bytes, lds bytes between rows) computes it, bit for bit, and Yn (M, N; ldn elements between rows) = what u2tok_rmsnorm_bf16 makes
+ * of C with w_norm and eps, bit for bit.  Each workgroup releases its part of C at device scope and draws a ticket with an atomic
+ * add; the one that draws the last ticket acquires, norms the M rows (a wave per row) and puts the ticket back to 0 -- nobody
+ * waits for another workgroup.  ticket: 4 bytes of device memory, 4-byte aligned, that read 0 before the call (they read 0 again
+ * after it); two launches that may overlap must not share one.
+ * Only the non-pair form WITH a residual: flags 8, optionally | 1; C in the element type; N % 8 == 0, N <= 4096, ldc % 8 == 0,
+ * ldn % 8 == 0, C / w_norm / Yn 16-byte aligned.  The pair flag, fp32 C, no residual, a null w_norm / Yn / ticket, a misaligned
+ * ticket, and everything the plain product refuses: U2TOK_ERR_ARG, nothing launched, nothing written. */
+int u2tok_gemm_rows_norm(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K,
+                         int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, int32_t wform, const void* scale,
+                         int64_t lds, const void* w_norm, float eps, void* Yn, int64_t ldn, void* ticket, u2tok_stream_t stream);
 /* Batched decode attention: out[b] = softmax(q[b] K[b]^T scale over keys kv_start[b] <= j < T) V[b] for B sequences of ONE query
  * row each.  q / out: (B, Hq * D) rows, ldq / ldo elements apart (head h at column h * D); K / V: (B, Hkv, T, D), kv_stride
  * elements between (batch, kv head) entries (0: dense, T * D) -- an append-in-place buffer or the dense cache; D in {64, 96, 128},

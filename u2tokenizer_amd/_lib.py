@@ -82,6 +82,11 @@ class DecodeLayer(C.Structure):    # u2tok_decode_layer: raw addresses -- whoeve
                                           "lora")]   # lora: the address of a DecodeLora, or None
 
 
+class DecodeStackLayer(C.Structure):   # u2tok_decode_stack_layer: one layer of the whole-stack decode step
+    _fields_ = [("cfg", C.c_void_p), ("layer", C.c_void_p), ("k_cache", C.c_void_p), ("v_cache", C.c_void_p),
+                ("kv_stride", C.c_int64), ("s_off", C.c_int32), ("k_first", C.c_int32), ("T", C.c_int32)]
+
+
 class TokTaps(C.Structure):
     _fields_ = [("svr_in", C.POINTER(C.c_void_p)), ("svr_out", C.POINTER(C.c_void_p)), ("visual_in", C.c_void_p),
                 ("visual_out", C.c_void_p), ("tta_in", C.POINTER(C.c_void_p)), ("tta_out", C.POINTER(C.c_void_p))]
@@ -156,12 +161,20 @@ SIGNATURES = {
     "u2tok_decoder_decode_pre": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     # cfg, layer, x, qkv, K, V, T, kv_stride, batched, kv_start, out, workspace, workspace_bytes, stream
     "u2tok_decoder_decode_post": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # layers, n_layers
+    "u2tok_decoder_decode_stack_workspace_bytes": (_sz, [_vp, _i32]),
+    # layers, n_layers, x, cos, sin, cos_sin_f32, cs_ld, batched, kv_start, w_final_norm, final_eps, tail_norm, out, workspace,
+    # workspace_bytes, stream
+    "u2tok_decoder_decode_stack": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
     "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_gemm_rows_w8_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     # A, W4, S, C, bias, R, M, N, K, lda, ldw, lds, ldc, ldr, flags, stream
     "u2tok_gemm_rows_w4": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     # A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream
     "u2tok_gemm_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, wform, scale, lds, w_norm, eps, Yn, ldn, ticket, stream
+    "u2tok_gemm_rows_norm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _f32,
+                                    _vp, _i64, _vp, _vp]),
     "u2tok_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "u2tok_decode_attention": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),
     "u2tok_rope_apply": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),

@@ -2,6 +2,7 @@
 #include <math.h>
 #include <string.h>
 #include <new>
+#include <vector>
 #include "pipeline.h"
 
 using namespace u2;
@@ -366,16 +367,54 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* c, const u2tok_decode_l
   return decoder_decode_post(cfg, d, BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out), workspace,
                              workspace_bytes, ST(stream));
 }
-// ---- the few-rows product (gemm_rows.hip): one filler for the four exports; a quantised form without its scales is refused here
+// ---- the whole-stack step (decoder.hip): the layers' descriptors decoded as the two per-layer entries decode theirs, nothing kept
+static int stack_args(const u2tok_decode_stack_layer* L, int32_t n, std::vector<DecodeStackLayer>& v) {
+  if (!L || n <= 0) return U2_ERR_ARG;
+  try { v.resize((size_t)n); } catch (const std::bad_alloc&) { return U2_ERR_ARG; }
+  for (int32_t i = 0; i < n; ++i) {
+    DecodeStackLayer& s = v[(size_t)i];
+    const int e = dec_args(L[i].cfg, L[i].layer, s.cfg, s.layer);
+    if (e != U2_OK) return e;
+    s.kc = BFW(L[i].k_cache); s.vc = BFW(L[i].v_cache);
+    s.kv_stride = L[i].kv_stride; s.s_off = L[i].s_off; s.k_first = L[i].k_first; s.T = L[i].T;
+  }
+  return U2_OK;
+}
+size_t u2tok_decoder_decode_stack_workspace_bytes(const u2tok_decode_stack_layer* L, int32_t n_layers) {
+  std::vector<DecodeStackLayer> v;
+  return stack_args(L, n_layers, v) == U2_OK ? decoder_decode_stack_workspace_bytes(v.data(), n_layers) : 0;
+}
+int u2tok_decoder_decode_stack(const u2tok_decode_stack_layer* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                               int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start, const void* w_final_norm,
+                               float final_eps, int32_t tail_norm, void* out, void* workspace, size_t workspace_bytes,
+                               u2tok_stream_t stream) {
+  std::vector<DecodeStackLayer> v;
+  const int e = stack_args(L, n_layers, v);
+  if (e != U2_OK) return e;
+  return decoder_decode_stack(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, batched != 0, kv_start, BF(w_final_norm), final_eps,
+                              tail_norm != 0, BFW(out), workspace, workspace_bytes, ST(stream));
+}
+// ---- the few-rows product (gemm_rows.hip): one filler for the five exports; a quantised form without its scales is refused here
 static int rows(WForm form, const void* A, const void* W, const void* scale, int64_t lds, void* C, const void* bias, const void* R,
-                int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
+                int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream,
+                const RowsNorm& norm = RowsNorm{}) {
   if (form != WForm::ELEM && !scale) return U2_ERR_ARG;
   RowsArgs a;
   a.A = BF(A); a.W = W; a.scale = scale; a.form = form; a.C = C; a.bias = BF(bias); a.R = BF(R);
   a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.ldw = ldw; a.lds = lds; a.ldc = ldc; a.ldr = ldr;
   a.flags = flags;
+  a.norm = norm;
   return gemm_rows(a, ST(stream));
+}
+// (with the RMSNorm of the finished rows in the launch's tail; a null norm weight is refused: the plain products are the four below)
+int u2tok_gemm_rows_norm(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K, int64_t lda,
+                         int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, int32_t wform, const void* scale, int64_t lds,
+                         const void* w_norm, float eps, void* Yn, int64_t ldn, void* ticket, u2tok_stream_t stream) {
+  if (!w_norm || !wform_known((WForm)wform)) return U2_ERR_ARG;
+  RowsNorm nm;
+  nm.w = BF(w_norm); nm.Yn = BFW(Yn); nm.ticket = reinterpret_cast<uint32_t*>(ticket); nm.ld = ldn; nm.eps = eps;
+  return rows((WForm)wform, A, W, scale, lds, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream, nm);
 }
 int u2tok_gemm_rows_w8(const void* A, const void* W8, const float* scale, void* C, const void* bias, const void* R, int32_t M, int32_t N,
                        int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {

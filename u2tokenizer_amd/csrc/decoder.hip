@@ -5,7 +5,7 @@
 //   RMSNorm -> packed q|k|v GEMM -> per-head RMSNorm (Qwen3) + rotary embedding -> causal grouped-query attention
 //   (tokattn.hip) -> out-projection GEMM (+ residual) -> RMSNorm -> packed gate|up GEMM -> SiLU(gate) * up -> down GEMM (+ residual)
 // and these are the HBM-bound pieces between the GEMMs.  All bf16 in / out, fp32 arithmetic, 16-byte accesses.
-#include "kernels.h"
+#include "rows.h"
 
 namespace u2 {
 
@@ -16,44 +16,21 @@ template <int NC>  // 16-byte chunks per lane held in registers: C <= NC * 512
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                       bf16_t* __restrict__ y, int64_t rows, int C, int64_t ldx, int64_t ldy,
                                                       float eps) {
-  const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const bf16_t* xp = x + row * ldx;
-  bf16_t* yp = y + row * ldy;
-  const int nchunk = C >> 3;
-  uint4 v[NC];
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    const int c = i * 64 + lane;
-    v[i] = uint4{0, 0, 0, 0};
-    if (c < nchunk) {
-      v[i] = *reinterpret_cast<const uint4*>(xp + c * 8);
-      const float a0 = bf16lo(v[i].x), a1 = bf16hi(v[i].x), a2 = bf16lo(v[i].y), a3 = bf16hi(v[i].y);
-      const float a4 = bf16lo(v[i].z), a5 = bf16hi(v[i].z), a6 = bf16lo(v[i].w), a7 = bf16hi(v[i].w);
-      sq += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3 + a4 * a4 + a5 * a5 + a6 * a6 + a7 * a7;
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    const int c = i * 64 + lane;
-    if (c < nchunk) {
-      const uint4 uw = *reinterpret_cast<const uint4*>(w + c * 8);
-      const uint4 n = uint4{pack2_bf16(bf16lo(v[i].x) * rstd, bf16hi(v[i].x) * rstd), pack2_bf16(bf16lo(v[i].y) * rstd, bf16hi(v[i].y) * rstd),
-                            pack2_bf16(bf16lo(v[i].z) * rstd, bf16hi(v[i].z) * rstd), pack2_bf16(bf16lo(v[i].w) * rstd, bf16hi(v[i].w) * rstd)};
-      *reinterpret_cast<uint4*>(yp + c * 8) =
-          uint4{pack2_bf16(bf16lo(n.x) * bf16lo(uw.x), bf16hi(n.x) * bf16hi(uw.x)), pack2_bf16(bf16lo(n.y) * bf16lo(uw.y), bf16hi(n.y) * bf16hi(uw.y)),
-                pack2_bf16(bf16lo(n.z) * bf16lo(uw.z), bf16hi(n.z) * bf16hi(uw.z)), pack2_bf16(bf16lo(n.w) * bf16lo(uw.w), bf16hi(n.w) * bf16hi(uw.w))};
-    }
-  }
+  rmsnorm_row<NC>(x + row * ldx, w, y + row * ldy, C, eps, threadIdx.x & 63);  // (rows.h: the norm in a product's tail runs the same row)
+}
+
+// (the refusals alone: the whole-stack step asks them of every layer before its first launch)
+static int rmsnorm_check(const bf16_t* x, const bf16_t* w, const bf16_t* y, int64_t rows, int C, int64_t ldx, int64_t ldy) {
+  if (!x || !w || !y || rows <= 0 || C <= 0 || (C & 7) || C > 8192 || (ldx & 7) || (ldy & 7)) return U2_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) || cdiv(rows, 4) > 0x7fffffff) return U2_ERR_ARG;
+  return U2_OK;
 }
 
 int rmsnorm_bf16(const bf16_t* x, const bf16_t* w, bf16_t* y, int64_t rows, int C, int64_t ldx, int64_t ldy, float eps,
                  hipStream_t stream) {
-  if (!x || !w || !y || rows <= 0 || C <= 0 || (C & 7) || C > 8192 || (ldx & 7) || (ldy & 7)) return U2_ERR_ARG;
-  if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) || cdiv(rows, 4) > 0x7fffffff) return U2_ERR_ARG;
+  if (const int e = rmsnorm_check(x, w, y, rows, C, ldx, ldy)) return e;
   ProfScope ps(PROF_ROWOP, 0, stream, (double)rows * C * 4.0);
   dim3 grid((unsigned)cdiv(rows, 4));
 #define U2_RN(NC) hipLaunchKernelGGL((rmsnorm_kernel<NC>), grid, dim3(256), 0, stream, x, w, y, rows, C, ldx, ldy, eps)
@@ -137,15 +114,22 @@ struct Bf16Val {  // bf16 cos / sin tables
   __device__ explicit operator float() const { return bf16_to_f32(v); }
 };
 
-int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32,
-                 int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int S,
-                 int64_t kv_stride, int s_off, hipStream_t stream) {
+// (the refusals alone, and kv_stride resolved: 0 = dense)
+static int qk_norm_rope_check(const bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int64_t rows, int Hq,
+                              int Hkv, int D, const bf16_t* kc, const bf16_t* vc, int S, int64_t& kv_stride, int s_off) {
   if (!qkv || !cosp || !sinp || rows <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 96 && D != 128) || (!wq) != (!wk)) return U2_ERR_ARG;
   if ((!kc) != (!vc) || (kc && (S <= 0 || rows % S))) return U2_ERR_ARG;
   if (kv_stride == 0) kv_stride = (int64_t)S * D;
   if (kc && (s_off < 0 || kv_stride < (int64_t)(s_off + S) * D)) return U2_ERR_ARG;
+  if (cdiv(rows * (Hq + Hkv + (kc ? Hkv : 0)), 4) > 0x7fffffff) return U2_ERR_ARG;
+  return U2_OK;
+}
+
+int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32,
+                 int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int S,
+                 int64_t kv_stride, int s_off, hipStream_t stream) {
+  if (const int e = qk_norm_rope_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, kc, vc, S, kv_stride, s_off)) return e;
   const int64_t items = rows * (Hq + Hkv + (kc ? Hkv : 0));
-  if (cdiv(items, 4) > 0x7fffffff) return U2_ERR_ARG;
   ProfScope ps(PROF_ROWOP, 0, stream, (double)items * D * 4.0);
   dim3 grid((unsigned)cdiv(items, 4));
 #define U2_QK(D_, T_)                                                                                                     \
@@ -201,20 +185,48 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
 // One projection of the step on a weight (w, scale) in `form`: the element type's product through the plan, codes (the step's
 // DecodeCfg::form) through the few-rows product on 1-byte or 4-bit weights (gemm_rows.hip).  pair: w = gate | up, y (rows, out / 2).
+// What the whole-stack step adds (the per-layer halves pass neither):
+//   check_only: the product's refusals alone, nothing launched -- gemm_rows_check, or the plan's own verdict;
+//   norm (w set): the RMSNorm that follows the product, asked for in the product's tail (RowsNorm: the non-pair form with a
+//     residual).  *normed says whether the launch carried it: yes where the few-rows kernel runs the product (always on codes and
+//     above 16 rows, else when the plan picks it) and takes the norm (gemm_rows_check); no: the caller launches rmsnorm_bf16.
 static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const void* scale, WForm form, const bf16_t* b, bf16_t* y,
-                      int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st) {
+                      int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st,
+                      bool check_only = false, const RowsNorm* norm = nullptr, bool* normed = nullptr) {
   RowsArgs a;
   a.A = x; a.W = w; a.scale = scale; a.form = form; a.C = y; a.bias = b; a.R = R;
   a.M = rows; a.N = out; a.K = in;
   a.lda = ldx; a.ldw = in / wform_facts(form).ldw_div; a.lds = in >> 5; a.ldc = ldy; a.ldr = ldr;
   a.flags = pair ? GEMM_SWIGLU : (b ? GEMM_BIAS_N : 0) | (R ? GEMM_RESIDUAL : 0);
-  if (form != WForm::ELEM || rows > 16) return gemm_rows(a, st);
+  if (normed) *normed = false;
+  bool tail = false;
+  if (norm && norm->w) {  // (a norm the tail does not take -- a row wider than it holds -- stays a launch of its own)
+    a.norm = *norm;
+    tail = gemm_rows_check(a) == U2_OK;
+    if (!tail) a.norm = RowsNorm{};
+  }
+  if (form != WForm::ELEM || rows > 16) {
+    if (check_only) return gemm_rows_check(a);
+    const int e = gemm_rows(a, st);
+    if (normed) *normed = tail && e == U2_OK;
+    return e;
+  }
   GemmDesc g;  // 16-bit weights, M <= 16: the plan (the same kernel, or a tile kernel when rows16_ok says no)
   g.A = x; g.B = reinterpret_cast<const bf16_t*>(w); g.C = y; g.bias = b; g.R = R;
   g.M = rows; g.N = out; g.K = in;
   g.lda = ldx; g.ldb = in; g.ldc = ldy; g.ldr = ldr;
   g.flags = a.flags;
-  return gemm_bf16(g, st);
+  if (!check_only && !tail) return gemm_bf16(g, st);
+  GemmDesc v = g;  // the plan's verdict without a launch
+  GemmPlan p;
+  const Scratch sc = ctx().scratch_of(st);
+  int e = gemm_validate(v);
+  if (e == U2_OK) e = gemm_plan(v, opts(), sc.p ? sc.bytes : 0, p);
+  if (e != U2_OK || check_only) return e;
+  if (p.nsteps != 1 || p.step[0].kind != GK_ROWS16) return gemm_bf16(g, st);  // (a tile kernel: no tail to carry the norm)
+  e = gemm_rows(a, st);  // the kernel the plan launches for this product, bit for bit, with the norm in its tail
+  if (normed) *normed = e == U2_OK;
+  return e;
 }
 
 // The adapter group of one product of the step (DecodeLora; lora_rows.hip): u at the head of the branch's scratch, the group's
@@ -252,20 +264,34 @@ size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
          256;
 }
 
+// What one call of a half does.  The per-layer entries check, then run (DEC_CHECK | DEC_RUN: today's two calls).  The whole-stack
+// step walks every half of every layer with DEC_CHECK alone -- the half's own refusals and, as nothing is launched behind them, those
+// its launchers would raise at their launch -- and only then runs them with DEC_RUN alone.
+enum : int { DEC_CHECK = 1, DEC_RUN = 2 };
+
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
-// (B, Hkv, 1, D) receive the new cache entries
-int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
-                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
-  if (!wform_step_ok(c, l, 0, 1)) return U2_ERR_ARG;
-  if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
+// (B, Hkv, 1, D) receive the new cache entries.  have_xn (the whole-stack step): the norm rode in the tail of the product that wrote x.
+static int dec_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
+                   bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes, hipStream_t st, int mode,
+                   bool have_xn) {
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
   const int nq = (c.Hq + 2 * c.Hkv) * c.D;
   const DecodeLora* lr = l.lora;
-  int e = lr ? dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, true, st) : U2_OK;
-  if (e != U2_OK) return e;
-  e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
+  int e = U2_OK;
+  if (mode & DEC_CHECK) {
+    if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
+    if (!wform_step_ok(c, l, 0, 1)) return U2_ERR_ARG;
+    if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
+    e = lr ? dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, true, st) : U2_OK;
+    if (e != U2_OK) return e;
+    if (!(mode & DEC_RUN)) {
+      e = rmsnorm_check(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E);
+      if (e == U2_OK) e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st, true);
+      if (e == U2_OK) e = qk_norm_rope_check(qkv, l.wq_norm, l.wk_norm, cosp, sinp, c.B, c.Hq, c.Hkv, c.D, kc, vc, 1, kv_stride, s_off);
+      return e;
+    }
+  }
+  if (!have_xn) e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
   e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
   if (e != U2_OK) return e;
@@ -275,19 +301,31 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
                       s_off, st);
 }
 
+int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                       int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+  return dec_pre(c, l, x, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, false);
+}
+
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
 // (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention() launch pair per sequence -- B <= 16
 // only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG)
-int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
-                        int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
-                        hipStream_t st) {
-  if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
-      !ws)
-    return U2_ERR_ARG;
-  if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
-  if (!wform_step_ok(c, l, 1, 3)) return U2_ERR_ARG;  // (everything the quantised products ask, before the attention is launched)
-  if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
+// The whole-stack step's tail norms -- ticket (null: none): the post-attention norm is asked for in the tail of the o product, and
+// `after` (w set: the norm that follows this layer -- the next layer's input norm or the stack's final one, into after->Yn) in the
+// tail of the down product; *after_done: that launch carried it.  A product followed by an adapter group keeps the norm's own
+// launch: the group adds to the product's rows after it.
+static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
+                    int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st, int mode,
+                    uint32_t* ticket, const RowsNorm* after, bool* after_done) {
+  if (mode & DEC_CHECK) {
+    if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
+        !ws)
+      return U2_ERR_ARG;
+    if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
+    if (!wform_step_ok(c, l, 1, 3)) return U2_ERR_ARG;  // (everything the quantised products ask, before the attention is launched)
+    if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
+  }
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
   bf16_t* p = reinterpret_cast<bf16_t*>(ws);
   bf16_t* h = p + (size_t)c.B * c.E;          // (xn of the first half lives at p)
@@ -300,13 +338,28 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
   const size_t aws_bytes = ws_bytes - used;
   const float scale = c.scale;
   if (kv_stride == 0) kv_stride = (int64_t)T * c.D;
-  if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
   const DecodeLora* lr = l.lora;
-  if (lr) {  // (the adapter groups: every refusal before the attention is launched)
-    int e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, true, st);
-    if (e == U2_OK) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, true, st);
-    if (e == U2_OK) e = dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, true, st);
-    if (e != U2_OK) return e;
+  const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
+  const bool gu_pair = !gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15);  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
+  if (mode & DEC_CHECK) {
+    if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
+    if (lr) {  // (the adapter groups: every refusal before the attention is launched)
+      int e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, true, st);
+      if (e == U2_OK) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, true, st);
+      if (e == U2_OK) e = dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, true, st);
+      if (e != U2_OK) return e;
+    }
+    if (!(mode & DEC_RUN)) {
+      // (the attention's own: 16-byte aligned q / K / V and partials, 32-bit offsets inside a (batch, kv head) entry)
+      if ((((uintptr_t)qkv | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ws) & 15) || (int64_t)T * c.D * 2 >= (1ll << 31) || !(scale > 0.f)) return U2_ERR_ARG;
+      int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st, true);
+      if (e == U2_OK) e = rmsnorm_check(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E);
+      if (e == U2_OK)
+        e = gu_pair ? dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st, true)
+                    : dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st, true);
+      if (e == U2_OK) e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st, true);
+      return e;
+    }
   }
   if (batched) {
     const int e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, scale, kv_start, aws, aws_bytes, st);
@@ -322,14 +375,16 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     const int e = attention(a, st);
     if (e != U2_OK) return e;
   }
-  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st);
+  RowsNorm o_norm;
+  if (ticket && !(lr && lr->n_o != 0)) o_norm.w = l.w_post_norm, o_norm.Yn = hn, o_norm.ld = c.E, o_norm.eps = c.eps, o_norm.ticket = ticket;
+  bool normed = false;
+  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st, false, &o_norm, &normed);
   if (e != U2_OK) return e;
   if (lr) e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, false, st);   // (after the residual epilogue: the same terms)
   if (e != U2_OK) return e;
-  e = rmsnorm_bf16(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
+  if (!normed) e = rmsnorm_bf16(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
   if (e != U2_OK) return e;
-  const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
-  if (!gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
+  if (gu_pair) {
     e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
     if (e != U2_OK) return e;
   } else {
@@ -340,9 +395,96 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
     e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
     if (e != U2_OK) return e;
   }
-  e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st);
+  const bool down_tail = ticket && after && !(lr && lr->n_down != 0);
+  e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st, false, down_tail ? after : nullptr,
+                 after_done);
   if (e != U2_OK || !lr) return e;
   return dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, false, st);
+}
+
+int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
+                        int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
+                        hipStream_t st) {
+  return dec_post(c, l, x, qkv, K, V, T, kv_stride, batched, kv_start, out, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, nullptr, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ one decode step of the stack
+// The whole decoder stack's step in ONE call: per layer exactly the launches of the two halves above, in their order, on the
+// caller's stream; the hidden state goes from layer to layer through two (B, E) rows of the workspace, the stack's final RMSNorm
+// (w_final: null = none) writes `out`.  The workspace: 256 bytes whose first 4 are the tail norms' ticket (zeroed once by whoever
+// owns the workspace; every launch that uses it leaves it zero), the layers' shared per-layer workspace (the largest
+// decoder_decode_workspace_bytes of them), the q|k|v rows, the two hidden rows.
+// tail_norm: the three norms that follow an o or a down product ride in that product's tail (dec_post).
+static size_t stack_layer_ws(const DecodeStackLayer* L, int n) {
+  size_t m = 0;
+  for (int i = 0; i < n; ++i) m = std::max(m, decoder_decode_workspace_bytes(L[i].cfg, L[i].T));
+  return (m + 255) & ~(size_t)255;
+}
+static size_t stack_qkv_bytes(const DecodeStackLayer* L, int n) {
+  size_t m = 0;
+  for (int i = 0; i < n; ++i) m = std::max(m, (size_t)L[i].cfg.B * (L[i].cfg.Hq + 2 * L[i].cfg.Hkv) * L[i].cfg.D * sizeof(bf16_t));
+  return (m + 255) & ~(size_t)255;
+}
+static size_t stack_hidden_bytes(const DecodeCfg& c) { return ((size_t)c.B * c.E * sizeof(bf16_t) + 255) & ~(size_t)255; }
+
+size_t decoder_decode_stack_workspace_bytes(const DecodeStackLayer* L, int n) {
+  if (!L || n <= 0) return 0;
+  for (int i = 0; i < n; ++i)
+    if (L[i].T <= 0 || L[i].cfg.B != L[0].cfg.B || L[i].cfg.E != L[0].cfg.E) return 0;
+  return 256 + stack_layer_ws(L, n) + stack_qkv_bytes(L, n) + 2 * stack_hidden_bytes(L[0].cfg);
+}
+
+int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
+                         bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+  if (!L || n <= 0 || !x || !out || !ws || ((uintptr_t)ws & 255)) return U2_ERR_ARG;
+  const DecodeCfg& c0 = L[0].cfg;
+  for (int i = 0; i < n; ++i) {
+    const DecodeStackLayer& s = L[i];
+    if (s.cfg.B != c0.B || s.cfg.E != c0.E || s.T <= 0 || s.k_first < 0 || s.s_off < 0 || (int64_t)s.k_first + s.T > (int64_t)s.s_off + 1) return U2_ERR_ARG;
+  }
+  const size_t need = decoder_decode_stack_workspace_bytes(L, n);
+  if (need == 0) return U2_ERR_ARG;
+  if (ws_bytes < need) return U2_ERR_WORKSPACE;
+  char* base = reinterpret_cast<char*>(ws);
+  uint32_t* ticket = tail_norm ? reinterpret_cast<uint32_t*>(base) : nullptr;
+  void* lws = base + 256;
+  const size_t lws_bytes = stack_layer_ws(L, n);
+  bf16_t* qkv = reinterpret_cast<bf16_t*>(base + 256 + lws_bytes);
+  bf16_t* hid[2];
+  hid[0] = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(qkv) + stack_qkv_bytes(L, n));
+  hid[1] = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(hid[0]) + stack_hidden_bytes(c0));
+  bf16_t* xn = reinterpret_cast<bf16_t*>(lws);  // (where every layer's first half keeps its normed input: dec_pre)
+  bool have_xn = false;
+  for (int pass = DEC_CHECK; pass <= DEC_RUN; ++pass) {  // every refusal of every layer, then every launch
+    const bf16_t* cur = x;
+    for (int i = 0; i < n; ++i) {
+      const DecodeStackLayer& s = L[i];
+      const bool last = i == n - 1;
+      bf16_t* nxt = last && !w_final ? out : hid[i & 1];
+      int e = dec_pre(s.cfg, s.layer, cur, cosp, sinp, cs_is_f32, cs_ld, qkv, s.kc, s.vc, s.kv_stride, s.s_off, lws, lws_bytes, st, pass, have_xn);
+      if (e != U2_OK) return e;   // (a null cache buffer among them: nothing below offsets one)
+      RowsNorm after;  // the norm that follows the layer: the next layer's input norm into its xn, or the final norm into out
+      if (!last) after.w = L[i + 1].layer.w_in_norm, after.Yn = xn, after.eps = L[i + 1].cfg.eps;
+      else if (w_final) after.w = w_final, after.Yn = out, after.eps = final_eps;
+      after.ld = c0.E;
+      after.ticket = ticket;
+      bool done = false;
+      const int64_t first = (int64_t)s.k_first * s.cfg.D;
+      e = dec_post(s.cfg, s.layer, cur, qkv, s.kc + first, s.vc + first, s.T, s.kv_stride, batched, kv_start, nxt, lws, lws_bytes, st, pass,
+                   ticket, after.w ? &after : nullptr, &done);
+      if (e != U2_OK) return e;
+      have_xn = done && !last;
+      if (last && w_final) {
+        if (pass == DEC_CHECK) e = rmsnorm_check(nxt, w_final, out, c0.B, c0.E, c0.E, c0.E);
+        else if (!done) e = rmsnorm_bf16(nxt, w_final, out, c0.B, c0.E, c0.E, c0.E, final_eps, st);
+        if (e != U2_OK) return e;
+      }
+      cur = nxt;
+    }
+    have_xn = false;
+  }
+  return U2_OK;
 }
 
 }  // namespace u2

@@ -26,8 +26,14 @@ namespace u2 {
 // the prefill): the workgroup's 16 weight rows are 8 gate rows and the SAME 8 up rows, so the lanes of column groups 0 / 1 hold
 // the gates and those of groups 2 / 3 (32 lanes further) the matching ups; the decode step's SwiGLU launch goes away.
 // a.W / a.ldw: bytes with codes (e4m3: one per byte, e2m1: two), else elements of the element type.
-template <int NW, int NB, bool PAIR, WForm F>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_min_waves(NW, NB, F)))) void gemm_rows16_kernel(RowsArgs a) {
+// NORM (RowsNorm, non-pair alone): after its rows_store every workgroup goes through rows_norm_tail (rows.h) -- release, ticket, and
+// in the workgroup that draws the last one the RMSNorm of the M finished rows.  A template parameter, not a branch on a.norm.w: the
+// row function keeps a row's 16-byte chunks and the weight's in registers (NC = 8: about 100 VGPRs), and as a branch that tail set
+// the register count -- 4 waves per SIMD instead of 5 .. 8, 144 bytes of scratch in the 64-register instantiations -- of every
+// product that never asks for a norm.  The 72 instantiations without it are compiled from the text they had (DESIGN f12).
+template <int NW, int NB, bool PAIR, WForm F, bool NORM = false>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_min_waves(NW, NB, F, NORM)))) void gemm_rows16_kernel(RowsArgs a) {
+  static_assert(!(PAIR && NORM), "the norm follows the non-pair epilogue");
   __shared__ float red[NB][NW][64][4];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (scalar: the row block of the epilogue too)
   const int l15 = lane & 15, g = lane >> 4;
@@ -54,15 +60,36 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_mi
   for (int b = 0; b < NB; ++b) *reinterpret_cast<f32x4*>(red[b][wv][lane]) = acc[b];
   __syncthreads();
   const int rb = wv;                          // (NW >= 4 >= NB: a wave per row block)
+  const int mb = min(16, a.M - 16 * rb);      // rows of the block (rb < NB: >= 1, NB = ceil(M / 16))
+  const int m = 16 * rb + l15;
+  auto tile_sum = [&](float (&v)[4]) {        // the NW partial tiles of the row block, in slice order
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] += red[rb][w][lane][r];
+  };
+  auto store = [&](float (&v)[4]) {           // the non-pair epilogue of the lane's 4 columns of row m
+    if constexpr (W8) {  // the scaled sum is an fp32 value of its own before the epilogue sees it (alpha = 1 there)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] *= reinterpret_cast<const float*>(a.scale)[wrow(4 * g + r)];
+    }
+    RowsEpi e = a;
+    if constexpr (W8 || W4 || NB > 1) e.alpha = e.alpha_lo = 1.f, e.nsplit = 0;  // (only a plan's step, 16-bit and M <= 16, sets them: constants here)
+    rows_store(e, v, m, n0 + 4 * g, reinterpret_cast<char*>(a.C), a.R);
+  };
+  if constexpr (NORM) {  // the RMSNorm of the finished rows in this launch's tail: every thread gets there, epilogue or not
+    if (rb < NB && l15 < mb) {
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      tile_sum(v);
+      store(v);
+    }
+    rows_norm_tail(a.norm, reinterpret_cast<const bf16_t*>(a.C), a.ldc, a.M, a.N, NW, reinterpret_cast<uint32_t*>(&red[0][0][0][0]));
+    return;
+  }
   if (rb >= NB) return;
-  const int mb = min(16, a.M - 16 * rb);      // rows of the block (>= 1: NB = ceil(M / 16))
   if (!PAIR && l15 >= mb) return;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int w = 0; w < NW; ++w)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += red[rb][w][lane][r];
-  const int m = 16 * rb + l15;
+  tile_sum(v);
   if constexpr (PAIR) {  // (all 64 lanes: lanes of rows >= M carry copies of row M - 1 and write nothing)
     auto mult = [&](int r) {
       const int c = 4 * g + r;  // (wrow(c) written out: through the nested lambda <4, 4, true, true> takes 8 more VGPRs and loses a wave)
@@ -73,13 +100,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(rows_mi
     rows_pair_store(v, mult, g < 2 && l15 < mb, m, (int)blockIdx.x * 8 + 4 * g, I2, reinterpret_cast<bf16_t*>(a.C), a.ldc);
     return;
   }
-  if constexpr (W8) {  // the scaled sum is an fp32 value of its own before the epilogue sees it (alpha = 1 there)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] *= reinterpret_cast<const float*>(a.scale)[wrow(4 * g + r)];
-  }
-  RowsEpi e = a;
-  if constexpr (W8 || W4 || NB > 1) e.alpha = e.alpha_lo = 1.f, e.nsplit = 0;  // (only a plan's step, 16-bit and M <= 16, sets them: constants here)
-  rows_store(e, v, m, n0 + 4 * g, reinterpret_cast<char*>(a.C), a.R);
+  store(v);
 }
 
 // What gemm_rows accepts: one function for all weight forms, the per-form numbers from WFormFacts (kernels.h).
@@ -94,6 +115,11 @@ int gemm_rows_check(const RowsArgs& a) {
   if (a.lda < a.K || (a.lda & 7) || a.ldw < a.K / f.ldw_div || a.ldw % f.ldw_mult || a.ldc < (pair ? a.N >> 1 : a.N)) return U2_ERR_ARG;
   if (f.scale_bytes && (!a.scale || (uintptr_t)a.scale % f.scale_align || (f.scale_k && a.lds < a.K / f.scale_k))) return U2_ERR_ARG;
   if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) || ((uintptr_t)a.C & ((a.flags & GEMM_OUT_F32) ? 3 : 1))) return U2_ERR_ARG;
+  if (const RowsNorm& n = a.norm; n.w) {  // the norm in the tail: the non-pair form with a residual on element-type rows rmsnorm_row reads
+    if (pair || !(a.flags & GEMM_RESIDUAL) || (a.flags & GEMM_OUT_F32) || !n.Yn || !n.ticket || ((uintptr_t)n.ticket & 3)) return U2_ERR_ARG;
+    if ((a.N & 7) || a.N > ROWS_NORM_MAX_N || (a.ldc & 7) || n.ld < a.N || (n.ld & 7) || (((uintptr_t)a.C | (uintptr_t)n.w | (uintptr_t)n.Yn) & 15))
+      return U2_ERR_ARG;
+  }
   return U2_OK;
 }
 
@@ -109,8 +135,17 @@ int gemm_rows_launch(const RowsArgs& a, hipStream_t stream) {
   void (*const k[3][2][3][4])(RowsArgs) = {ROWS_FORM(WForm::ELEM), ROWS_FORM(WForm::E4M3), ROWS_FORM(WForm::E2M1)};
 #undef ROWS_FORM
 #undef ROWS_NB
+  // ... and the 36 with the norm in the tail: [WForm][NW = 16, 8, 4][NB - 1]
+#define ROWS_NORM_NB(NW, F)                                                                                                           \
+  {gemm_rows16_kernel<NW, 1, false, F, true>, gemm_rows16_kernel<NW, 2, false, F, true>, gemm_rows16_kernel<NW, 3, false, F, true>, \
+   gemm_rows16_kernel<NW, 4, false, F, true>}
+#define ROWS_NORM_FORM(F) {ROWS_NORM_NB(16, F), ROWS_NORM_NB(8, F), ROWS_NORM_NB(4, F)}
+  void (*const kn[3][3][4])(RowsArgs) = {ROWS_NORM_FORM(WForm::ELEM), ROWS_NORM_FORM(WForm::E4M3), ROWS_NORM_FORM(WForm::E2M1)};
+#undef ROWS_NORM_FORM
+#undef ROWS_NORM_NB
   const dim3 grid((unsigned)(pair ? cdiv(a.N >> 1, 8) : cdiv(a.N, 16)));
-  hipLaunchKernelGGL(k[(int)a.form][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
+  const bool norm = a.norm.w && !pair;  // (gemm_rows_check: never on the pair form)
+  hipLaunchKernelGGL(norm ? kn[(int)a.form][2 - nw / 8][nb - 1] : k[(int)a.form][pair][2 - nw / 8][nb - 1], grid, dim3(nw * 64), 0, stream, a);
   return launch_status();
 }
 

@@ -121,12 +121,25 @@ constexpr const WFormFacts& wform_facts(WForm f) { return WFORM_FACTS[(int)f]; }
 // The few-rows (weight-streaming) product (gemm_rows.hip; arithmetic: rows.h): C = epilogue(A . W^T) for 1 <= M <= 64 rows on
 // weights in the element type, C = epilogue(scale[n] * A . e4m3(W)^T) on e4m3 codes, C = epilogue(A . (e2m1(W) 2^(scale - 127))^T)
 // on e2m1 codes; 16-byte aligned A / W rows.  Each block of 16 rows has the bits of the M <= 16 product on it.
+// The RMSNorm of the finished rows in the tail of the product that wrote them (gemm_rows.hip: the workgroup that draws the last
+// ticket norms all M rows of C): Yn = rmsnorm(C) * w over the N columns, bit for bit rmsnorm_bf16's.  Set (w != nullptr) only on
+// the non-pair form with a residual and an element-type C, N % 8 == 0, N <= ROWS_NORM_MAX_N; `ticket`: 4 bytes of device memory
+// that read 0 before the launch and read 0 again after it.
+struct RowsNorm {
+  const bf16_t* w = nullptr;     // [N]
+  bf16_t* Yn = nullptr;          // [M][N], leading dim ld
+  uint32_t* ticket = nullptr;
+  int64_t ld = 0;
+  float eps = 0.f;
+};
+constexpr int ROWS_NORM_MAX_N = 4096;  // (the tail holds a row in 8 x 16 bytes per lane: the 64-register instantiations must not spill)
 struct RowsEpi {                 // what the epilogue of a lane's 4 columns reads (rows.h: rows_store)
   const bf16_t* bias = nullptr;  // [N] (GEMM_BIAS_N) or [M] (GEMM_BIAS_M)
   int N = 0, flags = 0;
   int nsplit = 0;                // columns n < nsplit take alpha_lo instead of alpha (GemmDesc)
   int64_t ldc = 0, ldr = 0;
   float alpha = 1.f, alpha_lo = 1.f;
+  RowsNorm norm;                 // gemm_rows alone (a plan's step leaves it unset)
 };
 struct RowsArgs : RowsEpi {
   const bf16_t* A = nullptr;     // [M][K] elements, leading dim lda
@@ -389,6 +402,23 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
 int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
                         int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
                         hipStream_t st);
+// One layer of the whole-stack step (capi.hip decodes u2tok_decode_stack_layer into it): the layer's two halves on its
+// append-in-place cache buffers kc / vc (B, Hkv, capacity, D; kv_stride = capacity * D).  The step's k / v rows go to position
+// s_off, the attention reads positions k_first .. k_first + T - 1 <= s_off.
+struct DecodeStackLayer {
+  DecodeCfg cfg;
+  DecodeLayer layer;
+  bf16_t *kc, *vc;
+  int64_t kv_stride;
+  int s_off, k_first, T;
+};
+// Every layer's pre and post in one call, the hidden state through the workspace, the final RMSNorm (w_final: null = the last hidden
+// state as it is) into out; every refusal of every layer before the first launch.  tail_norm: gemm_rows' RowsNorm for the norms
+// behind the o and down products.  The first 4 bytes of the (256-byte aligned) workspace are the ticket: zero before the call.
+size_t decoder_decode_stack_workspace_bytes(const DecodeStackLayer* L, int n);
+int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
+                         bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
+                         size_t ws_bytes, hipStream_t st);
 // ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
 // One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
 // q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between

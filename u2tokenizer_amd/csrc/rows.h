@@ -96,7 +96,8 @@ constexpr bool rows_guarded(int NB, WForm F) { return F != WForm::ELEM && NB > 1
 // element and e4m3 instantiations compile as without the attribute).  e2m1 with NB > 1 on 4 or 8 waves: 8, the occupancy of the e4m3
 // instantiations of the same (NW, NB) -- left alone the allocator keeps all 4 NB activation fragments of a quad step in flight and
 // ends at 6 .. 7 waves for NB = 3 / 4; held to 64 registers it still neither spills nor touches scratch (DESIGN f11).
-constexpr int rows_min_waves(int NW, int NB, WForm F) { return F == WForm::E2M1 && NB > 1 && NW < 16 ? 8 : NW / 4; }
+// With the norm in the tail (NORM) the tail sets the register count: what the launch bounds say.
+constexpr int rows_min_waves(int NW, int NB, WForm F, bool NORM = false) { return F == WForm::E2M1 && NB > 1 && NW < 16 && !NORM ? 8 : NW / 4; }
 
 // Steps [s0, s1) of one slice for NB row blocks.  wp = the lane's weight row + 16 g bytes (a step is 64 bytes of a weight row in
 // every form: 8 elements, 16 or 32 codes per lane group); xp[b] = its activation row of block b + 8 g (e4m3: 16 g, e2m1: 32 g)
@@ -188,6 +189,76 @@ __device__ __forceinline__ void rows_pair_store(const float (&v)[4], Mult mult, 
       C[(int64_t)m * ldc + n] = f32_to_bf16(bf16_to_f32(f32_to_bf16(sg)) * up);
     }
   }
+}
+
+// One row of the RMSNorm, by one wave: yp[:] = bf16(xp[:] * rsqrt(mean(xp[:]^2) + eps)) * w (the normalised value is rounded to the
+// element type before the product with w).  ONE definition for rmsnorm_kernel (decoder.hip) and for the norm in the tail of the
+// few-rows product (rows_norm_tail): lane l holds the 16-byte chunks l, 64 + l, ... of the row (NC of them: C <= NC * 512), adds
+// their squares in that order and the wave adds the 64 sums in wave_sum's order -- nothing depends on the block the wave sits in,
+// nor on NC beyond the chunks it covers.
+template <int NC>
+__device__ __forceinline__ void rmsnorm_row(const bf16_t* xp, const bf16_t* w, bf16_t* yp, int C, float eps, int lane) {
+  const int nchunk = C >> 3;
+  uint4 v[NC];
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = i * 64 + lane;
+    v[i] = uint4{0, 0, 0, 0};
+    if (c < nchunk) {
+      v[i] = *reinterpret_cast<const uint4*>(xp + c * 8);
+      const float a0 = bf16lo(v[i].x), a1 = bf16hi(v[i].x), a2 = bf16lo(v[i].y), a3 = bf16hi(v[i].y);
+      const float a4 = bf16lo(v[i].z), a5 = bf16hi(v[i].z), a6 = bf16lo(v[i].w), a7 = bf16hi(v[i].w);
+      sq += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3 + a4 * a4 + a5 * a5 + a6 * a6 + a7 * a7;
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = i * 64 + lane;
+    if (c < nchunk) {
+      const uint4 uw = *reinterpret_cast<const uint4*>(w + c * 8);
+      const uint4 n = uint4{pack2_bf16(bf16lo(v[i].x) * rstd, bf16hi(v[i].x) * rstd), pack2_bf16(bf16lo(v[i].y) * rstd, bf16hi(v[i].y) * rstd),
+                            pack2_bf16(bf16lo(v[i].z) * rstd, bf16hi(v[i].z) * rstd), pack2_bf16(bf16lo(v[i].w) * rstd, bf16hi(v[i].w) * rstd)};
+      *reinterpret_cast<uint4*>(yp + c * 8) =
+          uint4{pack2_bf16(bf16lo(n.x) * bf16lo(uw.x), bf16hi(n.x) * bf16hi(uw.x)), pack2_bf16(bf16lo(n.y) * bf16lo(uw.y), bf16hi(n.y) * bf16hi(uw.y)),
+                pack2_bf16(bf16lo(n.z) * bf16lo(uw.z), bf16hi(n.z) * bf16hi(uw.z)), pack2_bf16(bf16lo(n.w) * bf16lo(uw.w), bf16hi(n.w) * bf16hi(uw.w))};
+    }
+  }
+}
+
+// The norm in the tail of the few-rows product (RowsNorm), reached by EVERY thread of the workgroup after its rows_store.  flag: 4
+// bytes of LDS nobody reads any more.
+//   * every thread fences its stores to C at agent scope (release), the workgroup meets at a barrier, and one thread draws the
+//     workgroup's ticket with an atomic add at agent scope: whoever sees that ticket's value sees the workgroup's part of C;
+//   * the workgroup whose ticket is the last of the grid (every other part of C has been released before it) fences again (acquire:
+//     its loads of C must not be served from lines a compute unit kept from an earlier launch on the same buffer), its NW waves norm
+//     the M rows, a wave per row and launch rmsnorm_kernel's row function, and it puts the ticket back to 0 for the next launch
+//     (the end of the kernel releases that store; nobody else touches the ticket after the last draw).
+// Nobody waits for another workgroup: a workgroup that is not the last leaves.
+__device__ __forceinline__ void rows_norm_tail(const RowsNorm& nm, const bf16_t* C, int64_t ldc, int M, int N, int nw, uint32_t* flag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();  // (also: the epilogue's reads of the LDS tiles are over before `flag` is written)
+  if (threadIdx.x == 0) {
+    const uint32_t t = __hip_atomic_fetch_add(nm.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    *flag = t == gridDim.x - 1 ? 1u : 0u;
+  }
+  __syncthreads();
+  if (*flag == 0u) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const int lane = threadIdx.x & 63;
+  for (int row = threadIdx.x >> 6; row < M; row += nw) {
+    const bf16_t* xp = C + (int64_t)row * ldc;
+    bf16_t* yp = nm.Yn + (int64_t)row * nm.ld;
+    if (N <= 1024) rmsnorm_row<2>(xp, nm.w, yp, N, nm.eps, lane);
+    else if (N <= 2048) rmsnorm_row<4>(xp, nm.w, yp, N, nm.eps, lane);
+    else rmsnorm_row<8>(xp, nm.w, yp, N, nm.eps, lane);
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(nm.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  (void)nm; (void)C; (void)ldc; (void)M; (void)N; (void)nw; (void)flag;
+#endif
 }
 
 __host__ __device__ inline int rows16_slices(int nsteps) { return nsteps >= 64 ? 16 : nsteps >= 16 ? 8 : 4; }  // (the launcher's choice of NW)

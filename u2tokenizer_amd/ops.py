@@ -909,6 +909,50 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, out
     return _rows_call("u2tok_gemm_rows", a, (w,), (w.stride(0),), w.shape[0], bias, residual, out_f32, swiglu, out)
 
 
+@_guarded
+def gemm_rows_norm(a: torch.Tensor, w: torch.Tensor, norm_weight: torch.Tensor, eps: float, ticket: torch.Tensor, *, residual,
+                   scale: Optional[torch.Tensor] = None, bias=None, out: Optional[torch.Tensor] = None,
+                   out_norm: Optional[torch.Tensor] = None, flags: Optional[int] = None):
+    """(Y, Yn): the few-rows product with a residual, Y (M <= 64, N) = a @ W^T (+ bias) + residual, and in the SAME launch Yn =
+    rmsnorm(Y, norm_weight, eps) (u2tok_gemm_rows_norm: the workgroup that finishes last norms the rows).  W: (N, K) in the element
+    type (scale None), float8_e4m3fn with `scale` (N,) fp32, or uint8 e2m1 codes (N, K / 2) with `scale` (N, K / 32) uint8 block
+    scales.  Y has the bits of gemm_rows / gemm_rows_w8 / gemm_rows_w4, Yn those of `rmsnorm(Y)`.  ticket: an int32 / uint32 tensor
+    of one element on the GPU that holds 0; it holds 0 again afterwards.  N % 8 == 0, N <= 4096.  flags (tests): the raw epilogue
+    flags instead of those the arguments imply."""
+    h = _lib.load_library()
+    _need(a, ELEM, "A")
+    a2 = a.reshape(-1, a.shape[-1])
+    if a2.stride(1) != 1:
+        a2 = a2.contiguous()
+    M, K = a2.shape
+    if scale is None:
+        _need(w, ELEM, "W")
+        wform, ldw, lds = 0, w.stride(0), 0
+    elif w.dtype == torch.float8_e4m3fn:
+        wform, ldw, lds = 1, K, 0
+    else:
+        wform, ldw, lds = 2, K // 2, K // 32
+    if wform and not (w.is_contiguous() and scale.is_contiguous() and w.is_cuda and scale.is_cuda):
+        raise RuntimeError("gemm_rows_norm: codes and scales must be contiguous GPU tensors")
+    N = w.shape[0]
+    dt = elem_dtype()
+    out = torch.empty((M, N), dtype=dt, device=a.device) if out is None else out
+    out_norm = torch.empty((M, N), dtype=dt, device=a.device) if out_norm is None else out_norm
+    for t, name in ((out, "out"), (out_norm, "out_norm")):
+        if t.shape != (M, N) or t.stride(1) != 1 or t.dtype != dt:
+            raise RuntimeError(f"gemm_rows_norm: {name} must be (M, N) with unit column stride in the element type")
+    if bias is not None:
+        bias = _need(bias, ELEM, "bias").contiguous()
+    norm_weight = _need(norm_weight, ELEM, "norm_weight").contiguous()
+    if flags is None:
+        flags = (GEMM_RESIDUAL if residual is not None else 0) | (GEMM_BIAS_N if bias is not None else 0)
+    st = h.u2tok_gemm_rows_norm(_ptr(a2), _ptr(w), _ptr(out), _ptr(bias), _ptr(residual), M, N, K, a2.stride(0), ldw, out.stride(0),
+                                residual.stride(0) if residual is not None else 0, flags, wform, _ptr(scale), lds, _ptr(norm_weight),
+                                float(eps), _ptr(out_norm), out_norm.stride(0), _ptr(ticket), _stream())
+    _lib.check(st, "u2tok_gemm_rows_norm")
+    return out, out_norm
+
+
 # ---------------------------------------------------------------------------------- rank-r adapter (LoRA) products
 def _segment(t: torch.Tensor, name: str):
     """A 2-D view with unit column stride -> (tensor, element offset 0, row stride): the kernels take a column segment of a packed

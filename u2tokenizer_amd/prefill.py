@@ -31,6 +31,9 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     else, and goes when the switch goes off.  With `lora` the adapter branch follows each of the four products UNMERGED -- on
     many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of csrc/lora_rows.hip
     inside the two library calls --, and a wrapper that is merged or disabled runs as its base layer.
+  * stack_decode: the decoder STACK's forward is wrapped as well; a decode step that `route` would hand to the fused step in every
+    layer (`stack_route`) runs as one library call for all of them (`_stack_step`: u2tok_decoder_decode_stack, the per-layer calls'
+    launches in their order), with the bits of the per-layer route; every other call goes on to the stack's own forward.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -121,6 +124,10 @@ SWITCHES = (
            "layer's weights again in HBM; exact on the quantised weights, the quantiser's cost in accuracy is unmeasured on trained "
            "weights; with `fp8_decode` as well a layer takes e2m1 where it qualifies, else e4m3 where it qualifies, else 16 bits; "
            "`w4_stats`, `w4_weights(layer)`"),
+    Switch("stack_decode", "stack", "u2_fused_stack_decode", False, (), (), (),
+           "a decode step the fused step would take layer by layer runs as ONE library call for the whole decoder stack "
+           "(u2tok_decoder_decode_stack: the per-layer calls' launches in their order, the same bits, no Python between the "
+           "layers; `stack_route` lists what it asks, everything else keeps the per-layer routes); `stack_stats`"),
 )
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
@@ -138,6 +145,11 @@ wide_stats = {"decode": 0, "padded_decode": 0}
 # ... and the layer calls of the no-grad routes (counted above as well) that computed at least one unmerged adapter (lora), per
 # route, and the adapters they computed
 lora_stats = {"prefill": 0, "extend": 0, "decode": 0, "adapters": 0}
+# ... and the MODEL calls that ran as one whole-stack step (stack_decode); their layers are counted above as decode steps as well
+stack_stats = {"decode": 0, "padded_decode": 0}
+# whether the whole-stack step asks for its three RMSNorms in the tail of the product before them (u2tok_gemm_rows_norm): the same
+# bits either way; the default is the measurement's verdict (DESIGN f12)
+STACK_TAIL_NORM = False
 
 
 class _QForm(NamedTuple):
@@ -395,6 +407,7 @@ class _StackState:
     wide: bool = False
     lora: bool = False
     fp4: bool = False
+    stack: bool = False
     pad: tuple = _NO_PAD       # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
     pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
     scratch: dict = field(default_factory=dict)
@@ -1018,6 +1031,217 @@ def _decode_step(self, x, pe, cache, window, pr):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- the whole-stack decode step
+_MISSING = object()
+_STACK_ARGS = ("input_ids", "attention_mask", "position_ids", "past_key_values", "inputs_embeds", "use_cache")
+_STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep")   # what the step keeps in a (B, device, stream) scratch entry
+_PE_STUBS = {}
+
+
+@dataclass(slots=True, eq=False)
+class _StackRun:
+    """The whole-stack route's own state, on the decoder stack as `_u2_stack_run` (outside `_StackState`: its fields are the
+    switches): the forward the stack had (`had`: the instance attribute it was, or _MISSING for the class's method) and the per-layer
+    plan of the call being admitted."""
+    orig: object
+    had: object
+    plan: list = field(default_factory=list)
+
+
+def _stack_wrap(base) -> None:
+    if "_u2_stack_run" not in base.__dict__:
+        base._u2_stack_run = _StackRun(base.forward, base.__dict__.get("forward", _MISSING))
+        base.forward = types.MethodType(_stack_forward, base)
+
+
+def _stack_unwrap(base) -> None:
+    """Put the stack's own forward back and drop what the route kept: its state, and the workspaces, descriptor arrays and
+    descriptor references in the decode steps' scratch."""
+    run = base.__dict__.pop("_u2_stack_run", None)
+    if run is None:
+        return
+    if run.had is _MISSING:
+        del base.forward
+    else:
+        base.forward = run.had
+    stack = base.__dict__.get("_u2_stack")
+    for sc in (stack.scratch.values() if stack is not None else ()):
+        for k in _STACK_SCRATCH:
+            sc.pop(k, None)
+
+
+def _no_hooks(m) -> bool:
+    d = m.__dict__
+    return not (d.get(_HOOKS_F) or d.get(_HOOKS_FP) or d.get(_HOOKS_B) or d.get(_HOOKS_BP))
+
+
+def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool, plan: list = None) -> str:
+    """Whether a call of the patched decoder stack `base` runs as ONE whole-stack decode step ("stack") or goes on to the stack's
+    own forward and the per-layer routes ("layers").  B, S, dtype, is_cuda: of the call's (B, S) ids or (B, S, E) embeddings (ids:
+    the embedding table's type); kw: the call's keyword arguments by name, `use_cache`, `output_hidden_states` and
+    `output_attentions` resolved against the config.  "stack" needs ALL of:
+      * the switch on, grad off, one new position per sequence on the GPU, `use_cache`, a cache, no `output_hidden_states`, no
+        `output_attentions`;
+      * every layer of the stack patched, none with forward hooks, forward pre-hooks or any other hook table entry (the stack's
+        final norm is called as the module it is);
+      * `route()` answering "decode" for EVERY layer on this call's shape and keyword arguments -- it keeps deciding masks (the
+        pre-hook's verdict: `stack.pad` is current), wide batches, adapters, windows, head dims, types;
+      * `_decode_state(...).ok` for every layer, one head dim and one hidden size for all of them;
+      * every layer's cache entry one the per-layer step writes in place (`_KVWrite`: the append-in-place layer a fused prefill
+        left, holding this batch): a plain DynamicLayer, a DynamicSlidingWindowLayer, an offloaded or static cache send the whole
+        call to the per-layer routes.
+    plan (a list): receives one (layer, state, projections, `_Decode16`, scratch, window) per layer of a "stack" verdict."""
+    stack = base.__dict__.get("_u2_stack")
+    if stack is None or not stack.stack or grad or S != 1 or not is_cuda:
+        return "layers"
+    cache = kw.get("past_key_values")
+    if not kw.get("use_cache") or cache is None or kw.get("output_hidden_states") or kw.get("output_attentions"):
+        return "layers"
+    layers = list(base.layers[:base.config.num_hidden_layers])
+    if not layers or not hasattr(base, "norm"):
+        return "layers"
+    cl = _plain_layers(cache)
+    if cl is None:
+        return "layers"
+    lkw = {k: v for k, v in kw.items() if k not in ("input_ids", "inputs_embeds", "attention_mask", "position_ids", "use_cache",
+                                                    "output_hidden_states")}
+    steps = []
+    hd = E = None
+    for layer in layers:
+        if not is_patched(layer) or not _no_hooks(layer):
+            return "layers"
+        st = layer._u2_prefill
+        att = layer.self_attn
+        pr = st.layout.projections(layer)
+        E1 = _base(pr[0]).weight.shape[1]
+        pe = _PE_STUBS.get(att.head_dim)
+        if pe is None:   # (route() reads the tables' last dimension alone)
+            pe = _PE_STUBS[att.head_dim] = (torch.empty(0, att.head_dim),) * 2
+        lkw["position_embeddings"] = pe
+        how, window = route(layer, (B, 1, E1), dtype, is_cuda, (), lkw, False, pr)
+        if how != "decode" or (hd is not None and (att.head_dim != hd or E1 != E)):
+            return "layers"
+        hd, E = att.head_dim, E1
+        idx = att.layer_idx
+        lay = cl[idx] if idx < len(cl) else None
+        if lay is None or type(lay) is not _APPEND_LAYER or lay.keys.shape[0] != B:
+            return "layers"
+        d, sc = _decode_state(layer, B, _base(pr[0]).weight.device, pr)
+        if not d.ok:
+            return "layers"
+        steps.append((layer, st, pr, d, sc, window))
+    if plan is not None:
+        plan[:] = steps
+    return "stack"
+
+
+def _stack_forward(self, *args, **kwargs):
+    """The forward of a decoder stack while `stack_decode` is on: the whole-stack step for the calls `stack_route` admits, the
+    stack's own forward -- and with it the per-layer routes -- unchanged for every other call.  (The `_mask_hook` pre-hook has run:
+    `stack.pad` is this call's.)"""
+    run = self._u2_stack_run
+    if len(args) > len(_STACK_ARGS) or any(n in kwargs for n in _STACK_ARGS[:len(args)]):
+        return run.orig(*args, **kwargs)
+    kw = dict(zip(_STACK_ARGS, args), **kwargs)
+    ids, x = kw.get("input_ids"), kw.get("inputs_embeds")
+    t = x if x is not None else ids
+    if (ids is None) == (x is None) or not torch.is_tensor(t) or t.dim() != (3 if x is not None else 2):
+        return run.orig(*args, **kwargs)
+    cfg = self.config
+    for name in ("use_cache", "output_hidden_states", "output_attentions"):
+        if kw.get(name) is None:
+            kw[name] = getattr(cfg, name, False)
+    dtype = x.dtype if x is not None else self.embed_tokens.weight.dtype
+    plan = run.plan
+    if stack_route(self, t.shape[0], t.shape[1], dtype, t.is_cuda, kw, torch.is_grad_enabled(), plan) != "stack":
+        return run.orig(*args, **kwargs)
+    try:
+        return _stack_step(self, plan, ids, x, kw["past_key_values"], kw.get("position_ids"))
+    finally:
+        plan.clear()
+
+
+def _stack_step(base, plan, ids, x, cache, position_ids):
+    """One decode step of the whole decoder stack in ONE library call (u2tok_decoder_decode_stack): per layer what `_decode_step`
+    does around its two calls -- the weight form's copies, the adapters' operands and scratch, the layer descriptor's variant, room
+    for one more row in the layer's cache buffers --, then the call, then every layer's commit.  The rotary tables come from ONE
+    call of the stack's `rotary_emb`, as the layers receive them from the stock forward."""
+    import ctypes as C
+    from transformers.modeling_outputs import BaseModelOutputWithPast
+    from . import _lib
+    if x is None:
+        x = base.embed_tokens(ids)
+    B, _, E = x.shape
+    if position_ids is None:
+        position_ids = (torch.arange(1, device=x.device) + cache.get_seq_length()).unsqueeze(0)
+    pe = base.rotary_emb(x, position_ids)
+    n = len(plan)
+    stack = plan[0][1].stack
+    sc = plan[0][4]            # (one scratch entry per (B, device, stream): every layer's `_decode_state` returned the same)
+    hd = plan[0][3].hd
+    with ops.on_device(x) as (h, stream):
+        x2 = _rows(x)
+        cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
+        arr = sc.get("stack_arr")
+        if arr is None or len(arr) != n:
+            arr = sc["stack_arr"] = (_lib.DecodeStackLayer * n)()
+            sc["stack_keep"] = [None] * n
+            sc["stack_ws"] = None
+        keep = sc["stack_keep"]
+        rows, lss, Tmax = [], [], 0
+        for i, (layer, st, pr, d, _, window) in enumerate(plan):
+            form = _weight_form(st, d, pr)
+            ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
+            if ls is not None:
+                _lora_scratch(ls, B, sc, h)
+                lss.append(ls)
+            v = st.variants.get((form, ls is not None))
+            if v is None:
+                v = _decode_layer(st, form, ls is not None)
+            lay = cache.layers[layer.self_attn.layer_idx]
+            T0 = lay._room(1, sc["kc"])
+            kb, vb = lay._kb, lay._vb
+            slot = arr[i]
+            if keep[i] is None or keep[i][0] is not v or keep[i][1] is not kb:   # (rewrite what changed: a rebuilt variant, a re-homed buffer)
+                slot.cfg, slot.layer = C.addressof(v[3]), C.addressof(v[0])
+                slot.k_cache, slot.v_cache, slot.kv_stride = kb.data_ptr(), vb.data_ptr(), kb.stride(1)
+                keep[i] = (v, kb, vb)
+            T1 = T0 + 1
+            first = 0 if window is None else max(0, T1 - window)
+            slot.s_off, slot.k_first, slot.T = T0, first, T1 - first
+            Tmax = max(Tmax, T1 - first)
+            rows.append((lay, T1))
+        for ls in lss:   # (a later layer's larger group may have replaced the shared adapter scratch: all of them read the last one)
+            ls.desc.scratch, ls.desc.scratch_bytes = sc["lora"].data_ptr(), sc["lora"].numel()
+        if sc["stack_ws"] is None or sc["stack_T"] < Tmax:
+            Tcap = max(2048, 2 * Tmax)                    # (grows geometrically, as the per-layer step's workspace does)
+            for i in range(n):
+                arr[i].T = Tcap
+            need = h.u2tok_decoder_decode_stack_workspace_bytes(arr, n)
+            for i, (_, T1) in enumerate(rows):
+                arr[i].T = T1 - arr[i].k_first
+            if need == 0:
+                raise RuntimeError("u2tok_decoder_decode_stack_workspace_bytes refused the stack's descriptors")
+            sc["stack_ws"] = torch.zeros(need, dtype=torch.uint8, device=x.device)   # (zeros: the tail norms' ticket, once)
+            sc["stack_T"] = Tcap
+        ws = sc["stack_ws"]
+        out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
+        _, kv_start, _ = stack.pad
+        left = kv_start is not None
+        # (w_final_norm = NULL: the stack's final norm stays the module's own below, as on the per-layer routes -- the library's
+        #  RMSNorm and the module's add a row's squares in another order, and one element in some ten thousand rounds the other way)
+        _lib.check(h.u2tok_decoder_decode_stack(arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
+                                                cos.stride(0), int(left or B > 16), kv_start.data_ptr() if left else None,
+                                                None, 0.0, int(STACK_TAIL_NORM),
+                                                out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack")
+        for lay, T1 in rows:
+            lay._commit(T1)
+    for _, st, _, _, _, _ in plan:
+        _count(st, "decode", B)
+    stack_stats["padded_decode" if left else "decode"] += 1
+    return BaseModelOutputWithPast(last_hidden_state=base.norm(out), past_key_values=cache)
+
+
 def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor):
     """For a plain HF DynamicCache whose layer `layer_idx` is still empty: put an append-in-place layer there with room for S
     positions (and as many again for the decode steps) and return it; None for every other cache (its `update` is used)."""
@@ -1090,7 +1314,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
-                         fp4_decode: bool = False) -> int:
+                         fp4_decode: bool = False, stack_decode: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
@@ -1098,7 +1322,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
                  fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
-                 fp4_decode=fp4_decode)
+                 fp4_decode=fp4_decode, stack_decode=stack_decode)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
@@ -1134,6 +1358,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     for layer, layout in todo:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
+    (_stack_wrap if stack.stack else _stack_unwrap)(base)
     return len(todo)
 
 
@@ -1143,6 +1368,7 @@ def disable_fused_prefill(model) -> None:
         st = layer.__dict__.pop("_u2_prefill", None)
         if st is not None:
             layer.forward = st.orig
+    _stack_unwrap(base)
     stack = base.__dict__.pop("_u2_stack", None)
     if stack is not None:
         stack.hook.remove()
