@@ -453,6 +453,39 @@ int u2tok_decoder_decode_stack(const u2tok_decode_stack_layer* L, int32_t n_laye
                                int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start,
                                const void* w_final_norm /* NULL: none */, float final_eps, int32_t tail_norm, void* out,
                                void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- the head of a decode step: everything between the last layer and the next token's logits.  For the B <= 64 rows of a step,
+ *   xn     = what u2tok_rmsnorm_bf16 makes of the UN-NORMED hidden rows x (B, E; ldx elements between rows) with w_norm and eps;
+ *   logits = (B, V) FP32, ld_logits >= V floats between rows: what the few-rows product of the head's weight form makes of xn with
+ *            fp32 C (flag 16) -- wform 0: u2tok_gemm_rows on W (V, E) in the element type; 1: u2tok_gemm_rows_w8_wide on e4m3 codes
+ *            with scale = fp32 (V); 2: u2tok_gemm_rows_w4 on e2m1 codes with scale = the e8m0 block-scale bytes (V, E / 32)
+ * -- bit for bit: the entry adds no kernel, it launches those two.  The logits are not rounded to 16 bits on the way.  Columns of
+ * the logits' rows beyond V are neither read nor written.  ldw (elements for wform 0, bytes for codes) and lds (bytes): 0 = dense.
+ * U2TOK_ERR_ARG, nothing launched: B outside 1 .. 64, V < 2, a null pointer (scale with wform 1 / 2), an unknown wform, ldx < E,
+ * ld_logits < V, a workspace not 16-byte aligned, and everything u2tok_rmsnorm_bf16 (E % 8, E <= 8192, 16-byte aligned x and
+ * w_norm) and the product of that form (E % 32 / 64 / 128, 16-byte aligned W, ...) refuse; U2TOK_ERR_WORKSPACE: fewer than
+ * u2tok_decode_head_workspace_bytes(B, E) bytes (the normed rows; 0 for B outside 1 .. 64 or E < 1). */
+typedef struct u2tok_decode_head_desc {
+  const void* w_norm;  /* (E), element type: the stack's final RMSNorm */
+  const void* W;       /* (V, E) in wform */
+  const void* scale;   /* wform 0: ignored; 1: fp32 (V); 2: e8m0 bytes (V, E / 32) */
+  int32_t E, V;
+  int32_t wform;       /* 0 = element type, 1 = e4m3 with a scale per row, 2 = e2m1 with e8m0 block scales */
+  float eps;
+  int64_t ldw, lds;    /* 0: dense */
+} u2tok_decode_head_desc;
+size_t u2tok_decode_head_workspace_bytes(int32_t B, int32_t E);
+int u2tok_decode_head(const u2tok_decode_head_desc* head, const void* x, int64_t ldx, int32_t B, float* logits, int64_t ld_logits,
+                      void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* u2tok_decoder_decode_stack (with w_final_norm = NULL: out (B, E) receives the last layer's hidden rows as they are) followed by
+ * u2tok_decode_head on out, in ONE call with the bits of the two.  The stack step's rule covers both: every refusal of every layer
+ * AND of the head is evaluated before the first launch -- an error code means nothing was launched, no cache row, hidden row or logit
+ * was written.  head->E must be the layers' E, B is theirs.  workspace: u2tok_decoder_decode_stack_head_workspace_bytes(L, n_layers,
+ * head) bytes (0: descriptors it refuses) -- the stack step's workspace, ticket included, followed by the head's --, 256-byte aligned. */
+size_t u2tok_decoder_decode_stack_head_workspace_bytes(const u2tok_decode_stack_layer* L, int32_t n_layers, const u2tok_decode_head_desc* head);
+int u2tok_decoder_decode_stack_head(const u2tok_decode_stack_layer* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                                    int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start, int32_t tail_norm,
+                                    void* out, const u2tok_decode_head_desc* head, float* logits, int64_t ld_logits, void* workspace,
+                                    size_t workspace_bytes, u2tok_stream_t stream);
 /* ---- products on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
  * attention and the KV cache stay in the element type).  A product is exactly x . (scale[n] * e4m3(W8[n][:])) with fp32
  * accumulation -- the codes are widened to the element type in registers, where every e4m3 value is exact --, so all the loss is
@@ -697,6 +730,21 @@ int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_
 size_t u2tok_sample_warp_workspace_bytes(int32_t rows, int32_t V);
 int u2tok_sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
                       int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* The split-row form, for calls of a few rows: the semantics, arguments, refusals and determinism of u2tok_sample_warp word for word,
+ * and `out` BIT-EQUAL to its `out` on the same input, with equal kept counts (record word 5; the other record words need not match).
+ * A row is spread over min(16, ceil(V / 8192)) workgroups and every pass of the descent is a launch of its own on the caller's
+ * stream: each workgroup adds the non-empty bins of its slice's histogram to a per-row table in the workspace with device-scope
+ * integer atomics (counts and 2^-40 masses: no sum depends on an order), the NEXT launch reads the table, and every workgroup takes
+ * the bin decision from it again.  The kernel boundary is the only ordering between workgroups: nobody spins, nobody waits.  The number
+ * of launches follows from the parameters alone (u2tok_sample_warp_split_launches: 3 + 4 with a top-k stage + 8 with a top-p stage
+ * + 8 with top-p and min_keep > 1); a launch whose pass is decided already returns at once.  The call does not depend on what the
+ * workspace holds at entry (its first launch zeroes what the others accumulate into).  out may be logits: the last launch is the
+ * only writer.  workspace: u2tok_sample_warp_split_workspace_bytes(rows, V) bytes, 4-byte aligned: the records of
+ * u2tok_sample_warp, then about 61 KB per row. */
+size_t u2tok_sample_warp_split_workspace_bytes(int32_t rows, int32_t V);
+int32_t u2tok_sample_warp_split_launches(int32_t V, int32_t top_k, float top_p, int32_t min_keep);
+int u2tok_sample_warp_split(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
+                            int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
 /* ---- rank-r adapter (LoRA) products of the decoder training route (csrc/lora.hip; u2tokenizer_amd/decoder_train.py: LoraDeltaFn) ----
  * Three bandwidth-bound kernels for r in {16, 32, 64}, outside u2tok_gemm_bf16's plan.  All operands are 16-bit elements of the

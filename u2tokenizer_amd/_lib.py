@@ -87,6 +87,11 @@ class DecodeStackLayer(C.Structure):   # u2tok_decode_stack_layer: one layer of 
                 ("kv_stride", C.c_int64), ("s_off", C.c_int32), ("k_first", C.c_int32), ("T", C.c_int32)]
 
 
+class DecodeHead(C.Structure):    # u2tok_decode_head_desc: the final RMSNorm and the output matrix of a decode step's head
+    _fields_ = [("w_norm", C.c_void_p), ("W", C.c_void_p), ("scale", C.c_void_p), ("E", C.c_int32), ("V", C.c_int32),
+                ("wform", C.c_int32), ("eps", C.c_float), ("ldw", C.c_int64), ("lds", C.c_int64)]
+
+
 class TokTaps(C.Structure):
     _fields_ = [("svr_in", C.POINTER(C.c_void_p)), ("svr_out", C.POINTER(C.c_void_p)), ("visual_in", C.c_void_p),
                 ("visual_out", C.c_void_p), ("tta_in", C.POINTER(C.c_void_p)), ("tta_out", C.POINTER(C.c_void_p))]
@@ -166,6 +171,15 @@ SIGNATURES = {
     # layers, n_layers, x, cos, sin, cos_sin_f32, cs_ld, batched, kv_start, w_final_norm, final_eps, tail_norm, out, workspace,
     # workspace_bytes, stream
     "u2tok_decoder_decode_stack": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
+    "u2tok_decode_head_workspace_bytes": (_sz, [_i32, _i32]),
+    # head, x, ldx, B, logits, ld_logits, workspace, workspace_bytes, stream
+    "u2tok_decode_head": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _sz, _vp]),
+    # layers, n_layers, head
+    "u2tok_decoder_decode_stack_head_workspace_bytes": (_sz, [_vp, _i32, _vp]),
+    # layers, n_layers, x, cos, sin, cos_sin_f32, cs_ld, batched, kv_start, tail_norm, out, head, logits, ld_logits, workspace,
+    # workspace_bytes, stream
+    "u2tok_decoder_decode_stack_head": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _sz,
+                                               _vp]),
     "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_gemm_rows_w8_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     # A, W4, S, C, bias, R, M, N, K, lda, ldw, lds, ldc, ldr, flags, stream
@@ -215,6 +229,9 @@ SIGNATURES = {
     "u2tok_sample_warp_workspace_bytes": (_sz, [_i32, _i32]),
     # logits, ld_in, out, ld_out, rows, V, temperature, top_k, top_p, min_keep, workspace, workspace_bytes, stream
     "u2tok_sample_warp": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _sz, _vp]),
+    "u2tok_sample_warp_split_workspace_bytes": (_sz, [_i32, _i32]),
+    "u2tok_sample_warp_split_launches": (_i32, [_i32, _i32, _f32, _i32]),   # V, top_k, top_p, min_keep
+    "u2tok_sample_warp_split": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _sz, _vp]),
     # X, x_off, ldx, A, lda, U, ldu, M, K, r, alpha, stream
     "u2tok_lora_down": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     # U, ldu, W, ldw, Y, y_off, ldy, M, N, r, alpha, accumulate, stream

@@ -394,6 +394,42 @@ int u2tok_decoder_decode_stack(const u2tok_decode_stack_layer* L, int32_t n_laye
   return decoder_decode_stack(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, batched != 0, kv_start, BF(w_final_norm), final_eps,
                               tail_norm != 0, BFW(out), workspace, workspace_bytes, ST(stream));
 }
+// ---- the head of the step (decoder.hip): wform names the form outright (0 / 1 / 2); a leading dimension of 0 is the dense one
+static int head_args(const u2tok_decode_head_desc* h, DecodeHead& d) {
+  if (!h || h->wform < 0 || h->wform > 2 || h->E <= 0 || h->ldw < 0 || h->lds < 0) return U2_ERR_ARG;
+  d.form = (WForm)h->wform;
+  d.w_norm = BF(h->w_norm); d.W = h->W; d.scale = h->scale;
+  d.E = h->E; d.V = h->V; d.eps = h->eps;
+  d.ldw = h->ldw ? h->ldw : h->E / wform_facts(d.form).ldw_div;
+  d.lds = h->lds ? h->lds : h->E >> 5;
+  return U2_OK;
+}
+size_t u2tok_decode_head_workspace_bytes(int32_t B, int32_t E) { return decode_head_workspace_bytes(B, E); }
+int u2tok_decode_head(const u2tok_decode_head_desc* head, const void* x, int64_t ldx, int32_t B, float* logits, int64_t ld_logits,
+                      void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  DecodeHead d;
+  const int e = head_args(head, d);
+  if (e != U2_OK) return e;
+  return decode_head(d, BF(x), ldx, B, logits, ld_logits, workspace, workspace_bytes, ST(stream));
+}
+size_t u2tok_decoder_decode_stack_head_workspace_bytes(const u2tok_decode_stack_layer* L, int32_t n_layers, const u2tok_decode_head_desc* head) {
+  std::vector<DecodeStackLayer> v;
+  DecodeHead d;
+  if (stack_args(L, n_layers, v) != U2_OK || head_args(head, d) != U2_OK) return 0;
+  return decoder_decode_stack_head_workspace_bytes(v.data(), n_layers, d);
+}
+int u2tok_decoder_decode_stack_head(const u2tok_decode_stack_layer* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                                    int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start, int32_t tail_norm,
+                                    void* out, const u2tok_decode_head_desc* head, float* logits, int64_t ld_logits, void* workspace,
+                                    size_t workspace_bytes, u2tok_stream_t stream) {
+  std::vector<DecodeStackLayer> v;
+  DecodeHead d;
+  int e = stack_args(L, n_layers, v);
+  if (e == U2_OK) e = head_args(head, d);
+  if (e != U2_OK) return e;
+  return decoder_decode_stack_head(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, batched != 0, kv_start, tail_norm != 0, BFW(out), d,
+                                   logits, ld_logits, workspace, workspace_bytes, ST(stream));
+}
 // ---- the few-rows product (gemm_rows.hip): one filler for the five exports; a quantised form without its scales is refused here
 static int rows(WForm form, const void* A, const void* W, const void* scale, int64_t lds, void* C, const void* bias, const void* R,
                 int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream,
@@ -496,6 +532,14 @@ int u2tok_ce_stats_update(const void* Z, int64_t ldz, int32_t rows, int32_t Vs, 
 int u2tok_ce_grad_inplace(void* Z, int64_t ldz, int32_t rows, int32_t Vs, int64_t v0, const int64_t* labels, const float* lse,
                           const float* coef, u2tok_stream_t stream) {
   return ce_grad_inplace(BFW(Z), ldz, rows, Vs, v0, labels, lse, coef, ST(stream));
+}
+size_t u2tok_sample_warp_split_workspace_bytes(int32_t rows, int32_t V) { return sample_warp_split_workspace_bytes(rows, V); }
+int32_t u2tok_sample_warp_split_launches(int32_t V, int32_t top_k, float top_p, int32_t min_keep) {
+  return sample_warp_split_launches(V, top_k, top_p, min_keep);
+}
+int u2tok_sample_warp_split(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,
+                            int32_t top_k, float top_p, int32_t min_keep, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return sample_warp_split(logits, ld_in, out, ld_out, rows, V, temperature, top_k, top_p, min_keep, workspace, workspace_bytes, ST(stream));
 }
 size_t u2tok_sample_warp_workspace_bytes(int32_t rows, int32_t V) { return sample_warp_workspace_bytes(rows, V); }
 int u2tok_sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int32_t rows, int32_t V, float temperature,

@@ -434,9 +434,10 @@ size_t decoder_decode_stack_workspace_bytes(const DecodeStackLayer* L, int n) {
   return 256 + stack_layer_ws(L, n) + stack_qkv_bytes(L, n) + 2 * stack_hidden_bytes(L[0].cfg);
 }
 
-int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
-                         bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
-                         size_t ws_bytes, hipStream_t st) {
+// passes: DEC_CHECK | DEC_RUN is the step; the step with the head asks for the two walks one at a time, its head's checks between them
+static int stack_walk(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
+                      bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
+                      size_t ws_bytes, hipStream_t st, int passes) {
   if (!L || n <= 0 || !x || !out || !ws || ((uintptr_t)ws & 255)) return U2_ERR_ARG;
   const DecodeCfg& c0 = L[0].cfg;
   for (int i = 0; i < n; ++i) {
@@ -457,6 +458,7 @@ int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, cons
   bf16_t* xn = reinterpret_cast<bf16_t*>(lws);  // (where every layer's first half keeps its normed input: dec_pre)
   bool have_xn = false;
   for (int pass = DEC_CHECK; pass <= DEC_RUN; ++pass) {  // every refusal of every layer, then every launch
+    if (!(passes & pass)) continue;
     const bf16_t* cur = x;
     for (int i = 0; i < n; ++i) {
       const DecodeStackLayer& s = L[i];
@@ -485,6 +487,80 @@ int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, cons
     have_xn = false;
   }
   return U2_OK;
+}
+
+int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
+                         bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+  return stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, w_final, final_eps, tail_norm, out, ws, ws_bytes, st,
+                    DEC_CHECK | DEC_RUN);
+}
+
+// ------------------------------------------------------------------------------------------------ the head of a decode step
+// Everything between the last layer and the next token's logits, for the B <= 64 rows of a step: the stack's final RMSNorm of the
+// un-normed hidden rows x (B, E; ldx) into the workspace, then logits (B, V; fp32, ldl) = normed rows . W^T on the few-rows product
+// in the head's weight form.  No kernel of its own: rmsnorm_bf16, then gemm_rows with GEMM_OUT_F32 -- the logits are by definition
+// the bits of those two calls.
+size_t decode_head_workspace_bytes(int B, int E) {
+  return B > 0 && B <= 64 && E > 0 ? ((size_t)B * E * sizeof(bf16_t) + 255) & ~(size_t)255 : 0;
+}
+
+static RowsArgs head_rows(const DecodeHead& h, const bf16_t* xn, int B, float* logits, int64_t ldl) {
+  RowsArgs a;
+  a.A = xn; a.W = h.W; a.scale = h.scale; a.form = h.form; a.C = logits;
+  a.M = B; a.N = h.V; a.K = h.E;
+  a.lda = h.E; a.ldw = h.ldw; a.lds = h.lds; a.ldc = ldl;
+  a.flags = GEMM_OUT_F32;
+  return a;
+}
+
+// (every refusal of the head, nothing launched: its own, the norm's, the product's)
+static int head_check(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes) {
+  if (!wform_known(h.form) || B <= 0 || B > 64 || h.E <= 0 || h.V < 2 || !x || !h.w_norm || !h.W || !logits || !ws || ((uintptr_t)ws & 15))
+    return U2_ERR_ARG;
+  if (h.form != WForm::ELEM && !h.scale) return U2_ERR_ARG;
+  if (ldx < h.E || ldl < h.V) return U2_ERR_ARG;
+  bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
+  int e = rmsnorm_check(x, h.w_norm, xn, B, h.E, ldx, h.E);
+  if (e == U2_OK) e = gemm_rows_check(head_rows(h, xn, B, logits, ldl));
+  if (e != U2_OK) return e;
+  return ws_bytes < decode_head_workspace_bytes(B, h.E) ? U2_ERR_WORKSPACE : U2_OK;
+}
+
+static int head_run(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, hipStream_t st) {
+  bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
+  const int e = rmsnorm_bf16(x, h.w_norm, xn, B, h.E, ldx, h.E, h.eps, st);
+  return e != U2_OK ? e : gemm_rows(head_rows(h, xn, B, logits, ldl), st);
+}
+
+int decode_head(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes,
+                hipStream_t st) {
+  const int e = head_check(h, x, ldx, B, logits, ldl, ws, ws_bytes);
+  return e != U2_OK ? e : head_run(h, x, ldx, B, logits, ldl, ws, st);
+}
+
+// The whole-stack step followed by the head, in one call: out (B, E) receives the last layer's hidden rows as they are (the stack
+// step with w_final = null), the head norms them and writes the logits.  The workspace is the stack step's followed by the head's.
+// The stack's rule holds for both: the layers' DEC_CHECK walk, then the head's checks, and only then the first launch.
+size_t decoder_decode_stack_head_workspace_bytes(const DecodeStackLayer* L, int n, const DecodeHead& h) {
+  const size_t s = decoder_decode_stack_workspace_bytes(L, n);
+  if (s == 0 || h.E != L[0].cfg.E) return 0;
+  const size_t hb = decode_head_workspace_bytes(L[0].cfg.B, h.E);
+  return hb ? s + hb : 0;
+}
+
+int decoder_decode_stack_head(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                              int64_t cs_ld, bool batched, const int* kv_start, bool tail_norm, bf16_t* out, const DecodeHead& h,
+                              float* logits, int64_t ldl, void* ws, size_t ws_bytes, hipStream_t st) {
+  const size_t sb = decoder_decode_stack_workspace_bytes(L, n);  // (0: null or no layers, descriptors the step refuses)
+  if (sb == 0 || !ws || h.E != L[0].cfg.E) return U2_ERR_ARG;
+  if (ws_bytes < sb) return U2_ERR_WORKSPACE;
+  const int B = L[0].cfg.B;
+  void* hws = reinterpret_cast<char*>(ws) + sb;
+  int e = stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, nullptr, 0.f, tail_norm, out, ws, sb, st, DEC_CHECK);
+  if (e == U2_OK) e = head_check(h, out, h.E, B, logits, ldl, hws, ws_bytes - sb);
+  if (e == U2_OK) e = stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, nullptr, 0.f, tail_norm, out, ws, sb, st, DEC_RUN);
+  return e != U2_OK ? e : head_run(h, out, h.E, B, logits, ldl, hws, st);
 }
 
 }  // namespace u2

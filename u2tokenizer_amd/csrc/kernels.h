@@ -256,6 +256,13 @@ int ce_grad_inplace(bf16_t* Z, int64_t ldz, int rows, int Vs, int64_t v0, const 
                     hipStream_t stream);
 // sampling warper (sample.hip): temperature / top-k / top-p filtering of fp32 logits, one launch, no sort
 size_t sample_warp_workspace_bytes(int rows, int V);
+// The split-row form (sample.hip): sample_warp's contract and bits of `out`, a row over min(16, ceil(V / SAMPLE_SPLIT_SLICE)) workgroups,
+// one launch per pass of the descent (sample_warp_split_launches of them, fixed by the parameters alone)
+constexpr int SAMPLE_SPLIT_SLICE = 8192;
+size_t sample_warp_split_workspace_bytes(int rows, int V);
+int sample_warp_split_launches(int V, int top_k, float top_p, int min_keep);
+int sample_warp_split(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int rows, int V, float temperature, int top_k,
+                      float top_p, int min_keep, void* ws, size_t ws_bytes, hipStream_t st);
 int sample_warp(const float* logits, int64_t ld_in, float* out, int64_t ld_out, int rows, int V, float temperature, int top_k,
                 float top_p, int min_keep, void* ws, size_t ws_bytes, hipStream_t stream);
 // sharded AdamW step (dp.py): see backward.hip
@@ -419,6 +426,28 @@ size_t decoder_decode_stack_workspace_bytes(const DecodeStackLayer* L, int n);
 int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
                          bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
                          size_t ws_bytes, hipStream_t st);
+// The head of a decode step (capi.hip decodes u2tok_decode_head_desc into it): the stack's final RMSNorm (w_norm (E), eps), then the
+// output matrix W (V, E) in `form` -- ldw elements (ELEM) or bytes (codes) between rows; scale: [V] fp32 (E4M3) or [V][E / 32] e8m0
+// bytes with lds bytes between rows (E2M1).
+struct DecodeHead {
+  const bf16_t* w_norm = nullptr;
+  const void *W = nullptr, *scale = nullptr;
+  WForm form = WForm::ELEM;
+  int E = 0, V = 0;
+  float eps = 0.f;
+  int64_t ldw = 0, lds = 0;
+};
+// logits (B <= 64, V; fp32, ldl) = gemm_rows(GEMM_OUT_F32) of rmsnorm_bf16 of x (B, E; ldx), bit for bit; the normed rows live in
+// the workspace (16-byte aligned).  decoder_decode_stack_head: decoder_decode_stack with w_final = null into out, then the head on
+// out, in one call whose every refusal -- the layers' and the head's -- precedes its first launch; workspace: the stack step's, then
+// the head's.
+size_t decode_head_workspace_bytes(int B, int E);
+int decode_head(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes,
+                hipStream_t st);
+size_t decoder_decode_stack_head_workspace_bytes(const DecodeStackLayer* L, int n, const DecodeHead& h);
+int decoder_decode_stack_head(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                              int64_t cs_ld, bool batched, const int* kv_start, bool tail_norm, bf16_t* out, const DecodeHead& h,
+                              float* logits, int64_t ldl, void* ws, size_t ws_bytes, hipStream_t st);
 // ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
 // One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
 // q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between

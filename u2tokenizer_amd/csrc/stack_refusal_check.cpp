@@ -1,5 +1,5 @@
 // Stand-alone check of the whole-stack decode step's refusal walk (decoder.hip: decoder_decode_stack; capi.hip: the decoding of the
-// layer descriptors), meant to be built with the host code under AddressSanitizer and UBSan (make stack_refusal_check) and run on a
+// layer descriptors) and of the head's (decode_head, decoder_decode_stack_head; u2tok_decode_head_desc), meant to be built with the host code under AddressSanitizer and UBSan (make stack_refusal_check) and run on a
 // CPU: every call below must return its error code from the walk that precedes the first launch -- without a GPU a launch would not
 // return one of these codes -- and must not read or write anything but the descriptors.
 #include <cstdio>
@@ -78,6 +78,68 @@ int main() {
   std::vector<u2tok_decode_stack_layer> many(64, L[0]);
   many[63].layer = nullptr;
   expect("64 layers, the last one bad", call(many.data(), 64, u2tok_decoder_decode_stack_workspace_bytes(L, 1), 0), U2TOK_ERR_ARG);
+  // ---- the head of the step (u2tok_decode_head) and the step with the head (u2tok_decoder_decode_stack_head): the head's refusals
+  // come from the check-only pass that follows the layers' walk, so a good stack with a bad head launches nothing either
+  constexpr int V = 1000;
+  float* LG = reinterpret_cast<float*>(mem);
+  const u2tok_decode_head_desc good{P, P, nullptr, E, V, 0, 1e-6f, 0, 0};
+  const size_t hneed = u2tok_decode_head_workspace_bytes(B, E);
+  expect("head workspace bytes", (long long)hneed, 1024);
+  expect("head workspace bytes of no rows", (long long)u2tok_decode_head_workspace_bytes(0, E), 0);
+  expect("head workspace bytes of 65 rows", (long long)u2tok_decode_head_workspace_bytes(65, E), 0);
+  const size_t sneed = u2tok_decoder_decode_stack_head_workspace_bytes(L, n, &good);
+  expect("stack + head workspace bytes", (long long)sneed, (long long)(need + hneed));
+  expect("stack + head workspace bytes of a null head", (long long)u2tok_decoder_decode_stack_head_workspace_bytes(L, n, nullptr), 0);
+  struct HeadCase { const char* what; u2tok_decode_head_desc h; int64_t ldx, ldl; int rows; void* ws; size_t short_by; int want; };  // (both entries)
+  auto with = [&](auto edit) { u2tok_decode_head_desc h = good; edit(h); return h; };
+  char* Pc = mem;
+  const HeadCase cases[] = {
+      {"V = 1", with([](u2tok_decode_head_desc& h) { h.V = 1; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"null W", with([](u2tok_decode_head_desc& h) { h.W = nullptr; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"null norm weight", with([](u2tok_decode_head_desc& h) { h.w_norm = nullptr; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"misaligned W", with([&](u2tok_decode_head_desc& h) { h.W = Pc + 8; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"unknown form", with([](u2tok_decode_head_desc& h) { h.wform = 3; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"e4m3 without scales", with([](u2tok_decode_head_desc& h) { h.wform = 1; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"e2m1 without scales", with([](u2tok_decode_head_desc& h) { h.wform = 2; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"e4m3 with a misaligned scale", with([&](u2tok_decode_head_desc& h) { h.wform = 1; h.scale = Pc + 2; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"e2m1 with a short scale row", with([&](u2tok_decode_head_desc& h) { h.wform = 2; h.scale = Pc; h.lds = E / 32 - 1; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"a weight row shorter than E", with([](u2tok_decode_head_desc& h) { h.ldw = E - 8; }), E, V, B, P, 0, U2TOK_ERR_ARG},
+      {"logits rows shorter than V", good, E, V - 1, B, P, 0, U2TOK_ERR_ARG},
+      {"misaligned workspace", good, E, V, B, Pc + 8, 0, U2TOK_ERR_ARG},
+      {"null workspace", good, E, V, B, nullptr, 0, U2TOK_ERR_ARG},
+      {"short workspace", good, E, V, B, P, 1, U2TOK_ERR_WORKSPACE},
+  };
+  for (const HeadCase& c : cases) {
+    expect(c.what, u2tok_decode_head(&c.h, P, c.ldx, c.rows, LG, c.ldl, c.ws, hneed - c.short_by, nullptr), c.want);
+    expect(c.what, u2tok_decoder_decode_stack_head(L, n, P, P, P, 1, 64, 0, nullptr, 0, P, &c.h, LG, c.ldl, c.ws, sneed - c.short_by, nullptr),
+           c.want);
+  }
+  // (shapes that are the standalone entry's alone)
+  const u2tok_decode_head_desc e192 = with([&](u2tok_decode_head_desc& h) { h.wform = 2; h.scale = Pc; h.E = 192; });
+  const u2tok_decode_head_desc e96 = with([&](u2tok_decode_head_desc& h) { h.wform = 1; h.scale = Pc; h.E = 96; });
+  const u2tok_decode_head_desc e512 = with([](u2tok_decode_head_desc& h) { h.E = 512; });
+  expect("E % 128 != 0 with e2m1", u2tok_decode_head(&e192, P, 192, B, LG, V, P, 4096, nullptr), U2TOK_ERR_ARG);
+  expect("E % 64 != 0 with e4m3", u2tok_decode_head(&e96, P, 96, B, LG, V, P, 4096, nullptr), U2TOK_ERR_ARG);
+  expect("x rows shorter than E", u2tok_decode_head(&good, P, E - 8, B, LG, V, P, hneed, nullptr), U2TOK_ERR_ARG);
+  expect("65 rows", u2tok_decode_head(&good, P, E, 65, LG, V, P, 1 << 20, nullptr), U2TOK_ERR_ARG);
+  expect("no rows", u2tok_decode_head(&good, P, E, 0, LG, V, P, hneed, nullptr), U2TOK_ERR_ARG);
+  expect("null head", u2tok_decode_head(nullptr, P, E, B, LG, V, P, hneed, nullptr), U2TOK_ERR_ARG);
+  expect("null x", u2tok_decode_head(&good, nullptr, E, B, LG, V, P, hneed, nullptr), U2TOK_ERR_ARG);
+  expect("null logits", u2tok_decode_head(&good, P, E, B, nullptr, V, P, hneed, nullptr), U2TOK_ERR_ARG);
+  // the joint call: the head's hidden size is the layers', a bad layer is still refused, a null head too
+  auto joint = [&](const u2tok_decode_head_desc* h, size_t bytes) {
+    return u2tok_decoder_decode_stack_head(L, n, P, P, P, 1, 64, 0, nullptr, 0, P, h, LG, V, P, bytes, nullptr);
+  };
+  expect("joint: null head", joint(nullptr, sneed), U2TOK_ERR_ARG);
+  expect("joint: another hidden size", joint(&e512, sneed), U2TOK_ERR_ARG);
+  expect("joint: room for the stack but not for the head", joint(&good, need), U2TOK_ERR_WORKSPACE);
+  expect("joint: no room for the stack", joint(&good, need - 1), U2TOK_ERR_WORKSPACE);
+  lay[2].Wdown = nullptr;
+  expect("joint: layer 2 Wdown null", joint(&good, sneed), U2TOK_ERR_ARG);
+  lay[2].Wdown = P;
+  lay[0].w_in_norm = nullptr;
+  expect("joint: layer 0 input norm null", joint(&good, sneed), U2TOK_ERR_ARG);
+  lay[0].w_in_norm = P;
   if (failures == 0) std::printf("stack_refusal_check: ok\n");
   return failures != 0;
 }

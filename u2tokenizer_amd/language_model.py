@@ -206,6 +206,15 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
                     shift=shifted is None)
             return CausalLMOutputWithPast(loss=loss, logits=predictions, past_key_values=outputs.past_key_values,
                                           hidden_states=outputs.hidden_states, attentions=outputs.attentions)
+        if "_u2_stack" in self.model.__dict__:
+            # `config.u2_fused_decode_head` (default False): a decode step without labels that the whole-stack route admits runs
+            # its head in the same library call (prefill.head_route: final norm, lm_head in `config.u2_fused_head_form`, logits
+            # (B, 1, V) fp32); every other call goes on below as it came
+            from . import prefill
+            out = prefill.head_forward(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache,
+                                       labels, kwargs)
+            if out is not None:
+                return out
         return super().forward(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                use_cache=use_cache, **kwargs)
@@ -213,11 +222,12 @@ class _u2CausalLMMixin(u2MetaForCausalLM):
     def _get_logits_processor(self, *args, **kwargs):
         """transformers' processor list; with `config.u2_fused_sampling` (default False) its temperature / top-k / top-p run becomes one
         FusedSamplingWarper (sampling.py: one HIP launch, no sort; beam sampling's min_tokens_to_keep = 2 included).  With the switch off
-        the list is returned untouched."""
+        the list is returned untouched.  `config.u2_fused_sampling_split` (default False, read only with the first): calls of at most
+        sampling.SPLIT_MAX_ROWS rows take the split-row form of the kernel (the same bits)."""
         processors = super()._get_logits_processor(*args, **kwargs)
         if bool(getattr(self.config, "u2_fused_sampling", False)):
             from .sampling import fuse_warpers
-            processors = fuse_warpers(processors)
+            processors = fuse_warpers(processors, split=bool(getattr(self.config, "u2_fused_sampling_split", False)))
         return processors
 
     @torch.no_grad()

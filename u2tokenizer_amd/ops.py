@@ -953,6 +953,51 @@ def gemm_rows_norm(a: torch.Tensor, w: torch.Tensor, norm_weight: torch.Tensor, 
     return out, out_norm
 
 
+def head_desc(norm_weight: torch.Tensor, eps: float, w: torch.Tensor, scale: Optional[torch.Tensor] = None):
+    """The u2tok_decode_head_desc of a final RMSNorm weight (E,) and an output matrix: w (V, E) in the element type (scale None; it
+    may be a row-strided view), float8_e4m3fn with `scale` (V,) fp32, or uint8 e2m1 codes (V, E / 2) with `scale` (V, E / 32) uint8
+    block scales -- the operands of gemm_rows, gemm_rows_w8 and gemm_rows_w4.  Holds raw addresses: the caller keeps the tensors."""
+    E = norm_weight.numel()
+    if scale is None:
+        wform, cols, ldw, lds = 0, E, w.stride(0), 0
+    elif w.dtype == torch.float8_e4m3fn:
+        wform, cols, ldw, lds = 1, E, E, 0
+    else:
+        wform, cols, ldw, lds = 2, E // 2, E // 2, E // 32
+    if w.dim() != 2 or w.shape[1] != cols or w.stride(1) != 1 or not w.is_cuda or not norm_weight.is_contiguous() or (
+            wform and not (w.is_contiguous() and scale.is_contiguous() and scale.is_cuda)):
+        raise RuntimeError(f"head_desc: expected a (V, E = {E}) output matrix on the GPU -- elements, or contiguous codes and scales --, "
+                           f"got {tuple(w.shape)} {w.dtype}")
+    return _lib.DecodeHead(w_norm=_ptr(norm_weight), W=_ptr(w), scale=_ptr(scale), E=E, V=w.shape[0], wform=wform, eps=float(eps),
+                           ldw=ldw, lds=lds)
+
+
+@_guarded
+def decode_head(x: torch.Tensor, norm_weight: torch.Tensor, eps: float, w: torch.Tensor, scale: Optional[torch.Tensor] = None, *,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The head of a decode step (u2tok_decode_head): fp32 logits (B <= 64, V) = the few-rows product of the head's weight form,
+    with fp32 C, on rmsnorm(x, norm_weight, eps) of the UN-NORMED hidden rows x (B, E) -- the bits of `rmsnorm` followed by
+    gemm_rows / gemm_rows_w8 / gemm_rows_w4 (..., out_f32=True), in one library call.  w / scale: as `head_desc` takes them.
+    `out`: an fp32 (B, V) view with unit column stride (a row-strided one keeps its other columns)."""
+    h = _lib.load_library()
+    _need(x, ELEM, "x"), _need(norm_weight, ELEM, "norm_weight")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] != norm_weight.numel():
+        raise RuntimeError("decode_head: x must be (B, E) with a contiguous last dim")
+    if scale is None:
+        _need(w, ELEM, "W")
+    desc = head_desc(norm_weight, eps, w, scale)
+    B, V = x.shape[0], desc.V
+    if out is None:
+        out = torch.empty((B, V), dtype=torch.float32, device=x.device)
+    if out.shape != (B, V) or out.stride(1) != 1 or out.dtype != torch.float32 or not out.is_cuda:
+        raise RuntimeError("decode_head: out must be fp32 (B, V) with unit column stride on the GPU")
+    need = h.u2tok_decode_head_workspace_bytes(B, desc.E)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    _lib.check(h.u2tok_decode_head(C.addressof(desc), _ptr(x), x.stride(0), B, _ptr(out), out.stride(0), _ptr(ws), need, _stream()),
+               "u2tok_decode_head")
+    return out
+
+
 # ---------------------------------------------------------------------------------- rank-r adapter (LoRA) products
 def _segment(t: torch.Tensor, name: str):
     """A 2-D view with unit column stride -> (tensor, element offset 0, row stride): the kernels take a column segment of a packed
@@ -1532,4 +1577,32 @@ def sample_warp(scores: torch.Tensor, temperature: float = 1.0, top_k: int = 0, 
     _lib.check(h.u2tok_sample_warp(_ptr(scores), scores.stride(0) if rows > 1 else V, _ptr(out), out.stride(0) if rows > 1 else V,
                                    rows, V, float(temperature), int(top_k), float(top_p), int(min_keep), _ptr(ws), nbytes,
                                    _stream()), "u2tok_sample_warp")
+    return out
+
+
+@_guarded(infer=False)
+def sample_warp_split(scores: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_keep: int = 1,
+                      out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sample_warp` with every row spread over several workgroups and one launch per pass of the descent (u2tok_sample_warp_split):
+    the same arguments, `out` bit-equal to sample_warp's; for calls of a few rows.  workspace: a uint8 tensor of at least
+    u2tok_sample_warp_split_workspace_bytes(rows, V) bytes to use instead of a fresh one (its contents do not matter; afterwards
+    its first 32 bytes per row are the row's record)."""
+    h = _lib.load_library()
+    _need(scores, torch.float32, "scores")
+    if scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] < 1 or scores.shape[1] < 2:
+        raise RuntimeError(f"sample_warp_split: scores must be (rows >= 1, V >= 2) with a contiguous last dim, got {tuple(scores.shape)}")
+    rows, V = scores.shape
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=scores.device)
+    else:
+        _need(out, torch.float32, "out")
+        if out.shape != scores.shape or out.stride(1) != 1 or out.device != scores.device:
+            raise RuntimeError("sample_warp_split: out must be an fp32 (rows, V) tensor on the scores' device with a contiguous last dim")
+    nbytes = h.u2tok_sample_warp_split_workspace_bytes(rows, V)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=scores.device) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != scores.device or ws.numel() < nbytes:
+        raise RuntimeError(f"sample_warp_split: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on the scores' device")
+    _lib.check(h.u2tok_sample_warp_split(_ptr(scores), scores.stride(0) if rows > 1 else V, _ptr(out), out.stride(0) if rows > 1 else V,
+                                         rows, V, float(temperature), int(top_k), float(top_p), int(min_keep), _ptr(ws), ws.numel(),
+                                         _stream()), "u2tok_sample_warp_split")
     return out

@@ -34,6 +34,10 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
   * stack_decode: the decoder STACK's forward is wrapped as well; a decode step that `route` would hand to the fused step in every
     layer (`stack_route`) runs as one library call for all of them (`_stack_step`: u2tok_decoder_decode_stack, the per-layer calls'
     launches in their order), with the bits of the per-layer route; every other call goes on to the stack's own forward.
+  * head: a u2 causal LM's call that `head_route` admits runs the whole-stack step WITH its head (`_stack_step(..., head=)`:
+    u2tok_decoder_decode_stack_head -- the stack's final RMSNorm and lm_head, in `config.u2_fused_head_form`, fp32 logits) from
+    `language_model._u2CausalLMMixin.forward` through `head_forward`; the head's descriptor and quantised copy live on the model
+    (`_HeadState`), not in the stack's state.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -128,6 +132,11 @@ SWITCHES = (
            "a decode step the fused step would take layer by layer runs as ONE library call for the whole decoder stack "
            "(u2tok_decoder_decode_stack: the per-layer calls' launches in their order, the same bits, no Python between the "
            "layers; `stack_route` lists what it asks, everything else keeps the per-layer routes); `stack_stats`"),
+    Switch("head", "head", "u2_fused_decode_head", False, ("stack_decode",), (), (),
+           "a whole-stack step of a causal LM called without labels also runs its head -- the stack's final RMSNorm and lm_head, "
+           "fp32 logits -- in the same library call (u2tok_decoder_decode_stack_head); `head_route` lists what it asks, every other "
+           "call runs the module norm and nn.Linear as before; `config.u2_fused_head_form` (\"elem\", \"fp8\", \"fp4\") picks lm_head's "
+           "weight form, the quantised ones unmeasured in accuracy on trained weights; `head_stats`"),
 )
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
@@ -147,6 +156,10 @@ wide_stats = {"decode": 0, "padded_decode": 0}
 lora_stats = {"prefill": 0, "extend": 0, "decode": 0, "adapters": 0}
 # ... and the MODEL calls that ran as one whole-stack step (stack_decode); their layers are counted above as decode steps as well
 stack_stats = {"decode": 0, "padded_decode": 0}
+# ... and the causal-LM calls while the head switch is on: "head" took the step with the head, "fallback" ran the module norm and
+# nn.Linear (`head_route` said no), "form_fallback" the head-route calls whose requested weight form the shape does not take (they ran
+# on the element type)
+head_stats = {"head": 0, "fallback": 0, "form_fallback": 0}
 # whether the whole-stack step asks for its three RMSNorms in the tail of the product before them (u2tok_gemm_rows_norm): the same
 # bits either way; the default is the measurement's verdict (DESIGN f12)
 STACK_TAIL_NORM = False
@@ -408,6 +421,7 @@ class _StackState:
     lora: bool = False
     fp4: bool = False
     stack: bool = False
+    head: bool = False
     pad: tuple = _NO_PAD       # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
     pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
     scratch: dict = field(default_factory=dict)
@@ -1034,7 +1048,7 @@ def _decode_step(self, x, pe, cache, window, pr):
 # ---------------------------------------------------------------------------------------------- the whole-stack decode step
 _MISSING = object()
 _STACK_ARGS = ("input_ids", "attention_mask", "position_ids", "past_key_values", "inputs_embeds", "use_cache")
-_STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep")   # what the step keeps in a (B, device, stream) scratch entry
+_STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep", "stack_head")   # what the step keeps in a (B, device, stream) scratch entry
 _PE_STUBS = {}
 
 
@@ -1161,11 +1175,13 @@ def _stack_forward(self, *args, **kwargs):
         plan.clear()
 
 
-def _stack_step(base, plan, ids, x, cache, position_ids):
+def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
     """One decode step of the whole decoder stack in ONE library call (u2tok_decoder_decode_stack): per layer what `_decode_step`
     does around its two calls -- the weight form's copies, the adapters' operands and scratch, the layer descriptor's variant, room
     for one more row in the layer's cache buffers --, then the call, then every layer's commit.  The rotary tables come from ONE
-    call of the stack's `rotary_emb`, as the layers receive them from the stock forward."""
+    call of the stack's `rotary_emb`, as the layers receive them from the stock forward.
+    head (a `_HeadState`, the head route): the step with the head (u2tok_decoder_decode_stack_head) -- the stack's final norm and
+    lm_head ride in the call, and the result is (last hidden rows un-normed (B, 1, E), fp32 logits (B, 1, V))."""
     import ctypes as C
     from transformers.modeling_outputs import BaseModelOutputWithPast
     from . import _lib
@@ -1213,33 +1229,184 @@ def _stack_step(base, plan, ids, x, cache, position_ids):
             rows.append((lay, T1))
         for ls in lss:   # (a later layer's larger group may have replaced the shared adapter scratch: all of them read the last one)
             ls.desc.scratch, ls.desc.scratch_bytes = sc["lora"].data_ptr(), sc["lora"].numel()
-        if sc["stack_ws"] is None or sc["stack_T"] < Tmax:
-            Tcap = max(2048, 2 * Tmax)                    # (grows geometrically, as the per-layer step's workspace does)
+        if sc["stack_ws"] is None or sc["stack_T"] < Tmax or (head is not None and not sc.get("stack_head")):
+            Tcap = max(2048, 2 * Tmax, sc.get("stack_T", 0))   # (grows geometrically, as the per-layer step's workspace does)
             for i in range(n):
                 arr[i].T = Tcap
-            need = h.u2tok_decoder_decode_stack_workspace_bytes(arr, n)
+            # (the head's normed rows behind the stack step's workspace: a workspace once sized for the head serves both calls)
+            need = (h.u2tok_decoder_decode_stack_workspace_bytes(arr, n) if head is None else
+                    h.u2tok_decoder_decode_stack_head_workspace_bytes(arr, n, head.ref))
             for i, (_, T1) in enumerate(rows):
                 arr[i].T = T1 - arr[i].k_first
             if need == 0:
                 raise RuntimeError("u2tok_decoder_decode_stack_workspace_bytes refused the stack's descriptors")
             sc["stack_ws"] = torch.zeros(need, dtype=torch.uint8, device=x.device)   # (zeros: the tail norms' ticket, once)
             sc["stack_T"] = Tcap
+            sc["stack_head"] = head is not None
         ws = sc["stack_ws"]
         out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
         _, kv_start, _ = stack.pad
         left = kv_start is not None
         # (w_final_norm = NULL: the stack's final norm stays the module's own below, as on the per-layer routes -- the library's
         #  RMSNorm and the module's add a row's squares in another order, and one element in some ten thousand rounds the other way)
-        _lib.check(h.u2tok_decoder_decode_stack(arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
-                                                cos.stride(0), int(left or B > 16), kv_start.data_ptr() if left else None,
-                                                None, 0.0, int(STACK_TAIL_NORM),
-                                                out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack")
+        if head is None:
+            _lib.check(h.u2tok_decoder_decode_stack(arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
+                                                    cos.stride(0), int(left or B > 16), kv_start.data_ptr() if left else None,
+                                                    None, 0.0, int(STACK_TAIL_NORM),
+                                                    out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack")
+        else:
+            logits = torch.empty((B, 1, head.desc.V), dtype=torch.float32, device=x.device)
+            _lib.check(h.u2tok_decoder_decode_stack_head(
+                arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32), cos.stride(0),
+                int(left or B > 16), kv_start.data_ptr() if left else None, int(STACK_TAIL_NORM), out.data_ptr(), head.ref,
+                logits.data_ptr(), head.desc.V, ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack_head")
         for lay, T1 in rows:
             lay._commit(T1)
     for _, st, _, _, _, _ in plan:
         _count(st, "decode", B)
     stack_stats["padded_decode" if left else "decode"] += 1
+    if head is not None:
+        return out, logits
     return BaseModelOutputWithPast(last_hidden_state=base.norm(out), past_key_values=cache)
+
+
+# ---------------------------------------------------------------------------------------------- the head of the decode step
+HEAD_FORMS = {"elem": 0, "fp8": 1, "fp4": 2}   # config.u2_fused_head_form -> the form number of u2tok_decode_head_desc
+
+
+@dataclass(slots=True, eq=False)
+class _HeadState:
+    """What the head route keeps on the causal LM (`_u2_head`): the sources it was built from (`key`), the form lm_head runs in, its
+    quantised copy ((codes, scales), None in the element type) -- the head's own: with tied embeddings `embed_tokens` keeps reading
+    the 16-bit table --, the u2tok_decode_head_desc and the reference handed to the library."""
+    key: tuple
+    form: int
+    copy: tuple
+    desc: object
+    ref: object
+
+
+def head_form(requested: str, E: int) -> tuple:
+    """(form number, fell back) of `config.u2_fused_head_form` for a hidden size E: "elem" -> 0; "fp8" -> 1 where E % 64 == 0; "fp4"
+    -> 2 where E % 128 == 0 (what the few-rows product of that form asks of K); a shape the form does not take runs on the element
+    type (0, True).  Another word than the three: ValueError."""
+    if requested not in HEAD_FORMS:
+        raise ValueError(f"u2_fused_head_form: expected one of {sorted(HEAD_FORMS)}, got {requested!r}")
+    form = HEAD_FORMS[requested]
+    if form and E % _QFORM_OF[form].multiple:
+        return 0, True
+    return form, False
+
+
+def head_weights(model):
+    """The (codes, scales) pair lm_head's quantised head reads -- ops.quantize_rows_fp8's or ops.quantize_blocks_fp4's --, or None
+    (switch off, no head-route call yet, the element type)."""
+    hs = model.__dict__.get("_u2_head")
+    return None if hs is None else hs.copy
+
+
+def _head_state(model, form: int) -> _HeadState:
+    """The head's descriptor for `form`, built at the first head-route call and rebuilt when lm_head.weight's or the final norm
+    weight's data_ptr() or _version changed (an optimiser step, load_state_dict, weight.mul_) or another form is asked for --
+    as `_quant_state` has it for a layer."""
+    import ctypes as C
+    w, norm = model.lm_head.weight, _stack_of(model).norm
+    key = (w.data_ptr(), w._version, norm.weight.data_ptr(), norm.weight._version, float(norm.variance_epsilon), form)
+    hs = model.__dict__.get("_u2_head")
+    if hs is None or hs.key != key:
+        copy = _QFORM_OF[form].quantise(w.detach()) if form else None
+        desc = ops.head_desc(norm.weight.detach(), norm.variance_epsilon, *(copy if form else (w.detach(),)))
+        hs = model.__dict__["_u2_head"] = _HeadState(key, form, copy, desc, C.byref(desc))
+    return hs
+
+
+def head_route(model, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool, labels=None, plan: list = None) -> str:
+    """Whether a call of the causal LM `model` (its decoder stack patched) runs the whole-stack step WITH the head ("head": final
+    norm, lm_head and fp32 logits in the stack's library call) or today's path ("stock": the stack's forward -- the whole-stack step
+    where `stack_route` admits it -- then the module norm and nn.Linear).  B, S, dtype, is_cuda, kw, grad, plan: as `stack_route`
+    takes them (kw: the STACK's keyword arguments, resolved against the config); "logits_to_keep" and "return_dict" of the model call
+    ride in kw as well.  "head" needs ALL of:
+      * the switch on, no `labels`, one position per sequence, every position's logits asked for (`logits_to_keep` 0, 1 or absent),
+        a ModelOutput asked for;
+      * lm_head exactly nn.Linear: no bias, no hooks, not adapter-wrapped; its weight in the call's element type (bf16 or fp16),
+        rows of unit stride a multiple of 8 elements apart, on the device of the stack's weights;
+      * the stack's `norm` of the class of the layers' input norm (the decoder's own RMSNorm), without hooks, its weight like
+        lm_head's; no hook on the stack but the route's own mask hook;
+      * shapes the norm and the product take: hidden size a multiple of 32 up to 8192, a vocabulary of at least 2, lm_head (V, E);
+      * `stack_route` answering "stack" for this call."""
+    base = _stack_of(model)
+    stack = base.__dict__.get("_u2_stack")
+    if stack is None or not stack.head or labels is not None or S != 1:
+        return "stock"
+    keep = kw.get("logits_to_keep", 0)
+    if not (keep is None or (isinstance(keep, int) and not isinstance(keep, bool) and keep in (0, 1))) or kw.get("return_dict", True) is False:
+        return "stock"
+    head, norm = getattr(model, "lm_head", None), getattr(base, "norm", None)
+    layers = base.layers[:base.config.num_hidden_layers]
+    if type(head) is not torch.nn.Linear or head.bias is not None or not _no_hooks(head) or norm is None or not len(layers):
+        return "stock"
+    in_norm = getattr(layers[0], "input_layernorm", None)
+    if in_norm is None or type(norm) is not type(in_norm) or not _no_hooks(norm) or not hasattr(norm, "variance_epsilon"):
+        return "stock"
+    hooks = base.__dict__
+    if hooks.get(_HOOKS_F) or hooks.get(_HOOKS_B) or hooks.get(_HOOKS_BP) or list((hooks.get(_HOOKS_FP) or {}).values()) != [_mask_hook]:
+        return "stock"
+    w, nw = head.weight, getattr(norm, "weight", None)
+    if nw is None or w.dtype != dtype or dtype not in INFER_DTYPES or nw.dtype != dtype or w.device != in_norm.weight.device \
+            or nw.device != w.device:
+        return "stock"
+    V, E = w.shape
+    if nw.shape != (E,) or not nw.is_contiguous() or E % 32 or E > 8192 or V < 2 or w.stride(1) != 1 or w.stride(0) < E or w.stride(0) % 8:
+        return "stock"
+    if w.data_ptr() % 16 or nw.data_ptr() % 16:   # (a view that starts inside a row)
+        return "stock"
+    skw = {k: v for k, v in kw.items() if k not in ("logits_to_keep", "return_dict")}
+    if stack_route(base, B, S, dtype, is_cuda, skw, grad, plan) != "stack":
+        return "stock"
+    if plan is not None and plan and _base(plan[0][2][0]).weight.shape[1] != E:
+        plan.clear()
+        return "stock"
+    return "head"
+
+
+def head_forward(model, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, labels, kwargs):
+    """What `_u2CausalLMMixin.forward` asks while the decoder stack is patched: the CausalLMOutputWithPast of the head route --
+    logits (B, 1, V) fp32 --, or None: the call goes on to the stock forward with its arguments as they came (counted in
+    `head_stats` while the switch is on)."""
+    base = _stack_of(model)
+    stack = base.__dict__.get("_u2_stack")
+    if stack is None or not stack.head:
+        return None
+    run = base.__dict__.get("_u2_stack_run")
+    x = inputs_embeds
+    t = x if x is not None else input_ids
+    ok = run is not None and (input_ids is None) != (x is None) and torch.is_tensor(t) and t.dim() == (3 if x is not None else 2)
+    if ok:
+        kw = dict(kwargs, input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,
+                  inputs_embeds=x, use_cache=use_cache)
+        cfg = base.config
+        for name in ("use_cache", "output_hidden_states", "output_attentions"):
+            if kw.get(name) is None:
+                kw[name] = getattr(cfg, name, False)
+        dtype = x.dtype if x is not None else base.embed_tokens.weight.dtype
+        # (the stack is not called as a module on this route: its mask pre-hook's verdict is asked for here)
+        if t.shape[1] == 1 and labels is None:
+            _mask_hook(base, (), {"attention_mask": attention_mask})
+        plan = run.plan
+        ok = head_route(model, t.shape[0], t.shape[1], dtype, t.is_cuda, kw, torch.is_grad_enabled(), labels, plan) == "head"
+    if not ok:
+        head_stats["fallback"] += 1
+        return None
+    from transformers.modeling_outputs import CausalLMOutputWithPast
+    try:
+        form, fell = head_form(str(getattr(model.config, "u2_fused_head_form", "elem")), model.lm_head.weight.shape[1])
+        hs = _head_state(model, form)
+        _, logits = _stack_step(base, plan, input_ids, x, kw["past_key_values"], kw.get("position_ids"), head=hs)
+    finally:
+        plan.clear()
+    head_stats["head"] += 1
+    head_stats["form_fallback"] += fell
+    return CausalLMOutputWithPast(logits=logits, past_key_values=kw["past_key_values"])
 
 
 def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor):
@@ -1314,7 +1481,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
-                         fp4_decode: bool = False, stack_decode: bool = False) -> int:
+                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
@@ -1322,7 +1489,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
                  fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
-                 fp4_decode=fp4_decode, stack_decode=stack_decode)
+                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
@@ -1359,11 +1526,14 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
         layer._u2_prefill = _LayerState(layer.forward, stack, layout)
         layer.forward = types.MethodType(_layer_forward, layer)
     (_stack_wrap if stack.stack else _stack_unwrap)(base)
+    if not stack.head:
+        model.__dict__.pop("_u2_head", None)   # (lm_head's copies and descriptor go with the switch)
     return len(todo)
 
 
 def disable_fused_prefill(model) -> None:
     base = _stack_of(model)
+    model.__dict__.pop("_u2_head", None)
     for layer in base.layers:
         st = layer.__dict__.pop("_u2_prefill", None)
         if st is not None:

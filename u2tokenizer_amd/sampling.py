@@ -19,14 +19,22 @@ import torch
 from transformers.generation.logits_process import (LogitsProcessor, LogitsProcessorList, TemperatureLogitsWarper, TopKLogitsWarper,
                                                     TopPLogitsWarper)
 
-stats = {"fused": 0, "stock": 0}   # calls of FusedSamplingWarper per branch (as prefill.stats counts the decoder's routes)
+stats = {"fused": 0, "stock": 0, "split": 0}   # calls of FusedSamplingWarper per branch (as prefill.stats counts the decoder's routes);
+#                                                  "split": the fused calls (counted there as well) that took the split-row form
+# `config.u2_fused_sampling_split` (default False; read only with `u2_fused_sampling`): calls of at most SPLIT_MAX_ROWS rows go to
+# ops.sample_warp_split -- a row over G = min(16, ceil(V / 8192)) workgroups, one launch per pass, the same bits.  Measured
+# (profiles/decode_head_ab.json; us per call at T 0.7, p 0.9, one workgroup | split): V = 151 936: 327 | 71 at 1 row,
+# 330 | 72 at 8 rows; V = 32 064: 79 | 60 at 1 row, 79 | 63 at 8.  The split form wins at every measured row count, so the crossover
+# lies above 8 rows, the largest count measured: that is the constant.
+SPLIT_MAX_ROWS = 8
 
 
 class FusedSamplingWarper(LogitsProcessor):
     """temperature -> top-k -> top-p as one processor.  `stock`: the warpers it replaces, in order; they are applied instead
     whenever the scores are not what the kernel takes (fp32, on the GPU, 2-D, at least two columns)."""
 
-    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_tokens_to_keep: int = 1, stock=()):
+    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_tokens_to_keep: int = 1, stock=(),
+                 split: bool = False):
         if not temperature > 0 or top_k < 0 or not 0 < top_p <= 1 or min_tokens_to_keep < 1:
             raise ValueError(f"FusedSamplingWarper: temperature {temperature}, top_k {top_k}, top_p {top_p}, "
                              f"min_tokens_to_keep {min_tokens_to_keep}")
@@ -35,6 +43,7 @@ class FusedSamplingWarper(LogitsProcessor):
         self.top_p = float(top_p)
         self.min_tokens_to_keep = int(min_tokens_to_keep)
         self.stock = list(stock)
+        self.split = bool(split)
 
     def __call__(self, input_ids: torch.LongTensor, scores: torch.FloatTensor) -> torch.FloatTensor:
         if scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.shape[1] >= 2 and scores.shape[0] >= 1:
@@ -42,6 +51,9 @@ class FusedSamplingWarper(LogitsProcessor):
             stats["fused"] += 1
             if scores.stride(1) != 1:
                 scores = scores.contiguous()
+            if self.split and scores.shape[0] <= SPLIT_MAX_ROWS:
+                stats["split"] += 1
+                return ops.sample_warp_split(scores, self.temperature, self.top_k, self.top_p, self.min_tokens_to_keep)
             return ops.sample_warp(scores, self.temperature, self.top_k, self.top_p, self.min_tokens_to_keep)
         stats["stock"] += 1
         for p in self.stock:
@@ -56,7 +68,7 @@ class FusedSamplingWarper(LogitsProcessor):
 _KINDS = (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper)
 
 
-def fuse_warpers(processors) -> LogitsProcessorList:
+def fuse_warpers(processors, split: bool = False) -> LogitsProcessorList:
     """The processor list with its run [TemperatureLogitsWarper]? [TopKLogitsWarper]? [TopPLogitsWarper]? replaced by one
     FusedSamplingWarper; every other object stays, by identity and in place.  The run is taken only when it is the whole story: the
     list's temperature / top-k / top-p warpers (subclasses counted) are adjacent, in that order, at most one of each, each EXACTLY the
@@ -81,5 +93,6 @@ def fuse_warpers(processors) -> LogitsProcessorList:
         return same
     temp = run[0].temperature if type(run[0]) is TemperatureLogitsWarper else 1.0
     # TopKLogitsWarper stores max(top_k, min_tokens_to_keep) as its top_k; the kernel takes the same maximum again
-    fused = FusedSamplingWarper(temp, topk.top_k if topk is not None else 0, topp.top_p if topp is not None else 1.0, min_keep, stock=run)
+    fused = FusedSamplingWarper(temp, topk.top_k if topk is not None else 0, topp.top_p if topp is not None else 1.0, min_keep, stock=run,
+                                split=split)
     return LogitsProcessorList(procs[:at[0]] + [fused] + procs[at[-1] + 1:])
