@@ -422,6 +422,18 @@ int u2tok_decoder_decode_pre(const u2tok_decode_config* cfg, const u2tok_decode_
 int u2tok_decoder_decode_post(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* qkv,
                               const void* K, const void* V, int32_t T, int64_t kv_stride, int32_t batched, const int32_t* kv_start,
                               void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* post on an FP8 (e4m3) KV cache (u2tok_kv_quantize_rows below: the format): K / V are replaced by the dense code buffers k_codes /
+ * v_codes (B, Hkv, capacity, D) bytes and their scales k_scales / v_scales (B, Hkv, capacity) fp32.  k_new / v_new: the step's
+ * 16-bit rows, dense (B, Hkv, 1, D) -- what u2tok_decoder_decode_pre wrote with kv_stride = 0, s_off = 0.  The call quantises them
+ * into position s_off of the buffers, then attends over positions k_first .. s_off (a window: k_first > 0) with
+ * u2tok_decode_attention_kv8 -- always the batched form: Hq / Hkv <= 16, kv_start (NULL or device int32[B]) counted from k_first
+ * --; everything after the attention is u2tok_decoder_decode_post's, all weight forms and adapter groups.  Workspace:
+ * u2tok_decoder_decode_workspace_bytes(cfg, s_off - k_first + 1).  Everything either launcher or post refuses, 0 <= k_first <= s_off
+ * < capacity violated: U2TOK_ERR_ARG / U2TOK_ERR_WORKSPACE before anything is launched or written. */
+int u2tok_decoder_decode_post_kv8(const u2tok_decode_config* cfg, const u2tok_decode_layer* layer, const void* x, const void* qkv,
+                                  const void* k_new, const void* v_new, void* k_codes, void* v_codes, float* k_scales, float* v_scales,
+                                  int32_t capacity, int32_t k_first, int32_t s_off, const int32_t* kv_start, void* out, void* workspace,
+                                  size_t workspace_bytes, u2tok_stream_t stream);
 /* ---- one decode step of the WHOLE decoder stack in one call: for each of the n_layers layers exactly the launches of
  * u2tok_decoder_decode_pre followed by u2tok_decoder_decode_post, in their order, on the caller's stream (no graph, nothing
  * captured), so every value has the bits the per-layer calls give it.  Layer l reads the hidden state layer l - 1 wrote (layer 0: x,
@@ -556,6 +568,28 @@ size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv
 int u2tok_decode_attention(const void* q, const void* K, const void* V, void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T,
                            int32_t D, int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int32_t* kv_start,
                            void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- the FP8 (e4m3) KV cache.  One row = the D values of one (sequence, kv head, position), K and V each: scale = amax / 448 in
+ * fp32 (an all-zero row: 1.0), code = e4m3fn(clamp(x / scale, +-448)), round to nearest even, IEEE division; the NaN codes never
+ * occur; value = code x scale exactly.  Finite inputs only (a non-finite row does not fault; its codes are unspecified).
+ * u2tok_kv_quantize_rows: k / v (B, Hkv, n, D) rows in the element type -- unit stride inside a row, *_bs / *_hs / *_rs elements
+ * between sequences / heads / positions, multiples of 8, 16-byte aligned -- into positions s_off .. s_off + n - 1 of the dense
+ * buffers k_codes / v_codes (B, Hkv, capacity, D) bytes (16-byte aligned) and k_scales / v_scales (B, Hkv, capacity) fp32, K and
+ * V in one launch; bit-equal to ops.quantize_kv_fp8.  D in {64, 96, 128}.  A null pointer, a misaligned one, another D,
+ * s_off + n > capacity: U2TOK_ERR_ARG, nothing launched, nothing written.
+ * u2tok_decode_attention_kv8: u2tok_decode_attention over codes -- the same splits, fp32 partials merged in ascending order, no
+ * atomics, bit-repeatable, zeros for a sequence without a visible key.  kv_stride BYTES between (batch, kv head) code entries (0:
+ * dense, T * D; a multiple of 16), scale_stride floats between their scale entries (0: T).  Codes are widened to the element type
+ * in registers (exact), the MFMAs stay in the element type: s_j = k_scales[j] * sum_d q_d code(K_jd), p_j = exp2(s_j c - m), the
+ * row sum takes p_j, the P operand is rnd(p_j * v_scales[j]) (the IEEE-half build: times 2^8, undone where the sum is divided).
+ * workspace: u2tok_decode_attention_kv8_workspace_bytes (= u2tok_decode_attention_workspace_bytes). */
+int u2tok_kv_quantize_rows(const void* k, const void* v, int32_t B, int32_t Hkv, int32_t n, int32_t D, int64_t k_bs, int64_t k_hs,
+                           int64_t k_rs, int64_t v_bs, int64_t v_hs, int64_t v_rs, void* k_codes, void* v_codes, float* k_scales,
+                           float* v_scales, int32_t capacity, int32_t s_off, u2tok_stream_t stream);
+size_t u2tok_decode_attention_kv8_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D);
+int u2tok_decode_attention_kv8(const void* q, const void* k_codes, const void* v_codes, const float* k_scales, const float* v_scales,
+                               void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D, int64_t ldq, int64_t kv_stride,
+                               int64_t scale_stride, int64_t ldo, float scale, const int32_t* kv_start, void* workspace,
+                               size_t workspace_bytes, u2tok_stream_t stream);
 
 /* in-place rotate-half RoPE (rope.py:6-13,77-80): rows indexed (outer, s, inner), position = s; inverse != 0 rotates
  * the other way (the backward of the rotation) */

@@ -367,6 +367,21 @@ int u2tok_decoder_decode_post(const u2tok_decode_config* c, const u2tok_decode_l
   return decoder_decode_post(cfg, d, BF(x), BF(qkv), BF(K), BF(V), T, kv_stride, batched != 0, kv_start, BFW(out), workspace,
                              workspace_bytes, ST(stream));
 }
+int u2tok_decoder_decode_post_kv8(const u2tok_decode_config* c, const u2tok_decode_layer* l, const void* x, const void* qkv,
+                                  const void* k_new, const void* v_new, void* k_codes, void* v_codes, float* k_scales, float* v_scales,
+                                  int32_t capacity, int32_t k_first, int32_t s_off, const int32_t* kv_start, void* out, void* workspace,
+                                  size_t workspace_bytes, u2tok_stream_t stream) {
+  DecodeCfg cfg;
+  DecodeLayer d;
+  const int e = dec_args(c, l, cfg, d);
+  if (e != U2_OK) return e;
+  DecodeKv8 kv;
+  kv.k_new = BF(k_new); kv.v_new = BF(v_new);
+  kv.Kc = reinterpret_cast<uint8_t*>(k_codes); kv.Vc = reinterpret_cast<uint8_t*>(v_codes);
+  kv.Ks = k_scales; kv.Vs = v_scales;
+  kv.capacity = capacity; kv.k_first = k_first; kv.s_off = s_off;
+  return decoder_decode_post_kv8(cfg, d, BF(x), BF(qkv), kv, kv_start, BFW(out), workspace, workspace_bytes, ST(stream));
+}
 // ---- the whole-stack step (decoder.hip): the layers' descriptors decoded as the two per-layer entries decode theirs, nothing kept
 static int stack_args(const u2tok_decode_stack_layer* L, int32_t n, std::vector<DecodeStackLayer>& v) {
   if (!L || n <= 0) return U2_ERR_ARG;
@@ -472,6 +487,23 @@ int u2tok_gemm_rows_w4(const void* A, const void* W4, const uint8_t* S, void* C,
 int u2tok_gemm_rows(const void* A, const void* W, void* C, const void* bias, const void* R, int32_t M, int32_t N, int32_t K, int64_t lda,
                     int64_t ldw, int64_t ldc, int64_t ldr, int32_t flags, u2tok_stream_t stream) {
   return rows(WForm::ELEM, A, W, nullptr, 0, C, bias, R, M, N, K, lda, ldw, ldc, ldr, flags, stream);
+}
+int u2tok_kv_quantize_rows(const void* k, const void* v, int32_t B, int32_t Hkv, int32_t n, int32_t D, int64_t k_bs, int64_t k_hs,
+                           int64_t k_rs, int64_t v_bs, int64_t v_hs, int64_t v_rs, void* k_codes, void* v_codes, float* k_scales,
+                           float* v_scales, int32_t capacity, int32_t s_off, u2tok_stream_t stream) {
+  return kv_quantize_rows(BF(k), BF(v), B, Hkv, n, D, k_bs, k_hs, k_rs, v_bs, v_hs, v_rs, reinterpret_cast<uint8_t*>(k_codes),
+                          reinterpret_cast<uint8_t*>(v_codes), k_scales, v_scales, capacity, s_off, false, ST(stream));
+}
+size_t u2tok_decode_attention_kv8_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
+  return decode_attention_kv8_workspace_bytes(B, Hq, Hkv, T, D);
+}
+int u2tok_decode_attention_kv8(const void* q, const void* k_codes, const void* v_codes, const float* k_scales, const float* v_scales,
+                               void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D, int64_t ldq, int64_t kv_stride,
+                               int64_t scale_stride, int64_t ldo, float scale, const int32_t* kv_start, void* workspace,
+                               size_t workspace_bytes, u2tok_stream_t stream) {
+  return decode_attention_kv8(BF(q), reinterpret_cast<const uint8_t*>(k_codes), reinterpret_cast<const uint8_t*>(v_codes), k_scales,
+                              v_scales, BFW(out), B, Hq, Hkv, T, D, ldq, kv_stride, scale_stride, ldo, scale, kv_start, workspace,
+                              workspace_bytes, false, ST(stream));
 }
 size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
   return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);

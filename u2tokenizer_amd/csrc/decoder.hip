@@ -317,9 +317,9 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
 // launch: the group adds to the product's rows after it.
 static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
                     int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st, int mode,
-                    uint32_t* ticket, const RowsNorm* after, bool* after_done) {
+                    uint32_t* ticket, const RowsNorm* after, bool* after_done, const DecodeKv8* q8 = nullptr) {
   if (mode & DEC_CHECK) {
-    if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || !K || !V || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
+    if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || (!q8 && (!K || !V)) || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
         !ws)
       return U2_ERR_ARG;
     if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
@@ -338,11 +338,26 @@ static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, c
   const size_t aws_bytes = ws_bytes - used;
   const float scale = c.scale;
   if (kv_stride == 0) kv_stride = (int64_t)T * c.D;
+  // an e4m3 cache (decoder_decode_post_kv8): the step's rows into position s_off, the attention over positions k_first .. s_off
+  auto kv8_quantise = [&](bool check_only) {
+    return kv_quantize_rows(q8->k_new, q8->v_new, c.B, c.Hkv, 1, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, q8->Kc,
+                            q8->Vc, q8->Ks, q8->Vs, q8->capacity, q8->s_off, check_only, st);
+  };
+  auto kv8_attention = [&](bool check_only) {
+    return decode_attention_kv8(qkv, q8->Kc + (int64_t)q8->k_first * c.D, q8->Vc + (int64_t)q8->k_first * c.D, q8->Ks + q8->k_first,
+                                q8->Vs + q8->k_first, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, (int64_t)q8->capacity * c.D, q8->capacity, qd, scale,
+                                kv_start, aws, aws_bytes, check_only, st);
+  };
   const DecodeLora* lr = l.lora;
   const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
   const bool gu_pair = !gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15);  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
   if (mode & DEC_CHECK) {
-    if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
+    if (q8) {  // (both launchers' refusals, before either launch)
+      if (!batched || q8->k_first < 0 || q8->s_off < q8->k_first || T != q8->s_off - q8->k_first + 1) return U2_ERR_ARG;
+      int e = kv8_quantise(true);
+      if (e == U2_OK) e = kv8_attention(true);
+      if (e != U2_OK) return e;
+    } else if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
     if (lr) {  // (the adapter groups: every refusal before the attention is launched)
       int e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, true, st);
       if (e == U2_OK) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, true, st);
@@ -351,6 +366,7 @@ static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, c
     }
     if (!(mode & DEC_RUN)) {
       // (the attention's own: 16-byte aligned q / K / V and partials, 32-bit offsets inside a (batch, kv head) entry)
+      if (q8) return U2_ERR_ARG;  // (the whole-stack walk does not take an e4m3 cache)
       if ((((uintptr_t)qkv | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ws) & 15) || (int64_t)T * c.D * 2 >= (1ll << 31) || !(scale > 0.f)) return U2_ERR_ARG;
       int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st, true);
       if (e == U2_OK) e = rmsnorm_check(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E);
@@ -361,11 +377,15 @@ static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, c
       return e;
     }
   }
-  if (batched) {
+  if (q8) {
+    int e = kv8_quantise(false);
+    if (e == U2_OK) e = kv8_attention(false);
+    if (e != U2_OK) return e;
+  } else if (batched) {
     const int e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, scale, kv_start, aws, aws_bytes, st);
     if (e != U2_OK) return e;
   }
-  for (int b = 0; b < c.B && !batched; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
+  for (int b = 0; b < c.B && !batched && !q8; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
     AttnCall a;
     a.q = qkv + (size_t)b * nq; a.k = K + (size_t)b * c.Hkv * kv_stride; a.v = V + (size_t)b * c.Hkv * kv_stride;
     a.out = ctx + (size_t)b * qd;
@@ -406,6 +426,14 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
                         int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
                         hipStream_t st) {
   return dec_post(c, l, x, qkv, K, V, T, kv_stride, batched, kv_start, out, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, nullptr, nullptr, nullptr);
+}
+
+int decoder_decode_post_kv8(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const DecodeKv8& kv,
+                            const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int64_t T = (int64_t)kv.s_off - kv.k_first + 1;
+  if (T <= 0 || T > 0x7fffffff) return U2_ERR_ARG;
+  return dec_post(c, l, x, qkv, nullptr, nullptr, (int)T, 0, true, kv_start, out, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, nullptr, nullptr,
+                  nullptr, &kv);
 }
 
 // ------------------------------------------------------------------------------------------------ one decode step of the stack

@@ -456,5 +456,28 @@ size_t decode_attention_workspace_bytes(int B, int Hq, int Hkv, int T, int D);
 int decode_attention(const bf16_t* q, const bf16_t* K, const bf16_t* V, bf16_t* out, int B, int Hq, int Hkv, int T, int D,
                      int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int* kv_start, void* ws, size_t ws_bytes,
                      hipStream_t stream);
+// ---- the FP8 (e4m3) KV cache (decode_attn.hip): codes (B, Hkv, capacity, D) bytes and ONE fp32 scale per cache row, (B, Hkv,
+// capacity); value = code x scale.  kv_quantize_rows: the 16-bit rows k / v (B, Hkv, n, D; *_bs / *_hs / *_rs elements between
+// sequences / heads / positions, multiples of 8) as codes and scales at positions s_off .. s_off + n - 1 of dense buffers, one
+// launch for both.  decode_attention_kv8: decode_attention over codes -- kv_stride BYTES and sc_stride floats between (batch, kv
+// head) entries (0: dense, T D and T).  check_only: every refusal of the call, nothing launched.
+int kv_quantize_rows(const bf16_t* k, const bf16_t* v, int B, int Hkv, int n, int D, int64_t k_bs, int64_t k_hs, int64_t k_rs, int64_t v_bs,
+                     int64_t v_hs, int64_t v_rs, uint8_t* kc, uint8_t* vc, float* ksc, float* vsc, int capacity, int s_off, bool check_only,
+                     hipStream_t stream);
+size_t decode_attention_kv8_workspace_bytes(int B, int Hq, int Hkv, int T, int D);
+int decode_attention_kv8(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, const float* Ks, const float* Vs, bf16_t* out, int B, int Hq,
+                         int Hkv, int T, int D, int64_t ldq, int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale,
+                         const int* kv_start, void* ws, size_t ws_bytes, bool check_only, hipStream_t stream);
+// The second half of a layer's decode step on such a cache: the step's new 16-bit rows k_new / v_new (B, Hkv, 1, D; dense: what
+// decoder_decode_pre wrote) are quantised into position s_off of the dense buffers (capacity positions per (batch, kv head)
+// entry), the attention -- always the batched kernel -- reads positions k_first .. s_off, kv_start counted from k_first.
+struct DecodeKv8 {
+  const bf16_t *k_new, *v_new;
+  uint8_t *Kc, *Vc;
+  float *Ks, *Vs;
+  int capacity, k_first, s_off;
+};
+int decoder_decode_post_kv8(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const DecodeKv8& kv,
+                            const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace u2

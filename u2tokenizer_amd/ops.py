@@ -1388,6 +1388,77 @@ def decode_attention(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, heads: i
     return out
 
 
+# ---------------------------------------------------------------------------------------------- FP8 (e4m3) KV cache
+def quantize_kv_fp8(x: torch.Tensor):
+    """The KV cache's e4m3 form, the reference (plain torch, any device): x (..., D) keys or values in bf16 / fp16 / fp32 ->
+    (codes (..., D) torch.float8_e4m3fn, scales (...) fp32).  One row = the last dimension (the D values of one (sequence, kv head,
+    position)): scale = amax / 448 in fp32 (1.0 for an all-zero row), codes = e4m3(clamp(x_fp32 / scale, +-448)), round to nearest
+    even -- `quantize_rows_fp8`'s rule per cache row; the NaN codes never occur.  Finite inputs only: a non-finite row gives
+    unspecified codes (nothing is checked: no synchronisation)."""
+    xf = x.detach().float()
+    amax = xf.abs().amax(-1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    codes = (xf / scale[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return codes, scale
+
+
+def dequantize_kv_fp8(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """code x scale -- exact in fp32 and fp64 (a 4-bit significand times a 24-bit one), rounded once for a 16-bit `dtype`.  codes:
+    torch.float8_e4m3fn or the same bytes as uint8."""
+    if codes.dtype == torch.uint8:
+        codes = codes.view(torch.float8_e4m3fn)
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    return (codes.to(wide) * scales.to(wide)[..., None]).to(dtype)
+
+
+def _kv8_buffers(who: str, kc, vc, ks, vs):
+    B, Hkv, cap, D = kc.shape
+    for t, dt, shape in ((kc, torch.uint8, (B, Hkv, cap, D)), (vc, torch.uint8, (B, Hkv, cap, D)), (ks, torch.float32, (B, Hkv, cap)),
+                         (vs, torch.float32, (B, Hkv, cap))):
+        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"{who}: code buffers (B, Hkv, capacity, D) uint8 and scale buffers (B, Hkv, capacity) fp32, dense, on "
+                               f"the GPU; got {tuple(t.shape)} {t.dtype}")
+    return B, Hkv, cap, D
+
+
+@_guarded
+def kv_quantize_rows(k: torch.Tensor, v: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                     s_off: int) -> None:
+    """The quantising append (u2tok_kv_quantize_rows): k / v (B, Hkv, n, D) in the element type, unit stride inside a row, any
+    other strides that are multiples of 8 -> codes and scales at positions s_off .. s_off + n - 1 of the dense buffers, with the
+    bits of `quantize_kv_fp8`."""
+    h = _lib.load_library()
+    _need(k, ELEM, "k"), _need(v, ELEM, "v")
+    B, Hkv, cap, D = _kv8_buffers("kv_quantize_rows", kc, vc, ks, vs)
+    if k.dim() != 4 or k.shape != v.shape or tuple(k.shape[:2]) != (B, Hkv) or k.shape[3] != D or k.stride(3) != 1 or v.stride(3) != 1:
+        raise RuntimeError(f"kv_quantize_rows: k / v {tuple(k.shape)} / {tuple(v.shape)} against buffers {tuple(kc.shape)}")
+    _lib.check(h.u2tok_kv_quantize_rows(_ptr(k), _ptr(v), B, Hkv, k.shape[2], D, k.stride(0), k.stride(1), k.stride(2), v.stride(0),
+                                        v.stride(1), v.stride(2), _ptr(kc), _ptr(vc), _ptr(ks), _ptr(vs), cap, int(s_off), _stream()),
+               "u2tok_kv_quantize_rows")
+
+
+@_guarded
+def decode_attention_kv8(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor, T: int, heads: int,
+                         scale: float, kv_start: Optional[torch.Tensor] = None, k_first: int = 0) -> torch.Tensor:
+    """`decode_attention` over an e4m3 cache (u2tok_decode_attention_kv8): q (B, heads * d) rows in the element type; kc / vc
+    (B, kv_heads, capacity, d) uint8 codes and ks / vs (B, kv_heads, capacity) fp32 scales, dense buffers of which positions k_first
+    .. k_first + T - 1 are attended over (kv_start int32 (B,) counts from k_first).  -> (B, heads * d)."""
+    h = _lib.load_library()
+    _need(q, ELEM, "q")
+    B, Hkv, cap, d = _kv8_buffers("decode_attention_kv8", kc, vc, ks, vs)
+    if q.dim() != 2 or q.stride(1) != 1 or q.shape != (B, heads * d) or heads % Hkv or k_first < 0 or T < 1 or k_first + T > cap:
+        raise RuntimeError(f"decode_attention_kv8: q {tuple(q.shape)}, buffers {tuple(kc.shape)}, heads {heads}, T {T}, k_first {k_first}")
+    kv_start = _kv_len_arg(kv_start, B, q.device)
+    out = torch.empty((B, heads * d), dtype=elem_dtype(), device=q.device)
+    nbytes = h.u2tok_decode_attention_kv8_workspace_bytes(B, heads, Hkv, T, d)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+    _lib.check(h.u2tok_decode_attention_kv8(_ptr(q), _ptr(kc) + k_first * d, _ptr(vc) + k_first * d, _ptr(ks) + 4 * k_first,
+                                            _ptr(vs) + 4 * k_first, _ptr(out), B, heads, Hkv, T, d, q.stride(0), cap * d, cap,
+                                            heads * d, float(scale), _ptr(kv_start), _ptr(ws) if nbytes else None, nbytes, _stream()),
+               "u2tok_decode_attention_kv8")
+    return out
+
+
 @_guarded
 def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, heads: int, kv_heads: int, scale: float,
                       kv_len: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,

@@ -38,6 +38,10 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     u2tok_decoder_decode_stack_head -- the stack's final RMSNorm and lm_head, in `config.u2_fused_head_form`, fp32 logits) from
     `language_model._u2CausalLMMixin.forward` through `head_forward`; the head's descriptor and quantised copy live on the model
     (`_HeadState`), not in the stack's state.
+  * kv8: the cache a fused prefill starts is a `Kv8Layer` (e4m3 codes and a scale per cached row) where the append-in-place layer
+    would go; `route` takes it for the decode step alone (`_decode_step`: u2tok_decoder_decode_pre onto the scratch rows, then
+    u2tok_decoder_decode_post_kv8, which quantises them into the layer's buffers and attends over the codes); every other route
+    refuses it and reads the same cache dequantised through the layer's `update`.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -137,6 +141,14 @@ SWITCHES = (
            "fp32 logits -- in the same library call (u2tok_decoder_decode_stack_head); `head_route` lists what it asks, every other "
            "call runs the module norm and nn.Linear as before; `config.u2_fused_head_form` (\"elem\", \"fp8\", \"fp4\") picks lm_head's "
            "weight form, the quantised ones unmeasured in accuracy on trained weights; `head_stats`"),
+    Switch("kv8", "kv8", "u2_fused_kv_fp8", False, (), (), (),
+           "the KV cache a fused prefill starts is FP8: a `Kv8Layer` (e4m3 codes, one fp32 scale per cached row of K and of V: half "
+           "the cache's bytes in HBM and per decode step) where the append-in-place layer would go; the prefill commits through the "
+           "layer's `update`, the decode step quantises its new rows and attends over the codes (u2tok_decoder_decode_post_kv8: "
+           "always the batched decode attention, so at most 16 query heads per kv head); the continued prefill refuses the layer "
+           "(stock layers on the dequantised cache) and the whole-stack and head calls are out of scope on such a cache "
+           "(`stack_route` answers \"layers\", `head_route` \"stock\"); exact on the quantised cache, the quantiser's cost in "
+           "accuracy is unmeasured on trained weights; `kv8_stats`"),
 )
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
@@ -160,6 +172,8 @@ stack_stats = {"decode": 0, "padded_decode": 0}
 # nn.Linear (`head_route` said no), "form_fallback" the head-route calls whose requested weight form the shape does not take (they ran
 # on the element type)
 head_stats = {"head": 0, "fallback": 0, "form_fallback": 0}
+# ... and the decode steps (counted in `stats` as well) that ran on an e4m3 KV cache (kv8), per layer call
+kv8_stats = {"decode": 0, "padded_decode": 0}
 # whether the whole-stack step asks for its three RMSNorms in the tail of the product before them (u2tok_gemm_rows_norm): the same
 # bits either way; the default is the measurement's verdict (DESIGN f12)
 STACK_TAIL_NORM = False
@@ -422,7 +436,8 @@ class _StackState:
     fp4: bool = False
     stack: bool = False
     head: bool = False
-    pad: tuple = _NO_PAD       # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
+    kv8: bool = False
+    pad: tuple = _NO_PAD      # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
     pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
     scratch: dict = field(default_factory=dict)
 
@@ -544,9 +559,12 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             return "stock", None
     if shape[1] == 1:   # one new position per sequence, batch <= 16 (wide_decode=True: <= 64), against a plain DynamicCache
         wide = shape[0] > 16   # (17 .. 64 sequences: the few-rows product on up to four blocks of 16 rows, always the batched attention)
-        ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode \
-            and _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None) is not None
-        if (ranged or wide) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
+        lay = _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None, kv8=stack.kv8)
+        ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode and lay is not None
+        q8 = type(lay) is Kv8Layer   # (an e4m3 cache of this batch on the GPU: its step is always the batched decode attention)
+        if q8 and (lay._kc is None or lay._kc.shape[0] != shape[0] or not lay._kc.is_cuda):
+            ok = False
+        if (ranged or wide or q8) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
             ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
     # an empty cache and no more positions than the window: the plain causal prefill
@@ -602,15 +620,16 @@ class _KVWrite:
     `commit` makes them the layer's.  Without it: dense tensors through the cache's own `update` -- in `views` when the step
     attends over the cache, else in `commit`.
     fresh = (H_kv, d, like): the call is the first into this layer; an empty DynamicLayer of a plain DynamicCache is replaced by an
-    append-in-place one with room for the call and as many positions again (`_prefill_append_layer`)."""
+    append-in-place one with room for the call and as many positions again (`_prefill_append_layer`) -- kv8: by a `Kv8Layer`,
+    which is written through its own `update` (`lay` stays None)."""
     __slots__ = ("cache", "idx", "n", "window", "lay", "T0")
 
-    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None):
+    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None, kv8: bool = False):
         self.cache, self.idx, self.n, self.window, self.T0 = cache, idx, n, window, 0
         lay = None
         if cache is not None:
-            if fresh is not None:
-                lay = _prefill_append_layer(cache, idx, B, fresh[0], n, fresh[1], fresh[2])
+            if fresh is not None:   # (kv8: a `Kv8Layer` goes there and None comes back -- the step commits through its `update`)
+                lay = _prefill_append_layer(cache, idx, B, fresh[0], n, fresh[1], fresh[2], kv8)
             else:
                 lay = cache.layers[idx]
                 if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:   # (a reordered or re-batched layer: `_room` re-homes it)
@@ -676,7 +695,7 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
         q3 = qkv.view(B, S, -1)
         _, kv_start, kv_len = st.stack.pad
         filled = extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0
-        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x))
+        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x), kv8=st.stack.kv8)
         lay = kv.lay
         r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
                              qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
@@ -754,6 +773,167 @@ def _append_layer_class():
     return _APPEND_LAYER
 
 
+_CACHE_LAYER = getattr(cache_utils, "CacheLayerMixin", None)
+
+
+class Kv8Layer(_CACHE_LAYER if _CACHE_LAYER is not None else object):
+    """A cache layer (CacheLayerMixin's protocol) that keeps K and V as FP8: e4m3 codes (B, H_kv, capacity, d) uint8 and one fp32
+    scale per cached row (B, H_kv, capacity), K and V each (`ops.quantize_kv_fp8`: the format; value = code x scale), in buffers with
+    room to grow -- they double, the old codes and scales are copied bit for bit.  What the cache HOLDS defines the semantics,
+    whatever route reads it:
+      * `update()` on an empty layer quantises its inputs and returns them as they came (HF's own quantized-cache rule: the
+        prefill attends over what it computed); on a filled layer it quantises the new rows and returns the whole cache dequantised
+        in the callers' type -- so the stock layers, and every route that refuses the layer, attend over the same quantised cache
+        the fused decode step reads as codes (`_decode_step`: u2tok_decoder_decode_post_kv8);
+      * length, mask sizes, crop, batch selection / repetition, beam reordering, reset, offload / prefetch work on codes and scales
+        directly: nothing is ever dequantised and requantised (rnd(code x scale) does not requantise to the same codes);
+      * `.keys` / `.values` are read-only, dequantised on demand for foreign readers; assigning them raises.
+    Quantisation runs the kernel (u2tok_kv_quantize_rows) for 16-bit rows on the GPU that it takes, the torch reference elsewhere:
+    the same bits; the layer works on the CPU."""
+    is_sliding = False
+    is_compileable = False
+
+    def __init__(self, **kwargs):
+        self._kc = self._vc = self._ks = self._vs = None
+        self._T = 0
+        self.dtype = self.device = None
+        self.is_initialized = False
+
+    def _dequant(self, codes, scales):
+        if not self.is_initialized or codes is None:
+            return None
+        T = self._T
+        return ops.dequantize_kv_fp8(codes[:, :, :T], scales[:, :, :T], self.dtype)
+
+    @property
+    def keys(self):
+        return self._dequant(self._kc, self._ks)
+
+    @keys.setter
+    def keys(self, value):
+        raise AttributeError("Kv8Layer.keys is read-only: the layer holds e4m3 codes and scales")
+
+    @property
+    def values(self):
+        return self._dequant(self._vc, self._vs)
+
+    @values.setter
+    def values(self, value):
+        raise AttributeError("Kv8Layer.values is read-only: the layer holds e4m3 codes and scales")
+
+    def lazy_initialization(self, key_states, value_states) -> None:
+        self.dtype, self.device = key_states.dtype, key_states.device
+        self.is_initialized = True
+
+    def codes(self):
+        """(K codes, V codes, K scales, V scales) of the cached positions: views of the buffers (None while empty)"""
+        if self._kc is None:
+            return None
+        T = self._T
+        return self._kc[:, :, :T], self._vc[:, :, :T], self._ks[:, :, :T], self._vs[:, :, :T]
+
+    def _set(self, kc, vc, ks, vs, T: int) -> None:
+        self._kc, self._vc, self._ks, self._vs, self._T = kc, vc, ks, vs, T
+
+    def _room(self, n: int, B: int, H: int, d: int, device) -> int:
+        """Make sure `n` more positions fit behind the current ones; returns the current length."""
+        T0, kc = self._T, self._kc
+        if kc is None or T0 + n > kc.shape[2] or kc.shape[:2] != (B, H) or kc.shape[3] != d or kc.device != device:
+            if kc is not None and T0 and (kc.shape[:2] != (B, H) or kc.shape[3] != d):
+                raise RuntimeError(f"Kv8Layer: rows of shape {(B, H, n, d)} against a cache of {tuple(kc.shape)}")
+            cap = max(256, 2 * (T0 + n))
+            new = (torch.empty((B, H, cap, d), dtype=torch.uint8, device=device), torch.empty((B, H, cap, d), dtype=torch.uint8, device=device),
+                   torch.empty((B, H, cap), dtype=torch.float32, device=device), torch.empty((B, H, cap), dtype=torch.float32, device=device))
+            if T0:
+                for dst, src in zip(new, (self._kc, self._vc, self._ks, self._vs)):
+                    dst[:, :, :T0].copy_(src[:, :, :T0])
+            self._kc, self._vc, self._ks, self._vs = new
+        return T0
+
+    def _quantise(self, k, v, T0: int) -> None:
+        n, d = k.shape[2], k.shape[3]
+        if k.is_cuda and k.dtype in INFER_DTYPES and v.dtype == k.dtype and d in INFER_HEAD_DIMS and k.stride(3) == 1 and v.stride(3) == 1 \
+                and not any(s % 8 for t in (k, v) for s in t.stride()[:3]) and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0:
+            ops.kv_quantize_rows(k, v, self._kc, self._vc, self._ks, self._vs, T0)
+            return
+        for x, codes, scales in ((k, self._kc, self._ks), (v, self._vc, self._vs)):
+            c, s = ops.quantize_kv_fp8(x)
+            codes[:, :, T0:T0 + n].copy_(c.view(torch.uint8))
+            scales[:, :, T0:T0 + n].copy_(s)
+
+    def update(self, key_states, value_states, *args, **kwargs):
+        if not self.is_initialized:
+            self.lazy_initialization(key_states, value_states)
+        B, H, n, d = key_states.shape
+        T0 = self._room(n, B, H, d, key_states.device)
+        self._quantise(key_states, value_states, T0)
+        self._T = T0 + n
+        if T0 == 0:
+            return key_states, value_states
+        dt = key_states.dtype
+        return (ops.dequantize_kv_fp8(self._kc[:, :, :self._T], self._ks[:, :, :self._T], dt),
+                ops.dequantize_kv_fp8(self._vc[:, :, :self._T], self._vs[:, :, :self._T], dt))
+
+    def get_seq_length(self) -> int:
+        return self._T
+
+    def get_mask_sizes(self, query_length) -> tuple:
+        if not isinstance(query_length, int):      # (a cache_position tensor: earlier 4.5x protocol)
+            query_length = query_length.shape[0]
+        return self._T + query_length, 0
+
+    def get_max_length(self) -> int:
+        return -1
+
+    def get_max_cache_shape(self) -> int:
+        return -1
+
+    def crop(self, tokens_to_remove: int) -> None:
+        """DynamicLayer.crop's meaning: a negative number removes that many positions from the end, a positive one is the length to
+        keep (nothing happens when it is not shorter than the cache)."""
+        T = self._T
+        if tokens_to_remove > 0:
+            if tokens_to_remove >= T:
+                return
+            self._T = tokens_to_remove
+        else:
+            self._T = max(0, T + tokens_to_remove)
+
+    def _each(self, fn) -> None:
+        if self._kc is not None:
+            self._kc, self._vc, self._ks, self._vs = (fn(t) for t in (self._kc, self._vc, self._ks, self._vs))
+
+    def batch_repeat_interleave(self, repeats: int) -> None:
+        if self._T > 0:
+            self._each(lambda t: t.repeat_interleave(repeats, dim=0))
+
+    def batch_select_indices(self, indices) -> None:
+        if self._T > 0:
+            self._each(lambda t: t[indices, ...].contiguous())
+
+    def reorder_cache(self, beam_idx) -> None:
+        if self._T > 0:
+            self._each(lambda t: t.index_select(0, beam_idx.to(t.device)))
+
+    def reset(self) -> None:
+        self._T = 0
+
+    def offload(self) -> None:
+        self._each(lambda t: t.to("cpu", non_blocking=True))
+
+    def prefetch(self) -> None:
+        if self._kc is not None and self.device is not None and self._kc.device != self.device:
+            self._each(lambda t: t.to(self.device, non_blocking=True))
+
+
+def kv8_cache(n_layers: int):
+    """A plain HF DynamicCache of `n_layers` empty `Kv8Layer`s: what `kv8` leaves behind a fused prefill, for a caller that wants
+    the FP8 cache on the stock layers as well (any device)."""
+    cache = _DYN_CACHE()
+    cache.layers.extend(Kv8Layer() for _ in range(n_layers))
+    return cache
+
+
 def _plain_layers(cache):
     """The `layers` list of `cache` if it is a plain HF DynamicCache (no offloading), else None."""
     layers = getattr(cache, "layers", None)
@@ -762,15 +942,16 @@ def _plain_layers(cache):
     return layers
 
 
-def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False):
+def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False, kv8: bool = False):
     """The cache layer if `cache` is a plain HF DynamicCache (no offloading) whose layer `layer_idx` is a non-empty DynamicLayer
     -- the case the fused decode step handles (its `update` is a torch.cat: dense (B, H_kv, T, d) tensors come back).
-    sliding=True (a layer with an attention window): a DynamicSlidingWindowLayer is taken as well."""
+    sliding=True (a layer with an attention window): a DynamicSlidingWindowLayer is taken as well.  kv8=True (the switch): a
+    `Kv8Layer` too."""
     layers = _plain_layers(cache)
     if layers is None or layer_idx >= len(layers):
         return None
     lay = layers[layer_idx]
-    kinds = (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
+    kinds = (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER, Kv8Layer if kv8 else _DYN_LAYER)
     return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
 
 
@@ -999,7 +1180,10 @@ def _decode_step(self, x, pe, cache, window, pr):
     the few-rows kernel (csrc/gemm_rows.hip: the weights are still read once per step, and each block of 16 sequences gets the
     bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch.
     fp8_decode / fp4_decode / lora: the same two calls on another variant of the layer descriptor (`_decode_layer`); the adapter groups ride in
-    the calls."""
+    the calls.
+    kv8 (a `Kv8Layer` in the cache): the first call writes the step's rows to the scratch rows, the second is
+    u2tok_decoder_decode_post_kv8 -- it quantises them into position T0 of the layer's buffers and attends over the codes, always
+    with the batched kernel; counted in `kv8_stats`."""
     from . import _lib
     att = self.self_attn
     B, _, E = x.shape
@@ -1022,6 +1206,29 @@ def _decode_step(self, x, pe, cache, window, pr):
         out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
         # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers; else into the
         # step's scratch rows, for the cache's own `update`
+        lay8 = cache.layers[att.layer_idx] if st.stack.kv8 and _plain_layers(cache) is not None else None
+        if type(lay8) is Kv8Layer:
+            # an e4m3 cache: the step's rows go to the scratch rows, the second call quantises them into position T0 of the layer's
+            # buffers and attends over the codes of positions lo .. T0 (a window W: the last W)
+            T0 = lay8._room(1, B, d.Hkv, d.hd, x.device)
+            lo = 0 if window is None else max(0, T0 + 1 - window)
+            if ls is not None:
+                _lora_scratch(ls, B, sc, h)
+            v = st.variants.get((form, ls is not None))
+            _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, form, ls is not None)
+            _lib.check(h.u2tok_decoder_decode_pre(cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                                                  int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), sc["kc"].data_ptr(),
+                                                  sc["vc"].data_ptr(), 0, 0, ws, nws, stream), "u2tok_decoder_decode_pre")
+            _, kv_start, _ = st.stack.pad
+            left = kv_start is not None
+            _lib.check(h.u2tok_decoder_decode_post_kv8(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), sc["kc"].data_ptr(),
+                                                       sc["vc"].data_ptr(), lay8._kc.data_ptr(), lay8._vc.data_ptr(), lay8._ks.data_ptr(),
+                                                       lay8._vs.data_ptr(), lay8._kc.shape[2], lo, T0,
+                                                       kv_start.data_ptr() if left else None, out.data_ptr(), ws, nws, stream),
+                       "u2tok_decoder_decode_post_kv8")
+            lay8._T = T0 + 1
+            kv8_stats["padded_decode" if left else "decode"] += 1
+            return out
         kv = _KVWrite(cache, att.layer_idx, B, 1, window, like=sc["kc"])
         lay = kv.lay
         if lay is None:
@@ -1409,9 +1616,11 @@ def head_forward(model, input_ids, attention_mask, position_ids, past_key_values
     return CausalLMOutputWithPast(logits=logits, past_key_values=kw["past_key_values"])
 
 
-def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor):
+def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor, kv8: bool = False):
     """For a plain HF DynamicCache whose layer `layer_idx` is still empty: put an append-in-place layer there with room for S
-    positions (and as many again for the decode steps) and return it; None for every other cache (its `update` is used)."""
+    positions (and as many again for the decode steps) and return it; None for every other cache (its `update` is used).
+    kv8 (the switch): exactly there a `Kv8Layer` is put instead (an empty one stays), and None is returned: the caller commits
+    through the layer's `update`, which quantises."""
     layers = _plain_layers(cache)
     if layers is None:
         return None
@@ -1419,7 +1628,12 @@ def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: in
     if getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER:
         while len(layers) <= layer_idx:
             layers.append(_DYN_LAYER())
-    if layer_idx >= len(layers) or type(layers[layer_idx]) not in (_DYN_LAYER, cls) or layers[layer_idx].get_seq_length() != 0:
+    if layer_idx >= len(layers) or type(layers[layer_idx]) not in (_DYN_LAYER, cls, Kv8Layer if kv8 else cls) \
+            or layers[layer_idx].get_seq_length() != 0:
+        return None
+    if kv8:
+        if _CACHE_LAYER is not None and type(layers[layer_idx]) is not Kv8Layer:
+            layers[layer_idx] = Kv8Layer()
         return None
     try:
         lay = cls()
@@ -1481,7 +1695,7 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
-                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False) -> int:
+                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False, kv8: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
@@ -1489,7 +1703,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
                  fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
-                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head)
+                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head, kv8=kv8)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
