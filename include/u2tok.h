@@ -71,6 +71,7 @@ u2tok_ctx_t u2tok_ctx_get_current(void);     /* NULL when the thread uses the de
     "tok_flash" {1: the tokenizer's attention cores run the fused kernel of u2tok_tok_attention, 0: GEMM -> softmax -> GEMM},
     "tok_wide" {1: head dims 256 / 512 (not 384) of that kernel run its 8-wave form (a wave pair per 16-query block, two waves per SIMD),
     0: the 4-wave form},
+    "svr_fold" {1: a tokenizer forward that asks for no SVR intermediate uses the fold slots of its weight table (below), 0: never},
     "profile" {0, 1} */
 int u2tok_set_option(const char* name, int value);
 /* Scratch for split-K partial sums of u2tok_gemm_bf16 calls on `stream` (fp32, slices x M x N), registered on the
@@ -158,6 +159,20 @@ typedef struct {
  *       norm_self.weight, .bias, norm_cross_v.weight, .bias, norm_cross_t.weight, .bias
  *   then ATT layer_linagg.linear_aggregator (wv/dense present in the state dict but never read: tta.py:47-48,62-65) */
 #define U2TOK_TOK_NW(layers) (1 + 18 * (layers) + 4 + 33 * (layers) + 9)
+/* FOLD SLOTS: U2TOK_TOK_NFOLD(layers) more pointers behind the U2TOK_TOK_NW(layers) above, a (W', b') pair per SVR attention that
+ * has a predecessor.  The SVR stack is a chain of 2 L attentions with nothing between them (svr.py:23-40,50-62: no residual, norm
+ * or activation), so the output projection (dense / out_proj) of attention j - 1 is followed directly by the packed q | k | v
+ * projection of attention j: with W' = W_qkv W_o (3E, E) and b' = W_qkv b_o + b_qkv (3E) -- u2tok_tokenizer_svr_fold builds both --
+ * q | k | v of attention j is context(j - 1) W'^T + b' and the E x E product of attention j - 1 is not run.  Attention j = 2 l is
+ * layer l's spatial attention, j = 2 l + 1 its temporal one; the pair of attention j >= 1 is at U2TOK_TOK_NW + 2 (j - 1), + 1:
+ *   layer 0 temporal, layer 1 spatial, layer 1 temporal, ..., layer L-1 temporal.
+ * A null pointer in a pair means "not folded".  A pair is used when option "svr_fold" is 1, the call asks for no SVR intermediate
+ * (svr_out null; no svr_in / svr_out tap) and wq | wk | wv of attention j are packed (back to back, weights and biases); a call
+ * that asks for an SVR intermediate is parity instrumentation, runs every projection at the reference's rounding points and DOES
+ * NOT READ the slots -- every other call does, so its table must have them (null where there is no fold).  The last attention's
+ * output projection always runs.  The folded route rounds W' once to the element type where the unfolded one rounds the projected
+ * tokens; (2 L - 1) 3 E^2 elements of device memory, which the caller owns and rebuilds when a weight changes. */
+#define U2TOK_TOK_NFOLD(layers) ((layers) > 0 ? 2 * (2 * (layers) - 1) : 0)
 
 /* ---- the hot path ------------------------------------------------------------------------------ */
 
@@ -177,11 +192,19 @@ int u2tok_spp_forward(const u2tok_spp_config* cfg, const void* const* weights, c
  * aligned tokens (B,num_query,E) bf16.  topk_idx_out (optional, may be null): (B,top_k) int64 indices chosen by
  * TokenSelection (only written when !enable_diffts) -- the path's integer output.  svr_out (optional, may be null):
  * (B,T*N,E) bf16 copy of the refined tokens the selection stage scores (output of svr.py:166-170), so that a checker
- * can replay the selection on identical inputs. */
+ * can replay the selection on identical inputs.  weights: U2TOK_TOK_NW(L) + U2TOK_TOK_NFOLD(L) pointers (the fold slots are read
+ * by a call with svr_out null). */
 size_t u2tok_tokenizer_workspace_bytes(const u2tok_tokenizer_config* cfg);
 int u2tok_tokenizer_forward(const u2tok_tokenizer_config* cfg, const void* const* weights, const void* v_token,
                             const void* t_token, void* out, int64_t* topk_idx_out, void* svr_out, void* workspace,
                             size_t workspace_bytes, u2tok_stream_t stream);
+
+/* One fold slot of the tokenizer weight table: w_fold (3E, E) = w_qkv (3E, E) w_o (E, E) -- one u2tok_gemm_bf16 product, w_o read
+ * K-major as it lies -- and b_fold (3E) = b_o w_qkv^T + b_qkv; fp32 accumulation, one rounding to the element type each.  w_qkv /
+ * b_qkv: the packed wq | wk | wv of the attention, w_o / b_o: dense (out_proj) of the attention before it.  All pointers are
+ * required and the outputs must not alias the inputs; E a multiple of 8. */
+int u2tok_tokenizer_svr_fold(const void* w_qkv, const void* b_qkv, const void* w_o, const void* b_o, void* w_fold, void* b_fold,
+                             int32_t E, u2tok_stream_t stream);
 
 /* Same forward with PARITY TAPS (tests): any layer's input can be replaced by a caller buffer ("teacher forcing": each
  * layer of the residual-free SVR stack / of the TTA is then compared on the reference's own fp32 input for that layer) and

@@ -125,6 +125,8 @@ SIGNATURES = {
     "u2tok_tokenizer_forward": (_i32, [C.POINTER(TokConfig), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_tokenizer_forward_taps": (_i32, [C.POINTER(TokConfig), C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(TokTaps),
                                             _vp, _sz, _vp]),
+    # w_qkv, b_qkv, w_o, b_o, w_fold, b_fold, E, stream
+    "u2tok_tokenizer_svr_fold": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "u2tok_tok_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "u2tok_tok_attention": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                    _i64, _f32, _vp, _i32, _i32, _vp, _sz, _vp]),

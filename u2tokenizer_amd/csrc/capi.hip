@@ -62,6 +62,7 @@ int u2tok_set_option(const char* name, int value) {
       {"vit_vt_epilogue", &Options::vit_vt_epilogue, 0, 1},
       {"tok_flash", &Options::tok_flash, 0, 1},
       {"tok_wide", &Options::tok_wide, 0, 2},
+      {"svr_fold", &Options::svr_fold, 0, 1},
   };
   if (!strcmp(name, "gemm_tile")) {
     if (value != 0 && value != 64 && value != 128) return U2_ERR_ARG;
@@ -139,6 +140,11 @@ int u2tok_tokenizer_forward_taps(const u2tok_tokenizer_config* cfg, const void* 
   if (!cfg || !taps || !workspace || ((uintptr_t)workspace & 255)) return U2_ERR_ARG;
   return tokenizer_forward(*cfg, weights, BF(v_token), BF(t_token), BFW(out), topk_idx_out, nullptr, taps, workspace,
                            workspace_bytes, false, nullptr, ST(stream));
+}
+
+int u2tok_tokenizer_svr_fold(const void* w_qkv, const void* b_qkv, const void* w_o, const void* b_o, void* w_fold, void* b_fold,
+                             int32_t E, u2tok_stream_t stream) {
+  return svr_fold_build(BF(w_qkv), BF(b_qkv), BF(w_o), BF(b_o), BFW(w_fold), BFW(b_fold), E, ST(stream));
 }
 
 size_t u2tok_preprocess_workspace_bytes(int32_t D, int32_t H, int32_t W) { return preprocess_workspace_bytes(D, H, W); }

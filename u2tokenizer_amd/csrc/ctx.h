@@ -32,7 +32,8 @@ struct Options {
   int tok_flash = 1;        // 1: fused attention kernel for the tokenizer's attention cores (tokattn.hip); 0: GEMM chain
   int tok_wide = 2;         // 2 (1: the same kernel with FLAT-encoded global_load_lds pieces instead of buffer_load ... lds -- A/B): head dims 256 / 512 of the fused kernel run the 8-wave form (two waves per SIMD, tok_attn2_kernel); 0: the 4-wave form (A/B)
   int tta_overlap = 1;      // k | v projections of the TTA cross attentions on a side stream
-  int profile = 0;          // bracket every launch with hipEvents (u2tok_profile_collect)
+  int svr_fold = 1;         // 1: a tokenizer forward that asks for no SVR intermediate reads the fold slots of its weight table (output projection folded into the next q | k | v); 0: never (A/B)
+  int profile = 0;         // bracket every launch with hipEvents (u2tok_profile_collect)
 };
 
 struct SideStream {  // created lazily, one per caller stream that ever ran a tokenizer forward on this context

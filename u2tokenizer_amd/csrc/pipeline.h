@@ -25,5 +25,8 @@ int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_
 int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_token, const bf16_t* t_token,
                       bf16_t* out, int64_t* topk_idx_out, bf16_t* svr_out, const TokTaps* taps, void* ws, size_t ws_bytes,
                       bool dry, size_t* peak, hipStream_t st);
+// One fold slot of the tokenizer weight table: Wf[3E][E] = Wqkv[3E][E] Wo[E][E], bf[3E] = bo Wqkv^T + bqkv (one rounding each)
+int svr_fold_build(const bf16_t* Wqkv, const bf16_t* bqkv, const bf16_t* Wo, const bf16_t* bo, bf16_t* Wf, bf16_t* bf, int E,
+                   hipStream_t st);
 
 }  // namespace u2

@@ -358,7 +358,10 @@ int spp_forward(const SppConfig& c, const void* const* W, const bf16_t* x, bf16_
 // =========================================================================== u2Tokenizer
 namespace {
 struct Att { Lin q, k, v, o; const bf16_t* rb; };  // an attention module's projections and its relative-bias table (null: none)
-struct SvrLayer { Att spatial, temporal; };
+// fold: the packed q | k | v projection applied to the output projection of the attention BEFORE this one (svr_fold_build);
+// null: not folded, that output projection runs
+struct SvrAtt : Att { Lin fold; };
+struct SvrLayer { SvrAtt spatial, temporal; };
 struct TtaLayer { Att self, visual, text; Lin norm_self, norm_v, norm_t; };
 struct TokWeights {
   const bf16_t* query;
@@ -367,16 +370,31 @@ struct TokWeights {
   std::vector<SvrLayer> svr;  // per layer
   std::vector<TtaLayer> tta;
 };
+// n projections of one input lie back to back in HBM, weights and biases (tokenizer.py: pack_weights)
+bool packed(const Lin* l, int n, int E) {
+  bool p = l[0].w && l[0].b;
+  for (int i = 1; i < n; ++i) p = p && l[i].w == l[i - 1].w + (size_t)E * E && l[i].b == l[i - 1].b + E;
+  return p;
+}
 // The tokenizer weight table (include/u2tok.h, "Tokenizer weight table"): read here and nowhere else.  Only the self attentions of
-// attn_type rma have a bias table; whatever the table holds in that slot of any other attention is dropped here.
-TokWeights tok_weights(const TokConfig& c, Table t) {
+// attn_type rma have a bias table; whatever the table holds in that slot of any other attention is dropped here.  The fold slots
+// behind the table are read only when `folds`; a slot is taken when both its pointers are there and its attention's q | k | v is packed.
+TokWeights tok_weights(const TokConfig& c, Table t, bool folds) {
   auto att = [&](int i, bool self) {
     return Att{{t[i], t[i + 1]}, {t[i + 2], t[i + 3]}, {t[i + 4], t[i + 5]}, {t[i + 6], t[i + 7]}, self && c.attn_type == 0 ? t[i + 8] : nullptr};
   };
-  const int L = c.num_layers, i_sel = 1 + 18 * L, i_tta = i_sel + 4, i_lin = i_tta + 33 * L;
+  const int L = c.num_layers, i_sel = 1 + 18 * L, i_tta = i_sel + 4, i_lin = i_tta + 33 * L, i_fold = U2TOK_TOK_NW(L);
+  // SVR attention j = 2 l (spatial) / 2 l + 1 (temporal) of the chain; fold slot j - 1 holds its (W', b')
+  auto svr_att = [&](int i, int j) {
+    SvrAtt a{att(i, true), {nullptr, nullptr}};
+    const Lin qkv[3] = {a.q, a.k, a.v};
+    if (folds && j > 0 && t[i_fold + 2 * (j - 1)] && t[i_fold + 2 * (j - 1) + 1] && packed(qkv, 3, c.E))
+      a.fold = {t[i_fold + 2 * (j - 1)], t[i_fold + 2 * (j - 1) + 1]};
+    return a;
+  };
   TokWeights w{t[0], {t[i_sel], t[i_sel + 1]}, {nullptr, nullptr}, att(i_lin, false), {}, {}};
   if (c.enable_dmtp) w.gate = {t[i_sel + 2], t[i_sel + 3]};
-  for (int l = 0, i = 1; l < L; ++l, i += 18) w.svr.push_back({att(i, true), att(i + 9, true)});
+  for (int l = 0, i = 1; l < L; ++l, i += 18) w.svr.push_back({svr_att(i, 2 * l), svr_att(i + 9, 2 * l + 1)});
   for (int l = 0, i = i_tta; l < L; ++l, i += 33)
     w.tta.push_back({att(i, true), att(i + 9, false), att(i + 18, false), {t[i + 27], t[i + 28]}, {t[i + 29], t[i + 30]}, {t[i + 31], t[i + 32]}});
   return w;
@@ -388,9 +406,7 @@ TokWeights tok_weights(const TokConfig& c, Table t) {
 // out[rows][n E] = x W^T + b for the n projections p: {q, k, v} or {k, v} of one attention
 int packed_proj(const Run& r, const bf16_t* x, std::initializer_list<Lin> p, bf16_t* out, int64_t rows, int E) {
   const Lin* l = p.begin(); const int n = (int)p.size();
-  bool packed = l[0].w && l[0].b;
-  for (int i = 1; i < n; ++i) packed = packed && l[i].w == l[i - 1].w + (size_t)E * E && l[i].b == l[i - 1].b + E;
-  if (packed) return linear(r, x, l[0], out, n * E, rows, E, n * E);
+  if (packed(l, n, E)) return linear(r, x, l[0], out, n * E, rows, E, n * E);
   for (int i = 0; i < n; ++i) U2_TRY(linear(r, x, l[i], out + i * E, n * E, rows, E, E));
   return U2_OK;
 }
@@ -411,6 +427,7 @@ struct Tok {  // one tokenizer forward: what its stages share, and the stages in
   Heads hd;
   int64_t rows, qrows;                // B * T * N visual rows, B * Q query rows
   bf16_t *xa, *xb, *qkv, *sctx;       // SVR: ping-pong token buffers, packed q | k | v, attention context
+  bool x_ctx = false;                 // SVR: x is an attention's context, its output projection folded into the next q | k | v
   const bf16_t* V; int Lv;            // the Lv visual tokens per batch entry the aggregation attends to
   bf16_t *qa, *qb, *qc, *qproj, *qctx, *qo;  // TTA: query ping-pong (+ qc), projections, context, sub-layer output
   // k | v of the two cross attentions of every layer: one buffer each, filled on the side stream (or kv_inline, in line)
@@ -418,8 +435,8 @@ struct Tok {  // one tokenizer forward: what its stages share, and the stages in
   bf16_t *kv_inline, *kv_v[8], *kv_t[8], *k_lin;  // k_lin: key projection of the final linear aggregation
 
   // attn_type 2 with B > 1, temporal: the sequence is the B*N (batch, token) pairs of one chunk index: gather rows (b, t, n) ->
-  // (t, b, n), attend, scatter
-  int temporal_across_batch() {
+  // (t, b, n), attend, scatter into actx
+  int temporal_across_batch(bf16_t* actx) {
     const size_t mark = r.ar.off;
     bf16_t* g = r.ar.get<bf16_t>((size_t)rows * 3 * E);
     bf16_t* gc = r.ar.get<bf16_t>((size_t)rows * E);
@@ -429,8 +446,30 @@ struct Tok {  // one tokenizer forward: what its stages share, and the stages in
       U2_TRY(copy_runs(r, g + (size_t)b * N * 3 * E, S2 * 3 * E, qkv + (size_t)b * T * N * 3 * E, (size_t)N * 3 * E, (size_t)N * 3 * E, T));
     U2_TRY(self_attention(r, hd, g, gc, T, (int)S2, 3 * E, (int64_t)S2 * 3 * E, nullptr));
     for (int b = 0; b < B; ++b)
-      U2_TRY(copy_runs(r, sctx + (size_t)b * T * N * E, (size_t)N * E, gc + (size_t)b * N * E, S2 * E, (size_t)N * E, T));
+      U2_TRY(copy_runs(r, actx + (size_t)b * T * N * E, (size_t)N * E, gc + (size_t)b * N * E, S2 * E, (size_t)N * E, T));
     r.ar.off = mark;
+    return U2_OK;
+  }
+
+  // The SVR stack is a chain of 2 L attentions with nothing between them (svr.py:23-40,50-62): the output projection of one is
+  // followed directly by the packed q | k | v projection of the next, a Linear applied to a Linear.  Where the next attention has its
+  // fold (W' = W_qkv W_o, b' = W_qkv b_o + b_qkv: SvrAtt::fold), the output projection is skipped and x stays that attention's
+  // CONTEXT (x_ctx) for the folded projection to read: one E x E product per attention less.  The last attention's always runs.
+  // q | k | v of attention a from x
+  int svr_qkv(const SvrAtt& a, const bf16_t* x) {
+    if (x_ctx) return linear(r, x, a.fold, qkv, 3 * E, rows, E, 3 * E);
+    return packed_proj(r, x, {a.q, a.k, a.v}, qkv, rows, E);
+  }
+  // where attention a's context goes: sctx, or xa when x (which the projection before it reads) is sctx itself
+  bf16_t* svr_ctx(const bf16_t* x) const { return x == sctx ? xa : sctx; }
+  // x = the output projection of attention a's context actx (into xa / xb, whichever neither x nor actx is), or actx itself when the
+  // attention `next` folds the projection
+  int svr_project(const SvrAtt& a, const SvrAtt* next, bf16_t* actx, const bf16_t*& x) {
+    x_ctx = next && next->fold.w;
+    if (x_ctx) { x = actx; return U2_OK; }
+    bf16_t* y = (x == xa || actx == xa) ? xb : xa;
+    U2_TRY(linear(r, actx, a.o, y, E, rows, E, E));
+    x = y;
     return U2_OK;
   }
 
@@ -440,28 +479,27 @@ struct Tok {  // one tokenizer forward: what its stages share, and the stages in
   // "temporal" = across the B*N (batch, token) pairs of a chunk index.
   int svr_layer(int l, const bf16_t*& x) {
     const SvrLayer& a = w.svr[l];
-    if (const void* in = slot(taps.svr_in, l)) x = reinterpret_cast<const bf16_t*>(in);
-    bf16_t* y = (x == xa) ? xb : xa;
+    if (const void* in = slot(taps.svr_in, l)) x = reinterpret_cast<const bf16_t*>(in);  // (a call with SVR taps has no folds)
     // spatial: sequences of N tokens inside each chunk (svr.py:27-30)
-    U2_TRY(packed_proj(r, x, {a.spatial.q, a.spatial.k, a.spatial.v}, qkv, rows, E));
+    bf16_t* actx = svr_ctx(x);
+    U2_TRY(svr_qkv(a.spatial, x));
     if (c.attn_type == 1) U2_TRY(rope_qk(r, hd, qkv, (int64_t)B * T, N, 1));
     if (c.attn_type == 2)  // sequence = the B*T (batch, chunk) pairs, batch = token position
-      U2_TRY(chunk_axis_attention(r, hd, qkv, sctx, 1, B * T, N, a.spatial.rb));
+      U2_TRY(chunk_axis_attention(r, hd, qkv, actx, 1, B * T, N, a.spatial.rb));
     else
-      U2_TRY(self_attention(r, hd, qkv, sctx, B * T, N, 3 * E, (int64_t)N * 3 * E, a.spatial.rb));
-    U2_TRY(linear(r, sctx, a.spatial.o, y, E, rows, E, E));
+      U2_TRY(self_attention(r, hd, qkv, actx, B * T, N, 3 * E, (int64_t)N * 3 * E, a.spatial.rb));
+    U2_TRY(svr_project(a.spatial, &a.temporal, actx, x));
     // temporal: sequences of T chunks at each token position (svr.py:32-36); rows stay in (b t n) order
-    bf16_t* y2 = (y == xa) ? xb : xa;
-    U2_TRY(packed_proj(r, y, {a.temporal.q, a.temporal.k, a.temporal.v}, qkv, rows, E));
+    actx = svr_ctx(x);
+    U2_TRY(svr_qkv(a.temporal, x));
     if (c.attn_type == 1) U2_TRY(rope_qk(r, hd, qkv, B, T, N));
     if (c.attn_type == 2 && B == 1)  // sequence = the N tokens of a chunk, batch = chunk
-      U2_TRY(self_attention(r, hd, qkv, sctx, T, N, 3 * E, (int64_t)N * 3 * E, a.temporal.rb));
+      U2_TRY(self_attention(r, hd, qkv, actx, T, N, 3 * E, (int64_t)N * 3 * E, a.temporal.rb));
     else if (c.attn_type == 2)
-      U2_TRY(temporal_across_batch());
+      U2_TRY(temporal_across_batch(actx));
     else
-      U2_TRY(chunk_axis_attention(r, hd, qkv, sctx, B, T, N, a.temporal.rb));
-    U2_TRY(linear(r, sctx, a.temporal.o, y2, E, rows, E, E));
-    x = y2;
+      U2_TRY(chunk_axis_attention(r, hd, qkv, actx, B, T, N, a.temporal.rb));
+    U2_TRY(svr_project(a.temporal, l + 1 < L ? &w.svr[l + 1].spatial : nullptr, actx, x));
     return tap(r, slot(taps.svr_out, l), x, (size_t)rows * E);
   }
 
@@ -631,7 +669,12 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
   const int B = c.B, E = c.E, d = E / c.num_heads, L = c.num_layers, k = c.top_k;
   if (!c.enable_diffts && k > c.T * c.N) return U2_ERR_ARG;                     // torch.topk would raise
   if (c.N > c.max_seq_len || c.T > c.max_seq_len || c.num_query > c.max_seq_len) return U2_ERR_ARG;  // rma.py:64-68 index range
-  const TokWeights w = tok_weights(c, Table{dry ? nullptr : W});
+  // The SVR folds are for calls that ask for the aligned tokens alone.  A call that asks for an SVR intermediate (the refined tokens,
+  // an SVR tap) is parity instrumentation: it runs projection by projection, at the reference's rounding points, and does not read
+  // the fold slots at all.  (The TTA / visual taps sit behind the stack and do not look into it.)
+  bool folds = !dry && opts().svr_fold && !svr_out;
+  for (int l = 0; folds && taps && l < L; ++l) folds = !slot(taps->svr_in, l) && !slot(taps->svr_out, l);
+  const TokWeights w = tok_weights(c, Table{dry ? nullptr : W}, folds);
 
   Arena ar(ws, ws_bytes, dry);
   // split-K scratch for the skinny linear layers of this forward (M = 256 queries against E x E weights); registered
@@ -669,6 +712,22 @@ int tokenizer_forward(const TokConfig& c, const void* const* W, const bf16_t* v_
   if (peak) *peak = ar.peak;
   U2_CHECK_WS(ar);
   return U2_OK;
+}
+
+// y = ctx Wo^T + bo, then q | k | v = y Wqkv^T + bqkv  ==  ctx (Wqkv Wo)^T + (bo Wqkv^T + bqkv).  Wo [E_out][E_in] is the K-major B
+// operand of the first product as it lies.  No split-K scratch, whatever the caller registered: the same bits for the same weights.
+int svr_fold_build(const bf16_t* Wqkv, const bf16_t* bqkv, const bf16_t* Wo, const bf16_t* bo, bf16_t* Wf, bf16_t* bf, int E,
+                   hipStream_t st) {
+  if (!Wqkv || !bqkv || !Wo || !bo || !Wf || !bf || E <= 0 || (E & 7)) return U2_ERR_ARG;
+  if (Wf == Wqkv || Wf == Wo || bf == bqkv || bf == bo) return U2_ERR_ARG;
+  ScratchScope scratch_scope(ctx(), st, nullptr, 0, true);
+  GemmDesc g;
+  g.A = Wqkv; g.B = Wo; g.C = Wf;
+  g.M = 3 * E; g.N = E; g.K = E;
+  g.lda = E; g.ldb = E; g.ldc = E;
+  g.flags = GEMM_B_KMAJOR;
+  U2_TRY(gemm_bf16(g, st));
+  return gemm_bf16(linear_desc(bo, E, Wqkv, bqkv, bf, 3 * E, 1, E, 3 * E, 0, nullptr, 0), st);
 }
 
 }  // namespace u2

@@ -205,6 +205,26 @@ def _att_ptrs(m, value_side: bool = True):
             getattr(m, "relative_bias", None)]
 
 
+def _fold_sources(m):
+    """(packed q | k | v weight, its bias, output projection weight, its bias) of one SVR attention, and the parameters behind
+    them (whose in-place version counters say when a fold built from them is stale)."""
+    if isinstance(m, nn.MultiheadAttention):
+        return (m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias), \
+            [m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias]
+    return (m.wq.weight, m.wq.bias, m.dense.weight, m.dense.bias), \
+        [m.wq.weight, m.wq.bias, m.wk.weight, m.wk.bias, m.wv.weight, m.wv.bias, m.dense.weight, m.dense.bias]
+
+
+def _qkv_packed(m) -> bool:
+    if isinstance(m, nn.MultiheadAttention):
+        return m.in_proj_weight is not None and m.in_proj_bias is not None and m.out_proj.bias is not None
+    ws, bs = [m.wq.weight, m.wk.weight, m.wv.weight], [m.wq.bias, m.wk.bias, m.wv.bias]
+    if any(b is None for b in bs) or m.dense.bias is None:
+        return False
+    sw, sb = ws[0].numel() * ws[0].element_size(), bs[0].numel() * bs[0].element_size()
+    return all(ws[i + 1].data_ptr() == ws[i].data_ptr() + sw and bs[i + 1].data_ptr() == bs[i].data_ptr() + sb for i in (0, 1))
+
+
 def _unshare_packed(module, state_dict, prefix, local_metadata):
     """state_dict hook: parameters that pack_weights() turned into views of one q | k | v buffer are handed out as
     unshared copies, so that safetensors / save_pretrained (which refuse tensors sharing storage) and any consumer that
@@ -237,6 +257,8 @@ class u2Tokenizer(nn.Module):
         self.enable_diffts, self.enable_dmtp = bool(enable_diffts), bool(enable_dmtp)
         self._ws = ops._Workspace()
         self._packed_key = None
+        self._folds = None      # SVR folds (pack_weights): plain attributes -- derived data, never in state_dict()
+        self._fold_key = None
         self._dead_offloaded = False
         self._register_state_dict_hook(_unshare_packed)
         self.last_topk_indices = None  # (B, top_k) int64 -- set by forward() when hard top-k selection is on
@@ -266,24 +288,82 @@ class u2Tokenizer(nn.Module):
         """Idempotent.  Runs eagerly whenever the parameters move (.to() / .cuda() / .bfloat16() go through _apply) and
         as a safety net at the head of forward().  Packing re-points wq / wk / wv at freshly written buffers, so it ends
         with a device-wide synchronisation: every stream sees the packed weights, and the old storages are idle when
-        the caching allocator takes them back (forward calls may be issued on several non-blocking streams)."""
+        the caching allocator takes them back (forward calls may be issued on several non-blocking streams).
+
+        On the GPU it then builds the SVR folds (include/u2tok.h, "FOLD SLOTS"): for every SVR attention but the first,
+        W' = W_qkv W_o and b' = W_qkv b_o + b_qkv with the output projection of the attention before it, (2 L - 1) 3 E^2
+        elements in all.  They are rebuilt with the packing and whenever a parameter they were built from has been written in
+        place since (copy_, load_state_dict: the tensors' version counters), and a forward on the autograd route drops them
+        (an optimiser that writes through param.data, as Zero1AdamW and DeepSpeed do, leaves no other trace); only the
+        inference forward reads them.  A write through param.data with no training forward in between (an EMA copy, a
+        broadcast) needs invalidate_folds()."""
         key = (self.query_tokens.data_ptr(), self.query_tokens.dtype)
-        if self._packed_key == key:
-            return
-        with torch.no_grad():
-            for layer in self.svt_module.attention_network.layers:
-                _pack_qkv(layer.spatial_attention)
-                _pack_qkv(layer.temporal_attention)
-            for layer in self.tta_module.layers_vt:
-                for m in (layer.self_attention, layer.visual_cross_attention, layer.text_cross_attention):
-                    _pack_qkv(m)
+        repacked = self._packed_key != key
+        if repacked:
+            with torch.no_grad():
+                for layer in self.svt_module.attention_network.layers:
+                    _pack_qkv(layer.spatial_attention)
+                    _pack_qkv(layer.temporal_attention)
+                for layer in self.tta_module.layers_vt:
+                    for m in (layer.self_attention, layer.visual_cross_attention, layer.text_cross_attention):
+                        _pack_qkv(m)
+            self.invalidate_folds()
         if self.query_tokens.is_cuda:
-            torch.cuda.synchronize(self.query_tokens.device)
+            refold = self._fold_key is None or self._fold_key != self._fold_versions()
+            if refold:
+                self._build_folds()
+            if refold or repacked:
+                torch.cuda.synchronize(self.query_tokens.device)
         self._packed_key = key
+
+    def invalidate_folds(self) -> None:
+        """Drops the SVR folds (and their memory); the next pack_weights() / inference forward on the GPU rebuilds them."""
+        self._folds = self._fold_key = None
+
+    def _svr_chain(self):
+        """The SVR attentions in the order they run: layer 0 spatial, layer 0 temporal, layer 1 spatial, ..."""
+        return [m for layer in self.svt_module.attention_network.layers
+                for m in (layer.spatial_attention, layer.temporal_attention)]
+
+    def _fold_versions(self):
+        return tuple(p._version for m in self._svr_chain() for p in _fold_sources(m)[1])
+
+    def _build_folds(self) -> None:
+        """One (W', b') per SVR attention behind the first, through u2tok_tokenizer_svr_fold on the current stream; None where
+        an attention's q | k | v is not packed or the parameters are not 16-bit (such a model cannot run the forward either)."""
+        chain, dt, dev = self._svr_chain(), self.query_tokens.dtype, self.query_tokens.device
+        self._folds, self._fold_key = None, self._fold_versions()
+        if len(chain) < 2 or dt not in ops.ELEM_OF:
+            return
+        E, n = self.embed_size, len(chain) - 1
+        with torch.no_grad(), ops.on_device(self.query_tokens, elem=dt) as (h, stream):
+            W = torch.empty((n, 3 * E, E), dtype=dt, device=dev)  # noqa: N806
+            b = torch.empty((n, 3 * E), dtype=dt, device=dev)
+            folds = []
+            for j in range(1, len(chain)):
+                if not _qkv_packed(chain[j]):
+                    folds.append(None)
+                    continue
+                (w_qkv, b_qkv, _, _), _ = _fold_sources(chain[j])
+                (_, _, w_o, b_o), _ = _fold_sources(chain[j - 1])
+                _lib.check(h.u2tok_tokenizer_svr_fold(w_qkv.data_ptr(), b_qkv.data_ptr(), w_o.data_ptr(), b_o.data_ptr(),
+                                                      W[j - 1].data_ptr(), b[j - 1].data_ptr(), E, stream),
+                           "u2tok_tokenizer_svr_fold")
+                folds.append((W[j - 1], b[j - 1]))
+        self._folds = folds
+
+    def _fold_slots(self):
+        """The fold slots of the weight table (behind _weights()): W', b' per SVR attention that has a predecessor, None = not
+        folded.  The library decides per call whether it reads them (a call that asks for SVR tensors does not)."""
+        n = max(0, 2 * self.num_layers - 1)
+        if self._folds is None:
+            return [None] * (2 * n)
+        return [t for f in self._folds for t in (f if f is not None else (None, None))]
 
     def _apply(self, fn, *args, **kwargs):
         r = super()._apply(fn, *args, **kwargs)
         self._packed_key = None
+        self.invalidate_folds()
         if self.query_tokens.is_cuda:
             self.pack_weights()
             if self._dead_offloaded:
@@ -342,7 +422,7 @@ class u2Tokenizer(nn.Module):
         L, Q, dev = self.num_layers, self.num_query, v_token.device
         Lv = self.top_k + (self.top_k // 2 + self.top_k // 4 if self.use_multi_scale else 0)
         cfg = self._config(B, T, N, E, t_token.shape[1])
-        table = ops.weight_table(self._weights())
+        table = ops.weight_table(self._weights() + self._fold_slots())  # (the svr_out taps keep the library off the folds)
         nbytes = h.u2tok_tokenizer_workspace_bytes(C.byref(cfg))
         keep = []
 
@@ -395,6 +475,7 @@ class u2Tokenizer(nn.Module):
                                         or any(p.requires_grad for p in self.parameters())):
             # training: the same kernels sequenced op by op behind torch.autograd.Function (autograd.py)
             from . import autograd as AG
+            self.invalidate_folds()   # the weights are about to change, possibly through param.data; this route reads no fold
             ops.training_needs_bf16(self.query_tokens.dtype, "u2Tokenizer")
             ops._need(v_token, ops.ELEM, "v_token"), ops._need(t_token, ops.ELEM, "t_token")
             (B, T, N, E) = v_token.size()
@@ -411,7 +492,7 @@ class u2Tokenizer(nn.Module):
             raise RuntimeError(f"shape mismatch: v_token {tuple(v_token.shape)}, t_token {tuple(t_token.shape)}")
         self._check_envelope(B, T, N, E, t_token.shape[1])
         cfg = self._config(B, T, N, E, t_token.shape[1])
-        table = ops.weight_table(self._weights())
+        table = ops.weight_table(self._weights() + self._fold_slots())  # (capture_svr_tokens keeps the library off the folds)
         nbytes = h.u2tok_tokenizer_workspace_bytes(C.byref(cfg))
         if nbytes == 0:
             raise RuntimeError("u2tok_tokenizer_workspace_bytes rejected the configuration "
