@@ -390,6 +390,9 @@ int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, i
  * or per sequence as before.  B > 64, and B > 16 with batched = 0: U2TOK_ERR_ARG before anything is launched.
  * A sliding-window layer (Phi-3: the last W positions) passes K / V advanced to its first visible position and T = W.
  * One workspace for both calls: u2tok_decoder_decode_workspace_bytes(cfg, T) bytes.
+ * EVERY refusal of pre, of post and of post_kv8 -- the half's own argument checks and everything one of its launches would refuse
+ * (the products', the row kernels', the attention's, the adapter groups') -- is evaluated before the call's first launch, as in the
+ * whole-stack step below: an error code other than U2TOK_ERR_LAUNCH means nothing was launched and nothing was written.
  * The layer's parameters travel in one descriptor, filled once per layer; the library keeps no pointer to it.  With the four
  * scales NULL the four W* are contiguous (N, K) matrices in the element type.  With all four set the step is weight-only FP8:
  * the W* are OCP e4m3 codes (contiguous (N, K) bytes) with one fp32 scale per weight row, every product is u2tok_gemm_rows_w8's

@@ -311,3 +311,43 @@ def test_every_refusal_comes_before_the_first_launch(ops):
     want = m.model(inputs_embeds=xs[:, 1:2], past_key_values=cache, use_cache=True).last_hidden_state
     assert torch.equal(m.model.norm(raw[:, None]), want)
     prefill.disable_fused_prefill(m)
+
+
+@pytest.mark.parametrize("entry", ["per sequence", "batched", "kv8"])
+def test_a_per_layer_refusal_comes_before_the_first_launch(ops, entry):
+    """u2tok_decoder_decode_post / _post_kv8 called directly (B = 2, E = 256, 4 / 2 heads of 64, I = 512, T = 18) with a 16-bit Wdown
+    8 bytes off alignment -- an in-bounds offset into a real allocation, every other buffer real too, so a call that were accepted
+    could not fault.  Only the down product's own check sees it, the last launch of the half: the call returns U2TOK_ERR_ARG and `out`,
+    the whole workspace and (kv8) the code and scale buffers keep every sentinel byte -- neither the attention nor a product before
+    the refusal was launched."""
+    from u2tokenizer_amd import _lib
+    B, E, Hq, Hkv, Dh, I, T, CAP = 2, 256, 4, 2, 64, 512, 18, 32
+    nq = (Hq + 2 * Hkv) * Dh
+
+    def z(*shape):
+        return torch.zeros(*shape, dtype=bf, device=D)
+
+    x, qkv, K, V = z(B, E), z(B, nq), z(B, Hkv, T, Dh), z(B, Hkv, T, Dh)
+    Wo, post, Wgu, Wdown = z(E, Hq * Dh), z(E), z(2 * I, E), z(E * I + 8)
+    cfg = _lib.DecodeConfig(B=B, E=E, Hq=Hq, Hkv=Hkv, D=Dh, I=I, eps=1e-6, qk_eps=1e-6, scale=Dh ** -0.5, wform=0)
+    lay = _lib.DecodeLayer(Wo=Wo.data_ptr(), w_post_norm=post.data_ptr(), Wgu=Wgu.data_ptr(), Wdown=Wdown.data_ptr() + 8)
+    assert Wdown.data_ptr() % 16 == 0
+    out = torch.full((B, E), 7.0, dtype=bf, device=D)
+    k_new, v_new = z(B, Hkv, 1, Dh), z(B, Hkv, 1, Dh)
+    codes = [torch.full((B, Hkv, CAP, Dh), 0x55, dtype=torch.uint8, device=D) for _ in range(2)]
+    scales = [torch.full((B, Hkv, CAP), 7.0, dtype=torch.float32, device=D) for _ in range(2)]
+    with ops.on_device(x) as (h, stream):
+        need = h.u2tok_decoder_decode_workspace_bytes(C.byref(cfg), T)
+        assert need > 0
+        ws = torch.full((need,), 0x55, dtype=torch.uint8, device=D)
+        if entry == "kv8":
+            st = h.u2tok_decoder_decode_post_kv8(C.byref(cfg), C.byref(lay), x.data_ptr(), qkv.data_ptr(), k_new.data_ptr(), v_new.data_ptr(),
+                                                 codes[0].data_ptr(), codes[1].data_ptr(), scales[0].data_ptr(), scales[1].data_ptr(), CAP, 0,
+                                                 T - 1, None, out.data_ptr(), ws.data_ptr(), need, stream)
+        else:
+            st = h.u2tok_decoder_decode_post(C.byref(cfg), C.byref(lay), x.data_ptr(), qkv.data_ptr(), K.data_ptr(), V.data_ptr(), T, 0,
+                                             int(entry == "batched"), None, out.data_ptr(), ws.data_ptr(), need, stream)
+        torch.cuda.synchronize()
+    assert st == -1                                                   # U2TOK_ERR_ARG
+    assert bool((out == 7).all()) and bool((ws == 0x55).all())
+    assert all(bool((c == 0x55).all()) for c in codes) and all(bool((s == 7).all()) for s in scales)

@@ -7,8 +7,8 @@ Qwen3-8B layer shape with synthetic weights, and the microseconds `route` plus a
                                       [--pairs 3] [--rounds 3] [--layers 4] [--host-only]
 
 Cells: decode B = 1 and B = 8 at T = 1024 on append-in-place caches; B = 8 left-padded (padded); B = 1 fp8_decode; B = 32
-wide_decode; B = 1 lora (r = 16 on all seven projections); B = 1 fp4_decode; B = 32 fp4_decode + wide_decode; prefill B = 1,
-S = 1024; and `route_us`, which needs no GPU: a patched
+wide_decode; B = 1 lora (r = 16 on all seven projections); B = 1 fp4_decode; B = 32 fp4_decode + wide_decode; B = 1 and B = 8
+stack_decode (the whole-stack step: one library call per token); prefill B = 1, S = 1024; and `route_us`, which needs no GPU: a patched
 layer's forward on the decode route with `_decode_step` replaced by a stub, on the CPU with a tensor that reports `is_cuda`
 (--host-only runs this cell alone and opens no GPU anywhere).
 
@@ -41,6 +41,8 @@ DECODE_CELLS = {
     "decode_b1_lora": (1, dict(lora=True), False, True),
     "decode_b1_fp4": (1, dict(fp4_decode=True), False, False),
     "decode_b32_wide_fp4": (32, dict(fp4_decode=True, wide_decode=True), False, False),
+    "decode_b1_stack": (1, dict(stack_decode=True), False, False),
+    "decode_b8_stack": (8, dict(stack_decode=True), False, False),
 }
 GPU_CELLS = list(DECODE_CELLS) + ["prefill_b1_s1024"]
 HOST_CELL = "route_us"
@@ -141,11 +143,12 @@ def child(a):
         if padded:   # (built outside the clock: sequence b has 3 b pads)
             full = (torch.arange(T + n, device=dev)[None, :] >= 3 * torch.arange(B, device=dev)[:, None]).long()
             masks = [full[:, :T + i + 1].contiguous() for i in range(n)]
-        s0 = dict(prefill.stats)
+        s0, k0 = dict(prefill.stats), prefill.stack_stats["decode"]
         out[cell] = timed(lambda i: m.model(inputs_embeds=x, past_key_values=cache, use_cache=True,
                                             **({} if masks is None else {"attention_mask": masks[i]})))
         key = "padded_decode" if padded else "decode"
         assert prefill.stats[key] - s0[key] == n * a.layers, (cell, "the steps did not take the fused route")
+        assert prefill.stack_stats["decode"] - k0 == (n if flags.get("stack_decode") else 0), (cell, "whole-stack steps")
         prefill.disable_fused_prefill(m)
         if adapters:
             merge_lora(m)   # (B is zero: the weights are what they were)

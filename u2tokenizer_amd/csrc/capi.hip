@@ -518,7 +518,7 @@ int u2tok_decode_attention(const void* q, const void* K, const void* V, void* ou
                            int32_t D, int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int32_t* kv_start,
                            void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
   return decode_attention(BF(q), BF(K), BF(V), BFW(out), B, Hq, Hkv, T, D, ldq, kv_stride, ldo, scale, kv_start, workspace,
-                          workspace_bytes, ST(stream));
+                          workspace_bytes, false, ST(stream));
 }
 int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, int64_t ld_in, int64_t ld_out,
                       u2tok_stream_t stream) {

@@ -295,7 +295,7 @@ size_t decode_attention_workspace_bytes(int B, int Hq, int Hkv, int T, int D) {
 
 int decode_attention(const bf16_t* q, const bf16_t* K, const bf16_t* V, bf16_t* out, int B, int Hq, int Hkv, int T, int D,
                      int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int* kv_start, void* ws, size_t ws_bytes,
-                     hipStream_t stream) {
+                     bool check_only, hipStream_t stream) {
   if (!q || !K || !V || !out || B <= 0 || B > 65535 || T <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 16) return U2_ERR_ARG;
   if (D != 64 && D != 96 && D != 128) return U2_ERR_ARG;
   if (kv_stride == 0) kv_stride = (int64_t)T * D;
@@ -320,6 +320,7 @@ int decode_attention(const bf16_t* q, const bf16_t* K, const bf16_t* V, bf16_t* 
   }
   const int64_t grid = (int64_t)B * Hkv * a.ns;
   if (grid > 0x7fffffff) return U2_ERR_ARG;
+  if (check_only) return U2_OK;
   ProfScope ps(PROF_TOKATTN, 4.0 * B * Hq * (double)T * D, stream, 2.0 * B * D * (2.0 * Hq + 2.0 * T * Hkv));
 #define U2_DA(D_)                                                                                                      \
   do {                                                                                                                 \

@@ -168,11 +168,15 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const bf16_t* __restrict__ 
             pack2_bf16(f(bf16lo(g.w), bf16lo(u.w)), f(bf16hi(g.w), bf16hi(u.w)))};
 }
 
-int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out, hipStream_t stream) {
+int swiglu_check(const bf16_t* gu, const bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out) {
   if (!gu || !out || rows <= 0 || I <= 0 || (I & 7) || (ld_in & 7) || (ld_out & 7) || (((uintptr_t)gu | (uintptr_t)out) & 15))
     return U2_ERR_ARG;
+  return cdiv(rows * (I >> 3), 256) > 0x7fffffff ? U2_ERR_ARG : U2_OK;
+}
+
+int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out, hipStream_t stream) {
+  if (const int e = swiglu_check(gu, out, rows, I, ld_in, ld_out)) return e;
   const int64_t total = rows * (I >> 3);
-  if (cdiv(total, 256) > 0x7fffffff) return U2_ERR_ARG;
   ProfScope ps(PROF_ROWOP, 0, stream, (double)rows * I * 6.0);
   hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, gu, out, rows, I, ld_in, ld_out);
   return launch_status();
@@ -183,16 +187,43 @@ int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_i
 // step `generate` repeats up to 768 times per report is bound by the host's launch rate when every kernel is its own Python
 // call (7.9 ms per step of a 36-layer decoder, ~4 ms of kernels).  Between the halves the host appends k / v to its cache
 // (HF DynamicCache: a torch.cat) and hands back the dense (B, H_kv, T, D) tensors.
+// Every entry point walks its sequence of launches twice, through one Step: a DEC_CHECK walk, in which each op answers with the
+// refusals of its launcher -- the launcher's own code -- and launches nothing, then a DEC_RUN walk, in which each op launches.  The
+// sequence is written once, and every refusal of a call, whichever launcher raises it, precedes the call's first launch.
+enum : int { DEC_CHECK = 1, DEC_RUN = 2 };
+
+struct Step {
+  int mode;
+  hipStream_t st;
+  bool check() const { return mode == DEC_CHECK; }
+
+  int norm(const bf16_t* x, const bf16_t* w, bf16_t* y, int rows, int C, int64_t ldx, float eps) const {
+    return check() ? rmsnorm_check(x, w, y, rows, C, ldx, C) : rmsnorm_bf16(x, w, y, rows, C, ldx, C, eps, st);
+  }
+  int rows(const RowsArgs& a) const { return check() ? gemm_rows_check(a) : gemm_rows(a, st); }
+  int rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32, int rows, int Hq, int Hkv,
+           int D, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off) const {
+    const int64_t ld = (int64_t)(Hq + 2 * Hkv) * D;
+    return check() ? qk_norm_rope_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, kc, vc, 1, kv_stride, s_off)
+                   : qk_norm_rope(qkv, wq, wk, cosp, sinp, cs_is_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, kc, vc, 1, kv_stride, s_off, st);
+  }
+  int swiglu(const bf16_t* gu, bf16_t* act, int rows, int I) const {
+    return check() ? swiglu_check(gu, act, rows, I, 2 * I, I) : swiglu_bf16(gu, act, rows, I, 2 * I, I, st);
+  }
+  int attend(const AttnCall& a) const { return check() ? attention_check(a) : attention(a, st); }
+  // (decode_attention, decode_attention_kv8, kv_quantize_rows, lora_rows: launchers that take the walk's mode themselves)
+};
+
 // One projection of the step on a weight (w, scale) in `form`: the element type's product through the plan, codes (the step's
 // DecodeCfg::form) through the few-rows product on 1-byte or 4-bit weights (gemm_rows.hip).  pair: w = gate | up, y (rows, out / 2).
-// What the whole-stack step adds (the per-layer halves pass neither):
-//   check_only: the product's refusals alone, nothing launched -- gemm_rows_check, or the plan's own verdict;
-//   norm (w set): the RMSNorm that follows the product, asked for in the product's tail (RowsNorm: the non-pair form with a
-//     residual).  *normed says whether the launch carried it: yes where the few-rows kernel runs the product (always on codes and
-//     above 16 rows, else when the plan picks it) and takes the norm (gemm_rows_check); no: the caller launches rmsnorm_bf16.
-static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const void* scale, WForm form, const bf16_t* b, bf16_t* y,
-                      int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, hipStream_t st,
-                      bool check_only = false, const RowsNorm* norm = nullptr, bool* normed = nullptr) {
+// In a check walk: the product's refusals alone -- gemm_rows_check, or the plan's own verdict.
+// norm (w set; the whole-stack step's): the RMSNorm that follows the product, asked for in the product's tail (RowsNorm: the
+//   non-pair form with a residual).  *normed says whether the launch carried it: yes where the few-rows kernel runs the product
+//   (always on codes and above 16 rows, else when the plan picks it) and takes the norm (gemm_rows_check); no -- and in a check walk
+//   always -- the caller's next op is the norm itself.
+static int dec_linear(const Step& s, const bf16_t* x, int64_t ldx, const void* w, const void* scale, WForm form, const bf16_t* b, bf16_t* y,
+                      int64_t ldy, int rows, int in, int out, const bf16_t* R, int64_t ldr, bool pair, const RowsNorm* norm = nullptr,
+                      bool* normed = nullptr) {
   RowsArgs a;
   a.A = x; a.W = w; a.scale = scale; a.form = form; a.C = y; a.bias = b; a.R = R;
   a.M = rows; a.N = out; a.K = in;
@@ -206,9 +237,8 @@ static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const void* s
     if (!tail) a.norm = RowsNorm{};
   }
   if (form != WForm::ELEM || rows > 16) {
-    if (check_only) return gemm_rows_check(a);
-    const int e = gemm_rows(a, st);
-    if (normed) *normed = tail && e == U2_OK;
+    const int e = s.rows(a);
+    if (normed) *normed = tail && e == U2_OK && !s.check();
     return e;
   }
   GemmDesc g;  // 16-bit weights, M <= 16: the plan (the same kernel, or a tile kernel when rows16_ok says no)
@@ -216,28 +246,28 @@ static int dec_linear(const bf16_t* x, int64_t ldx, const void* w, const void* s
   g.M = rows; g.N = out; g.K = in;
   g.lda = ldx; g.ldb = in; g.ldc = ldy; g.ldr = ldr;
   g.flags = a.flags;
-  if (!check_only && !tail) return gemm_bf16(g, st);
+  if (!s.check() && !tail) return gemm_bf16(g, s.st);
   GemmDesc v = g;  // the plan's verdict without a launch
   GemmPlan p;
-  const Scratch sc = ctx().scratch_of(st);
+  const Scratch sc = ctx().scratch_of(s.st);
   int e = gemm_validate(v);
   if (e == U2_OK) e = gemm_plan(v, opts(), sc.p ? sc.bytes : 0, p);
-  if (e != U2_OK || check_only) return e;
-  if (p.nsteps != 1 || p.step[0].kind != GK_ROWS16) return gemm_bf16(g, st);  // (a tile kernel: no tail to carry the norm)
-  e = gemm_rows(a, st);  // the kernel the plan launches for this product, bit for bit, with the norm in its tail
+  if (e != U2_OK || s.check()) return e;
+  if (p.nsteps != 1 || p.step[0].kind != GK_ROWS16) return gemm_bf16(g, s.st);  // (a tile kernel: no tail to carry the norm)
+  e = gemm_rows(a, s.st);  // the kernel the plan launches for this product, bit for bit, with the norm in its tail
   if (normed) *normed = e == U2_OK;
   return e;
 }
 
 // The adapter group of one product of the step (DecodeLora; lora_rows.hip): u at the head of the branch's scratch, the group's
-// workspace behind it.  check_only: the refusals alone, for the checks that precede the step's first launch.
-static int dec_lora(const DecodeLora* lr, const LoraSeg* segs, int n, int nmax, const bf16_t* x, int64_t ldx, bf16_t* y, int64_t ldy, int rows,
-                    int in, bool check_only, hipStream_t st) {
+// workspace behind it.  No adapters, or none on this product: no op.
+static int dec_lora(const Step& s, const DecodeLora* lr, const LoraSeg* segs, int n, int nmax, const bf16_t* x, int64_t ldx, bf16_t* y,
+                    int64_t ldy, int rows, int in) {
   if (!lr || n == 0) return U2_OK;
   if (n < 0 || n > nmax || !lr->scratch || ((uintptr_t)lr->scratch & 15)) return U2_ERR_ARG;
   if (lr->scratch_bytes < DECODE_LORA_U_BYTES) return U2_ERR_WORKSPACE;
   return lora_rows(x, ldx, segs, n, reinterpret_cast<bf16_t*>(lr->scratch), DECODE_LORA_U_LD, y, ldy, rows, in,
-                   reinterpret_cast<char*>(lr->scratch) + DECODE_LORA_U_BYTES, lr->scratch_bytes - DECODE_LORA_U_BYTES, check_only, st);
+                   reinterpret_cast<char*>(lr->scratch) + DECODE_LORA_U_BYTES, lr->scratch_bytes - DECODE_LORA_U_BYTES, s.check(), s.st);
 }
 
 // What a quantised form asks of a step before anything is launched (WFormFacts): E, Hq D and I multiples of the form's step, and of
@@ -264,67 +294,59 @@ size_t decoder_decode_workspace_bytes(const DecodeCfg& c, int T) {
          256;
 }
 
-// What one call of a half does.  The per-layer entries check, then run (DEC_CHECK | DEC_RUN: today's two calls).  The whole-stack
-// step walks every half of every layer with DEC_CHECK alone -- the half's own refusals and, as nothing is launched behind them, those
-// its launchers would raise at their launch -- and only then runs them with DEC_RUN alone.
-enum : int { DEC_CHECK = 1, DEC_RUN = 2 };
+// The two walks of a per-layer entry (the whole-stack step makes them over all its layers: stack_walk)
+template <typename Half>
+static int check_then_run(hipStream_t st, const Half& half) {
+  const int e = half(Step{DEC_CHECK, st});
+  return e != U2_OK ? e : half(Step{DEC_RUN, st});
+}
 
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
 // (B, Hkv, 1, D) receive the new cache entries.  have_xn (the whole-stack step): the norm rode in the tail of the product that wrote x.
-static int dec_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
-                   bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes, hipStream_t st, int mode,
-                   bool have_xn) {
-  bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
-  const int nq = (c.Hq + 2 * c.Hkv) * c.D;
-  const DecodeLora* lr = l.lora;
-  int e = U2_OK;
-  if (mode & DEC_CHECK) {
+static int dec_pre(const Step& s, const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                   int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes, bool have_xn) {
+  if (s.check()) {  // the half's own refusals; everything below is a launcher's
     if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
     if (!wform_step_ok(c, l, 0, 1)) return U2_ERR_ARG;
     if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
-    e = lr ? dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, true, st) : U2_OK;
-    if (e != U2_OK) return e;
-    if (!(mode & DEC_RUN)) {
-      e = rmsnorm_check(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E);
-      if (e == U2_OK) e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st, true);
-      if (e == U2_OK) e = qk_norm_rope_check(qkv, l.wq_norm, l.wk_norm, cosp, sinp, c.B, c.Hq, c.Hkv, c.D, kc, vc, 1, kv_stride, s_off);
-      return e;
-    }
   }
-  if (!have_xn) e = rmsnorm_bf16(x, l.w_in_norm, xn, c.B, c.E, c.E, c.E, c.eps, st);
-  if (e != U2_OK) return e;
-  e = dec_linear(xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false, st);
-  if (e != U2_OK) return e;
-  if (lr) e = dec_lora(lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E, false, st);   // (before the head norm and the rotary embedding)
-  if (e != U2_OK) return e;
-  return qk_norm_rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, nq, cs_ld, c.qk_eps, kc, vc, 1, kv_stride,
-                      s_off, st);
+  bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
+  const int nq = (c.Hq + 2 * c.Hkv) * c.D;
+  const DecodeLora* lr = l.lora;
+  int e = have_xn ? U2_OK : s.norm(x, l.w_in_norm, xn, c.B, c.E, c.E, c.eps);
+  if (e == U2_OK) e = dec_linear(s, xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false);
+  if (e == U2_OK && lr) e = dec_lora(s, lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E);  // (before the head norm and the rotary embedding)
+  if (e == U2_OK) e = s.rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, cs_ld, c.qk_eps, kc, vc, kv_stride, s_off);
+  return e;
 }
 
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
                        int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes,
                        hipStream_t st) {
-  return dec_pre(c, l, x, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, false);
+  return check_then_run(st, [&](const Step& s) {
+    return dec_pre(s, c, l, x, cosp, sinp, cs_is_f32, cs_ld, qkv, kc, vc, kv_stride, s_off, ws, ws_bytes, false);
+  });
 }
 
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
 // (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention() launch pair per sequence -- B <= 16
-// only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG)
+// only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG.  q8: an e4m3 cache, decoder_decode_post_kv8)
 // The whole-stack step's tail norms -- ticket (null: none): the post-attention norm is asked for in the tail of the o product, and
 // `after` (w set: the norm that follows this layer -- the next layer's input norm or the stack's final one, into after->Yn) in the
 // tail of the down product; *after_done: that launch carried it.  A product followed by an adapter group keeps the norm's own
 // launch: the group adds to the product's rows after it.
-static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V, int T,
-                    int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st, int mode,
-                    uint32_t* ticket, const RowsNorm* after, bool* after_done, const DecodeKv8* q8 = nullptr) {
-  if (mode & DEC_CHECK) {
+static int dec_post(const Step& s, const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
+                    int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, uint32_t* ticket,
+                    const RowsNorm* after, bool* after_done, const DecodeKv8* q8 = nullptr) {
+  if (s.check()) {  // the half's own refusals; everything below is a launcher's
     if (c.B <= 0 || c.B > 64 || (c.B > 16 && !batched) || c.Hkv <= 0 || T <= 0 || !x || !qkv || (!q8 && (!K || !V)) || !l.Wo || !l.w_post_norm || !l.Wgu || !l.Wdown || !out ||
         !ws)
       return U2_ERR_ARG;
     if (batched ? c.Hq / c.Hkv > 16 || ((uintptr_t)kv_start & 3) : kv_start != nullptr) return U2_ERR_ARG;
-    if (!wform_step_ok(c, l, 1, 3)) return U2_ERR_ARG;  // (everything the quantised products ask, before the attention is launched)
+    if (!wform_step_ok(c, l, 1, 3)) return U2_ERR_ARG;
     if (ws_bytes < decoder_decode_workspace_bytes(c, T)) return U2_ERR_WORKSPACE;
+    if (q8 && (!batched || q8->k_first < 0 || q8->s_off < q8->k_first || T != q8->s_off - q8->k_first + 1)) return U2_ERR_ARG;
   }
   const int g = c.Hq / c.Hkv, nq = (c.Hq + 2 * c.Hkv) * c.D, qd = c.Hq * c.D;
   bf16_t* p = reinterpret_cast<bf16_t*>(ws);
@@ -336,104 +358,71 @@ static int dec_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, c
   size_t used = ((size_t)c.B * ((size_t)3 * c.E + qd + (size_t)3 * c.I) * sizeof(bf16_t) + 255) & ~(size_t)255;
   char* aws = reinterpret_cast<char*>(ws) + used;
   const size_t aws_bytes = ws_bytes - used;
-  const float scale = c.scale;
   if (kv_stride == 0) kv_stride = (int64_t)T * c.D;
-  // an e4m3 cache (decoder_decode_post_kv8): the step's rows into position s_off, the attention over positions k_first .. s_off
-  auto kv8_quantise = [&](bool check_only) {
-    return kv_quantize_rows(q8->k_new, q8->v_new, c.B, c.Hkv, 1, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, q8->Kc,
-                            q8->Vc, q8->Ks, q8->Vs, q8->capacity, q8->s_off, check_only, st);
-  };
-  auto kv8_attention = [&](bool check_only) {
-    return decode_attention_kv8(qkv, q8->Kc + (int64_t)q8->k_first * c.D, q8->Vc + (int64_t)q8->k_first * c.D, q8->Ks + q8->k_first,
-                                q8->Vs + q8->k_first, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, (int64_t)q8->capacity * c.D, q8->capacity, qd, scale,
-                                kv_start, aws, aws_bytes, check_only, st);
-  };
   const DecodeLora* lr = l.lora;
-  const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
-  const bool gu_pair = !gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15);  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
-  if (mode & DEC_CHECK) {
-    if (q8) {  // (both launchers' refusals, before either launch)
-      if (!batched || q8->k_first < 0 || q8->s_off < q8->k_first || T != q8->s_off - q8->k_first + 1) return U2_ERR_ARG;
-      int e = kv8_quantise(true);
-      if (e == U2_OK) e = kv8_attention(true);
-      if (e != U2_OK) return e;
-    } else if (kv_stride < (int64_t)T * c.D || (kv_stride & 7)) return U2_ERR_ARG;
-    if (lr) {  // (the adapter groups: every refusal before the attention is launched)
-      int e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, true, st);
-      if (e == U2_OK) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, true, st);
-      if (e == U2_OK) e = dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, true, st);
-      if (e != U2_OK) return e;
-    }
-    if (!(mode & DEC_RUN)) {
-      // (the attention's own: 16-byte aligned q / K / V and partials, 32-bit offsets inside a (batch, kv head) entry)
-      if (q8) return U2_ERR_ARG;  // (the whole-stack walk does not take an e4m3 cache)
-      if ((((uintptr_t)qkv | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ws) & 15) || (int64_t)T * c.D * 2 >= (1ll << 31) || !(scale > 0.f)) return U2_ERR_ARG;
-      int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st, true);
-      if (e == U2_OK) e = rmsnorm_check(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E);
-      if (e == U2_OK)
-        e = gu_pair ? dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st, true)
-                    : dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st, true);
-      if (e == U2_OK) e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st, true);
-      return e;
-    }
-  }
-  if (q8) {
-    int e = kv8_quantise(false);
-    if (e == U2_OK) e = kv8_attention(false);
-    if (e != U2_OK) return e;
+  int e = U2_OK;
+  if (q8) {  // the step's rows into position s_off as codes, then the attention over positions k_first .. s_off
+    e = kv_quantize_rows(q8->k_new, q8->v_new, c.B, c.Hkv, 1, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, q8->Kc, q8->Vc,
+                         q8->Ks, q8->Vs, q8->capacity, q8->s_off, s.check(), s.st);
+    if (e == U2_OK)
+      e = decode_attention_kv8(qkv, q8->Kc + (int64_t)q8->k_first * c.D, q8->Vc + (int64_t)q8->k_first * c.D, q8->Ks + q8->k_first,
+                               q8->Vs + q8->k_first, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, (int64_t)q8->capacity * c.D, q8->capacity, qd, c.scale,
+                               kv_start, aws, aws_bytes, s.check(), s.st);
   } else if (batched) {
-    const int e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, scale, kv_start, aws, aws_bytes, st);
-    if (e != U2_OK) return e;
+    e = decode_attention(qkv, K, V, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, kv_stride, qd, c.scale, kv_start, aws, aws_bytes, s.check(), s.st);
+  } else {
+    // attention() is every caller's launcher and asks less of a cache than decode_attention: a scale that is not positive, a
+    // (batch, kv head) entry shorter than its T rows or past 32-bit offsets stay the step's to refuse, where the whole-stack walk
+    // has always refused them, so that a call's status does not depend on the attention it asks for
+    if (s.check() && (!(c.scale > 0.f) || kv_stride < (int64_t)T * c.D || (int64_t)T * c.D * 2 >= (1ll << 31))) return U2_ERR_ARG;
+    for (int b = 0; b < c.B && e == U2_OK; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
+      AttnCall a;
+      a.q = qkv + (size_t)b * nq; a.k = K + (size_t)b * c.Hkv * kv_stride; a.v = V + (size_t)b * c.Hkv * kv_stride;
+      a.out = ctx + (size_t)b * qd;
+      a.nb = c.Hkv; a.Sq = 1; a.Skv = T; a.H = g; a.Hkv = 1; a.d = c.D;
+      a.ldq = a.ldo = a.q_bs = a.o_bs = (int64_t)g * c.D; a.ldk = a.ldv = c.D; a.k_bs = a.v_bs = kv_stride;
+      a.scale = c.scale; a.ws = aws; a.ws_bytes = aws_bytes;
+      e = s.attend(a);
+    }
   }
-  for (int b = 0; b < c.B && !batched && !q8; ++b) {  // entries of one batch element: its kv heads; the g query heads of a group are the "heads"
-    AttnCall a;
-    a.q = qkv + (size_t)b * nq; a.k = K + (size_t)b * c.Hkv * kv_stride; a.v = V + (size_t)b * c.Hkv * kv_stride;
-    a.out = ctx + (size_t)b * qd;
-    a.nb = c.Hkv; a.Sq = 1; a.Skv = T; a.H = g; a.Hkv = 1; a.d = c.D;
-    a.ldq = a.ldo = a.q_bs = a.o_bs = (int64_t)g * c.D; a.ldk = a.ldv = c.D; a.k_bs = a.v_bs = kv_stride;
-    a.scale = scale; a.ws = aws; a.ws_bytes = aws_bytes;
-    const int e = attention(a, st);
-    if (e != U2_OK) return e;
-  }
+  if (e != U2_OK) return e;
   RowsNorm o_norm;
   if (ticket && !(lr && lr->n_o != 0)) o_norm.w = l.w_post_norm, o_norm.Yn = hn, o_norm.ld = c.E, o_norm.eps = c.eps, o_norm.ticket = ticket;
   bool normed = false;
-  int e = dec_linear(ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, st, false, &o_norm, &normed);
+  e = dec_linear(s, ctx, qd, l.Wo, l.scale_o, c.form, l.bo, h, c.E, c.B, qd, c.E, x, c.E, false, &o_norm, &normed);
+  if (e == U2_OK && lr) e = dec_lora(s, lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd);   // (after the residual epilogue: the same terms)
+  if (e == U2_OK && !normed) e = s.norm(h, l.w_post_norm, hn, c.B, c.E, c.E, c.eps);
   if (e != U2_OK) return e;
-  if (lr) e = dec_lora(lr, lr->o, lr->n_o, 1, ctx, qd, h, c.E, c.B, qd, false, st);   // (after the residual epilogue: the same terms)
-  if (e != U2_OK) return e;
-  if (!normed) e = rmsnorm_bf16(h, l.w_post_norm, hn, c.B, c.E, c.E, c.E, c.eps, st);
-  if (e != U2_OK) return e;
-  if (gu_pair) {
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true, st);
-    if (e != U2_OK) return e;
+  const bool gu_lora = lr && lr->n_gu != 0;   // a gate or up adapter: the pair product in its unfused form, the group before the SiLU
+  if (!gu_lora && !l.bgu && !(c.E & 63) && !(c.I & 15)) {  // SiLU(gate) * up in the epilogue of the pair product (gemm_rows16_kernel<., true>)
+    e = dec_linear(s, hn, c.E, l.Wgu, l.scale_gu, c.form, nullptr, act, c.I, c.B, c.E, 2 * c.I, nullptr, 0, true);
   } else {
-    e = dec_linear(hn, c.E, l.Wgu, l.scale_gu, c.form, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false, st);
-    if (e != U2_OK) return e;
-    if (gu_lora) e = dec_lora(lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E, false, st);
-    if (e != U2_OK) return e;
-    e = swiglu_bf16(gu, act, c.B, c.I, 2 * c.I, c.I, st);
-    if (e != U2_OK) return e;
+    e = dec_linear(s, hn, c.E, l.Wgu, l.scale_gu, c.form, l.bgu, gu, 2 * c.I, c.B, c.E, 2 * c.I, nullptr, 0, false);
+    if (e == U2_OK && gu_lora) e = dec_lora(s, lr, lr->gu, lr->n_gu, 2, hn, c.E, gu, 2 * c.I, c.B, c.E);
+    if (e == U2_OK) e = s.swiglu(gu, act, c.B, c.I);
   }
+  if (e != U2_OK) return e;
   const bool down_tail = ticket && after && !(lr && lr->n_down != 0);
-  e = dec_linear(act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, st, false, down_tail ? after : nullptr,
-                 after_done);
-  if (e != U2_OK || !lr) return e;
-  return dec_lora(lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I, false, st);
+  e = dec_linear(s, act, c.I, l.Wdown, l.scale_down, c.form, l.bdown, out, c.E, c.B, c.I, c.E, h, c.E, false, down_tail ? after : nullptr, after_done);
+  if (e == U2_OK && lr) e = dec_lora(s, lr, lr->down, lr->n_down, 1, act, c.I, out, c.E, c.B, c.I);
+  return e;
 }
 
 int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const bf16_t* K, const bf16_t* V,
                         int T, int64_t kv_stride, bool batched, const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes,
                         hipStream_t st) {
-  return dec_post(c, l, x, qkv, K, V, T, kv_stride, batched, kv_start, out, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, nullptr, nullptr, nullptr);
+  return check_then_run(st, [&](const Step& s) {
+    return dec_post(s, c, l, x, qkv, K, V, T, kv_stride, batched, kv_start, out, ws, ws_bytes, nullptr, nullptr, nullptr);
+  });
 }
 
 int decoder_decode_post_kv8(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const DecodeKv8& kv,
                             const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
   const int64_t T = (int64_t)kv.s_off - kv.k_first + 1;
   if (T <= 0 || T > 0x7fffffff) return U2_ERR_ARG;
-  return dec_post(c, l, x, qkv, nullptr, nullptr, (int)T, 0, true, kv_start, out, ws, ws_bytes, st, DEC_CHECK | DEC_RUN, nullptr, nullptr,
-                  nullptr, &kv);
+  return check_then_run(st, [&](const Step& s) {
+    return dec_post(s, c, l, x, qkv, nullptr, nullptr, (int)T, 0, true, kv_start, out, ws, ws_bytes, nullptr, nullptr, nullptr, &kv);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ one decode step of the stack
@@ -462,19 +451,24 @@ size_t decoder_decode_stack_workspace_bytes(const DecodeStackLayer* L, int n) {
   return 256 + stack_layer_ws(L, n) + stack_qkv_bytes(L, n) + 2 * stack_hidden_bytes(L[0].cfg);
 }
 
-// passes: DEC_CHECK | DEC_RUN is the step; the step with the head asks for the two walks one at a time, its head's checks between them
-static int stack_walk(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
-                      bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
-                      size_t ws_bytes, hipStream_t st, int passes) {
-  if (!L || n <= 0 || !x || !out || !ws || ((uintptr_t)ws & 255)) return U2_ERR_ARG;
-  const DecodeCfg& c0 = L[0].cfg;
-  for (int i = 0; i < n; ++i) {
-    const DecodeStackLayer& s = L[i];
-    if (s.cfg.B != c0.B || s.cfg.E != c0.E || s.T <= 0 || s.k_first < 0 || s.s_off < 0 || (int64_t)s.k_first + s.T > (int64_t)s.s_off + 1) return U2_ERR_ARG;
+// One walk over every half of every layer: the step is the check walk, then the run walk; the step with the head puts its head's
+// walks behind each of the two.
+static int stack_walk(const Step& s, const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
+                      int64_t cs_ld, bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out,
+                      void* ws, size_t ws_bytes) {
+  if (s.check()) {
+    if (!L || n <= 0 || !x || !out || !ws || ((uintptr_t)ws & 255)) return U2_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+      const DecodeStackLayer& sl = L[i];
+      if (sl.cfg.B != L[0].cfg.B || sl.cfg.E != L[0].cfg.E || sl.T <= 0 || sl.k_first < 0 || sl.s_off < 0 ||
+          (int64_t)sl.k_first + sl.T > (int64_t)sl.s_off + 1)
+        return U2_ERR_ARG;
+    }
+    const size_t need = decoder_decode_stack_workspace_bytes(L, n);
+    if (need == 0) return U2_ERR_ARG;
+    if (ws_bytes < need) return U2_ERR_WORKSPACE;
   }
-  const size_t need = decoder_decode_stack_workspace_bytes(L, n);
-  if (need == 0) return U2_ERR_ARG;
-  if (ws_bytes < need) return U2_ERR_WORKSPACE;
+  const DecodeCfg& c0 = L[0].cfg;
   char* base = reinterpret_cast<char*>(ws);
   uint32_t* ticket = tail_norm ? reinterpret_cast<uint32_t*>(base) : nullptr;
   void* lws = base + 256;
@@ -484,35 +478,27 @@ static int stack_walk(const DecodeStackLayer* L, int n, const bf16_t* x, const v
   hid[0] = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(qkv) + stack_qkv_bytes(L, n));
   hid[1] = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(hid[0]) + stack_hidden_bytes(c0));
   bf16_t* xn = reinterpret_cast<bf16_t*>(lws);  // (where every layer's first half keeps its normed input: dec_pre)
+  const bf16_t* cur = x;
   bool have_xn = false;
-  for (int pass = DEC_CHECK; pass <= DEC_RUN; ++pass) {  // every refusal of every layer, then every launch
-    if (!(passes & pass)) continue;
-    const bf16_t* cur = x;
-    for (int i = 0; i < n; ++i) {
-      const DecodeStackLayer& s = L[i];
-      const bool last = i == n - 1;
-      bf16_t* nxt = last && !w_final ? out : hid[i & 1];
-      int e = dec_pre(s.cfg, s.layer, cur, cosp, sinp, cs_is_f32, cs_ld, qkv, s.kc, s.vc, s.kv_stride, s.s_off, lws, lws_bytes, st, pass, have_xn);
-      if (e != U2_OK) return e;   // (a null cache buffer among them: nothing below offsets one)
-      RowsNorm after;  // the norm that follows the layer: the next layer's input norm into its xn, or the final norm into out
-      if (!last) after.w = L[i + 1].layer.w_in_norm, after.Yn = xn, after.eps = L[i + 1].cfg.eps;
-      else if (w_final) after.w = w_final, after.Yn = out, after.eps = final_eps;
-      after.ld = c0.E;
-      after.ticket = ticket;
-      bool done = false;
-      const int64_t first = (int64_t)s.k_first * s.cfg.D;
-      e = dec_post(s.cfg, s.layer, cur, qkv, s.kc + first, s.vc + first, s.T, s.kv_stride, batched, kv_start, nxt, lws, lws_bytes, st, pass,
-                   ticket, after.w ? &after : nullptr, &done);
-      if (e != U2_OK) return e;
-      have_xn = done && !last;
-      if (last && w_final) {
-        if (pass == DEC_CHECK) e = rmsnorm_check(nxt, w_final, out, c0.B, c0.E, c0.E, c0.E);
-        else if (!done) e = rmsnorm_bf16(nxt, w_final, out, c0.B, c0.E, c0.E, c0.E, final_eps, st);
-        if (e != U2_OK) return e;
-      }
-      cur = nxt;
-    }
-    have_xn = false;
+  for (int i = 0; i < n; ++i) {
+    const DecodeStackLayer& sl = L[i];
+    const bool last = i == n - 1;
+    bf16_t* nxt = last && !w_final ? out : hid[i & 1];
+    int e = dec_pre(s, sl.cfg, sl.layer, cur, cosp, sinp, cs_is_f32, cs_ld, qkv, sl.kc, sl.vc, sl.kv_stride, sl.s_off, lws, lws_bytes, have_xn);
+    if (e != U2_OK) return e;   // (a null cache buffer among them: nothing below offsets one)
+    RowsNorm after;  // the norm that follows the layer: the next layer's input norm into its xn, or the final norm into out
+    if (!last) after.w = L[i + 1].layer.w_in_norm, after.Yn = xn, after.eps = L[i + 1].cfg.eps;
+    else if (w_final) after.w = w_final, after.Yn = out, after.eps = final_eps;
+    after.ld = c0.E;
+    after.ticket = ticket;
+    bool done = false;  // the down product's tail carried `after` (never in a check walk: the norm's own refusals are asked for)
+    const int64_t first = (int64_t)sl.k_first * sl.cfg.D;
+    e = dec_post(s, sl.cfg, sl.layer, cur, qkv, sl.kc + first, sl.vc + first, sl.T, sl.kv_stride, batched, kv_start, nxt, lws, lws_bytes, ticket,
+                 after.w ? &after : nullptr, &done);
+    if (e == U2_OK && last && w_final && !done) e = s.norm(nxt, w_final, out, c0.B, c0.E, c0.E, final_eps);
+    if (e != U2_OK) return e;
+    have_xn = done && !last;
+    cur = nxt;
   }
   return U2_OK;
 }
@@ -520,8 +506,9 @@ static int stack_walk(const DecodeStackLayer* L, int n, const bf16_t* x, const v
 int decoder_decode_stack(const DecodeStackLayer* L, int n, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32, int64_t cs_ld,
                          bool batched, const int* kv_start, const bf16_t* w_final, float final_eps, bool tail_norm, bf16_t* out, void* ws,
                          size_t ws_bytes, hipStream_t st) {
-  return stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, w_final, final_eps, tail_norm, out, ws, ws_bytes, st,
-                    DEC_CHECK | DEC_RUN);
+  return check_then_run(st, [&](const Step& s) {
+    return stack_walk(s, L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, w_final, final_eps, tail_norm, out, ws, ws_bytes);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ the head of a decode step
@@ -542,29 +529,25 @@ static RowsArgs head_rows(const DecodeHead& h, const bf16_t* xn, int B, float* l
   return a;
 }
 
-// (every refusal of the head, nothing launched: its own, the norm's, the product's)
-static int head_check(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes) {
-  if (!wform_known(h.form) || B <= 0 || B > 64 || h.E <= 0 || h.V < 2 || !x || !h.w_norm || !h.W || !logits || !ws || ((uintptr_t)ws & 15))
-    return U2_ERR_ARG;
-  if (h.form != WForm::ELEM && !h.scale) return U2_ERR_ARG;
-  if (ldx < h.E || ldl < h.V) return U2_ERR_ARG;
+// (a check walk: every refusal of the head, nothing launched -- its own, the norm's, the product's)
+static int head_walk(const Step& s, const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes) {
+  if (s.check()) {
+    if (!wform_known(h.form) || B <= 0 || B > 64 || h.E <= 0 || h.V < 2 || !x || !h.w_norm || !h.W || !logits || !ws || ((uintptr_t)ws & 15))
+      return U2_ERR_ARG;
+    if (h.form != WForm::ELEM && !h.scale) return U2_ERR_ARG;
+    if (ldx < h.E || ldl < h.V) return U2_ERR_ARG;
+  }
   bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
-  int e = rmsnorm_check(x, h.w_norm, xn, B, h.E, ldx, h.E);
-  if (e == U2_OK) e = gemm_rows_check(head_rows(h, xn, B, logits, ldl));
-  if (e != U2_OK) return e;
-  return ws_bytes < decode_head_workspace_bytes(B, h.E) ? U2_ERR_WORKSPACE : U2_OK;
-}
-
-static int head_run(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, hipStream_t st) {
-  bf16_t* xn = reinterpret_cast<bf16_t*>(ws);
-  const int e = rmsnorm_bf16(x, h.w_norm, xn, B, h.E, ldx, h.E, h.eps, st);
-  return e != U2_OK ? e : gemm_rows(head_rows(h, xn, B, logits, ldl), st);
+  int e = s.norm(x, h.w_norm, xn, B, h.E, ldx, h.eps);
+  if (e == U2_OK) e = s.rows(head_rows(h, xn, B, logits, ldl));
+  // (the workspace's size behind the launchers' refusals: the order in which the head has always answered)
+  if (e == U2_OK && s.check() && ws_bytes < decode_head_workspace_bytes(B, h.E)) e = U2_ERR_WORKSPACE;
+  return e;
 }
 
 int decode_head(const DecodeHead& h, const bf16_t* x, int64_t ldx, int B, float* logits, int64_t ldl, void* ws, size_t ws_bytes,
                 hipStream_t st) {
-  const int e = head_check(h, x, ldx, B, logits, ldl, ws, ws_bytes);
-  return e != U2_OK ? e : head_run(h, x, ldx, B, logits, ldl, ws, st);
+  return check_then_run(st, [&](const Step& s) { return head_walk(s, h, x, ldx, B, logits, ldl, ws, ws_bytes); });
 }
 
 // The whole-stack step followed by the head, in one call: out (B, E) receives the last layer's hidden rows as they are (the stack
@@ -585,10 +568,10 @@ int decoder_decode_stack_head(const DecodeStackLayer* L, int n, const bf16_t* x,
   if (ws_bytes < sb) return U2_ERR_WORKSPACE;
   const int B = L[0].cfg.B;
   void* hws = reinterpret_cast<char*>(ws) + sb;
-  int e = stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, nullptr, 0.f, tail_norm, out, ws, sb, st, DEC_CHECK);
-  if (e == U2_OK) e = head_check(h, out, h.E, B, logits, ldl, hws, ws_bytes - sb);
-  if (e == U2_OK) e = stack_walk(L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, nullptr, 0.f, tail_norm, out, ws, sb, st, DEC_RUN);
-  return e != U2_OK ? e : head_run(h, out, h.E, B, logits, ldl, hws, st);
+  return check_then_run(st, [&](const Step& s) {
+    const int e = stack_walk(s, L, n, x, cosp, sinp, cs_is_f32, cs_ld, batched, kv_start, nullptr, 0.f, tail_norm, out, ws, sb);
+    return e != U2_OK ? e : head_walk(s, h, out, h.E, B, logits, ldl, hws, ws_bytes - sb);
+  });
 }
 
 }  // namespace u2

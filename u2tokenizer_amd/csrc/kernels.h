@@ -330,6 +330,7 @@ struct AttnCall {
   int window = 0;              // W > 0 (causal): ... and only if j > i + Skv - Sq - W
 };
 int attention(const AttnCall& c, hipStream_t stream);
+int attention_check(const AttnCall& c);  // every refusal of attention(c, .), nothing launched
 // tok_attention_supported: the plain form takes these shapes / strides (pipeline.hip falls back to the GEMM chain otherwise)
 bool tok_attention_supported(const AttnCall& c);
 size_t tok_attention_workspace_bytes(int nb, int H, int Sq, int Skv, int d);
@@ -363,6 +364,7 @@ int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* co
                  int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int S,
                  int64_t kv_stride, int s_off, hipStream_t stream);
 int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out, hipStream_t stream);
+int swiglu_check(const bf16_t* gu, const bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out);  // its refusals alone
 struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
   int B, E, Hq, Hkv, D, I;
   float eps, qk_eps, scale;
@@ -451,11 +453,12 @@ int decoder_decode_stack_head(const DecodeStackLayer* L, int n, const bf16_t* x,
 // ------------------------------------------------------------------ batched decode attention (decode_attn.hip)
 // One query row per sequence over its KV cache, all B sequences and heads in one launch (+ one merge of the key splits):
 // q / out (B, Hq * D) rows with ldq / ldo elements between sequences, K / V (B, Hkv, T, D) with kv_stride elements between
-// (batch, kv head) entries; key j of sequence b is visible iff j >= kv_start[b] (NULL: all).
+// (batch, kv head) entries; key j of sequence b is visible iff j >= kv_start[b] (NULL: all).  check_only: every refusal of the
+// call, nothing launched.
 size_t decode_attention_workspace_bytes(int B, int Hq, int Hkv, int T, int D);
 int decode_attention(const bf16_t* q, const bf16_t* K, const bf16_t* V, bf16_t* out, int B, int Hq, int Hkv, int T, int D,
                      int64_t ldq, int64_t kv_stride, int64_t ldo, float scale, const int* kv_start, void* ws, size_t ws_bytes,
-                     hipStream_t stream);
+                     bool check_only, hipStream_t stream);
 // ---- the FP8 (e4m3) KV cache (decode_attn.hip): codes (B, Hkv, capacity, D) bytes and ONE fp32 scale per cache row, (B, Hkv,
 // capacity); value = code x scale.  kv_quantize_rows: the 16-bit rows k / v (B, Hkv, n, D; *_bs / *_hs / *_rs elements between
 // sequences / heads / positions, multiples of 8) as codes and scales at positions s_off .. s_off + n - 1 of dense buffers, one

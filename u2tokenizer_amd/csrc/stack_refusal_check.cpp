@@ -73,6 +73,34 @@ int main() {
     expect("adapter count out of range", call(L, n, need, tail), U2TOK_ERR_ARG);
     lay[2].lora = nullptr;
   }
+  // ---- faults that only a launcher's own check sees (the step's own refusals pass them): the whole-stack step and the per-layer
+  // second half, per sequence and batched, answer from the walk that precedes their first launch.  (Before the per-layer entries
+  // walked twice, u2tok_decoder_decode_post answered these from a launch -- run once on that commit, without a GPU: -2, U2TOK_ERR_LAUNCH,
+  // for every one of them but the scale of 0 with `batched`, which the batched attention, the first launcher, refused itself.)
+  {
+    char* Pc = mem;
+    const size_t lneed = u2tok_decoder_decode_workspace_bytes(&cfg[0], T);
+    auto everywhere = [&](const char* what) {
+      expect(what, call(L, n, need, 0), U2TOK_ERR_ARG);
+      expect(what, call(L, n, need, 1), U2TOK_ERR_ARG);
+      for (int batched = 0; batched < 2; ++batched)
+        expect(what, u2tok_decoder_decode_post(&cfg[1], &lay[1], P, P, P, P, T, 256 * 64, batched, nullptr, P, P, lneed, nullptr), U2TOK_ERR_ARG);
+    };
+    lay[1].Wdown = Pc + 8;
+    everywhere("16-bit Wdown 8 bytes off alignment");
+    lay[1].Wdown = P;
+    lay[1].Wo = Pc + 8;
+    everywhere("16-bit Wo 8 bytes off alignment");
+    lay[1].Wo = P;
+    lay[1].bgu = P;  // a gate|up bias: the product un-paired, SwiGLU a launch of its own, the down product behind it
+    lay[1].Wdown = Pc + 8;
+    everywhere("un-paired gate|up, Wdown 8 bytes off alignment");
+    lay[1].Wdown = P;
+    lay[1].bgu = nullptr;
+    cfg[1].scale = 0.f;
+    everywhere("a scale of 0");
+    cfg[1].scale = 0.125f;
+  }
   expect("workspace bytes of no layers", (long long)u2tok_decoder_decode_stack_workspace_bytes(L, 0), 0);
   expect("workspace bytes of null layers", (long long)u2tok_decoder_decode_stack_workspace_bytes(nullptr, n), 0);
   std::vector<u2tok_decode_stack_layer> many(64, L[0]);

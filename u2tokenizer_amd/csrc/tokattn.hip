@@ -888,13 +888,20 @@ static void tok_attn_launch(const TokAttnArgs& a, int d, int wide, unsigned grid
   tok_attn_launch_d<64, EX, BAND>(a, wide, grid, stream);
 }
 
-int attention(const AttnCall& c, hipStream_t stream) {
-  const AttnForm form = attn_form(c);
-  if (!attn_call_ok(c, form)) return U2_ERR_ARG;
+// What a call's launch is sized by, behind every refusal of the call: its form, the key splits (ns of tps tiles each) and the grid.
+struct AttnShape {
+  AttnForm form;
+  int tps, ns;
+  int64_t grid;
+};
+
+static int attn_shape(const AttnCall& c, AttnShape& s) {
+  s.form = attn_form(c);
+  if (!attn_call_ok(c, s.form)) return U2_ERR_ARG;
   const int nb = c.nb, Sq = c.Sq, Skv = c.Skv, H = c.H, d = c.d;
   const int ntile = (int)cdiv(Skv, tok_attn_bk(d));
   int ns = 1;  // (a causal unit's key range depends on its query block: no key splits; prefill has enough units)
-  if (form == ATTN_PLAIN && !c.causal) {
+  if (s.form == ATTN_PLAIN && !c.causal) {
     const size_t fit = c.ws ? c.ws_bytes / tok_attn_split_bytes(nb, H, Sq, d) : 0;  // splits whose partial results the scratch holds
     ns = c.force_splits > 0 ? std::min(c.force_splits, ntile)
                             : std::max((int)std::min<size_t>(tok_attn_want_splits(nb, H, Sq, Skv, d), fit), 1);
@@ -903,6 +910,22 @@ int attention(const AttnCall& c, hipStream_t stream) {
       ns = 1;
     }
   }
+  s.tps = (int)cdiv(ntile, ns);
+  s.ns = (int)cdiv(ntile, s.tps);  // no empty splits
+  s.grid = (int64_t)nb * H * cdiv(Sq, 64) * s.ns;
+  return s.grid > 0x7fffffff ? U2_ERR_ARG : U2_OK;
+}
+
+int attention_check(const AttnCall& c) {
+  AttnShape s;
+  return attn_shape(c, s);
+}
+
+int attention(const AttnCall& c, hipStream_t stream) {
+  AttnShape s;
+  if (const int e = attn_shape(c, s)) return e;
+  const AttnForm form = s.form;
+  const int nb = c.nb, Sq = c.Sq, Skv = c.Skv, H = c.H, d = c.d;
   TokAttnArgs a;
   a.q = c.q; a.k = c.k; a.v = c.v; a.out = c.out;
   a.ldq = c.ldq; a.ldk = c.ldk; a.ldv = c.ldv; a.ldo = c.ldo; a.q_bs = c.q_bs; a.k_bs = c.k_bs; a.v_bs = c.v_bs; a.o_bs = c.o_bs;
@@ -913,21 +936,19 @@ int attention(const AttnCall& c, hipStream_t stream) {
   a.causal = c.causal ? 1 : 0;
   a.kv_len = c.kv_len; a.kv_start = c.kv_start; a.lse = c.lse; a.lse_ld = c.lse_ld;
   a.k_hs = c.k_hs ? c.k_hs : d; a.v_hs = c.v_hs ? c.v_hs : d; a.window = c.window;
-  a.tps = (int)cdiv(ntile, ns);
-  a.ns = (int)cdiv(ntile, a.tps);  // no empty splits
+  a.tps = s.tps; a.ns = s.ns;
   a.opart = nullptr; a.ml = nullptr;
   if (a.ns > 1) {
     a.opart = reinterpret_cast<float*>(c.ws);
     a.ml = a.opart + (size_t)a.ns * nb * Sq * H * d;
   }
-  const int64_t grid = (int64_t)nb * H * a.nqb * a.ns;
-  if (grid > 0x7fffffff) return U2_ERR_ARG;
+  const unsigned grid = (unsigned)s.grid;
   ProfScope ps(PROF_TOKATTN, (c.causal ? 2.0 : 4.0) * nb * H * (double)Sq * Skv * d, stream,
                2.0 * nb * d * (2.0 * Sq * H + 2.0 * Skv * c.Hkv));  // q, k, v read + o written, once
   if (form == ATTN_PLAIN) {
     int wide = (d == 256 || d == 512) && !c.causal ? opts().tok_wide : 0;  // (tok_attn2_kernel is not built for 384)
     if (wide == 2 && ((int64_t)Skv * c.ldk >= (1ll << 29) || (int64_t)Skv * c.ldv >= (1ll << 29))) wide = 1;  // (past its buffer offsets)
-    tok_attn_launch<false, false>(a, d, wide, (unsigned)grid, stream);
+    tok_attn_launch<false, false>(a, d, wide, grid, stream);
     if (a.ns > 1) {
       const int64_t total = (int64_t)nb * Sq * (H * d / 4);
       const dim3 cg((unsigned)cdiv(total, 256));
@@ -939,9 +960,9 @@ int attention(const AttnCall& c, hipStream_t stream) {
 #undef U2_CMB
     }
   } else if (form == ATTN_RANGE) {
-    tok_attn_launch<true, false>(a, d, 0, (unsigned)grid, stream);
+    tok_attn_launch<true, false>(a, d, 0, grid, stream);
   } else {
-    tok_attn_launch<true, true>(a, d, 0, (unsigned)grid, stream);
+    tok_attn_launch<true, true>(a, d, 0, grid, stream);
   }
   return launch_status();
 }
