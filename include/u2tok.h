@@ -272,6 +272,22 @@ int u2tok_gemm_bf16(const void* A, const void* B, void* C, const void* bias, con
                     int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int32_t nz, int32_t nbh,
                     int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, int64_t sRb,
                     int64_t sRh, float alpha, int32_t flags, u2tok_stream_t stream);
+/* u2tok_gemm_bf16 with the column split and the transposed side output of the ViT's q|k|v product:
+ *   - nsplit (a multiple of 16, not with flag 512): columns n < nsplit are scaled by alpha_lo instead of alpha, from the fp32
+ *     accumulator and before the bias -- once, whatever kernel and however many K slices the product takes;
+ *   - vt != NULL: columns n >= vt_n0 of the many-row part of the product are NOT written to C (those elements of C are left
+ *     untouched) but, transposed, to vt[m / vt_rows][n - vt_n0][perm16(m % vt_rows)] (bf16; row stride vt_ld keys, chunk stride
+ *     vt_bs elements), perm16 = the key order of u2tok_transpose_bf16(..., perm16 = 1): inside every group of 16 keys
+ *     [0-3, 8-11, 4-7, 12-15].  Rows past the last multiple of 256 (<= 16: the ViT's cls rows) are written whole to C.
+ *     Only the deep 256 x 192 big-tile forms have it: plain bf16 output (flags 0, nz 1), the heuristic route (option gemm_big 0),
+ *     vt_n0 and N - vt_n0 multiples of 192, nsplit <= vt_n0, vt_rows a multiple of 256 that divides the many-row part, vt 16-byte
+ *     aligned, vt_ld >= vt_rows, vt_bs >= (N - vt_n0) * vt_ld, both multiples of 8; U2TOK_ERR_ARG otherwise, before any launch.
+ * With nsplit = 0, alpha_lo = 1 and vt = NULL this is u2tok_gemm_bf16: the same kernels, the same bits. */
+int u2tok_gemm_bf16_ex(const void* A, const void* B, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                       int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int32_t nz, int32_t nbh,
+                       int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, int64_t sRb,
+                       int64_t sRh, float alpha, int32_t flags, int32_t nsplit, float alpha_lo, void* vt, int32_t vt_n0,
+                       int32_t vt_rows, int64_t vt_ld, int64_t vt_bs, u2tok_stream_t stream);
 int u2tok_layernorm_bf16(const void* x, const void* res, const void* w, const void* b, void* y, int32_t rows,
                          int32_t C, float eps, u2tok_stream_t stream);
 /* The strided form: y[b][r] = LN(x[b][r] (+ res[b][r])) w + b for b < nb, r < rows; row r of batch entry b at

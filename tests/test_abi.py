@@ -66,6 +66,8 @@ def test_workspace_sizing_runs_without_a_gpu(lib):
 def test_null_arguments_are_rejected_not_dereferenced(lib):
     assert lib.u2tok_gemm_bf16(None, None, None, None, None, 8, 8, 8, 8, 8, 8, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1.0, 0,
                                None) == -1
+    assert lib.u2tok_gemm_bf16_ex(None, None, None, None, None, 8, 8, 8, 8, 8, 8, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1.0, 0,
+                                  0, 1.0, None, 0, 0, 0, 0, None) == -1
     assert lib.u2tok_topk_sorted(None, None, 1, 8, 4, None) == -1
     assert lib.u2tok_im2col_patches(None, 0, None, 1, 32, 64, 64, 4, 16, 16, None) == -1
 

@@ -137,6 +137,10 @@ SIGNATURES = {
     "u2tok_embed_splice": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
     "u2tok_gemm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32,
                                _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp]),
+    # ... alpha, flags, nsplit, alpha_lo, vt, vt_n0, vt_rows, vt_ld, vt_bs, stream
+    "u2tok_gemm_bf16_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32,
+                                  _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _i32, _f32, _vp, _i32, _i32, _i64, _i64,
+                                  _vp]),
     "u2tok_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp]),
     # x, res, w, b, y, nb, rows, C, x_bs, x_ld, res_bs, res_ld, y_bs, y_ld, eps, stream
     "u2tok_layernorm_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),

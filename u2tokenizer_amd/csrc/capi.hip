@@ -192,6 +192,37 @@ int u2tok_gemm_bf16(const void* A, const void* B, void* C, const void* bias, con
   return gemm_bf16(g, ST(stream));
 }
 
+// u2tok_gemm_bf16 with the descriptor fields the ViT's q|k|v product sets (pipeline.hip: vit_block): the column split and the
+// transposed side output.  Neutral values (nsplit 0, alpha_lo 1, vt NULL) leave the descriptor u2tok_gemm_bf16 builds.
+int u2tok_gemm_bf16_ex(const void* A, const void* B, void* C, const void* bias, const void* R, int32_t M, int32_t N,
+                       int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int32_t nz, int32_t nbh,
+                       int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, int64_t sRb,
+                       int64_t sRh, float alpha, int32_t flags, int32_t nsplit, float alpha_lo, void* vt, int32_t vt_n0,
+                       int32_t vt_rows, int64_t vt_ld, int64_t vt_bs, u2tok_stream_t stream) {
+  GemmDesc g;
+  g.A = BF(A); g.B = BF(B); g.C = C; g.bias = BF(bias); g.R = BF(R);
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
+  g.nz = nz; g.nbh = nbh;
+  g.sAb = sAb; g.sAh = sAh; g.sBb = sBb; g.sBh = sBh; g.sCb = sCb; g.sCh = sCh; g.sRb = sRb; g.sRh = sRh;
+  g.alpha = alpha;
+  g.flags = flags & (GEMM_BIAS_N | GEMM_BIAS_M | GEMM_GELU | GEMM_RESIDUAL | GEMM_OUT_F32 | GEMM_A_KMAJOR | GEMM_B_KMAJOR |
+                     GEMM_SWIGLU);
+  if (flags & GEMM_B_KTILE) {
+    if ((K & 63) || nz != 1) return U2_ERR_ARG;
+    g.ldb = 64;
+    g.ldbk = (int64_t)N * 64;
+  }
+  g.nsplit = nsplit; g.alpha_lo = alpha_lo;
+  if (vt) {
+    // 16-byte stores of 8 keys; every chunk of vt_rows keys holds N - vt_n0 rows of vt_ld keys inside its vt_bs elements
+    if (vt_n0 <= 0 || vt_n0 >= N || vt_rows <= 0 || ((uintptr_t)vt & 15) || (vt_ld & 7) || (vt_bs & 7) || vt_ld < vt_rows ||
+        vt_bs < (int64_t)(N - vt_n0) * vt_ld || !gemm_vt_supported(g, vt_n0, vt_rows))
+      return U2_ERR_ARG;
+    g.vt = BFW(vt); g.vt_n0 = vt_n0; g.vt_rows = vt_rows; g.vt_ld = vt_ld; g.vt_bs = vt_bs;
+  }
+  return gemm_bf16(g, ST(stream));
+}
+
 int u2tok_layernorm_bf16(const void* x, const void* res, const void* w, const void* b, void* y, int32_t rows,
                          int32_t C, float eps, u2tok_stream_t stream) {
   return layernorm_dense(BF(x), BF(res), BF(w), BF(b), BFW(y), rows, C, eps, ST(stream));

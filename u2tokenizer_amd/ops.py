@@ -1155,6 +1155,31 @@ def gemm_strided(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, M, N, K
 
 
 @_guarded
+def gemm_ex(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, M, N, K, lda, ldb, ldc, ldr=0, nz=1, nbh=1, sAb=0, sAh=0,
+            sBb=0, sBh=0, sCb=0, sCh=0, sRb=0, sRh=0, alpha=1.0, flags=0, bias=None, residual=None, a_off=0, b_off=0, c_off=0,
+            r_off=0, nsplit=0, alpha_lo=1.0, vt: Optional[torch.Tensor] = None, vt_n0=0, vt_rows=0, vt_ld=0, vt_bs=0,
+            vt_off=0) -> torch.Tensor:
+    """The whole descriptor of u2tok_gemm_bf16_ex on STORAGES (any shape; *_off are element offsets into them): `flags` as the
+    header numbers them (bias and residual must come with their flag), columns n < nsplit scaled by alpha_lo instead of alpha,
+    and with `vt` the columns n >= vt_n0 of the many-row part written transposed to vt[m // vt_rows][n - vt_n0][perm16(m % vt_rows)]
+    instead of C (include/u2tok.h has the conditions; anything else raises).  The neutral values give u2tok_gemm_bf16's bits."""
+    h = _lib.load_library()
+    _need(a, ELEM, "A"), _need(b, ELEM, "B")
+    if vt is not None:
+        _need(vt, ELEM, "vt")
+    if (bias is not None) != bool(flags & (GEMM_BIAS_N | GEMM_BIAS_M)) or (residual is not None) != bool(flags & GEMM_RESIDUAL):
+        raise RuntimeError("gemm_ex: bias / residual and their flags do not agree")
+    es = a.element_size()
+    st = h.u2tok_gemm_bf16_ex(a.data_ptr() + es * a_off, b.data_ptr() + es * b_off, out.data_ptr() + out.element_size() * c_off,
+                              _ptr(bias), None if residual is None else residual.data_ptr() + es * r_off, M, N, K, lda, ldb, ldc,
+                              ldr, nz, nbh, sAb, sAh, sBb, sBh, sCb, sCh, sRb, sRh, float(alpha), int(flags), int(nsplit),
+                              float(alpha_lo), None if vt is None else vt.data_ptr() + es * vt_off, vt_n0, vt_rows, vt_ld, vt_bs,
+                              _stream())
+    _lib.check(st, "u2tok_gemm_bf16_ex")
+    return out
+
+
+@_guarded
 def transpose_ex(x: torch.Tensor, nz: int, R: int, Cc: int, ld_in: int, in_zs: int, ld_out: int = None,
                  x_off: int = 0) -> torch.Tensor:
     """out[z][c][r] = x[z][r][c] for a strided source (row stride ld_in, batch stride in_zs, elements); out is dense
