@@ -40,7 +40,8 @@ LOG2E = 1.0 / LN2
 ELEM = {"bf16": (torch.bfloat16, 2.0 ** -8, 0.0), "f16": (torch.float16, 2.0 ** -11, 2.0 ** -25)}
 STALE = 7.3   # log2 units the emulation's stale row max lies below the true one (the kernel's lazy branch allows up to 8)
 
-Case = collections.namedtuple("Case", "sweep entry nb Sq Skv Hq Hkv d window kv_start kv_len causal spare layout data edge tile")
+Case = collections.namedtuple("Case", "sweep entry nb Sq Skv Hq Hkv d window kv_start kv_len causal spare layout data edge tile thr",
+                              defaults=(8.0,))    # thr: the lazy-rescale threshold the `steps` data straddles, in log2 units
 
 
 def case(sweep, entry, nb, Sq, Skv, Hq, Hkv, d, window=None, kv_start=None, kv_len=None, causal=True, spare=0, layout="cache",
@@ -194,7 +195,7 @@ def _operands(key, elem):
     c = key
     dt = ELEM[elem][0]
     cap = c.Skv + c.spare
-    g = B._gen(7, c.nb, c.Sq, c.Skv, c.Hq, c.Hkv, c.d, c.window or 0, len(c.data), c.tile, sum(c.edge or (0,)))
+    g = B._gen(7, c.nb, c.Sq, c.Skv, c.Hq, c.Hkv, c.d, c.window or 0, len(c.data), c.tile, sum(c.edge or (0,)))   # (thr: steps draws nothing)
     m = _pattern(c.d)
     scale = c.d ** -0.5
     q = torch.randn(c.nb, c.Sq, c.Hq, c.d, generator=g)
@@ -229,8 +230,11 @@ def _operands(key, elem):
             # S1 = scale (d / 2) q1 log2 e = 8 (to the 0.3 % of q1's rounding) and S2 = 0.05: steps of S1 - 0.1 and S1 + 0.1 in turn
             h, t = c.d // 2, j // c.tile
             per = scale * h * LOG2E
-            q1, q2 = torch.tensor(8.0 / per).to(dt).float(), torch.tensor(0.05 / (per * 2.0 ** -4)).to(dt).float()
-            q = (torch.cat([q1.expand(h), q2.expand(h)]) * m).expand(c.nb, c.Sq, c.Hq, c.d)
+            q1, q2 = torch.tensor(c.thr / per).to(dt).float(), torch.tensor(0.05 / (per * 2.0 ** -4)).to(dt).float()
+            q = torch.cat([q1.expand(h), q2.expand(h)])
+            if c.thr != 8.0:   # (q1's own rounding, 0.4 % of S1, is more than 0.1 beyond S1 = 25: the half's last element takes it up)
+                q[h - 1] = torch.tensor(c.thr / per * h - float(q1) * (h - 1)).to(dt).float()
+            q = (q * m).expand(c.nb, c.Sq, c.Hq, c.d)
             k = torch.cat([t[:, None].float().expand(cap, h), torch.where(t % 2 == 0, 1.0, -1.0)[:, None].expand(cap, h) * 2.0 ** -4], 1) * m
             k = k[None, None].expand(c.nb, c.Hkv, cap, c.d)
         elif c.data == "equal":
@@ -251,16 +255,18 @@ def operands(c, elem):
 
 
 # ------------------------------------------------------------------------------------------------------------ bound model
-def _scores(q, k, scale, vis):
+def _scores(q, k, scale, vis, bias=None):
     G = q.shape[1] // k.shape[1]
     kk = k.repeat_interleave(G, 1)
     s = (q @ kk.transpose(-1, -2)) * scale
+    if bias is not None:
+        s = s + bias
     s = s.masked_fill(~vis[:, None], float("-inf"))
     m = s.max(-1, keepdim=True).values
     return s, torch.where(m == float("-inf"), torch.zeros_like(m), m), kk
 
 
-def model(q, k, v, scale, vis, U, tiny=0.0):
+def model(q, k, v, scale, vis, U, tiny=0.0, bias=None, c_bias=0.0, pw=None):
     """q (nb, Hq, Sq, d), k / v (nb, Hkv, Skv, d) float64, vis (nb | 1, Sq, Skv) -> out (nb, Hq, Sq, d) and its per-element bound.
     A row that sees no key has out = 0 and bound = 0: the kernels must return exact zeros there.
 
@@ -276,9 +282,16 @@ def model(q, k, v, scale, vis, U, tiny=0.0):
       tiny sum_j |v_j| / l_i          (IEEE half only) a probability below 2^-14 is rounded to a multiple of 2^-24: off by up to
                                       tiny = 2^-25 absolutely.  The kernel's p_j = exp(s_ij - m') with m' <= m_i, so its row sum
                                       is >= l_i = sum_j exp(s_ij - m_i) >= 1 and the absolute errors are scaled down at least as
-                                      much as charged here."""
+                                      much as charged here.
+
+    The encoder attention kernels (tests/enc_attn_cases.py, where both are derived) add two parameters:
+      bias, c_bias   an additive score term (1 | nb, Hq, Sq, Skv), exact in float64: s_ij = scale q_i . k_j + bias_ij, and e_ij gains
+                     c_bias u |bias_ij| for the fp32 operations that touch the bias alone.
+      pw             the weight of sum_j P_j |v_j| that stands for P's rounding before the P V product (default U; 0 for a kernel
+                     that keeps P in fp32).  Returns also lse = m_i + log l_i (natural log; -inf for a row that sees no key)."""
     d, Skv = q.shape[3], k.shape[2]
-    s, m, kk = _scores(q, k, scale, vis)
+    pw = U if pw is None else pw
+    s, m, kk = _scores(q, k, scale, vis, bias)
     G = q.shape[1] // k.shape[1]
     vv = v.repeat_interleave(G, 1)
     p = torch.exp(s - m)
@@ -287,23 +300,27 @@ def model(q, k, v, scale, vis, U, tiny=0.0):
     out = P @ vv
     A = scale * (q.abs() @ kk.abs().transpose(-1, -2))
     e = u * (d * A + 4 * (s.masked_fill(~vis[:, None], 0.0).abs() + m.abs()) + 8)
+    if bias is not None:
+        e = e + c_bias * u * bias.abs()
     Pe = P * e
-    bound = U * out.abs() + (U + (Skv + d) * u) * (P @ vv.abs()) + Pe @ vv.abs() + Pe.sum(-1, keepdim=True) * out.abs()
+    bound = U * out.abs() + (pw + (Skv + d) * u) * (P @ vv.abs()) + Pe @ vv.abs() + Pe.sum(-1, keepdim=True) * out.abs()
     if tiny:
         bound = bound + tiny * (vis[:, None].to(torch.float64).expand(-1, q.shape[1], -1, -1) @ vv.abs()) / l.clamp_min(1.0)
-    return dict(out=out, bound=bound, P=P, s=s)
+    lse = torch.where(l > 0, m + torch.log(l.clamp_min(1e-300)), torch.full_like(l, float("-inf")))[..., 0]
+    return dict(out=out, bound=bound, P=P, s=s, lse=lse)
 
 
-def emulate(q, k, v, scale, vis, dt, stale=0.0):
-    """the kernels: p = exp(s - m') rounded to the element type for the P V product, m' the row max or `stale` log2 units below it
-    (the lazy branch keeps a running max up to 8 below a tile's), the row sum of the unrounded p divides, one output rounding"""
+def emulate(q, k, v, scale, vis, dt, stale=0.0, bias=None, round_p=True):
+    """the kernels: p = exp(s - m') rounded to the element type for the P V product (round_p False: kept as it is, a kernel whose
+    P stays in fp32), m' the row max or `stale` log2 units below it (the lazy branch keeps a running max up to 8 below a tile's),
+    the row sum of the unrounded p divides, one output rounding"""
     def rnd(t):
         return t.float().to(dt).double()
-    s, m, _ = _scores(q, k, scale, vis)
+    s, m, _ = _scores(q, k, scale, vis, bias)
     p = torch.exp(s - m + stale * LN2)
     l = p.sum(-1, keepdim=True)
     G = q.shape[1] // k.shape[1]
-    o = rnd(p) @ v.repeat_interleave(G, 1)
+    o = (rnd(p) if round_p else p) @ v.repeat_interleave(G, 1)
     return rnd(torch.where(l > 0, o / l.clamp_min(1e-300), torch.zeros_like(o)))
 
 
