@@ -309,9 +309,13 @@ int u2tok_avgpool3d_tokens(const void* x, void* y, int32_t nb, int32_t g1, int32
                            int32_t w2, int32_t w3, int32_t C, u2tok_stream_t stream);
 int u2tok_score_gemv(const void* x, const void* w, const void* bias, float* scores, int32_t rows, int32_t E,
                      u2tok_stream_t stream);
+/* idx[b][0..k): the indices of the k largest of scores[b][0..n), n <= 8192, 1 <= k <= n: descending score, ties by ascending
+ * index, -0.0 == +0.0, every NaN (either sign bit, any payload) first -- torch.sort(descending=True, stable=True). */
 int u2tok_topk_sorted(const float* scores, int64_t* idx, int32_t B, int32_t n, int32_t k, u2tok_stream_t stream);
 int u2tok_gather_rows(const void* x, const int64_t* idx, void* out, int32_t B, int32_t n, int32_t k, int32_t E,
                       u2tok_stream_t stream);
+/* dst[b * dst_bs + e] = src[e] for b < nb, e < n: one row broadcast into nb slots dst_bs elements apart (dst_bs >= n) */
+int u2tok_fill_rows(const void* src, void* dst, int32_t nb, int64_t n, int64_t dst_bs, u2tok_stream_t stream);
 /* ws: B*3*16*ceil(E/256) floats (only read/written when gate_w != null) */
 int u2tok_multiscale_pool(const void* x, void* out, int32_t B, int32_t k, int32_t E, const void* gate_w,
                           const void* gate_b, float* ws, u2tok_stream_t stream);

@@ -276,7 +276,8 @@ def exact_scores(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor])
 
 
 def canonical_topk(scores: torch.Tensor, k: int) -> torch.Tensor:
-    """torch.topk(..., sorted) (svr.py:82) with the canonical tie rule: ties by ascending index; -0.0 == +0.0."""
+    """torch.topk(..., sorted) (svr.py:82) with the canonical tie rule: ties by ascending index; -0.0 == +0.0; every NaN
+    (either sign bit, any payload) ranks first, ties among NaNs by ascending index too (torch.sort's order)."""
     s = scores + 0.0  # -0.0 -> +0.0
     return torch.sort(s, dim=1, descending=True, stable=True).indices[:, :k]
 

@@ -270,6 +270,10 @@ int u2tok_gather_rows(const void* x, const int64_t* idx, void* out, int32_t B, i
   return gather_rows(BF(x), idx, BFW(out), B, n, k, E, ST(stream));
 }
 
+int u2tok_fill_rows(const void* src, void* dst, int32_t nb, int64_t n, int64_t dst_bs, u2tok_stream_t stream) {
+  return fill_rows(BF(src), BFW(dst), nb, n, dst_bs, ST(stream));
+}
+
 int u2tok_multiscale_pool(const void* x, void* out, int32_t B, int32_t k, int32_t E, const void* gate_w,
                           const void* gate_b, float* ws, u2tok_stream_t stream) {
   return multiscale_pool(BF(x), BFW(out), B, k, E, BF(gate_w), BF(gate_b), ws, ST(stream));

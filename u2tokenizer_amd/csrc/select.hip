@@ -48,12 +48,15 @@ int score_gemv(const bf16_t* x, const bf16_t* w, const bf16_t* bias, float* scor
 // ---------------------------------------------------------------- top-k, sorted, canonical ties
 // torch.topk(scores, k, dim=1) (svr.py:82) returns values sorted descending; its order among EQUAL
 // scores is unspecified.  Canonical rule here (and in oracle/): descending score, ties by ascending
-// index (== torch.sort(stable=True, descending=True)); -0.0 == +0.0.  One workgroup bitonic-sorts the
+// index (== torch.sort(stable=True, descending=True)); -0.0 == +0.0; every NaN, whatever its sign bit and payload, ranks
+// first (above +inf), ties among NaNs by ascending index as well.  One workgroup bitonic-sorts the
 // 64-bit keys (orderable score bits << 32 | ~index) of one batch row in LDS.
 __device__ __forceinline__ uint64_t topk_key(float f, uint32_t idx) {
   if (f == 0.f) f = 0.f;  // -0.0 -> +0.0
   uint32_t u = __float_as_uint(f);
   u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+  // a NaN with the sign bit set (x86's inf - inf) would otherwise sort below -inf, one without it by its payload
+  if (f != f) u = 0xffffffffu;
   return ((uint64_t)u << 32) | (uint64_t)(0xffffffffu - idx);
 }
 

@@ -57,7 +57,15 @@ class u2Transform:
     def from_dhw(self, vol: torch.Tensor, target_image_size: int = 256, padding_size: int = 32 * 8,
                  aug: Optional[dict] = None) -> torch.Tensor:
         """aug: explicit augmentation parameters (keys of sample_augmentation()); None = draw them when
-        data_type == "training", none otherwise."""
+        data_type == "training", none otherwise.
+
+        `last_info` (int32[12], on the device) tells how the call went: [0] status, [1:4] / [4:7] the foreground box lo / hi over
+        (d, h, w), [7:10] the resized size, [10:12] the two percentiles (float32 bits).  Status 0: the volume is in the output.
+        Status 1: no voxel above the lower percentile (no foreground); the output is all zeros, only the percentiles are
+        meaningful.  Status 2: an axis of the crop is more than 9.25 times its resized extent, so the anti-aliasing Gaussian
+        (sigma = (in / out - 1) / 2 > 4.125) needs more than the 16 taps per side the filter keeps; nothing is filtered or
+        resized, the output is all zeros, the box, the resized size and the percentiles are reported as for status 0.  The call
+        itself succeeds in all three cases: check `last_info[0]` before using the output."""
         h = _lib.load_library()
         vol = ops._need(vol, torch.float32, "volume").contiguous()
         if vol.dim() == 4 and vol.shape[0] == 1:
