@@ -627,7 +627,16 @@ int u2tok_decode_attention(const void* q, const void* K, const void* V, void* ou
  * dense, T * D; a multiple of 16), scale_stride floats between their scale entries (0: T).  Codes are widened to the element type
  * in registers (exact), the MFMAs stay in the element type: s_j = k_scales[j] * sum_d q_d code(K_jd), p_j = exp2(s_j c - m), the
  * row sum takes p_j, the P operand is rnd(p_j * v_scales[j]) (the IEEE-half build: times 2^8, undone where the sum is divided).
- * workspace: u2tok_decode_attention_kv8_workspace_bytes (= u2tok_decode_attention_workspace_bytes). */
+ * workspace: u2tok_decode_attention_kv8_workspace_bytes (= u2tok_decode_attention_workspace_bytes).
+ * u2tok_attention_kv8_rows: the same attention for Sq >= 1 NEW positions per sequence (a continued prefill on such a cache: a prompt
+ * fed in chunks, a second turn, draft verification).  q / out: B * Sq rows, row b * Sq + i at ldq / ldo elements apart (the q
+ * columns of packed q|k|v rows; a dense context).  Codes, scales, kv_stride, sc_stride as above, the pointers advanced to the first
+ * position read; T counts the positions read, the Sq new ones last.  Row i sees key j iff kv_start[b] <= j <= i + T - Sq and, for
+ * window W > 0, j > i + T - Sq - W (window = 0: no lower edge).  The 16 rows of a workgroup's operand are 16 consecutive flat rows
+ * i * (Hq / Hkv) + head-in-group of one kv head, so the cache is read once per 16 such rows: the form for few new positions.  A
+ * row that sees no key: zeros.  Bit-repeatable; Sq = 1, window = 0 gives the bits of u2tok_decode_attention_kv8.  Everything that
+ * entry refuses, Sq < 1, Sq > T, window < 0, B * Sq * Hq >= 2^31: U2TOK_ERR_ARG / U2TOK_ERR_WORKSPACE before anything is launched.
+ * workspace: u2tok_attention_kv8_rows_workspace_bytes. */
 int u2tok_kv_quantize_rows(const void* k, const void* v, int32_t B, int32_t Hkv, int32_t n, int32_t D, int64_t k_bs, int64_t k_hs,
                            int64_t k_rs, int64_t v_bs, int64_t v_hs, int64_t v_rs, void* k_codes, void* v_codes, float* k_scales,
                            float* v_scales, int32_t capacity, int32_t s_off, u2tok_stream_t stream);
@@ -636,6 +645,11 @@ int u2tok_decode_attention_kv8(const void* q, const void* k_codes, const void* v
                                void* out, int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D, int64_t ldq, int64_t kv_stride,
                                int64_t scale_stride, int64_t ldo, float scale, const int32_t* kv_start, void* workspace,
                                size_t workspace_bytes, u2tok_stream_t stream);
+size_t u2tok_attention_kv8_rows_workspace_bytes(int32_t B, int32_t Sq, int32_t Hq, int32_t Hkv, int32_t T, int32_t D);
+int u2tok_attention_kv8_rows(const void* q, const void* k_codes, const void* v_codes, const float* k_scales, const float* v_scales,
+                             void* out, int32_t B, int32_t Sq, int32_t Hq, int32_t Hkv, int32_t T, int32_t D, int64_t ldq,
+                             int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale, int32_t window, const int32_t* kv_start,
+                             void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 
 /* in-place rotate-half RoPE (rope.py:6-13,77-80): rows indexed (outer, s, inner), position = s; inverse != 0 rotates
  * the other way (the backward of the rotation) */

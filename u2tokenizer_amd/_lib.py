@@ -205,6 +205,11 @@ SIGNATURES = {
     # q, k_codes, v_codes, k_scales, v_scales, out, B, Hq, Hkv, T, D, ldq, kv_stride, scale_stride, ldo, scale, kv_start, ws, ws_bytes, stream
     "u2tok_decode_attention_kv8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp,
                                           _sz, _vp]),
+    "u2tok_attention_kv8_rows_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    # q, k_codes, v_codes, k_scales, v_scales, out, B, Sq, Hq, Hkv, T, D, ldq, kv_stride, sc_stride, ldo, scale, window, kv_start, ws,
+    # ws_bytes, stream
+    "u2tok_attention_kv8_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _i32,
+                                        _vp, _vp, _sz, _vp]),
     # cfg, layer, x, qkv, k_new, v_new, k_codes, v_codes, k_scales, v_scales, capacity, k_first, s_off, kv_start, out, ws, ws_bytes, stream
     "u2tok_decoder_decode_post_kv8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "u2tok_rope_apply": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),

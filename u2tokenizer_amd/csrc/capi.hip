@@ -546,6 +546,17 @@ int u2tok_decode_attention_kv8(const void* q, const void* k_codes, const void* v
                               v_scales, BFW(out), B, Hq, Hkv, T, D, ldq, kv_stride, scale_stride, ldo, scale, kv_start, workspace,
                               workspace_bytes, false, ST(stream));
 }
+size_t u2tok_attention_kv8_rows_workspace_bytes(int32_t B, int32_t Sq, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
+  return attention_kv8_rows_workspace_bytes(B, Sq, Hq, Hkv, T, D);
+}
+int u2tok_attention_kv8_rows(const void* q, const void* k_codes, const void* v_codes, const float* k_scales, const float* v_scales,
+                             void* out, int32_t B, int32_t Sq, int32_t Hq, int32_t Hkv, int32_t T, int32_t D, int64_t ldq,
+                             int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale, int32_t window, const int32_t* kv_start,
+                             void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  return attention_kv8_rows(BF(q), reinterpret_cast<const uint8_t*>(k_codes), reinterpret_cast<const uint8_t*>(v_codes), k_scales, v_scales,
+                            BFW(out), B, Sq, Hq, Hkv, T, D, ldq, kv_stride, sc_stride, ldo, scale, window, kv_start, workspace,
+                            workspace_bytes, false, ST(stream));
+}
 size_t u2tok_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t Hkv, int32_t T, int32_t D) {
   return decode_attention_workspace_bytes(B, Hq, Hkv, T, D);
 }

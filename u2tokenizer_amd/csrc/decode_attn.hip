@@ -444,6 +444,7 @@ struct DecAttn8Args {
   float scale_log2e;
   float* opart;
   float* ml;
+  int Sq, nrb, window;  // the rows form (decode_attn_kv8_kernel<D, true>): new positions per sequence, row blocks per kv head, W (0: none)
 };
 
 #if U2_ELEM_IS_F16
@@ -486,7 +487,15 @@ typedef uint32_t da_u2_t __attribute__((ext_vector_type(2)));
 #define DA8_OUT3(n, t) DA8_OUT2(n, t), [n##02] "=&v"(t[0][2]), [n##12] "=&v"(t[1][2]), [n##22] "=&v"(t[2][2]), [n##32] "=&v"(t[3][2])
 #define DA8_OUT4(n, t) DA8_OUT3(n, t), [n##03] "=&v"(t[0][3]), [n##13] "=&v"(t[1][3]), [n##23] "=&v"(t[2][3]), [n##33] "=&v"(t[3][3])
 
-template <int D>
+// ROWS (the continued prefill on such a cache, u2tok_attention_kv8_rows): Sq new positions per sequence instead of one.  The 16 rows
+// of the B operand are 16 consecutive FLAT rows f = i G + gh of the kv head (i: the new position, gh: the query head inside the
+// group; G need not divide 16: a block may straddle positions), workgroup = (sequence, kv head, row block, key split); rows
+// f >= Sq G of the last block carry zero queries and are never stored.  With c = T - Sq the lane's row sees key j iff
+// kv_start[b] <= j <= i + c and, for a window W > 0, j > i + c - W; a block walks the tiles between its first row's lower edge and
+// its last row's diagonal, the masked path on every tile that an edge of one of its rows crosses (wave-uniform).  Partials and
+// output are indexed by b' = b Sq + i where the decode form has b: the merge kernel is the same.  Everything else -- the tiles, the
+// LDS image, the reads, the counted waits, the waves' merge -- is the code below, shared; ROWS = false compiles to the decode kernel.
+template <int D, bool ROWS = false>
 __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args a) {
   constexpr int BK = 64;              // keys per tile
   constexpr int CPR = D / 16;         // 16-byte chunks per tile row
@@ -504,12 +513,33 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
   char* const wl = lds + w * 2 * STAGE;
 
   const int sp = blockIdx.x % a.ns;
-  const int bh = blockIdx.x / a.ns;
+  const int rb = ROWS ? (blockIdx.x / a.ns) % a.nrb : 0;  // row block
+  const int bh = ROWS ? blockIdx.x / a.ns / a.nrb : blockIdx.x / a.ns;
   const int hkv = bh % a.Hkv, b = bh / a.Hkv;
   const int T = a.T, G = a.G;
   const int ntile = (T + BK - 1) / BK;
   const int kvs = a.kv_start ? max(0, min(a.kv_start[b], T)) : 0;
-  const int t_lo = max(sp * a.tps, kvs / BK), t_hi = min(ntile, sp * a.tps + a.tps);
+  // ROWS: the block's live rows, the lane's row f = (position r_i, head r_gh) and its visible keys [j_lo, j_hi]; the block's edges:
+  // e_hi = the first row's diagonal (a tile reaching beyond it is masked), e_lo = the last row's lower edge (a tile starting below it is)
+  // (the decode form reads none of the six: its expressions stand where they stood)
+  int nlive = G, r_i = 0, r_gh = min(l15, G - 1), j_lo = 0, j_hi = 0, e_lo = 0, e_hi = 0, t_first = 0, t_end = 0;
+  if constexpr (ROWS) {
+    const int c = T - a.Sq, W = a.window, f0 = rb * 16;
+    nlive = min(16, a.Sq * G - f0);
+    const int f = f0 + min(l15, nlive - 1);
+    r_i = f / G;
+    r_gh = f - r_i * G;
+    const int i0 = f0 / G, i1 = (f0 + nlive - 1) / G;
+    j_hi = r_i + c;
+    j_lo = W > 0 ? max(kvs, r_i + c - W + 1) : kvs;
+    e_hi = i0 + c;
+    e_lo = W > 0 ? max(kvs, i1 + c - W + 1) : kvs;
+    const int k_lo = W > 0 ? max(kvs, i0 + c - W + 1) : kvs;  // the block's keys: k_lo .. i1 + c, every one seen by some row
+    t_first = k_lo / BK;
+    t_end = k_lo > i1 + c ? t_first : (i1 + c) / BK + 1;      // (kv_start beyond the last row's diagonal: no tile)
+  }
+  const int t_lo = ROWS ? max(sp * a.tps, t_first) : max(sp * a.tps, kvs / BK);
+  const int t_hi = ROWS ? min(t_end, sp * a.tps + a.tps) : min(ntile, sp * a.tps + a.tps);
 
   const uint8_t* kb_ = a.k + ((int64_t)b * a.Hkv + hkv) * a.kv_stride;
   const uint8_t* vb_ = a.v + ((int64_t)b * a.Hkv + hkv) * a.kv_stride;
@@ -537,11 +567,12 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
   // ---- the group's queries (B operand), as decode_attn_kernel has them
   bf16x8 qf[KS];
   {
-    const bf16_t* qp = a.q + (int64_t)b * a.ldq + (int64_t)(hkv * G + min(l15, G - 1)) * D + g * 8;
+    const bf16_t* qp = ROWS ? a.q + ((int64_t)b * a.Sq + r_i) * a.ldq + (int64_t)(hkv * G + r_gh) * D + g * 8
+                            : a.q + (int64_t)b * a.ldq + (int64_t)(hkv * G + min(l15, G - 1)) * D + g * 8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 32);
-      if (l15 >= G) qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (l15 >= nlive) qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
   }
 
@@ -619,11 +650,12 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
       }
     }
     // ---- online softmax: the lane owns keys kt * 64 + 16 (i >> 2) + 4 g + (i & 3) of head l15
-    if (kt * BK < kvs || kt * BK + BK > T) {  // (wave-uniform) the partial first / last tile of the visible range
+    // (wave-uniform) the partial first / last tile of the visible range; ROWS: a tile that an edge of one of the block's rows crosses
+    if (ROWS ? kt * BK < e_lo || kt * BK + BK - 1 > e_hi : kt * BK < kvs || kt * BK + BK > T) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int j = kt * BK + (i >> 2) * 16 + 4 * g + (i & 3);
-        if (j < kvs || j >= T) x[i] = -INFINITY, pv[i] = 0.f;
+        if (ROWS ? j < j_lo || j > j_hi : j < kvs || j >= T) x[i] = -INFINITY, pv[i] = 0.f;
       }
     }
     float mt = x[0];
@@ -706,7 +738,7 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
   __syncthreads();  // every wave is done with its tiles: the staging area is free
   float* const so = reinterpret_cast<float*>(lds);  // [4][16][D]
   float* const sml = so + 4 * 16 * D;               // [4][16][2]
-  if (l15 < G) {
+  if (l15 < nlive) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       float* const p = so + (w * 16 + l15) * D + 32 * s + 8 * g;
@@ -719,7 +751,7 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
     }
   }
   __syncthreads();
-  for (int idx = tid; idx < G * (D / 4); idx += 256) {
+  for (int idx = tid; idx < nlive * (D / 4); idx += 256) {
     const int qh = idx / (D / 4), c4 = (idx - qh * (D / 4)) * 4;
     float m = -INFINITY;
 #pragma unroll
@@ -732,13 +764,16 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const DecAttn8Args
       const float4 t = *reinterpret_cast<const float4*>(so + (u * 16 + qh) * D + c4);
       acc[0] += wgt * t.x; acc[1] += wgt * t.y; acc[2] += wgt * t.z; acc[3] += wgt * t.w;
     }
-    const int head = hkv * G + qh;
+    const int oi = ROWS ? (rb * 16 + qh) / G : 0;                       // ROWS: row qh of the block = (position oi, head)
+    const int head = hkv * G + (ROWS ? rb * 16 + qh - oi * G : qh);
+    const int64_t ob = ROWS ? (int64_t)b * a.Sq + oi : (int64_t)b;      // the row of out and of the partials
+    const int64_t nb = ROWS ? (int64_t)a.B * a.Sq : (int64_t)a.B;
     if (a.ns == 1) {
       const float inv = (L > 0.f ? 1.f / L : 0.f) * DA8_PRE_INV;  // no visible key: zeros
-      *reinterpret_cast<uint2*>(a.out + (int64_t)b * a.ldo + head * D + c4) =
+      *reinterpret_cast<uint2*>(a.out + ob * a.ldo + head * D + c4) =
           uint2{pack2_bf16(acc[0] * inv, acc[1] * inv), pack2_bf16(acc[2] * inv, acc[3] * inv)};
     } else {  // (the partials leave without the pre-scale: decode_attn_merge_kernel is the 16-bit kernel's)
-      const int64_t e = ((int64_t)sp * a.B + b) * a.Hq + head;
+      const int64_t e = ((int64_t)sp * nb + ob) * a.Hq + head;
       *reinterpret_cast<float4*>(a.opart + e * D + c4) =
           float4{acc[0] * DA8_PRE_INV, acc[1] * DA8_PRE_INV, acc[2] * DA8_PRE_INV, acc[3] * DA8_PRE_INV};
       if (c4 == 0) {
@@ -768,6 +803,7 @@ int decode_attention_kv8(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, 
   a.q = q; a.k = Kc; a.v = Vc; a.ks = Ks; a.vs = Vs; a.out = out; a.kv_start = kv_start;
   a.ldq = ldq; a.ldo = ldo; a.kv_stride = kv_stride; a.sc_stride = sc_stride;
   a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv; a.T = T;
+  a.Sq = 1; a.nrb = 1; a.window = 0;  // (read by the rows form only)
   a.scale_log2e = scale * 1.44269504088896340736f;
   const int ntile = (int)cdiv(T, 64);
   int ns = ws ? std::min(dec_attn_splits(B, Hkv, T), ntile) : 1;  // (no workspace: unsplit)
@@ -801,6 +837,78 @@ int decode_attention_kv8(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, 
     m.B = B; m.Hq = Hq; m.Hkv = Hkv; m.G = a.G; m.T = T; m.ns = a.ns; m.tps = a.tps;
     m.scale_log2e = a.scale_log2e; m.opart = a.opart; m.ml = a.ml;
     const int64_t total = (int64_t)B * Hq * (D / 4);
+    hipLaunchKernelGGL(decode_attn_merge_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, m, D);
+  }
+  return launch_status();
+}
+
+// ---- the rows form: Sq new positions per sequence against the codes (the continued prefill on an e4m3 cache).  nrb row blocks of 16
+// flat rows per (sequence, kv head); the splits are dec_attn_splits' on B nrb where the decode entry has B, so Sq = 1 has the decode
+// entry's grid, splits and bits.  The cache is streamed once per row block: the form for FEW new positions.
+static int da8_row_blocks(int Sq, int G) { return (int)cdiv((int64_t)Sq * G, 16); }
+static int da8_rows_splits(int B, int Sq, int Hq, int Hkv, int T) {
+  const int64_t blocks = (int64_t)B * da8_row_blocks(Sq, Hq / Hkv);
+  return std::min(dec_attn_splits((int)std::min<int64_t>(blocks, 1 << 30), Hkv, T), (int)cdiv(T, 64));
+}
+
+size_t attention_kv8_rows_workspace_bytes(int B, int Sq, int Hq, int Hkv, int T, int D) {
+  if (B <= 0 || Sq <= 0 || Hq <= 0 || Hkv <= 0 || T <= 0 || D <= 0 || Hq % Hkv) return 0;
+  const int ns = da8_rows_splits(B, Sq, Hq, Hkv, T);
+  return ns > 1 ? (size_t)ns * B * Sq * Hq * ((size_t)D * 4 + 8) : 0;
+}
+
+int attention_kv8_rows(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, const float* Ks, const float* Vs, bf16_t* out, int B, int Sq,
+                       int Hq, int Hkv, int T, int D, int64_t ldq, int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale, int window,
+                       const int* kv_start, void* ws, size_t ws_bytes, bool check_only, hipStream_t stream) {
+  if (!q || !Kc || !Vc || !Ks || !Vs || !out || B <= 0 || B > 65535 || T <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 16) return U2_ERR_ARG;
+  if (D != 64 && D != 96 && D != 128) return U2_ERR_ARG;
+  if (Sq < 1 || Sq > T || window < 0 || (int64_t)B * Sq > 0x7fffffff / Hq) return U2_ERR_ARG;  // (the merge's 32-bit row and head)
+  if (kv_stride == 0) kv_stride = (int64_t)T * D;
+  if (sc_stride == 0) sc_stride = T;
+  if (kv_stride < (int64_t)T * D || (kv_stride & 15) || sc_stride < T || (int64_t)T * D >= (1ll << 31)) return U2_ERR_ARG;  // (32-bit DMA offsets)
+  if (ldq < (int64_t)Hq * D || ldo < (int64_t)Hq * D || (ldq & 7) || (ldo & 3) || !(scale > 0.f)) return U2_ERR_ARG;
+  if ((((uintptr_t)q | (uintptr_t)Kc | (uintptr_t)Vc) & 15) || ((uintptr_t)out & 7) || (((uintptr_t)kv_start | (uintptr_t)Ks | (uintptr_t)Vs) & 3))
+    return U2_ERR_ARG;
+  DecAttn8Args a;
+  a.q = q; a.k = Kc; a.v = Vc; a.ks = Ks; a.vs = Vs; a.out = out; a.kv_start = kv_start;
+  a.ldq = ldq; a.ldo = ldo; a.kv_stride = kv_stride; a.sc_stride = sc_stride;
+  a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv; a.T = T;
+  a.Sq = Sq; a.nrb = da8_row_blocks(Sq, a.G); a.window = window;
+  a.scale_log2e = scale * 1.44269504088896340736f;
+  const int ntile = (int)cdiv(T, 64);
+  const int ns = ws ? da8_rows_splits(B, Sq, Hq, Hkv, T) : 1;  // (no workspace: unsplit)
+  a.tps = (int)cdiv(ntile, ns);
+  a.ns = (int)cdiv(ntile, a.tps);  // no split beyond the last tile
+  a.opart = nullptr; a.ml = nullptr;
+  const size_t rows = (size_t)B * Sq;
+  if (a.ns > 1) {
+    if (ws_bytes < (size_t)a.ns * rows * Hq * ((size_t)D * 4 + 8)) return U2_ERR_WORKSPACE;
+    if ((uintptr_t)ws & 15) return U2_ERR_ARG;
+    a.opart = reinterpret_cast<float*>(ws);
+    a.ml = a.opart + (size_t)a.ns * rows * Hq * D;
+  }
+  const int64_t grid = (int64_t)B * Hkv * a.nrb * a.ns;
+  if (grid > 0x7fffffff) return U2_ERR_ARG;
+  if (check_only) return U2_OK;
+  ProfScope ps(PROF_TOKATTN, 4.0 * rows * Hq * (double)T * D, stream,
+               2.0 * rows * D * 2.0 * Hq + 2.0 * B * Hkv * (double)a.nrb * (double)T * (D + 4.0));
+#define U2_DA8R(D_)                                                                                                         \
+  do {                                                                                                                      \
+    constexpr size_t smem_ = 4 * 2 * (2 * 64 * (D_) + 512);  /* the decode form's: 4 waves x 2 stages; >= the merge area */   \
+    static_assert(smem_ >= 4 * 16 * (D_) * 4 + 512, "merge area");                                                          \
+    hipLaunchKernelGGL((decode_attn_kv8_kernel<D_, true>), dim3((unsigned)grid), dim3(256), smem_, stream, a);              \
+  } while (0)
+  if (D == 128) U2_DA8R(128);
+  else if (D == 96) U2_DA8R(96);
+  else U2_DA8R(64);
+#undef U2_DA8R
+  if (a.ns > 1) {
+    DecAttnArgs m;
+    m.q = nullptr; m.k = nullptr; m.v = nullptr; m.out = out; m.kv_start = nullptr;
+    m.ldq = ldq; m.ldo = ldo; m.kv_stride = 0;
+    m.B = (int)rows; m.Hq = Hq; m.Hkv = Hkv; m.G = a.G; m.T = T; m.ns = a.ns; m.tps = a.tps;
+    m.scale_log2e = a.scale_log2e; m.opart = a.opart; m.ml = a.ml;
+    const int64_t total = (int64_t)rows * Hq * (D / 4);
     hipLaunchKernelGGL(decode_attn_merge_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, m, D);
   }
   return launch_status();

@@ -471,6 +471,13 @@ size_t decode_attention_kv8_workspace_bytes(int B, int Hq, int Hkv, int T, int D
 int decode_attention_kv8(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, const float* Ks, const float* Vs, bf16_t* out, int B, int Hq,
                          int Hkv, int T, int D, int64_t ldq, int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale,
                          const int* kv_start, void* ws, size_t ws_bytes, bool check_only, hipStream_t stream);
+// attention_kv8_rows: Sq >= 1 new positions per sequence over the codes -- q / out are B Sq rows (row b Sq + i, ldq / ldo elements
+// apart), T counts the positions read (the new ones last); row i sees key j iff kv_start[b] <= j <= i + T - Sq and, window W > 0,
+// j > i + T - Sq - W.  Sq = 1, window = 0: the bits of decode_attention_kv8.
+size_t attention_kv8_rows_workspace_bytes(int B, int Sq, int Hq, int Hkv, int T, int D);
+int attention_kv8_rows(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, const float* Ks, const float* Vs, bf16_t* out, int B, int Sq,
+                       int Hq, int Hkv, int T, int D, int64_t ldq, int64_t kv_stride, int64_t sc_stride, int64_t ldo, float scale, int window,
+                       const int* kv_start, void* ws, size_t ws_bytes, bool check_only, hipStream_t stream);
 // The second half of a layer's decode step on such a cache: the step's new 16-bit rows k_new / v_new (B, Hkv, 1, D; dense: what
 // decoder_decode_pre wrote) are quantised into position s_off of the dense buffers (capacity positions per (batch, kv head)
 // entry), the attention -- always the batched kernel -- reads positions k_first .. s_off, kv_start counted from k_first.

@@ -1485,6 +1485,36 @@ def decode_attention_kv8(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, ks
 
 
 @_guarded
+def attention_kv8_rows(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor, T: int, heads: int,
+                       scale: float, window: Optional[int] = None, kv_start: Optional[torch.Tensor] = None,
+                       k_first: int = 0) -> torch.Tensor:
+    """`decode_attention_kv8` for Sq >= 1 new positions per sequence (u2tok_attention_kv8_rows: the continued prefill on an e4m3
+    cache): q (B, Sq, heads * d) in the element type -- unit stride inside a row, one stride between the B Sq rows (the q columns
+    of packed q|k|v rows qualify) --, buffers as there, of which positions k_first .. k_first + T - 1 are attended over, the Sq new
+    ones last: row i sees key j (counted from k_first) iff kv_start[b] <= j <= i + T - Sq and, with a window W, j > i + T - Sq - W.
+    -> (B, Sq, heads * d), dense."""
+    h = _lib.load_library()
+    _need(q, ELEM, "q")
+    B, Hkv, cap, d = _kv8_buffers("attention_kv8_rows", kc, vc, ks, vs)
+    W = int(window or 0)
+    if q.dim() != 3 or q.stride(2) != 1 or tuple(q.shape[::2]) != (B, heads * d) or heads % Hkv or k_first < 0 or q.shape[1] < 1 \
+            or T < q.shape[1] or k_first + T > cap or W < 0 or (B > 1 and q.shape[1] > 1 and q.stride(0) != q.shape[1] * q.stride(1)):
+        raise RuntimeError(f"attention_kv8_rows: q {tuple(q.shape)} / strides {q.stride()}, buffers {tuple(kc.shape)}, heads {heads}, T {T}, "
+                           f"k_first {k_first}, window {window}")
+    Sq = q.shape[1]
+    kv_start = _kv_len_arg(kv_start, B, q.device)
+    out = torch.empty((B, Sq, heads * d), dtype=elem_dtype(), device=q.device)
+    nbytes = h.u2tok_attention_kv8_rows_workspace_bytes(B, Sq, heads, Hkv, T, d)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+    _lib.check(h.u2tok_attention_kv8_rows(_ptr(q), _ptr(kc) + k_first * d, _ptr(vc) + k_first * d, _ptr(ks) + 4 * k_first,
+                                          _ptr(vs) + 4 * k_first, _ptr(out), B, Sq, heads, Hkv, T, d,
+                                          q.stride(1) if Sq > 1 else q.stride(0) if B > 1 else heads * d, cap * d, cap, heads * d,
+                                          float(scale), W, _ptr(kv_start), _ptr(ws) if nbytes else None, nbytes, _stream()),
+               "u2tok_attention_kv8_rows")
+    return out
+
+
+@_guarded
 def attention_gqa_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, heads: int, kv_heads: int, scale: float,
                       kv_len: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
                       d_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:

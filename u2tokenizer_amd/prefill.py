@@ -42,6 +42,9 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     would go; `route` takes it for the decode step alone (`_decode_step`: u2tok_decoder_decode_pre onto the scratch rows, then
     u2tok_decoder_decode_post_kv8, which quantises them into the layer's buffers and attends over the codes); every other route
     refuses it and reads the same cache dequantised through the layer's `update`.
+  * kv8_continued: `route` also takes a filled `Kv8Layer` for "extend" (`_prefill_step`: the rotary kernel's dense new rows are
+    quantised behind the cached ones, u2tok_attention_kv8_rows attends over the codes -- nothing is dequantised); calls longer
+    than KV8_EXTEND_MAX_ROWS stay stock.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -141,6 +144,13 @@ SWITCHES = (
            "fp32 logits -- in the same library call (u2tok_decoder_decode_stack_head); `head_route` lists what it asks, every other "
            "call runs the module norm and nn.Linear as before; `config.u2_fused_head_form` (\"elem\", \"fp8\", \"fp4\") picks lm_head's "
            "weight form, the quantised ones unmeasured in accuracy on trained weights; `head_stats`"),
+    Switch("kv8_continued", "kv8x", "u2_fused_kv_fp8_continued", False, ("kv8", "continued"), (), (),
+           "more than one new position against a filled `Kv8Layer` stays on the HIP layers: the new rows are quantised into the "
+           "layer's buffers and the new queries attend over the codes, the new rows' included (u2tok_attention_kv8_rows: 16 rows "
+           "of (position, query head) per workgroup, so the cache is read once per 16 such rows -- the form for few new positions; "
+           "at most 16 query heads per kv head; a call of more than `KV8_EXTEND_MAX_ROWS` positions stays stock); what the cache "
+           "holds defines the semantics, as on the stock route; left-padded continuations with `padded`; the whole-stack and head "
+           "calls stay out of scope; `kv8_extend_stats`"),
     Switch("kv8", "kv8", "u2_fused_kv_fp8", False, (), (), (),
            "the KV cache a fused prefill starts is FP8: a `Kv8Layer` (e4m3 codes, one fp32 scale per cached row of K and of V: half "
            "the cache's bytes in HBM and per decode step) where the append-in-place layer would go; the prefill commits through the "
@@ -148,7 +158,7 @@ SWITCHES = (
            "always the batched decode attention, so at most 16 query heads per kv head); the continued prefill refuses the layer "
            "(stock layers on the dequantised cache) and the whole-stack and head calls are out of scope on such a cache "
            "(`stack_route` answers \"layers\", `head_route` \"stock\"); exact on the quantised cache, the quantiser's cost in "
-           "accuracy is unmeasured on trained weights; `kv8_stats`"),
+           "accuracy is unmeasured on trained weights; `kv8_stats`.  `kv8_continued` keeps the continued prefill on the codes as well"),
 )
 
 # layer calls per route of the no-grad routes (as decoder_train.stats / loss_head.stats: a route that fell back to the stock layers
@@ -174,6 +184,12 @@ stack_stats = {"decode": 0, "padded_decode": 0}
 head_stats = {"head": 0, "fallback": 0, "form_fallback": 0}
 # ... and the decode steps (counted in `stats` as well) that ran on an e4m3 KV cache (kv8), per layer call
 kv8_stats = {"decode": 0, "padded_decode": 0}
+# ... and the continued prefills (counted in `extend_stats` as well) that attended over the codes of such a cache (kv8_continued)
+kv8_extend_stats = {"extend": 0, "padded_extend": 0}
+# the longest call (new positions per sequence) the continued prefill on an e4m3 cache takes, None: no cap.  The kernel streams the
+# cache once per 16 rows of (position, query head), so a long call could lose to the stock route's one dequantisation; the value is
+# the measurement's verdict (DESIGN f15: faster than the stock route at every measured length up to 1024, so no cap)
+KV8_EXTEND_MAX_ROWS = None
 # whether the whole-stack step asks for its three RMSNorms in the tail of the product before them (u2tok_gemm_rows_norm): the same
 # bits either way; the default is the measurement's verdict (DESIGN f12)
 STACK_TAIL_NORM = False
@@ -436,6 +452,7 @@ class _StackState:
     fp4: bool = False
     stack: bool = False
     head: bool = False
+    kv8x: bool = False
     kv8: bool = False
     pad: tuple = _NO_PAD      # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
     pad_shape: tuple = None    # ... and, for a mask with a key range, its (B, columns)
@@ -571,7 +588,10 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     if (W is None or shape[1] <= W) and (cache is None or cache.get_seq_length(att.layer_idx) == 0):
         return "prefill", W
     # continued=True: the band and the cache's layout inside the attention kernel (u2tok_attention_gqa_band)
-    if stack.continued and (cache is None or _extend_layer_ok(cache, att.layer_idx, W is not None)):
+    # (kv8_continued: a filled `Kv8Layer` of this batch on the GPU as well, its codes read by u2tok_attention_kv8_rows)
+    if stack.continued and (cache is None or _extend_layer_ok(
+            cache, att.layer_idx, W is not None,
+            (shape[0], shape[1], att.config.num_attention_heads // att.config.num_key_value_heads) if stack.kv8x else None)):
         return "extend", W
     return "stock", None
 
@@ -621,12 +641,15 @@ class _KVWrite:
     attends over the cache, else in `commit`.
     fresh = (H_kv, d, like): the call is the first into this layer; an empty DynamicLayer of a plain DynamicCache is replaced by an
     append-in-place one with room for the call and as many positions again (`_prefill_append_layer`) -- kv8: by a `Kv8Layer`,
-    which is written through its own `update` (`lay` stays None)."""
-    __slots__ = ("cache", "idx", "n", "window", "lay", "T0")
+    which is written through its own `update` (`lay` stays None).
+    codes = (H_kv, d, device) (a filled extend with kv8_continued): a filled `Kv8Layer` becomes `lay8` with room for the call; the
+    rotary kernel writes dense new rows, `attend8` quantises them behind the `T0` cached positions and attends over the codes,
+    `commit` sets the layer's length."""
+    __slots__ = ("cache", "idx", "n", "window", "lay", "T0", "lay8")
 
-    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None, kv8: bool = False):
+    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None, kv8: bool = False, codes=None):
         self.cache, self.idx, self.n, self.window, self.T0 = cache, idx, n, window, 0
-        lay = None
+        lay = self.lay8 = None
         if cache is not None:
             if fresh is not None:   # (kv8: a `Kv8Layer` goes there and None comes back -- the step commits through its `update`)
                 lay = _prefill_append_layer(cache, idx, B, fresh[0], n, fresh[1], fresh[2], kv8)
@@ -635,6 +658,8 @@ class _KVWrite:
                 if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:   # (a reordered or re-batched layer: `_room` re-homes it)
                     self.T0 = lay._room(n, lay.keys if like is None else like)
                 else:
+                    if codes is not None and type(lay) is Kv8Layer:
+                        self.lay8, self.T0 = lay, lay._room(n, B, *codes)
                     lay = None
         self.lay = lay
 
@@ -659,8 +684,20 @@ class _KVWrite:
             K, V = K.contiguous(), V.contiguous()    # (not a view the band kernel reads where it lies)
         return K, V, 0
 
+    def attend8(self, q, kc, vc, heads: int, scale: float, kv_start):
+        """The `lay8` case: the dense new rows kc / vc (B, H_kv, n, d) as codes and scales at positions T0 .. T0 + n - 1, then the n
+        new queries q (B, n, heads d) over positions lo .. T0 + n - 1 of the codes (a window W: lo as in `views`)."""
+        n, W, lay = self.n, self.window, self.lay8
+        T1 = self.T0 + n
+        lo = 0 if W is None else max(0, T1 - (n + W - 1))
+        bufs = (lay._kc, lay._vc, lay._ks, lay._vs)
+        ops.kv_quantize_rows(kc, vc, *bufs, self.T0)
+        return ops.attention_kv8_rows(q, *bufs, T1 - lo, heads, scale, window=W, kv_start=kv_start, k_first=lo)
+
     def commit(self, kc=None, vc=None) -> None:
-        if self.lay is not None:
+        if self.lay8 is not None:
+            self.lay8._T = self.T0 + self.n
+        elif self.lay is not None:
             self.lay._commit(self.T0 + self.n)
         elif self.cache is not None:
             self.cache.update(kc, vc, self.idx)
@@ -695,20 +732,25 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
         q3 = qkv.view(B, S, -1)
         _, kv_start, kv_len = st.stack.pad
         filled = extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0
-        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x), kv8=st.stack.kv8)
+        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x), kv8=st.stack.kv8,
+                      codes=(Hkv, d, x.device) if filled and st.stack.kv8x else None)
         lay = kv.lay
         r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
                              qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
                              kv_out=None if lay is None else (lay._kb, lay._vb), kv_pos=kv.T0)
         kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
-        if filled:
-            K, V, _ = kv.views(kc, vc)
-        else:   # its own keys / values: columns of the q|k|v rows
-            K, V = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
-        # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros.  extend: query i sees
-        # its own key and the window - 1 before it
-        ctx = ops.attention_gqa_band(q3[..., :Hq * d], K, V, Hq, Hkv, float(att.scaling), window=window if extend else None,
-                                     kv_start=kv_start, kv_len=kv_len, causal=True)
+        if kv.lay8 is not None:   # an e4m3 cache (kv8_continued): over the codes, the quantised new rows included
+            ctx = kv.attend8(q3[..., :Hq * d], kc, vc, Hq, float(att.scaling), kv_start)
+            kv8_extend_stats["extend" if kv_start is None else "padded_extend"] += 1
+        else:
+            if filled:
+                K, V, _ = kv.views(kc, vc)
+            else:   # its own keys / values: columns of the q|k|v rows
+                K, V = q3[..., Hq * d:(Hq + Hkv) * d], q3[..., (Hq + Hkv) * d:]
+            # a padded batch: the key range of each sequence inside the kernel; padding rows come back as zeros.  extend: query i sees
+            # its own key and the window - 1 before it
+            ctx = ops.attention_gqa_band(q3[..., :Hq * d], K, V, Hq, Hkv, float(att.scaling), window=window if extend else None,
+                                         kv_start=kv_start, kv_len=kv_len, causal=True)
         ctx2 = ctx.view(rows, Hq * d)
         h = ops.gemm(ctx2, Wo, bias=bo, residual=x2)
         _lora_add(h, ctx2, g_o)   # (after the residual epilogue: the same terms)
@@ -955,17 +997,24 @@ def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False, kv8: bool
     return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
 
 
-def _extend_layer_ok(cache, layer_idx: int, sliding: bool) -> bool:
+def _extend_layer_ok(cache, layer_idx: int, sliding: bool, kv8=None) -> bool:
     """Whether the continued prefill takes this layer of `cache`: a plain HF DynamicCache (no offloading) whose layer is a
     DynamicLayer, the append-in-place layer or -- sliding=True: a layer with an attention window -- a DynamicSlidingWindowLayer,
     empty or filled; a layer the cache would still create lazily as a DynamicLayer counts.  Static, quantized and offloaded
-    caches and other layer classes: no."""
+    caches and other layer classes: no.  kv8 = (B, S, query heads per kv head) of the call (the kv8_continued switch, else None):
+    a `Kv8Layer` too -- filled, on the GPU, holding this batch, at most 16 query heads per kv head (the test route() makes for the
+    decode step) and no more than KV8_EXTEND_MAX_ROWS new positions."""
     layers = _plain_layers(cache)
     if layers is None:
         return False
     if layer_idx >= len(layers):
         return getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER
-    return type(layers[layer_idx]) in (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
+    lay = layers[layer_idx]
+    if kv8 is not None and type(lay) is Kv8Layer:
+        B, S, G = kv8
+        return (lay.get_seq_length() > 0 and lay._kc is not None and lay._kc.shape[0] == B and lay._kc.is_cuda and G <= 16
+                and (KV8_EXTEND_MAX_ROWS is None or S <= KV8_EXTEND_MAX_ROWS))
+    return type(lay) in (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
 
 
 @dataclass(slots=True, eq=False)
@@ -1695,7 +1744,8 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
-                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False, kv8: bool = False) -> int:
+                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False, kv8_continued: bool = False,
+                         kv8: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
@@ -1703,7 +1753,7 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
                  fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
-                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head, kv8=kv8)
+                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head, kv8_continued=kv8_continued, kv8=kv8)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
