@@ -388,6 +388,17 @@ int u2tok_qk_norm_rope(void* qkv, const void* wq, const void* wk, const void* co
 int u2tok_qk_norm_rope_kv(void* qkv, const void* wq, const void* wk, const void* cos, const void* sin, int32_t cos_sin_f32,
                           int64_t rows, int32_t Hq, int32_t Hkv, int32_t D, int64_t ld, int64_t cs_ld, float eps,
                           void* k_cache, void* v_cache, int32_t S, int64_t kv_stride, int32_t s_off, u2tok_stream_t stream);
+/* u2tok_qk_norm_rope_kv on an FP8 (e4m3) KV cache (u2tok_kv_quantize_rows below: the format), in ONE launch: the q and k columns of
+ * qkv get the bits u2tok_qk_norm_rope_kv leaves there; the finished k heads and the v heads are written as codes into positions
+ * s_off .. s_off + S - 1 of the dense buffers k_codes / v_codes (B = rows / S, Hkv, capacity, D) bytes (16-byte aligned) and their
+ * scales into k_scales / v_scales (B, Hkv, capacity) fp32 -- quantised from the values rounded to the element type, so codes and
+ * scales have the bits of u2tok_qk_norm_rope_kv into dense 16-bit rows followed by u2tok_kv_quantize_rows of those rows (=
+ * ops.quantize_kv_fp8).  No 16-bit K / V row is written.  Everything u2tok_qk_norm_rope_kv refuses, a null or misaligned buffer,
+ * S < 1, s_off < 0, s_off + S > capacity, capacity * D >= 2^31: U2TOK_ERR_ARG, nothing launched, nothing written. */
+int u2tok_qk_norm_rope_kv8(void* qkv, const void* wq, const void* wk, const void* cos, const void* sin, int32_t cos_sin_f32,
+                           int64_t rows, int32_t Hq, int32_t Hkv, int32_t D, int64_t ld, int64_t cs_ld, float eps, void* k_codes,
+                           void* v_codes, float* k_scales, float* v_scales, int32_t S, int32_t capacity, int32_t s_off,
+                           u2tok_stream_t stream);
 /* out[r][i] = bf16(silu(gate_up[r][i])) * gate_up[r][I + i]   (LlamaMLP / Qwen3MLP with gate | up packed); I % 8 == 0 */
 int u2tok_swiglu_bf16(const void* gate_up, void* out, int64_t rows, int32_t I, int64_t ld_in, int64_t ld_out,
                       u2tok_stream_t stream);
@@ -544,6 +555,41 @@ int u2tok_decoder_decode_stack_head(const u2tok_decode_stack_layer* L, int32_t n
                                     int32_t cos_sin_f32, int64_t cs_ld, int32_t batched, const int32_t* kv_start, int32_t tail_norm,
                                     void* out, const u2tok_decode_head_desc* head, float* logits, int64_t ld_logits, void* workspace,
                                     size_t workspace_bytes, u2tok_stream_t stream);
+/* ---- the whole-stack step, and the step with the head, on an FP8 (e4m3) KV cache: u2tok_decoder_decode_stack /
+ * u2tok_decoder_decode_stack_head with every layer's cache as the dense code buffers k_codes / v_codes (B, Hkv, capacity, D) bytes
+ * and scales k_scales / v_scales (B, Hkv, capacity) fp32 of u2tok_decoder_decode_post_kv8.  Per layer the launches are those of
+ * u2tok_decoder_decode_pre with u2tok_qk_norm_rope_kv8 in the rotary kernel's place -- the step's k / v rows go to position s_off
+ * as codes in that launch, no 16-bit row is written and nothing is quantised afterwards -- followed by those of
+ * u2tok_decoder_decode_post_kv8 from u2tok_decode_attention_kv8 on: as many launches as a layer of the 16-bit stack step has, and
+ * every value -- hidden rows, codes, scales, logits -- has the bits the per-layer calls on such a cache give it.  The attention is
+ * always the batched form (no `batched` argument; Hq / Hkv <= 16) over positions k_first .. s_off, kv_start counted from k_first.
+ * All weight forms, adapter groups, tail_norm, w_final_norm and the head: as in the 16-bit entries.  The workspace has their layout
+ * and their size on the same (cfg, T): u2tok_decoder_decode_stack_kv8_workspace_bytes / _head_kv8_workspace_bytes (0: descriptors
+ * they refuse), 256-byte aligned, the ticket in its first 4 bytes.
+ * EVERY refusal of every layer and of the head precedes the first launch -- everything the 16-bit entries refuse, everything
+ * u2tok_qk_norm_rope_kv8 and u2tok_decode_attention_kv8 refuse (a null or misaligned code or scale buffer among them), and
+ * 0 <= k_first <= s_off < capacity with T == s_off - k_first + 1 violated: U2TOK_ERR_ARG / U2TOK_ERR_WORKSPACE, and no code, scale,
+ * hidden row or logit was written. */
+typedef struct u2tok_decode_stack_layer_kv8 {
+  const u2tok_decode_config* cfg;    /* per layer: wform may differ between layers */
+  const u2tok_decode_layer*  layer;
+  void *k_codes, *v_codes;           /* (B, Hkv, capacity, D) bytes */
+  float *k_scales, *v_scales;        /* (B, Hkv, capacity) fp32 */
+  int32_t capacity;
+  int32_t s_off;                     /* position the step's k / v rows are written at */
+  int32_t k_first, T;                /* attention reads positions k_first .. k_first + T - 1 = s_off */
+} u2tok_decode_stack_layer_kv8;
+size_t u2tok_decoder_decode_stack_kv8_workspace_bytes(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers);
+int u2tok_decoder_decode_stack_kv8(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers, const void* x, const void* cos,
+                                   const void* sin, int32_t cos_sin_f32, int64_t cs_ld, const int32_t* kv_start,
+                                   const void* w_final_norm /* NULL: none */, float final_eps, int32_t tail_norm, void* out,
+                                   void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
+size_t u2tok_decoder_decode_stack_head_kv8_workspace_bytes(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers,
+                                                           const u2tok_decode_head_desc* head);
+int u2tok_decoder_decode_stack_head_kv8(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers, const void* x, const void* cos,
+                                        const void* sin, int32_t cos_sin_f32, int64_t cs_ld, const int32_t* kv_start, int32_t tail_norm,
+                                        void* out, const u2tok_decode_head_desc* head, float* logits, int64_t ld_logits,
+                                        void* workspace, size_t workspace_bytes, u2tok_stream_t stream);
 /* ---- products on FP8 weights (weight-only: OCP e4m3 codes, one fp32 scale per weight row; activations, biases, norms,
  * attention and the KV cache stay in the element type).  A product is exactly x . (scale[n] * e4m3(W8[n][:])) with fp32
  * accumulation -- the codes are widened to the element type in registers, where every e4m3 value is exact --, so all the loss is

@@ -87,6 +87,12 @@ class DecodeStackLayer(C.Structure):   # u2tok_decode_stack_layer: one layer of 
                 ("kv_stride", C.c_int64), ("s_off", C.c_int32), ("k_first", C.c_int32), ("T", C.c_int32)]
 
 
+class DecodeStackLayerKv8(C.Structure):   # u2tok_decode_stack_layer_kv8: one layer of the whole-stack step on an e4m3 KV cache
+    _fields_ = [("cfg", C.c_void_p), ("layer", C.c_void_p), ("k_codes", C.c_void_p), ("v_codes", C.c_void_p),
+                ("k_scales", C.c_void_p), ("v_scales", C.c_void_p), ("capacity", C.c_int32), ("s_off", C.c_int32),
+                ("k_first", C.c_int32), ("T", C.c_int32)]
+
+
 class DecodeHead(C.Structure):    # u2tok_decode_head_desc: the final RMSNorm and the output matrix of a decode step's head
     _fields_ = [("w_norm", C.c_void_p), ("W", C.c_void_p), ("scale", C.c_void_p), ("E", C.c_int32), ("V", C.c_int32),
                 ("wform", C.c_int32), ("eps", C.c_float), ("ldw", C.c_int64), ("lds", C.c_int64)]
@@ -167,6 +173,9 @@ SIGNATURES = {
     "u2tok_qk_norm_rope": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp]),
     "u2tok_qk_norm_rope_kv": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _vp, _i32,
                                      _i64, _i32, _vp]),
+    # qkv, wq, wk, cos, sin, cos_sin_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, k_codes, v_codes, k_scales, v_scales, S, capacity, s_off, stream
+    "u2tok_qk_norm_rope_kv8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i32,
+                                      _i32, _i32, _vp]),
     "u2tok_swiglu_bf16": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp]),
     "u2tok_decoder_decode_workspace_bytes": (_sz, [_vp, _i32]),
     # cfg, layer, x, cos, sin, cos_sin_f32, cs_ld, qkv, k_cache, v_cache, kv_stride, s_off, workspace, workspace_bytes, stream
@@ -187,6 +196,13 @@ SIGNATURES = {
     # workspace_bytes, stream
     "u2tok_decoder_decode_stack_head": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _sz,
                                                _vp]),
+    # (on an e4m3 KV cache: DecodeStackLayerKv8 layers, no `batched`)
+    "u2tok_decoder_decode_stack_kv8_workspace_bytes": (_sz, [_vp, _i32]),
+    # layers, n_layers, x, cos, sin, cos_sin_f32, cs_ld, kv_start, w_final_norm, final_eps, tail_norm, out, workspace, workspace_bytes, stream
+    "u2tok_decoder_decode_stack_kv8": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
+    "u2tok_decoder_decode_stack_head_kv8_workspace_bytes": (_sz, [_vp, _i32, _vp]),
+    # layers, n_layers, x, cos, sin, cos_sin_f32, cs_ld, kv_start, tail_norm, out, head, logits, ld_logits, workspace, workspace_bytes, stream
+    "u2tok_decoder_decode_stack_head_kv8": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "u2tok_gemm_rows_w8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "u2tok_gemm_rows_w8_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     # A, W4, S, C, bias, R, M, N, K, lda, ldw, lds, ldc, ldr, flags, stream

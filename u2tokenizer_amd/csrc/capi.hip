@@ -358,6 +358,13 @@ int u2tok_qk_norm_rope_kv(void* qkv, const void* wq, const void* wk, const void*
   return qk_norm_rope(BFW(qkv), BF(wq), BF(wk), cos, sin, cos_sin_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, BFW(k_cache),
                       BFW(v_cache), S, kv_stride, s_off, ST(stream));
 }
+int u2tok_qk_norm_rope_kv8(void* qkv, const void* wq, const void* wk, const void* cos, const void* sin, int32_t cos_sin_f32,
+                           int64_t rows, int32_t Hq, int32_t Hkv, int32_t D, int64_t ld, int64_t cs_ld, float eps, void* k_codes,
+                           void* v_codes, float* k_scales, float* v_scales, int32_t S, int32_t capacity, int32_t s_off,
+                           u2tok_stream_t stream) {
+  return qk_norm_rope_kv8(BFW(qkv), BF(wq), BF(wk), cos, sin, cos_sin_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, reinterpret_cast<uint8_t*>(k_codes),
+                          reinterpret_cast<uint8_t*>(v_codes), k_scales, v_scales, S, capacity, s_off, ST(stream));
+}
 static DecodeCfg dec_cfg(const u2tok_decode_config* c) {
   DecodeCfg d;
   d.B = c->B; d.E = c->E; d.Hq = c->Hq; d.Hkv = c->Hkv; d.D = c->D; d.I = c->I;
@@ -424,18 +431,32 @@ int u2tok_decoder_decode_post_kv8(const u2tok_decode_config* c, const u2tok_deco
   return decoder_decode_post_kv8(cfg, d, BF(x), BF(qkv), kv, kv_start, BFW(out), workspace, workspace_bytes, ST(stream));
 }
 // ---- the whole-stack step (decoder.hip): the layers' descriptors decoded as the two per-layer entries decode theirs, nothing kept
-static int stack_args(const u2tok_decode_stack_layer* L, int32_t n, std::vector<DecodeStackLayer>& v) {
+extern "C++" {
+// (the cache of one layer, per kind of descriptor)
+static void stack_cache(const u2tok_decode_stack_layer& l, DecodeStackLayer& s) {
+  s.kc = BFW(l.k_cache); s.vc = BFW(l.v_cache);
+  s.kv_stride = l.kv_stride;
+}
+static void stack_cache(const u2tok_decode_stack_layer_kv8& l, DecodeStackLayer& s) {
+  s.kv8 = true;
+  s.Kc = reinterpret_cast<uint8_t*>(l.k_codes); s.Vc = reinterpret_cast<uint8_t*>(l.v_codes);
+  s.Ks = l.k_scales; s.Vs = l.v_scales;
+  s.capacity = l.capacity;
+}
+template <typename Layer>  // u2tok_decode_stack_layer or u2tok_decode_stack_layer_kv8
+static int stack_args(const Layer* L, int32_t n, std::vector<DecodeStackLayer>& v) {
   if (!L || n <= 0) return U2_ERR_ARG;
   try { v.resize((size_t)n); } catch (const std::bad_alloc&) { return U2_ERR_ARG; }
   for (int32_t i = 0; i < n; ++i) {
     DecodeStackLayer& s = v[(size_t)i];
     const int e = dec_args(L[i].cfg, L[i].layer, s.cfg, s.layer);
     if (e != U2_OK) return e;
-    s.kc = BFW(L[i].k_cache); s.vc = BFW(L[i].v_cache);
-    s.kv_stride = L[i].kv_stride; s.s_off = L[i].s_off; s.k_first = L[i].k_first; s.T = L[i].T;
+    stack_cache(L[i], s);
+    s.s_off = L[i].s_off; s.k_first = L[i].k_first; s.T = L[i].T;
   }
   return U2_OK;
 }
+}  // extern "C++"
 size_t u2tok_decoder_decode_stack_workspace_bytes(const u2tok_decode_stack_layer* L, int32_t n_layers) {
   std::vector<DecodeStackLayer> v;
   return stack_args(L, n_layers, v) == U2_OK ? decoder_decode_stack_workspace_bytes(v.data(), n_layers) : 0;
@@ -485,6 +506,40 @@ int u2tok_decoder_decode_stack_head(const u2tok_decode_stack_layer* L, int32_t n
   if (e != U2_OK) return e;
   return decoder_decode_stack_head(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, batched != 0, kv_start, tail_norm != 0, BFW(out), d,
                                    logits, ld_logits, workspace, workspace_bytes, ST(stream));
+}
+// ---- the whole-stack step and the step with the head on an e4m3 KV cache: the same two walks over layers marked kv8, always with
+// the batched decode attention
+size_t u2tok_decoder_decode_stack_kv8_workspace_bytes(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers) {
+  std::vector<DecodeStackLayer> v;
+  return stack_args(L, n_layers, v) == U2_OK ? decoder_decode_stack_workspace_bytes(v.data(), n_layers) : 0;
+}
+int u2tok_decoder_decode_stack_kv8(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                                   int32_t cos_sin_f32, int64_t cs_ld, const int32_t* kv_start, const void* w_final_norm, float final_eps,
+                                   int32_t tail_norm, void* out, void* workspace, size_t workspace_bytes, u2tok_stream_t stream) {
+  std::vector<DecodeStackLayer> v;
+  const int e = stack_args(L, n_layers, v);
+  if (e != U2_OK) return e;
+  return decoder_decode_stack(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, true, kv_start, BF(w_final_norm), final_eps,
+                              tail_norm != 0, BFW(out), workspace, workspace_bytes, ST(stream));
+}
+size_t u2tok_decoder_decode_stack_head_kv8_workspace_bytes(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers,
+                                                           const u2tok_decode_head_desc* head) {
+  std::vector<DecodeStackLayer> v;
+  DecodeHead d;
+  if (stack_args(L, n_layers, v) != U2_OK || head_args(head, d) != U2_OK) return 0;
+  return decoder_decode_stack_head_workspace_bytes(v.data(), n_layers, d);
+}
+int u2tok_decoder_decode_stack_head_kv8(const u2tok_decode_stack_layer_kv8* L, int32_t n_layers, const void* x, const void* cos, const void* sin,
+                                        int32_t cos_sin_f32, int64_t cs_ld, const int32_t* kv_start, int32_t tail_norm, void* out,
+                                        const u2tok_decode_head_desc* head, float* logits, int64_t ld_logits, void* workspace,
+                                        size_t workspace_bytes, u2tok_stream_t stream) {
+  std::vector<DecodeStackLayer> v;
+  DecodeHead d;
+  int e = stack_args(L, n_layers, v);
+  if (e == U2_OK) e = head_args(head, d);
+  if (e != U2_OK) return e;
+  return decoder_decode_stack_head(v.data(), n_layers, BF(x), cos, sin, cos_sin_f32, cs_ld, true, kv_start, tail_norm != 0, BFW(out), d, logits,
+                                   ld_logits, workspace, workspace_bytes, ST(stream));
 }
 // ---- the few-rows product (gemm_rows.hip): one filler for the five exports; a quantised form without its scales is refused here
 static int rows(WForm form, const void* A, const void* W, const void* scale, int64_t lds, void* C, const void* bias, const void* R,

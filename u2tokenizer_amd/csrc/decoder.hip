@@ -145,6 +145,115 @@ int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* co
   return launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------ q / k: head norm + rotary, k / v: quantising append
+// qk_norm_rope_kernel on an FP8 (e4m3) KV cache (decode_attn.hip: the format): the same work split and the same q and k columns of
+// qkv, bit for bit; where that kernel writes the finished k head and copies the v head to 16-bit cache rows, this one writes them
+// as codes -- D bytes at row (b Hkv + h) cap + s_off + s of kcd / vcd, one fp32 scale at that row of ksc / vsc --, quantised from
+// the values ROUNDED to the element type (k: what it has just stored in qkv; v: the row as it stands there).  So codes and scales
+// have the bits of kv_quantize_rows_kernel on the 16-bit rows qk_norm_rope_kernel would have written: the row maximum is exact in
+// any order (idle lanes hold 0), the two divisions are IEEE fp32.  No 16-bit K / V row is written anywhere.
+// Stores: v_cvt_pk_fp8_f32 leaves a lane's codes l and l + D/2 in bytes 0 and 1 of one register, and they go out as two
+// global_store_byte, the second after one shift (read in the ISA: one conversion, one v_lshrrev, two byte stores, the scale's
+// global_store_dword).  A store's up to 64 bytes are one contiguous run, the same lines dword stores would touch; collecting four
+// lanes' codes into a dword first costs cross-lane moves and selects per half and still leaves two store instructions -- it saves
+// active lanes only, on one row per (sequence, kv head).
+template <int D, typename CS>
+__global__ __launch_bounds__(256) void qk_norm_rope_kv8_kernel(bf16_t* __restrict__ qkv, const bf16_t* __restrict__ wq,
+                                                               const bf16_t* __restrict__ wk, const CS* __restrict__ cosp,
+                                                               const CS* __restrict__ sinp, int64_t rows, int Hq, int Hkv, int64_t ld,
+                                                               int64_t cs_ld, float eps, uint8_t* __restrict__ kcd,
+                                                               uint8_t* __restrict__ vcd, float* __restrict__ ksc,
+                                                               float* __restrict__ vsc, int S, int cap, int s_off) {
+  const int lane = threadIdx.x & 63;
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nh = Hq + 2 * Hkv;
+  if (item >= rows * nh) return;
+  const int64_t row = item / nh;
+  const int hh = (int)(item - row * nh);
+  bf16_t* p = qkv + row * ld + (int64_t)hh * D;  // k heads follow the q heads in the packed row, v heads the k heads
+  constexpr int HALF = D / 2;
+  const bool on = lane < HALF;
+  const bool is_v = hh >= Hq + Hkv;
+  float a = 0.f, b = 0.f;
+  if (on) {
+    a = bf16_to_f32(p[lane]);
+    b = bf16_to_f32(p[lane + HALF]);
+  }
+  if (!is_v) {  // a q or k head: qk_norm_rope_kernel's arithmetic and rounding points
+    const bf16_t* w = hh < Hq ? wq : wk;
+    if (w) {
+      const float rstd = rsqrtf(wave_sum(a * a + b * b) / (float)D + eps);
+      if (on) {
+        a = bf16_to_f32(f32_to_bf16(a * rstd)) * bf16_to_f32(w[lane]);
+        b = bf16_to_f32(f32_to_bf16(b * rstd)) * bf16_to_f32(w[lane + HALF]);
+        a = bf16_to_f32(f32_to_bf16(a));
+        b = bf16_to_f32(f32_to_bf16(b));
+      }
+    }
+    if (on) {
+      const CS* cr = cosp + row * cs_ld;
+      const CS* sr = sinp + row * cs_ld;
+      const float c0 = (float)cr[lane], c1 = (float)cr[lane + HALF], s0 = (float)sr[lane], s1 = (float)sr[lane + HALF];
+      const bf16_t r0 = f32_to_bf16(a * c0 - b * s0), r1 = f32_to_bf16(b * c1 + a * s1);  // rotate_half(x) = (-x2, x1)
+      p[lane] = r0;
+      p[lane + HALF] = r1;
+      a = bf16_to_f32(r0);  // (the cache row is quantised from the rounded values)
+      b = bf16_to_f32(r1);
+    }
+    if (hh < Hq) return;
+  }
+  // the row as codes: kv_quantize_rows_kernel's arithmetic (wave-uniform from here: a k or a v head)
+  const float am = wave_max(fmaxf(fabsf(a), fabsf(b)));
+  const float scale = am > 0.f ? am / 448.f : 1.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int c = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a / scale, -448.f), 448.f), fminf(fmaxf(b / scale, -448.f), 448.f), 0, false);
+#else
+  const int c = 0;
+#endif
+  const int hk = hh - Hq - (is_v ? Hkv : 0);
+  const int64_t bi = row / S, si = row - bi * S;
+  const int64_t pos = (bi * Hkv + hk) * cap + s_off + si;
+  if (on) {
+    uint8_t* dst = (is_v ? vcd : kcd) + pos * D;
+    dst[lane] = (uint8_t)c;
+    dst[lane + HALF] = (uint8_t)(c >> 8);
+  }
+  if (lane == 0) (is_v ? vsc : ksc)[pos] = scale;
+}
+
+// (the refusals alone: qk_norm_rope_check's, and of the destination what kv_quantize_rows refuses of its own)
+static int qk_norm_rope_kv8_check(const bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int64_t rows, int Hq,
+                                  int Hkv, int D, const uint8_t* kcd, const uint8_t* vcd, const float* ksc, const float* vsc, int S, int capacity,
+                                  int s_off) {
+  if (!kcd || !vcd || !ksc || !vsc || capacity <= 0 || S <= 0 || s_off < 0 || (int64_t)s_off + S > capacity) return U2_ERR_ARG;
+  if ((((uintptr_t)kcd | (uintptr_t)vcd) & 15) || (((uintptr_t)ksc | (uintptr_t)vsc) & 3)) return U2_ERR_ARG;
+  int64_t kv_stride = (int64_t)capacity * D;  // (rows of D elements: that check's room for s_off + S is the one made above)
+  if (const int e = qk_norm_rope_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, reinterpret_cast<const bf16_t*>(kcd),
+                                       reinterpret_cast<const bf16_t*>(vcd), S, kv_stride, s_off))
+    return e;
+  return (int64_t)capacity * D >= (1ll << 31) ? U2_ERR_ARG : U2_OK;
+}
+
+int qk_norm_rope_kv8(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32, int64_t rows, int Hq,
+                     int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, uint8_t* kcd, uint8_t* vcd, float* ksc, float* vsc, int S,
+                     int capacity, int s_off, hipStream_t stream) {
+  if (const int e = qk_norm_rope_kv8_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, kcd, vcd, ksc, vsc, S, capacity, s_off)) return e;
+  const int64_t items = rows * (Hq + 2 * Hkv);
+  ProfScope ps(PROF_ROWOP, 0, stream, (double)items * D * 4.0);
+  dim3 grid((unsigned)cdiv(items, 4));
+#define U2_QK8(D_, T_)                                                                                                        \
+  hipLaunchKernelGGL((qk_norm_rope_kv8_kernel<D_, T_>), grid, dim3(256), 0, stream, qkv, wq, wk, reinterpret_cast<const T_*>(cosp), \
+                     reinterpret_cast<const T_*>(sinp), rows, Hq, Hkv, ld, cs_ld, eps, kcd, vcd, ksc, vsc, S, capacity, s_off)
+  if (D == 128 && cs_is_f32) U2_QK8(128, float);
+  else if (D == 128) U2_QK8(128, Bf16Val);
+  else if (D == 96 && cs_is_f32) U2_QK8(96, float);   // (lanes 48..63 of each wave idle)
+  else if (D == 96) U2_QK8(96, Bf16Val);
+  else if (cs_is_f32) U2_QK8(64, float);
+  else U2_QK8(64, Bf16Val);
+#undef U2_QK8
+  return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------ SwiGLU
 // out[r][i] = silu(gu[r][i]) * gu[r][I + i]   (LlamaMLP / Qwen3MLP: down_proj(act_fn(gate_proj(x)) * up_proj(x)) with the
 // gate | up projections packed into one GEMM); the reference rounds silu(gate) to bf16 before the product: kept.
@@ -206,6 +315,14 @@ struct Step {
     const int64_t ld = (int64_t)(Hq + 2 * Hkv) * D;
     return check() ? qk_norm_rope_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, kc, vc, 1, kv_stride, s_off)
                    : qk_norm_rope(qkv, wq, wk, cosp, sinp, cs_is_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, kc, vc, 1, kv_stride, s_off, st);
+  }
+  // (the same on an e4m3 cache: the step's k / v rows go to position q8.s_off of its buffers as codes)
+  int rope8(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32, int rows, int Hq, int Hkv, int D,
+            int64_t cs_ld, float eps, const DecodeKv8& q8) const {
+    const int64_t ld = (int64_t)(Hq + 2 * Hkv) * D;
+    return check() ? qk_norm_rope_kv8_check(qkv, wq, wk, cosp, sinp, rows, Hq, Hkv, D, q8.Kc, q8.Vc, q8.Ks, q8.Vs, 1, q8.capacity, q8.s_off)
+                   : qk_norm_rope_kv8(qkv, wq, wk, cosp, sinp, cs_is_f32, rows, Hq, Hkv, D, ld, cs_ld, eps, q8.Kc, q8.Vc, q8.Ks, q8.Vs, 1, q8.capacity,
+                                      q8.s_off, st);
   }
   int swiglu(const bf16_t* gu, bf16_t* act, int rows, int I) const {
     return check() ? swiglu_check(gu, act, rows, I, 2 * I, I) : swiglu_bf16(gu, act, rows, I, 2 * I, I, st);
@@ -303,10 +420,13 @@ static int check_then_run(hipStream_t st, const Half& half) {
 
 // input RMSNorm -> q|k|v projection -> per-head RMSNorm + rotary; qkv (B, (Hq + 2 Hkv) D) keeps the finished queries, kc / vc
 // (B, Hkv, 1, D) receive the new cache entries.  have_xn (the whole-stack step): the norm rode in the tail of the product that wrote x.
+// q8 (the whole-stack step on an e4m3 cache): the new entries go to position q8->s_off of its buffers as codes, in the rotary
+// kernel's launch (qk_norm_rope_kv8); kc / vc are not read.
 static int dec_pre(const Step& s, const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
-                   int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes, bool have_xn) {
+                   int64_t cs_ld, bf16_t* qkv, bf16_t* kc, bf16_t* vc, int64_t kv_stride, int s_off, void* ws, size_t ws_bytes, bool have_xn,
+                   const DecodeKv8* q8 = nullptr) {
   if (s.check()) {  // the half's own refusals; everything below is a launcher's
-    if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || !kc || !vc || !ws) return U2_ERR_ARG;
+    if (c.B <= 0 || c.B > 64 || c.Hkv <= 0 || c.Hq % c.Hkv || !x || !l.w_in_norm || !l.Wqkv || !qkv || (!q8 && (!kc || !vc)) || !ws) return U2_ERR_ARG;
     if (!wform_step_ok(c, l, 0, 1)) return U2_ERR_ARG;
     if (ws_bytes < (size_t)c.B * c.E * sizeof(bf16_t)) return U2_ERR_WORKSPACE;
   }
@@ -316,8 +436,9 @@ static int dec_pre(const Step& s, const DecodeCfg& c, const DecodeLayer& l, cons
   int e = have_xn ? U2_OK : s.norm(x, l.w_in_norm, xn, c.B, c.E, c.E, c.eps);
   if (e == U2_OK) e = dec_linear(s, xn, c.E, l.Wqkv, l.scale_qkv, c.form, l.bqkv, qkv, nq, c.B, c.E, nq, nullptr, 0, false);
   if (e == U2_OK && lr) e = dec_lora(s, lr, lr->qkv, lr->n_qkv, 3, xn, c.E, qkv, nq, c.B, c.E);  // (before the head norm and the rotary embedding)
-  if (e == U2_OK) e = s.rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, cs_ld, c.qk_eps, kc, vc, kv_stride, s_off);
-  return e;
+  if (e != U2_OK) return e;
+  return q8 ? s.rope8(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, cs_ld, c.qk_eps, *q8)
+            : s.rope(qkv, l.wq_norm, l.wk_norm, cosp, sinp, cs_is_f32, c.B, c.Hq, c.Hkv, c.D, cs_ld, c.qk_eps, kc, vc, kv_stride, s_off);
 }
 
 int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const void* cosp, const void* sinp, int cs_is_f32,
@@ -331,7 +452,8 @@ int decoder_decode_pre(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x
 // attention over the cache (keys split over workgroups) -> out projection + residual -> RMSNorm -> gate|up -> SwiGLU -> down
 // projection + residual.  K / V: (B, Hkv, T, D) with kv_stride elements between (batch, kv head) entries (0: dense); out (B, E).
 // (batched: decode_attn.hip's kernel over all sequences with kv_start, else one attention() launch pair per sequence -- B <= 16
-// only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG.  q8: an e4m3 cache, decoder_decode_post_kv8)
+// only: 17 .. 64 sequences take the batched kernel or U2_ERR_ARG.  q8: an e4m3 cache, decoder_decode_post_kv8; with k_new and
+// v_new both null -- the whole-stack step, whose rotary kernel has put the step's rows at s_off already -- no quantising launch)
 // The whole-stack step's tail norms -- ticket (null: none): the post-attention norm is asked for in the tail of the o product, and
 // `after` (w set: the norm that follows this layer -- the next layer's input norm or the stack's final one, into after->Yn) in the
 // tail of the down product; *after_done: that launch carried it.  A product followed by an adapter group keeps the norm's own
@@ -362,8 +484,9 @@ static int dec_post(const Step& s, const DecodeCfg& c, const DecodeLayer& l, con
   const DecodeLora* lr = l.lora;
   int e = U2_OK;
   if (q8) {  // the step's rows into position s_off as codes, then the attention over positions k_first .. s_off
-    e = kv_quantize_rows(q8->k_new, q8->v_new, c.B, c.Hkv, 1, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, q8->Kc, q8->Vc,
-                         q8->Ks, q8->Vs, q8->capacity, q8->s_off, s.check(), s.st);
+    if (q8->k_new || q8->v_new)
+      e = kv_quantize_rows(q8->k_new, q8->v_new, c.B, c.Hkv, 1, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, (int64_t)c.Hkv * c.D, c.D, c.D, q8->Kc, q8->Vc,
+                           q8->Ks, q8->Vs, q8->capacity, q8->s_off, s.check(), s.st);
     if (e == U2_OK)
       e = decode_attention_kv8(qkv, q8->Kc + (int64_t)q8->k_first * c.D, q8->Vc + (int64_t)q8->k_first * c.D, q8->Ks + q8->k_first,
                                q8->Vs + q8->k_first, ctx, c.B, c.Hq, c.Hkv, T, c.D, nq, (int64_t)q8->capacity * c.D, q8->capacity, qd, c.scale,
@@ -419,7 +542,7 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
 int decoder_decode_post_kv8(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* x, const bf16_t* qkv, const DecodeKv8& kv,
                             const int* kv_start, bf16_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
   const int64_t T = (int64_t)kv.s_off - kv.k_first + 1;
-  if (T <= 0 || T > 0x7fffffff) return U2_ERR_ARG;
+  if (T <= 0 || T > 0x7fffffff || !kv.k_new || !kv.v_new) return U2_ERR_ARG;  // (this entry always quantises: its rows are the caller's)
   return check_then_run(st, [&](const Step& s) {
     return dec_post(s, c, l, x, qkv, nullptr, nullptr, (int)T, 0, true, kv_start, out, ws, ws_bytes, nullptr, nullptr, nullptr, &kv);
   });
@@ -432,6 +555,8 @@ int decoder_decode_post_kv8(const DecodeCfg& c, const DecodeLayer& l, const bf16
 // owns the workspace; every launch that uses it leaves it zero), the layers' shared per-layer workspace (the largest
 // decoder_decode_workspace_bytes of them), the q|k|v rows, the two hidden rows.
 // tail_norm: the three norms that follow an o or a down product ride in that product's tail (dec_post).
+// A layer on an e4m3 cache (DecodeStackLayer::kv8): the same walk, the same workspace; its first half's rotary kernel writes the
+// step's rows as codes (qk_norm_rope_kv8), its second half attends over the codes -- as many launches as a 16-bit layer has.
 static size_t stack_layer_ws(const DecodeStackLayer* L, int n) {
   size_t m = 0;
   for (int i = 0; i < n; ++i) m = std::max(m, decoder_decode_workspace_bytes(L[i].cfg, L[i].T));
@@ -463,6 +588,8 @@ static int stack_walk(const Step& s, const DecodeStackLayer* L, int n, const bf1
       if (sl.cfg.B != L[0].cfg.B || sl.cfg.E != L[0].cfg.E || sl.T <= 0 || sl.k_first < 0 || sl.s_off < 0 ||
           (int64_t)sl.k_first + sl.T > (int64_t)sl.s_off + 1)
         return U2_ERR_ARG;
+      // (an e4m3 cache: the attention reads up to the step's own row, 0 <= k_first <= s_off < capacity, and only in its batched form)
+      if (sl.kv8 && (!batched || sl.s_off >= sl.capacity || (int64_t)sl.T != (int64_t)sl.s_off - sl.k_first + 1)) return U2_ERR_ARG;
     }
     const size_t need = decoder_decode_stack_workspace_bytes(L, n);
     if (need == 0) return U2_ERR_ARG;
@@ -484,7 +611,10 @@ static int stack_walk(const Step& s, const DecodeStackLayer* L, int n, const bf1
     const DecodeStackLayer& sl = L[i];
     const bool last = i == n - 1;
     bf16_t* nxt = last && !w_final ? out : hid[i & 1];
-    int e = dec_pre(s, sl.cfg, sl.layer, cur, cosp, sinp, cs_is_f32, cs_ld, qkv, sl.kc, sl.vc, sl.kv_stride, sl.s_off, lws, lws_bytes, have_xn);
+    // (an e4m3 cache: the rotary kernel appends the codes, the second half finds the rows in place -- no k_new / v_new)
+    const DecodeKv8 q8v{nullptr, nullptr, sl.Kc, sl.Vc, sl.Ks, sl.Vs, sl.capacity, sl.k_first, sl.s_off};
+    const DecodeKv8* q8 = sl.kv8 ? &q8v : nullptr;
+    int e = dec_pre(s, sl.cfg, sl.layer, cur, cosp, sinp, cs_is_f32, cs_ld, qkv, sl.kc, sl.vc, sl.kv_stride, sl.s_off, lws, lws_bytes, have_xn, q8);
     if (e != U2_OK) return e;   // (a null cache buffer among them: nothing below offsets one)
     RowsNorm after;  // the norm that follows the layer: the next layer's input norm into its xn, or the final norm into out
     if (!last) after.w = L[i + 1].layer.w_in_norm, after.Yn = xn, after.eps = L[i + 1].cfg.eps;
@@ -493,8 +623,8 @@ static int stack_walk(const Step& s, const DecodeStackLayer* L, int n, const bf1
     after.ticket = ticket;
     bool done = false;  // the down product's tail carried `after` (never in a check walk: the norm's own refusals are asked for)
     const int64_t first = (int64_t)sl.k_first * sl.cfg.D;
-    e = dec_post(s, sl.cfg, sl.layer, cur, qkv, sl.kc + first, sl.vc + first, sl.T, sl.kv_stride, batched, kv_start, nxt, lws, lws_bytes, ticket,
-                 after.w ? &after : nullptr, &done);
+    e = dec_post(s, sl.cfg, sl.layer, cur, qkv, q8 ? nullptr : sl.kc + first, q8 ? nullptr : sl.vc + first, sl.T, sl.kv_stride, batched, kv_start,
+                 nxt, lws, lws_bytes, ticket, after.w ? &after : nullptr, &done, q8);
     if (e == U2_OK && last && w_final && !done) e = s.norm(nxt, w_final, out, c0.B, c0.E, c0.E, final_eps);
     if (e != U2_OK) return e;
     have_xn = done && !last;

@@ -363,6 +363,11 @@ int rmsnorm_bf16(const bf16_t* x, const bf16_t* w, bf16_t* y, int64_t rows, int 
 int qk_norm_rope(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32,
                  int64_t rows, int Hq, int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, bf16_t* kc, bf16_t* vc, int S,
                  int64_t kv_stride, int s_off, hipStream_t stream);
+// (qk_norm_rope on an e4m3 cache: the finished k heads and the v heads as codes and scales at positions s_off .. s_off + S - 1 of
+//  the dense buffers -- the bits of qk_norm_rope into 16-bit rows followed by kv_quantize_rows, in one launch)
+int qk_norm_rope_kv8(bf16_t* qkv, const bf16_t* wq, const bf16_t* wk, const void* cosp, const void* sinp, int cs_is_f32, int64_t rows, int Hq,
+                     int Hkv, int D, int64_t ld, int64_t cs_ld, float eps, uint8_t* kcd, uint8_t* vcd, float* ksc, float* vsc, int S,
+                     int capacity, int s_off, hipStream_t stream);
 int swiglu_bf16(const bf16_t* gu, bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out, hipStream_t stream);
 int swiglu_check(const bf16_t* gu, const bf16_t* out, int64_t rows, int I, int64_t ld_in, int64_t ld_out);  // its refusals alone
 struct DecodeCfg {  // one decode step of a decoder layer (decoder.hip)
@@ -414,12 +419,20 @@ int decoder_decode_post(const DecodeCfg& c, const DecodeLayer& l, const bf16_t* 
 // One layer of the whole-stack step (capi.hip decodes u2tok_decode_stack_layer into it): the layer's two halves on its
 // append-in-place cache buffers kc / vc (B, Hkv, capacity, D; kv_stride = capacity * D).  The step's k / v rows go to position
 // s_off, the attention reads positions k_first .. k_first + T - 1 <= s_off.
+// kv8 (capi.hip decodes u2tok_decode_stack_layer_kv8 into it): the layer's cache is e4m3 -- the dense code buffers Kc / Vc (B, Hkv,
+// capacity, D) bytes and scales Ks / Vs (B, Hkv, capacity) of DecodeKv8 below; the step's rows go to position s_off as codes in the
+// first half's rotary launch (qk_norm_rope_kv8), the attention -- batched only -- reads the codes of positions k_first .. s_off, so
+// T = s_off - k_first + 1 and s_off < capacity; kc / vc / kv_stride are not read.
 struct DecodeStackLayer {
   DecodeCfg cfg;
   DecodeLayer layer;
-  bf16_t *kc, *vc;
-  int64_t kv_stride;
+  bf16_t *kc = nullptr, *vc = nullptr;
+  int64_t kv_stride = 0;
   int s_off, k_first, T;
+  bool kv8 = false;
+  uint8_t *Kc = nullptr, *Vc = nullptr;
+  float *Ks = nullptr, *Vs = nullptr;
+  int capacity = 0;
 };
 // Every layer's pre and post in one call, the hidden state through the workspace, the final RMSNorm (w_final: null = the last hidden
 // state as it is) into out; every refusal of every layer before the first launch.  tail_norm: gemm_rows' RowsNorm for the norms
@@ -481,6 +494,7 @@ int attention_kv8_rows(const bf16_t* q, const uint8_t* Kc, const uint8_t* Vc, co
 // The second half of a layer's decode step on such a cache: the step's new 16-bit rows k_new / v_new (B, Hkv, 1, D; dense: what
 // decoder_decode_pre wrote) are quantised into position s_off of the dense buffers (capacity positions per (batch, kv head)
 // entry), the attention -- always the batched kernel -- reads positions k_first .. s_off, kv_start counted from k_first.
+// (Inside the whole-stack step k_new / v_new are null: the rows are in the buffers already and nothing is quantised.)
 struct DecodeKv8 {
   const bf16_t *k_new, *v_new;
   uint8_t *Kc, *Vc;

@@ -168,6 +168,78 @@ int main() {
   lay[0].w_in_norm = nullptr;
   expect("joint: layer 0 input norm null", joint(&good, sneed), U2TOK_ERR_ARG);
   lay[0].w_in_norm = P;
+  // ---- the same two entries on an e4m3 KV cache (u2tok_decoder_decode_stack_kv8, u2tok_decoder_decode_stack_head_kv8): the walk
+  // is the 16-bit one over layers whose first half appends codes (u2tok_qk_norm_rope_kv8's refusals) and whose second half attends
+  // over them (u2tok_decode_attention_kv8's); every refusal below comes from the check walk, with and without the head behind it
+  {
+    constexpr int n8 = 2, CAP = 256;
+    float* F = reinterpret_cast<float*>(mem);
+    u2tok_decode_stack_layer_kv8 L8[n8];
+    for (int i = 0; i < n8; ++i) L8[i] = u2tok_decode_stack_layer_kv8{&cfg[i], &lay[i], P, P, F, F, CAP, T - 1, 0, T};
+    const size_t need8 = u2tok_decoder_decode_stack_kv8_workspace_bytes(L8, n8);
+    expect("kv8: workspace bytes are the 16-bit step's", (long long)need8, (long long)u2tok_decoder_decode_stack_workspace_bytes(L, n8));
+    const size_t sneed8 = u2tok_decoder_decode_stack_head_kv8_workspace_bytes(L8, n8, &good);
+    expect("kv8: stack + head workspace bytes", (long long)sneed8, (long long)(need8 + hneed));
+    expect("kv8: workspace bytes of no layers", (long long)u2tok_decoder_decode_stack_kv8_workspace_bytes(L8, 0), 0);
+    expect("kv8: workspace bytes of null layers", (long long)u2tok_decoder_decode_stack_kv8_workspace_bytes(nullptr, n8), 0);
+    expect("kv8: stack + head workspace bytes of a null head", (long long)u2tok_decoder_decode_stack_head_kv8_workspace_bytes(L8, n8, nullptr), 0);
+    auto both = [&](const char* what, int want, size_t cut = 0) {
+      for (int tail = 0; tail < 2; ++tail) {
+        expect(what, u2tok_decoder_decode_stack_kv8(L8, n8, P, P, P, 1, 64, nullptr, P, 1e-6f, tail, P, P, need8 - cut, nullptr), want);
+        expect(what, u2tok_decoder_decode_stack_head_kv8(L8, n8, P, P, P, 1, 64, nullptr, tail, P, &good, LG, V, P, sneed8 - cut, nullptr), want);
+      }
+    };
+    L8[1].k_scales = nullptr;
+    both("kv8: layer 1 with a null scale buffer", U2TOK_ERR_ARG);
+    L8[1].k_scales = F;
+    L8[1].v_codes = nullptr;
+    both("kv8: layer 1 with a null code buffer", U2TOK_ERR_ARG);
+    L8[1].v_codes = P;
+    L8[1].k_codes = Pc + 8;
+    both("kv8: codes 8 bytes off alignment", U2TOK_ERR_ARG);
+    L8[1].k_codes = P;
+    L8[1].v_scales = reinterpret_cast<float*>(Pc + 2);
+    both("kv8: scales 2 bytes off alignment", U2TOK_ERR_ARG);
+    L8[1].v_scales = F;
+    L8[1].capacity = T - 1;
+    both("kv8: s_off == capacity", U2TOK_ERR_ARG);
+    L8[1].capacity = 1 << 25;
+    both("kv8: capacity * D >= 2^31", U2TOK_ERR_ARG);
+    L8[1].capacity = CAP;
+    L8[1].k_first = 1;
+    both("kv8: T != s_off - k_first + 1", U2TOK_ERR_ARG);
+    L8[1].k_first = -1;
+    both("kv8: a negative first position", U2TOK_ERR_ARG);
+    L8[1].k_first = 0;
+    lay[1].Wo = Pc + 8;
+    both("kv8: 16-bit Wo 8 bytes off alignment behind a good layer 1 of 2", U2TOK_ERR_ARG);
+    lay[1].Wo = P;
+    cfg[1].Hq = 34;
+    expect("kv8: 17 query heads per kv head",
+           u2tok_decoder_decode_stack_kv8(L8, n8, P, P, P, 1, 64, nullptr, P, 1e-6f, 0, P, P, (size_t)1 << 30, nullptr), U2TOK_ERR_ARG);
+    cfg[1].Hq = 4;
+    both("kv8: short workspace", U2TOK_ERR_WORKSPACE, 1);
+    expect("kv8: null layers", u2tok_decoder_decode_stack_kv8(nullptr, n8, P, P, P, 1, 64, nullptr, P, 1e-6f, 0, P, P, need8, nullptr), U2TOK_ERR_ARG);
+    expect("kv8: joint with a null head",
+           u2tok_decoder_decode_stack_head_kv8(L8, n8, P, P, P, 1, 64, nullptr, 0, P, nullptr, LG, V, P, sneed8, nullptr), U2TOK_ERR_ARG);
+    expect("kv8: joint with room for the stack but not for the head",
+           u2tok_decoder_decode_stack_head_kv8(L8, n8, P, P, P, 1, 64, nullptr, 0, P, &good, LG, V, P, need8, nullptr), U2TOK_ERR_WORKSPACE);
+    // the rotary entry with the quantising append, by itself
+    auto rope8 = [&](void* kc, float* ks, int S, int cap, int s_off) {
+      return u2tok_qk_norm_rope_kv8(P, nullptr, nullptr, P, P, 1, 6, 4, 2, 64, 512, 64, 1e-6f, kc, P, ks, F, S, cap, s_off, nullptr);
+    };
+    expect("rope kv8: null codes", rope8(nullptr, F, 3, 16, 0), U2TOK_ERR_ARG);
+    expect("rope kv8: null scales", rope8(P, nullptr, 3, 16, 0), U2TOK_ERR_ARG);
+    expect("rope kv8: misaligned codes", rope8(Pc + 8, F, 3, 16, 0), U2TOK_ERR_ARG);
+    expect("rope kv8: s_off + S > capacity", rope8(P, F, 3, 16, 14), U2TOK_ERR_ARG);
+    expect("rope kv8: s_off + S overflows", rope8(P, F, 3, 16, 0x7fffffff), U2TOK_ERR_ARG);
+    expect("rope kv8: rows not a multiple of S", rope8(P, F, 4, 16, 0), U2TOK_ERR_ARG);
+    // the per-layer second half keeps its quantising launch: no rows, no call
+    expect("post_kv8: null new rows",
+           u2tok_decoder_decode_post_kv8(&cfg[0], &lay[0], P, P, nullptr, nullptr, P, P, F, F, CAP, 0, T - 1, nullptr, P, P,
+                                         u2tok_decoder_decode_workspace_bytes(&cfg[0], T), nullptr),
+           U2TOK_ERR_ARG);
+  }
   if (failures == 0) std::printf("stack_refusal_check: ok\n");
   return failures != 0;
 }

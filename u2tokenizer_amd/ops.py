@@ -1463,6 +1463,30 @@ def kv_quantize_rows(k: torch.Tensor, v: torch.Tensor, kc: torch.Tensor, vc: tor
 
 
 @_guarded
+def qk_norm_rope_kv8(qkv: torch.Tensor, q_norm_w, k_norm_w, cos: torch.Tensor, sin: torch.Tensor, heads: int, kv_heads: int,
+                     head_dim: int, eps: float, kc: torch.Tensor, vc: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor, S: int,
+                     s_off: int) -> torch.Tensor:
+    """`qk_norm_rope` with the quantising append in the same launch (u2tok_qk_norm_rope_kv8): in place on the q and k heads of qkv
+    (B S, (heads + 2 kv_heads) * head_dim); the finished k heads and the v heads go to positions s_off .. s_off + S - 1 of the dense
+    buffers as codes and scales, with the bits of `qk_norm_rope(..., kv_cache_seq=S)` followed by `kv_quantize_rows`.  Room in the
+    buffers is the library's to refuse."""
+    h = _lib.load_library()
+    _need(qkv, ELEM, "qkv")
+    B, Hkv, cap, D = _kv8_buffers("qk_norm_rope_kv8", kc, vc, ks, vs)
+    rows = qkv.shape[0]
+    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] != (heads + 2 * kv_heads) * head_dim or (Hkv, D) != (kv_heads, head_dim) \
+            or S <= 0 or rows != B * S:
+        raise RuntimeError(f"qk_norm_rope_kv8: qkv {tuple(qkv.shape)} against buffers {tuple(kc.shape)}, S {S}")
+    if cos.dtype != sin.dtype or cos.dtype not in (torch.float32, elem_dtype()) or cos.shape != (rows, head_dim) \
+            or sin.shape != cos.shape or cos.stride(1) != 1 or sin.stride(1) != 1 or cos.stride(0) != sin.stride(0):
+        raise RuntimeError("qk_norm_rope_kv8: cos / sin must be (rows, head_dim) fp32 or bf16 with equal strides")
+    _lib.check(h.u2tok_qk_norm_rope_kv8(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(cos), _ptr(sin), int(cos.dtype == torch.float32),
+                                        rows, heads, kv_heads, head_dim, qkv.stride(0), cos.stride(0), float(eps), _ptr(kc), _ptr(vc),
+                                        _ptr(ks), _ptr(vs), int(S), cap, int(s_off), _stream()), "u2tok_qk_norm_rope_kv8")
+    return qkv
+
+
+@_guarded
 def decode_attention_kv8(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor, T: int, heads: int,
                          scale: float, kv_start: Optional[torch.Tensor] = None, k_first: int = 0) -> torch.Tensor:
     """`decode_attention` over an e4m3 cache (u2tok_decode_attention_kv8): q (B, heads * d) rows in the element type; kc / vc

@@ -38,6 +38,8 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     u2tok_decoder_decode_stack_head -- the stack's final RMSNorm and lm_head, in `config.u2_fused_head_form`, fp32 logits) from
     `language_model._u2CausalLMMixin.forward` through `head_forward`; the head's descriptor and quantised copy live on the model
     (`_HeadState`), not in the stack's state.
+  * stack_kv8: `stack_route` also admits a cache whose every layer is a filled `Kv8Layer`; `_stack_step` then calls
+    u2tok_decoder_decode_stack_kv8 (with the head: _stack_head_kv8), whose rotary kernel writes the step's rows as codes.
   * kv8: the cache a fused prefill starts is a `Kv8Layer` (e4m3 codes and a scale per cached row) where the append-in-place layer
     would go; `route` takes it for the decode step alone (`_decode_step`: u2tok_decoder_decode_pre onto the scratch rows, then
     u2tok_decoder_decode_post_kv8, which quantises them into the layer's buffers and attends over the codes); every other route
@@ -144,20 +146,29 @@ SWITCHES = (
            "fp32 logits -- in the same library call (u2tok_decoder_decode_stack_head); `head_route` lists what it asks, every other "
            "call runs the module norm and nn.Linear as before; `config.u2_fused_head_form` (\"elem\", \"fp8\", \"fp4\") picks lm_head's "
            "weight form, the quantised ones unmeasured in accuracy on trained weights; `head_stats`"),
+    Switch("stack_kv8", "stack8", "u2_fused_stack_kv_fp8", False, ("stack_decode", "kv8"), (), (),
+           "a decode step on a cache of filled `Kv8Layer`s runs as ONE library call for the whole stack as well "
+           "(u2tok_decoder_decode_stack_kv8; with `head`, u2tok_decoder_decode_stack_head_kv8): the rotary kernel writes the step's "
+           "rows into the layers' buffers as codes (u2tok_qk_norm_rope_kv8), so a layer has as many launches as on the 16-bit "
+           "stack step, and every hidden row, code, scale and logit has the bits of the per-layer step on that cache; every layer "
+           "of the cache must be a filled `Kv8Layer` of this batch on the GPU with at most 16 query heads per kv head -- a cache "
+           "that mixes them with append-in-place layers keeps the per-layer routes, which keep their two-launch quantiser; the "
+           "continued prefill on codes and 17 .. 64 sequences are as `kv8_continued` and `wide_decode` have them; "
+           "`stack_kv8_stats`"),
     Switch("kv8_continued", "kv8x", "u2_fused_kv_fp8_continued", False, ("kv8", "continued"), (), (),
            "more than one new position against a filled `Kv8Layer` stays on the HIP layers: the new rows are quantised into the "
            "layer's buffers and the new queries attend over the codes, the new rows' included (u2tok_attention_kv8_rows: 16 rows "
            "of (position, query head) per workgroup, so the cache is read once per 16 such rows -- the form for few new positions; "
            "at most 16 query heads per kv head; a call of more than `KV8_EXTEND_MAX_ROWS` positions stays stock); what the cache "
            "holds defines the semantics, as on the stock route; left-padded continuations with `padded`; the whole-stack and head "
-           "calls stay out of scope; `kv8_extend_stats`"),
+           "calls on such a cache are `stack_kv8`'s, decode steps only; `kv8_extend_stats`"),
     Switch("kv8", "kv8", "u2_fused_kv_fp8", False, (), (), (),
            "the KV cache a fused prefill starts is FP8: a `Kv8Layer` (e4m3 codes, one fp32 scale per cached row of K and of V: half "
            "the cache's bytes in HBM and per decode step) where the append-in-place layer would go; the prefill commits through the "
            "layer's `update`, the decode step quantises its new rows and attends over the codes (u2tok_decoder_decode_post_kv8: "
            "always the batched decode attention, so at most 16 query heads per kv head); the continued prefill refuses the layer "
-           "(stock layers on the dequantised cache) and the whole-stack and head calls are out of scope on such a cache "
-           "(`stack_route` answers \"layers\", `head_route` \"stock\"); exact on the quantised cache, the quantiser's cost in "
+           "(stock layers on the dequantised cache) and the whole-stack and head calls keep off such a cache (`stack_route` answers "
+           "\"layers\", `head_route` \"stock\") unless `stack_kv8` is on; exact on the quantised cache, the quantiser's cost in "
            "accuracy is unmeasured on trained weights; `kv8_stats`.  `kv8_continued` keeps the continued prefill on the codes as well"),
 )
 
@@ -186,6 +197,9 @@ head_stats = {"head": 0, "fallback": 0, "form_fallback": 0}
 kv8_stats = {"decode": 0, "padded_decode": 0}
 # ... and the continued prefills (counted in `extend_stats` as well) that attended over the codes of such a cache (kv8_continued)
 kv8_extend_stats = {"extend": 0, "padded_extend": 0}
+# ... and the MODEL calls (counted in `stack_stats` as well) that ran as one whole-stack step on such a cache (stack_kv8); their layers
+# are counted in `stats` and `kv8_stats` as decode steps
+stack_kv8_stats = {"decode": 0, "padded_decode": 0}
 # the longest call (new positions per sequence) the continued prefill on an e4m3 cache takes, None: no cap.  The kernel streams the
 # cache once per 16 rows of (position, query head), so a long call could lose to the stock route's one dequantisation; the value is
 # the measurement's verdict (DESIGN f15: faster than the stock route at every measured length up to 1024, so no cap)
@@ -452,6 +466,7 @@ class _StackState:
     fp4: bool = False
     stack: bool = False
     head: bool = False
+    stack8: bool = False
     kv8x: bool = False
     kv8: bool = False
     pad: tuple = _NO_PAD      # the verdict on the call's mask: pad_rule's (kind, kv_start, kv_len), or None = stock (`_mask_hook`)
@@ -1304,7 +1319,7 @@ def _decode_step(self, x, pe, cache, window, pr):
 # ---------------------------------------------------------------------------------------------- the whole-stack decode step
 _MISSING = object()
 _STACK_ARGS = ("input_ids", "attention_mask", "position_ids", "past_key_values", "inputs_embeds", "use_cache")
-_STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep", "stack_head")   # what the step keeps in a (B, device, stream) scratch entry
+_STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep", "stack_head", "stack_arr8", "stack_keep8")   # what the step keeps in a (B, device, stream) scratch entry
 _PE_STUBS = {}
 
 
@@ -1359,7 +1374,10 @@ def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool
       * `_decode_state(...).ok` for every layer, one head dim and one hidden size for all of them;
       * every layer's cache entry one the per-layer step writes in place (`_KVWrite`: the append-in-place layer a fused prefill
         left, holding this batch): a plain DynamicLayer, a DynamicSlidingWindowLayer, an offloaded or static cache send the whole
-        call to the per-layer routes.
+        call to the per-layer routes;
+      * or, with `stack_kv8` on, EVERY layer's entry a filled `Kv8Layer` (the test `route()` makes for its "decode": this batch, on
+        the GPU, at most 16 query heads per kv head) -- the step then runs on the codes (u2tok_decoder_decode_stack_kv8); a cache
+        that mixes the two kinds, and any `Kv8Layer` with the switch off, send the call to the per-layer routes.
     plan (a list): receives one (layer, state, projections, `_Decode16`, scratch, window) per layer of a "stack" verdict."""
     stack = base.__dict__.get("_u2_stack")
     if stack is None or not stack.stack or grad or S != 1 or not is_cuda:
@@ -1394,7 +1412,12 @@ def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool
         hd, E = att.head_dim, E1
         idx = att.layer_idx
         lay = cl[idx] if idx < len(cl) else None
-        if lay is None or type(lay) is not _APPEND_LAYER or lay.keys.shape[0] != B:
+        if type(lay) is Kv8Layer:   # (route() said "decode": filled, this batch, on the GPU, at most 16 query heads per kv head)
+            if not stack.stack8:
+                return "layers"
+        elif lay is None or type(lay) is not _APPEND_LAYER or lay.keys.shape[0] != B:
+            return "layers"
+        if steps and type(lay) is not type(cl[steps[0][0].self_attn.layer_idx]):   # (one kind of cache for the whole call)
             return "layers"
         d, sc = _decode_state(layer, B, _base(pr[0]).weight.device, pr)
         if not d.ok:
@@ -1432,7 +1455,8 @@ def _stack_forward(self, *args, **kwargs):
 
 
 def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
-    """One decode step of the whole decoder stack in ONE library call (u2tok_decoder_decode_stack): per layer what `_decode_step`
+    """One decode step of the whole decoder stack in ONE library call (u2tok_decoder_decode_stack; on a cache of `Kv8Layer`s
+    u2tok_decoder_decode_stack_kv8, whose rotary kernel appends the step's rows as codes): per layer what `_decode_step`
     does around its two calls -- the weight form's copies, the adapters' operands and scratch, the layer descriptor's variant, room
     for one more row in the layer's cache buffers --, then the call, then every layer's commit.  The rotary tables come from ONE
     call of the stack's `rotary_emb`, as the layers receive them from the stock forward.
@@ -1454,12 +1478,15 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
-        arr = sc.get("stack_arr")
+        # (`stack_route`: one kind of cache per call -- append-in-place layers, or `Kv8Layer`s and the entries on codes)
+        q8 = type(cache.layers[plan[0][0].self_attn.layer_idx]) is Kv8Layer
+        k_arr, k_keep = ("stack_arr8", "stack_keep8") if q8 else ("stack_arr", "stack_keep")
+        arr = sc.get(k_arr)
         if arr is None or len(arr) != n:
-            arr = sc["stack_arr"] = (_lib.DecodeStackLayer * n)()
-            sc["stack_keep"] = [None] * n
+            arr = sc[k_arr] = ((_lib.DecodeStackLayerKv8 if q8 else _lib.DecodeStackLayer) * n)()
+            sc[k_keep] = [None] * n
             sc["stack_ws"] = None
-        keep = sc["stack_keep"]
+        keep = sc[k_keep]
         rows, lss, Tmax = [], [], 0
         for i, (layer, st, pr, d, _, window) in enumerate(plan):
             form = _weight_form(st, d, pr)
@@ -1471,13 +1498,22 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
             if v is None:
                 v = _decode_layer(st, form, ls is not None)
             lay = cache.layers[layer.self_attn.layer_idx]
-            T0 = lay._room(1, sc["kc"])
-            kb, vb = lay._kb, lay._vb
             slot = arr[i]
+            if q8:   # (as `_decode_step` derives them: room for the row, the buffers, the window's first position below)
+                T0 = lay._room(1, B, d.Hkv, d.hd, x.device)
+                kb = lay._kc
+            else:
+                T0 = lay._room(1, sc["kc"])
+                kb = lay._kb
             if keep[i] is None or keep[i][0] is not v or keep[i][1] is not kb:   # (rewrite what changed: a rebuilt variant, a re-homed buffer)
                 slot.cfg, slot.layer = C.addressof(v[3]), C.addressof(v[0])
-                slot.k_cache, slot.v_cache, slot.kv_stride = kb.data_ptr(), vb.data_ptr(), kb.stride(1)
-                keep[i] = (v, kb, vb)
+                if q8:
+                    slot.k_codes, slot.v_codes, slot.k_scales, slot.v_scales = (t.data_ptr() for t in (kb, lay._vc, lay._ks, lay._vs))
+                    slot.capacity = kb.shape[2]
+                    keep[i] = (v, kb, lay._vc, lay._ks, lay._vs)
+                else:
+                    slot.k_cache, slot.v_cache, slot.kv_stride = kb.data_ptr(), lay._vb.data_ptr(), kb.stride(1)
+                    keep[i] = (v, kb, lay._vb)
             T1 = T0 + 1
             first = 0 if window is None else max(0, T1 - window)
             slot.s_off, slot.k_first, slot.T = T0, first, T1 - first
@@ -1490,8 +1526,12 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
             for i in range(n):
                 arr[i].T = Tcap
             # (the head's normed rows behind the stack step's workspace: a workspace once sized for the head serves both calls)
-            need = (h.u2tok_decoder_decode_stack_workspace_bytes(arr, n) if head is None else
-                    h.u2tok_decoder_decode_stack_head_workspace_bytes(arr, n, head.ref))
+            # (the entries on codes size it as the 16-bit ones do on the same (cfg, T): one workspace serves both kinds)
+            if head is None:
+                need = (h.u2tok_decoder_decode_stack_kv8_workspace_bytes if q8 else h.u2tok_decoder_decode_stack_workspace_bytes)(arr, n)
+            else:
+                need = (h.u2tok_decoder_decode_stack_head_kv8_workspace_bytes if q8 else
+                        h.u2tok_decoder_decode_stack_head_workspace_bytes)(arr, n, head.ref)
             for i, (_, T1) in enumerate(rows):
                 arr[i].T = T1 - arr[i].k_first
             if need == 0:
@@ -1505,22 +1545,29 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
         left = kv_start is not None
         # (w_final_norm = NULL: the stack's final norm stays the module's own below, as on the per-layer routes -- the library's
         #  RMSNorm and the module's add a row's squares in another order, and one element in some ten thousand rounds the other way)
+        # (the entries on codes take no `batched`: an e4m3 cache always has the batched decode attention)
+        front = (arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32), cos.stride(0))
+        front += (() if q8 else (int(left or B > 16),)) + (kv_start.data_ptr() if left else None,)
         if head is None:
-            _lib.check(h.u2tok_decoder_decode_stack(arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32),
-                                                    cos.stride(0), int(left or B > 16), kv_start.data_ptr() if left else None,
-                                                    None, 0.0, int(STACK_TAIL_NORM),
-                                                    out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack")
+            name = "u2tok_decoder_decode_stack_kv8" if q8 else "u2tok_decoder_decode_stack"
+            _lib.check(getattr(h, name)(*front, None, 0.0, int(STACK_TAIL_NORM), out.data_ptr(), ws.data_ptr(), ws.numel(), stream), name)
         else:
+            name = "u2tok_decoder_decode_stack_head_kv8" if q8 else "u2tok_decoder_decode_stack_head"
             logits = torch.empty((B, 1, head.desc.V), dtype=torch.float32, device=x.device)
-            _lib.check(h.u2tok_decoder_decode_stack_head(
-                arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32), cos.stride(0),
-                int(left or B > 16), kv_start.data_ptr() if left else None, int(STACK_TAIL_NORM), out.data_ptr(), head.ref,
-                logits.data_ptr(), head.desc.V, ws.data_ptr(), ws.numel(), stream), "u2tok_decoder_decode_stack_head")
+            _lib.check(getattr(h, name)(*front, int(STACK_TAIL_NORM), out.data_ptr(), head.ref, logits.data_ptr(), head.desc.V,
+                                        ws.data_ptr(), ws.numel(), stream), name)
         for lay, T1 in rows:
-            lay._commit(T1)
+            if q8:
+                lay._T = T1
+            else:
+                lay._commit(T1)
+    key = "padded_decode" if left else "decode"
     for _, st, _, _, _, _ in plan:
         _count(st, "decode", B)
-    stack_stats["padded_decode" if left else "decode"] += 1
+    stack_stats[key] += 1
+    if q8:
+        kv8_stats[key] += n
+        stack_kv8_stats[key] += 1
     if head is not None:
         return out, logits
     return BaseModelOutputWithPast(last_hidden_state=base.norm(out), past_key_values=cache)
@@ -1744,8 +1791,8 @@ def _layer_protocol_ok(layer, base=None) -> bool:
 def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train: bool = False, prefill: bool = True,
                          padded: bool = False, continued: bool = False, fp8_decode: bool = False,
                          train_phi3: bool = False, wide_decode: bool = False, train_lora: bool = False, lora: bool = False,
-                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False, kv8_continued: bool = False,
-                         kv8: bool = False) -> int:
+                         fp4_decode: bool = False, stack_decode: bool = False, head: bool = False, stack_kv8: bool = False,
+                         kv8_continued: bool = False, kv8: bool = False) -> int:
     """Patch the decoder layers of an HF Llama / Qwen3 / Phi-3 causal LM (u2LlamaForCausalLM / u2Qwen3ForCausalLM /
     u2Phi3ForCausalLM included) for the fused prefill and the fused decode step.  Idempotent; returns the number of layers
     patched.  The keywords are the route switches: SWITCHES describes each once, the module docstring what they share.  Every
@@ -1753,7 +1800,8 @@ def enable_fused_prefill(model, decode: bool = True, strict: bool = True, train:
     `disable_fused_prefill` restores the stock forwards."""
     given = dict(decode=decode, strict=strict, train=train, prefill=prefill, padded=padded, continued=continued,
                  fp8_decode=fp8_decode, train_phi3=train_phi3, wide_decode=wide_decode, train_lora=train_lora, lora=lora,
-                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head, kv8_continued=kv8_continued, kv8=kv8)
+                 fp4_decode=fp4_decode, stack_decode=stack_decode, head=head, stack_kv8=stack_kv8, kv8_continued=kv8_continued,
+                 kv8=kv8)
     base = _stack_of(model)
     layers = getattr(base, "layers", None)
     if layers is None:
