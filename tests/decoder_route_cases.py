@@ -1,6 +1,7 @@
 """The cases of tests/test_gpu_decoder_route_bits.py: every host route of the decoder layers (prefill, continued prefill, decode
 step, training; u2tokenizer_amd/prefill.py) on two-layer decoders, pinned BIT FOR BIT in tests/golden/decoder_route_bits.json
-(and, the e2m1 decode step's, in tests/golden/decoder_route_bits_fp4.json): per
+(the e2m1 decode step's in tests/golden/decoder_route_bits_fp4.json; the routes over the kinds of cache layer -- FP8 KV cache,
+whole-stack step, head -- in tests/golden/decoder_route_bits_cache.json): per
 case the SHA-256 of each call's last hidden state, of every layer's cached keys and values, of the training cases' gradients, and
 the deltas of the route counters -- the route taken as well as the numbers.  Importable without a GPU (the host half of the test
 checks the case list and the inputs).
@@ -13,7 +14,7 @@ of 128 with attention and MLP biases (no head norm, the unfused gate|up branch);
 96, sliding_window 16.  A prefill has 70 positions (two 64-key tiles, the second ragged), a continuation 9, then 3 decode steps;
 all inputs are seeded `inputs_embeds`, the decode steps (B, 1, E), so that lm_head stays out.
 
-`python tests/decoder_route_cases.py --record --commit HASH [--fp4] [--out FILE]` runs every case of one fixture on the GPU and writes the fixture; the test
+`python tests/decoder_route_cases.py --record --commit HASH [--fp4 | --cache] [--out FILE]` runs every case of one fixture on the GPU and writes the fixture; the test
 itself only ever reads it."""
 import argparse
 import hashlib
@@ -104,8 +105,55 @@ FP4_COUNTERS = {
 }
 MIXED_INTER = (256, 320, 288)   # model M: a multiple of 128 (e2m1), of 64 only (e4m3), of 32 only (the element type)
 FIXTURE_FP4 = FIXTURE.with_name("decoder_route_bits_fp4.json")
-FIXTURES = {FIXTURE: CASES, FIXTURE_FP4: FP4_CASES}
-ALL_CASES = {**CASES, **FP4_CASES}
+# The routes over the kinds of cache layer -- the decode step and the continued prefill on an e4m3 cache (kv8, kv8_continued), the
+# whole-stack step on either kind (stack_decode, stack_kv8) and the head -- in a third fixture, recorded before those routes were
+# folded onto one cache-kind rule.  A `Kv8Layer`'s digests are of its codes and scales.  U = Q's sizes as a u2Qwen3ForCausalLM:
+# the switches come from its config, every call goes through the causal LM and the digests are of its `logits`.
+# mixed: after the prefill layer 1 of the cache is replaced by an append-in-place layer holding the same (dequantised) positions.
+KV8, KV8X, STACK, STACK8 = dict(kv8=True), dict(kv8_continued=True), dict(stack_decode=True), dict(stack_kv8=True)
+CACHE_CASES = {
+    "v-Q-kv8-decode": _case("Q", flags=KV8, steps=STEPS, expect=("stats.prefill", "kv8_stats.decode")),
+    "v-Q-kv8-decode-left-padded": _case("Q", flags=dict(KV8, padded=True), left=(0, 5), steps=STEPS,
+                                        expect=("stats.padded_prefill", "kv8_stats.padded_decode")),
+    "v-P-kv8-decode-past-window": _case("P", S=24, flags=dict(KV8, continued=True), steps=STEPS,
+                                        expect=("extend_stats.extend", "kv8_stats.decode")),
+    "v-Q-kv8-wide": _case("Q", B=17, flags=dict(KV8, wide_decode=True), steps=2, expect=("kv8_stats.decode", "wide_stats.decode")),
+    "w-Q-kv8-continued": _case("Q", flags=KV8X, chunk=CHUNK, steps=STEPS,
+                               expect=("stats.prefill", "kv8_extend_stats.extend", "kv8_stats.decode")),
+    "w-Q-kv8-continued-left-padded": _case("Q", flags=dict(KV8X, padded=True), left=(0, 5), chunk=CHUNK, steps=STEPS,
+                                           expect=("kv8_extend_stats.padded_extend", "kv8_stats.padded_decode")),
+    "w-P-kv8-continued-window": _case("P", S=24, flags=KV8X, chunk=CHUNK, expect=("extend_stats.extend", "kv8_extend_stats.extend")),
+    "x-Q-stack": _case("Q", flags=STACK, steps=STEPS, expect=("stack_stats.decode", "stats.decode")),
+    "x-Q-stack-left-padded": _case("Q", flags=dict(STACK, padded=True), left=(0, 5), steps=STEPS,
+                                   expect=("stack_stats.padded_decode", "stats.padded_decode")),
+    "x-P-stack-past-window": _case("P", S=24, flags=dict(STACK, continued=True), steps=STEPS, expect=("stack_stats.decode",)),
+    "x-Q-stack-fp8-lora": _case("Q", flags=dict(STACK, fp8_decode=True, lora=True), lora=LORA_TARGETS, steps=STEPS,
+                                expect=("stack_stats.decode", "w8_stats.decode", "lora_stats.decode")),
+    "x-M-stack-fp4-fp8": _case("M", flags=dict(STACK, fp4_decode=True, fp8_decode=True), steps=STEPS,
+                               expect=("stack_stats.decode", "w4_stats.decode", "w8_stats.decode")),
+    "y-Q-stack-kv8": _case("Q", flags=STACK8, steps=STEPS, expect=("stack_kv8_stats.decode", "stack_stats.decode", "kv8_stats.decode")),
+    "y-Q-stack-kv8-left-padded": _case("Q", flags=dict(STACK8, padded=True), left=(0, 5), steps=STEPS,
+                                       expect=("stack_kv8_stats.padded_decode", "kv8_stats.padded_decode")),
+    "y-P-stack-kv8-past-window": _case("P", S=24, flags=dict(STACK8, continued=True), steps=STEPS,
+                                       expect=("stack_kv8_stats.decode", "kv8_stats.decode")),
+    "y-Q-stack-kv8-mixed-cache": dict(_case("Q", flags=STACK8, steps=STEPS, expect=("stats.decode", "kv8_stats.decode")), mixed=True),
+    "z-U-head-elem": dict(_case("U", flags=dict(head=True), steps=STEPS, expect=("head_stats.head", "stack_stats.decode")), head_form="elem"),
+    "z-U-head-fp8": dict(_case("U", flags=dict(head=True), steps=STEPS, expect=("head_stats.head", "stack_stats.decode")), head_form="fp8"),
+    "z-U-head-elem-stack-kv8": dict(_case("U", flags=dict(STACK8, head=True), steps=STEPS,
+                                          expect=("head_stats.head", "stack_kv8_stats.decode")), head_form="elem"),
+}
+# exact deltas: the mixed cache ran layer by layer (no whole-stack call: one e4m3 and one 16-bit layer per step); the head cases
+# took the head at every step and the stock head for the prefill alone
+CACHE_COUNTERS = {
+    "y-Q-stack-kv8-mixed-cache": {"stats.prefill": 2, "stats.decode": 2 * STEPS, "kv8_stats.decode": STEPS},
+    "y-Q-stack-kv8": {"stats.prefill": 2, "stats.decode": 2 * STEPS, "kv8_stats.decode": 2 * STEPS, "stack_stats.decode": STEPS,
+                      "stack_kv8_stats.decode": STEPS},
+    "z-U-head-elem": {"stats.prefill": 2, "stats.decode": 2 * STEPS, "stack_stats.decode": STEPS, "head_stats.head": STEPS,
+                      "head_stats.fallback": 1},
+}
+FIXTURE_CACHE = FIXTURE.with_name("decoder_route_bits_cache.json")
+FIXTURES = {FIXTURE: CASES, FIXTURE_FP4: FP4_CASES, FIXTURE_CACHE: CACHE_CASES}
+ALL_CASES = {**CASES, **FP4_CASES, **CACHE_CASES}
 # the test functions (a few seconds each): the cases by what they exercise
 GROUPS = {
     "plain": ("a-Q-prefill", "b-Q-prefill-decode", "c-Q-decode-stock-cache", "d-L-prefill", "d-L-prefill-decode", "e-Q-f16"),
@@ -118,6 +166,8 @@ GROUPS = {
     "train": ("r-Q-train", "s-P-train-phi3", "t-Q-train-lora"),
 }
 FP4_GROUPS = {"fp4": tuple(FP4_CASES)}
+CACHE_GROUPS = {name: tuple(c for c in CACHE_CASES if c[0] == letter)
+                for name, letter in (("kv8", "v"), ("kv8-continued", "w"), ("stack", "x"), ("stack-kv8", "y"), ("head", "z"))}
 
 
 def case_ids(fixture=FIXTURE):
@@ -137,6 +187,9 @@ def build_model(kind):
         m = Qwen3ForCausalLM(cfg)
         for layer, inter in zip(m.model.layers, MIXED_INTER):
             layer.mlp = Qwen3MLP(Qwen3Config(**{**cfg.to_dict(), "intermediate_size": inter}))
+    elif kind == "U":   # Q's sizes as the project's causal LM (the head route lives in its forward)
+        from u2tokenizer_amd import language_model as LM
+        m = LM.u2Qwen3ForCausalLM(LM.u2Qwen3Config(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64, **common))
     elif kind == "Q":
         m = Qwen3ForCausalLM(Qwen3Config(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, head_dim=64, **common))
     elif kind == "L":
@@ -188,13 +241,16 @@ def mask(c, n):
 # ------------------------------------------------------------------------------------------------------------------ running a case
 def _sha(t):
     t = t.detach().contiguous().cpu()
+    if t.dtype == torch.uint8:   # (the codes of a `Kv8Layer`)
+        return hashlib.sha256(t.numpy().tobytes()).hexdigest()
     return hashlib.sha256(t.view(torch.int32 if t.dtype == torch.float32 else torch.int16).numpy().tobytes()).hexdigest()
 
 
 def _counters():
     from u2tokenizer_amd import decoder_train, prefill
     dicts = {"stats": prefill.stats, "extend_stats": prefill.extend_stats, "w8_stats": prefill.w8_stats, "w4_stats": prefill.w4_stats,
-             "wide_stats": prefill.wide_stats,
+             "wide_stats": prefill.wide_stats, "stack_stats": prefill.stack_stats, "head_stats": prefill.head_stats,
+             "kv8_stats": prefill.kv8_stats, "kv8_extend_stats": prefill.kv8_extend_stats, "stack_kv8_stats": prefill.stack_kv8_stats,
              "lora_stats": prefill.lora_stats, "train.stats": decoder_train.stats, "train.lora_stats": decoder_train.lora_stats}
     return {f"{n}.{k}": v for n, d in dicts.items() for k, v in d.items()}
 
@@ -227,24 +283,44 @@ def run_case(cid):
         S, B = c["S"], c["B"]
         cache = None if c["cache"] is None else DynamicCache(config=m.config) if c["cache"] == "config" else DynamicCache()
         x = embeds(c, "x_prefill", S).to(c["dtype"]).to(dev)
+        call = lambda **k: m.model(**k).last_hidden_state   # noqa: E731
+        if c["model"] == "U":   # (the causal LM sets the switches from its config at its first call)
+            from u2tokenizer_amd.prefill import SWITCHES
+            for s in SWITCHES:
+                if c["flags"].get(s.kw):
+                    setattr(m.config, s.config, True)
+            m.config.u2_fused_head_form = c["head_form"]
+            call = lambda **k: m(**k).logits   # noqa: E731
         with torch.no_grad():
-            if c["cache"] == "stock":   # (the stock layers fill the cache; its bits are not what the fixture is about)
+            if c["model"] == "U":
+                dig["prefill"] = _sha(call(inputs_embeds=x, past_key_values=cache, use_cache=True, **kw(S)))
+            elif c["cache"] == "stock":   # (the stock layers fill the cache; its bits are not what the fixture is about)
                 m.model(inputs_embeds=x, past_key_values=cache, use_cache=True, **kw(S))
                 enable_fused_prefill(m, **c["flags"])
             else:
                 enable_fused_prefill(m, **c["flags"])
                 dig["prefill"] = _sha(m.model(inputs_embeds=x, past_key_values=cache, use_cache=cache is not None, **kw(S)).last_hidden_state)
             T = S
+            if c.get("mixed"):
+                from u2tokenizer_amd import prefill
+                lay = prefill._append_layer_class()()
+                lay.update(cache.layers[1].keys, cache.layers[1].values)
+                cache.layers[1] = lay
             if c["chunk"]:
                 xc = embeds(c, "x_chunk", c["chunk"]).to(c["dtype"]).to(dev)
                 T += c["chunk"]
-                dig["chunk"] = _sha(m.model(inputs_embeds=xc, past_key_values=cache, use_cache=True, **kw(T)).last_hidden_state)
+                dig["chunk"] = _sha(call(inputs_embeds=xc, past_key_values=cache, use_cache=True, **kw(T)))
             for t in range(c["steps"]):
                 xs = embeds(c, f"x_step{t}", 1).to(c["dtype"]).to(dev)
                 T += 1
-                dig[f"step{t}"] = _sha(m.model(inputs_embeds=xs, past_key_values=cache, use_cache=True, **kw(T)).last_hidden_state)
+                dig[f"step{t}"] = _sha(call(inputs_embeds=xs, past_key_values=cache, use_cache=True, **kw(T)))
             if cache is not None:
                 for i, lay in enumerate(cache.layers):
+                    codes = lay.codes() if hasattr(lay, "codes") else None
+                    if codes is not None:   # a `Kv8Layer`: what it holds -- K codes, V codes, K scales, V scales
+                        assert codes[0].shape[0] == B and codes[0].shape[2] == cache.get_seq_length(i) == T, (cid, i, T)
+                        dig[f"keys{i}"], dig[f"values{i}"], dig[f"key_scales{i}"], dig[f"value_scales{i}"] = map(_sha, codes)
+                        continue
                     assert lay.keys.shape[0] == B and cache.get_seq_length(i) == T, (cid, i, T)
                     dig[f"keys{i}"], dig[f"values{i}"] = _sha(lay.keys), _sha(lay.values)
     torch.cuda.synchronize()
@@ -258,9 +334,10 @@ def main():
     ap.add_argument("--record", action="store_true", help="run every case on the GPU and write the fixture")
     ap.add_argument("--commit", default="", help="the commit whose Python is recorded (written into the file)")
     ap.add_argument("--fp4", action="store_true", help="the cases of decoder_route_bits_fp4.json instead")
+    ap.add_argument("--cache", action="store_true", help="the cases of decoder_route_bits_cache.json instead")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    fixture = FIXTURE_FP4 if a.fp4 else FIXTURE
+    fixture = FIXTURE_CACHE if a.cache else FIXTURE_FP4 if a.fp4 else FIXTURE
     a.out = a.out or str(fixture)
     if not a.record:
         print(f"{len(FIXTURES[fixture])} cases; --record writes their digests")

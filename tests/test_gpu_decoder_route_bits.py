@@ -1,7 +1,8 @@
 """The decoder layers' host routes, BIT FOR BIT: every case of tests/decoder_route_cases.py -- prefill, continued prefill, decode
 steps and training on two-layer Qwen3, Llama and Phi-3 decoders, under every route switch -- against
 tests/golden/decoder_route_bits.json (the e2m1 decode step's cases: decoder_route_bits_fp4.json, recorded likewise at the commit
-that brought that form), recorded once (twice, with equal results) with the Python of the commit named inside it on
+that brought that form; the FP8 KV cache's, the whole-stack step's and the head's: decoder_route_bits_cache.json, recorded before
+those routes were folded onto one cache-kind rule), recorded once (twice, with equal results) with the Python of the commit named inside it on
 this build of the library, before prefill.py's routes were rewritten around one switch table, one admission function and one
 descriptor cache.  Per case: the SHA-256 of each call's last hidden state, of every layer's cached keys and values, of the
 training cases' output and gradients, and the deltas of the route counters.  The kernels and their order did not change, so a
@@ -27,14 +28,17 @@ def fixture():
     return cases
 
 
+ALL_GROUPS = {**C.GROUPS, **C.FP4_GROUPS, **C.CACHE_GROUPS}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("group", list(C.GROUPS) + list(C.FP4_GROUPS))
+@pytest.mark.parametrize("group", list(ALL_GROUPS))
 def test_route_bits(fixture, group):
     assert torch.cuda.is_available(), "these tests need the MI355X"
     from u2tokenizer_amd import ops
     ops.device_check()
     bad = {}
-    for cid in {**C.GROUPS, **C.FP4_GROUPS}[group]:
+    for cid in ALL_GROUPS[group]:
         got, want = C.run_case(cid), fixture[cid]
         moved = sorted(k for k in set(got["digests"]) | set(want["digests"]) if got["digests"].get(k) != want["digests"].get(k))
         if moved or got["stats"] != want["stats"]:
@@ -44,10 +48,16 @@ def test_route_bits(fixture, group):
 
 # ------------------------------------------------------------------------------------------------------------- host: cases and inputs
 def test_fixture_lists_exactly_the_cases(fixture):
-    assert sorted(fixture) == sorted(C.ALL_CASES) == sorted(c for g in {**C.GROUPS, **C.FP4_GROUPS}.values() for c in g)
+    assert sorted(fixture) == sorted(C.ALL_CASES) == sorted(c for g in ALL_GROUPS.values() for c in g)
     for cid, want in C.FP4_COUNTERS.items():                  # the e2m1 cases: the form each layer ran in, exactly
         got = {k: v for k, v in fixture[cid]["stats"].items() if k.startswith(("w4_stats.", "w8_stats."))}
         assert got == want, (cid, got)
+    for cid, want in C.CACHE_COUNTERS.items():                # the mixed cache ran layer by layer; the head at every step
+        assert fixture[cid]["stats"] == want, (cid, fixture[cid]["stats"])
+    for cid, c in C.CACHE_CASES.items():                      # an e4m3 layer is pinned as what it holds: codes and scales
+        d = fixture[cid]["digests"]
+        kv8 = any(c["flags"].get(k) for k in ("kv8", "kv8_continued", "stack_kv8"))
+        assert [f"key_scales{i}" in d and f"value_scales{i}" in d for i in range(2)] == [kv8, kv8 and not c.get("mixed")], cid
     for cid, c in C.ALL_CASES.items():
         f = fixture[cid]
         for counter in c["expect"]:                       # the route the case is about was taken when it was recorded

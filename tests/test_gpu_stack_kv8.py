@@ -302,7 +302,7 @@ def test_every_refusal_comes_before_the_first_launch(ops, dt):
     for i in range(n):
         lay, _, _, cfg = m.model.layers[i]._u2_prefill.variants[(0, False)]
         cl = cache.layers[i]
-        T0 = cl._room(1, B, Hkv, 64, x.device)
+        T0 = cl._room(1, torch.empty(B, Hkv, 1, 64, device=x.device))
         s = arr[i]
         s.cfg, s.layer = C.addressof(cfg), C.addressof(lay)
         s.k_codes, s.v_codes, s.k_scales, s.v_scales = (t.data_ptr() for t in (cl._kc, cl._vc, cl._ks, cl._vs))

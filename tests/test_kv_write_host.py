@@ -108,6 +108,51 @@ def test_every_other_layer_goes_through_update_once():
     assert prefill._KVWrite(cache, 0, B + 1, 1, None, like=_like(B + 1)).lay is None
 
 
+def _codes(T=9, batch=B):
+    """a plain DynamicCache whose layer 0 is a `Kv8Layer` of T positions whose codes say they are on the GPU"""
+    from test_decoder_route_host import _FakeCuda
+    cache = DynamicCache()
+    lay = prefill.Kv8Layer()
+    kv = torch.arange(batch * H * T * D, dtype=torch.float32).view(batch, H, T, D)
+    lay.update(kv, -kv)
+    lay._kc = lay._kc.as_subclass(_FakeCuda)
+    cache.layers.append(lay)
+    return cache, lay
+
+
+def test_the_codes_kind():
+    cache, lay = _codes()
+    bufs = lay._buffers()
+    for n, like in ((1, _like()), (3, None)):                                 # the decode step's call and the continued prefill's
+        kv = prefill._KVWrite(cache, 0, B, n, 4, like=like)
+        assert kv.kind is prefill.KV8 and kv.lay is lay and kv.T0 == 9 and lay._buffers() == bufs
+        assert kv.first == 6                                                  # the last n + W - 1 of T0 + n: 9 + 1 - 4, whatever n
+        assert lay.get_seq_length() == 9                                      # (nothing is the layer's before `commit`)
+    kv = prefill._KVWrite(cache, 0, B, 1, None, like=_like())
+    assert kv.first == 0 and kv.T0 == 9
+    kv = prefill._KVWrite(cache, 0, B, 1, 40, like=_like())                   # a window longer than the cache: everything
+    assert kv.first == 0
+    kv.commit()
+    assert lay.get_seq_length() == 10 and lay.codes()[0].shape[2] == 10 and lay._buffers() == bufs
+    # a re-batched layer (batch selection: the codes now hold two sequences) is not written in place for a call of three ...
+    lay.batch_select_indices(torch.tensor([2, 0]))
+    kv = prefill._KVWrite(cache, 0, B, 1, None, like=_like())
+    assert kv.kind is not prefill.KV8 and kv.lay is None and kv.T0 == 0
+    new = torch.ones(B, H, 1, D)
+    try:                                                                      # ... and its own `update` refuses the rows
+        kv.views(new, -new)
+        raise AssertionError("a Kv8Layer took rows of another batch")
+    except RuntimeError as e:
+        assert "against a cache of" in str(e)
+    assert lay.get_seq_length() == 10
+    # ... nor are codes on the CPU, or an empty layer
+    cache, lay = _codes()
+    lay._kc = lay._kc.as_subclass(torch.Tensor)
+    assert prefill._KVWrite(cache, 0, B, 1, None, like=_like()).kind is not prefill.KV8
+    cache.layers[0] = prefill.Kv8Layer()
+    assert prefill._KVWrite(cache, 0, B, 1, None, like=_like()).lay is None
+
+
 def test_first_call_into_a_layer():
     cache = DynamicCache()
     x = torch.zeros(1)

@@ -177,15 +177,15 @@ def test_phi3_training_mode_with_residual_dropout_takes_the_stock_forward():
 
 def test_the_sliding_window_cache_layer_is_taken_only_for_windowed_layers():
     from transformers.cache_utils import DynamicCache, DynamicSlidingWindowLayer
-    from u2tokenizer_amd.prefill import _PackedLayout, _plain_dynamic_layer
+    from u2tokenizer_amd.kv_cache import DENSE, SLIDING, layer_kind
+    from u2tokenizer_amd.prefill import _PackedLayout
     m = _phi3(sliding_window=32)
     assert _PackedLayout.window(m.model.layers[0]) == 32
     cache = DynamicCache(config=m.config)
     assert type(cache.layers[0]) is DynamicSlidingWindowLayer
     kv = torch.zeros(1, 2, 5, 96)
     cache.update(kv, kv, 0)
-    assert _plain_dynamic_layer(cache, 0, sliding=True) is cache.layers[0]
-    assert _plain_dynamic_layer(cache, 0) is None
+    assert layer_kind(cache, 0, 1) == (SLIDING, cache.layers[0])     # (a kind of its own: `route` takes it under a window alone)
     plain = DynamicCache()
     plain.update(kv, kv, 0)
-    assert _plain_dynamic_layer(plain, 0) is plain.layers[0] and _plain_dynamic_layer(plain, 0, sliding=True) is plain.layers[0]
+    assert layer_kind(plain, 0, 1) == (DENSE, plain.layers[0])

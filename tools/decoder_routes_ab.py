@@ -8,7 +8,10 @@ Qwen3-8B layer shape with synthetic weights, and the microseconds `route` plus a
 
 Cells: decode B = 1 and B = 8 at T = 1024 on append-in-place caches; B = 8 left-padded (padded); B = 1 fp8_decode; B = 32
 wide_decode; B = 1 lora (r = 16 on all seven projections); B = 1 fp4_decode; B = 32 fp4_decode + wide_decode; B = 1 and B = 8
-stack_decode (the whole-stack step: one library call per token); prefill B = 1, S = 1024; and `route_us`, which needs no GPU: a patched
+stack_decode (the whole-stack step: one library call per token); on an FP8 KV cache (`Kv8Layer`s of T positions) B = 1 kv8, B = 8
+kv8 left-padded and B = 1 stack_kv8; B = 1 head (the whole-stack step with the head, through `prefill.head_forward`); a continued
+prefill of 16 positions against 1024 cached on codes (kv8_continued; the cache is cropped back after every call); prefill B = 1,
+S = 1024; and `route_us`, which needs no GPU: a patched
 layer's forward on the decode route with `_decode_step` replaced by a stub, on the CPU with a tensor that reports `is_cuda`
 (--host-only runs this cell alone and opens no GPU anywhere).
 
@@ -31,7 +34,7 @@ import time
 from pathlib import Path
 
 STEPS, E, INTER, HQ, HKV, HD, T = 16, 4096, 12288, 32, 8, 128, 1024
-# cell -> (batch, enable_fused_prefill keywords, left-padded, adapters)
+# cell -> (batch, enable_fused_prefill keywords, left-padded, adapters[, "kv8": the cache holds codes | "head": the step with the head])
 DECODE_CELLS = {
     "decode_b1": (1, {}, False, False),
     "decode_b8": (8, {}, False, False),
@@ -43,8 +46,13 @@ DECODE_CELLS = {
     "decode_b32_wide_fp4": (32, dict(fp4_decode=True, wide_decode=True), False, False),
     "decode_b1_stack": (1, dict(stack_decode=True), False, False),
     "decode_b8_stack": (8, dict(stack_decode=True), False, False),
+    "decode_b1_kv8": (1, dict(kv8=True), False, False, "kv8"),
+    "decode_b8_kv8_left_padded": (8, dict(kv8=True, padded=True), True, False, "kv8"),
+    "decode_b1_stack_kv8": (1, dict(stack_kv8=True), False, False, "kv8"),
+    "decode_b1_stack_head": (1, dict(head=True), False, False, "head"),
 }
-GPU_CELLS = list(DECODE_CELLS) + ["prefill_b1_s1024"]
+EXTEND_CELL, EXTEND_S = "extend_b1_s16_kv8", 16
+GPU_CELLS = list(DECODE_CELLS) + [EXTEND_CELL, "prefill_b1_s1024"]
 HOST_CELL = "route_us"
 
 
@@ -126,33 +134,63 @@ def child(a):
             ms.append(t0.elapsed_time(t1) / STEPS)
         return statistics.median(ms[1:])
 
-    for cell, (B, flags, padded, adapters) in DECODE_CELLS.items():
+    def codes_cache(B):
+        """`Kv8Layer`s holding T positions of noise"""
+        cache = prefill.kv8_cache(a.layers)
+        for lay in cache.layers:
+            lay.update(torch.randn(B, HKV, T, HD, device=dev, dtype=bf), torch.randn(B, HKV, T, HD, device=dev, dtype=bf))
+        return cache
+
+    for cell, (B, flags, padded, adapters, *kind) in DECODE_CELLS.items():
+        kind = kind[0] if kind else None
         if adapters:
             add_lora(m, r=16, alpha=32, dropout=0.0)
         prefill.enable_fused_prefill(m, **flags)
-        cache = DynamicCache(config=m.config)   # the append-in-place layers a fused prefill of T positions leaves, filled with noise
-        for li in range(a.layers):
-            lay = prefill._prefill_append_layer(cache, li, B, HKV, T, HD, like)
-            assert lay is not None, "this transformers' DynamicCache does not take the append-in-place layer"
-            lay._kb.normal_()
-            lay._vb.normal_()
-            lay._commit(T)
+        if kind == "kv8":
+            cache = codes_cache(B)
+        else:
+            cache = DynamicCache(config=m.config)   # the append-in-place layers a fused prefill of T positions leaves, filled with noise
+            for li in range(a.layers):
+                lay = prefill._prefill_append_layer(cache, li, B, HKV, T, HD, like)
+                assert lay is not None, "this transformers' DynamicCache does not take the append-in-place layer"
+                lay._kb.normal_()
+                lay._vb.normal_()
+                lay._commit(T)
         x = torch.randn(B, 1, E, device=dev, dtype=bf, generator=torch.Generator(device=dev).manual_seed(B))
         n = (a.rounds + 1) * STEPS
         masks = None
         if padded:   # (built outside the clock: sequence b has 3 b pads)
             full = (torch.arange(T + n, device=dev)[None, :] >= 3 * torch.arange(B, device=dev)[:, None]).long()
             masks = [full[:, :T + i + 1].contiguous() for i in range(n)]
-        s0, k0 = dict(prefill.stats), prefill.stack_stats["decode"]
-        out[cell] = timed(lambda i: m.model(inputs_embeds=x, past_key_values=cache, use_cache=True,
-                                            **({} if masks is None else {"attention_mask": masks[i]})))
+        whole = bool(flags.get("stack_decode") or flags.get("stack_kv8") or flags.get("head"))
+        s0, k0, q0, h0 = dict(prefill.stats), prefill.stack_stats["decode"], dict(prefill.kv8_stats), prefill.head_stats["head"]
+        if kind == "head":   # (the causal LM's route, asked for as `_u2CausalLMMixin.forward` asks)
+            out[cell] = timed(lambda i: prefill.head_forward(m, None, None, None, cache, x, True, None, {}).logits)
+        else:
+            out[cell] = timed(lambda i: m.model(inputs_embeds=x, past_key_values=cache, use_cache=True,
+                                                **({} if masks is None else {"attention_mask": masks[i]})))
         key = "padded_decode" if padded else "decode"
         assert prefill.stats[key] - s0[key] == n * a.layers, (cell, "the steps did not take the fused route")
-        assert prefill.stack_stats["decode"] - k0 == (n if flags.get("stack_decode") else 0), (cell, "whole-stack steps")
+        assert prefill.stack_stats["decode"] - k0 == (n if whole else 0), (cell, "whole-stack steps")
+        assert prefill.kv8_stats[key] - q0[key] == (n * a.layers if kind == "kv8" else 0), (cell, "steps on codes")
+        assert prefill.head_stats["head"] - h0 == (n if kind == "head" else 0), (cell, "steps with the head")
         prefill.disable_fused_prefill(m)
         if adapters:
             merge_lora(m)   # (B is zero: the weights are what they were)
         del cache
+    prefill.enable_fused_prefill(m, kv8_continued=True)
+    cache = codes_cache(1)
+    xe = torch.randn(1, EXTEND_S, E, device=dev, dtype=bf, generator=torch.Generator(device=dev).manual_seed(5))
+    s0 = prefill.kv8_extend_stats["extend"]
+
+    def extend(i):
+        m.model(inputs_embeds=xe, past_key_values=cache, use_cache=True)
+        cache.crop(T)   # (back to T cached positions: a length, nothing is copied)
+
+    out[EXTEND_CELL] = timed(extend)
+    assert prefill.kv8_extend_stats["extend"] - s0 == (a.rounds + 1) * STEPS * a.layers, (EXTEND_CELL, "the calls did not attend over the codes")
+    prefill.disable_fused_prefill(m)
+    del cache
     prefill.enable_fused_prefill(m)
     xs = torch.randn(1, 1024, E, device=dev, dtype=bf, generator=torch.Generator(device=dev).manual_seed(7))
     s0 = prefill.stats["prefill"]

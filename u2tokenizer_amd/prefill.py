@@ -31,22 +31,15 @@ does); `enable_fused_prefill` and `language_model._maybe_fuse` both walk that ta
     else, and goes when the switch goes off.  With `lora` the adapter branch follows each of the four products UNMERGED -- on
     many rows the down / up kernels of csrc/lora.hip, on a decode step the two-launch group product of csrc/lora_rows.hip
     inside the two library calls --, and a wrapper that is merged or disabled runs as its base layer.
-  * stack_decode: the decoder STACK's forward is wrapped as well; a decode step that `route` would hand to the fused step in every
-    layer (`stack_route`) runs as one library call for all of them (`_stack_step`: u2tok_decoder_decode_stack, the per-layer calls'
-    launches in their order), with the bits of the per-layer route; every other call goes on to the stack's own forward.
-  * head: a u2 causal LM's call that `head_route` admits runs the whole-stack step WITH its head (`_stack_step(..., head=)`:
-    u2tok_decoder_decode_stack_head -- the stack's final RMSNorm and lm_head, in `config.u2_fused_head_form`, fp32 logits) from
-    `language_model._u2CausalLMMixin.forward` through `head_forward`; the head's descriptor and quantised copy live on the model
-    (`_HeadState`), not in the stack's state.
-  * stack_kv8: `stack_route` also admits a cache whose every layer is a filled `Kv8Layer`; `_stack_step` then calls
-    u2tok_decoder_decode_stack_kv8 (with the head: _stack_head_kv8), whose rotary kernel writes the step's rows as codes.
-  * kv8: the cache a fused prefill starts is a `Kv8Layer` (e4m3 codes and a scale per cached row) where the append-in-place layer
-    would go; `route` takes it for the decode step alone (`_decode_step`: u2tok_decoder_decode_pre onto the scratch rows, then
-    u2tok_decoder_decode_post_kv8, which quantises them into the layer's buffers and attends over the codes); every other route
-    refuses it and reads the same cache dequantised through the layer's `update`.
-  * kv8_continued: `route` also takes a filled `Kv8Layer` for "extend" (`_prefill_step`: the rotary kernel's dense new rows are
-    quantised behind the cached ones, u2tok_attention_kv8_rows attends over the codes -- nothing is dequantised); calls longer
-    than KV8_EXTEND_MAX_ROWS stay stock.
+  * stack_decode, head: the decoder STACK's forward is wrapped as well; a decode step `route` would hand to the fused step in every
+    layer (`stack_route`) runs as one library call for all of them (`_stack_step`), with the bits of the per-layer route; a u2
+    causal LM's call that `head_route` admits runs that step WITH its head (final RMSNorm, lm_head, fp32 logits) through
+    `head_forward`; the head's descriptor and quantised copy live on the model (`_HeadState`), not in the stack's state.
+  * kv8, kv8_continued, stack_kv8: the cache a fused prefill starts is a `Kv8Layer` (e4m3 codes and a scale per cached row) where
+    the append-in-place layer would go; the decode step (u2tok_decoder_decode_post_kv8), with kv8_continued the continued prefill
+    (u2tok_attention_kv8_rows; calls longer than KV8_EXTEND_MAX_ROWS stay stock) and with stack_kv8 the whole-stack step and the
+    head (u2tok_decoder_decode_stack_kv8 / _stack_head_kv8) write and read the codes; every route that refuses the layer reads the
+    same cache dequantised through the layer's `update`.
 q|k|v and gate|up are packed the way the tokenizer packs its projections: the nn.Parameters keep their names and shapes,
 their storage becomes a view of one buffer, so the stock modules keep working on them.
 
@@ -58,27 +51,33 @@ plain DynamicCache, the append-in-place layer or the DynamicSlidingWindowLayer t
 
 `route` decides once per call which forward a patched layer takes: the opt-in training route of decoder_train.py, the decode
 step, the prefill or the stock forward.  The patch state is one `_LayerState` per layer and one `_StackState` per decoder stack.
+
+The cache-kind rule, once: WHAT a call's cache layer is, is `kv_cache.layer_kind`'s answer and nobody else's; the cache layers and
+`_KVWrite` (where a step's rows go: T0, the first position of a window, the buffers, the commit) live in kv_cache.py and know no
+switch.  WHICH kinds a call may take is decided here: `route` (the decode step: filled 16-bit layers, codes with kv8; the continued
+prefill: those, nothing cached yet, codes with kv8_continued; the caps on a group's query heads and KV8_EXTEND_MAX_ROWS), which
+leaves its answer on the layer's state for the step, and `stack_route` (one in-place kind for every layer; codes with stack_kv8).
+The steps branch on that kind alone; what the whole-stack step does differently on codes is one record (`_STACK_KINDS`).
 """
 from __future__ import annotations
 
+import ctypes as C
 import types
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import NamedTuple, Optional
 
 import torch
-from transformers import cache_utils
 
-from . import decoder_train, ops
+from . import _lib, decoder_train, ops
+from .kv_cache import (APPEND, APPEND_OTHER, DENSE, EMPTY, KERNEL_DTYPES, KERNEL_HEAD_DIMS, KV8, LAZY, NO_CACHE, SLIDING,  # noqa: F401
+                       Kv8Layer, _append_layer_class, _KVWrite, _plain_layers, _prefill_append_layer, kv8_cache, layer_kind, window_first)
 from .lora import _HOOK_TABLES, adapter_of, base_only_of, dropout_inactive
-
-# the HF cache classes the fused steps work with (None where this transformers lacks one: before 4.56 no per-layer caches)
-_DYN_CACHE, _DYN_LAYER, _SLIDING_LAYER = (getattr(cache_utils, n, None) for n in
-                                          ("DynamicCache", "DynamicLayer", "DynamicSlidingWindowLayer"))
 
 # What the kernels compute, per route: element types and head dims of the prefill / decode kernels, and of the backward
 # kernels the training route needs (bf16 only; head dim 96 -- the flash backward's <96> kernels behind
 # u2tok_attention_gqa_bwd_d96 -- with the train_phi3 switch, which also admits the packed Phi-3 layout)
-INFER_DTYPES, INFER_HEAD_DIMS = (torch.bfloat16, torch.float16), (64, 96, 128)
+INFER_DTYPES, INFER_HEAD_DIMS = KERNEL_DTYPES, KERNEL_HEAD_DIMS
 TRAIN_DTYPES, TRAIN_HEAD_DIMS = (torch.bfloat16,), (64, 128)
 TRAIN_PHI3_HEAD_DIMS = (64, 96, 128)
 
@@ -228,14 +227,24 @@ _QFORMS = (_QForm(2, "fp4", "w4", 128, ops.quantize_blocks_fp4, w4_stats, 2),
            _QForm(1, "fp8", "w8", 64, ops.quantize_rows_fp8, w8_stats, None))
 _QFORM_OF = {q.form: q for q in _QFORMS}
 
+# the kinds of cache layer the 16-bit steps take (sliding layers and codes: see `route`)
+_DECODE_KINDS = (DENSE, APPEND, APPEND_OTHER)
+_EXTEND_KINDS = _DECODE_KINDS + (NO_CACHE, LAZY, EMPTY)
 _NO_PAD = ("none", None, None)   # the mask verdict of a call without padding (`pad_rule`, `_mask_hook`): compared by identity first
 
 
-def _count(st, how: str, B: int) -> None:
-    """One routed layer call (how: "prefill", "extend" or "decode") in the six dicts above."""
+def _count(st, how: str, B: int, codes: bool = False, whole: bool = False) -> None:
+    """One routed layer call (how: "prefill", "extend" or "decode") in the dicts above.  codes: it writes and reads an e4m3 cache
+    layer in place (kind KV8); whole: it is the first layer of a whole-stack step, which is counted with it."""
     stack = st.stack
     pad = stack.pad   # (a routed call: the verdict is a tuple)
     key = how if pad is _NO_PAD or pad[0] == "none" else "padded_" + how
+    if codes:
+        (kv8_extend_stats if how == "extend" else kv8_stats)[key] += 1
+    if whole:
+        stack_stats[key] += 1
+        if codes:
+            stack_kv8_stats[key] += 1
     (extend_stats if how == "extend" else stats)[key] += 1
     if how == "decode" and (B > 16 or stack.fp8 or stack.fp4):
         for q in _QFORMS:   # (`_weight_form`: a layer keeps the copies of one form)
@@ -502,6 +511,7 @@ class _LayerState:
     stack: _StackState
     layout: type
     ads: tuple = None          # lora: the call's adapters per projection (`_admit`, set by route() for the step that follows)
+    kind: object = None        # `layer_kind`'s answer for the call's cache layer (set by route(), taken by the step that follows)
     dec: object = None         # `_Decode16`
     w8: tuple = None           # fp8_decode: (key, the four (W8, scale) pairs)
     lora: _LoraOps = None
@@ -537,12 +547,12 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
     """The forward a call of the patched `layer` takes, from the input's shape, dtype and device flag (no tensor needed):
     ("train", kv_len) or stock with grad enabled, else ("decode", W), ("prefill", W), ("extend", W) or stock; W = the attention
     window or None.  "extend" (stack.continued, opt-in): more than one position that the plain prefill refuses -- the layer's
-    cache already holds positions, or the call is longer than the window -- with a cache `_extend_layer_ok` takes.  Masks: decode,
+    cache already holds positions, or the call is longer than the window -- with a cache layer of a kind the continued prefill takes (`kv_cache.layer_kind`).  Masks: decode,
     prefill and extend read the stack pre-hook's verdict on the call's 2-D mask, the training route the layer's own 4-D mask (layer_mask_kv_len: cached on the tensor, so a checkpoint recompute sees its own forward's).  `pr`: the
     layout's projections (read once per call)."""
     st = layer._u2_prefill
     stack, lo, att = st.stack, st.layout, layer.self_attn
-    st.ads = None
+    st.ads = st.kind = None
     if not (stack.train if grad else stack.prefill):
         return "stock", None
     pe = kwargs.get("position_embeddings")
@@ -591,23 +601,25 @@ def route(layer, shape, dtype, is_cuda: bool, args, kwargs, grad: bool, pr):
             return "stock", None
     if shape[1] == 1:   # one new position per sequence, batch <= 16 (wide_decode=True: <= 64), against a plain DynamicCache
         wide = shape[0] > 16   # (17 .. 64 sequences: the few-rows product on up to four blocks of 16 rows, always the batched attention)
-        lay = _plain_dynamic_layer(cache, att.layer_idx, sliding=W is not None, kv8=stack.kv8)
-        ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode and lay is not None
-        q8 = type(lay) is Kv8Layer   # (an e4m3 cache of this batch on the GPU: its step is always the batched decode attention)
-        if q8 and (lay._kc is None or lay._kc.shape[0] != shape[0] or not lay._kc.is_cuda):
-            ok = False
-        if (ranged or wide or q8) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
+        kind, lay = layer_kind(cache, att.layer_idx, shape[0])
+        st.kind = kind
+        # a filled 16-bit layer of a plain cache (sliding: under a window); kv8: codes the kernels take, always the batched attention
+        ok = (shape[0] <= 64 and stack.wide if wide else True) and stack.decode and (
+            kind in _DECODE_KINDS or (kind is KV8 and stack.kv8) or (kind is SLIDING and W is not None and lay.get_seq_length() > 0))
+        if (ranged or wide or kind is KV8) and att.config.num_attention_heads // att.config.num_key_value_heads > 16:
             ok = False  # (the batched decode attention holds a group's query heads in one 16-row operand)
         return ("decode", W) if ok else ("stock", None)
     # an empty cache and no more positions than the window: the plain causal prefill
     if (W is None or shape[1] <= W) and (cache is None or cache.get_seq_length(att.layer_idx) == 0):
         return "prefill", W
-    # continued=True: the band and the cache's layout inside the attention kernel (u2tok_attention_gqa_band)
-    # (kv8_continued: a filled `Kv8Layer` of this batch on the GPU as well, its codes read by u2tok_attention_kv8_rows)
-    if stack.continued and (cache is None or _extend_layer_ok(
-            cache, att.layer_idx, W is not None,
-            (shape[0], shape[1], att.config.num_attention_heads // att.config.num_key_value_heads) if stack.kv8x else None)):
-        return "extend", W
+    # continued=True: the band and the cache's layout inside the attention kernel (u2tok_attention_gqa_band), for every layer of a
+    # plain cache the step can write; kv8_continued: codes the kernels take as well (u2tok_attention_kv8_rows, the two caps)
+    if stack.continued:
+        kind = st.kind = layer_kind(cache, att.layer_idx, shape[0])[0]
+        if kind in _EXTEND_KINDS or (kind is SLIDING and W is not None) or (
+                kind is KV8 and stack.kv8x and att.config.num_attention_heads // att.config.num_key_value_heads <= 16
+                and (KV8_EXTEND_MAX_ROWS is None or shape[1] <= KV8_EXTEND_MAX_ROWS)):
+            return "extend", W
     return "stock", None
 
 
@@ -618,12 +630,13 @@ def _layer_forward(self, hidden_states, *args, **kwargs):
     shape = x.shape
     how, arg = route(self, shape, x.dtype, x.is_cuda, args, kwargs, torch.is_grad_enabled(), pr)
     if how == "decode":
+        codes = st.kind is KV8
         out = _decode_step(self, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, pr)
         if out is not None:
-            _count(st, how, shape[0])
+            _count(st, how, shape[0], codes)
             return out
     elif how == "prefill" or how == "extend":
-        _count(st, how, shape[0])
+        _count(st, how, shape[0], st.kind is KV8)
         return _prefill_step(self, st.layout, x, kwargs["position_embeddings"], kwargs.get("past_key_values"), arg, how == "extend")
     elif how == "train":
         return _train_step(self, st.layout, x, kwargs["position_embeddings"], arg)
@@ -646,76 +659,6 @@ def _lora_add(y, x2, segs):
     for A16, B16, col0, scale in segs:
         u = ops.lora_down(x2, A16)
         ops.lora_up(u, B16, y[:, col0:col0 + B16.shape[0]], alpha=scale, accumulate=True)
-
-
-class _KVWrite:
-    """Where the new keys / values of a step go and what it attends over, for the prefill, the continued prefill and the decode
-    step.  `lay`: the append-in-place layer of a plain DynamicCache holding this batch, or None.  With it the rotary kernel writes
-    behind the `T0` old positions of the layer's buffers (`lay._kb`, `lay._vb`), the attention reads views of those buffers, and
-    `commit` makes them the layer's.  Without it: dense tensors through the cache's own `update` -- in `views` when the step
-    attends over the cache, else in `commit`.
-    fresh = (H_kv, d, like): the call is the first into this layer; an empty DynamicLayer of a plain DynamicCache is replaced by an
-    append-in-place one with room for the call and as many positions again (`_prefill_append_layer`) -- kv8: by a `Kv8Layer`,
-    which is written through its own `update` (`lay` stays None).
-    codes = (H_kv, d, device) (a filled extend with kv8_continued): a filled `Kv8Layer` becomes `lay8` with room for the call; the
-    rotary kernel writes dense new rows, `attend8` quantises them behind the `T0` cached positions and attends over the codes,
-    `commit` sets the layer's length."""
-    __slots__ = ("cache", "idx", "n", "window", "lay", "T0", "lay8")
-
-    def __init__(self, cache, idx: int, B: int, n: int, window, like=None, fresh=None, kv8: bool = False, codes=None):
-        self.cache, self.idx, self.n, self.window, self.T0 = cache, idx, n, window, 0
-        lay = self.lay8 = None
-        if cache is not None:
-            if fresh is not None:   # (kv8: a `Kv8Layer` goes there and None comes back -- the step commits through its `update`)
-                lay = _prefill_append_layer(cache, idx, B, fresh[0], n, fresh[1], fresh[2], kv8)
-            else:
-                lay = cache.layers[idx]
-                if type(lay) is _APPEND_LAYER and lay.keys.shape[0] == B:   # (a reordered or re-batched layer: `_room` re-homes it)
-                    self.T0 = lay._room(n, lay.keys if like is None else like)
-                else:
-                    if codes is not None and type(lay) is Kv8Layer:
-                        self.lay8, self.T0 = lay, lay._room(n, B, *codes)
-                    lay = None
-        self.lay = lay
-
-    def views(self, kc, vc, stride=0):
-        """(K, V, stride of one (batch, kv head) entry -- 0: dense) to attend over; kc / vc: the dense new keys / values for a cache
-        that is not written in place, stride: the buffers' for one that is.  A window W: the last n + W - 1 positions of an
-        in-place layer; of a dense cache the last W for a decode step (a longer call hands the band kernel what `update`
-        returned: its masks are relative to the last key, and a DynamicSlidingWindowLayer returns its kept W - 1 positions and the
-        new ones)."""
-        n, W, lay = self.n, self.window, self.lay
-        if lay is not None:
-            T1 = self.T0 + n
-            lo = 0 if W is None else max(0, T1 - (n + W - 1))
-            return lay._kb[:, :, lo:T1], lay._vb[:, :, lo:T1], stride
-        K, V = self.cache.update(kc, vc, self.idx)   # DynamicLayer: torch.cat -> dense (B, H_kv, T, d)
-        self.cache = None                            # (updated: nothing left for `commit`)
-        if n == 1:
-            K, V = K.contiguous(), V.contiguous()
-            if W is not None and K.shape[2] > W:     # (the last W positions: rows of each (batch, kv head) entry)
-                return K[:, :, -W:], V[:, :, -W:], K.stride(1)
-        elif K.stride() != V.stride() or K.stride(3) != 1 or K.stride(2) != K.shape[3] or K.stride(0) != K.shape[1] * K.stride(1):
-            K, V = K.contiguous(), V.contiguous()    # (not a view the band kernel reads where it lies)
-        return K, V, 0
-
-    def attend8(self, q, kc, vc, heads: int, scale: float, kv_start):
-        """The `lay8` case: the dense new rows kc / vc (B, H_kv, n, d) as codes and scales at positions T0 .. T0 + n - 1, then the n
-        new queries q (B, n, heads d) over positions lo .. T0 + n - 1 of the codes (a window W: lo as in `views`)."""
-        n, W, lay = self.n, self.window, self.lay8
-        T1 = self.T0 + n
-        lo = 0 if W is None else max(0, T1 - (n + W - 1))
-        bufs = (lay._kc, lay._vc, lay._ks, lay._vs)
-        ops.kv_quantize_rows(kc, vc, *bufs, self.T0)
-        return ops.attention_kv8_rows(q, *bufs, T1 - lo, heads, scale, window=W, kv_start=kv_start, k_first=lo)
-
-    def commit(self, kc=None, vc=None) -> None:
-        if self.lay8 is not None:
-            self.lay8._T = self.T0 + self.n
-        elif self.lay is not None:
-            self.lay._commit(self.T0 + self.n)
-        elif self.cache is not None:
-            self.cache.update(kc, vc, self.idx)
 
 
 def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
@@ -747,16 +690,18 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
         q3 = qkv.view(B, S, -1)
         _, kv_start, kv_len = st.stack.pad
         filled = extend and cache is not None and cache.get_seq_length(att.layer_idx) > 0
-        kv = _KVWrite(cache, att.layer_idx, B, S, window, fresh=None if filled else (Hkv, d, x), kv8=st.stack.kv8,
-                      codes=(Hkv, d, x.device) if filled and st.stack.kv8x else None)
-        lay = kv.lay
+        kind, st.kind = st.kind, None   # (route()'s answer, where it routed this call)
+        codes = kind is KV8       # an e4m3 cache (kv8_continued): the rotary kernel's new rows stay dense, `attend8` quantises them
+        kv = _KVWrite(cache, att.layer_idx, B, S, window, like=x.new_empty((B, Hkv, 0, d)) if codes else None,
+                      fresh=None if filled else (Hkv, d, x), kv8=st.stack.kv8, kind=kind)
+        codes = kv.kind is KV8
+        kv_out = kv.lay._buffers() if kv.kind is APPEND else None
         r = ops.qk_norm_rope(qkv, None if qn is None else qn.weight, None if kn is None else kn.weight, cos, sin, Hq, Hkv, d,
                              qn.variance_epsilon if qn is not None else 1e-6, kv_cache_seq=S if cache is not None else 0,
-                             kv_out=None if lay is None else (lay._kb, lay._vb), kv_pos=kv.T0)
-        kc, vc = (r[1], r[2]) if cache is not None and lay is None else (None, None)
-        if kv.lay8 is not None:   # an e4m3 cache (kv8_continued): over the codes, the quantised new rows included
+                             kv_out=kv_out, kv_pos=kv.T0)
+        kc, vc = (r[1], r[2]) if cache is not None and kv_out is None else (None, None)
+        if codes:   # over the codes, the quantised new rows included
             ctx = kv.attend8(q3[..., :Hq * d], kc, vc, Hq, float(att.scaling), kv_start)
-            kv8_extend_stats["extend" if kv_start is None else "padded_extend"] += 1
         else:
             if filled:
                 K, V, _ = kv.views(kc, vc)
@@ -782,256 +727,6 @@ def _prefill_step(self, lo, x, pe, cache, window=None, extend=False):
     return out.view(B, S, E)
 
 
-_APPEND_LAYER = None
-
-
-def _append_layer_class():
-    """A DynamicLayer that APPENDS IN PLACE: keys / values are views [:, :, :T] of buffers with room to grow (doubling), so a decode
-    step writes one row instead of re-copying the whole cache (DynamicLayer.update is a torch.cat: two launches and 2 x T rows per
-    layer and step).  Everything else -- crop, batch selection, beam reordering, the stock attention reading `.keys` -- is
-    DynamicLayer's: those reassign `.keys` / `.values`, after which the next update re-homes them."""
-    global _APPEND_LAYER
-    if _APPEND_LAYER is None:
-        class AppendLayer(_DYN_LAYER):
-            _kb = _vb = None
-
-            def _room(self, n: int, like: torch.Tensor) -> int:
-                """Make sure `n` more positions fit behind the current ones; returns the current length."""
-                T0 = self.keys.shape[-2] if self.is_initialized and self.keys.numel() else 0
-                kb = self._kb
-                homed = kb is not None and (T0 == 0 or (self.keys.data_ptr() == kb.data_ptr() and self.values.data_ptr() == self._vb.data_ptr()
-                                                        and self.keys.shape[:2] == kb.shape[:2]))
-                if not homed or T0 + n > kb.shape[-2] or kb.shape[:2] != like.shape[:2]:
-                    cap = max(256, 2 * (T0 + n))
-                    shape = (like.shape[0], like.shape[1], cap, like.shape[3])
-                    nk = torch.empty(shape, dtype=like.dtype, device=like.device)
-                    nv = torch.empty(shape, dtype=like.dtype, device=like.device)
-                    if T0:
-                        nk[:, :, :T0].copy_(self.keys)
-                        nv[:, :, :T0].copy_(self.values)
-                    self._kb, self._vb = nk, nv
-                    self.keys, self.values = nk[:, :, :T0], nv[:, :, :T0]
-                return T0
-
-            def _commit(self, T: int) -> None:
-                self.keys, self.values = self._kb[:, :, :T], self._vb[:, :, :T]
-
-            def update(self, key_states, value_states, *args, **kwargs):
-                if not self.is_initialized:
-                    self.lazy_initialization(key_states, value_states)
-                n = key_states.shape[-2]
-                T0 = self._room(n, key_states)
-                self._kb[:, :, T0:T0 + n].copy_(key_states)
-                self._vb[:, :, T0:T0 + n].copy_(value_states)
-                self._commit(T0 + n)
-                return self.keys, self.values
-
-        _APPEND_LAYER = AppendLayer
-    return _APPEND_LAYER
-
-
-_CACHE_LAYER = getattr(cache_utils, "CacheLayerMixin", None)
-
-
-class Kv8Layer(_CACHE_LAYER if _CACHE_LAYER is not None else object):
-    """A cache layer (CacheLayerMixin's protocol) that keeps K and V as FP8: e4m3 codes (B, H_kv, capacity, d) uint8 and one fp32
-    scale per cached row (B, H_kv, capacity), K and V each (`ops.quantize_kv_fp8`: the format; value = code x scale), in buffers with
-    room to grow -- they double, the old codes and scales are copied bit for bit.  What the cache HOLDS defines the semantics,
-    whatever route reads it:
-      * `update()` on an empty layer quantises its inputs and returns them as they came (HF's own quantized-cache rule: the
-        prefill attends over what it computed); on a filled layer it quantises the new rows and returns the whole cache dequantised
-        in the callers' type -- so the stock layers, and every route that refuses the layer, attend over the same quantised cache
-        the fused decode step reads as codes (`_decode_step`: u2tok_decoder_decode_post_kv8);
-      * length, mask sizes, crop, batch selection / repetition, beam reordering, reset, offload / prefetch work on codes and scales
-        directly: nothing is ever dequantised and requantised (rnd(code x scale) does not requantise to the same codes);
-      * `.keys` / `.values` are read-only, dequantised on demand for foreign readers; assigning them raises.
-    Quantisation runs the kernel (u2tok_kv_quantize_rows) for 16-bit rows on the GPU that it takes, the torch reference elsewhere:
-    the same bits; the layer works on the CPU."""
-    is_sliding = False
-    is_compileable = False
-
-    def __init__(self, **kwargs):
-        self._kc = self._vc = self._ks = self._vs = None
-        self._T = 0
-        self.dtype = self.device = None
-        self.is_initialized = False
-
-    def _dequant(self, codes, scales):
-        if not self.is_initialized or codes is None:
-            return None
-        T = self._T
-        return ops.dequantize_kv_fp8(codes[:, :, :T], scales[:, :, :T], self.dtype)
-
-    @property
-    def keys(self):
-        return self._dequant(self._kc, self._ks)
-
-    @keys.setter
-    def keys(self, value):
-        raise AttributeError("Kv8Layer.keys is read-only: the layer holds e4m3 codes and scales")
-
-    @property
-    def values(self):
-        return self._dequant(self._vc, self._vs)
-
-    @values.setter
-    def values(self, value):
-        raise AttributeError("Kv8Layer.values is read-only: the layer holds e4m3 codes and scales")
-
-    def lazy_initialization(self, key_states, value_states) -> None:
-        self.dtype, self.device = key_states.dtype, key_states.device
-        self.is_initialized = True
-
-    def codes(self):
-        """(K codes, V codes, K scales, V scales) of the cached positions: views of the buffers (None while empty)"""
-        if self._kc is None:
-            return None
-        T = self._T
-        return self._kc[:, :, :T], self._vc[:, :, :T], self._ks[:, :, :T], self._vs[:, :, :T]
-
-    def _set(self, kc, vc, ks, vs, T: int) -> None:
-        self._kc, self._vc, self._ks, self._vs, self._T = kc, vc, ks, vs, T
-
-    def _room(self, n: int, B: int, H: int, d: int, device) -> int:
-        """Make sure `n` more positions fit behind the current ones; returns the current length."""
-        T0, kc = self._T, self._kc
-        if kc is None or T0 + n > kc.shape[2] or kc.shape[:2] != (B, H) or kc.shape[3] != d or kc.device != device:
-            if kc is not None and T0 and (kc.shape[:2] != (B, H) or kc.shape[3] != d):
-                raise RuntimeError(f"Kv8Layer: rows of shape {(B, H, n, d)} against a cache of {tuple(kc.shape)}")
-            cap = max(256, 2 * (T0 + n))
-            new = (torch.empty((B, H, cap, d), dtype=torch.uint8, device=device), torch.empty((B, H, cap, d), dtype=torch.uint8, device=device),
-                   torch.empty((B, H, cap), dtype=torch.float32, device=device), torch.empty((B, H, cap), dtype=torch.float32, device=device))
-            if T0:
-                for dst, src in zip(new, (self._kc, self._vc, self._ks, self._vs)):
-                    dst[:, :, :T0].copy_(src[:, :, :T0])
-            self._kc, self._vc, self._ks, self._vs = new
-        return T0
-
-    def _quantise(self, k, v, T0: int) -> None:
-        n, d = k.shape[2], k.shape[3]
-        if k.is_cuda and k.dtype in INFER_DTYPES and v.dtype == k.dtype and d in INFER_HEAD_DIMS and k.stride(3) == 1 and v.stride(3) == 1 \
-                and not any(s % 8 for t in (k, v) for s in t.stride()[:3]) and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0:
-            ops.kv_quantize_rows(k, v, self._kc, self._vc, self._ks, self._vs, T0)
-            return
-        for x, codes, scales in ((k, self._kc, self._ks), (v, self._vc, self._vs)):
-            c, s = ops.quantize_kv_fp8(x)
-            codes[:, :, T0:T0 + n].copy_(c.view(torch.uint8))
-            scales[:, :, T0:T0 + n].copy_(s)
-
-    def update(self, key_states, value_states, *args, **kwargs):
-        if not self.is_initialized:
-            self.lazy_initialization(key_states, value_states)
-        B, H, n, d = key_states.shape
-        T0 = self._room(n, B, H, d, key_states.device)
-        self._quantise(key_states, value_states, T0)
-        self._T = T0 + n
-        if T0 == 0:
-            return key_states, value_states
-        dt = key_states.dtype
-        return (ops.dequantize_kv_fp8(self._kc[:, :, :self._T], self._ks[:, :, :self._T], dt),
-                ops.dequantize_kv_fp8(self._vc[:, :, :self._T], self._vs[:, :, :self._T], dt))
-
-    def get_seq_length(self) -> int:
-        return self._T
-
-    def get_mask_sizes(self, query_length) -> tuple:
-        if not isinstance(query_length, int):      # (a cache_position tensor: earlier 4.5x protocol)
-            query_length = query_length.shape[0]
-        return self._T + query_length, 0
-
-    def get_max_length(self) -> int:
-        return -1
-
-    def get_max_cache_shape(self) -> int:
-        return -1
-
-    def crop(self, tokens_to_remove: int) -> None:
-        """DynamicLayer.crop's meaning: a negative number removes that many positions from the end, a positive one is the length to
-        keep (nothing happens when it is not shorter than the cache)."""
-        T = self._T
-        if tokens_to_remove > 0:
-            if tokens_to_remove >= T:
-                return
-            self._T = tokens_to_remove
-        else:
-            self._T = max(0, T + tokens_to_remove)
-
-    def _each(self, fn) -> None:
-        if self._kc is not None:
-            self._kc, self._vc, self._ks, self._vs = (fn(t) for t in (self._kc, self._vc, self._ks, self._vs))
-
-    def batch_repeat_interleave(self, repeats: int) -> None:
-        if self._T > 0:
-            self._each(lambda t: t.repeat_interleave(repeats, dim=0))
-
-    def batch_select_indices(self, indices) -> None:
-        if self._T > 0:
-            self._each(lambda t: t[indices, ...].contiguous())
-
-    def reorder_cache(self, beam_idx) -> None:
-        if self._T > 0:
-            self._each(lambda t: t.index_select(0, beam_idx.to(t.device)))
-
-    def reset(self) -> None:
-        self._T = 0
-
-    def offload(self) -> None:
-        self._each(lambda t: t.to("cpu", non_blocking=True))
-
-    def prefetch(self) -> None:
-        if self._kc is not None and self.device is not None and self._kc.device != self.device:
-            self._each(lambda t: t.to(self.device, non_blocking=True))
-
-
-def kv8_cache(n_layers: int):
-    """A plain HF DynamicCache of `n_layers` empty `Kv8Layer`s: what `kv8` leaves behind a fused prefill, for a caller that wants
-    the FP8 cache on the stock layers as well (any device)."""
-    cache = _DYN_CACHE()
-    cache.layers.extend(Kv8Layer() for _ in range(n_layers))
-    return cache
-
-
-def _plain_layers(cache):
-    """The `layers` list of `cache` if it is a plain HF DynamicCache (no offloading), else None."""
-    layers = getattr(cache, "layers", None)
-    if type(cache) is not _DYN_CACHE or not isinstance(layers, list) or getattr(cache, "offloading", False):
-        return None
-    return layers
-
-
-def _plain_dynamic_layer(cache, layer_idx: int, sliding: bool = False, kv8: bool = False):
-    """The cache layer if `cache` is a plain HF DynamicCache (no offloading) whose layer `layer_idx` is a non-empty DynamicLayer
-    -- the case the fused decode step handles (its `update` is a torch.cat: dense (B, H_kv, T, d) tensors come back).
-    sliding=True (a layer with an attention window): a DynamicSlidingWindowLayer is taken as well.  kv8=True (the switch): a
-    `Kv8Layer` too."""
-    layers = _plain_layers(cache)
-    if layers is None or layer_idx >= len(layers):
-        return None
-    lay = layers[layer_idx]
-    kinds = (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER, Kv8Layer if kv8 else _DYN_LAYER)
-    return lay if type(lay) in kinds and lay.get_seq_length() > 0 else None
-
-
-def _extend_layer_ok(cache, layer_idx: int, sliding: bool, kv8=None) -> bool:
-    """Whether the continued prefill takes this layer of `cache`: a plain HF DynamicCache (no offloading) whose layer is a
-    DynamicLayer, the append-in-place layer or -- sliding=True: a layer with an attention window -- a DynamicSlidingWindowLayer,
-    empty or filled; a layer the cache would still create lazily as a DynamicLayer counts.  Static, quantized and offloaded
-    caches and other layer classes: no.  kv8 = (B, S, query heads per kv head) of the call (the kv8_continued switch, else None):
-    a `Kv8Layer` too -- filled, on the GPU, holding this batch, at most 16 query heads per kv head (the test route() makes for the
-    decode step) and no more than KV8_EXTEND_MAX_ROWS new positions."""
-    layers = _plain_layers(cache)
-    if layers is None:
-        return False
-    if layer_idx >= len(layers):
-        return getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER
-    lay = layers[layer_idx]
-    if kv8 is not None and type(lay) is Kv8Layer:
-        B, S, G = kv8
-        return (lay.get_seq_length() > 0 and lay._kc is not None and lay._kc.shape[0] == B and lay._kc.is_cuda and G <= 16
-                and (KV8_EXTEND_MAX_ROWS is None or S <= KV8_EXTEND_MAX_ROWS))
-    return type(lay) in (_DYN_LAYER, _APPEND_LAYER, _SLIDING_LAYER if sliding else _DYN_LAYER)
-
-
 @dataclass(slots=True, eq=False)
 class _Decode16:
     """Per-layer constants of the decode step: the config struct, the 16-bit layer descriptor, the packed operands it points at."""
@@ -1049,8 +744,6 @@ class _Decode16:
 def _decode_state(self, B: int, device, pr):
     """Per-layer constants of the decode step (weight pointers of the packed projections, the config struct), rebuilt when a
     weight moved or the batch size changed; per-model scratch (workspace, q|k|v row, new cache entries) shared by all layers."""
-    import ctypes as C
-    from . import _lib
     st = self._u2_prefill
     lo = st.layout
     att = self.self_attn
@@ -1171,8 +864,6 @@ _LORA_PRODUCTS = ("qkv", "o", "gu", "down")
 def _lora_scratch(ls, B: int, sc, h) -> None:
     """Point the adapters' u2tok_decode_lora (built here on first use) at the calling stream's scratch for B rows: u, then the
     largest group workspace; shared by all layers like the step's other scratch."""
-    import ctypes as C
-    from . import _lib
     desc = ls.desc
     if desc is None:
         desc = ls.desc = _lib.DecodeLora()
@@ -1199,8 +890,6 @@ def _decode_layer(st, form: int, lora: bool):
     sources as they are now; a rebuilt source drops all of them."""
     v = st.variants.get((form, lora))
     if v is None:
-        import ctypes as C
-        from . import _lib
         lay = _lib.DecodeLayer.from_buffer_copy(st.dec.layer)
         cfg, cfg_ref = st.dec.cfg, st.dec.cfg_ref
         if form:
@@ -1231,32 +920,34 @@ def w4_weights(layer):
     return None if st is None or st.w4 is None else st.w4[1]
 
 
+def _step_variant(st, d, pr, x, B: int, sc, h):
+    """What a layer's decode step runs on: weight form -> adapter operands -> adapter scratch for B rows -> descriptor variant
+    (found without a call once built).  -> (`_decode_layer`'s tuple, the `_LoraOps` or None)."""
+    form = _weight_form(st, d, pr)
+    ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
+    if ls is not None:
+        _lora_scratch(ls, B, sc, h)
+    v = st.variants.get((form, ls is not None))
+    return (v if v is not None else _decode_layer(st, form, ls is not None)), ls
+
+
 def _decode_step(self, x, pe, cache, window, pr):
-    """One decode step of a layer (B <= 16 new tokens -- wide_decode=True: B <= 64 --, one each, against the KV cache): the step `generate` repeats up to 768
-    times per report (eval/mrg.py:74-77).  Every product is weight streaming -- q|k|v, out, gate|up and down go through the
-    few-rows GEMM (gemm_rows.hip: gemm_rows16_kernel, all loads of a wave in flight before its first MFMA) --, the attention is the
-    fused kernel with the KEYS split over workgroups (batch x kv-head entries of (T, d) keys, the query heads of a group as its
-    heads).  TWO library calls per layer (u2tok_decoder_decode_pre / _post, 10 launches) around the cache's own `update`: with a
-    Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels).
-    window = W (a sliding-window layer): the query attends over the last min(T, W) positions -- an offset into the cache
-    buffers, the same kernels.
-    B > 16 (the route's wide_decode switch): the same two calls; the library runs the four products on its 17 .. 64-row form of
-    the few-rows kernel (csrc/gemm_rows.hip: the weights are still read once per step, and each block of 16 sequences gets the
-    bits it has in a step of its own) and the attention is always the batched kernel, with kv_start = NULL for an unpadded batch.
-    fp8_decode / fp4_decode / lora: the same two calls on another variant of the layer descriptor (`_decode_layer`); the adapter groups ride in
-    the calls.
-    kv8 (a `Kv8Layer` in the cache): the first call writes the step's rows to the scratch rows, the second is
-    u2tok_decoder_decode_post_kv8 -- it quantises them into position T0 of the layer's buffers and attends over the codes, always
-    with the batched kernel; counted in `kv8_stats`."""
-    from . import _lib
+    """One decode step of a layer (B <= 16 new tokens -- wide_decode: B <= 64 --, one each, against the KV cache): the step
+    `generate` repeats up to 768 times per report (eval/mrg.py:74-77).  TWO library calls per layer (u2tok_decoder_decode_pre /
+    _post, 10 launches) around the cache's own `update`: the products are the weight-streaming few-rows GEMM (gemm_rows.hip; 17 ..
+    64 rows: its wide form, always with the batched attention), the attention is the fused kernel with the KEYS split over
+    workgroups; with a Python call per kernel the step was bound by the host (7.9 ms against ~4 ms of kernels).
+    window = W (a sliding-window layer): the query attends over the last min(T, W) positions -- an offset into the cache buffers.
+    fp8_decode / fp4_decode / lora: the same two calls on another variant of the layer descriptor (`_step_variant`).
+    Where the rows go is `_KVWrite`'s answer: the first call writes them into an append-in-place layer's buffers at T0, else onto
+    the scratch rows; the second reads what `views` returns -- or, on codes (KV8), is u2tok_decoder_decode_post_kv8: it quantises
+    the scratch rows into position T0 of the layer's buffers and attends over the codes, always with the batched kernel."""
     att = self.self_attn
     B, _, E = x.shape
     d, sc = _decode_state(self, B, x.device, pr)
     if not d.ok:
         return None                                   # (the caller takes the stock layer)
     st = self._u2_prefill
-    form = _weight_form(st, d, pr)
-    ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, 1, d.hd, x.dtype)
@@ -1269,50 +960,32 @@ def _decode_step(self, x, pe, cache, window, pr):
         ws, nws = sc["ws"].data_ptr(), sc["ws"].numel()
         out = torch.empty((B, 1, E), dtype=x.dtype, device=x.device)
         # append in place: the rotary kernel writes the step's keys / values at position T0 of the layer's buffers; else into the
-        # step's scratch rows, for the cache's own `update`
-        lay8 = cache.layers[att.layer_idx] if st.stack.kv8 and _plain_layers(cache) is not None else None
-        if type(lay8) is Kv8Layer:
-            # an e4m3 cache: the step's rows go to the scratch rows, the second call quantises them into position T0 of the layer's
-            # buffers and attends over the codes of positions lo .. T0 (a window W: the last W)
-            T0 = lay8._room(1, B, d.Hkv, d.hd, x.device)
-            lo = 0 if window is None else max(0, T0 + 1 - window)
-            if ls is not None:
-                _lora_scratch(ls, B, sc, h)
-            v = st.variants.get((form, ls is not None))
-            _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, form, ls is not None)
-            _lib.check(h.u2tok_decoder_decode_pre(cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
-                                                  int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), sc["kc"].data_ptr(),
-                                                  sc["vc"].data_ptr(), 0, 0, ws, nws, stream), "u2tok_decoder_decode_pre")
-            _, kv_start, _ = st.stack.pad
-            left = kv_start is not None
-            _lib.check(h.u2tok_decoder_decode_post_kv8(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), sc["kc"].data_ptr(),
-                                                       sc["vc"].data_ptr(), lay8._kc.data_ptr(), lay8._vc.data_ptr(), lay8._ks.data_ptr(),
-                                                       lay8._vs.data_ptr(), lay8._kc.shape[2], lo, T0,
-                                                       kv_start.data_ptr() if left else None, out.data_ptr(), ws, nws, stream),
-                       "u2tok_decoder_decode_post_kv8")
-            lay8._T = T0 + 1
-            kv8_stats["padded_decode" if left else "decode"] += 1
-            return out
-        kv = _KVWrite(cache, att.layer_idx, B, 1, window, like=sc["kc"])
-        lay = kv.lay
-        if lay is None:
-            kd, vd, kvs = sc["kc"], sc["vc"], 0
+        # step's scratch rows -- for the cache's own `update`, or for the second call to quantise into position T0 of the codes
+        kind, st.kind = st.kind, None   # (route()'s answer, where it routed this call)
+        kv = _KVWrite(cache, att.layer_idx, B, 1, window, like=sc["kc"], kind=kind)
+        if kv.kind is APPEND:
+            kd, vd = kv.lay._buffers()
+            kvs, s_off = kd.stride(1), kv.T0
         else:
-            kd, vd, kvs = lay._kb, lay._vb, lay._kb.stride(1)
-        if ls is not None:
-            _lora_scratch(ls, B, sc, h)
-        v = st.variants.get((form, ls is not None))
-        _, layer_ref, cfg_ref, _ = v if v is not None else _decode_layer(st, form, ls is not None)
+            kd, vd, kvs, s_off = sc["kc"], sc["vc"], 0, 0
+        (_, layer_ref, cfg_ref, _), _ = _step_variant(st, d, pr, x, B, sc, h)
         _lib.check(h.u2tok_decoder_decode_pre(cfg_ref, layer_ref, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                                               int(cos.dtype == torch.float32), cos.stride(0), sc["qkv"].data_ptr(), kd.data_ptr(),
-                                              vd.data_ptr(), kvs, kv.T0, ws, nws, stream), "u2tok_decoder_decode_pre")
-        K, V, kvs = kv.views(kd, vd, kvs)
-        kv.commit()
+                                              vd.data_ptr(), kvs, s_off, ws, nws, stream), "u2tok_decoder_decode_pre")
         _, kv_start, _ = st.stack.pad
         left = kv_start is not None   # a left-padded batch: the batched decode attention with each sequence's first visible position
-        _lib.check(h.u2tok_decoder_decode_post(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
-                                               K.shape[2], kvs, int(left or B > 16), kv_start.data_ptr() if left else None,
-                                               out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post")
+        start = kv_start.data_ptr() if left else None
+        if kv.kind is KV8:            # over the codes of positions `first` .. T0 (a window W: the last W)
+            kc, vc, ks, vs = kv.lay._buffers()
+            _lib.check(h.u2tok_decoder_decode_post_kv8(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), kd.data_ptr(), vd.data_ptr(),
+                                                       kc.data_ptr(), vc.data_ptr(), ks.data_ptr(), vs.data_ptr(), kc.shape[2], kv.first,
+                                                       kv.T0, start, out.data_ptr(), ws, nws, stream), "u2tok_decoder_decode_post_kv8")
+        else:
+            K, V, kvs = kv.views(kd, vd, kvs)
+            _lib.check(h.u2tok_decoder_decode_post(cfg_ref, layer_ref, x2.data_ptr(), sc["qkv"].data_ptr(), K.data_ptr(), V.data_ptr(),
+                                                   K.shape[2], kvs, int(left or B > 16), start, out.data_ptr(), ws, nws, stream),
+                       "u2tok_decoder_decode_post")
+        kv.commit()
     return out
 
 
@@ -1321,6 +994,19 @@ _MISSING = object()
 _STACK_ARGS = ("input_ids", "attention_mask", "position_ids", "past_key_values", "inputs_embeds", "use_cache")
 _STACK_SCRATCH = ("stack_ws", "stack_T", "stack_arr", "stack_keep", "stack_head", "stack_arr8", "stack_keep8")   # what the step keeps in a (B, device, stream) scratch entry
 _PE_STUBS = {}
+
+
+# What the whole-stack step does differently per kind of cache: the struct of a layer's slot; the scratch keys of the slot array and
+# of what each slot was filled from; the slot's fields for the addresses of `_buffers()`; its extent field and what it holds of the
+# first buffer; the entry without and with the head, each sized by its name + "_workspace_bytes"; whether the entries take `batched`
+# (on codes the attention is always the batched one)
+_StackKind = namedtuple("_StackKind", "struct arr keep ptrs extent entry head_entry batched")
+_STACK_KINDS = {
+    APPEND: _StackKind(_lib.DecodeStackLayer, "stack_arr", "stack_keep", ("k_cache", "v_cache"), ("kv_stride", lambda kb: kb.stride(1)),
+                       "u2tok_decoder_decode_stack", "u2tok_decoder_decode_stack_head", True),
+    KV8: _StackKind(_lib.DecodeStackLayerKv8, "stack_arr8", "stack_keep8", ("k_codes", "v_codes", "k_scales", "v_scales"),
+                    ("capacity", lambda kc: kc.shape[2]), "u2tok_decoder_decode_stack_kv8", "u2tok_decoder_decode_stack_head_kv8", False),
+}
 
 
 @dataclass(slots=True, eq=False)
@@ -1372,12 +1058,9 @@ def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool
       * `route()` answering "decode" for EVERY layer on this call's shape and keyword arguments -- it keeps deciding masks (the
         pre-hook's verdict: `stack.pad` is current), wide batches, adapters, windows, head dims, types;
       * `_decode_state(...).ok` for every layer, one head dim and one hidden size for all of them;
-      * every layer's cache entry one the per-layer step writes in place (`_KVWrite`: the append-in-place layer a fused prefill
-        left, holding this batch): a plain DynamicLayer, a DynamicSlidingWindowLayer, an offloaded or static cache send the whole
-        call to the per-layer routes;
-      * or, with `stack_kv8` on, EVERY layer's entry a filled `Kv8Layer` (the test `route()` makes for its "decode": this batch, on
-        the GPU, at most 16 query heads per kv head) -- the step then runs on the codes (u2tok_decoder_decode_stack_kv8); a cache
-        that mixes the two kinds, and any `Kv8Layer` with the switch off, send the call to the per-layer routes.
+      * every layer's cache entry of ONE in-place kind (`kv_cache.layer_kind`): the append-in-place layer a fused prefill left,
+        holding this batch -- or, with `stack_kv8` on, codes the kernels take (u2tok_decoder_decode_stack_kv8); a dense or sliding
+        layer, a cache that mixes the two kinds and codes with the switch off send the call to the per-layer routes.
     plan (a list): receives one (layer, state, projections, `_Decode16`, scratch, window) per layer of a "stack" verdict."""
     stack = base.__dict__.get("_u2_stack")
     if stack is None or not stack.stack or grad or S != 1 or not is_cuda:
@@ -1388,13 +1071,10 @@ def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool
     layers = list(base.layers[:base.config.num_hidden_layers])
     if not layers or not hasattr(base, "norm"):
         return "layers"
-    cl = _plain_layers(cache)
-    if cl is None:
-        return "layers"
     lkw = {k: v for k, v in kw.items() if k not in ("input_ids", "inputs_embeds", "attention_mask", "position_ids", "use_cache",
                                                     "output_hidden_states")}
     steps = []
-    hd = E = None
+    hd = E = kind0 = None
     for layer in layers:
         if not is_patched(layer) or not _no_hooks(layer):
             return "layers"
@@ -1410,15 +1090,10 @@ def stack_route(base, B: int, S: int, dtype, is_cuda: bool, kw: dict, grad: bool
         if how != "decode" or (hd is not None and (att.head_dim != hd or E1 != E)):
             return "layers"
         hd, E = att.head_dim, E1
-        idx = att.layer_idx
-        lay = cl[idx] if idx < len(cl) else None
-        if type(lay) is Kv8Layer:   # (route() said "decode": filled, this batch, on the GPU, at most 16 query heads per kv head)
-            if not stack.stack8:
-                return "layers"
-        elif lay is None or type(lay) is not _APPEND_LAYER or lay.keys.shape[0] != B:
-            return "layers"
-        if steps and type(lay) is not type(cl[steps[0][0].self_attn.layer_idx]):   # (one kind of cache for the whole call)
-            return "layers"
+        kind = st.kind                                   # (route() said "decode": of the kinds it admits)
+        if not (kind is APPEND or (kind is KV8 and stack.stack8)) or (kind0 is not None and kind is not kind0):
+            return "layers"                              # (one in-place kind for the whole call; codes with `stack_kv8` alone)
+        kind0 = kind
         d, sc = _decode_state(layer, B, _base(pr[0]).weight.device, pr)
         if not d.ok:
             return "layers"
@@ -1456,15 +1131,12 @@ def _stack_forward(self, *args, **kwargs):
 
 def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
     """One decode step of the whole decoder stack in ONE library call (u2tok_decoder_decode_stack; on a cache of `Kv8Layer`s
-    u2tok_decoder_decode_stack_kv8, whose rotary kernel appends the step's rows as codes): per layer what `_decode_step`
-    does around its two calls -- the weight form's copies, the adapters' operands and scratch, the layer descriptor's variant, room
-    for one more row in the layer's cache buffers --, then the call, then every layer's commit.  The rotary tables come from ONE
-    call of the stack's `rotary_emb`, as the layers receive them from the stock forward.
-    head (a `_HeadState`, the head route): the step with the head (u2tok_decoder_decode_stack_head) -- the stack's final norm and
-    lm_head ride in the call, and the result is (last hidden rows un-normed (B, 1, E), fp32 logits (B, 1, V))."""
-    import ctypes as C
+    u2tok_decoder_decode_stack_kv8, whose rotary kernel appends the step's rows as codes): per layer what `_decode_step` does
+    around its two calls -- `_step_variant`, room for one more row in the layer's buffers --, then the call, then every layer's
+    commit.  The rotary tables come from ONE call of the stack's `rotary_emb`, as the layers receive them from the stock forward.
+    head (a `_HeadState`): the step with the head (u2tok_decoder_decode_stack_head) -- the stack's final norm and lm_head ride in
+    the call, and the result is (last hidden rows un-normed (B, 1, E), fp32 logits (B, 1, V))."""
     from transformers.modeling_outputs import BaseModelOutputWithPast
-    from . import _lib
     if x is None:
         x = base.embed_tokens(ids)
     B, _, E = x.shape
@@ -1475,65 +1147,52 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
     stack = plan[0][1].stack
     sc = plan[0][4]            # (one scratch entry per (B, device, stream): every layer's `_decode_state` returned the same)
     hd = plan[0][3].hd
+    # (`stack_route`: one kind of cache per call -- append-in-place layers, or `Kv8Layer`s and the entries on codes)
+    which = plan[0][1].kind or layer_kind(cache, plan[0][0].self_attn.layer_idx, B)[0]   # (route()'s answer)
+    kind = _STACK_KINDS[which]
+    layers, like = cache.layers, sc["kc"]
     with ops.on_device(x) as (h, stream):
         x2 = _rows(x)
         cos, sin = _rotary_rows(pe, B, 1, hd, x.dtype)
-        # (`stack_route`: one kind of cache per call -- append-in-place layers, or `Kv8Layer`s and the entries on codes)
-        q8 = type(cache.layers[plan[0][0].self_attn.layer_idx]) is Kv8Layer
-        k_arr, k_keep = ("stack_arr8", "stack_keep8") if q8 else ("stack_arr", "stack_keep")
-        arr = sc.get(k_arr)
+        arr = sc.get(kind.arr)
         if arr is None or len(arr) != n:
-            arr = sc[k_arr] = ((_lib.DecodeStackLayerKv8 if q8 else _lib.DecodeStackLayer) * n)()
-            sc[k_keep] = [None] * n
+            arr = sc[kind.arr] = (kind.struct * n)()
+            sc[kind.keep] = [None] * n
             sc["stack_ws"] = None
-        keep = sc[k_keep]
+        keep = sc[kind.keep]
         rows, lss, Tmax = [], [], 0
         for i, (layer, st, pr, d, _, window) in enumerate(plan):
-            form = _weight_form(st, d, pr)
-            ls = _lora_state(st, st.layout, pr, x.dtype, x.device) if st.ads is not None else None
+            v, ls = _step_variant(st, d, pr, x, B, sc, h)
             if ls is not None:
-                _lora_scratch(ls, B, sc, h)
                 lss.append(ls)
-            v = st.variants.get((form, ls is not None))
-            if v is None:
-                v = _decode_layer(st, form, ls is not None)
-            lay = cache.layers[layer.self_attn.layer_idx]
-            slot = arr[i]
-            if q8:   # (as `_decode_step` derives them: room for the row, the buffers, the window's first position below)
-                T0 = lay._room(1, B, d.Hkv, d.hd, x.device)
-                kb = lay._kc
-            else:
-                T0 = lay._room(1, sc["kc"])
-                kb = lay._kb
-            if keep[i] is None or keep[i][0] is not v or keep[i][1] is not kb:   # (rewrite what changed: a rebuilt variant, a re-homed buffer)
+            lay = layers[layer.self_attn.layer_idx]   # (`_KVWrite`'s rule for an in-place layer, without the object)
+            T0 = lay._room(1, like)
+            first = window_first(T0, window)
+            bufs = lay._buffers()
+            slot, had = arr[i], keep[i]
+            if had is None or had[0] is not v or had[1] is not bufs[0]:   # (rewrite what changed: a rebuilt variant, a re-homed buffer)
                 slot.cfg, slot.layer = C.addressof(v[3]), C.addressof(v[0])
-                if q8:
-                    slot.k_codes, slot.v_codes, slot.k_scales, slot.v_scales = (t.data_ptr() for t in (kb, lay._vc, lay._ks, lay._vs))
-                    slot.capacity = kb.shape[2]
-                    keep[i] = (v, kb, lay._vc, lay._ks, lay._vs)
-                else:
-                    slot.k_cache, slot.v_cache, slot.kv_stride = kb.data_ptr(), lay._vb.data_ptr(), kb.stride(1)
-                    keep[i] = (v, kb, lay._vb)
-            T1 = T0 + 1
-            first = 0 if window is None else max(0, T1 - window)
-            slot.s_off, slot.k_first, slot.T = T0, first, T1 - first
-            Tmax = max(Tmax, T1 - first)
-            rows.append((lay, T1))
+                for f, t in zip(kind.ptrs, bufs):
+                    setattr(slot, f, t.data_ptr())
+                setattr(slot, kind.extent[0], kind.extent[1](bufs[0]))
+                keep[i] = (v,) + bufs
+            T = T0 + 1 - first
+            slot.s_off, slot.k_first, slot.T = T0, first, T
+            if T > Tmax:
+                Tmax = T
+            rows.append((lay, T0 + 1, T))
         for ls in lss:   # (a later layer's larger group may have replaced the shared adapter scratch: all of them read the last one)
             ls.desc.scratch, ls.desc.scratch_bytes = sc["lora"].data_ptr(), sc["lora"].numel()
+        name = kind.entry if head is None else kind.head_entry
         if sc["stack_ws"] is None or sc["stack_T"] < Tmax or (head is not None and not sc.get("stack_head")):
             Tcap = max(2048, 2 * Tmax, sc.get("stack_T", 0))   # (grows geometrically, as the per-layer step's workspace does)
             for i in range(n):
                 arr[i].T = Tcap
-            # (the head's normed rows behind the stack step's workspace: a workspace once sized for the head serves both calls)
-            # (the entries on codes size it as the 16-bit ones do on the same (cfg, T): one workspace serves both kinds)
-            if head is None:
-                need = (h.u2tok_decoder_decode_stack_kv8_workspace_bytes if q8 else h.u2tok_decoder_decode_stack_workspace_bytes)(arr, n)
-            else:
-                need = (h.u2tok_decoder_decode_stack_head_kv8_workspace_bytes if q8 else
-                        h.u2tok_decoder_decode_stack_head_workspace_bytes)(arr, n, head.ref)
-            for i, (_, T1) in enumerate(rows):
-                arr[i].T = T1 - arr[i].k_first
+            # (the head's normed rows lie behind the stack step's workspace, and the entries on codes size it as the 16-bit ones do on
+            #  the same (cfg, T): a workspace once sized for the head serves all four entries)
+            need = getattr(h, name + "_workspace_bytes")(arr, n, *(() if head is None else (head.ref,)))
+            for i, row in enumerate(rows):
+                arr[i].T = row[2]
             if need == 0:
                 raise RuntimeError("u2tok_decoder_decode_stack_workspace_bytes refused the stack's descriptors")
             sc["stack_ws"] = torch.zeros(need, dtype=torch.uint8, device=x.device)   # (zeros: the tail norms' ticket, once)
@@ -1545,29 +1204,18 @@ def _stack_step(base, plan, ids, x, cache, position_ids, head=None):
         left = kv_start is not None
         # (w_final_norm = NULL: the stack's final norm stays the module's own below, as on the per-layer routes -- the library's
         #  RMSNorm and the module's add a row's squares in another order, and one element in some ten thousand rounds the other way)
-        # (the entries on codes take no `batched`: an e4m3 cache always has the batched decode attention)
         front = (arr, n, x2.data_ptr(), cos.data_ptr(), sin.data_ptr(), int(cos.dtype == torch.float32), cos.stride(0))
-        front += (() if q8 else (int(left or B > 16),)) + (kv_start.data_ptr() if left else None,)
+        front += ((int(left or B > 16),) if kind.batched else ()) + (kv_start.data_ptr() if left else None,)
         if head is None:
-            name = "u2tok_decoder_decode_stack_kv8" if q8 else "u2tok_decoder_decode_stack"
             _lib.check(getattr(h, name)(*front, None, 0.0, int(STACK_TAIL_NORM), out.data_ptr(), ws.data_ptr(), ws.numel(), stream), name)
         else:
-            name = "u2tok_decoder_decode_stack_head_kv8" if q8 else "u2tok_decoder_decode_stack_head"
             logits = torch.empty((B, 1, head.desc.V), dtype=torch.float32, device=x.device)
             _lib.check(getattr(h, name)(*front, int(STACK_TAIL_NORM), out.data_ptr(), head.ref, logits.data_ptr(), head.desc.V,
                                         ws.data_ptr(), ws.numel(), stream), name)
-        for lay, T1 in rows:
-            if q8:
-                lay._T = T1
-            else:
-                lay._commit(T1)
-    key = "padded_decode" if left else "decode"
-    for _, st, _, _, _, _ in plan:
-        _count(st, "decode", B)
-    stack_stats[key] += 1
-    if q8:
-        kv8_stats[key] += n
-        stack_kv8_stats[key] += 1
+        for lay, T1, _ in rows:
+            lay._commit(T1)
+    for i, step in enumerate(plan):
+        _count(step[1], "decode", B, which is KV8, i == 0)
     if head is not None:
         return out, logits
     return BaseModelOutputWithPast(last_hidden_state=base.norm(out), past_key_values=cache)
@@ -1612,7 +1260,6 @@ def _head_state(model, form: int) -> _HeadState:
     """The head's descriptor for `form`, built at the first head-route call and rebuilt when lm_head.weight's or the final norm
     weight's data_ptr() or _version changed (an optimiser step, load_state_dict, weight.mul_) or another form is asked for --
     as `_quant_state` has it for a layer."""
-    import ctypes as C
     w, norm = model.lm_head.weight, _stack_of(model).norm
     key = (w.data_ptr(), w._version, norm.weight.data_ptr(), norm.weight._version, float(norm.variance_epsilon), form)
     hs = model.__dict__.get("_u2_head")
@@ -1710,36 +1357,6 @@ def head_forward(model, input_ids, attention_mask, position_ids, past_key_values
     head_stats["head"] += 1
     head_stats["form_fallback"] += fell
     return CausalLMOutputWithPast(logits=logits, past_key_values=kw["past_key_values"])
-
-
-def _prefill_append_layer(cache, layer_idx: int, B: int, Hkv: int, S: int, d: int, like: torch.Tensor, kv8: bool = False):
-    """For a plain HF DynamicCache whose layer `layer_idx` is still empty: put an append-in-place layer there with room for S
-    positions (and as many again for the decode steps) and return it; None for every other cache (its `update` is used).
-    kv8 (the switch): exactly there a `Kv8Layer` is put instead (an empty one stays), and None is returned: the caller commits
-    through the layer's `update`, which quantises."""
-    layers = _plain_layers(cache)
-    if layers is None:
-        return None
-    cls = _append_layer_class()
-    if getattr(cache, "layer_class_to_replicate", None) is _DYN_LAYER:
-        while len(layers) <= layer_idx:
-            layers.append(_DYN_LAYER())
-    if layer_idx >= len(layers) or type(layers[layer_idx]) not in (_DYN_LAYER, cls, Kv8Layer if kv8 else cls) \
-            or layers[layer_idx].get_seq_length() != 0:
-        return None
-    if kv8:
-        if _CACHE_LAYER is not None and type(layers[layer_idx]) is not Kv8Layer:
-            layers[layer_idx] = Kv8Layer()
-        return None
-    try:
-        lay = cls()
-        proto = torch.empty((B, Hkv, 0, d), dtype=like.dtype, device=like.device)
-        lay.lazy_initialization(proto, proto)
-        lay._room(S, torch.empty((B, Hkv, 1, d), dtype=like.dtype, device=like.device))
-    except (TypeError, AttributeError):  # (another transformers version's layer protocol)
-        return None
-    layers[layer_idx] = lay
-    return lay
 
 
 def _mask_hook(module, args, kwargs):
